@@ -18,9 +18,13 @@ row-tile tables of the octree convolutions (ocnn's `octree2col` per call): `Octr
 runs at the top of every step.  For N > 1 the step ends with the RCCL all-gather of the (B_local,256)
 descriptors.  Weak scaling: each rank encodes its own contiguous slice of the global batch.
 
-What one default run times (same W-warm-up / K-step / barrier protocol for every leg, rank 0, N = 1):
+A plain run times the headline alone: set-up, W warm-ups, the K timed steps, the outputs of the last timed step written
+when `--dump-outputs DIR` is given (DIR/<name>.npy, float32: the descriptors, and for --train a fixed seeded sample of the
+parameter gradients), then the JSON line:
   value          boundary-faithful step, Linear layers as 3-term split-bf16 products with fp32 accumulation on the
                  hand-written MFMA GEMM (`--gemm x3`), window attention on fp16 (hi, lo) pairs
+
+`--full` adds everything else (same W-warm-up / K-step / barrier protocol for every leg, rank 0, N = 1):
   resident_plan  the same step with the plan / tap tables kept on the octree between steps (what a caller that
                  re-submits one octree sees; round 2's headline)
   matched_precision   the boundary-faithful step at the REFERENCE'S ARITHMETIC on hand-written kernels: every
@@ -36,12 +40,14 @@ What one default run times (same W-warm-up / K-step / barrier protocol for every
   unpinned_host  the headline step with the CPU affinity left alone, in a child process (the headline itself runs on its rank's
                  eighth of the host's logical CPUs: --pin-cores); every leg's `host_issue` = host time to queue the K steps vs
                  their wall time
-and then, outside any timed value: the `roofline` legs (HIP events per launch: `roofline` = the step's dominant kernel, the
-fused MLP launch; `roofline_window` the fp16 window kernel, `roofline_fused` for the
+and then, outside any timed value: the `kernels` table, the `roofline` legs (HIP events per launch: `roofline` = the step's
+dominant kernel, the fused MLP launch; `roofline_window` the fp16 window kernel, `roofline_fused` for the
 one-kernel LayerNorm -> qkv -> attention launch of the OctFormer stage, `roofline_ws` for the one with relay tokens of the
 finest pyramid level, `roofline_fp32` for the f32-MFMA window kernel of the matched-precision leg) and the `cpu_baseline`
 (the CPU oracle, a port of the reference forward, BASELINE.md section 3 protocol) whose descriptors are also the
-`parity` reference of the timed workload's GPU descriptors (BASELINE metric: "descriptor L2 vs ref").
+`parity` reference of the timed workload's GPU descriptors (BASELINE metric: "descriptor L2 vs ref"), `parity_reference`
+(the same descriptors against the reference model's stored output), the CPE's counter bound and, for N > 1, the
+all-gather timed alone (`allgather_ms`).  The `--no-*` switches below trim a `--full` run.
 """
 
 import argparse
@@ -98,6 +104,12 @@ def parse():
     ap.add_argument('--no-train-x3', action='store_true', help='A/B with --train: Linear layers as fp32 torch GEMMs')
     ap.add_argument('--x3-nt', type=int, default=None, help='A/B: non-temporal store bits of the hand-written GEMM (0..3)')
     ap.add_argument('--no-collective', action='store_true', help='A/B: skip the descriptor all-gather (N > 1 diagnostics)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, every other leg: resident plan, matched precision, e2e, roofline / kernel '
+                         'timings, the config-3 / config-5 / unpinned child processes, the CPU baseline and the parity blocks '
+                         '(off: the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)')
     ap.add_argument('--no-extras', action='store_true', help='only the headline timed region (no other legs)')
     ap.add_argument('--no-train-leg', action='store_true', help='skip the config-3 child process')
     ap.add_argument('--no-oxford-leg', action='store_true', help="skip the config-5 per-rank workload's child process")
@@ -334,6 +346,7 @@ def main():
     model = model_factory(params)
     syn.fill_synthetic_weights(model, 'init')
     model = model.to(dev).eval()
+    torch.manual_seed(0)                                # --train: the stochastic-depth draws repeat from run to run
     log('model ready')
 
     # this rank's contiguous slice of the global batch (ordered)
@@ -375,7 +388,8 @@ def main():
         if state['fresh_plan']:
             octree.drop_forward_caches()
         if args.train and args.multistaged:
-            multistaged_training_step(model, [batch], pos_mask, neg_mask, loss_fn, optim, n_total=n_tot, reducer=reducer)
+            state['stats'] = multistaged_training_step(model, [batch], pos_mask, neg_mask, loss_fn, optim, n_total=n_tot,
+                                                       reducer=reducer)
             return torch.ones(1, device=dev)
         if args.train:
             model.zero_grad(set_to_none=True)
@@ -384,7 +398,7 @@ def main():
             return y.detach()
         y = model(batch)['global']
         if collective:
-            all_gather_descriptors(y, args.batch * world, force=True)      # (B_total, 256) on every rank
+            state['gathered'] = all_gather_descriptors(y, args.batch * world, force=True)      # (B_total, 256) on every rank
         return y
 
     dev_clouds = [torch.from_numpy(c).to(dev) for c in clouds]             # e2e leg: points resident, octree not
@@ -421,13 +435,15 @@ def main():
         return {'value': round(args.batch * args.steps / dt, 2), 'unit': 'clouds/s',
                 'ms_per_step': round(dt / args.steps * 1e3, 3), 'steps': args.steps, 'warmup': args.warmup}
 
-    extras = world == 1 and not args.train and not args.no_extras
+    extras = world == 1 and not args.train and not args.no_extras and args.full
     resident_line = fp32_line = e2e_line = kern_iso = kern_all = iso_sizes = kern_iso32 = fused_roof = ws_roof = mlp_roof = None
     lib_line = x6_sizes = None
     with (torch.enable_grad() if args.train else torch.inference_mode()):
         # ---- the headline: W warm-ups, K timed steps, nothing instrumented inside the timed region
         elapsed = timed(step, args.steps, args.warmup, tag='value')
         log('timed region done: %.3f s for %d steps' % (elapsed, args.steps))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last['value'], state, model, args)
         if extras:
             state['fresh_plan'] = not state['fresh_plan']
             dt = timed(step, args.steps, args.warmup)
@@ -517,7 +533,7 @@ def main():
     allgather_ms = None
     if use_dist:
         per_rank, elapsed_max = rank_report(dist, elapsed, args.steps, dev)
-        if collective:
+        if collective and args.full:
             y = torch.zeros((args.batch, params.output_dim), device=dev)
             for _ in range(3):
                 all_gather_descriptors(y, args.batch * world, force=True)
@@ -620,7 +636,7 @@ def main():
             line['split_linear'] = fp32_line
         if e2e_line:
             line['e2e'] = e2e_line
-        cpe = cpe_l1_bound() if (args.config == 'wild-places' and not args.train) else None
+        cpe = cpe_l1_bound() if (args.full and args.config == 'wild-places' and not args.train) else None
         if cpe:
             others = dict(others or {})
             others['hfl_cpe_forward.bound'] = cpe
@@ -668,7 +684,7 @@ def main():
                                               'logical CPUs; the headline runs on %s)' % (os.cpu_count() or 0, args.host_affinity),
                                               keys=('host_issue',))
             log('unpinned leg:', line['unpinned_host'])
-        if world == 1 and not args.no_cpu_baseline and not args.train:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.train:
             line['cpu_baseline'], want = cpu_baseline(params, depth, args)
             line['gpu_over_cpu'] = round(line['value'] / line['cpu_baseline']['value'], 1)
             # descriptors of the LAST timed step of each leg against the oracle's on the same clouds and weights
@@ -682,8 +698,8 @@ def main():
         # reference model files run in the build container: oracle/gen_golden.py::WORKLOAD_CASES -> tests/golden/
         # model_wild_places_b32.npz; tests/test_gpu_model.py::test_full_size_workloads_match_reference_golden checks the same)
         gold = os.path.join(ROOT, 'tests', 'golden', 'model_wild_places_b32.npz')
-        if (world == 1 and not args.train and args.config == 'wild-places' and args.batch == 32 and args.points == 4096
-                and not args.points_max and os.path.exists(gold) and 'value' in last):
+        if (args.full and world == 1 and not args.train and args.config == 'wild-places' and args.batch == 32
+                and args.points == 4096 and not args.points_max and os.path.exists(gold) and 'value' in last):
             import numpy as np
             ref = np.load(gold)['descriptors']
             pr = {'reference': 'tests/golden/model_wild_places_b32.npz (reference model output, oracle/gen_golden.py)',
@@ -714,6 +730,50 @@ def bench_clouds(syn, params, args, rank):
                                       n_points_max=args.points_max, first_index=i)
         return clouds
     return syn.make_clouds(2, args.batch, args.points, params.coordinates, first_index=rank * args.batch)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+GRAD_SAMPLE = 1 << 22          # elements of the seeded gradient / parameter sample (16 MB in float32)
+
+
+def dump_outputs(out_dir, y, state, model, args):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files (at most DUMP_BUDGET_BYTES).
+    Forward: the descriptors (`global`; with the all-gather, also the gathered `global_all_ranks`).  --train: the
+    descriptors and a fixed, seeded sample of the parameter gradients flattened in named_parameters order (the whole
+    gradient is ~140 MB); --multistaged: the loss statistics and the same sample of the parameters after the optimiser
+    step."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if args.train and args.multistaged:
+        stats = state.get('stats') or {}
+        keys = sorted(k for k, v in stats.items() if isinstance(v, (int, float)) or torch.is_tensor(v) and v.numel() == 1)
+        arrays['loss_stats'] = np.array([float(stats[k]) for k in keys], dtype=np.float32)       # in key order
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+        arrays['param_sample'] = flat
+    else:
+        arrays['global'] = y
+        if 'gathered' in state:
+            arrays['global_all_ranks'] = state['gathered']
+        if args.train:
+            flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                              for _, p in model.named_parameters()])
+            arrays['grad_sample'] = flat
+    for name in ('param_sample', 'grad_sample'):
+        if name in arrays:
+            flat = arrays[name]
+            gen = torch.Generator().manual_seed(12345)
+            idx = torch.randint(0, flat.numel(), (min(GRAD_SAMPLE, flat.numel()),), generator=gen)
+            arrays[name] = flat[idx.to(flat.device)]
+    total = 0
+    for name, a in arrays.items():
+        a = (a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32))
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit('bench.py --dump-outputs: outputs exceed %d bytes' % DUMP_BUDGET_BYTES)
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    log('outputs of the last timed step written to %s: %s' % (out_dir, ', '.join(sorted(arrays))))
 
 
 def native_attention_timing(step, steps):

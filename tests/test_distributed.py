@@ -367,6 +367,36 @@ def test_bench_self_launch_reports_missing_gpus_from_the_children():
     assert 'need 2 GPUs on this node' in r.stderr, r.stderr[-800:]
 
 
+def test_bench_dump_outputs_are_float32_seeded_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's descriptors as DIR/global.npy, and for --train a fixed seeded sample of
+    the flattened parameter gradients -- float32, the same sample from run to run, at most 64 MB in all."""
+    import importlib.util
+    import types
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod', _BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    model = torch.nn.Sequential(torch.nn.Linear(2000, 2500), torch.nn.Linear(2500, 8))     # 5 M parameters
+    for i, p in enumerate(model.parameters()):
+        p.grad = torch.arange(p.numel(), dtype=torch.float32).reshape(p.shape) + i
+    y = np.random.default_rng(0).standard_normal((4, 256)).astype(np.float32)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        bench.dump_outputs(str(d), y, {}, model, types.SimpleNamespace(train=True, multistaged=False))
+        files = sorted(os.listdir(d))
+        assert files == ['global.npy', 'grad_sample.npy']
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        assert np.array_equal(arrs['global.npy'], y)
+        assert arrs['grad_sample.npy'].shape == (bench.GRAD_SAMPLE,)
+        runs.append(arrs['grad_sample.npy'])
+    assert np.array_equal(runs[0], runs[1])
+    flat = torch.cat([p.grad.reshape(-1) for p in model.parameters()]).numpy()
+    assert np.isin(runs[0], flat).all()
+
+
 def _rank_report_worker(rank, world, port, result_dir):
     import importlib.util
     os.environ['MASTER_ADDR'] = '127.0.0.1'

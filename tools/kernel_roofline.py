@@ -3,7 +3,7 @@
 Both inputs are written by tools/profile_serial.sh / tools/profile_round.sh (rocprofv3 --kernel-trace --stats, and the separate
 --pmc FETCH_SIZE / WRITE_SIZE passes corrected as MI355X_MICROARCH.md prescribes).  'frac' = bytes / time / 8 TB/s: how close
 each kernel group runs to the HBM roof with the bytes it ACTUALLY moved; the algorithmic-byte rooflines of the two attention
-kernels are in bench.py's JSON line (roofline, roofline_fused)."""
+kernels are in the JSON line of bench.py --full (roofline, roofline_fused)."""
 import collections
 import csv
 import json

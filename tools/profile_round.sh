@@ -2,7 +2,7 @@
 # One profiling pass of the default bench for profiles/: tools/profile_round.sh <tag>   (run on the GPU box)
 #  1. rocprofv3 --kernel-trace --stats    -> gpurun_out/<tag>_stats/   (+ summary table; 18 model steps: 2 warm-up + 16 timed)
 #  2. rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, kernel-trace only) -> <tag>_pmc_traffic.json
-#  3. un-profiled default bench line (with the CPU baseline)              -> <tag>_bench_default.json
+#  3. un-profiled bench line with every leg (--full, the CPU baseline included) -> <tag>_bench_default.json
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 tag=$1
@@ -18,5 +18,5 @@ done
 f=$(find $out/${tag}_pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1)
 w=$(find $out/${tag}_pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1)
 python tools/pmc_summary.py "$f" "$w" $out/${tag}_pmc_traffic.json > $out/${tag}_pmc_summary.txt
-python bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+python bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 tail -c 1500 $out/${tag}_bench_default.json

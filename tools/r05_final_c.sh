@@ -9,5 +9,5 @@ python -c "from hotformerloc_amd import _native; _native.load(); print('library 
 tools/cpe_counters.sh r05 > $out/r05_cpe_counters.log 2>&1
 python tools/stamp_sources.py hotformerloc_amd/csrc/dwconv.hip >> $out/r05_cpe_counters.txt
 python -m pytest tests -m gpu -x -q --durations=10 > $out/r05_gputest.log 2>&1; tail -16 $out/r05_gputest.log
-python bench.py > $out/r05_bench_default.json 2> $out/r05_bench_default.err
+python bench.py --full > $out/r05_bench_default.json 2> $out/r05_bench_default.err
 tail -c 600 $out/r05_bench_default.json

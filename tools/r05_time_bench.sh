@@ -1,7 +1,8 @@
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+out=${OUT:-bench_out}
+mkdir -p $out
 s=$(date +%s)
-python bench.py > gpurun_out/r05_bench_timed.json 2> gpurun_out/r05_bench_timed.err
+python bench.py --full > $out/r05_bench_timed.json 2> $out/r05_bench_timed.err
 e=$(date +%s)
-echo "default bench wall: $((e-s)) s" > gpurun_out/r05_bench_timed.txt
-grep -E "^\[bench" gpurun_out/r05_bench_timed.err | tail -40 >> gpurun_out/r05_bench_timed.txt
+echo "default bench wall: $((e-s)) s" > $out/r05_bench_timed.txt
+grep -E "^\[bench" $out/r05_bench_timed.err | tail -40 >> $out/r05_bench_timed.txt
