@@ -232,12 +232,6 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib = lib
-    # probe knobs from the environment (A/B runs of bench.py): HFL_VARIANTS="key=value,key=value" -> hfl_set_variant
-    for kv in os.environ.get('HFL_VARIANTS', '').split(','):
-        if '=' in kv:
-            k, v = kv.split('=', 1)
-            if lib.hfl_set_variant(k.strip().encode(), int(v)) != 0:
-                raise NativeLibraryError('HFL_VARIANTS: unknown knob %r' % k)
     return lib
 
 

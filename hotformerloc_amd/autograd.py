@@ -8,8 +8,6 @@ The reference gets all of this from PyTorch autograd over its materialised masks
 
 import ctypes
 
-import os
-
 import torch
 
 from . import _native, ops
@@ -164,27 +162,21 @@ class LiveTapConvFn(torch.autograd.Function):
         src, slot, edges = octree.sparse_taps(depth, kernel, stride)
         kdim, cin, cout = weights.shape
         x6 = _x6_taps_ok(cin, cout) and edges[-1] > 0 and data.dtype == torch.float32
-        grouped = not x6 and _grouped_ok(cin, cout) and edges[-1] > 0
         if x6:
             # one grouped launch at fp32-grade products (hfl_linear_x6_grouped_gather): the tile loader reads the pairs' input
             # rows itself, so the (pairs, Cin) matrix is neither written here nor kept for the backward (it is re-gathered there)
             npad = max(cout, 128)
-            part = ops.linear_x6_grouped_gather(data, src, _tap_blocks(weights, True, npad, x6=True),
+            part = ops.linear_x6_grouped_gather(data, src, _tap_blocks(weights, True, npad),
                                                 octree.tap_tiles(depth, kernel, stride, npad), cout)
             ctx.save_for_backward(data, weights)
         else:
             g = ops.octree_gather(data, src)
-            if grouped:            # one grouped split-precision launch over all taps (hfl_linear_x3_grouped)
-                npad = max(cout, 128)
-                part = ops.linear_x3_grouped(ops.split2(g), _tap_blocks(weights, True, npad),
-                                             octree.tap_tiles(depth, kernel, stride, npad), cout)
-            else:
-                part = torch.empty((g.shape[0], cout), dtype=torch.float32, device=data.device)
-                for k in range(kdim):
-                    if edges[k + 1] > edges[k]:
-                        torch.mm(g[edges[k]:edges[k + 1]], weights[k], out=part[edges[k]:edges[k + 1]])
+            part = torch.empty((g.shape[0], cout), dtype=torch.float32, device=data.device)
+            for k in range(kdim):
+                if edges[k + 1] > edges[k]:
+                    torch.mm(g[edges[k]:edges[k + 1]], weights[k], out=part[edges[k]:edges[k + 1]])
             ctx.save_for_backward(g, weights)
-        ctx.octree, ctx.key, ctx.n_src, ctx.grouped, ctx.x6 = octree, (depth, kernel, stride), data.shape[0], grouped, x6
+        ctx.octree, ctx.key, ctx.n_src, ctx.x6 = octree, (depth, kernel, stride), data.shape[0], x6
         return ops.slot_sum(part, slot) if _slot_sum_ok(part, slot) else ops.dwconv_forward_backward(part, _unit_taps(kdim, cout, data.device), slot)
 
     @staticmethod
@@ -216,12 +208,8 @@ class LiveTapConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if ctx.x6:
                 npad = max(cin, 128)
-                dg = ops.linear_x6_grouped_gather(dout, rowof, _tap_blocks(weights, False, npad, x6=True),
+                dg = ops.linear_x6_grouped_gather(dout, rowof, _tap_blocks(weights, False, npad),
                                                   ctx.octree.tap_tiles(*ctx.key, npad), cin)
-            elif ctx.grouped:
-                npad = max(cin, 128)
-                dg = ops.linear_x3_grouped(ops.split2(dpart), _tap_blocks(weights, False, npad),
-                                           ctx.octree.tap_tiles(*ctx.key, npad), cin)
             else:
                 dg = torch.empty_like(g)
                 for k in range(kdim):
@@ -237,34 +225,24 @@ def _slot_sum_ok(part, slot) -> bool:
     return part.shape[1] % 4 == 0 and part.shape[1] <= 1024 and slot.shape[1] <= 27 and slot.dtype == torch.int32
 
 
-def _grouped_ok(cin, cout) -> bool:
-    return (cin % 32 == 0 and cout % 32 == 0 and (cout % 128 == 0 or cout == 64) and (cin % 128 == 0 or cin == 64)
-            and _GROUPED_TAPS)
-
-
-# off by default on the TRAINING path: the grouped split-precision launch bought 0.6 % of the config-3 step, and the deepest
-# gradient of the loss chain (first stem convolution, amplified by the 1/tau = 100 of the listwise loss) moved from 8.5e-4 to
-# 2.2e-3 of the oracle chain with it; the fp32 per-tap GEMMs stay (HFL_GROUPED_TAPS_TRAIN=1 switches it on)
-_GROUPED_TAPS = __import__('os').environ.get('HFL_GROUPED_TAPS_TRAIN', '0') != '0'
-# what the training path runs instead: the same grouped launch at fp32-grade products (hfl_linear_x6_grouped_gather; its
-# error is below the fp32 library GEMM's, so the gradient bar is untouched); HFL_X6_TAPS_TRAIN=0 (with HFL_PROBES=1) goes
-# back to the 27 fp32 library GEMMs per convolution
-_X6_TAPS = not (__import__('os').environ.get('HFL_PROBES', '0') == '1'
-                and __import__('os').environ.get('HFL_X6_TAPS_TRAIN', '1') == '0')
+# The training path's live-tap convolutions run as ONE grouped launch at fp32-grade products (hfl_linear_x6_grouped_gather;
+# its error is below the fp32 library GEMM's, so the gradient bar is untouched) where the channel widths allow, else as the
+# fp32 per-tap GEMMs.  (The grouped split-precision launch bought 0.6 % of the config-3 step, but the deepest gradient of the
+# loss chain -- first stem convolution, amplified by the 1/tau = 100 of the listwise loss -- moved from 8.5e-4 to 2.2e-3 of
+# the oracle chain with it; that path has since been removed.)
 _TAP_BLOCK_CACHE = {}
 
 
 def _x6_taps_ok(cin, cout) -> bool:
-    return (cin % 32 == 0 and cout % 32 == 0 and (cout % 128 == 0 or cout == 64) and (cin % 128 == 0 or cin == 64)
-            and _X6_TAPS)
+    return cin % 32 == 0 and cout % 32 == 0 and (cout % 128 == 0 or cout == 64) and (cin % 128 == 0 or cin == 64)
 
 
-def _tap_blocks(weights, transposed: bool, npad: int, x6: bool = False):
-    """split2 layout (x6: the three bf16 planes, `ops.x6_pack`) of the per-tap weight blocks of an octree convolution, every
-    block padded to `npad` rows: transposed = W[k]^T (Cout x Cin) for the forward product, else W[k] (Cin x Cout) for the
-    input gradient; rebuilt when the optimizer updates the parameter."""
+def _tap_blocks(weights, transposed: bool, npad: int):
+    """The three bf16 planes (`ops.x6_pack`) of the per-tap weight blocks of an octree convolution, every block padded to
+    `npad` rows: transposed = W[k]^T (Cout x Cin) for the forward product, else W[k] (Cin x Cout) for the input gradient;
+    rebuilt when the optimizer updates the parameter."""
     import weakref
-    key = (id(weights), transposed, npad, x6)
+    key = (id(weights), transposed, npad)
     hit = _TAP_BLOCK_CACHE.get(key)
     if hit is None or hit[0]() is not weights or hit[1] != weights._version or hit[3] != weights.data_ptr():
         w = weights.detach()
@@ -275,8 +253,7 @@ def _tap_blocks(weights, transposed: bool, npad: int, x6: bool = False):
         if len(_TAP_BLOCK_CACHE) > 256:
             _TAP_BLOCK_CACHE.clear()
         stacked = blocks.reshape(kdim * npad, kk).contiguous()
-        hit = (weakref.ref(weights), weights._version, ops.x6_pack(stacked) if x6 else ops.split2(stacked),
-               weights.data_ptr())
+        hit = (weakref.ref(weights), weights._version, ops.x6_pack(stacked), weights.data_ptr())
         _TAP_BLOCK_CACHE[key] = hit
     return hit[2]
 
@@ -651,9 +628,6 @@ def mlp_x3(h, w1, b1, w2, b2):
 
 
 # ------------------------------------------------ conditional position encoding, training forward as one launch
-_CPE_BWD_GATHER = (os.environ.get('HFL_TRAIN_CPE_BWD_GATHER', '1') if os.environ.get('HFL_PROBES', '0') == '1' else '1') != '0'   # probe knob
-
-
 class CpeFn(torch.autograd.Function):
     """[x +] LayerNorm(dwconv(x)) (CPE.forward and its callers' residual: models/layers/octformer_layers.py:138-142,
     models/octformer_backbone.py:258) with the inference path's fused launch as the forward -- it additionally writes the
@@ -679,7 +653,7 @@ class CpeFn(torch.autograd.Function):
         dout = dout.contiguous()
         dconv, dg, dbeta = ops.layer_norm_bwd(dout, conv, gamma, ctx.eps)
         dx = None
-        if need[0] and _CPE_BWD_GATHER and x.shape[1] in (32, 64, 128, 256) and neigh.dtype == torch.int32:
+        if need[0] and x.shape[1] in (32, 64, 128, 256) and neigh.dtype == torch.int32:
             # the same gather as the forward, over the inverse table, the skip gradient added in its epilogue
             dx = ops.dwconv_add(dconv, weights, _inverse_of(neigh), dout if ctx.residual else None)
         elif need[0]:

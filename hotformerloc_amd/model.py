@@ -39,19 +39,6 @@ from .plan import WindowPlan
 
 _FORCE_TRAIN_PATH = False
 
-# Configuration surface.  PRODUCT switches (read from the environment at import, each selects a tested mode):
-#   HFL_GEMM = x3 | x6 | fp32 | bf16x3     Linear arithmetic (set_gemm_mode): split precision (default), matched precision, ...
-#   HFL_CHECKPOINT = auto | always | never activation checkpointing policy of the training path (set_checkpoint_policy)
-#   HFL_CHECKPOINT_FREE_FRACTION           its memory threshold
-# Everything else below is a PROBE knob of the A/B scripts under tools/ (profiles/*_ab_*.log): the schedule and fusion choices
-# those measurements settled.  They keep their measured defaults unless HFL_PROBES=1 is set in the environment.
-_PROBES = os.environ.get('HFL_PROBES', '0') == '1'
-
-
-def _knob(name: str, default: str) -> str:
-    return os.environ.get(name, default) if _PROBES else default
-
-
 
 def _grad_path(x=None) -> bool:
     """True when autograd must see the op (training / fine-tuning): route through the
@@ -76,7 +63,7 @@ def _ln(x, m: nn.LayerNorm):
     """LayerNorm over channels: HIP kernel in inference, torch (autograd) when grads are needed."""
     if x.is_cuda and not _grad_path(x) and x.shape[-1] in ops._LN_CHANNELS:
         return ops.layer_norm(x, m.weight, m.bias, m.eps)
-    if x.is_cuda and _TRAIN_LN and x.numel() > 0 and x.shape[-1] in ops._LN_CHANNELS and x.dtype == torch.float32:
+    if x.is_cuda and x.numel() > 0 and x.shape[-1] in ops._LN_CHANNELS and x.dtype == torch.float32:
         return ag.layer_norm(x, m.weight, m.bias, m.eps)            # HIP forward + backward
     return F.layer_norm(x, m.normalized_shape, m.weight, m.bias, m.eps)
 
@@ -97,36 +84,29 @@ def _add_ln(x, y, m: nn.LayerNorm):
 # six plane products, fp32 accumulation: as accurate as an fp32 GEMM), fp32 LayerNorm / softmax / GELU, window attention
 # on the fp32 matrix cores -- the reference's own arithmetic (models/layers/octformer_layers.py:53-59,
 # models/octformer_backbone.py:52-93) without a library GEMM in the transformer blocks.
-_GEMM_MODE = os.environ.get('HFL_GEMM', 'x3')
-_PYRAMID_STREAMS = _knob('HFL_PYRAMID_STREAMS', '1') != '0'
-_SIDE_STREAM_MAX_ROWS = int(_knob('HFL_SIDE_STREAM_MAX_ROWS', '32768'))
+_GEMM_MODE = os.environ.get('HFL_GEMM', 'x3')   # product switch (set_gemm_mode): x3 | x6 | fp32 | bf16x3
+_SIDE_STREAM_MAX_ROWS = 32768                    # pyramid depths up to this many rows run on side streams
+
+# Schedule and fusion seams: module attributes (no environment read) switched only by the tests and bench.py, each to compare a
+# fused launch or a schedule with the plain form it replaces.
+_PYRAMID_STREAMS = True        # pyramid depths on separate HIP streams (set_pyramid_streams)
+_SERIAL_STREAMS = False        # ... their launches in the same order on one stream (set_pyramid_streams('serial'))
 # training-path Linear layers on split-bf16 GEMMs (autograd.LinearSplitFn).  Off by default: parity-tested, but
 # at 191 ms/step (B=32, Wild-Places) still slower than the fp32 hipBLASLt route (145 ms) because the operand
 # splits of the backward are torch element-wise passes; needs fused split kernels to pay off.
-_TRAIN_SPLIT = _knob('HFL_TRAIN_SPLIT', '0') != '0'
+_TRAIN_SPLIT = False
 # training-path Linear layers on the hand-written split GEMMs (autograd.LinearX3Fn: forward + dx on hfl_linear_x3, dW / db
 # on hfl_wgrad_x3)
-_TRAIN_X3 = _knob('HFL_TRAIN_X3', '1') != '0'
-_ATTN_F16 = _knob('HFL_ATTN_F16', '1') != '0'   # fp16 (hi, lo) MFMA window attention where eligible (A/B switch)
-_TRAIN_LN = _knob('HFL_TRAIN_LN', '1') != '0'    # training-path LayerNorm: HIP forward + backward kernels
-_TRAIN_MLP = _knob('HFL_TRAIN_MLP', '1') != '0'          # fused fc1 -> GELU -> fc2 autograd Function
-_GROUPED_TAPS = _knob('HFL_GROUPED_TAPS', '1') != '0'     # live-tap convolutions: one grouped x3 launch for all taps
-_SPARSE_CONV = _knob('HFL_SPARSE_CONV', '1') != '0'    # large 3x3x3 convs over live taps only
-_GATHER_IN_GEMM = _knob('HFL_GATHER_IN_GEMM', '1') != '0'   # grouped tap GEMM gathers its A rows itself
-_LT_EPILOGUE = _knob('HFL_LT_EPILOGUE', '1') != '0'      # proj / fc2: bias + residual in the GEMM launch
-_EARLY_PHASE = _knob('HFL_EARLY_PHASE', '1') != '0'      # token-row half of a block issued before / beside RTSA
-_DROP_POOL = _knob('HFL_DROP_POOL', '1') != '0'          # stochastic-depth draws of a forward in one batch of launches
+_TRAIN_X3 = True
+_TRAIN_MLP = True              # fused fc1 -> GELU -> fc2 autograd Function
+_SPARSE_CONV = True            # large 3x3x3 convs over live taps only
+_EARLY_PHASE = True            # token-row half of a block issued before / beside RTSA
 # LN1 -> qkv -> window attention of a relay-token block's token rows as one launch (csrc/attn_ws.hip) from this many token rows
-_RTSA_SEGMENTS = _knob('HFL_RTSA_SEGMENTS', '1') != '0'  # RTSA reads the levels' relay rows in place (no torch.cat)
-_TRAIN_CPE_FUSED = _knob('HFL_TRAIN_CPE_FUSED', '1') != '0'  # training CPE forward as the fused launch (autograd.CpeFn)
-_CPE_FIRST = _knob('HFL_CPE_FIRST', '0') != '0'       # plain schedule: the finest level's CPE before the relay-token block (same stream)
-_TRAIN_CPE_BUFFER = _knob('HFL_TRAIN_CPE_BUFFER', '1') != '0'     # probe: 0 = slices + torch.cat around the CPE of a block
-_RELAY_IN_PLACE = _knob('HFL_RELAY_IN_PLACE', '1') != '0'  # blocks read RTSA's relay rows in place (no copy launch)
-_ATTN_WS = _knob('HFL_ATTN_WS', '1') != '0'
-_ATTN_WS_MIN_ROWS = int(_knob('HFL_ATTN_WS_MIN_ROWS', '40000'))
-_ATTN_WS_EARLY = _knob('HFL_ATTN_WS_EARLY', '0') != '0'   # keep the early-phase schedule beside it (A/B, tests)
-_MERGED_ATTN = _knob('HFL_MERGED_ATTN', '1') != '0'      # window attention of an iteration's levels as one launch
-_MAIN_HI = _knob('HFL_MAIN_HI', '0') != '0'             # probe: the inference forward on a high-priority stream
+_ATTN_WS = True
+_ATTN_WS_MIN_ROWS = 40000
+_ATTN_WS_EARLY = False         # keep the early-phase schedule beside it
+_MERGED_ATTN = True            # window attention of an iteration's levels as one launch
+_NATIVE_BLOCK = True           # inference blocks as one native call (hfl_block_forward_x3)
 
 
 def set_train_split(enabled: bool):
@@ -139,15 +119,6 @@ def set_train_x3(enabled: bool):
     """Training-path Linear layers through `autograd.LinearX3Fn` (default on in GEMM mode 'x3')."""
     global _TRAIN_X3
     _TRAIN_X3 = bool(enabled)
-
-
-def set_attention_f16(enabled: bool):
-    """Window attention on the fp16 (hi, lo) MFMA kernel (qkv written as its operands by the projection GEMM)."""
-    global _ATTN_F16
-    _ATTN_F16 = bool(enabled)
-
-
-_SERIAL_STREAMS = False
 
 
 def set_pyramid_streams(enabled):
@@ -228,8 +199,7 @@ def _block_tail_x6(x, attn_out, proj: nn.Linear, norm2: nn.LayerNorm, mlp: 'MLP'
 # that the three-launch form is as fast ALONE.  In the step the coarse pyramid levels' chains are launch-bound: with them on the
 # fused launches too -- hidden / feature dimension split over the chip -- three alternating runs gave 2952-2975 clouds/s against
 # 2914-2947, profiles/r05_g_ab.log.)
-_MLP_FUSED = _knob('HFL_MLP_FUSED', '1') != '0'
-_MLP_FUSED_MIN_ROWS = int(_knob('HFL_MLP_FUSED_MIN_ROWS', '1000'))
+_MLP_FUSED_MIN_ROWS = 1000
 
 
 def _mlp_pack(mlp: 'MLP', rows: int):
@@ -237,7 +207,7 @@ def _mlp_pack(mlp: 'MLP', rows: int):
     missing biases).  Cached per (fc1, fc2) parameter pair like `_w2`."""
     f1, f2 = mlp.fc1, mlp.fc2
     c = f1.in_features
-    if not (_MLP_FUSED and rows >= _MLP_FUSED_MIN_ROWS and c in (128, 256) and f1.out_features == 4 * c
+    if not (rows >= _MLP_FUSED_MIN_ROWS and c in (128, 256) and f1.out_features == 4 * c
             and f2.in_features == 4 * c and f2.out_features == c and f1.bias is not None and f2.bias is not None):
         return None
     w1, w2 = f1.weight, f2.weight
@@ -255,39 +225,16 @@ def _mlp_pack(mlp: 'MLP', rows: int):
 # LN1 -> qkv of the token rows as ONE launch (csrc/qkv_fused.hip) from 24 576 rows on (C = 128, 118 096 rows: 71 vs 96 us for
 # LayerNorm + qkv GEMM; C = 256, 65 536 rows: 95 vs 114-122 us).  Round 3 skipped C = 256 shapes whose last round of 32 768 rows
 # was less than half full (66 775 rows, 2.04 rounds: three passes, 153 vs 127 us); since the left-over rows are computed with
-# the output features split over the workgroups (round 4) that shape takes 101 us and the restriction is gone
-# (HFL_QKV_FUSED_MIN_FILL restores it).
-_QKV_FUSED = _knob('HFL_QKV_FUSED', '1') != '0'
-_QKV_FUSED_MIN_ROWS = int(_knob('HFL_QKV_FUSED_MIN_ROWS', '1000'))
-_RTSA_MLP_FUSED = _knob('HFL_RTSA_MLP_FUSED', '1') != '0'
-# relay-token block: LN1 -> qkv as ONE launch (csrc/qkv_fused.hip, output features split over the chip for the ~2 k rows) and
-# the ragged attention reading its fp16 (hi, lo) rows and writing attention.proj's split2 operand itself
-# (hfl_relay_attention_f16_fwd): LayerNorm, qkv GEMM, memset, attention, split2 -> two launches.  The block is a chain of tiny
-# launches on the cycle every H-OSA iteration waits for.
-_RTSA_SLIM = _knob('HFL_RTSA_SLIM', '1') != '0'
-# LN1 -> qkv -> window attention of the blocks without relay tokens (OctFormer stage) as one launch (csrc/attn_fused.hip)
-_ATTN_FUSED = _knob('HFL_ATTN_FUSED', '1') != '0'
-# attentional pooling of the head as one launch per level (csrc/attn_pool.hip) instead of GEMM + segment softmax + two
-# padding copies + batched GEMM
-_ATTN_POOL = _knob('HFL_ATTN_POOL', '1') != '0'
-# join every pyramid stream at the end of every H-OSA iteration (the schedule of rounds 2-3); 0: only the true dependencies
-_ITER_JOIN = _knob('HFL_ITER_JOIN', '0') != '0'
-_PLAN_LATE = _knob('HFL_PLAN_LATE', '1') != '0'           # window plan built after the stem has been issued
-# relay-token self-attention on a stream of its own (1) or on the finest level's, behind that level's CPE / LN1 / qkv (0)
-_RTSA_STREAM = _knob('HFL_RTSA_STREAM', '1') != '0'
-_QKV_FUSED_MIN_FILL = float(_knob('HFL_QKV_FUSED_MIN_FILL', '0.0'))
+# the output features split over the workgroups (round 4) that shape takes 101 us and the restriction is gone.
+_QKV_FUSED_MIN_ROWS = 1000
 
 
 def _qkv_pack(att: 'OctreeAttention', rows: int):
     """Weight image of the fused LN1 -> qkv launch for this block, or None when the launch does not apply / does not pay."""
     lin = att.qkv
     c = lin.in_features
-    if not (_QKV_FUSED and rows >= _QKV_FUSED_MIN_ROWS and c in (128, 256) and lin.out_features == 3 * c and lin.bias is not None):
+    if not (rows >= _QKV_FUSED_MIN_ROWS and c in (128, 256) and lin.out_features == 3 * c and lin.bias is not None):
         return None
-    if c == 256:
-        fill = (rows % 32768) / 32768.0
-        if 0.0 < fill < _QKV_FUSED_MIN_FILL:
-            return None
     w = lin.weight
     key = ('qkvpack', id(w))
     hit = _W3_CACHE.get(key)
@@ -345,32 +292,16 @@ class SplitLinear(nn.Linear):
         return F.linear(x, self.weight, self.bias)
 
 
-_TAP_STREAMS = int(_knob('HFL_TAP_STREAMS', '1'))       # >1: per-tap GEMMs on a stream pool (measured neutral)
-_TAP_POOLS = {}
-
-
-def _tap_stream_pool(device):
-    key = (device.type, device.index)
-    if key not in _TAP_POOLS:
-        _TAP_POOLS[key] = [torch.cuda.Stream(device=device) for _ in range(_TAP_STREAMS)]
-    return _TAP_POOLS[key]
-
-
 def _block_tail_split(x, attn_out3, attn: 'OctreeAttention', norm2: nn.LayerNorm, mlp: 'MLP'):
-    """proj -> +residual -> LN2 -> fc1 -> GELU -> fc2 -> +residual with every bias folded into
-    the element-wise kernel that follows its GEMM."""
+    """proj -> +residual -> LN2 -> fc1 -> GELU -> fc2 -> +residual: bias + residual in the proj / fc2 GEMM launches, fc1's
+    bias in the GELU pass that follows its GEMM."""
     if _GEMM_MODE == 'x3':
         return _block_tail_x3(x, attn_out3, attn, norm2, mlp)
-    if _LT_EPILOGUE:
-        # bias + residual ride in the GEMM launch (hfl_gemm_bf16): no pass over the residual stream
-        x = ops.gemm_bf16(attn_out3, _w3(attn.proj), bias=attn.proj.bias, residual=x)
-        h3 = ops.layer_norm_split3(x, norm2.weight, norm2.bias, norm2.eps)
-        g3 = ops.bias_gelu_split3(ops.split_mm(h3, _w3(mlp.fc1)), mlp.fc1.bias)
-        return ops.gemm_bf16(g3, _w3(mlp.fc2), bias=mlp.fc2.bias, residual=x)
-    p = ops.split_mm(attn_out3, _w3(attn.proj))
-    x, h3 = ops.add_layer_norm_split3(x, p, norm2.weight, norm2.bias, norm2.eps, add_bias=attn.proj.bias)
+    # bias + residual ride in the GEMM launch (hfl_gemm_bf16): no pass over the residual stream
+    x = ops.gemm_bf16(attn_out3, _w3(attn.proj), bias=attn.proj.bias, residual=x)
+    h3 = ops.layer_norm_split3(x, norm2.weight, norm2.bias, norm2.eps)
     g3 = ops.bias_gelu_split3(ops.split_mm(h3, _w3(mlp.fc1)), mlp.fc1.bias)
-    return ops.add_bias(x, ops.split_mm(g3, _w3(mlp.fc2)), mlp.fc2.bias)
+    return ops.gemm_bf16(g3, _w3(mlp.fc2), bias=mlp.fc2.bias, residual=x)
 
 
 # Activation checkpointing policy.  `grad_checkpoint = True` in the reference's configs buys memory with a second forward of
@@ -547,7 +478,7 @@ class OctreeConv(nn.Module):
         """Inference: does forward() run the grouped split-precision GEMM over the live taps, i.e. can it take the split2
         form of its input (rows, 2 Cin) bf16 instead of fp32 rows?"""
         return (_SPARSE_CONV and (self.kernel, self.stride) in (('333', 1), ('222', 2)) and self.in_channels >= 32
-                and _GROUPED_TAPS and _GEMM_MODE == 'x3' and self.in_channels % 32 == 0
+                and _GEMM_MODE == 'x3' and self.in_channels % 32 == 0
                 and (self.out_channels % 128 == 0 or self.out_channels == 64) and not _grad_path())
 
     def forward(self, data: torch.Tensor, octree, depth: int):
@@ -578,14 +509,14 @@ class OctreeConv(nn.Module):
         then every output row sums its own partial products through the slot table (the depth-wise conv kernel
         with unit weights: no atomics, fixed summation order)."""
         src, slot, edges = octree.sparse_taps(depth, self.kernel, self.stride)
-        if (_GROUPED_TAPS and _GEMM_MODE == 'x3' and self.in_channels % 32 == 0
+        if (_GEMM_MODE == 'x3' and self.in_channels % 32 == 0
                 and (self.out_channels % 128 == 0 or self.out_channels == 64) and edges[-1] > 0):
             # ONE launch of the split-precision GEMM over all taps: the pairs are gathered from the split2 form of the input
             # (a split2 row is Cin 4-byte cells, so the same gather kernel moves it), row tiles never straddle a tap and
             # carry the offset of their tap's weight block
             npad = max(self.out_channels, 128)
             d2 = data if data.dtype == torch.bfloat16 else ops.split2(data)
-            if _GATHER_IN_GEMM and d2.shape[0] * self.in_channels * 4 < (1 << 32):
+            if d2.shape[0] * self.in_channels * 4 < (1 << 32):
                 # the GEMM's tile loader fetches the pairs' input rows itself: no (pairs, Cin) matrix in memory
                 part = ops.linear_x3_grouped_gather(d2, src, self._tap_weights_split2(npad),
                                                     octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
@@ -594,7 +525,7 @@ class OctreeConv(nn.Module):
                 part = ops.linear_x3_grouped(gs, self._tap_weights_split2(npad),
                                              octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
             return self._slot_sum(part, slot)
-        if (_GEMM_MODE == 'x6' and _GROUPED_TAPS and not _grad_path() and data.dtype == torch.float32 and edges[-1] > 0
+        if (_GEMM_MODE == 'x6' and not _grad_path() and data.dtype == torch.float32 and edges[-1] > 0
                 and self.in_channels % 32 == 0 and (self.out_channels % 128 == 0 or self.out_channels == 64)):
             # matched precision: the same grouped launch on hfl_linear_x6 (fp32-grade products; the tile loader gathers the pairs'
             # input rows from the f32 rows themselves)
@@ -605,21 +536,8 @@ class OctreeConv(nn.Module):
         g = ops.octree_gather(data, src)                                  # (P, Cin)
         part = torch.empty((g.shape[0], self.out_channels), dtype=torch.float32, device=data.device)
         w = self.weights
-        live = [k for k in range(self.kdim) if edges[k + 1] > edges[k]]
-        if _TAP_STREAMS > 1 and len(live) > 2:
-            # the per-tap GEMMs are small (thousands of rows each) and independent: deal them over a few HIP streams so
-            # that they overlap instead of running one 10-us launch after another
-            main = torch.cuda.current_stream()
-            pool = _tap_stream_pool(data.device)
-            for st in pool:
-                st.wait_stream(main)
-            for i, k in enumerate(live):
-                with torch.cuda.stream(pool[i % len(pool)]):
-                    torch.mm(g[edges[k]:edges[k + 1]], w[k], out=part[edges[k]:edges[k + 1]])
-            for st in pool:
-                main.wait_stream(st)
-        else:
-            for k in live:
+        for k in range(self.kdim):
+            if edges[k + 1] > edges[k]:
                 torch.mm(g[edges[k]:edges[k + 1]], w[k], out=part[edges[k]:edges[k + 1]])
         return self._slot_sum(part, slot)
 
@@ -766,7 +684,7 @@ def _mlp_branch(x, norm: nn.LayerNorm, mlp: 'MLP', row_scale=None):
     """x + mlp(LN(x)) on the training path: one fused autograd Function when the shapes allow (LayerNorm writes the GEMM
     operand, GELU and the residual ride in the GEMM epilogues, the skip gradient joins inside the LayerNorm backward)."""
     f1, f2 = mlp.fc1, mlp.fc2
-    if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and _TRAIN_LN and x.is_cuda and x.numel() > 0
+    if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and x.is_cuda and x.numel() > 0
             and x.dtype == torch.float32 and x.shape[-1] in ops._LN_CHANNELS and f1.bias is not None and f2.bias is not None
             and ag.linear_x3_ok(f1.in_features, f1.out_features) and ag.linear_x3_ok(f2.in_features, f2.out_features)):
         return ag.ln_mlp_residual_x3(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
@@ -798,7 +716,7 @@ class CPE(nn.Module):
                 out.copy_(y)
                 return out
             return y
-        if (_TRAIN_CPE_FUSED and _grad_path(data) and data.shape[1] in (32, 64, 128, 256) and data.is_cuda
+        if (_grad_path(data) and data.shape[1] in (32, 64, 128, 256) and data.is_cuda
                 and data.dtype == torch.float32 and out is None):
             # training: the fused launch as the forward (it also writes the convolution's output for the backward)
             return ag.cpe(data, self.conv.weights, self.norm.weight, self.norm.bias, plan.neigh(depth), residual,
@@ -859,7 +777,7 @@ class OctreeAttention(nn.Module):
     def residual_branch(self, x, norm1: nn.LayerNorm, plan: WindowPlan, depth: int, row_scale=None):
         """x + attention(LN(x)) on the training path: one fused autograd Function when the shapes allow."""
         C = self.dim
-        if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and _TRAIN_LN and x.is_cuda and x.numel() > 0
+        if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and x.is_cuda and x.numel() > 0
                 and x.dtype == torch.float32 and C in ops._LN_CHANNELS and ag.linear_x3_ok(C, 3 * C)
                 and ag.linear_x3_ok(C, C) and self.proj.bias is not None):
             nt = plan.n_tokens[depth]
@@ -875,8 +793,8 @@ class OctreeAttention(nn.Module):
     def forward_split(self, x, norm1: nn.LayerNorm, plan: WindowPlan, depth: int):
         """LN1 -> qkv -> attention, split-precision path; returns the bf16 operand of `proj`."""
         if _GEMM_MODE == 'x3':         # qkv bias folded into the GEMM epilogue, attention writes split2 rows
-            f16 = _ATTN_F16 and ops.window_attention_f16_ok(x.shape[0], self.patch_size, self.dilation,
-                                                            self.rt_per_window, self.num_heads, depth)
+            f16 = ops.window_attention_f16_ok(x.shape[0], self.patch_size, self.dilation,
+                                              self.rt_per_window, self.num_heads, depth)
             qs = 16 ** -0.5 * 1.4426950408889634
             nt = plan.n_tokens[depth]
             qpack = _qkv_pack(self, nt) if (f16 and x.dtype == torch.float32 and x.is_contiguous()) else None
@@ -914,9 +832,6 @@ def _init_layer_scale(block, dim, layer_scale):
         block.gamma2 = nn.Parameter(layer_scale * torch.ones(dim))
     else:
         block.gamma1 = block.gamma2 = 1
-
-
-_NATIVE_BLOCK = _knob('HFL_NATIVE_BLOCK', '1') != '0'     # inference blocks as one native call (hfl_block_forward_x3)
 
 
 _F16_OK_CACHE = {}
@@ -978,7 +893,7 @@ def _native_block_call(block, x_in, plan: WindowPlan, depth: int):
     work differs."""
     att = block.attention
     C = att.dim
-    if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _ATTN_F16 and _split_path(x_in) and ops.KernelTimer.active is None
+    if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _split_path(x_in) and ops.KernelTimer.active is None
             and not block.use_layer_scale and not _drops(block) and not block.cpe.xcpe and C % 128 == 0
             and x_in.dtype == torch.float32 and x_in.is_contiguous()):
         return None
@@ -999,7 +914,8 @@ def _native_block_call(block, x_in, plan: WindowPlan, depth: int):
     mlp = block.mlp
     qpack = _qkv_pack(att, nt)
     w.qkv_pack = None if qpack is None else qpack.data_ptr()
-    w.fuse_attention = (1 if _ATTN_FUSED else 0) | (0 if _RELAY_IN_PLACE else 4)
+    # LN1 -> qkv -> window attention of the blocks without relay tokens (OctFormer stage) as one launch (csrc/attn_fused.hip)
+    w.fuse_attention = 1
     tables3 = None
     if qpack is not None and _attn_ws_wanted(att, rows, nt, plan.n_windows[depth], depth):
         tables3 = ops.rpe_expand(table, att.num_heads, bnd, depth, 2)
@@ -1127,7 +1043,7 @@ class HOTFormerBlock(nn.Module):
         nt = plan.n_tokens[depth]
         if _grad_path(buf):
             c = self.cpe
-            if (not c.xcpe and _TRAIN_CPE_FUSED and _TRAIN_CPE_BUFFER and buf.shape[1] in (32, 64, 128, 256) and buf.is_cuda
+            if (not c.xcpe and buf.shape[1] in (32, 64, 128, 256) and buf.is_cuda
                     and buf.dtype == torch.float32 and nt > 0):
                 # the CPE launch writes the token rows of the new [tokens | relay rows] buffer (no slices, no concatenation)
                 buf = ag.cpe_buffer(buf, relay, c.conv.weights, c.norm.weight, c.norm.bias, plan.neigh(depth), nt, c.norm.eps)
@@ -1210,9 +1126,9 @@ class RelayTokenTransformerBlock(nn.Module):
             # (the MLP branch as the fused launch with the hidden dimension split over the chip: 27 us against 48 us for the
             # three launches alone, and inside the step the relay tokens' fc2 -- K = 1024 over 28 workgroups -- took 120 us:
             # 2361 -> 2417 clouds/s, three alternating runs each)
-            mpack = _mlp_pack(mlp, _MLP_FUSED_MIN_ROWS) if (_RTSA_MLP_FUSED and att.dim in (128, 256)) else None
-            # (LN1 -> qkv as one launch and the attention writing proj's operand: six launches -> three, see _RTSA_SLIM)
-            qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS) if _RTSA_SLIM else None
+            mpack = _mlp_pack(mlp, _MLP_FUSED_MIN_ROWS)
+            # (LN1 -> qkv as one launch and the attention writing proj's operand: six launches -> three, see forward)
+            qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS)
             keep = (_w2(att.qkv), _w2(att.proj), _w2(mlp.fc1), _w2(mlp.fc2), mpack, qpack)
             w = RelayBlockWeights(channels=att.dim, n_heads=att.num_heads, eps=self.norm1.eps,
                                   mlp_pack=None if mpack is None else mpack.data_ptr(),
@@ -1230,7 +1146,7 @@ class RelayTokenTransformerBlock(nn.Module):
         """forward(torch.cat(parts)) -- without the concatenation launch when the native call can read the rows where they are
         (hfl_relay_block_io.x_segments: the fused LN1 -> qkv launch and proj's residual take a row-segment table)."""
         p0 = parts[0]
-        if (_RTSA_SEGMENTS and len(parts) <= 4 and _GEMM_MODE == 'x3' and _split_path(p0) and not self.use_layer_scale
+        if (len(parts) <= 4 and _GEMM_MODE == 'x3' and _split_path(p0) and not self.use_layer_scale
                 and not _drops(self) and _NATIVE_BLOCK and ops.KernelTimer.active is None
                 and all(p.dtype == torch.float32 and p.is_contiguous() and p.shape[0] > 0 for p in parts)):
             static = self._native_static(p0.device)
@@ -1247,7 +1163,11 @@ class RelayTokenTransformerBlock(nn.Module):
                     return ops.relay_block_forward_x3(static[0], static[1], rt, plan.seq_rows, plan.seq_off, plan.B,
                                                       plan.max_seq_len, plan.orphan_rows)
             att = self.rt_attention
-            qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS) if _RTSA_SLIM else None
+            # LN1 -> qkv as ONE launch (csrc/qkv_fused.hip, output features split over the chip for the ~2 k rows) and the
+            # ragged attention reading its fp16 (hi, lo) rows and writing attention.proj's split2 operand itself
+            # (hfl_relay_attention_f16_fwd): LayerNorm, qkv GEMM, memset, attention, split2 -> two launches.  The block is a
+            # chain of tiny launches on the cycle every H-OSA iteration waits for.
+            qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS)
             if qpack is not None:
                 qkv = ops.ln_qkv_fused(rt, self.norm1.weight, self.norm1.bias, self.norm1.eps, qpack, att.qkv.bias,
                                        0.25 * 1.4426950408889634)
@@ -1257,7 +1177,7 @@ class RelayTokenTransformerBlock(nn.Module):
                 a2 = ops.layer_norm_split2(rt, self.norm1.weight, self.norm1.bias, self.norm1.eps)
                 qkv = ops.linear_x3(a2, _w2(att.qkv), bias=att.qkv.bias)
                 o2 = ops.split2(ops.relay_attention(qkv, plan.seq_rows, plan.seq_off, plan.B, att.num_heads, plan.max_seq_len))
-            return _block_tail_x3(rt, o2, att, self.norm2, self.mlp, fused_any_rows=_RTSA_MLP_FUSED and att.dim in (128, 256))
+            return _block_tail_x3(rt, o2, att, self.norm2, self.mlp, fused_any_rows=True)
         if self.use_layer_scale or (self.training and self.drop_path.drop_prob > 0.0):
             bid = plan.relay_cloud()
             rt = rt + self.drop_path(self.gamma1 * self.rt_attention(_ln(rt, self.norm1), plan), bid, plan.B)
@@ -1431,7 +1351,7 @@ class HOTFormerStage(nn.Module):
         blk = self.hosa_blocks[0][0]
         att = blk.attention
         nt = plan.n_tokens[depth]
-        if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _ATTN_F16 and _split_path(buf) and ops.KernelTimer.active is None
+        if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _split_path(buf) and ops.KernelTimer.active is None
                 and not blk.use_layer_scale and not _drops(blk) and not blk.cpe.xcpe and buf.dtype == torch.float32
                 and _attn_f16_ok(buf.shape[0], att, depth)):
             return False
@@ -1448,7 +1368,7 @@ class HOTFormerStage(nn.Module):
                 # once both are done -- the ~120 us chain of eight tiny RTSA launches leaves the critical path.
                 main = torch.cuda.current_stream()
                 side = [main] * (len(depths) - 1) if _SERIAL_STREAMS else self._side_streams(data.device)
-                rs = main if (_SERIAL_STREAMS or not _RTSA_STREAM) else self._rtsa_stream(data.device)
+                rs = main if _SERIAL_STREAMS else self._rtsa_stream(data.device)
                 small = [not (j == 0 or bufs[d].shape[0] > _SIDE_STREAM_MAX_ROWS) for j, d in enumerate(depths)]
                 sts = [side[j - 1] if small[j] else main for j in range(len(depths))]
                 # issue order = critical path first (the host runs only just ahead of the GPU here): the finest level's
@@ -1458,9 +1378,9 @@ class HOTFormerStage(nn.Module):
                 # RTSA i; RTSA i needs every level's block i - 1.  Nothing else: in particular the finest level's CPE / LN1 /
                 # qkv of iteration i do not wait for the coarse levels' MLP launches of iteration i - 1, which run (starved)
                 # beside and after the finest level's chip-filling fused MLP -- with a join of all streams at the end of every
-                # iteration (HFL_ITER_JOIN=1, rounds 2-3) the finest level's queue stood idle ~80 us per iteration there
-                # (kernel trace, profiles/r04_phases_iteration_timeline_join.log).
-                join = _ITER_JOIN or done is None
+                # iteration (the schedule of rounds 2-3, since removed) the finest level's queue stood idle ~80 us per
+                # iteration there (kernel trace, profiles/r04_phases_iteration_timeline_join.log).
+                join = done is None
                 ev0 = main.record_event() if join else None
                 if first is None:
                     first = (dict(bufs), dict(rts))
@@ -1528,7 +1448,7 @@ class HOTFormerStage(nn.Module):
                     with torch.cuda.stream(sts[j]):
                         bufs[depths[j]] = outs[j]
                         rts[depths[j]] = self.up_projections[j][i](outs[j][nts[j]:]) if proj else outs[j][nts[j]:]
-                if _ITER_JOIN or i + 1 == self.num_blocks:
+                if i + 1 == self.num_blocks:
                     for j in range(len(depths)):
                         if sts[j] is not main:
                             main.wait_stream(sts[j])
@@ -1536,17 +1456,6 @@ class HOTFormerStage(nn.Module):
                     done = [st.record_event() for st in dict.fromkeys(sts)]
                 del calls, old, fresh, rt_all
                 continue
-            call0 = None
-            if (_CPE_FIRST and _PYRAMID_STREAMS and not _SERIAL_STREAMS and not ckpt and not _grad_path(data) and data.is_cuda
-                    and not proj):
-                # Probe (off): the finest level's CPE, which reads token rows only, issued BEFORE the relay-token block on the same
-                # stream (no event hop), so that it runs alone instead of behind the coarse levels' forked launches (kernel
-                # timeline profiles/r06_x_phases_iteration_5.log: 131 us there, 44 us alone).  Measured -1.9 % on the headline,
-                # Oxford -0.4 % (profiles/r06_aa_ab_cpe_first.log): the relay-token block then starts 44 us later and everything
-                # that waits for it with it.
-                call0 = _native_block_call(self.hosa_blocks[0][i], bufs[depths[0]], plan, depths[0])
-                if call0 is not None:
-                    call0.run(1)
             if ckpt:                                                    # 596-601
                 rt_all = _checkpoint_block(self.rtsa_blocks[i], torch.cat([rts[d] for d in depths], 0), plan)
             else:
@@ -1573,14 +1482,11 @@ class HOTFormerStage(nn.Module):
                         bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
                     used.append(j)
                 for j, d in enumerate(depths):
-                    if j == 0 and call0 is not None:            # the rest of the block whose CPE went out before RTSA
-                        out = self.hosa_blocks[0][i]._tail(call0.run(2, fresh[d]), plan, d)
-                        bufs[d], rts[d] = out, out[nts[0]:]
-                    elif j not in used:
+                    if j not in used:
                         bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
                 for j in used:
                     main.wait_stream(side[j - 1])
-                del keep, call0
+                del keep
             else:
                 for j, d in enumerate(depths):
                     bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
@@ -1632,7 +1538,7 @@ class HOTFormerBase(nn.Module):
                                          num_pyramid_levels=self.num_pyramid_levels,
                                          num_octf_levels=self.num_octf_levels, adape_mode=self.ADaPE_mode)
 
-        if _PLAN_LATE and not _grad_path() and data.is_cuda:
+        if not _grad_path() and data.is_cuda:
             # inference: the stem first (it only needs the tap lists, whose counts the host has to wait for anyway), THEN the
             # plan: its ~0.25 ms of host work runs while the GPU executes the stem's 0.7 ms instead of in front of it with
             # the GPU idle (kernel trace of a step's first millisecond, profiles/r04_phases_stem_head_end_of_round.log)
@@ -1699,8 +1605,9 @@ class AdaptivePooling(nn.Module):
         """x (N_t, C) ragged over clouds -> (B, k, C) (`out`: where to, e.g. this level's slice of the token matrix)."""
         if _grad_path(x):
             return ag.attentional_pooling_torch(x, self.query, plan, depth, self.scale)
-        if _ATTN_POOL and _GEMM_MODE == 'x3' and _split_path(x) and x.dtype == torch.float32 and ops.attn_pool_ok(x.shape[1]):
-            # scores -> softmax over the cloud's rows -> weighted sum in one launch, nothing padded (csrc/attn_pool.hip)
+        if _GEMM_MODE == 'x3' and _split_path(x) and x.dtype == torch.float32 and ops.attn_pool_ok(x.shape[1]):
+            # scores -> softmax over the cloud's rows -> weighted sum in one launch, nothing padded (csrc/attn_pool.hip; was GEMM
+            # + segment softmax + two padding copies + batched GEMM)
             return ops.attn_pool(x, plan.cloud_off[depth], self.query, plan.B, self.scale, out=out)
         scores = torch.mm(x, self.query.t())                              # (N_t, k)
         ops.segment_softmax_(scores, plan.cloud_off[depth], plan.B, self.scale)
@@ -1731,9 +1638,6 @@ class FeatureMixerLayer(nn.Module):
 
     def forward(self, x):
         return x + self.mix(x)
-
-
-_MIXER_FUSED = _knob('HFL_MIXER_FUSED', '1') != '0'
 
 
 def _mixer_pack(fc1: nn.Linear, fc2: nn.Linear):
@@ -1774,7 +1678,7 @@ class Mixer(nn.Module):
             x2 = x.reshape(b * k, c)
             for m in self.mix:
                 ln, fc1, _, fc2 = m.mix
-                if _MIXER_FUSED and _GEMM_MODE == 'x3' and ops.mlp_fused_shape_ok(c, fc1.out_features):
+                if _GEMM_MODE == 'x3' and ops.mlp_fused_shape_ok(c, fc1.out_features):
                     # the whole layer as the block MLP's launch (hidden = C): one launch (+ the hidden split's reduce) for three
                     x2 = ops.ln_mlp_fused(x2.contiguous(), ln.weight, ln.bias, ln.eps, _mixer_pack(fc1, fc2), fc1.bias, fc2.bias)
                     continue
@@ -1794,7 +1698,7 @@ class Mixer(nn.Module):
             x = x2.view(b, k, c)
         else:
             x = self.mix(x)
-        if (_MIXER_FUSED and _GEMM_MODE == 'x3' and x.is_cuda and not _grad_path() and x.dtype == torch.float32
+        if (_GEMM_MODE == 'x3' and x.is_cuda and not _grad_path() and x.dtype == torch.float32
                 and x.shape[-1] % 4 == 0 and self.row_proj.out_features <= 8 and self.channel_proj.bias is not None
                 and self.row_proj.bias is not None and x.shape[1] * self.row_proj.out_features <= 16000):
             # channel_proj, row_proj and the flatten as one small launch (row_proj first: the maps commute)
@@ -2024,26 +1928,9 @@ class HOTFormerLoc(nn.Module):
         if octree.device.type != 'cuda':
             raise RuntimeError('HOTFormerLoc (MI355X build) needs the octree on a GPU; '
                                'call to_device(batch, "cuda") first -- there is no CPU path')
-        if _MAIN_HI and not _grad_path() and not _SERIAL_STREAMS:
-            # probe (HFL_MAIN_HI=1): the whole inference forward on a HIGH-priority stream, so that the finest pyramid level's
-            # chain (which stays on it) wins the CUs against the coarse levels' side streams (normal priority)
-            hi = self.__dict__.get('_hi_stream')
-            if hi is None or hi.device != octree.device:
-                hi = self.__dict__['_hi_stream'] = torch.cuda.Stream(device=octree.device, priority=-1)
-            cur = torch.cuda.current_stream(octree.device)
-            hi.wait_stream(cur)
-            with torch.cuda.stream(hi):
-                out = self._forward(batch)
-            cur.wait_stream(hi)
-            out['global'].record_stream(cur)
-            return out
-        return self._forward(batch)
-
-    def _forward(self, batch):
-        octree = batch['octree']
         octree.construct_all_neigh()                     # no-op when misc/torch_utils.to_device did it
         data = octree.get_input_feature(self.input_features, nempty=True)
-        armed = self.training and _DROP_POOL
+        armed = self.training
         if armed:
             arm_drop_paths(self, int(octree.batch_size), data.device, data.dtype)
         try:

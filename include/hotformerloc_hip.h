@@ -307,7 +307,7 @@ int hfl_gemm_bf16_tn(float* out, const uint16_t* a, const uint16_t* b, int64_t n
  * build: "window_attention" (4 = default, 2 = three-lookup fp32 kernel), "window_rpe_form1_max_depth" (table form of the fp16
  * kernel), "window_bwd", "window_heads_per_wg", "window_v4_wgs_per_cu" / "window_v2_wgs_per_cu", "window_debug",
  * "tail_split" / "dynamic_units" / "mlp_stagger" (left-over rows, work tickets and start stagger of the row-tile kernels),
- * "attn_fused_split", "cpe_variant", "cpe_chunk_rows", "x3_dbg".  The variants that lost their A/B measurements in rounds
+ * "attn_fused_split", "cpe_chunk_rows", "x3_dbg".  The variants that lost their A/B measurements in rounds
  * 2-4 (per-round launches, relay rows first, CU-masked streams, device-flag hops, the x3 ring kernel, 4-wave row tiles) are
  * gone from the library; their logs are under profiles/.  Returns HFL_EINVAL for an unknown key. */
 int hfl_set_variant(const char* key, int value);
@@ -643,9 +643,7 @@ typedef struct hfl_block_weights {
                                                           bit 1: a block WITH relay rows runs LN1 -> qkv -> window attention of its
                                                           token rows as ONE launch (hfl_attn_ws_fwd) when hfl_attn_ws_ok takes the
                                                           configuration; needs qkv_pack and rpe_tables3.  Phase 1 is then the CPE
-                                                          alone (the launch reads the relay rows' q / k / v).
-                                                          bit 2: copy the relay rows into the block's buffer first (the form before
-                                                          proj's residual read them in place; for A/B runs) */
+                                                          alone (the launch reads the relay rows' q / k / v). */
   const float* rpe_tables3;                            /* hfl_window_rpe_expand(..., f16_operand = 2) of rpe_table, or NULL */
 } hfl_block_weights;
 typedef struct hfl_block_io {

@@ -142,6 +142,26 @@ def test_product_never_imports_oracle():
             assert '/root/reference' not in open(path).read()
 
 
+def test_package_reads_only_the_product_and_build_variables():
+    """No environment variable changes what the model computes or how it schedules work except the product switches
+    (HFL_GEMM, HFL_CHECKPOINT, HFL_CHECKPOINT_FREE_FRACTION); the build reads ROCM_PATH, HIPCC and HFL_EXTRA_HIPCC_FLAGS, and
+    the package sets hipBLASLt's TENSILE_STREAMK_DATA_PARALLEL.  Schedule and fusion seams are module attributes."""
+    read = set()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, 'hotformerloc_amd')):
+        for f in files:
+            if not f.endswith('.py'):
+                continue
+            src = open(os.path.join(dirpath, f)).read()
+            assert 'HFL_PROBES' not in src, f
+            uses = re.findall(r'\b(?:environ|getenv)\b', src)
+            names = re.findall(r'\b(?:environ\s*(?:\.\s*(?:get|setdefault|pop)\s*\(|\[)|getenv\s*\()\s*[\'"]([A-Za-z0-9_]+)[\'"]',
+                               src)
+            assert len(names) == len(uses), (f, 'an environment access without a literal variable name')
+            read.update(names)
+    assert read == {'HFL_GEMM', 'HFL_CHECKPOINT', 'HFL_CHECKPOINT_FREE_FRACTION', 'ROCM_PATH', 'HIPCC',
+                    'HFL_EXTRA_HIPCC_FLAGS', 'TENSILE_STREAMK_DATA_PARALLEL'}, read
+
+
 def test_synthetic_generators_are_pinned():
     u = syn.hash_uniform(12345, 4)
     assert np.allclose(u, syn.hash_uniform(12345, 6)[:4]) and np.all(np.abs(u) < 1)
