@@ -135,6 +135,8 @@ SIGNATURES = {
     'hfl_linear_x6_padded_k': (c_int64, [c_int64]),
     'hfl_linear_x6_pack': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'hfl_linear_x6': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    'hfl_linear_x6_gelu_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    'hfl_linear_x6_gelu_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     'hfl_layer_norm_split2': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                       c_float, c_void_p]),
     'hfl_layer_norm_relu': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p]),
@@ -160,6 +162,8 @@ SIGNATURES = {
                                     c_int, c_void_p, c_void_p]),
     'hfl_wgrad_x3_workspace': (c_int64, [c_int64, c_int64, c_int64]),
     'hfl_wgrad_x3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    'hfl_wgrad_f32_workspace': (c_int64, [c_int64, c_int64, c_int64]),
+    'hfl_wgrad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'hfl_layer_norm_bwd_blocks': (c_int, [c_int64, c_int64]),
     'hfl_layer_norm_bwd_add': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                        c_float, c_void_p]),

@@ -627,6 +627,131 @@ def mlp_x3(h, w1, b1, w2, b2):
     return MlpX3Fn.apply(h, w1, b1, w2, b2)
 
 
+# ------------------------------------------------ matched-precision Linear on the hand-written kernels (GEMM mode x6)
+def _w6_cached(weight, transposed: bool):
+    """The three bf16 planes (`ops.x6_pack`) of a Linear weight, or of its transpose for dx = dy W, rebuilt when the optimizer
+    updates the parameter (a checkpointed block's recomputation finds them)."""
+    import weakref
+    key = (id(weight), transposed, 'x6')
+    hit = _WSPLIT_CACHE.get(key)
+    if hit is None or hit[0]() is not weight or hit[1] != weight._version or hit[3] != weight.data_ptr():
+        w = weight.detach().t().contiguous() if transposed else weight.detach()
+        if len(_WSPLIT_CACHE) > 4096:
+            _WSPLIT_CACHE.clear()
+        hit = (weakref.ref(weight), weight._version, ops.x6_pack(w), weight.data_ptr())
+        _WSPLIT_CACHE[key] = hit
+    return hit[2]
+
+
+def linear_x6_ok(in_features: int, out_features: int) -> bool:
+    """Shapes `hfl_linear_x6` takes in both directions (forward and dx = dy W) and `hfl_wgrad_f32` takes for dW."""
+    return (in_features % 128 == 0 and out_features % 128 == 0 and ops.linear_x6_ok(in_features, out_features)
+            and ops.linear_x6_ok(out_features, in_features))
+
+
+def _wgrad6(dy, x, need_w: bool, need_b: bool):
+    """(dW, db) through `hfl_wgrad_f32`, or (None, None) without a launch when neither is wanted (frozen layers)."""
+    if not (need_w or need_b):
+        return None, None
+    dw, db = ops.wgrad_f32(dy, x, with_bias=need_b)
+    return (dw if need_w else None), db
+
+
+class LinearX6Fn(torch.autograd.Function):
+    """y = x W^T + b at fp32 grade on hand-written kernels: forward and dx = dy W on `hfl_linear_x6` (three bf16 planes per
+    operand, six plane products, fp32 accumulation), dW = dy^T x and db on `hfl_wgrad_f32` (fp32 MFMA).  The forward is the
+    x6 inference launch, with or without autograd.  What is kept for the backward is x itself."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1]).contiguous()
+        ctx.has_bias = bias is not None
+        ctx.shape = shape
+        ctx.save_for_backward(x2, weight)
+        if x2.shape[0] == 0:
+            return x.new_zeros(*shape[:-1], weight.shape[0])
+        return ops.linear_x6(x2, _w6_cached(weight, False), bias=bias).view(*shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, weight = ctx.saved_tensors
+        dy2 = dy.reshape(-1, weight.shape[0]).contiguous()
+        need = ctx.needs_input_grad
+        dx = ops.linear_x6(dy2, _w6_cached(weight, True)).view(ctx.shape) if need[0] else None
+        dw, db = _wgrad6(dy2, x2, need[1], ctx.has_bias and need[2])
+        return dx, dw, db
+
+
+def linear_x6(x, weight, bias=None):
+    return LinearX6Fn.apply(x, weight, bias)
+
+
+class MlpX6Fn(torch.autograd.Function):
+    """fc2(gelu(fc1(h))) at fp32 grade: fc1 writes gelu(.) and the pre-activation in one launch (hfl_linear_x6_gelu_fwd), the
+    backward's dx GEMM of fc2 multiplies by gelu'(pre-activation) in its epilogue (hfl_linear_x6_gelu_bwd); weight gradients
+    on hfl_wgrad_f32.  The forward is bitwise the x6 inference MLP (MLP.forward)."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2):
+        shape = h.shape
+        h2 = h.reshape(-1, shape[-1]).contiguous()
+        g, pre = ops.linear_x6_gelu_fwd(h2, _w6_cached(w1, False), b1)
+        ctx.save_for_backward(h2, g, pre, w1, w2)
+        ctx.shape = shape
+        return ops.linear_x6(g, _w6_cached(w2, False), bias=b2).view(*shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, dout):
+        h2, g, pre, w1, w2 = ctx.saved_tensors
+        dy = dout.reshape(-1, w2.shape[0]).contiguous()
+        need = ctx.needs_input_grad
+        dp = ops.linear_x6_gelu_bwd(dy, _w6_cached(w2, True), pre)
+        dw2, db2 = _wgrad6(dy, g, need[3], need[4])
+        dh = ops.linear_x6(dp, _w6_cached(w1, True)).view(ctx.shape) if need[0] else None
+        dw1, db1 = _wgrad6(dp, h2, need[1], need[2])
+        return dh, dw1, db1, dw2, db2
+
+
+def mlp_x6(h, w1, b1, w2, b2):
+    return MlpX6Fn.apply(h, w1, b1, w2, b2)
+
+
+class LnMlpResidualX6Fn(torch.autograd.Function):
+    """x + s * fc2(gelu(fc1(LN(x)))) at fp32 grade (the x6 counterpart of LnMlpResidualX3Fn; s = the per-row stochastic-depth
+    factor or None): LayerNorm, fc1 + GELU (+ pre-activation), fc2 + bias + scale + residual forward; the skip path's gradient
+    joins inside the LayerNorm backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, w1, b1, w2, b2, row_scale):
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1]).contiguous()
+        h = ops.layer_norm(x2, gamma, beta, eps)
+        g, pre = ops.linear_x6_gelu_fwd(h, _w6_cached(w1, False), b1)
+        ctx.save_for_backward(x2, gamma, h, g, pre, w1, w2, row_scale if row_scale is not None else x2.new_empty(0))
+        ctx.shape, ctx.eps, ctx.scaled = shape, eps, row_scale is not None
+        return ops.linear_x6(g, _w6_cached(w2, False), bias=b2, residual=x2, row_scale=row_scale).view(shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, gamma, h, g, pre, w1, w2, row_scale = ctx.saved_tensors
+        dout2 = dout.reshape(-1, w2.shape[0]).contiguous()
+        dy = dout2 * row_scale.unsqueeze(1) if ctx.scaled else dout2
+        dp = ops.linear_x6_gelu_bwd(dy, _w6_cached(w2, True), pre)
+        need = ctx.needs_input_grad                    # (x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
+        dw2, db2 = _wgrad6(dy, g, need[6], need[7])
+        dw1, db1 = _wgrad6(dp, h, need[4], need[5])
+        if not (need[0] or need[1] or need[2]):
+            return None, None, None, None, dw1, db1, dw2, db2, None
+        dh = ops.linear_x6(dp, _w6_cached(w1, True))
+        dx, dg, dbeta = ops.layer_norm_bwd(dh, x2, gamma, ctx.eps, dres=dout2)
+        return (dx.view(ctx.shape), dg if need[1] else None, dbeta if need[2] else None, None, dw1, db1, dw2, db2, None)
+
+
+def ln_mlp_residual_x6(x, gamma, beta, eps, w1, b1, w2, b2, row_scale=None):
+    return LnMlpResidualX6Fn.apply(x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
+
+
 # ------------------------------------------------ conditional position encoding, training forward as one launch
 class CpeFn(torch.autograd.Function):
     """[x +] LayerNorm(dwconv(x)) (CPE.forward and its callers' residual: models/layers/octformer_layers.py:138-142,

@@ -2,6 +2,8 @@
 //
 //     y (M,N) = x (M,K) . W (N,K)^T  [+ bias]  [GELU]  [* row_scale]  [+ residual]        (all f32 in memory)
 //
+// and for the training path (GEMM mode x6 under autograd) gelu(acc + bias) together with acc + bias, and acc * gelu'(pre).
+//
 // Replaces torch.nn.Linear + the element-wise op that follows it where the caller wants the reference's own arithmetic
 // (fp32 Linear layers: models/octformer_backbone.py:70,91; fc1 -> GELU -> fc2: models/layers/octformer_layers.py:53-59;
 // residual adds: models/octformer_backbone.py:275-278, models/hotformerloc_backbone.py:213-216) instead of the 16-bit-operand
@@ -86,6 +88,7 @@ struct X6Params {
   const int32_t* tiles;
   const int32_t* gather;
   int n_valid;
+  float* out2;              // (M, N): the pre-activation acc + bias of the GELU-forward epilogue (EPI 2), else unused
 };
 
 __device__ __forceinline__ int x6_swz(int row) { return (0x1320 >> (((row >> 2) & 3) << 2)) & 3; }
@@ -120,9 +123,13 @@ __device__ __forceinline__ unsigned char* x6_ep_region(unsigned char* sx1, unsig
 // wavefront owns.  The wave transposes 16 rows at a time through its LDS region (16-B chunks XOR-swizzled by the row:
 // conflict-free both ways) so that 16 consecutive lanes hold 256 contiguous bytes of one output row: every store instruction
 // writes whole 128-B lines.
-template <int GELU, int MT>
+// EPI: 0 = (acc + bias) [* row_scale] [+ residual];  1 = gelu(acc + bias);  2 = as 1, and acc + bias to out2 (the training
+// forward of fc1);  3 = acc * gelu'(residual) (the training backward of fc2: `residual` is the saved pre-activation, read as
+// the residual is)
+template <int EPI, int MT>
 __device__ __forceinline__ void x6_epilogue(const X6Params& p, f32x4 (&acc)[4][MT], unsigned char* ep, int64_t m_tile, int n_tile,
                                             int lane, int64_t m_end) {
+  constexpr bool GELU = EPI == 1 || EPI == 2;
   const int frow = lane & 15, fq = lane >> 4;
   const int N = p.N;
   const int ecol = lane & 15;
@@ -158,8 +165,13 @@ __device__ __forceinline__ void x6_epilogue(const X6Params& p, f32x4 (&acc)[4][M
       if (m >= m_end || nbase >= p.n_valid) continue;
       float4 v = make_float4(a[0] + b.x, a[1] + b.y, a[2] + b.z, a[3] + b.w);
       if (GELU) {
+        if (EPI == 2) *reinterpret_cast<f32x4*>(p.out2 + m * N + nbase) = (f32x4){v.x, v.y, v.z, v.w};
         const f32x2 g01 = x3_gelu2((f32x2){v.x, v.y}), g23 = x3_gelu2((f32x2){v.z, v.w});
         v = make_float4(g01[0], g01[1], g23[0], g23[1]);
+      } else if (EPI == 3) {
+        const float4 pre = rs[GELU ? 0 : j][GELU ? 0 : it];
+        const f32x2 d01 = x3_gelu_grad2((f32x2){pre.x, pre.y}), d23 = x3_gelu_grad2((f32x2){pre.z, pre.w});
+        v = make_float4(v.x * d01[0], v.y * d01[1], v.z * d23[0], v.w * d23[1]);
       } else {
         if (p.row_scale != nullptr) {
           const float sc = rsc[GELU ? 0 : j][GELU ? 0 : it];
@@ -200,7 +212,7 @@ __device__ unsigned long long g_x6_stamps[2][512];
 // reads, splits and issues the LDS-DMA of W (t + 1).  Two barriers per k-step; the matrix pipe of every SIMD always has one
 // of its two waves in an MFMA phase (in lock-step, as one barrier per k-step has them, the fragment reads, the split and the
 // barrier skew of BOTH waves lie between the MFMA phases: the pipe was 34 % busy, PMC).
-template <int GELU, int MT, int NWN>
+template <int EPI, int MT, int NWN>
 __global__ void __launch_bounds__(512, 2)
 gemm_x6_kernel(const X6Params p) {
   using G = X6Geo<MT, NWN>;
@@ -438,7 +450,7 @@ gemm_x6_kernel(const X6Params p) {
       bar_lds();                                 // B2 (nk - 1)
       mfma_all();
       bar_full();                                // end of tile
-      x6_epilogue<GELU, MT>(p, acc, x6_ep_region<MT, NWN>(sx1, sw1, wave), m0 + wm * (16 * MT), n0 + wn * 64, lane, m_end);
+      x6_epilogue<EPI, MT>(p, acc, x6_ep_region<MT, NWN>(sx1, sw1, wave), m0 + wm * (16 * MT), n0 + wn * 64, lane, m_end);
     }
   } else {
     // ------------------------------------------------------------------ group B: [MFMA of the step before | reads, split, x request]
@@ -481,7 +493,7 @@ gemm_x6_kernel(const X6Params p) {
       prio_lo();
       bar_full();                                // end of tile
       mfma_all();                                // step nk - 1
-      x6_epilogue<GELU, MT>(p, acc, x6_ep_region<MT, NWN>(sx1, sw1, wave), m0 + wm * (16 * MT), n0 + wn * 64, lane, m_end);
+      x6_epilogue<EPI, MT>(p, acc, x6_ep_region<MT, NWN>(sx1, sw1, wave), m0 + wm * (16 * MT), n0 + wn * 64, lane, m_end);
     }
   }
 }
@@ -529,22 +541,27 @@ int hfl_linear_x6_pack(uint16_t* w3, const float* w, int64_t out_features, int64
   HFL_RETURN_LAST_ERROR();
 }
 
+// epi: the epilogue (x6_epilogue's EPI); out2: the pre-activation output of epi 2
 static int x6_launch(float* out, const float* x, const uint16_t* w3, const float* bias, const float* residual,
-                     const float* row_scale, int64_t n_rows, int in_features, int out_features, int gelu, hfl_stream_t stream,
-                     const int32_t* tiles, int64_t n_tiles, const int32_t* gather, int64_t w_rows) {
+                     const float* row_scale, int64_t n_rows, int in_features, int out_features, int epi, hfl_stream_t stream,
+                     const int32_t* tiles, int64_t n_tiles, const int32_t* gather, int64_t w_rows, float* out2 = nullptr) {
   if (n_rows < 0 || in_features <= 0 || out_features <= 0) return HFL_EINVAL;
   const bool grouped = tiles != nullptr;
   const bool narrow = grouped && out_features == 64;                 // W blocks padded to 128 rows by the caller
   if (in_features % 32 != 0 || (out_features % 128 != 0 && !narrow)) return HFL_EINVAL;
   if (out == nullptr || x == nullptr || w3 == nullptr) return HFL_EINVAL;
-  if (gelu && (residual != nullptr || row_scale != nullptr)) return HFL_EINVAL;
+  if (epi < 0 || epi > 3) return HFL_EINVAL;
+  if ((epi == 1 || epi == 2) && (residual != nullptr || row_scale != nullptr)) return HFL_EINVAL;
+  if (epi == 2 && out2 == nullptr) return HFL_EINVAL;
+  if (epi == 3 && (residual == nullptr || bias != nullptr || row_scale != nullptr)) return HFL_EINVAL;
+  if (epi >= 2 && tiles != nullptr) return HFL_EINVAL;
   const int64_t kp = hfl_linear_x6_padded_k(in_features);
   if (!grouped) w_rows = out_features;
   if (w_rows * kp * 2 >= ((int64_t)1 << 31)) return HFL_ECAPACITY;          // 32-bit offsets inside a W plane
   if (n_rows == 0 || (grouped && n_tiles == 0)) return HFL_OK;
   X6Params p;
   p.out = out; p.x = x; p.w3 = w3; p.bias = bias; p.residual = residual; p.row_scale = row_scale;
-  p.tiles = tiles; p.gather = gather; p.n_valid = out_features;
+  p.tiles = tiles; p.gather = gather; p.n_valid = out_features; p.out2 = out2;
   p.M = n_rows; p.N = out_features; p.K = in_features;
   p.nk = (int)(kp / 32);
   p.w_plane_bytes = w_rows * kp * 2;
@@ -583,7 +600,8 @@ static int x6_launch(float* out, const float* x, const uint16_t* w3, const float
   if (nwn == 4) { if (mt == 4) HFL_X6_LAUNCH(G, 4, 4); else HFL_X6_LAUNCH(G, 2, 4); }                \
   else if (mt == 4) HFL_X6_LAUNCH(G, 4, 2); else if (mt == 3) HFL_X6_LAUNCH(G, 3, 2);               \
   else if (mt == 2) HFL_X6_LAUNCH(G, 2, 2); else HFL_X6_LAUNCH(G, 1, 2);
-  if (gelu) { HFL_X6_SHAPES(1) } else { HFL_X6_SHAPES(0) }
+  if (epi == 1) { HFL_X6_SHAPES(1) } else if (epi == 2) { HFL_X6_SHAPES(2) } else if (epi == 3) { HFL_X6_SHAPES(3) }
+  else { HFL_X6_SHAPES(0) }
 #undef HFL_X6_SHAPES
 #undef HFL_X6_LAUNCH
   HFL_RETURN_LAST_ERROR();
@@ -591,7 +609,21 @@ static int x6_launch(float* out, const float* x, const uint16_t* w3, const float
 
 int hfl_linear_x6(float* out, const float* x, const uint16_t* w3, const float* bias, const float* residual,
                   const float* row_scale, int64_t n_rows, int in_features, int out_features, int gelu, hfl_stream_t stream) {
-  return x6_launch(out, x, w3, bias, residual, row_scale, n_rows, in_features, out_features, gelu, stream, nullptr, 0, nullptr, 0);
+  return x6_launch(out, x, w3, bias, residual, row_scale, n_rows, in_features, out_features, gelu ? 1 : 0, stream, nullptr, 0,
+                   nullptr, 0);
+}
+
+int hfl_linear_x6_gelu_fwd(float* out, float* preact, const float* x, const uint16_t* w3, const float* bias, int64_t n_rows,
+                           int in_features, int out_features, hfl_stream_t stream) {
+  if (preact == nullptr) return HFL_EINVAL;
+  return x6_launch(out, x, w3, bias, nullptr, nullptr, n_rows, in_features, out_features, 2, stream, nullptr, 0, nullptr, 0,
+                   preact);
+}
+
+int hfl_linear_x6_gelu_bwd(float* out, const float* dy, const uint16_t* wt3, const float* preact, int64_t n_rows,
+                           int in_features, int out_features, hfl_stream_t stream) {
+  if (preact == nullptr) return HFL_EINVAL;
+  return x6_launch(out, dy, wt3, nullptr, preact, nullptr, n_rows, in_features, out_features, 3, stream, nullptr, 0, nullptr, 0);
 }
 
 /* Grouped form with the gather done by the tile loader (see include/hotformerloc_hip.h): the per-tap products of an octree

@@ -98,6 +98,9 @@ _TRAIN_SPLIT = False
 # training-path Linear layers on the hand-written split GEMMs (autograd.LinearX3Fn: forward + dx on hfl_linear_x3, dW / db
 # on hfl_wgrad_x3)
 _TRAIN_X3 = True
+# GEMM mode 'x6' training-path Linear layers on the hand-written fp32-grade kernels (autograd.LinearX6Fn / MlpX6Fn /
+# LnMlpResidualX6Fn: forward and dx on hfl_linear_x6, dW / db on hfl_wgrad_f32); off = the fp32 library GEMMs (F.linear)
+_TRAIN_X6 = True
 _TRAIN_MLP = True              # fused fc1 -> GELU -> fc2 autograd Function
 _SPARSE_CONV = True            # large 3x3x3 convs over live taps only
 _EARLY_PHASE = True            # token-row half of a block issued before / beside RTSA
@@ -119,6 +122,13 @@ def set_train_x3(enabled: bool):
     """Training-path Linear layers through `autograd.LinearX3Fn` (default on in GEMM mode 'x3')."""
     global _TRAIN_X3
     _TRAIN_X3 = bool(enabled)
+
+
+def set_train_x6(enabled: bool):
+    """Training-path Linear layers of GEMM mode 'x6' through `autograd.LinearX6Fn` and the MLP Functions (default on);
+    False: torch's fp32 Linear (hipBLASLt) as before."""
+    global _TRAIN_X6
+    _TRAIN_X6 = bool(enabled)
 
 
 def set_pyramid_streams(enabled):
@@ -184,6 +194,13 @@ def _x6_path(x, *linears) -> bool:
     takes (in_features % 32 == 0, out_features % 128 == 0)."""
     return (_GEMM_MODE == 'x6' and x.is_cuda and not _grad_path() and x.dtype == torch.float32 and x.numel() > 0
             and all(_x6_lin_ok(l) for l in linears))
+
+
+def _x6_train(x, *linears) -> bool:
+    """Matched-precision training path: GEMM mode 'x6' under autograd (or `training_numerics`), fp32 rows on the GPU, every
+    Linear a shape the hand-written kernels take in both directions."""
+    return (_GEMM_MODE == 'x6' and _TRAIN_X6 and x.is_cuda and _grad_path() and x.dtype == torch.float32 and x.numel() > 0
+            and all(ag.linear_x6_ok(l.in_features, l.out_features) for l in linears))
 
 
 def _block_tail_x6(x, attn_out, proj: nn.Linear, norm2: nn.LayerNorm, mlp: 'MLP'):
@@ -286,6 +303,8 @@ class SplitLinear(nn.Linear):
         if (_GEMM_MODE == 'bf16x3' and _TRAIN_SPLIT and x.is_cuda and _grad_path()
                 and self.in_features % 8 == 0 and self.out_features % 8 == 0 and x.numel() > 0):
             return ag.linear_split(x, self.weight, self.bias)
+        if _x6_train(x, self):
+            return ag.linear_x6(x, self.weight, self.bias)       # fp32-grade forward and dx, fp32-MFMA dW
         if _x6_path(x, self):
             y = ops.linear_x6(x.reshape(-1, self.in_features), _w6(self), bias=self.bias)
             return y.view(*x.shape[:-1], self.out_features)
@@ -675,6 +694,8 @@ class MLP(nn.Module):
                 and f1.bias is not None and f2.bias is not None
                 and ag.linear_x3_ok(f1.in_features, f1.out_features) and ag.linear_x3_ok(f2.in_features, f2.out_features)):
             return ag.mlp_x3(x, f1.weight, f1.bias, f2.weight, f2.bias)      # GELU and its gradient inside the GEMMs
+        if _x6_train(x, f1, f2) and f1.bias is not None and f2.bias is not None:
+            return ag.mlp_x6(x, f1.weight, f1.bias, f2.weight, f2.bias)
         if _x6_path(x, f1, f2) and x.dim() == 2:
             return ops.linear_x6(ops.linear_x6(x, _w6(f1), bias=f1.bias, gelu=True), _w6(f2), bias=f2.bias)
         return self.fc2(F.gelu(self.fc1(x)))
@@ -688,6 +709,9 @@ def _mlp_branch(x, norm: nn.LayerNorm, mlp: 'MLP', row_scale=None):
             and x.dtype == torch.float32 and x.shape[-1] in ops._LN_CHANNELS and f1.bias is not None and f2.bias is not None
             and ag.linear_x3_ok(f1.in_features, f1.out_features) and ag.linear_x3_ok(f2.in_features, f2.out_features)):
         return ag.ln_mlp_residual_x3(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
+    if (_x6_train(x, f1, f2) and x.shape[-1] in ops._LN_CHANNELS and x.dim() == 2 and f1.bias is not None
+            and f2.bias is not None):
+        return ag.ln_mlp_residual_x6(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
     y = mlp(_ln(x, norm))
     return x + (y if row_scale is None else y * row_scale.unsqueeze(1))
 
@@ -1685,6 +1709,16 @@ class Mixer(nn.Module):
                 h2 = ops.layer_norm_split2(x2, ln.weight, ln.bias, ln.eps)
                 g2 = ops.linear_x3(h2, _w2(fc1), bias=fc1.bias, gelu_split_out=True)
                 x2 = ops.linear_x3(g2, _w2(fc2), bias=fc2.bias, residual=x2)
+            x = x2.view(b, k, c)
+        elif (all(_mixer_layer_fits(m) for m in self.mix) and x.shape[-1] in ops._LN_CHANNELS
+              and _x6_train(x, *[l for m in self.mix for l in (m.mix[1], m.mix[3])])):
+            # matched-precision training: every FeatureMixerLayer as one autograd Function (LayerNorm, fc1 + GELU, fc2 + bias +
+            # residual forward; weight gradients on hfl_wgrad_f32)
+            b, k, c = x.shape
+            x2 = x.reshape(b * k, c)
+            for m in self.mix:
+                ln, fc1, _, fc2 = m.mix
+                x2 = ag.ln_mlp_residual_x6(x2, ln.weight, ln.bias, ln.eps, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
             x = x2.view(b, k, c)
         elif all(_mixer_layer_fits(m) for m in self.mix) and _x6_path(x, *[l for m in self.mix for l in (m.mix[1], m.mix[3])]):
             # matched precision: LayerNorm, fc1 + bias + GELU, fc2 + bias + residual on hfl_linear_x6 (three launches per layer)

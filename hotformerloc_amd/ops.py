@@ -535,6 +535,39 @@ def linear_x6(x: torch.Tensor, w3: torch.Tensor, bias=None, residual=None, gelu:
     return out
 
 
+def linear_x6_gelu_fwd(x: torch.Tensor, w3: torch.Tensor, bias):
+    """(gelu(x W^T + b), x W^T + b) in one launch (hfl_linear_x6_gelu_fwd): the training forward of fc1 at matched precision.
+    The first is bitwise `linear_x6(x, w3, bias, gelu=True)`, the second bitwise `linear_x6(x, w3, bias)`."""
+    _dev(x, w3, bias)
+    assert w3.dtype == torch.bfloat16 and w3.is_contiguous() and w3.dim() == 3 and w3.shape[0] == 3
+    xc = _f32c(x)
+    m, k = xc.shape
+    n = w3.shape[1]
+    assert w3.shape[2] == (k + 63) // 64 * 64
+    out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    pre = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    with _timed('hfl_linear_x6', m * k * 4 + m * n * 8, 2 * m * k * n):
+        check(_native.load().hfl_linear_x6_gelu_fwd(out.data_ptr(), pre.data_ptr(), xc.data_ptr(), w3.data_ptr(),
+                                                    None if bias is None else _f32c(bias).data_ptr(), m, k, n, _stream()),
+              'hfl_linear_x6_gelu_fwd')
+    return out, pre
+
+
+def linear_x6_gelu_bwd(dy: torch.Tensor, wt3: torch.Tensor, preact: torch.Tensor) -> torch.Tensor:
+    """(dy W) * gelu'(preact) (hfl_linear_x6_gelu_bwd): wt3 = x6_pack(W^T), preact (rows, wt3.shape[1]) f32."""
+    _dev(dy, wt3, preact)
+    assert wt3.dtype == torch.bfloat16 and wt3.is_contiguous() and wt3.dim() == 3 and wt3.shape[0] == 3
+    dyc, pre = _f32c(dy), _f32c(preact)
+    m, k = dyc.shape
+    n = wt3.shape[1]
+    assert wt3.shape[2] == (k + 63) // 64 * 64 and tuple(pre.shape) == (m, n)
+    out = torch.empty((m, n), dtype=torch.float32, device=dy.device)
+    with _timed('hfl_linear_x6', m * k * 4 + m * n * 8, 2 * m * k * n):
+        check(_native.load().hfl_linear_x6_gelu_bwd(out.data_ptr(), dyc.data_ptr(), wt3.data_ptr(), pre.data_ptr(), m, k, n,
+                                                    _stream()), 'hfl_linear_x6_gelu_bwd')
+    return out
+
+
 def linear_x6_grouped_gather(x: torch.Tensor, src: torch.Tensor, w3: torch.Tensor, tiles: torch.Tensor,
                              out_features: int) -> torch.Tensor:
     """The per-tap products of an octree convolution over its live (row, tap) pairs at matched precision: row m of the
@@ -773,6 +806,32 @@ def wgrad_x3(dy2: torch.Tensor, x2: torch.Tensor, with_bias: bool = False):
     with _timed('hfl_wgrad_x3', m * (n + k) * 4, 2 * m * n * k):
         check(lib.hfl_wgrad_x3(dw.data_ptr(), None if db is None else db.data_ptr(), dy2.data_ptr(), x2.data_ptr(),
                                m, n, k, ws.data_ptr(), _stream()), 'hfl_wgrad_x3')
+    return dw, db
+
+
+def wgrad_f32(dy: torch.Tensor, x: torch.Tensor, with_bias: bool = False):
+    """(dW, db) of y = x W^T + b from f32 rows on the fp32 matrix cores: dW (N, K) = dy^T x, db (N) = dy summed over rows
+    (hfl_wgrad_f32; fixed reduction order, bitwise reproducible).  dy (M, N), x (M, K), N and K multiples of 128."""
+    _dev(dy, x)
+    dyc, xc = _f32c(dy), _f32c(x)
+    m, n = dyc.shape
+    k = xc.shape[1]
+    assert xc.shape[0] == m
+    dw = torch.empty((n, k), dtype=torch.float32, device=dy.device)
+    db = torch.empty(n, dtype=torch.float32, device=dy.device) if with_bias else None
+    if m == 0:
+        dw.zero_()
+        if db is not None:
+            db.zero_()
+        return dw, db
+    lib = _native.load()
+    nbytes = int(lib.hfl_wgrad_f32_workspace(m, n, k))
+    if nbytes <= 0:
+        raise _native.NativeLibraryError('hfl_wgrad_f32: unsupported shape (%d, %d, %d)' % (m, n, k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    with _timed('hfl_wgrad_f32', m * (n + k) * 4, 2 * m * n * k):
+        check(lib.hfl_wgrad_f32(dw.data_ptr(), None if db is None else db.data_ptr(), dyc.data_ptr(), xc.data_ptr(),
+                                m, n, k, ws.data_ptr(), _stream()), 'hfl_wgrad_f32')
     return dw, db
 
 

@@ -463,6 +463,14 @@ int hfl_linear_x3_gelu_bwd(uint16_t* out_split2, const uint16_t* dy_split2, cons
 int64_t hfl_wgrad_x3_workspace(int64_t n_rows, int64_t out_features, int64_t in_features);
 int hfl_wgrad_x3(float* dw, float* db, const uint16_t* dy_split2, const uint16_t* x_split2, int64_t n_rows,
                  int64_t out_features, int64_t in_features, void* workspace, hfl_stream_t stream);
+/* The same weight and bias gradient from f32 operands on the fp32 matrix cores (csrc/wgrad_f32.hip): dw (N,K) = dy^T x,
+ * db (N) = column sums of dy, dy (n_rows, N) and x (n_rows, K) f32 row-major, every product one f32 FMA
+ * (v_mfma_f32_16x16x4_f32, the reference's arithmetic), slabs of rows reduced in a fixed order (bitwise reproducible).  The
+ * weight gradient of the matched-precision training path (GEMM mode x6).  N % 128 == 0, K % 128 == 0; db may be NULL;
+ * workspace >= hfl_wgrad_f32_workspace(n_rows, N, K) bytes. */
+int64_t hfl_wgrad_f32_workspace(int64_t n_rows, int64_t out_features, int64_t in_features);
+int hfl_wgrad_f32(float* dw, float* db, const float* dy, const float* x, int64_t n_rows, int64_t out_features,
+                  int64_t in_features, void* workspace, hfl_stream_t stream);
 /* The qkv projection written straight into the operand layout of the fp16-MFMA window attention kernel
  * (hfl_window_attention_fwd_ex with flag 0x100): out (n_rows, out_features) 4-byte cells, every row = [Q | K | V] regions
  * of C = out_features / 3 features, per head 16 dims stored as [16 x hi | 16 x lo] fp16 (hi = RTZ(v), lo = RTZ(v - hi):
@@ -494,6 +502,16 @@ int64_t hfl_linear_x6_padded_k(int64_t in_features);
 int hfl_linear_x6_pack(uint16_t* w3, const float* w, int64_t out_features, int64_t in_features, hfl_stream_t stream);
 int hfl_linear_x6(float* out, const float* x, const uint16_t* w3, const float* bias, const float* residual,
                   const float* row_scale, int64_t n_rows, int in_features, int out_features, int gelu, hfl_stream_t stream);
+/* Training forms of hfl_linear_x6 for the MLP (models/layers/octformer_layers.py:53-59 under autograd), the counterparts of
+ * hfl_linear_x3_gelu_fwd / _bwd with f32 rows in and out:
+ *   _gelu_fwd: out = gelu(x W^T + bias) AND preact = x W^T + bias (n_rows, out_features) in one launch; out is bitwise
+ *              hfl_linear_x6(..., gelu = 1), preact bitwise hfl_linear_x6(..., gelu = 0);
+ *   _gelu_bwd: out = (dy W) * gelu'(preact): the input gradient of fc2 times the GELU derivative; wt3 = hfl_linear_x6_pack of
+ *              W^T (in_features = fc2's out_features, out_features = fc2's in_features), preact (n_rows, out_features). */
+int hfl_linear_x6_gelu_fwd(float* out, float* preact, const float* x, const uint16_t* w3, const float* bias, int64_t n_rows,
+                           int in_features, int out_features, hfl_stream_t stream);
+int hfl_linear_x6_gelu_bwd(float* out, const float* dy, const uint16_t* wt3, const float* preact, int64_t n_rows,
+                           int in_features, int out_features, hfl_stream_t stream);
 
 /* Grouped form of hfl_linear_x6 with the gather done by the tile loader: the per-tap products of an octree convolution over
  * its live (row, tap) pairs (models/layers/octformer_layers.py:89-95: ocnn's octree2col + mm) at matched precision -- the
