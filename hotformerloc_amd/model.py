@@ -410,7 +410,8 @@ def arm_drop_paths(model: nn.Module, batch_size: int, device, dtype=torch.float3
     """Draw the per-cloud stochastic-depth factors of every active `OctreeDropPath` of `model` for one forward in three
     launches (rand, floor, div over an (instances x 2, B) matrix) and hand each instance its two rows.  Same distribution as
     the reference's per-call draws (models/layers/octformer_layers.py:213-289: independent Bernoulli(keep) per call and
-    cloud); the draws themselves cannot match the reference's RNG stream either way."""
+    cloud).  The draws do not follow the reference's RNG stream; tests/test_gpu_train_drop_path.py replaces this function to
+    replay the draws recorded from the reference (tests/golden/train_*.npz) and so checks stochastic depth against it."""
     cache = model.__dict__.get('_drop_path_cache')
     if cache is None:
         cache = model.__dict__['_drop_path_cache'] = {'mods': [m for m in model.modules() if isinstance(m, OctreeDropPath)]}
@@ -448,9 +449,13 @@ class OctreeDropPath(nn.Module):
     _calls = 0
 
     def _draw(self, batch_size: int, dtype, device):
-        """(B,) per-cloud factor of one call: 0 or 1 / keep."""
+        """(B,) per-cloud factor of one call: 0 or 1 / keep.  Armed factors that do not fit the call are an error: drawing
+        fresh ones instead would silently give the two calls of a recomputation different draws."""
         f = self._factors
-        if f is not None and f.shape[1] == batch_size and f.device == device and f.dtype == dtype:
+        if f is not None:
+            if f.dim() != 2 or f.shape[1] != batch_size or f.device != device or f.dtype != dtype:
+                raise RuntimeError('OctreeDropPath: armed factors %s %s on %s do not match a call with batch %d, %s on %s'
+                                   % (tuple(f.shape), f.dtype, f.device, batch_size, dtype, device))
             r = f[self._calls % f.shape[0]]
             self._calls += 1
             return r

@@ -237,7 +237,17 @@ def window_attention(x, sd, p, mask, rel_pos, H, K, G, dilation):
     return _linear(out, sd, p + '.proj')
 
 
-def octformer_block(x, sd, p, plan, depth, H, dilation):
+def _drop(branch, factors, p, call, cloud):
+    """Stochastic depth (models/layers/octformer_layers.py:213-289) with recorded draws: `factors[p + '.drop_path']` is the
+    block's (2, B) per-cloud factor (row 0 = attention branch, row 1 = MLP branch), `cloud` the cloud of every row of
+    `branch` (leading dims), padding rows already clamped to the last cloud.  No factors: identity (eval)."""
+    f = None if factors is None else factors.get(p + '.drop_path')
+    if f is None:
+        return branch
+    return branch * f[call].to(branch.dtype)[cloud].unsqueeze(-1)
+
+
+def octformer_block(x, sd, p, plan, depth, H, dilation, factors=None):
     """models/octformer_backbone.py:251-299 (use_rt=False)."""
     K = plan.K
     dil = dilation > 1
@@ -245,26 +255,35 @@ def octformer_block(x, sd, p, plan, depth, H, dilation):
     x = plan.to_windows(x, depth, dil)
     mask = plan.dilate_mask[depth] if dil else plan.patch_mask[depth]
     pos = plan.dilate_pos[depth] if dil else plan.rel_pos[depth]
-    x = x + window_attention(_ln(x, sd, p + '.norm1'), sd, p + '.attention', mask, pos,
-                             H, K, 0, dilation)
-    x = x + _mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp')
+    # every token row its own cloud, padding rows the last cloud, in the (dilated) window layout
+    cloud = plan.batch_idx[depth].clamp(max=plan.B - 1)
+    if dil:
+        cloud = cloud.view(-1, K, plan.D).transpose(1, 2)
+    cloud = cloud.reshape(-1, K)
+    x = x + _drop(window_attention(_ln(x, sd, p + '.norm1'), sd, p + '.attention', mask, pos,
+                                   H, K, 0, dilation), factors, p, 0, cloud)
+    x = x + _drop(_mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp'), factors, p, 1, cloud)
     return plan.from_windows(x, depth, dil)
 
 
-def hosa_block(x, rt, sd, p, plan, depth, H):
+def hosa_block(x, rt, sd, p, plan, depth, H, factors=None):
     """models/hotformerloc_backbone.py:197-236 (rt_propagation off)."""
     K = plan.K
     x = x + cpe(x, sd, p + '.cpe', plan.octree, depth)
     x = plan.to_windows(x, depth, False)
     x = torch.cat([rt.unsqueeze(1), x], 1)
-    x = x + window_attention(_ln(x, sd, p + '.norm1'), sd, p + '.attention',
-                             plan.hat_mask[depth], plan.rel_pos[depth], H, K, 1, 1)
-    x = x + _mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp')
+    # relay row: its window's owner (the smallest cloud id = that of the first token); tokens their own cloud; padding
+    # rows (and all-padding windows' relay rows) the last cloud (models/octree.py:130-153)
+    w = plan.batch_idx[depth].view(-1, K)
+    cloud = torch.cat([plan.rt_batch_idx[depth].unsqueeze(1), w], 1).clamp(max=plan.B - 1)
+    x = x + _drop(window_attention(_ln(x, sd, p + '.norm1'), sd, p + '.attention',
+                                   plan.hat_mask[depth], plan.rel_pos[depth], H, K, 1, 1), factors, p, 0, cloud)
+    x = x + _drop(_mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp'), factors, p, 1, cloud)
     rt, x = x[:, 0], x[:, 1:]
     return plan.from_windows(x, depth, False), rt
 
 
-def rtsa_block(rts: Dict[int, torch.Tensor], sd, p, plan, H):
+def rtsa_block(rts: Dict[int, torch.Tensor], sd, p, plan, H, factors=None):
     """models/hotformerloc_backbone.py:275-295,83-119; relay_token_utils.py:12-79."""
     depths = plan.pyramid_depths
     B = plan.B
@@ -276,8 +295,9 @@ def rtsa_block(rts: Dict[int, torch.Tensor], sd, p, plan, H):
     qkv = _linear(h, sd, p + '.rt_attention.qkv').reshape(B, -1, 3, H, C // H).permute(2, 0, 3, 1, 4)
     a = _sdpa(qkv[0], qkv[1], qkv[2], plan.rt_attn_mask.unsqueeze(1), (C // H) ** -0.5)
     a = a.transpose(1, 2).reshape(B, -1, C)
-    x = x + _linear(a, sd, p + '.rt_attention.proj')
-    x = x + _mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp')
+    cloud = torch.arange(B).unsqueeze(1).expand(B, x.shape[1])     # padded (B, N) layout: row b is cloud b
+    x = x + _drop(_linear(a, sd, p + '.rt_attention.proj'), factors, p, 0, cloud)
+    x = x + _drop(_mlp(_ln(x, sd, p + '.norm2'), sd, p + '.mlp'), factors, p, 1, cloud)
     out = {d: [] for d in depths}
     for b in range(B):
         seq = x[b, :int(plan.rt_counts[b])]
@@ -324,13 +344,18 @@ def pyramid_attn_pool_mixer(feats: Dict[int, torch.Tensor], sd, p, plan, k_token
 
 
 # ---------------------------------------------------------------------- forward
-def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Optional[dict] = None):
+def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Optional[dict] = None,
+                      drop_factors: Optional[Dict[str, torch.Tensor]] = None):
     """models/hotformerloc.py:33-59 -> hotformerloc_backbone.py:702-723,574-635.
 
-    sd:      state_dict (CPU fp32) with the reference's key names
+    sd:      state_dict (CPU, fp32 or fp64: the whole forward runs in its dtype) with the reference's key names
+             
     params:  object with the reference `ModelParams` fields (misc/utils.py:15-115)
     octree:  merged `oracle.ocnn_ref.Octree` with `construct_all_neigh()` done
     capture: optional dict that receives named intermediates
+    drop_factors: optional train-mode stochastic depth with recorded draws: reference drop-path module name
+             (`<block>.drop_path`) -> (2, B) per-cloud factors, row 0 for the attention branch, row 1 for the MLP branch
+             (tests/golden/train_*.npz); blocks without an entry are identity, as in eval
     """
     cap = capture if capture is not None else {}
     depth = octree.depth
@@ -342,7 +367,8 @@ def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Opti
     bb = 'backbone.backbone'
 
     # input feature 'P' (hotformerloc.py:28-31)
-    x = octree.points[depth] * (2 ** (1 - depth)) - 1.0
+    dtype = sd[bb + '.patch_embed.proj.conv.weights'].dtype
+    x = (octree.points[depth] * (2 ** (1 - depth)) - 1.0).to(dtype)
     cap['input_feature'] = x
 
     # patch embed (octformer_backbone.py:451-461)
@@ -361,7 +387,7 @@ def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Opti
     for s in range(noctf):
         for i in range(params.num_blocks[s]):
             x = octformer_block(x, sd, '%s.octf_stage.%d.blocks.%d' % (bb, s, i), plan, depth,
-                                heads[s], 1 if i % 2 == 0 else dil)
+                                heads[s], 1 if i % 2 == 0 else dil, drop_factors)
             cap['octf.%d.%d' % (s, i)] = x
         x = downsample(x, sd, '%s.downsample.%d' % (bb, s), octree, depth)
         depth -= 1
@@ -376,7 +402,7 @@ def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Opti
         rts[d] = relay_token_init(feats[d], sd, hs + '.relay_tokeniser', plan, d,
                                   use_cpe=(adape is None))
         if adape is not None:
-            rts[d] = rts[d] + _mlp(plan.window_stats[d], sd, hs + '.rt_adape.mlp')
+            rts[d] = rts[d] + _mlp(plan.window_stats[d].to(dtype), sd, hs + '.rt_adape.mlp')
         if j < nlev - 1:
             feats[d - 1] = downsample(feats[d], sd, '%s.downsamples.%d' % (hs, j), octree, d)
     for d in depths:
@@ -385,10 +411,10 @@ def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Opti
 
     # 10 x [RTSA ; 3 x H-OSA] (hotformerloc_backbone.py:593-633)
     for i in range(params.num_blocks[-1]):
-        rts = rtsa_block(rts, sd, '%s.rtsa_blocks.%d' % (hs, i), plan, H)
+        rts = rtsa_block(rts, sd, '%s.rtsa_blocks.%d' % (hs, i), plan, H, drop_factors)
         for j, d in enumerate(depths):
             feats[d], rts[d] = hosa_block(feats[d], rts[d], sd,
-                                          '%s.hosa_blocks.%d.%d' % (hs, j, i), plan, d, H)
+                                          '%s.hosa_blocks.%d.%d' % (hs, j, i), plan, d, H, drop_factors)
         if i == 0:
             for d in depths:
                 cap['feat_iter0.%d' % d] = feats[d]
@@ -405,6 +431,7 @@ def forward_with_grad(sd: Dict[str, torch.Tensor], params, octree, capture: Opti
 
 
 @torch.no_grad()
-def forward(sd: Dict[str, torch.Tensor], params, octree, capture: Optional[dict] = None):
+def forward(sd: Dict[str, torch.Tensor], params, octree, capture: Optional[dict] = None,
+            drop_factors: Optional[Dict[str, torch.Tensor]] = None):
     """Inference forward (no autograd graph); see :func:`forward_with_grad` for the body."""
-    return forward_with_grad(sd, params, octree, capture)
+    return forward_with_grad(sd, params, octree, capture, drop_factors)

@@ -50,3 +50,58 @@ def state_dict_spec(params) -> Dict[str, tuple]:
 def synthetic_state_dict(params, profile: str = 'stress') -> Dict[str, torch.Tensor]:
     return {k: torch.from_numpy(syn.synthetic_tensor(k, s, profile))
             for k, s in state_dict_spec(params).items()}
+
+
+# ------------------------------------------------------------- gradient sketches
+# A parameter gradient is stored in a fixture as a sketch that any side can recompute from the full tensor: its L2 norm,
+# SKETCH_ENTRIES strided entries and SKETCH_PROJ projections onto +-1 vectors derived from `synthetic.hash_uniform`
+# (oracle/gen_golden_train.py).
+SKETCH_ENTRIES = 64
+SKETCH_PROJ = 16
+_SIGNS = {}
+
+
+def _sketch_signs(n: int) -> np.ndarray:
+    if n not in _SIGNS:
+        _SIGNS[n] = np.stack([np.where(syn.hash_uniform(7100 + j, n) >= 0.0, 1.0, -1.0) for j in range(SKETCH_PROJ)])
+    return _SIGNS[n]
+
+
+def sketch_index(n: int) -> np.ndarray:
+    return (np.arange(SKETCH_ENTRIES, dtype=np.int64) * n) // SKETCH_ENTRIES
+
+
+def grad_sketch(g):
+    """(norm, entries (SKETCH_ENTRIES,), projections (SKETCH_PROJ,)) of a gradient, in float64."""
+    g = np.asarray(g, dtype=np.float64).reshape(-1)
+    return float(np.linalg.norm(g)), g[sketch_index(g.size)], _sketch_signs(g.size) @ g
+
+
+def sketch_error(got, norm, entries, proj, numel: int) -> float:
+    """Relative error of a gradient sketch against a reference sketch, on the scale of the reference's rel-L2: the worst of
+    the norm's relative difference, the projections' relative L2 difference (a +-1 projection preserves the L2 norm in
+    expectation) and the strided entries' L2 difference over their expected L2 norm (norm * sqrt(64 / n))."""
+    n_g, e_g, p_g = got
+    n = max(norm, 1e-300)
+    scale = n * np.sqrt(len(entries) / numel)
+    return float(max(abs(n_g - norm) / n,
+                     np.linalg.norm(p_g - proj) / max(np.linalg.norm(proj), 1e-300),
+                     np.linalg.norm(e_g - entries) / scale))
+
+
+def load_train_case(golden_dir: str, case: str) -> dict:
+    """tests/golden/<case>.npz of oracle/gen_golden_train.py, with `clouds` (list of float32 arrays) and `factors` as a
+    {reference module name: (2, B) float64} dict."""
+    z = np.load(os.path.join(golden_dir, '%s.npz' % case))
+    g = {k: z[k] for k in z.files}
+    g['cfg'] = _NAME[str(g['cfg'])]
+    g['octree_depth'] = int(g['octree_depth'])
+    g['profile'] = str(g['profile'])
+    src = str(g['points_case'])
+    pts = np.load(os.path.join(golden_dir, 'model_%s.npz' % src))['points'] if src else g['points']
+    offs = np.concatenate([[0], np.cumsum(g['n_points'])])
+    assert offs[-1] == pts.shape[0], (case, offs[-1], pts.shape)
+    g['clouds'] = [pts[offs[i]:offs[i + 1]] for i in range(len(g['n_points']))]
+    g['factor_dict'] = {str(n): g['factors'][i] for i, n in enumerate(g['factor_names'])}
+    g['grad_names'] = [str(n) for n in g['grad_names']]
+    return g

@@ -208,7 +208,8 @@ _ORACLE_GRADS = {}
                                               ('cs-wild-places', [2000, 1400], 'bf16x3-lt')])
 def test_forward_backward_matches_oracle_autograd(cfg, sizes, linear):
     """BASELINE config 3 (fwd+bwd): parameter gradients of the HIP training path against torch
-    autograd through the CPU oracle, drop_path = 0 (stochastic depth is RNG-dependent)."""
+    autograd through the CPU oracle, drop_path = 0.  Stochastic depth is checked against the reference with its recorded
+    draws in tests/test_gpu_train_drop_path.py."""
     params, depth = load_config(cfg)
     clouds = [syn.forest_cloud(1400 + i, n) if i % 2 else syn.unit_ball_cloud(1400 + i, n)
               for i, n in enumerate(sizes)]
@@ -222,7 +223,7 @@ def test_forward_backward_matches_oracle_autograd(cfg, sizes, linear):
         (y_ref * proj).sum().backward()
         _ORACLE_GRADS[key] = (y_ref.detach(), {k: v.grad for k, v in sd.items()})
     y_ref, grads_ref = _ORACLE_GRADS[key]
-    params.drop_path = 0.0                       # stochastic depth off: RNG parity is impossible
+    params.drop_path = 0.0                       # stochastic depth off (its own test replays the reference's draws)
     model = model_factory(params)
     syn.fill_synthetic_weights(model, 'stress')
     model = model.cuda().train()

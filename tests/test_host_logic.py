@@ -277,3 +277,22 @@ def test_ctypes_structures_match_the_c_header(tmp_path):
         assert n_c == len(cls._fields_)
         for fname, _ in cls._fields_:
             assert got[cname, fname] == getattr(cls, fname).offset, (cname, fname)
+
+
+def test_drop_path_replays_armed_factors_and_rejects_mismatched_ones():
+    """`OctreeDropPath._draw` hands out the armed rows in order (attention, MLP, then again for a recomputation) and raises
+    when the armed factors do not fit the call, instead of silently drawing fresh ones."""
+    from hotformerloc_amd.model import OctreeDropPath
+    dp = OctreeDropPath(0.5).train()
+    dp._factors = torch.tensor([[0.0, 2.0, 2.0], [2.0, 0.0, 2.0]])
+    assert torch.equal(dp._draw(3, torch.float32, torch.device('cpu')), dp._factors[0])
+    assert torch.equal(dp._draw(3, torch.float32, torch.device('cpu')), dp._factors[1])
+    assert torch.equal(dp._draw(3, torch.float32, torch.device('cpu')), dp._factors[0])
+    bid = torch.tensor([0, 0, 1, 2, 2])
+    dp._calls = 0
+    assert torch.equal(dp.row_scale(bid, 3, torch.empty(0)), torch.tensor([0.0, 0.0, 2.0, 2.0, 2.0]))
+    for batch, dtype in ((4, torch.float32), (3, torch.float64)):
+        with pytest.raises(RuntimeError, match='armed factors'):
+            dp._draw(batch, dtype, torch.device('cpu'))
+    dp._factors = None
+    assert dp._draw(3, torch.float32, torch.device('cpu')).shape == (3,)

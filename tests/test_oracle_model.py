@@ -81,3 +81,34 @@ def test_oracle_matches_reference_live(golden_dir):
     y = hotformer_ref.forward(sd, params, octree).numpy()
     rel = np.linalg.norm(y - ref, axis=1) / np.linalg.norm(ref, axis=1)
     assert rel.max() < 2e-5
+
+
+@pytest.mark.parametrize('case', ['train_wild_places_ragged', 'train_cs_wild_places_ragged'])
+def test_oracle_training_gradients_match_reference_with_stochastic_depth(golden_dir, case):
+    """The oracle's train-mode forward AND backward against the reference's own autograd: fp64 on both sides, stochastic
+    depth on with the per-cloud draws the reference made (oracle/gen_golden_train.py -> tests/golden/train_*.npz).  Pins
+    the row-to-cloud rules of the drop paths (tokens their own cloud, relay rows their window's owner, padding the last
+    cloud, the relay-token block by padded row) and every parameter gradient, through its sketch, within 1e-8."""
+    from oracle.testing import grad_sketch, load_train_case, sketch_error
+    g = load_train_case(golden_dir, case)
+    params, depth = load_config(g['cfg'])
+    assert depth == g['octree_depth']
+    octree = oracle_octree(g['clouds'], depth)
+    assert np.array_equal(octree.nnum_nempty.numpy(), g['nnum_nempty'])
+    B = len(g['clouds'])
+    sd = {k: v.double().requires_grad_() for k, v in synthetic_state_dict(params, g['profile']).items()}
+    factors = {k: torch.from_numpy(v) for k, v in g['factor_dict'].items()}
+    y = hotformer_ref.forward_with_grad(sd, params, octree, drop_factors=factors)
+    proj = torch.from_numpy(syn.hash_uniform(4242, B * 256).reshape(B, 256))
+    (y * proj).sum().backward()
+    ref = g['desc64']
+    rel = np.linalg.norm(y.detach().numpy() - ref, axis=1) / np.linalg.norm(ref, axis=1)
+    assert rel.max() <= 1e-8, rel
+    assert sorted(sd) == sorted(g['grad_names']), set(sd) ^ set(g['grad_names'])
+    errs = {}
+    for i, name in enumerate(g['grad_names']):
+        got = grad_sketch(sd[name].grad.numpy())
+        errs[name] = sketch_error(got, g['grad_norm'][i], g['grad_entries'][i], g['grad_proj'][i], int(g['grad_numel'][i]))
+    worst = max(errs, key=errs.get)
+    print(case, 'descriptor rel', rel.max(), 'worst gradient sketch error', worst, errs[worst])
+    assert errs[worst] <= 1e-8, (worst, errs[worst])
