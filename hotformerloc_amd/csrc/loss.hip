@@ -85,6 +85,71 @@ smoothap_rows_kernel(float* __restrict__ ap, float* __restrict__ dap_ds, const f
   for (int z = threadIdx.x; z < B; z += blockDim.x) dap_ds[(int64_t)q * B + z] = s_g[z];
 }
 
+
+// Distillation term of the MESA step (models/losses/loss.py:138-147): per row, with p = softmax(y / T) and q = softmax(t / T),
+//     kl = sum_j q_j (log q_j - log p_j),      d kl / d y_j = (p_j - q_j) / T.
+// One wavefront owns one row, K = D / 64 elements per lane in registers.  Student and teacher rows are nearly equal (the
+// teacher is a moving average of the student), so kl is a small difference of nearly equal numbers; it is therefore built
+// from the per-element log ratio of the max-subtracted exponentials
+//     delta_j = b_j - a_j,  a_j = (y_j - max y) / T,  b_j = (t_j - max t) / T,   exp(a_j) - exp(b_j) = exp(b_j) expm1(-delta_j)
+//     kl = sum_j q_j delta_j + c,   c = log(Zp / Zq) = log1p(sum_j (exp(a_j) - exp(b_j)) / Zq),
+//     p_j - q_j = q_j expm1(-(delta_j + c)),
+// and not from two log-sum-exps of about log D each.  Where the rows differ grossly (|delta| >= 1) the plain differences are
+// exact enough and cannot overflow.
+template <int K>
+__global__ void __launch_bounds__(256)
+kd_rows_kernel(float* __restrict__ kl, float* __restrict__ dkl, const float* __restrict__ Y, const float* __restrict__ Tt,
+               int B, float inv_t) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= B) return;                                      // whole wavefront leaves: no partial shuffles
+  const int64_t base = (int64_t)row * (K * 64);
+  float y[K], t[K];
+  float my = -INFINITY, mt = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    y[i] = Y[base + i * 64 + lane];
+    t[i] = Tt[base + i * 64 + lane];
+    my = fmaxf(my, y[i]);
+    mt = fmaxf(mt, t[i]);
+  }
+  my = hfl_group_max<64>(my);
+  mt = hfl_group_max<64>(mt);
+  const float dm = mt - my;
+  float zq = 0.f, s_diff = 0.f, s_qd = 0.f;
+  float eq[K], dl[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const float a = (y[i] - my) * inv_t, b = (t[i] - mt) * inv_t;
+    const float d = ((t[i] - y[i]) - dm) * inv_t;           // b - a, from the two small differences
+    const float e = expf(b);
+    eq[i] = e;
+    dl[i] = d;
+    zq += e;
+    s_diff += fabsf(d) < 1.f ? e * expm1f(-d) : expf(a) - e;
+    s_qd += e * d;                                           // e == 0 (underflow) times a finite d: 0
+  }
+  zq = hfl_group_sum<64>(zq);
+  s_diff = hfl_group_sum<64>(s_diff);
+  s_qd = hfl_group_sum<64>(s_qd);
+  const float x = s_diff / zq;                               // Zp / Zq - 1  (> -1)
+  const float c = x > -0.5f ? log1pf(x) : logf(1.f + x);
+  if (lane == 0) kl[row] = s_qd / zq + c;
+  const float inv_zq = 1.f / zq, inv_zp = 1.f / (zq + s_diff);
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const float q = eq[i] * inv_zq;
+    const float u = dl[i] + c;                               // log(q_j / p_j)
+    const float g = fabsf(u) < 1.f ? q * expm1f(-u) : expf((y[i] - my) * inv_t) * inv_zp - q;
+    dkl[base + i * 64 + lane] = g * inv_t;
+  }
+}
+
+template <int K>
+static void kd_launch(float* kl, float* dkl, const float* y, const float* t, int B, float inv_t, hipStream_t st) {
+  kd_rows_kernel<K><<<(B + 3) / 4, 256, 0, st>>>(kl, dkl, y, t, B, inv_t);
+}
+
 }  // namespace
 
 extern "C" int hfl_smoothap_rows(float* ap, float* dap_ds, const float* sim, const uint8_t* pos_mask,
@@ -100,5 +165,21 @@ extern "C" int hfl_smoothap_rows(float* ap, float* dap_ds, const float* sim, con
   }
   smoothap_rows_kernel<<<batch, 256, lds, static_cast<hipStream_t>(stream)>>>(
       ap, dap_ds, sim, pos_mask, neg_mask, closest_pos, batch, positives_per_query, tau);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_kd_rows(float* kl, float* dkl_dy, const float* y, const float* t, int batch, int dim, float temperature,
+                            hfl_stream_t stream) {
+  if (batch <= 0 || dim <= 0 || dim % 64 != 0 || dim > 1024 || !(temperature > 0.f)) return HFL_EINVAL;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const float inv_t = 1.0f / temperature;
+  switch (dim / 64) {
+#define HFL_KD_CASE(K) case K: kd_launch<K>(kl, dkl_dy, y, t, batch, inv_t, st); break;
+    HFL_KD_CASE(1) HFL_KD_CASE(2) HFL_KD_CASE(3) HFL_KD_CASE(4) HFL_KD_CASE(5) HFL_KD_CASE(6) HFL_KD_CASE(7) HFL_KD_CASE(8)
+    HFL_KD_CASE(9) HFL_KD_CASE(10) HFL_KD_CASE(11) HFL_KD_CASE(12) HFL_KD_CASE(13) HFL_KD_CASE(14) HFL_KD_CASE(15)
+    HFL_KD_CASE(16)
+#undef HFL_KD_CASE
+    default: return HFL_EINVAL;
+  }
   HFL_RETURN_LAST_ERROR();
 }

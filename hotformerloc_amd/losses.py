@@ -4,7 +4,10 @@
 signature `(embeddings, positives_mask, negatives_mask) -> (loss, stats)`, same `stats` keys.
 
 The (B, P, B) ranking algebra and its gradient run in one HIP kernel per call (`hfl_smoothap_rows`);
-the affinity matrix, the top-k selection of positives and dE = (dS + dS^T) E are dense torch ops."""
+the affinity matrix, the top-k selection of positives and dE = (dS + dS^T) E are dense torch ops.
+
+`kdloss` is the distillation term of the reference's MESA step (`models/losses/loss.py:138-147`): KL rows and their gradient in
+one HIP launch (`hfl_kd_rows`)."""
 
 import numpy as np
 import torch
@@ -68,3 +71,28 @@ class TruncatedSmoothAP:
                      'loss': loss.item(), 'ap': ap.item(),
                      'avg_embedding_norm': embeddings.norm(dim=1).mean().item()}
         return loss, stats
+
+
+class _KdRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, teacher, temperature):
+        kl, dkl = ops.kd_rows(y, teacher, temperature)
+        ctx.save_for_backward(dkl)
+        return kl
+
+    @staticmethod
+    def backward(ctx, grad_kl):
+        (dkl,) = ctx.saved_tensors
+        return dkl * grad_kl[:, None], None, None
+
+
+def kdloss(y, teacher_scores, T: float = 3.0, weight: float = 50.0):
+    """`weight * KLDivLoss(reduction='batchmean')(log_softmax(y / T), softmax(teacher_scores / T))`: the reference's
+    `kdloss(y, teacher_scores)` with its constants T = 3 and 50 as defaults.  y, teacher_scores: (B, D) fp32 rows on the GPU,
+    D a multiple of 64 up to 1024.  The gradient flows to `y` only; a teacher that requires grad is an error (detach it)."""
+    if teacher_scores.requires_grad:
+        raise ValueError('kdloss: the teacher rows must not require grad (the teacher receives no gradient); detach them')
+    if y.device.type != 'cuda':
+        raise _native.NativeLibraryError('kdloss runs on the GPU only (no CPU fallback)')
+    rows = _KdRows.apply(y.float().contiguous(), teacher_scores.float().contiguous(), float(T))
+    return weight * rows.sum() / y.shape[0]

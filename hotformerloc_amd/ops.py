@@ -1348,3 +1348,67 @@ def octree_neigh(neigh_parent, nidx, children, nkeys, depth: int, full_depth: in
         out.data_ptr(), None if neigh_parent is None else neigh_parent.data_ptr(), nidx.data_ptr(),
         children.data_ptr(), nkeys.data_ptr(), nne, depth, full_depth, _stream()), 'hfl_octree_neigh')
     return out
+
+
+# --------------------------------------------------------------------------- MESA: weight EMA and distillation rows
+EMA_CHUNK = 8192          # HFL_EMA_CHUNK of include/hotformerloc_hip.h
+
+
+def ema_table(ema_tensors, src_tensors):
+    """Device table of `hfl_ema_chunk` entries for `ema_update`: every (ema, src) pair of fp32 tensors cut into chunks of at
+    most EMA_CHUNK elements.  Returns (table, n_chunks); the table holds raw pointers, so it is valid only while every
+    tensor keeps its `data_ptr()` (the caller revalidates).  A tensor that appears twice (tied weights) is taken once."""
+    import numpy as np
+    ema_tensors, src_tensors = list(ema_tensors), list(src_tensors)
+    if len(ema_tensors) != len(src_tensors):
+        raise ValueError('ema_table: %d ema tensors, %d source tensors' % (len(ema_tensors), len(src_tensors)))
+    _dev(*ema_tensors, *src_tensors)
+    rows, seen = [], set()
+    for e, s in zip(ema_tensors, src_tensors):
+        if e.dtype != torch.float32 or s.dtype != torch.float32:
+            raise TypeError('ema_update takes float32 tensors, got %s and %s' % (e.dtype, s.dtype))
+        if e.shape != s.shape:
+            raise ValueError('ema_update: shapes %s and %s differ' % (tuple(e.shape), tuple(s.shape)))
+        if not (e.is_contiguous() and s.is_contiguous()):
+            raise ValueError('ema_update needs contiguous tensors')
+        n = e.numel()
+        if n == 0 or e.data_ptr() in seen:
+            continue
+        seen.add(e.data_ptr())
+        off = np.arange(0, n, EMA_CHUNK, dtype=np.int64)
+        chunk = np.empty((off.shape[0], 3), dtype=np.int64)
+        chunk[:, 0] = e.data_ptr() + 4 * off
+        chunk[:, 1] = s.data_ptr() + 4 * off
+        chunk[:, 2] = np.minimum(n - off, EMA_CHUNK)
+        rows.append(chunk)
+    if not rows:
+        return None, 0
+    table = np.concatenate(rows, 0)
+    return torch.from_numpy(table).to(ema_tensors[0].device), int(table.shape[0])
+
+
+def ema_update(table, n_chunks: int, w: float):
+    """ema <- ema + w * (src - ema) over every chunk of an `ema_table`, one launch."""
+    if n_chunks == 0:
+        return
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and tuple(table.shape) == (n_chunks, 3)
+    check(_native.load().hfl_ema_update(table.data_ptr(), n_chunks, float(w), _stream()), 'hfl_ema_update')
+
+
+def kd_rows(y: torch.Tensor, t: torch.Tensor, temperature: float):
+    """Per row: KL(softmax(t / T) || softmax(y / T)) and its derivative (p - q) / T with respect to y.  y, t: (B, D) fp32,
+    D a multiple of 64 up to 1024.  Returns (kl (B,), dkl_dy (B, D))."""
+    _dev(y, t)
+    if y.dim() != 2 or y.shape != t.shape:
+        raise ValueError('kd_rows: (B, D) student and teacher rows of one shape expected, got %s and %s'
+                         % (tuple(y.shape), tuple(t.shape)))
+    y, t = _f32c(y), _f32c(t)
+    b, d = y.shape
+    kl = torch.empty(b, dtype=torch.float32, device=y.device)
+    dkl = torch.empty((b, d), dtype=torch.float32, device=y.device)
+    if b == 0:
+        return kl, dkl
+    check(_native.load().hfl_kd_rows(kl.data_ptr(), dkl.data_ptr(), y.data_ptr(), t.data_ptr(), b, d, float(temperature),
+                                     _stream()), 'hfl_kd_rows')
+    return kl, dkl

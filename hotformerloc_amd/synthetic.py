@@ -173,3 +173,14 @@ def fill_synthetic_weights(model: torch.nn.Module, profile: str = 'stress') -> D
             t.copy_(torch.from_numpy(w).to(t.device, t.dtype))
             spec[name] = tuple(t.shape)
     return spec
+
+
+def kd_case(seed: int, batch: int, dim: int, scale: float = 1.0):
+    """Student and teacher descriptor rows for the distillation-loss tests, closed-form from `seed`: unit-norm student rows,
+    the teacher = those rows plus noise of standard deviation 0.05 per entry, re-normalised (a moving-average teacher stays
+    close to its student); both multiplied by `scale`.  (batch, dim) float32 each."""
+    y = hash_uniform(seed, batch * dim).reshape(batch, dim)
+    y /= np.linalg.norm(y, axis=1, keepdims=True)
+    t = y + 0.05 * np.sqrt(3.0) * hash_uniform(seed + 1, batch * dim).reshape(batch, dim)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    return (scale * y).astype(np.float32), (scale * t).astype(np.float32)

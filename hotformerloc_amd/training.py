@@ -269,24 +269,56 @@ class _null:
 def multistaged_training_step(model: torch.nn.Module, minibatches: List[dict], positives_mask: torch.Tensor,
                               negatives_mask: torch.Tensor, loss_fn: Callable, optimizer=None,
                               phase: str = 'train', n_total: Optional[int] = None, group=None,
-                              force_collectives: bool = False, reducer: Optional[OverlappedGradReducer] = None) -> dict:
+                              force_collectives: bool = False, reducer: Optional[OverlappedGradReducer] = None,
+                              model_ema=None, mesa: float = 0.0) -> dict:
     """One step.  `minibatches`: this rank's batch dicts ({'octree': ...}, already on the device with
     neighbours built), in global order; masks are (B_total, B_total) over the whole batch.  Returns the
     loss statistics (identical on every rank).  `n_total`: global batch size (default B_local * world).
     `force_collectives`: issue the all-gather and the gradient all-reduce at world size 1 too (single-GPU RCCL test).
     `reducer`: an `OverlappedGradReducer` over model.parameters() kept across steps: the gradient all-reduce then runs bucket
-    by bucket behind the last minibatch's backward instead of after it."""
+    by bucket behind the last minibatch's backward instead of after it.
+
+    MESA self-distillation (`trainer.py:161-163, 305-338, 360-361`).  `model_ema`: a `hotformerloc_amd.ema.ModelEma` of
+    `model`; `mesa`: weight of the distillation term (the trainer passes 0 until `mesa_start_ratio` of the epochs are done).
+    With `mesa > 0` in the training phase stage 1 also encodes every minibatch with the teacher `model_ema.module` (eval
+    mode, no autograd, the ordinary inference path: the teacher is never recomputed), the teacher rows are all-gathered like
+    the student rows, and stage 2 adds `mesa * kdloss(embeddings, embeddings_ema)` to the loss before the backward.  `stats`
+    is what `loss_fn` returned (its 'loss' is the listwise loss alone, as in the reference, which takes it before the sum)
+    plus `stats['mesa_kd']`, the value of `kdloss`, only when the term was evaluated.  Whenever `model_ema` is given the
+    training phase ends with `model_ema.update(model)` after the optimizer step, also with `mesa == 0`.  The EMA needs no
+    communication: after the gradient all-reduce every rank holds identical weights, hence identical averages.
+    `phase='val'` touches neither the teacher nor the EMA.  The reference does run the teacher and the distillation term in
+    its validation phase (`trainer.py:315-334, 434`), but nothing it returns depends on them: `stats` is taken before the sum
+    and there is no backward, so skipping them changes no reported value."""
     assert phase in ('train', 'val')
+    if mesa < 0:
+        raise ValueError('mesa must be >= 0, got %r' % (mesa,))
+    if mesa > 0 and model_ema is None:
+        raise ValueError('mesa > 0 needs the EMA teacher: pass model_ema=ModelEma(model)')
+    distill = mesa > 0 and phase == 'train'
     model.train() if phase == 'train' else model.eval()
     # ---- stage 1 ------------------------------------------------------------------------------
-    with torch.no_grad(), _stage1_numerics(model, phase):
-        local = torch.cat([model(mb)['global'] for mb in minibatches], 0)
+    local, local_ema = [], []
+    with torch.no_grad():
+        for mb in minibatches:
+            with _stage1_numerics(model, phase):
+                local.append(model(mb)['global'])
+            if distill:
+                local_ema.append(model_ema.module(mb)['global'])
+    local = torch.cat(local, 0)
     embeddings = all_gather_descriptors(local, n_total, group, force=force_collectives).detach()
+    if distill:
+        embeddings_ema = all_gather_descriptors(torch.cat(local_ema, 0), n_total, group, force=force_collectives).detach()
     # ---- stage 2 ------------------------------------------------------------------------------
     with torch.set_grad_enabled(phase == 'train'):
         if phase == 'train':
             embeddings.requires_grad_(True)
         loss, stats = loss_fn(embeddings, positives_mask, negatives_mask)
+        if distill:
+            from .losses import kdloss
+            kd = kdloss(embeddings, embeddings_ema)
+            stats['mesa_kd'] = kd.item()
+            loss = loss + mesa * kd
         if phase == 'train':
             loss.backward()
     if phase != 'train':
@@ -322,4 +354,6 @@ def multistaged_training_step(model: torch.nn.Module, minibatches: List[dict], p
         allreduce_gradients(model.parameters(), group, force=force_collectives)
     if optimizer is not None:
         optimizer.step()
+    if model_ema is not None:
+        model_ema.update(model)
     return stats

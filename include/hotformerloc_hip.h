@@ -779,6 +779,29 @@ int hfl_smoothap_rows(float* ap, float* dap_ds, const float* sim, const uint8_t*
                       const uint8_t* neg_mask, const int64_t* closest_pos, int batch, int positives_per_query,
                       float tau, hfl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
+ * ---------------------------------------------------------------------- */
+/* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
+ * tensor at multiples of HFL_EMA_CHUNK elements, so a chunk is 16-byte aligned exactly when its tensor is. */
+#define HFL_EMA_CHUNK 8192
+typedef struct hfl_ema_chunk {
+  float* ema;
+  const float* src;
+  int64_t count;
+} hfl_ema_chunk;
+/* ema <- ema + w * (src - ema) over every chunk of the DEVICE table (n_chunks entries), one launch, one workgroup per
+ * chunk.  The table's pointers and counts are trusted: the caller guarantees that every chunk lies inside its tensors and
+ * that no ema chunk overlaps another chunk.  0 <= w <= 1, else HFL_EINVAL. */
+int hfl_ema_update(const hfl_ema_chunk* table, int n_chunks, float w, hfl_stream_t stream);
+
+/* Distillation rows of kdloss: y, t (B, D) fp32 row-major, p = softmax(y / T), q = softmax(t / T) per row.
+ * kl (B): sum_j q_j (log q_j - log p_j);  dkl_dy (B, D): (p - q) / T, the derivative of kl[row] with respect to y[row].
+ * One wavefront per row, cross-lane sums in a fixed order (bitwise repeatable).  D a multiple of 64 up to 1024 and
+ * T > 0, else HFL_EINVAL. */
+int hfl_kd_rows(float* kl, float* dkl_dy, const float* y, const float* t, int batch, int dim, float temperature,
+                hfl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
