@@ -7,11 +7,14 @@ The reference gets all of this from PyTorch autograd over its materialised masks
 (`models/octformer_backbone.py:59-93`) and from `libs/dwconv/dwconv/nn.py:17-43`."""
 
 import ctypes
+import weakref
+from typing import Callable, NamedTuple
 
 import torch
 
 from . import _native, ops
 from ._native import WindowAttnDesc, check
+from .weight_cache import derived
 
 
 def _desc(n_tokens, n_windows, patch_size, dilation, n_relay, n_heads, batch_size, rt_row0, depth):
@@ -78,7 +81,6 @@ def _inverse_table(neigh, n_src):
     hit = _INV_CACHE.get(key)
     if hit is not None and hit[0]() is neigh:
         return hit[1]
-    import weakref
     inv = torch.empty((n_src, neigh.shape[1]), dtype=torch.int32, device=neigh.device)
     check(_native.load().hfl_inverse_table(inv.data_ptr(), n_src, neigh.data_ptr(), neigh.shape[0],
                                            neigh.shape[1], ops._stream()), 'hfl_inverse_table')
@@ -230,32 +232,22 @@ def _slot_sum_ok(part, slot) -> bool:
 # fp32 per-tap GEMMs.  (The grouped split-precision launch bought 0.6 % of the config-3 step, but the deepest gradient of the
 # loss chain -- first stem convolution, amplified by the 1/tau = 100 of the listwise loss -- moved from 8.5e-4 to 2.2e-3 of
 # the oracle chain with it; that path has since been removed.)
-_TAP_BLOCK_CACHE = {}
-
-
 def _x6_taps_ok(cin, cout) -> bool:
     return cin % 32 == 0 and cout % 32 == 0 and (cout % 128 == 0 or cout == 64) and (cin % 128 == 0 or cin == 64)
 
 
-def _tap_blocks(weights, transposed: bool, npad: int):
-    """The three bf16 planes (`ops.x6_pack`) of the per-tap weight blocks of an octree convolution, every block padded to
-    `npad` rows: transposed = W[k]^T (Cout x Cin) for the forward product, else W[k] (Cin x Cout) for the input gradient;
-    rebuilt when the optimizer updates the parameter."""
-    import weakref
-    key = (id(weights), transposed, npad)
-    hit = _TAP_BLOCK_CACHE.get(key)
-    if hit is None or hit[0]() is not weights or hit[1] != weights._version or hit[3] != weights.data_ptr():
+def _tap_blocks(weights, transposed: bool, npad: int, pack=ops.x6_pack, kind='taps6'):
+    """The three bf16 planes (`ops.x6_pack`; or another `pack` / `kind`: model.OctreeConv's split2 form) of the per-tap
+    weight blocks of an octree convolution, every block padded to `npad` rows: transposed = W[k]^T (Cout x Cin) for the
+    forward product, else W[k] (Cin x Cout) for the input gradient; rebuilt when the optimizer updates the parameter."""
+    def build():
         w = weights.detach()
         blocks = w.transpose(1, 2) if transposed else w                   # (kdim, rows, K)
         kdim, rows, kk = blocks.shape
         if npad > rows:
             blocks = torch.cat([blocks, blocks.new_zeros(kdim, npad - rows, kk)], 1)
-        if len(_TAP_BLOCK_CACHE) > 256:
-            _TAP_BLOCK_CACHE.clear()
-        stacked = blocks.reshape(kdim * npad, kk).contiguous()
-        hit = (weakref.ref(weights), weights._version, ops.x6_pack(stacked), weights.data_ptr())
-        _TAP_BLOCK_CACHE[key] = hit
-    return hit[2]
+        return pack(blocks.reshape(kdim * npad, kk).contiguous())
+    return derived((kind, transposed, npad), (weights,), build)
 
 
 _UNIT_TAPS = {}
@@ -395,20 +387,15 @@ def attentional_pooling_torch(x, query, plan, depth: int, scale: float):
 
 
 # ------------------------------------------------ split-precision Linear with HIP/hipBLASLt backward
-_WSPLIT_CACHE = {}      # (id(weight), transposed) -> (weakref, version, W3)
+def _weight_image(kind, pack, weight, transposed: bool):
+    """`pack` of a Linear weight, or of its transpose for dx = dy W: one `weight_cache` entry per (kind, orientation),
+    rebuilt when the optimizer updates the parameter (a checkpointed block's recomputation finds it), released with it."""
+    return derived((kind, transposed), (weight,),
+                   lambda: pack(weight.detach().t().contiguous() if transposed else weight.detach()))
 
 
 def _w3_cached(weight, transposed: bool):
-    import weakref
-    key = (id(weight), transposed)
-    hit = _WSPLIT_CACHE.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        w = weight.detach().t().contiguous() if transposed else weight.detach()
-        if len(_WSPLIT_CACHE) > 4096:
-            _WSPLIT_CACHE.clear()
-        hit = (weakref.ref(weight), weight._version, ops.split_weight(w))
-        _WSPLIT_CACHE[key] = hit
-    return hit[2]
+    return _weight_image('split3', ops.split_weight, weight, transposed)
 
 
 class LinearSplitFn(torch.autograd.Function):
@@ -445,19 +432,20 @@ def linear_split(x, weight, bias=None):
     return LinearSplitFn.apply(x, weight, bias)
 
 
-# ------------------------------------------------ split-precision Linear on the hand-written GEMM (csrc/gemm_x3.hip)
+# ------------------------------------------------ Linear / MLP on the hand-written GEMMs, one set of Functions for two families:
+# X3 = split precision (csrc/gemm_x3.hip: three-term bf16 split, fp32 accumulation, 4e-6 per GEMM; operands are "split2" rows,
+# same bytes as the f32 rows), X6 = matched precision of GEMM mode x6 (csrc/gemm_x6.hip: three bf16 planes per operand, six
+# plane products, fp32 accumulation -- fp32 grade; operands are the f32 rows themselves)
 def _w2_cached(weight, transposed: bool):
-    """split2 layout of a Linear weight (or of its transpose, for dx = dy W), rebuilt when the optimizer updates it."""
-    import weakref
-    key = (id(weight), transposed, 'x3')
-    hit = _WSPLIT_CACHE.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version or hit[3] != weight.data_ptr():
-        w = weight.detach().t().contiguous() if transposed else weight.detach()
-        if len(_WSPLIT_CACHE) > 4096:
-            _WSPLIT_CACHE.clear()
-        hit = (weakref.ref(weight), weight._version, ops.split2(w), weight.data_ptr())
-        _WSPLIT_CACHE[key] = hit
-    return hit[2]
+    """split2 layout of a Linear weight (or of its transpose, for dx = dy W).  model._w2 shares the entry and builds it with
+    `ops.split2_weight` (torch arithmetic): the two builders are bit-identical (torch.equal over every Linear weight, both
+    orientations, of the wild-places and cs-wild-places models, default and synthetic weights: 746 of 746 on an MI355X)."""
+    return _weight_image('x3', ops.split2, weight, transposed)
+
+
+def _w6_cached(weight, transposed: bool):
+    """The three bf16 planes (`ops.x6_pack`) of a Linear weight, or of its transpose for dx = dy W."""
+    return _weight_image('x6', ops.x6_pack, weight, transposed)
 
 
 def linear_x3_ok(in_features: int, out_features: int) -> bool:
@@ -465,112 +453,158 @@ def linear_x3_ok(in_features: int, out_features: int) -> bool:
     return in_features % 128 == 0 and out_features % 128 == 0
 
 
-class LinearX3Fn(torch.autograd.Function):
-    """y = x W^T + b on the hand-written split-precision kernels (three-term bf16 split, fp32 accumulation, 4e-6 per
-    GEMM): forward and dx = dy W on `hfl_linear_x3`, dW = dy^T x and db on `hfl_wgrad_x3`.  What is kept for the
-    backward is the split2 operand of x (same bytes as x)."""
+def linear_x6_ok(in_features: int, out_features: int) -> bool:
+    """Shapes `hfl_linear_x6` takes in both directions (forward and dx = dy W) and `hfl_wgrad_f32` takes for dW."""
+    return (in_features % 128 == 0 and out_features % 128 == 0 and ops.linear_x6_ok(in_features, out_features)
+            and ops.linear_x6_ok(out_features, in_features))
+
+
+def _scaled_rows(t, row_scale=None):
+    return t if row_scale is None else t * row_scale.unsqueeze(1)
+
+
+class GemmFamily(NamedTuple):
+    """The seven operations a training Function is written in; the Functions never ask which family they were given."""
+    operand: Callable       # (f32 rows, row_scale or None) -> GEMM operand of the rows [times their per-row factor]
+    ln_operand: Callable    # (f32 rows, gamma, beta, eps) -> GEMM operand of LayerNorm(rows)
+    weight: Callable        # (weight, transposed) -> cached weight image
+    linear: Callable        # (operand, weight image, bias=, residual=, row_scale=) -> f32 rows
+    gelu_fwd: Callable      # (operand, weight image, bias) -> (operand of gelu(pre-activation), f32 pre-activation)
+    gelu_bwd: Callable      # (operand of dy, image of W^T, pre-activation) -> operand of (dy W) * gelu'(pre-activation)
+    wgrad: Callable         # (operand of dy, operand of x, with_bias=) -> (dW, db), fixed reduction order
+
+
+X3 = GemmFamily(ops.split2, ops.layer_norm_split2, _w2_cached, ops.linear_x3, ops.linear_x3_gelu_fwd,
+                ops.linear_x3_gelu_bwd, ops.wgrad_x3)
+X6 = GemmFamily(_scaled_rows, ops.layer_norm, _w6_cached, ops.linear_x6, ops.linear_x6_gelu_fwd,
+                ops.linear_x6_gelu_bwd, ops.wgrad_f32)
+
+
+def _wgrad(fam: GemmFamily, dy, x, need_w: bool, need_b: bool):
+    """(dW, db) through `hfl_wgrad_x3` / `hfl_wgrad_f32`, or (None, None) without a launch when neither is wanted (frozen
+    layers)."""
+    if not (need_w or need_b):
+        return None, None
+    dw, db = fam.wgrad(dy, x, with_bias=need_b)
+    return (dw if need_w else None), db
+
+
+class LinearFn(torch.autograd.Function):
+    """y = x W^T + b on the hand-written kernels: forward and dx = dy W on `hfl_linear_x3` / `hfl_linear_x6`, dW = dy^T x
+    and db on `hfl_wgrad_x3` / `hfl_wgrad_f32` (fp32 MFMA).  What is kept for the backward is the GEMM operand of x (X3: its
+    split2 form, same bytes as x; X6: x itself).  The X6 forward is the x6 inference launch, with or without autograd.
+    Zero rows: zeros out, zero gradients, no launch."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, fam, x, weight, bias):
         shape = x.shape
         x2 = x.reshape(-1, shape[-1]).contiguous()
-        ctx.has_bias = bias is not None
-        ctx.shape = shape
+        ctx.fam, ctx.has_bias, ctx.shape = fam, bias is not None, shape
         if x2.shape[0] == 0:
             ctx.save_for_backward(None, weight)
             return x.new_zeros(*shape[:-1], weight.shape[0])
-        xs = ops.split2(x2)
+        xs = fam.operand(x2, None)
         ctx.save_for_backward(xs, weight)
-        return ops.linear_x3(xs, _w2_cached(weight, False), bias=bias).view(*shape[:-1], weight.shape[0])
+        return fam.linear(xs, fam.weight(weight, False), bias=bias).view(*shape[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         xs, weight = ctx.saved_tensors
-        dx = dw = db = None
+        fam = ctx.fam
         if xs is None:
-            return (torch.zeros(ctx.shape, device=dy.device), torch.zeros_like(weight),
+            return (None, torch.zeros(ctx.shape, device=dy.device), torch.zeros_like(weight),
                     torch.zeros(weight.shape[0], device=dy.device) if ctx.has_bias else None)
-        dys = ops.split2(dy.reshape(-1, weight.shape[0]).contiguous())
-        if ctx.needs_input_grad[0]:
-            dx = ops.linear_x3(dys, _w2_cached(weight, True)).view(ctx.shape)
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or need_b:
-            dw, db = ops.wgrad_x3(dys, xs, with_bias=need_b)
-        return dx, dw, db
+        dys = fam.operand(dy.reshape(-1, weight.shape[0]).contiguous(), None)
+        need = ctx.needs_input_grad                    # (fam, x, weight, bias)
+        dx = fam.linear(dys, fam.weight(weight, True)).view(ctx.shape) if need[1] else None
+        dw, db = _wgrad(fam, dys, xs, need[2], ctx.has_bias and need[3])
+        return None, dx, dw, db
 
 
 def linear_x3(x, weight, bias=None):
-    return LinearX3Fn.apply(x, weight, bias)
+    return LinearFn.apply(X3, x, weight, bias)
 
 
-def _wgrad(dys, xs, need_w: bool, need_b: bool):
-    """(dW, db) through `hfl_wgrad_x3`, or (None, None) without a launch when neither is wanted (frozen layers)."""
-    if not (need_w or need_b):
-        return None, None
-    dw, db = ops.wgrad_x3(dys, xs, with_bias=need_b)
-    return (dw if need_w else None), db
+def linear_x6(x, weight, bias=None):
+    return LinearFn.apply(X6, x, weight, bias)
 
 
-class MlpX3Fn(torch.autograd.Function):
+class MlpFn(torch.autograd.Function):
     """fc2(gelu(fc1(h))) of a transformer block (models/layers/octformer_layers.py:53-59) with no element-wise pass of its
-    own: fc1 writes split2(gelu(.)) and the pre-activation in one launch, the backward's dx GEMM of fc2 multiplies by
-    gelu'(pre-activation) in its epilogue and writes the split2 operand of fc1's gradient GEMMs directly."""
+    own: fc1 writes the operand of gelu(.) and the pre-activation in one launch (hfl_linear_x3_gelu_fwd /
+    hfl_linear_x6_gelu_fwd), the backward's dx GEMM of fc2 multiplies by gelu'(pre-activation) in its epilogue and writes the
+    operand of fc1's gradient GEMMs directly.  The X6 forward is bitwise the x6 inference MLP (MLP.forward)."""
 
     @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2):
+    def forward(ctx, fam, h, w1, b1, w2, b2):
         shape = h.shape
-        hs = ops.split2(h.reshape(-1, shape[-1]).contiguous())
-        gs, pre = ops.linear_x3_gelu_fwd(hs, _w2_cached(w1, False), b1)
+        hs = fam.operand(h.reshape(-1, shape[-1]).contiguous(), None)
+        gs, pre = fam.gelu_fwd(hs, fam.weight(w1, False), b1)
         ctx.save_for_backward(hs, gs, pre, w1, w2)
-        ctx.shape = shape
-        return ops.linear_x3(gs, _w2_cached(w2, False), bias=b2).view(*shape[:-1], w2.shape[0])
+        ctx.fam, ctx.shape = fam, shape
+        return fam.linear(gs, fam.weight(w2, False), bias=b2).view(*shape[:-1], w2.shape[0])
 
     @staticmethod
     def backward(ctx, dout):
         hs, gs, pre, w1, w2 = ctx.saved_tensors
-        dys = ops.split2(dout.reshape(-1, w2.shape[0]).contiguous())
-        dps = ops.linear_x3_gelu_bwd(dys, _w2_cached(w2, True), pre)
-        need = ctx.needs_input_grad
-        dw2, db2 = _wgrad(dys, gs, need[3], need[4])
-        dh = ops.linear_x3(dps, _w2_cached(w1, True)).view(ctx.shape) if need[0] else None
-        dw1, db1 = _wgrad(dps, hs, need[1], need[2])
-        return dh, dw1, db1, dw2, db2
+        fam = ctx.fam
+        dys = fam.operand(dout.reshape(-1, w2.shape[0]).contiguous(), None)
+        dps = fam.gelu_bwd(dys, fam.weight(w2, True), pre)
+        need = ctx.needs_input_grad                    # (fam, h, w1, b1, w2, b2)
+        dw2, db2 = _wgrad(fam, dys, gs, need[4], need[5])
+        dh = fam.linear(dps, fam.weight(w1, True)).view(ctx.shape) if need[1] else None
+        dw1, db1 = _wgrad(fam, dps, hs, need[2], need[3])
+        return None, dh, dw1, db1, dw2, db2
 
 
-class LnMlpResidualX3Fn(torch.autograd.Function):
+def mlp_x3(h, w1, b1, w2, b2):
+    return MlpFn.apply(X3, h, w1, b1, w2, b2)
+
+
+def mlp_x6(h, w1, b1, w2, b2):
+    return MlpFn.apply(X6, h, w1, b1, w2, b2)
+
+
+class LnMlpResidualFn(torch.autograd.Function):
     """x + s * fc2(gelu(fc1(LN(x)))): the whole pre-norm MLP branch of a transformer block (models/octformer_backbone.py:
-    275-278; s = the per-row stochastic-depth factor of OctreeDropPath or None) as three launches forward (LN -> split2,
+    275-278; s = the per-row stochastic-depth factor of OctreeDropPath or None) as three launches forward (LN -> operand,
     fc1 + GELU, fc2 + bias + scale + residual) and seven backward; no element-wise pass: LayerNorm writes the GEMM operand,
     the residual add rides in fc2's epilogue, the skip path's gradient joins inside the LayerNorm backward kernel."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, w1, b1, w2, b2, row_scale):
+    def forward(ctx, fam, x, gamma, beta, eps, w1, b1, w2, b2, row_scale):
         shape = x.shape
         x2 = x.reshape(-1, shape[-1]).contiguous()
-        hs = ops.layer_norm_split2(x2, gamma, beta, eps)
-        gs, pre = ops.linear_x3_gelu_fwd(hs, _w2_cached(w1, False), b1)
+        hs = fam.ln_operand(x2, gamma, beta, eps)
+        gs, pre = fam.gelu_fwd(hs, fam.weight(w1, False), b1)
         ctx.save_for_backward(x2, gamma, hs, gs, pre, w1, w2, row_scale if row_scale is not None else x2.new_empty(0))
-        ctx.shape, ctx.eps, ctx.scaled = shape, eps, row_scale is not None
-        return ops.linear_x3(gs, _w2_cached(w2, False), bias=b2, residual=x2, row_scale=row_scale).view(shape)
+        ctx.fam, ctx.shape, ctx.eps, ctx.scaled = fam, shape, eps, row_scale is not None
+        return fam.linear(gs, fam.weight(w2, False), bias=b2, residual=x2, row_scale=row_scale).view(shape)
 
     @staticmethod
     def backward(ctx, dout):
         x2, gamma, hs, gs, pre, w1, w2, row_scale = ctx.saved_tensors
+        fam = ctx.fam
         dout2 = dout.reshape(-1, w2.shape[0]).contiguous()
-        dys = ops.split2(dout2, row_scale if ctx.scaled else None)
-        dps = ops.linear_x3_gelu_bwd(dys, _w2_cached(w2, True), pre)
-        need = ctx.needs_input_grad                    # (x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
-        dw2, db2 = _wgrad(dys, gs, need[6], need[7])
-        dw1, db1 = _wgrad(dps, hs, need[4], need[5])
-        if not (need[0] or need[1] or need[2]):
-            return None, None, None, None, dw1, db1, dw2, db2, None
-        dh = ops.linear_x3(dps, _w2_cached(w1, True))
+        dys = fam.operand(dout2, row_scale if ctx.scaled else None)
+        dps = fam.gelu_bwd(dys, fam.weight(w2, True), pre)
+        need = ctx.needs_input_grad                    # (fam, x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
+        dw2, db2 = _wgrad(fam, dys, gs, need[7], need[8])
+        dw1, db1 = _wgrad(fam, dps, hs, need[5], need[6])
+        if not (need[1] or need[2] or need[3]):
+            return None, None, None, None, None, dw1, db1, dw2, db2, None
+        dh = fam.linear(dps, fam.weight(w1, True))
         dx, dg, dbeta = ops.layer_norm_bwd(dh, x2, gamma, ctx.eps, dres=dout2)
-        return (dx.view(ctx.shape), dg if need[1] else None, dbeta if need[2] else None, None, dw1, db1, dw2, db2, None)
+        return (None, dx.view(ctx.shape), dg if need[2] else None, dbeta if need[3] else None, None, dw1, db1, dw2, db2,
+                None)
 
 
 def ln_mlp_residual_x3(x, gamma, beta, eps, w1, b1, w2, b2, row_scale=None):
-    return LnMlpResidualX3Fn.apply(x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
+    return LnMlpResidualFn.apply(X3, x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
+
+
+def ln_mlp_residual_x6(x, gamma, beta, eps, w1, b1, w2, b2, row_scale=None):
+    return LnMlpResidualFn.apply(X6, x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
 
 
 class LnAttnResidualX3Fn(torch.autograd.Function):
@@ -600,7 +634,7 @@ class LnAttnResidualX3Fn(torch.autograd.Function):
         dys = ops.split2(dout2, row_scale if ctx.scaled else None)
         need = ctx.needs_input_grad    # (x, gamma, beta, eps, wqkv, bqkv, rpe_table, tok_meta, cfg, wp, bp, row_scale)
         do = ops.linear_x3(dys, _w2_cached(wp, True))
-        dwp, dbp = _wgrad(dys, os_, need[9], need[10])
+        dwp, dbp = _wgrad(X3, dys, os_, need[9], need[10])
         dtable = torch.zeros_like(table) if ctx.has_table else None
         d = _desc(cfg['n_tokens'], cfg['n_windows'], cfg['patch_size'], cfg['dilation'], cfg['n_relay'],
                   cfg['n_heads'], cfg['batch_size'], cfg.get('rt_row0', 0), cfg.get('depth', 0))
@@ -613,7 +647,7 @@ class LnAttnResidualX3Fn(torch.autograd.Function):
             if live < dqs.shape[0]:
                 dqs[live:].zero_()
         dh = ops.linear_x3(dqs, _w2_cached(wqkv, True))
-        dwqkv, dbqkv = _wgrad(dqs, hs, need[4], ctx.has_qkv_bias and need[5])
+        dwqkv, dbqkv = _wgrad(X3, dqs, hs, need[4], ctx.has_qkv_bias and need[5])
         dx, dg, dbeta = ops.layer_norm_bwd(dh, x2, gamma, ctx.eps, dres=dout2)
         return (dx.view(ctx.shape), dg if need[1] else None, dbeta if need[2] else None, None, dwqkv, dbqkv,
                 dtable if need[6] else None, None, None, dwp, dbp, None)
@@ -621,135 +655,6 @@ class LnAttnResidualX3Fn(torch.autograd.Function):
 
 def ln_attn_residual_x3(x, gamma, beta, eps, wqkv, bqkv, rpe_table, tok_meta, cfg, wp, bp, row_scale=None):
     return LnAttnResidualX3Fn.apply(x, gamma, beta, eps, wqkv, bqkv, rpe_table, tok_meta, cfg, wp, bp, row_scale)
-
-
-def mlp_x3(h, w1, b1, w2, b2):
-    return MlpX3Fn.apply(h, w1, b1, w2, b2)
-
-
-# ------------------------------------------------ matched-precision Linear on the hand-written kernels (GEMM mode x6)
-def _w6_cached(weight, transposed: bool):
-    """The three bf16 planes (`ops.x6_pack`) of a Linear weight, or of its transpose for dx = dy W, rebuilt when the optimizer
-    updates the parameter (a checkpointed block's recomputation finds them)."""
-    import weakref
-    key = (id(weight), transposed, 'x6')
-    hit = _WSPLIT_CACHE.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version or hit[3] != weight.data_ptr():
-        w = weight.detach().t().contiguous() if transposed else weight.detach()
-        if len(_WSPLIT_CACHE) > 4096:
-            _WSPLIT_CACHE.clear()
-        hit = (weakref.ref(weight), weight._version, ops.x6_pack(w), weight.data_ptr())
-        _WSPLIT_CACHE[key] = hit
-    return hit[2]
-
-
-def linear_x6_ok(in_features: int, out_features: int) -> bool:
-    """Shapes `hfl_linear_x6` takes in both directions (forward and dx = dy W) and `hfl_wgrad_f32` takes for dW."""
-    return (in_features % 128 == 0 and out_features % 128 == 0 and ops.linear_x6_ok(in_features, out_features)
-            and ops.linear_x6_ok(out_features, in_features))
-
-
-def _wgrad6(dy, x, need_w: bool, need_b: bool):
-    """(dW, db) through `hfl_wgrad_f32`, or (None, None) without a launch when neither is wanted (frozen layers)."""
-    if not (need_w or need_b):
-        return None, None
-    dw, db = ops.wgrad_f32(dy, x, with_bias=need_b)
-    return (dw if need_w else None), db
-
-
-class LinearX6Fn(torch.autograd.Function):
-    """y = x W^T + b at fp32 grade on hand-written kernels: forward and dx = dy W on `hfl_linear_x6` (three bf16 planes per
-    operand, six plane products, fp32 accumulation), dW = dy^T x and db on `hfl_wgrad_f32` (fp32 MFMA).  The forward is the
-    x6 inference launch, with or without autograd.  What is kept for the backward is x itself."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1]).contiguous()
-        ctx.has_bias = bias is not None
-        ctx.shape = shape
-        ctx.save_for_backward(x2, weight)
-        if x2.shape[0] == 0:
-            return x.new_zeros(*shape[:-1], weight.shape[0])
-        return ops.linear_x6(x2, _w6_cached(weight, False), bias=bias).view(*shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, weight = ctx.saved_tensors
-        dy2 = dy.reshape(-1, weight.shape[0]).contiguous()
-        need = ctx.needs_input_grad
-        dx = ops.linear_x6(dy2, _w6_cached(weight, True)).view(ctx.shape) if need[0] else None
-        dw, db = _wgrad6(dy2, x2, need[1], ctx.has_bias and need[2])
-        return dx, dw, db
-
-
-def linear_x6(x, weight, bias=None):
-    return LinearX6Fn.apply(x, weight, bias)
-
-
-class MlpX6Fn(torch.autograd.Function):
-    """fc2(gelu(fc1(h))) at fp32 grade: fc1 writes gelu(.) and the pre-activation in one launch (hfl_linear_x6_gelu_fwd), the
-    backward's dx GEMM of fc2 multiplies by gelu'(pre-activation) in its epilogue (hfl_linear_x6_gelu_bwd); weight gradients
-    on hfl_wgrad_f32.  The forward is bitwise the x6 inference MLP (MLP.forward)."""
-
-    @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2):
-        shape = h.shape
-        h2 = h.reshape(-1, shape[-1]).contiguous()
-        g, pre = ops.linear_x6_gelu_fwd(h2, _w6_cached(w1, False), b1)
-        ctx.save_for_backward(h2, g, pre, w1, w2)
-        ctx.shape = shape
-        return ops.linear_x6(g, _w6_cached(w2, False), bias=b2).view(*shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, dout):
-        h2, g, pre, w1, w2 = ctx.saved_tensors
-        dy = dout.reshape(-1, w2.shape[0]).contiguous()
-        need = ctx.needs_input_grad
-        dp = ops.linear_x6_gelu_bwd(dy, _w6_cached(w2, True), pre)
-        dw2, db2 = _wgrad6(dy, g, need[3], need[4])
-        dh = ops.linear_x6(dp, _w6_cached(w1, True)).view(ctx.shape) if need[0] else None
-        dw1, db1 = _wgrad6(dp, h2, need[1], need[2])
-        return dh, dw1, db1, dw2, db2
-
-
-def mlp_x6(h, w1, b1, w2, b2):
-    return MlpX6Fn.apply(h, w1, b1, w2, b2)
-
-
-class LnMlpResidualX6Fn(torch.autograd.Function):
-    """x + s * fc2(gelu(fc1(LN(x)))) at fp32 grade (the x6 counterpart of LnMlpResidualX3Fn; s = the per-row stochastic-depth
-    factor or None): LayerNorm, fc1 + GELU (+ pre-activation), fc2 + bias + scale + residual forward; the skip path's gradient
-    joins inside the LayerNorm backward kernel."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, w1, b1, w2, b2, row_scale):
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1]).contiguous()
-        h = ops.layer_norm(x2, gamma, beta, eps)
-        g, pre = ops.linear_x6_gelu_fwd(h, _w6_cached(w1, False), b1)
-        ctx.save_for_backward(x2, gamma, h, g, pre, w1, w2, row_scale if row_scale is not None else x2.new_empty(0))
-        ctx.shape, ctx.eps, ctx.scaled = shape, eps, row_scale is not None
-        return ops.linear_x6(g, _w6_cached(w2, False), bias=b2, residual=x2, row_scale=row_scale).view(shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        x2, gamma, h, g, pre, w1, w2, row_scale = ctx.saved_tensors
-        dout2 = dout.reshape(-1, w2.shape[0]).contiguous()
-        dy = dout2 * row_scale.unsqueeze(1) if ctx.scaled else dout2
-        dp = ops.linear_x6_gelu_bwd(dy, _w6_cached(w2, True), pre)
-        need = ctx.needs_input_grad                    # (x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
-        dw2, db2 = _wgrad6(dy, g, need[6], need[7])
-        dw1, db1 = _wgrad6(dp, h, need[4], need[5])
-        if not (need[0] or need[1] or need[2]):
-            return None, None, None, None, dw1, db1, dw2, db2, None
-        dh = ops.linear_x6(dp, _w6_cached(w1, True))
-        dx, dg, dbeta = ops.layer_norm_bwd(dh, x2, gamma, ctx.eps, dres=dout2)
-        return (dx.view(ctx.shape), dg if need[1] else None, dbeta if need[2] else None, None, dw1, db1, dw2, db2, None)
-
-
-def ln_mlp_residual_x6(x, gamma, beta, eps, w1, b1, w2, b2, row_scale=None):
-    return LnMlpResidualX6Fn.apply(x, gamma, beta, eps, w1, b1, w2, b2, row_scale)
 
 
 # ------------------------------------------------ conditional position encoding, training forward as one launch

@@ -19,10 +19,9 @@ from . import _native
 from . import ops
 
 # Per-module caches of launch state that the encoder keeps in a module's __dict__ (ctypes structures of raw device pointers,
-# HIP streams, packed weights).  They describe the ORIGINAL's tensors and some cannot be copied at all; the copy rebuilds its
+# HIP streams; the packed weights live in `weight_cache`, keyed by the parameters, so the copy's are its own).  They describe the ORIGINAL's tensors and some cannot be copied at all; the copy rebuilds its
 # own on its first forward.
-_DERIVED_STATE = ('_native_static', '_native_cache', '_rtsa_st', '_streams', '_w_taps', '_w_taps6', '_unit_taps',
-                  '_drop_path_mods', '_drop_path_cache')
+_DERIVED_STATE = ('_rtsa_st', '_streams', '_unit_taps', '_drop_path_mods', '_drop_path_cache')
 
 
 def _copy_model(model: nn.Module) -> nn.Module:

@@ -23,7 +23,6 @@ Only the options the shipped configs use are implemented; anything else raises.
 
 import contextlib
 import os
-import weakref
 from typing import Dict, List, Optional
 
 import torch
@@ -35,6 +34,7 @@ from . import autograd as ag
 from . import dwconv as hdw
 from . import ops
 from .plan import WindowPlan
+from .weight_cache import _STORE as _W3_CACHE, derived     # the one store of weight images
 
 
 _FORCE_TRAIN_PATH = False
@@ -95,11 +95,12 @@ _SERIAL_STREAMS = False        # ... their launches in the same order on one str
 # at 191 ms/step (B=32, Wild-Places) still slower than the fp32 hipBLASLt route (145 ms) because the operand
 # splits of the backward are torch element-wise passes; needs fused split kernels to pay off.
 _TRAIN_SPLIT = False
-# training-path Linear layers on the hand-written split GEMMs (autograd.LinearX3Fn: forward + dx on hfl_linear_x3, dW / db
-# on hfl_wgrad_x3)
+# training-path Linear layers on the hand-written split GEMMs (autograd.LinearFn with the X3 family: forward + dx on
+# hfl_linear_x3, dW / db on hfl_wgrad_x3)
 _TRAIN_X3 = True
-# GEMM mode 'x6' training-path Linear layers on the hand-written fp32-grade kernels (autograd.LinearX6Fn / MlpX6Fn /
-# LnMlpResidualX6Fn: forward and dx on hfl_linear_x6, dW / db on hfl_wgrad_f32); off = the fp32 library GEMMs (F.linear)
+# GEMM mode 'x6' training-path Linear layers on the hand-written fp32-grade kernels (autograd.LinearFn / MlpFn /
+# LnMlpResidualFn with the X6 family: forward and dx on hfl_linear_x6, dW / db on hfl_wgrad_f32); off = the fp32 library
+# GEMMs (F.linear)
 _TRAIN_X6 = True
 _TRAIN_MLP = True              # fused fc1 -> GELU -> fc2 autograd Function
 _SPARSE_CONV = True            # large 3x3x3 convs over live taps only
@@ -119,13 +120,13 @@ def set_train_split(enabled: bool):
 
 
 def set_train_x3(enabled: bool):
-    """Training-path Linear layers through `autograd.LinearX3Fn` (default on in GEMM mode 'x3')."""
+    """Training-path Linear layers through `autograd.linear_x3` (default on in GEMM mode 'x3')."""
     global _TRAIN_X3
     _TRAIN_X3 = bool(enabled)
 
 
 def set_train_x6(enabled: bool):
-    """Training-path Linear layers of GEMM mode 'x6' through `autograd.LinearX6Fn` and the MLP Functions (default on);
+    """Training-path Linear layers of GEMM mode 'x6' through `autograd.linear_x6` and the MLP Functions (default on);
     False: torch's fp32 Linear (hipBLASLt) as before."""
     global _TRAIN_X6
     _TRAIN_X6 = bool(enabled)
@@ -138,8 +139,6 @@ def set_pyramid_streams(enabled):
     global _PYRAMID_STREAMS, _SERIAL_STREAMS
     _SERIAL_STREAMS = enabled == 'serial'
     _PYRAMID_STREAMS = bool(enabled)
-
-_W3_CACHE = {}          # id(weight) -> (weakref to weight, version, W3)
 
 
 def set_gemm_mode(mode: str):
@@ -158,31 +157,14 @@ def _split_path(x) -> bool:
 
 
 def _w2(lin: nn.Linear):
-    """split2 layout of a Linear weight for `ops.linear_x3`, cached like `_w3`."""
-    w = lin.weight
-    key = ('x3', id(w))
-    hit = _W3_CACHE.get(key)
-    if hit is None or hit[0]() is not w or hit[1] != w._version or hit[3] != w.data_ptr():
-        if hit is None or hit[0]() is not w:
-            # the split copy is as large as the weight: release it with the parameter (a model that ran inference must
-            # not leak its Linear bytes for the life of the process)
-            weakref.finalize(w, _W3_CACHE.pop, key, None)
-        hit = (weakref.ref(w), w._version, ops.split2_weight(w), w.data_ptr())
-        _W3_CACHE[key] = hit
-    return hit[2]
+    """split2 layout of a Linear weight for `ops.linear_x3`: the entry of `autograd._w2_cached(w, False)`, built here with
+    torch arithmetic (bit-identical to the kernel's, see there; also runs on CPU tensors)."""
+    return ag._weight_image('x3', ops.split2_weight, lin.weight, False)
 
 
 def _w6(lin: nn.Linear):
-    """The three bf16 planes of a Linear weight for `ops.linear_x6`, cached like `_w2`."""
-    w = lin.weight
-    key = ('x6', id(w))
-    hit = _W3_CACHE.get(key)
-    if hit is None or hit[0]() is not w or hit[1] != w._version or hit[3] != w.data_ptr():
-        if hit is None or hit[0]() is not w:
-            weakref.finalize(w, _W3_CACHE.pop, key, None)
-        hit = (weakref.ref(w), w._version, ops.x6_pack(w), w.data_ptr())
-        _W3_CACHE[key] = hit
-    return hit[2]
+    """The three bf16 planes of a Linear weight for `ops.linear_x6` (one image for inference and training)."""
+    return ag._w6_cached(lin.weight, False)
 
 
 def _x6_lin_ok(lin: nn.Linear) -> bool:
@@ -194,6 +176,14 @@ def _x6_path(x, *linears) -> bool:
     takes (in_features % 32 == 0, out_features % 128 == 0)."""
     return (_GEMM_MODE == 'x6' and x.is_cuda and not _grad_path() and x.dtype == torch.float32 and x.numel() > 0
             and all(_x6_lin_ok(l) for l in linears))
+
+
+def _x3_train(x, *linears) -> bool:
+    """Split-precision training Functions apply: GEMM mode 'x3', fp32 rows on the GPU, every Linear a shape the hand-written
+    kernels take in both directions.  `_grad_path()` is not asked here but by the callers that need it: a block in train mode
+    with live stochastic depth takes the fused residual branches also without autograd."""
+    return (_GEMM_MODE == 'x3' and _TRAIN_X3 and x.is_cuda and x.dtype == torch.float32 and x.numel() > 0
+            and all(ag.linear_x3_ok(l.in_features, l.out_features) for l in linears))
 
 
 def _x6_train(x, *linears) -> bool:
@@ -228,15 +218,7 @@ def _mlp_pack(mlp: 'MLP', rows: int):
             and f2.in_features == 4 * c and f2.out_features == c and f1.bias is not None and f2.bias is not None):
         return None
     w1, w2 = f1.weight, f2.weight
-    key = ('mlp', id(w1), id(w2))
-    hit = _W3_CACHE.get(key)
-    stamp = (w1._version, w2._version, w1.data_ptr(), w2.data_ptr())
-    if hit is None or hit[0]() is not w1 or hit[1]() is not w2 or hit[2] != stamp:
-        if hit is None or hit[0]() is not w1:
-            weakref.finalize(w1, _W3_CACHE.pop, key, None)
-        hit = (weakref.ref(w1), weakref.ref(w2), stamp, ops.mlp_fused_pack(w1, w2))
-        _W3_CACHE[key] = hit
-    return hit[3]
+    return derived('mlp', (w1, w2), lambda: ops.mlp_fused_pack(w1, w2))
 
 
 # LN1 -> qkv of the token rows as ONE launch (csrc/qkv_fused.hip) from 24 576 rows on (C = 128, 118 096 rows: 71 vs 96 us for
@@ -253,15 +235,7 @@ def _qkv_pack(att: 'OctreeAttention', rows: int):
     if not (rows >= _QKV_FUSED_MIN_ROWS and c in (128, 256) and lin.out_features == 3 * c and lin.bias is not None):
         return None
     w = lin.weight
-    key = ('qkvpack', id(w))
-    hit = _W3_CACHE.get(key)
-    stamp = (w._version, w.data_ptr())
-    if hit is None or hit[0]() is not w or hit[1] != stamp:
-        if hit is None or hit[0]() is not w:
-            weakref.finalize(w, _W3_CACHE.pop, key, None)
-        hit = (weakref.ref(w), stamp, ops.qkv_fused_pack(w))
-        _W3_CACHE[key] = hit
-    return hit[2]
+    return derived('qkvpack', (w,), lambda: ops.qkv_fused_pack(w))
 
 
 def _block_tail_x3(x, attn_out2, attn: 'OctreeAttention', norm2: nn.LayerNorm, mlp: 'MLP', fused_any_rows: bool = False):
@@ -278,18 +252,7 @@ def _block_tail_x3(x, attn_out2, attn: 'OctreeAttention', norm2: nn.LayerNorm, m
 
 
 def _w3(lin: nn.Linear):
-    w = lin.weight
-    hit = _W3_CACHE.get(id(w))
-    # data_ptr: `module.to(other_device)` swaps `.data` without bumping the version counter
-    if hit is None or hit[0]() is not w or hit[1] != w._version or hit[3] != w.data_ptr():
-        if len(_W3_CACHE) > 4096:                     # drop entries whose weight is gone
-            for k in [k for k, v in _W3_CACHE.items() if v[0]() is None]:
-                del _W3_CACHE[k]
-        if hit is None or hit[0]() is not w:
-            weakref.finalize(w, _W3_CACHE.pop, id(w), None)
-        hit = (weakref.ref(w), w._version, ops.split_weight(w), w.data_ptr())
-        _W3_CACHE[id(w)] = hit
-    return hit[2]
+    return ag._w3_cached(lin.weight, False)
 
 
 class SplitLinear(nn.Linear):
@@ -297,8 +260,7 @@ class SplitLinear(nn.Linear):
     GEMM mode is 'bf16x3'; parameters, names and the fp32 fallback are those of nn.Linear."""
 
     def forward(self, x):
-        if (_GEMM_MODE == 'x3' and _TRAIN_X3 and x.is_cuda and _grad_path() and x.numel() > 0
-                and ag.linear_x3_ok(self.in_features, self.out_features)):
+        if _grad_path() and _x3_train(x, self):
             return ag.linear_x3(x, self.weight, self.bias)       # hand-written split GEMM, forward and dx
         if (_GEMM_MODE == 'bf16x3' and _TRAIN_SPLIT and x.is_cuda and _grad_path()
                 and self.in_features % 8 == 0 and self.out_features % 8 == 0 and x.numel() > 0):
@@ -542,11 +504,11 @@ class OctreeConv(nn.Module):
             d2 = data if data.dtype == torch.bfloat16 else ops.split2(data)
             if d2.shape[0] * self.in_channels * 4 < (1 << 32):
                 # the GEMM's tile loader fetches the pairs' input rows itself: no (pairs, Cin) matrix in memory
-                part = ops.linear_x3_grouped_gather(d2, src, self._tap_weights_split2(npad),
+                part = ops.linear_x3_grouped_gather(d2, src, ag._tap_blocks(self.weights, True, npad, ops.split2, 'taps2'),
                                                     octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
             else:
                 gs = ops.octree_gather(d2.view(torch.float32), src).view(torch.bfloat16)
-                part = ops.linear_x3_grouped(gs, self._tap_weights_split2(npad),
+                part = ops.linear_x3_grouped(gs, ag._tap_blocks(self.weights, True, npad, ops.split2, 'taps2'),
                                              octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
             return self._slot_sum(part, slot)
         if (_GEMM_MODE == 'x6' and not _grad_path() and data.dtype == torch.float32 and edges[-1] > 0
@@ -554,7 +516,7 @@ class OctreeConv(nn.Module):
             # matched precision: the same grouped launch on hfl_linear_x6 (fp32-grade products; the tile loader gathers the pairs'
             # input rows from the f32 rows themselves)
             npad = max(self.out_channels, 128)
-            part = ops.linear_x6_grouped_gather(data, src, self._tap_weights_x6(npad),
+            part = ops.linear_x6_grouped_gather(data, src, ag._tap_blocks(self.weights, True, npad),
                                                 octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
             return self._slot_sum(part, slot)
         g = ops.octree_gather(data, src)                                  # (P, Cin)
@@ -578,32 +540,6 @@ class OctreeConv(nn.Module):
             ones = torch.ones((self.kdim, 1, self.out_channels), dtype=torch.float32, device=device)
             self.__dict__['_unit_taps'] = ones
         return ones
-
-    def _tap_weights_x6(self, npad: int):
-        """The three bf16 planes of the per-tap weight blocks W[k]^T (Cout x Cin), each padded to `npad` rows, cached per
-        parameter version: (3, kdim * npad, Kp) bf16 (`ops.x6_pack`)."""
-        w = self.weights
-        hit = self.__dict__.get('_w_taps6')
-        if hit is None or hit[0] != w._version or hit[1] != w.data_ptr() or hit[2] != npad:
-            wt = w.detach().transpose(1, 2)                                   # (kdim, Cout, Cin)
-            if npad > self.out_channels:
-                wt = torch.cat([wt, wt.new_zeros(self.kdim, npad - self.out_channels, self.in_channels)], 1)
-            hit = (w._version, w.data_ptr(), npad, ops.x6_pack(wt.reshape(self.kdim * npad, self.in_channels).contiguous()))
-            self.__dict__['_w_taps6'] = hit
-        return hit[3]
-
-    def _tap_weights_split2(self, npad: int):
-        """split2 layout of the per-tap weight blocks W[k]^T (Cout x Cin), each padded to `npad` rows, cached per parameter
-        version: (kdim * npad, 2 Cin) bf16."""
-        w = self.weights
-        hit = self.__dict__.get('_w_taps')
-        if hit is None or hit[0] != w._version or hit[1] != w.data_ptr() or hit[2] != npad:
-            wt = w.detach().transpose(1, 2)                                   # (kdim, Cout, Cin)
-            if npad > self.out_channels:
-                wt = torch.cat([wt, wt.new_zeros(self.kdim, npad - self.out_channels, self.in_channels)], 1)
-            hit = (w._version, w.data_ptr(), npad, ops.split2(wt.reshape(self.kdim * npad, self.in_channels).contiguous()))
-            self.__dict__['_w_taps'] = hit
-        return hit[3]
 
 
 class OctreeDWConvParams(nn.Module):
@@ -695,12 +631,12 @@ class MLP(nn.Module):
 
     def forward(self, x):
         f1, f2 = self.fc1, self.fc2
-        if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and x.is_cuda and _grad_path() and x.numel() > 0
-                and f1.bias is not None and f2.bias is not None
-                and ag.linear_x3_ok(f1.in_features, f1.out_features) and ag.linear_x3_ok(f2.in_features, f2.out_features)):
-            return ag.mlp_x3(x, f1.weight, f1.bias, f2.weight, f2.bias)      # GELU and its gradient inside the GEMMs
-        if _x6_train(x, f1, f2) and f1.bias is not None and f2.bias is not None:
-            return ag.mlp_x6(x, f1.weight, f1.bias, f2.weight, f2.bias)
+        if f1.bias is not None and f2.bias is not None:
+            # the training family of these two Linears, or none (_TRAIN_MLP gates the x3 fused Functions only)
+            fused = (ag.mlp_x3 if _TRAIN_MLP and _grad_path() and _x3_train(x, f1, f2)
+                     else ag.mlp_x6 if _x6_train(x, f1, f2) else None)
+            if fused is not None:
+                return fused(x, f1.weight, f1.bias, f2.weight, f2.bias)      # GELU and its gradient inside the GEMMs
         if _x6_path(x, f1, f2) and x.dim() == 2:
             return ops.linear_x6(ops.linear_x6(x, _w6(f1), bias=f1.bias, gelu=True), _w6(f2), bias=f2.bias)
         return self.fc2(F.gelu(self.fc1(x)))
@@ -710,13 +646,12 @@ def _mlp_branch(x, norm: nn.LayerNorm, mlp: 'MLP', row_scale=None):
     """x + mlp(LN(x)) on the training path: one fused autograd Function when the shapes allow (LayerNorm writes the GEMM
     operand, GELU and the residual ride in the GEMM epilogues, the skip gradient joins inside the LayerNorm backward)."""
     f1, f2 = mlp.fc1, mlp.fc2
-    if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and x.is_cuda and x.numel() > 0
-            and x.dtype == torch.float32 and x.shape[-1] in ops._LN_CHANNELS and f1.bias is not None and f2.bias is not None
-            and ag.linear_x3_ok(f1.in_features, f1.out_features) and ag.linear_x3_ok(f2.in_features, f2.out_features)):
-        return ag.ln_mlp_residual_x3(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
-    if (_x6_train(x, f1, f2) and x.shape[-1] in ops._LN_CHANNELS and x.dim() == 2 and f1.bias is not None
-            and f2.bias is not None):
-        return ag.ln_mlp_residual_x6(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
+    if x.shape[-1] in ops._LN_CHANNELS and f1.bias is not None and f2.bias is not None:
+        # the training family of these two Linears, or none (_TRAIN_MLP gates the x3 fused Functions only)
+        fused = (ag.ln_mlp_residual_x3 if _TRAIN_MLP and _x3_train(x, f1, f2)
+                 else ag.ln_mlp_residual_x6 if x.dim() == 2 and _x6_train(x, f1, f2) else None)
+        if fused is not None:
+            return fused(x, norm.weight, norm.bias, norm.eps, f1.weight, f1.bias, f2.weight, f2.bias, row_scale)
     y = mlp(_ln(x, norm))
     return x + (y if row_scale is None else y * row_scale.unsqueeze(1))
 
@@ -806,9 +741,7 @@ class OctreeAttention(nn.Module):
     def residual_branch(self, x, norm1: nn.LayerNorm, plan: WindowPlan, depth: int, row_scale=None):
         """x + attention(LN(x)) on the training path: one fused autograd Function when the shapes allow."""
         C = self.dim
-        if (_GEMM_MODE == 'x3' and _TRAIN_X3 and _TRAIN_MLP and x.is_cuda and x.numel() > 0
-                and x.dtype == torch.float32 and C in ops._LN_CHANNELS and ag.linear_x3_ok(C, 3 * C)
-                and ag.linear_x3_ok(C, C) and self.proj.bias is not None):
+        if _TRAIN_MLP and _x3_train(x, self.qkv, self.proj) and C in ops._LN_CHANNELS and self.proj.bias is not None:
             nt = plan.n_tokens[depth]
             cfg = dict(n_tokens=nt, n_windows=plan.n_windows[depth], patch_size=self.patch_size,
                        dilation=self.dilation, n_relay=self.rt_per_window, n_heads=self.num_heads,
@@ -878,24 +811,23 @@ def _attn_f16_ok(rows, att, depth) -> bool:
 
 def _native_block_static(block, device):
     """(BlockWeights, tensors it points to) of a block, or None when the block's parameters do not qualify for the native
-    call; cached on the block and revalidated by the (version, pointer) stamp of every parameter (a few microseconds instead
-    of rebuilding a 20-field ctypes structure per block and forward: the host runs only just ahead of the GPU)."""
+    call; cached (`weight_cache.derived`) and revalidated by the (version, pointer) stamp of every parameter (a few
+    microseconds instead of rebuilding a 20-field ctypes structure per block and forward: the host runs only just ahead of
+    the GPU)."""
     att, mlp, cpe = block.attention, block.mlp, block.cpe
     table = None if att.rpe is None else att.rpe.rpe_table
     plist = (cpe.conv.weights, cpe.norm.weight, cpe.norm.bias, block.norm1.weight, block.norm1.bias, block.norm2.weight,
              block.norm2.bias, att.qkv.bias, att.proj.bias, mlp.fc1.bias, mlp.fc2.bias, att.qkv.weight, att.proj.weight,
              mlp.fc1.weight, mlp.fc2.weight, table)
-    stamp = tuple((p._version, p.data_ptr()) if p is not None else None for p in plist)
-    hit = block.__dict__.get('_native_static')
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    from ._native import BlockWeights
-    res = None
-    # the native call reads raw pointers: every parameter must be what the Python wrappers would have checked (fp32,
-    # contiguous, on this device), the biases must exist and the three LayerNorms must share one eps
-    ok = (all(p is not None for p in plist[:-1]) and block.norm1.eps == block.norm2.eps == cpe.norm.eps
-          and all(p is None or (p.dtype == torch.float32 and p.is_contiguous() and p.device == device) for p in plist))
-    if ok:
+
+    def build():
+        from ._native import BlockWeights
+        # the native call reads raw pointers: every parameter must be what the Python wrappers would have checked (fp32,
+        # contiguous, on this device), the biases must exist and the three LayerNorms must share one eps
+        ok = (all(p is not None for p in plist[:-1]) and block.norm1.eps == block.norm2.eps == cpe.norm.eps
+              and all(p is None or (p.dtype == torch.float32 and p.is_contiguous() and p.device == device) for p in plist))
+        if not ok:
+            return None
         keep = [_w2(att.qkv), _w2(att.proj), None, None]
         w = BlockWeights(channels=att.dim, eps=block.norm1.eps, q_scale=16 ** -0.5 * 1.4426950408889634,
                          cpe_weight=cpe.conv.weights.data_ptr(), cpe_gamma=cpe.norm.weight.data_ptr(),
@@ -905,9 +837,8 @@ def _native_block_static(block, device):
                          fc1_w=None, fc2_w=None, mlp_pack=None, qkv_b=att.qkv.bias.data_ptr(),
                          proj_b=att.proj.bias.data_ptr(), fc1_b=mlp.fc1.bias.data_ptr(), fc2_b=mlp.fc2.bias.data_ptr(),
                          rpe_table=None if table is None else table.data_ptr())
-        res = (w, keep)
-    block.__dict__['_native_static'] = (stamp, res)
-    return res
+        return w, keep
+    return derived('native-block', plist, build)
 
 
 def _attn_ws_wanted(att, rows: int, nt: int, n_windows: int, depth: int) -> bool:
@@ -970,6 +901,31 @@ def _native_block(block, x_in, relay, plan: WindowPlan, depth: int):
     return None if call is None else call.run(0, relay)
 
 
+def _block_body(block, x, plan: WindowPlan, depth: int, with_relay: bool):
+    """What OctFormerBlock and HOTFormerBlock do after their CPE heads: x + attention(LN1(x)), then x + mlp(LN2(x)), on the
+    first path that applies (the order is the behaviour: the split path is tested before layer scale, and so on down).
+    with_relay: x is the [tokens | relay rows] buffer of a HOTFormer level."""
+    if _split_path(x) and not block.use_layer_scale and not _drops(block):
+        o3 = block.attention.forward_split(x, block.norm1, plan, depth)
+        return _block_tail_split(x, o3, block.attention, block.norm2, block.mlp)
+    if block.use_layer_scale:
+        bid = plan.row_cloud(depth, with_relay=with_relay)
+        x = x + block.drop_path(block.gamma1 * block.attention(_ln(x, block.norm1), plan, depth), bid, plan.B)
+        return x + block.drop_path(block.gamma2 * block.mlp(_ln(x, block.norm2)), bid, plan.B)
+    if block.training and block.drop_path.drop_prob > 0.0:        # stochastic depth: per-row factor inside the branches
+        bid = plan.row_cloud(depth, with_relay=with_relay)
+        x = block.attention.residual_branch(x, block.norm1, plan, depth, block.drop_path.row_scale(bid, plan.B, x))
+        return _mlp_branch(x, block.norm2, block.mlp, block.drop_path.row_scale(bid, plan.B, x))
+    if _grad_path(x):
+        return _mlp_branch(block.attention.residual_branch(x, block.norm1, plan, depth), block.norm2, block.mlp)
+    att = block.attention
+    if _x6_path(x, att.qkv, att.proj, block.mlp.fc1, block.mlp.fc2) and x.shape[-1] in ops._LN_CHANNELS:
+        o = att.core(att.qkv(_ln(x, block.norm1)), plan, depth)
+        return _block_tail_x6(x, o, att.proj, block.norm2, block.mlp)
+    x, h = _add_ln(x, block.attention(_ln(x, block.norm1), plan, depth), block.norm2)
+    return x + block.mlp(h)
+
+
 class OctFormerBlock(nn.Module):
     """models/octformer_backbone.py:182-299 (use_rt=False)"""
 
@@ -990,25 +946,7 @@ class OctFormerBlock(nn.Module):
             if y is not None:
                 return y
         x = self.cpe(x, plan, depth, residual=True)
-        if _split_path(x) and not self.use_layer_scale and not _drops(self):
-            o3 = self.attention.forward_split(x, self.norm1, plan, depth)
-            return _block_tail_split(x, o3, self.attention, self.norm2, self.mlp)
-        if self.use_layer_scale:
-            bid = plan.row_cloud(depth, with_relay=False)
-            x = x + self.drop_path(self.gamma1 * self.attention(_ln(x, self.norm1), plan, depth), bid, plan.B)
-            return x + self.drop_path(self.gamma2 * self.mlp(_ln(x, self.norm2)), bid, plan.B)
-        if self.training and self.drop_path.drop_prob > 0.0:        # stochastic depth: per-row factor inside the branches
-            bid = plan.row_cloud(depth, with_relay=False)
-            x = self.attention.residual_branch(x, self.norm1, plan, depth, self.drop_path.row_scale(bid, plan.B, x))
-            return _mlp_branch(x, self.norm2, self.mlp, self.drop_path.row_scale(bid, plan.B, x))
-        if _grad_path(x):
-            return _mlp_branch(self.attention.residual_branch(x, self.norm1, plan, depth), self.norm2, self.mlp)
-        att = self.attention
-        if _x6_path(x, att.qkv, att.proj, self.mlp.fc1, self.mlp.fc2) and x.shape[-1] in ops._LN_CHANNELS:
-            o = att.core(att.qkv(_ln(x, self.norm1)), plan, depth)
-            return _block_tail_x6(x, o, att.proj, self.norm2, self.mlp)
-        x, h = _add_ln(x, self.attention(_ln(x, self.norm1), plan, depth), self.norm2)
-        return x + self.mlp(h)
+        return _block_body(self, x, plan, depth, with_relay=False)
 
 
 class OctFormerStage(nn.Module):
@@ -1086,25 +1024,7 @@ class HOTFormerBlock(nn.Module):
             self.cpe(buf[:nt], plan, depth, residual=True, out=new[:nt])
             new[nt:].copy_(buf[nt:] if relay is None else relay)
             buf = new
-        if _split_path(buf) and not self.use_layer_scale and not _drops(self):
-            o3 = self.attention.forward_split(buf, self.norm1, plan, depth)
-            return _block_tail_split(buf, o3, self.attention, self.norm2, self.mlp)
-        if self.use_layer_scale:
-            bid = plan.row_cloud(depth, with_relay=True)
-            buf = buf + self.drop_path(self.gamma1 * self.attention(_ln(buf, self.norm1), plan, depth), bid, plan.B)
-            return buf + self.drop_path(self.gamma2 * self.mlp(_ln(buf, self.norm2)), bid, plan.B)
-        if self.training and self.drop_path.drop_prob > 0.0:
-            bid = plan.row_cloud(depth, with_relay=True)
-            buf = self.attention.residual_branch(buf, self.norm1, plan, depth, self.drop_path.row_scale(bid, plan.B, buf))
-            return _mlp_branch(buf, self.norm2, self.mlp, self.drop_path.row_scale(bid, plan.B, buf))
-        if _grad_path(buf):
-            return _mlp_branch(self.attention.residual_branch(buf, self.norm1, plan, depth), self.norm2, self.mlp)
-        att = self.attention
-        if _x6_path(buf, att.qkv, att.proj, self.mlp.fc1, self.mlp.fc2) and buf.shape[-1] in ops._LN_CHANNELS:
-            o = att.core(att.qkv(_ln(buf, self.norm1)), plan, depth)
-            return _block_tail_x6(buf, o, att.proj, self.norm2, self.mlp)
-        buf, h = _add_ln(buf, self.attention(_ln(buf, self.norm1), plan, depth), self.norm2)
-        return buf + self.mlp(h)
+        return _block_body(self, buf, plan, depth, with_relay=True)
 
 
 class RTAttention(nn.Module):
@@ -1144,13 +1064,11 @@ class RelayTokenTransformerBlock(nn.Module):
         att, mlp = self.rt_attention, self.mlp
         plist = (self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, att.qkv.bias, att.proj.bias,
                  mlp.fc1.bias, mlp.fc2.bias, att.qkv.weight, att.proj.weight, mlp.fc1.weight, mlp.fc2.weight)
-        stamp = tuple((p._version, p.data_ptr()) if p is not None else None for p in plist)
-        hit = self.__dict__.get('_native_cache')
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-        res = None
-        if (all(p is not None and p.dtype == torch.float32 and p.is_contiguous() and p.device == device for p in plist)
-                and self.norm1.eps == self.norm2.eps and att.dim % 128 == 0 and att.num_heads * 16 == att.dim):
+
+        def build():
+            if not (all(p is not None and p.dtype == torch.float32 and p.is_contiguous() and p.device == device for p in plist)
+                    and self.norm1.eps == self.norm2.eps and att.dim % 128 == 0 and att.num_heads * 16 == att.dim):
+                return None
             from ._native import RelayBlockWeights
             # (the MLP branch as the fused launch with the hidden dimension split over the chip: 27 us against 48 us for the
             # three launches alone, and inside the step the relay tokens' fc2 -- K = 1024 over 28 workgroups -- took 120 us:
@@ -1167,9 +1085,8 @@ class RelayTokenTransformerBlock(nn.Module):
                                   qkv_w=keep[0].data_ptr(), proj_w=keep[1].data_ptr(), fc1_w=keep[2].data_ptr(),
                                   fc2_w=keep[3].data_ptr(), qkv_b=att.qkv.bias.data_ptr(), proj_b=att.proj.bias.data_ptr(),
                                   fc1_b=mlp.fc1.bias.data_ptr(), fc2_b=mlp.fc2.bias.data_ptr())
-            res = (w, keep)
-        self.__dict__['_native_cache'] = (stamp, res)
-        return res
+            return w, keep
+        return derived('native-relay', plist, build)
 
     def forward_parts(self, parts, plan):
         """forward(torch.cat(parts)) -- without the concatenation launch when the native call can read the rows where they are
@@ -1672,15 +1589,7 @@ class FeatureMixerLayer(nn.Module):
 def _mixer_pack(fc1: nn.Linear, fc2: nn.Linear):
     """`ops.mlp_fused_pack` image of a Mixer layer's two Linears, cached per parameter pair like `_mlp_pack`."""
     w1, w2 = fc1.weight, fc2.weight
-    key = ('mixer', id(w1), id(w2))
-    hit = _W3_CACHE.get(key)
-    stamp = (w1._version, w2._version, w1.data_ptr(), w2.data_ptr())
-    if hit is None or hit[0]() is not w1 or hit[1]() is not w2 or hit[2] != stamp:
-        if hit is None or hit[0]() is not w1:
-            weakref.finalize(w1, _W3_CACHE.pop, key, None)
-        hit = (weakref.ref(w1), weakref.ref(w2), stamp, ops.mlp_fused_pack(w1, w2))
-        _W3_CACHE[key] = hit
-    return hit[3]
+    return derived('mixer', (w1, w2), lambda: ops.mlp_fused_pack(w1, w2))
 
 
 def _mixer_layer_fits(m) -> bool:

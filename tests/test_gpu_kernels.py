@@ -995,7 +995,7 @@ def test_wgrad_x3_matches_fp64_and_is_reproducible():
 
 
 def test_mlp_x3_matches_fp64_autograd():
-    """fc2(gelu(fc1(h))) with GELU and its derivative fused into the GEMM epilogues (autograd.MlpX3Fn): output and all five
+    """fc2(gelu(fc1(h))) with GELU and its derivative fused into the GEMM epilogues (autograd.MlpFn, X3 family): output and all five
     gradients against torch autograd in fp64 (exact erf GELU), <= 2e-5 relative L2; ragged row count."""
     from hotformerloc_amd import autograd as ag
     g = torch.Generator().manual_seed(41)
@@ -1017,10 +1017,33 @@ def test_mlp_x3_matches_fp64_autograd():
         for a, b, name in zip(dev_in, ref_in, ('dh', 'dw1', 'db1', 'dw2', 'db2')):
             err = ((a.grad.cpu().double() - b.grad).norm() / b.grad.norm()).item()
             assert err < 2e-5, (m, c, name, err)
+    # the transposed split2 image of fc2 (dx = dy W) in the one store of weight images: cached; rebuilt, with no new entry,
+    # after an in-place update and after `.data` moved to new storage (same version, new data_ptr); gone with the parameter
+    import gc
+    from hotformerloc_amd import model as M
+    before = len(M._W3_CACHE)
+    p = torch.nn.Parameter(w2.to(DEV))
+    want = lambda: ops.split2(p.detach().t().contiguous())
+    i1 = ag._w2_cached(p, True)
+    assert torch.equal(i1, want()) and ag._w2_cached(p, True) is i1 and len(M._W3_CACHE) == before + 1
+    with torch.no_grad():
+        p.add_(1.0)
+    i2 = ag._w2_cached(p, True)
+    assert i2 is not i1 and torch.equal(i2, want()) and len(M._W3_CACHE) == before + 1
+    version = p._version
+    p.data = p.data.clone() + 1
+    i3 = ag._w2_cached(p, True)
+    assert p._version == version and i3 is not i2 and torch.equal(i3, want()) and len(M._W3_CACHE) == before + 1
+    # model._w2 (torch arithmetic) and the training path (hfl_split2) keep one image between them: the two are bit-identical
+    lin = torch.nn.Linear(c, 4 * c).to(DEV)
+    assert M._w2(lin) is ag._w2_cached(lin.weight, False) and torch.equal(M._w2(lin), ops.split2(lin.weight.detach()))
+    del p, i1, i2, i3, lin
+    gc.collect()
+    assert len(M._W3_CACHE) == before
 
 
 def test_ln_mlp_residual_x3_matches_fp64_autograd():
-    """x + fc2(gelu(fc1(LN(x)))) as one autograd Function (autograd.LnMlpResidualX3Fn): output and all seven gradients
+    """x + fc2(gelu(fc1(LN(x)))) as one autograd Function (autograd.LnMlpResidualFn, X3 family): output and all seven gradients
     against torch autograd in fp64, <= 3e-5 relative L2."""
     from hotformerloc_amd import autograd as ag
     g = torch.Generator().manual_seed(43)

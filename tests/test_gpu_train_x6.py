@@ -1,7 +1,7 @@
 """GEMM mode x6 under autograd: the matched-precision training path on hand-written kernels.
 
 Kernels: hfl_wgrad_f32 (dW = dy^T x and db on the fp32 matrix cores), the GELU-forward / GELU-backward epilogues of
-hfl_linear_x6.  Autograd: LinearX6Fn, MlpX6Fn, LnMlpResidualX6Fn against fp64 autograd next to torch's fp32 autograd.  Model:
+hfl_linear_x6.  Autograd: LinearFn, MlpFn, LnMlpResidualFn with the X6 family against fp64 autograd next to torch's fp32 autograd.  Model:
 no library GEMM in the block Linears, parameter gradients against the CPU oracle next to the fp32 library route
 (set_train_x6(False)), the multi-staged step, config 3 at full size.  Reference arithmetic: fp32 torch.nn.Linear under
 autograd (training/trainer.py:344-362)."""
@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from hotformerloc_amd import autograd as ag
 from hotformerloc_amd import build_batch_octree, load_config, model_factory, ops
+from hotformerloc_amd import model as M
 from hotformerloc_amd import synthetic as syn
 from hotformerloc_amd.model import set_gemm_mode, set_train_x6
 
@@ -93,7 +94,7 @@ def _grads(fn, tensors, dout):
 
 
 def test_linear_x6_fn_against_fp64_autograd():
-    """LinearX6Fn (forward / dx on hfl_linear_x6, dW / db on hfl_wgrad_f32): every gradient's rel-L2 error against fp64
+    """ag.linear_x6 (LinearFn, X6 family: forward / dx on hfl_linear_x6, dW / db on hfl_wgrad_f32): every gradient's rel-L2 error against fp64
     autograd at most 1.5x torch fp32 autograd's on the same data (with the 1e-6 floor of the wgrad test)."""
     g = torch.Generator(device=DEV).manual_seed(8)
     for m, k, n in ((20000, 256, 768), (4097, 128, 512), (300, 1024, 256)):
@@ -107,8 +108,40 @@ def test_linear_x6_fn_against_fp64_autograd():
         assert _rel(y6, y64) <= max(1.5 * _rel(y32, y64), 1e-6)
         for name, a, l, r in zip(('x', 'W', 'b'), g6, g32, g64):
             e, e32 = _rel(a, r), _rel(l, r)
-            print('LinearX6Fn M %d K %d N %d d%s: %.2e  fp32 autograd %.2e' % (m, k, n, name, e, e32))
+            print('linear_x6 M %d K %d N %d d%s: %.2e  fp32 autograd %.2e' % (m, k, n, name, e, e32))
             assert e <= max(1.5 * e32, 1e-6), (m, k, n, name, e, e32)
+    # the weight images these Functions multiply by live in the one store of model._W3_CACHE: the transposed x6 planes
+    # (dx = dy W) and the padded per-tap blocks of the live-tap convolution, both orientations
+    _check_image_cache(lambda t: ag._w6_cached(t, True), lambda t: ops.x6_pack(t.detach().t().contiguous()), (256, 128))
+    lin = torch.nn.Linear(128, 256).to(DEV)
+    assert M._w6(lin) is ag._w6_cached(lin.weight, False)             # one image for inference and training
+    for transposed in (True, False):
+        def want(t, transposed=transposed):
+            blocks = t.detach().transpose(1, 2) if transposed else t.detach()
+            pad = blocks.new_zeros(27, 128 - blocks.shape[1], blocks.shape[2])
+            return ops.x6_pack(torch.cat([blocks, pad], 1).reshape(27 * 128, -1).contiguous())
+        _check_image_cache(lambda t, transposed=transposed: ag._tap_blocks(t, transposed, 128), want, (27, 64, 64))
+
+
+def _check_image_cache(get, want, shape):
+    """cached on the second call; rebuilt, with no new entry, after an in-place update and after `.data` moved to new
+    storage (same version, new data_ptr: what module.to(device) does); gone from the store with the parameter"""
+    import gc
+    before = len(M._W3_CACHE)
+    p = torch.nn.Parameter(torch.randn(*shape, device=DEV) * 0.05)
+    a = get(p)
+    assert torch.equal(a, want(p)) and get(p) is a and len(M._W3_CACHE) == before + 1
+    with torch.no_grad():
+        p.add_(1.0)
+    b = get(p)
+    assert b is not a and torch.equal(b, want(p)) and len(M._W3_CACHE) == before + 1
+    version = p._version
+    p.data = p.data.clone() + 1
+    c = get(p)
+    assert p._version == version and c is not b and torch.equal(c, want(p)) and len(M._W3_CACHE) == before + 1
+    del p, a, b, c
+    gc.collect()
+    assert len(M._W3_CACHE) == before
 
 
 def _mlp_branch_ref(x, gamma, beta, w1, b1, w2, b2, s):
@@ -118,7 +151,7 @@ def _mlp_branch_ref(x, gamma, beta, w1, b1, w2, b2, s):
 
 @pytest.mark.parametrize('scaled', [False, True])
 def test_mlp_x6_functions_against_fp64_autograd(scaled):
-    """LnMlpResidualX6Fn (x + s * fc2(gelu(fc1(LN(x)))), s = the stochastic-depth row factor) and MlpX6Fn against fp64
+    """ag.ln_mlp_residual_x6 (x + s * fc2(gelu(fc1(LN(x)))), s = the stochastic-depth row factor) and ag.mlp_x6 against fp64
     autograd: x, W and b gradients within 1.5x torch fp32 autograd's error (1e-6 floor)."""
     g = torch.Generator(device=DEV).manual_seed(12 + scaled)
     for m, c in ((12000, 128), (5000, 256)):
@@ -149,14 +182,14 @@ def test_mlp_x6_functions_against_fp64_autograd(scaled):
         assert _rel(y6, y64) <= max(1.5 * _rel(y32, y64), 1e-6)
         for name, a, l, r in zip(names, g6, g32, g64):
             e, e32 = _rel(a, r), _rel(l, r)
-            print('LnMlpResidualX6Fn M %d C %d scaled %s d%s: %.2e  fp32 autograd %.2e' % (m, c, scaled, name, e, e32))
+            print('ln_mlp_residual_x6 M %d C %d scaled %s d%s: %.2e  fp32 autograd %.2e' % (m, c, scaled, name, e, e32))
             if name != 'gamma' and name != 'beta':
                 assert e <= max(1.5 * e32, 1e-6), (m, c, name, e, e32)
             else:                       # LayerNorm's parameters: the same HIP LayerNorm backward as the x3 path
                 assert e <= 1e-5, (m, c, name, e, e32)
         if scaled:
             continue
-        # MlpX6Fn: fc2(gelu(fc1(h))) alone (no LayerNorm, no residual)
+        # ag.mlp_x6: fc2(gelu(fc1(h))) alone (no LayerNorm, no residual)
         margs = (x, w1, b1, w2, b2)
         y6, g6 = _grads(ag.mlp_x6, margs, dout)
         mref = lambda x, w1, b1, w2, b2: F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)     # noqa: E731
@@ -165,7 +198,7 @@ def test_mlp_x6_functions_against_fp64_autograd(scaled):
         assert _rel(y6, y64) <= max(1.5 * _rel(y32, y64), 1e-6)
         for name, a, l, r in zip(('x', 'W1', 'b1', 'W2', 'b2'), g6, g32, g64):
             e, e32 = _rel(a, r), _rel(l, r)
-            print('MlpX6Fn M %d C %d d%s: %.2e  fp32 autograd %.2e' % (m, c, name, e, e32))
+            print('mlp_x6 M %d C %d d%s: %.2e  fp32 autograd %.2e' % (m, c, name, e, e32))
             assert e <= max(1.5 * e32, 1e-6), (m, c, name, e, e32)
 
 

@@ -212,6 +212,29 @@ def test_split_weight_cache_releases_with_the_parameter():
     del lin, w2, w3
     gc.collect()
     assert len(M._W3_CACHE) == before
+    # the training path's images live in the same store under the same rules (they once had a store of their own that
+    # ignored data_ptr and was only ever emptied wholesale): the transposed split3 image, dx = dy W of LinearSplitFn
+    from hotformerloc_amd import autograd as ag, ops
+    lin = torch.nn.Linear(64, 32)
+    w = lin.weight
+    t3 = ag._w3_cached(w, True)
+    assert t3.shape == (64, 96) and torch.equal(t3, ops.split_weight(w.detach().t().contiguous()))
+    assert ag._w3_cached(w, True) is t3 and len(M._W3_CACHE) == before + 1              # cached
+    assert ag._w3_cached(w, False) is M._w3(lin) and len(M._W3_CACHE) == before + 2      # one image for both files
+    with torch.no_grad():
+        w.add_(1.0)                                               # optimizer step: rebuilt in place
+    t3b = ag._w3_cached(w, True)
+    assert t3b is not t3 and torch.equal(t3b, ops.split_weight(w.detach().t().contiguous()))
+    assert len(M._W3_CACHE) == before + 2
+    version = w._version
+    w.data = w.data.clone() + 1                                   # what module.to(device) does: same version, new storage
+    assert w._version == version
+    t3c = ag._w3_cached(w, True)
+    assert t3c is not t3b and torch.equal(t3c, ops.split_weight(w.detach().t().contiguous()))
+    assert len(M._W3_CACHE) == before + 2
+    del lin, w, t3, t3b, t3c
+    gc.collect()
+    assert len(M._W3_CACHE) == before
 
 
 def test_tall_mm_split_k_weight_gradient_equals_autograd():
