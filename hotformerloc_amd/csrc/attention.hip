@@ -22,7 +22,6 @@
 #include "hfl_common.h"
 #include "x3_math.h"
 
-#include <cstring>
 #include <mutex>
 #include <vector>
 #include <type_traits>
@@ -55,7 +54,6 @@ struct WinParams {
   int qkv_f16;             // 1: qkv rows are the fp16 (hi, lo) attention operand layout of hfl_linear_x3_qkv (v5 kernel)
   const float* rpe2;       // (H, TS) expanded table of hfl_window_rpe_expand (v4), or null
   int depth;               // octree depth of the tokens (0 = unknown)
-  int dbg;                 // ablation bits (tools/kbench.py): 1 no softmax/MFMA, 2 no stores, 4 cached rows
 };
 
 // compiler-visible max of three (v5): the inline-asm form below is invisible to the hazard recogniser, and right behind a
@@ -411,8 +409,8 @@ window_attn_kernel_v2(const WinParams p) {
 //   * v_rcp_f32 instead of an IEEE divide, 32-bit byte offsets from the qkv / out base pointers
 //     (saddr + voffset addressing; the caller falls back to v2 when a buffer exceeds 4 GiB).
 // Occupancy target: 3 waves per SIMD (168 VGPRs) when the window has at most 3 token tiles (K = 48),
-// 2 otherwise (K = 64 needs ~190 VGPRs; forcing 3 spills).  Measured with back-to-back launches
-// (tools/kbench.py): 3 waves 109 us vs 2 waves + next-window register prefetch 161 us at depth 4 --
+// 2 otherwise (K = 64 needs ~190 VGPRs; forcing 3 spills).  Measured with back-to-back launches:
+// 3 waves 109 us vs 2 waves + next-window register prefetch 161 us at depth 4 --
 // the prefetch variant lost to plain occupancy and was dropped.
 constexpr int v4_waves_per_simd(int T, int G) { return (T - G) <= 3 ? 3 : 2; }
 
@@ -494,7 +492,6 @@ window_attn_kernel_v4(const WinParams p) {
         row = tok0 + (t * 16 + c) * tstep;
         ok = row < n_tok;
       }
-      if ((p.dbg & 4) && ok) row &= 63;
       if (ok) {
         const char* base = qkv_b + ((uint32_t)row * row_q + col_qk);
         qf[t] = *reinterpret_cast<const float4*>(base);
@@ -513,7 +510,6 @@ window_attn_kernel_v4(const WinParams p) {
           rv = tok0 + (t * 16 + 4 * g + r) * tstep;
           okv = rv < n_tok;
         }
-        if ((p.dbg & 4) && okv) rv &= 63;
         if (okv) vf[t][r] = *reinterpret_cast<const float*>(qkv_b + ((uint32_t)rv * row_q + col_v));
       }
     }
@@ -659,7 +655,7 @@ window_attn_kernel_v4(const WinParams p) {
         if (G > 0) o = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[T - 1][0], ert, o, 0, 0, 0);
         o *= inv;
         const int orow = qm.w;
-        if ((!MASKED || orow >= 0) && (!(p.dbg & 2) || o[0] == 1234.5f))
+        if (!MASKED || orow >= 0)
           att_store_row4(out_b, (uint32_t)orow, C, h * 16 + 4 * g, o, p.out_split);
       }
 
@@ -721,24 +717,10 @@ window_attn_kernel_v4(const WinParams p) {
         }
       }
     };
-    if (p.dbg & 1) {            // ablation: memory pattern only
-#pragma unroll
-      for (int qt = 0; qt < TW; ++qt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int orow = s_qry[qt * 16 + 4 * g + r].w;
-          if (orow >= 0 && !(p.dbg & 2)) {
-            const float v = qf[qt].x + kf[qt].y + vf[qt][r];
-            char* ob = out_b + ((uint32_t)orow * row_o);
-            if (p.out_split) {
-              att_store_split(reinterpret_cast<uint16_t*>(out_b), orow, C, h * 16 + c, v, p.out_split);
-            } else {
-              reinterpret_cast<float*>(ob)[h * 16 + c] = v;
-            }
-          }
-        }
-      if ((p.dbg & 2) && qf[0].x + kf[T - 1].y + vf[0][1] == 1234.5f) p.out[0] = 1.f;
-    } else if (homog)
+    // (compiler-only fence: the two instantiations of the body stay behind the window's loads and operand scaling instead of
+    // being merged into them -- without it the K = 48 + relay kernel spills four more registers at its 168-VGPR budget)
+    asm volatile("" ::: "memory");
+    if (homog)
       body(std::false_type{});
     else
       body(std::true_type{});
@@ -764,21 +746,7 @@ typedef _Float16 att_h8 __attribute__((ext_vector_type(8)));
 typedef short att_s4 __attribute__((ext_vector_type(4)));
 
 // RPE: 0 none, 1 expanded x + y-z tables (two lookups), 2 three clamped 1-D tables (deep octrees, three lookups)
-// probe (window_debug bit 3): s_memtime stamps of ONE wave (workgroup 0, wave 0) at the phase boundaries of its first 16 windows;
-// read back by hfl_internal_read_att_trace (tools/attn_trace.py)
-// (compiled in only with -DHFL_ATT_TRACE=1: `HFL_EXTRA_HIPCC_FLAGS=-DHFL_ATT_TRACE=1 python -m hotformerloc_amd.build`; the
-// branches cost the depth-5 launch 15 % even when the bit is off)
-#ifndef HFL_ATT_TRACE
-#define HFL_ATT_TRACE 0
-#endif
-__device__ unsigned long long g_att_trace[16 * 8];
-__device__ unsigned long long g_att_wg[4096 * 2];      // probe: s_memrealtime at the start and end of every workgroup
-#define HFL_ATT_STAMP(slot)                                                                      \
-  if (HFL_ATT_TRACE && trace_on) {                                                               \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                  \
-    if (it < 16 && lane == 0) g_att_trace[it * 8 + (slot)] = t_;                                 \
-  }
-
+//
 // (A variant that requested the NEXT window's fragments into a second register set before the softmax of the current one --
 // 2 waves per SIMD, <= 256 VGPRs, outputs held back so that no store sits in front of the next `s_waitcnt vmcnt(0)` -- was
 // neutral: 65.7 / 81.5 us against 68 / 80.5 us on the depth-5 / depth-4 launches; removed.)
@@ -823,7 +791,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int hw = tid >> 6;
-  const int wg_lin = blockIdx.y * gridDim.x + blockIdx.x;                // dispatch order (probes)
   const int gy = blockIdx.y;
   const int h = gy * nhw + hw;
   const int c = lane & 15, g = lane >> 4;
@@ -841,20 +808,14 @@ window_attn_kernel_v5(const WinMultiParams m) {
     reinterpret_cast<uint4*>(s_v + LP * 64)[i] = make_uint4(0u, 0u, 0u, 0u);
   const float mask2 = kMaskValue * 1.4426950408889634f;
   const float rt_add = (g == 0) ? 0.f : kDeadValue;   // the relay key lives in the g == 0 lanes only
-  // (probe build 3: head-group-major addressing of the SAME byte volume -- [head group][row][Q | K | V][heads of the group] --
-  // to price the operand layout; results are garbage)
-  const uint32_t hgw = (uint32_t)nhw * 64u;             // bytes of one region of one head group
-  const uint32_t row_q = HFL_ATT_TRACE == 3 ? 3u * hgw : (uint32_t)(3 * C) * 4u;       // bytes per qkv row (same as fp32 qkv)
+  const uint32_t row_q = (uint32_t)(3 * C) * 4u;       // bytes per qkv row (same as fp32 qkv)
   const char* qkv_b = reinterpret_cast<const char*>(p.qkv);
   char* out_b = reinterpret_cast<char*>(p.out);
-  const uint32_t rows_all = (uint32_t)(G > 0 ? p.rt_row0 + p.n_windows : p.n_tokens);
-  const uint32_t hg_base = HFL_ATT_TRACE == 3 ? (uint32_t)gy * rows_all * 3u * hgw : 0u;
   // this lane's 16-B chunk of the head's 64 B in the Q region (K and V: + C * 4, + C * 8)
-  const uint32_t col_l = HFL_ATT_TRACE == 3 ? hg_base + (uint32_t)hw * 64u + (uint32_t)(lane & 3) * 16u
-                                            : (uint32_t)h * 64u + (uint32_t)(lane & 3) * 16u;
+  const uint32_t col_l = (uint32_t)h * 64u + (uint32_t)(lane & 3) * 16u;
   // LDS block of the wave, 64-B rows: 16-B chunk j of row r sits in slot j ^ ((r >> 2) & 3), so that both the row-per-quad
   // accesses (lane l: row l >> 2, chunk l & 3) and the operand accesses (lane (c, g): row c, chunk g) are conflict-free
-  const uint32_t reg_k = HFL_ATT_TRACE == 3 ? hgw : (uint32_t)C * 4u;              // Q -> K -> V region stride
+  const uint32_t reg_k = (uint32_t)C * 4u;              // Q -> K -> V region stride
   const int st_quad = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) * 16);
   const int st_row = c * 64, st_x = (c >> 2) & 3;
   // transposed V reads: lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3 of its 4-key block
@@ -865,7 +826,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
   const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 
   const int tstep = p.D;
-  const bool nt_loads = (p.dbg & 16) != 0;
   // ---- request a window: metadata word + every fragment of this wave's head (index arithmetic only) ----------------
   // A quad of lanes reads ONE row's 64 B (lane l: row l >> 2 of the tile, 16-B chunk l & 3): 16 requests per load
   // instruction instead of the 64 of the MFMA operand mapping (lane (c, g): row c, chunk g -- four rows per quad), and the
@@ -893,32 +853,18 @@ window_attn_kernel_v5(const WinMultiParams m) {
       kr[t] = qr[t] = vr[t] = zero4;
       if (ok) {
         const char* base = qkv_b + (uint32_t)row * row_q + col_l;
-        if (nt_loads) {        // probe (window_debug bit 4): the operand rows are read once -- non-temporal loads
-          typedef unsigned int att_u4v __attribute__((ext_vector_type(4)));
-          const att_u4v a = __builtin_nontemporal_load(reinterpret_cast<const att_u4v*>(base));
-          const att_u4v b = __builtin_nontemporal_load(reinterpret_cast<const att_u4v*>(base + reg_k));
-          const att_u4v c = __builtin_nontemporal_load(reinterpret_cast<const att_u4v*>(base + 2u * reg_k));
-          qr[t] = make_uint4(a[0], a[1], a[2], a[3]);
-          kr[t] = make_uint4(b[0], b[1], b[2], b[3]);
-          vr[t] = make_uint4(c[0], c[1], c[2], c[3]);
-        } else {
-          qr[t] = *reinterpret_cast<const uint4*>(base);
-          kr[t] = *reinterpret_cast<const uint4*>(base + reg_k);
-          vr[t] = *reinterpret_cast<const uint4*>(base + 2u * reg_k);
-        }
+        qr[t] = *reinterpret_cast<const uint4*>(base);
+        kr[t] = *reinterpret_cast<const uint4*>(base + reg_k);
+        vr[t] = *reinterpret_cast<const uint4*>(base + 2u * reg_k);
       }
     }
   };
-  const bool trace_on = HFL_ATT_TRACE && (p.dbg & 8) && blockIdx.x == 0 && blockIdx.y == 0 && hw == 0;
-  if (HFL_ATT_TRACE && (p.dbg & 8) && tid == 0 && wg_lin < 4096) g_att_wg[2 * wg_lin] = __builtin_amdgcn_s_memrealtime();
   int it = 0;
   for (int w = wg_x; w < p.n_windows; w += wg_nx, ++it) {
     const int tok0 = (p.D == 1) ? w * K : (w / p.D) * K * p.D + (w % p.D);
     const int rt_row = (int)p.rt_row0 + w;
     uint2 mt;
     uint4 kr[T], qr[T], vr[T];
-    HFL_ATT_STAMP(0)
-    if (HFL_ATT_TRACE && trace_on && it < 16 && lane == 0) g_att_trace[it * 8 + 7] = __builtin_amdgcn_s_memrealtime();     // 100 MHz
     request(w, mt, kr, qr, vr);
     int4* s_qry = s_qry0 + (it & 1) * LP;
     int2* s_key = s_key0 + (it & 1) * LP;
@@ -963,7 +909,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
 #pragma unroll
     for (int t = 0; t < T; ++t) *reinterpret_cast<uint4*>(s_v + t * 1024 + lane * 16) = vr[t];
     __syncthreads();
-    HFL_ATT_STAMP(1)
     const int bid0 = s_kbid[0], bidl = s_kbid[K - 1];
     const int rt_bid = bid0 >= 0 ? bid0 : p.batch;     // the relay token carries the id of the window's first token
     const bool homog = __builtin_amdgcn_readfirstlane((bidl >= 0 && bid0 == bidl) ? 1 : 0) != 0;
@@ -998,8 +943,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
         }
     }
 
-    HFL_ATT_STAMP(2)
-
     auto body = [&](auto masked_tag) {
       constexpr bool MASKED = decltype(masked_tag)::value;
 #pragma unroll
@@ -1011,14 +954,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
         const int qxa = qm.x + tabb, qyza = qm.y + (RPE == 2 ? tabb * 0x10001 : tabb);
         const att_h8 bqh = __builtin_bit_cast(att_h8, qh[qt]);
         const att_h8 bql = __builtin_bit_cast(att_h8, ql[qt]);
-        if (HFL_ATT_TRACE >= 2) {      // probe build: the kernel's memory pattern alone (every load consumed, every row stored)
-          const uint4 m = make_uint4(ka[qt].x ^ qh[qt].x ^ ql[qt].x ^ (uint32_t)vhi[qt / 2][0], ka[qt].y ^ qh[qt].y ^ ql[qt].y,
-                                     ka[qt].z ^ qh[qt].z ^ ql[qt].z, ka[qt].w ^ qh[qt].w ^ ql[qt].w);
-          const int orow_m = is_rt ? (c == 0 ? rt_row : -1) : qm.w;
-          if (orow_m >= 0)
-            att_store_row4(out_b, (uint32_t)orow_m, C, h * 16 + 4 * g, __builtin_bit_cast(f32x4, m), p.out_split);
-          continue;
-        }
 
         f32x4 s[T];
 #pragma unroll
@@ -1144,10 +1079,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
         } else if (orow >= 0) {
           att_store_row4(out_b, (uint32_t)orow, C, h * 16 + 4 * g, o, p.out_split);
         }
-        if (HFL_ATT_TRACE && trace_on) {        // the stamp must not float above the tile: tie it to the tile's result
-          const unsigned long long t_ = __builtin_amdgcn_s_memtime() + (o[0] == 1234.5f ? 1 : 0);
-          if (it < 16 && lane == 0 && qt < 5) g_att_trace[it * 8 + 3 + qt] = t_;
-        }
       }
     };
     if (homog)
@@ -1155,7 +1086,6 @@ window_attn_kernel_v5(const WinMultiParams m) {
     else
       body(std::true_type{});
   }
-  if (HFL_ATT_TRACE && (p.dbg & 8) && tid == 0 && wg_lin < 4096) g_att_wg[2 * wg_lin + 1] = __builtin_amdgcn_s_memrealtime();
 }
 
 // expanded RPE table of v4: out (H, TS), TS = (W + W*W + 3) & ~3, W = 2R+1, R = 2^depth - 1 <= pos_bnd:
@@ -1201,13 +1131,13 @@ rpe_expand3_kernel(float* __restrict__ out, const float* __restrict__ table, int
   out[i] = v * 1.4426950408889634f;
 }
 
-// which expanded form a (depth, pos_bnd) pair takes: 1 = x table + y-z table (no clamp needed, depth <= 5), 2 = three
-// clamped 1-D tables (depth <= 7), 0 = none (the three-lookup kernel v2 reads the original table)
-// which expanded form a (depth, pos_bnd) pair takes, per consumer: the fp32 kernel (v4) knows form 1 only; the fp16 kernel (v5)
-// takes form 1 up to depth 4 and form 2 beyond -- at depth 5 the (2R+1)^2 y-z table is 16 KB per head, which left room for
-// 6 waves per CU only; the three 1-D tables (768 B per head) let 12 stay resident: 61.5 -> 53 us on the depth-5 bench launch
-// in spite of the third lookup (at depth 4, 4 KB per head, form 1 is the faster one: 70 vs 73 us)
-static int g_rpe_form1_max_depth = 4;       // probe knob 'window_rpe_form1_max_depth' (fp16 kernel)
+// Which expanded table form a (depth, pos_bnd) pair takes, per consumer: 1 = x table + y-z table (two lookups; no clamp needed,
+// so depth <= 5 and 2^depth - 1 <= pos_bnd), 2 = three clamped 1-D tables (depth <= 7), 0 = none (the three-lookup kernel v2
+// reads the original table).  The fp32 kernel (v4) knows form 1 only.  The fp16 kernel (v5) takes form 1 up to depth 4 and
+// form 2 beyond -- at depth 5 the (2R+1)^2 y-z table is 16 KB per head, which left room for 6 waves per CU only; the three 1-D
+// tables (768 B per head) let 12 stay resident: 61.5 -> 53 us on the depth-5 bench launch in spite of the third lookup (at
+// depth 4, 4 KB per head, form 1 is the faster one: 70 vs 73 us).
+static int g_rpe_form1_max_depth = 4;       // hfl_set_variant "window_rpe_form1_max_depth" (fp16 kernel; the tests run form 2 at every depth)
 static inline int rpe_form(int depth, int bnd, int f16) {
   if (depth < 1 || depth > 7) return 0;
   const bool fits = depth <= 5 && ((1 << depth) - 1) <= bnd;
@@ -1221,17 +1151,69 @@ static inline size_t rpe_form_floats(int depth, int bnd, int f16) {      // per 
   return f == 1 ? (size_t)((W + W * W + 3) & ~3) : f == 2 ? (size_t)((3 * W + 3) & ~3) : 0;
 }
 
-static int g_window_variant = 4;
-static int g_window_v4_wgs_per_cu = 1;   // multiples of the resident workgroup count
-static int g_window_dbg = 0;
-static int g_window_v2_wgs_per_cu = 16;
-static int g_window_heads_per_wg = 4;
-static int g_relay_fast = 1;            // probe (hfl_set_variant "relay_fast")
-static int g_window_bwd_rt = -1;        // probe ("window_bwd_rt"): 0 forces the scatter-add table gradient of the backward
+static int g_window_variant = 4;        // hfl_set_variant "window_attention": != 4 keeps the fp32 and fp16 kernels (v4, v5) out
+static int g_relay_fast = 1;            // "relay_fast": 0 = the general loop of relay_attn_f16_kernel for every length
+static int g_window_bwd_rt = -1;        // "window_bwd_rt": 0 forces the scatter-add table gradient of the backward
 
-// fp16 (hi, lo) operand layout: only the v5 kernel reads it (callers ask hfl_window_attention_f16_ok first).  `n` problems of
-// one shape in ONE launch (see WinMultiParams); HFL_EINVAL when they cannot share a launch (the caller then launches them
-// one by one).  Heads per workgroup: 4, or 2 when the expanded RPE tables of 4 heads do not leave room in LDS.
+// heads (= waves) per workgroup of the window kernels: 4 when the head count allows it
+static inline int win_heads_per_wg(int H) { return H % 4 == 0 ? 4 : H % 2 == 0 ? 2 : 1; }
+
+// The window kernels are instantiated for (T, G) = (16-row tiles per window with the relay tile, relay tokens per window):
+// K = 16 .. 64 tokens, with or without one relay token.  Calls f(integral_constant<int, T>, integral_constant<int, G>) for such
+// a shape and returns `none` for every other.
+template <typename F>
+static int win_dispatch(int T, int G, int none, F&& f) {
+  using std::integral_constant;
+  if (G == 0) {
+    switch (T) {
+      case 1: return f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+      case 2: return f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
+      case 3: return f(integral_constant<int, 3>{}, integral_constant<int, 0>{});
+      case 4: return f(integral_constant<int, 4>{}, integral_constant<int, 0>{});
+      default: return none;
+    }
+  }
+  if (G != 1) return none;
+  switch (T) {
+    case 2: return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+    case 3: return f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
+    case 4: return f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    case 5: return f(integral_constant<int, 5>{}, integral_constant<int, 1>{});
+    default: return none;
+  }
+}
+
+// Launch geometry of the fp16 window kernel (v5) for one attention problem, and whether the kernel takes the problem at all:
+// launch_window_v5 and hfl_window_attention_f16_ok both come here, so the launcher cannot refuse what the predicate accepted.
+struct V5Geom {
+  int form;        // expanded RPE table form (0: the problem has no table)
+  int hpw;         // heads (= waves) per workgroup: 4, or 2 when the tables of 4 heads crowd the LDS
+  size_t lds;      // dynamic LDS bytes of a workgroup
+};
+static bool v5_geometry(int T, int H, int depth, int bnd, bool has_table, int64_t rows_total, V5Geom* g) {
+  if (T < 1 || T > 5 || H <= 0 || depth < 1 || depth > 7) return false;
+  const int LP = T * 16, NP = (T + 1) / 2;
+  const int form = has_table ? rpe_form(depth, bnd, 1) : 0;
+  const size_t ts = has_table ? rpe_form_floats(depth, bnd, 1) : 0;         // table floats per head
+  if (has_table && form == 0) return false;
+  // per workgroup: double-buffered window metadata | the heads' tables | the waves' operand / V image blocks
+  auto lds_of = [&](int hpw) { return (size_t)2 * LP * (16 + 8 + 4) + (size_t)hpw * ts * 4 + (size_t)hpw * (2 * NP * 16) * 64; };
+  int hpw = win_heads_per_wg(H);
+  size_t lds = lds_of(hpw);
+  if (lds > 72 * 1024 && hpw == 4) {
+    hpw = 2;
+    lds = lds_of(hpw);
+  }
+  if (lds > 72 * 1024 || hpw * 64 < LP) return false;                       // (every window slot has a thread of its own)
+  const int W = 2 * ((1 << depth) - 1) + 1;
+  if (form == 2 && (size_t)hpw * ts * 4 + 12 * (size_t)W >= 65536) return false;      // two LDS addresses packed in one register
+  if (rows_total * 3 * H * 16 * 4 >= (int64_t)1 << 32) return false;       // 32-bit byte offsets from the qkv / out pointers
+  g->form = form;
+  g->hpw = hpw;
+  g->lds = lds;
+  return true;
+}
+
 // per-launch HIP events around the v5 launches (bench.py's roofline leg times the launches the product path really issues --
 // including those inside hfl_block_forward_x3 / hfl_block_attention_x3_multi, which no Python-side timer sees)
 struct AttnTimingRec {
@@ -1247,50 +1229,38 @@ static void attn_rec_drop(AttnTimingRec& r) {
   r.e0 = r.e1 = nullptr;
 }
 
+// fp16 (hi, lo) operand layout: only the v5 kernel reads it (callers ask hfl_window_attention_f16_ok first).  `n` problems of
+// one shape in ONE launch (see WinMultiParams); HFL_EINVAL when they cannot share a launch (the caller then launches them
+// one by one).
 template <int T, int G>
 static int launch_window_v5(const WinParams* ps, int n, hipStream_t s) {
-  constexpr int LP = T * 16;
-  constexpr int np5 = (T + 1) / 2;
   if (n < 1 || n > kWinMulti) return HFL_EINVAL;
-  int form0 = 0, hp0 = 0;
+  V5Geom g0{};
   size_t lds_max = 0;
   int64_t windows = 0;
   for (int i = 0; i < n; ++i) {
     const WinParams& p = ps[i];
-    int hpw = g_window_heads_per_wg;             // heads (= waves) per workgroup, at most 4
-    if (hpw < 1 || hpw > 4 || p.H % hpw != 0) hpw = (p.H % 4 == 0) ? 4 : (p.H % 2 == 0) ? 2 : 1;
     const int64_t rows_total = G > 0 ? p.rt_row0 + p.n_windows : p.n_tokens;
-    const int form = p.table ? rpe_form(p.depth, p.bnd, 1) : 0;
-    const size_t ts5 = p.table ? rpe_form_floats(p.depth, p.bnd, 1) : 0;
-    int hp5 = hpw;
-    size_t lds5 = 0;
-    for (;; hp5 >>= 1) {
-      lds5 = (size_t)2 * LP * (16 + 8 + 4) + (size_t)hp5 * ts5 * 4 + (size_t)hp5 * (2 * np5 * 16) * 64;
-      if (lds5 <= 72 * 1024 || hp5 <= 2 || p.H % (hp5 / 2) != 0) break;
-    }
-    const int W5 = 2 * ((1 << (p.depth > 0 && p.depth <= 7 ? p.depth : 0)) - 1) + 1;
-    if (!p.qkv_f16 || p.depth < 1 || p.depth > 7 || (p.table != nullptr && (p.rpe2 == nullptr || form == 0)) ||
-        (p.table == nullptr && p.depth > 10) || (form == 2 && (size_t)hp5 * ts5 * 4 + 12 * (size_t)W5 >= 65536) ||
-        rows_total * 3 * p.H * 16 * 4 >= (int64_t)1 << 32 || lds5 > 72 * 1024 || hp5 * 64 < LP || p.qkv_bias != nullptr ||
-        p.n_windows < 1)
+    V5Geom g;
+    if (!p.qkv_f16 || p.qkv_bias != nullptr || p.n_windows < 1 || (p.table != nullptr && p.rpe2 == nullptr) ||
+        !v5_geometry(T, p.H, p.depth, p.bnd, p.table != nullptr, rows_total, &g))
       return HFL_EINVAL;
-    if (i == 0) {
-      form0 = form;
-      hp0 = hp5;
-    } else if (form != form0 || hp5 != hp0 || p.H != ps[0].H || p.K != ps[0].K) {
+    if (i == 0)
+      g0 = g;
+    else if (g.form != g0.form || g.hpw != g0.hpw || p.H != ps[0].H || p.K != ps[0].K)
       return HFL_EINVAL;
-    }
-    if (lds5 > lds_max) lds_max = lds5;
+    if (g.lds > lds_max) lds_max = g.lds;
     windows += p.n_windows;
   }
+  const int hp0 = g0.hpw;
   const int groups5 = ps[0].H / hp0;
-  // persistent grid: exactly the workgroups that are resident at once (waves-per-SIMD target of the kernel, LDS), times
-  // g_window_v4_wgs_per_cu, dealt to the problems in proportion to their windows (at least one each)
+  // persistent grid: exactly the workgroups that are resident at once (waves-per-SIMD target of the kernel, LDS), dealt to the
+  // problems in proportion to their windows (at least one each)
   int resident = v4_waves_per_simd(T, G) * 4 / hp0;
   const int lds_fit = (int)((size_t)160 * 1024 / (lds_max + 512));
   if (resident > lds_fit) resident = lds_fit;
   if (resident < 1) resident = 1;
-  int64_t px = (int64_t)hfl_stream_cus(s) * resident * g_window_v4_wgs_per_cu / groups5;
+  int64_t px = (int64_t)hfl_stream_cus(s) * resident / groups5;
   if (px < n) px = n;
   WinMultiParams m;
   m.n = n;
@@ -1308,13 +1278,6 @@ static int launch_window_v5(const WinParams* ps, int n, hipStream_t s) {
   }
   dim3 grid5((unsigned)m.first[n], (unsigned)groups5);
   hipError_t e;
-#define HFL_V5_LAUNCH(F)                                                                                  \
-  {                                                                                                       \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v5<T, G, F>),                \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);                    \
-    if (e != hipSuccess) return (int)e;                                                                   \
-    window_attn_kernel_v5<T, G, F><<<grid5, hp0 * 64, lds_max, s>>>(m);                                   \
-  }
   AttnTimingRec rec{};
   if (g_attn_timing) {
     // algorithmic bytes: q, k, v read + out written = 16 B per (row, channel); 4 L^2 C FLOP per window
@@ -1340,7 +1303,6 @@ static int launch_window_v5(const WinParams* ps, int n, hipStream_t s) {
     if (timed) attn_rec_drop(rec); \
     return (int)e;              \
   }
-#undef HFL_V5_LAUNCH
 #define HFL_V5_LAUNCH(F)                                                                                  \
   {                                                                                                       \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v5<T, G, F>),                \
@@ -1348,7 +1310,7 @@ static int launch_window_v5(const WinParams* ps, int n, hipStream_t s) {
     HFL_V5_FAIL_IF(e != hipSuccess)                                                                       \
     window_attn_kernel_v5<T, G, F><<<grid5, hp0 * 64, lds_max, s>>>(m);                                   \
   }
-  if (form0 == 0) HFL_V5_LAUNCH(0) else if (form0 == 1) HFL_V5_LAUNCH(1) else HFL_V5_LAUNCH(2)
+  if (g0.form == 0) HFL_V5_LAUNCH(0) else if (g0.form == 1) HFL_V5_LAUNCH(1) else HFL_V5_LAUNCH(2)
 #undef HFL_V5_LAUNCH
   if (timed) {
     e = hipEventRecord(rec.e1, s);
@@ -1363,59 +1325,54 @@ static int launch_window_v5(const WinParams* ps, int n, hipStream_t s) {
 template <int T, int G>
 static int launch_window(const WinParams& p, hipStream_t s) {
   constexpr int LP = T * 16;
+  if (p.qkv_f16) return launch_window_v5<T, G>(&p, 1, s);
   const int nrpe = 2 * p.bnd + 1;
-  int blocks = p.n_windows;
-  const int cap = hfl_stream_cus(s) * 4;
-  if (blocks > cap) blocks = cap;
-  {
-    int hpw = g_window_heads_per_wg;             // heads (= waves) per workgroup, at most 4
-    if (hpw < 1 || hpw > 4 || p.H % hpw != 0) hpw = (p.H % 4 == 0) ? 4 : (p.H % 2 == 0) ? 2 : 1;
-    const size_t lds = (p.table ? (size_t)hpw * 3 * nrpe * 4 : 0) + (size_t)LP * (16 + 16 + 4);
-    const int groups = p.H / hpw;
-    int bx = p.n_windows;
-    const int capx = hfl_stream_cus(s) * g_window_v2_wgs_per_cu / groups;
-    if (bx > capx) bx = capx;
-    dim3 grid((unsigned)bx, (unsigned)groups);
-    const int64_t rows_total = G > 0 ? p.rt_row0 + p.n_windows : p.n_tokens;
-    const int R4 = (1 << (p.depth > 0 && p.depth <= 5 ? p.depth : 0)) - 1, W4 = 2 * R4 + 1;
-    const size_t ts4 = p.table ? (size_t)((W4 + W4 * W4 + 3) & ~3) : 0;
-    const size_t lds4 = (size_t)2 * LP * (16 + 8 + 4) + (size_t)hpw * ts4 * 4;
-    if (p.qkv_f16) {
-      return launch_window_v5<T, G>(&p, 1, s);
-    } else if (g_window_variant == 4 && !p.clamp && p.depth >= 1 && p.depth <= 5 &&
-        (p.table == nullptr || p.rpe2 != nullptr) && rows_total * 3 * p.H * 16 * 4 < (int64_t)1 << 32 &&
-        lds4 <= 72 * 1024 && hpw * 64 >= LP) {
-      // persistent grid: exactly the workgroups that are resident at once (waves-per-SIMD target of
-      // the kernel, LDS), times g_window_v4_wgs_per_cu
-      int resident = v4_waves_per_simd(T, G) * 4 / hpw;
-      const int lds_fit = (int)((size_t)160 * 1024 / (lds4 + 512));
-      if (resident > lds_fit) resident = lds_fit;
-      if (resident < 1) resident = 1;
-      int px = hfl_stream_cus(s) * resident * g_window_v4_wgs_per_cu / groups;
-      if (px < 1) px = 1;
-      if (px > p.n_windows) px = p.n_windows;
-      dim3 grid4((unsigned)px, (unsigned)groups);
-      if (lds4 > 48 * 1024) {
-        hipError_t e;
-        if (p.table == nullptr)
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v4<T, G, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-        else
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v4<T, G, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-        if (e != hipSuccess) return (int)e;
-      }
+  const int hpw = win_heads_per_wg(p.H);
+  const int groups = p.H / hpw;
+  const int64_t rows_total = G > 0 ? p.rt_row0 + p.n_windows : p.n_tokens;
+  const int R4 = (1 << (p.depth > 0 && p.depth <= 5 ? p.depth : 0)) - 1, W4 = 2 * R4 + 1;
+  const size_t ts4 = p.table ? (size_t)((W4 + W4 * W4 + 3) & ~3) : 0;
+  const size_t lds4 = (size_t)2 * LP * (16 + 8 + 4) + (size_t)hpw * ts4 * 4;
+  if (g_window_variant == 4 && !p.clamp && p.depth >= 1 && p.depth <= 5 &&
+      (p.table == nullptr || p.rpe2 != nullptr) && rows_total * 3 * p.H * 16 * 4 < (int64_t)1 << 32 &&
+      lds4 <= 72 * 1024 && hpw * 64 >= LP) {
+    // persistent grid: exactly the workgroups that are resident at once (waves-per-SIMD target of the kernel, LDS)
+    int resident = v4_waves_per_simd(T, G) * 4 / hpw;
+    const int lds_fit = (int)((size_t)160 * 1024 / (lds4 + 512));
+    if (resident > lds_fit) resident = lds_fit;
+    if (resident < 1) resident = 1;
+    int px = hfl_stream_cus(s) * resident / groups;
+    if (px < 1) px = 1;
+    if (px > p.n_windows) px = p.n_windows;
+    dim3 grid4((unsigned)px, (unsigned)groups);
+    if (lds4 > 48 * 1024) {
+      hipError_t e;
       if (p.table == nullptr)
-        window_attn_kernel_v4<T, G, false><<<grid4, hpw * 64, lds4, s>>>(p);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v4<T, G, false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
       else
-        window_attn_kernel_v4<T, G, true><<<grid4, hpw * 64, lds4, s>>>(p);
-    } else if (p.table == nullptr)
-      window_attn_kernel_v2<T, G, false, false><<<grid, hpw * 64, lds, s>>>(p);
-    else if (p.clamp)
-      window_attn_kernel_v2<T, G, true, true><<<grid, hpw * 64, lds, s>>>(p);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_kernel_v4<T, G, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+      if (e != hipSuccess) return (int)e;
+    }
+    if (p.table == nullptr)
+      window_attn_kernel_v4<T, G, false><<<grid4, hpw * 64, lds4, s>>>(p);
     else
-      window_attn_kernel_v2<T, G, false, true><<<grid, hpw * 64, lds, s>>>(p);
+      window_attn_kernel_v4<T, G, true><<<grid4, hpw * 64, lds4, s>>>(p);
+    HFL_RETURN_LAST_ERROR();
   }
+  // v2 (clamped coordinates, deep levels, buffers beyond 4 GiB): 16 workgroups per CU
+  const size_t lds = (p.table ? (size_t)hpw * 3 * nrpe * 4 : 0) + (size_t)LP * (16 + 16 + 4);
+  int bx = p.n_windows;
+  const int capx = hfl_stream_cus(s) * 16 / groups;
+  if (bx > capx) bx = capx;
+  dim3 grid((unsigned)bx, (unsigned)groups);
+  if (p.table == nullptr)
+    window_attn_kernel_v2<T, G, false, false><<<grid, hpw * 64, lds, s>>>(p);
+  else if (p.clamp)
+    window_attn_kernel_v2<T, G, true, true><<<grid, hpw * 64, lds, s>>>(p);
+  else
+    window_attn_kernel_v2<T, G, false, true><<<grid, hpw * 64, lds, s>>>(p);
   HFL_RETURN_LAST_ERROR();
 }
 
@@ -1669,25 +1626,15 @@ relay_attn_f16_kernel(unsigned char* __restrict__ out2, const unsigned char* __r
 
 extern "C" {
 
-extern "C" void hfl_internal_set_cpe_chunk(int rows);
-/* tuning / A-B hook: select kernel variants at run time (key "window_attention": 1 | 2) */
-void hfl_internal_set_x3_dbg(int v);
-void hfl_internal_set_window_bwd(int v);
-void hfl_internal_set_mlp_stagger(int v);
-#ifdef HFL_PROBES
-void hfl_internal_set_mlp_dbg(int v);
-#endif
-void hfl_internal_set_mlp_tail_split(int v);
-void hfl_internal_set_mlp_dynamic(int v);
-void hfl_internal_set_attn_fused_split(int v);
-void hfl_internal_set_ws_map(int v);
-#ifdef HFL_PROBES
-void hfl_internal_set_ws_dbg(int v);
-#endif
-void hfl_internal_set_qkv_tail_split(int v);
-// bench.py: switch the per-launch timing of the fp16 window kernel on / off (both drop what was recorded) ...
 int hfl_internal_rpe_form(int depth, int bnd, int f16) { return rpe_form(depth, bnd, f16); }     // (csrc/attn_fused.hip)
 
+// what hfl_set_variant (csrc/capi.hip) keeps of the kernel selection: see the globals above
+void hfl_internal_set_window_variant(int v) { g_window_variant = v; }
+void hfl_internal_set_rpe_form1_max_depth(int v) { g_rpe_form1_max_depth = v; }
+void hfl_internal_set_relay_fast(int v) { g_relay_fast = v; }
+void hfl_internal_set_window_bwd_rt(int v) { g_window_bwd_rt = v; }
+
+// bench.py: switch the per-launch timing of the fp16 window kernel on / off (both drop what was recorded) ...
 int hfl_internal_attn_timing(int on) {
   std::lock_guard<std::mutex> lk(g_attn_mu);
   for (auto& r : g_attn_recs) attn_rec_drop(r);
@@ -1711,109 +1658,16 @@ int hfl_internal_attn_timing_read(double* ms, double* bytes, double* flops, int 
   }
   return (int)g_attn_recs.size();
 }
-#if HFL_ATT_TRACE          // (probe build only: tools/attn_trace.py)
-int hfl_internal_read_att_trace(unsigned long long* host, int n) {
-  if (n > 16 * 8) n = 16 * 8;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_att_trace), (size_t)n * 8);
-}
-int hfl_internal_read_att_wg(unsigned long long* host, int n) {
-  if (n > 4096 * 2) n = 4096 * 2;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_att_wg), (size_t)n * 8);
-}
-#endif
-int hfl_set_variant(const char* key, int value) {
-  if (key == nullptr) return HFL_EINVAL;
-  auto is = [key](const char* name) { return strcmp(key, name) == 0; };
-  if (is("reset")) {                             // every probe knob back to its default (tests call it around each case)
-    g_window_variant = 4;
-    g_window_v4_wgs_per_cu = 1;
-    g_window_dbg = 0;
-    hfl_internal_attn_timing(0);
-    g_rpe_form1_max_depth = 4;
-    g_window_v2_wgs_per_cu = 16;
-    g_window_heads_per_wg = 4;
-    g_relay_fast = 1;
-    g_window_bwd_rt = -1;
-    hfl_internal_set_window_bwd(2);
-    hfl_internal_set_x3_dbg(0);
-    hfl_internal_set_x3_dbg(0x100);
-    hfl_internal_set_cpe_chunk(-1);
-    hfl_internal_set_mlp_stagger(1 | (8 << 8));
-#ifdef HFL_PROBES
-    hfl_internal_set_mlp_dbg(0);
-#endif
-    hfl_internal_set_mlp_tail_split(1);
-    hfl_internal_set_qkv_tail_split(1);
-    hfl_internal_set_mlp_dynamic(1);
-  } else if (is("attn_fused_split")) {
-    hfl_internal_set_attn_fused_split(value);
-  } else if (is("ws_map")) {
-    hfl_internal_set_ws_map(value);
-#ifdef HFL_PROBES
-  } else if (is("ws_dbg")) {
-    hfl_internal_set_ws_dbg(value);
-#endif
-  } else if (is("dynamic_units")) {
-    hfl_internal_set_mlp_dynamic(value);
-  } else if (is("tail_split")) {
-    hfl_internal_set_mlp_tail_split(value);
-    hfl_internal_set_qkv_tail_split(value);
-#ifdef HFL_PROBES
-  } else if (is("mlp_dbg")) {
-    hfl_internal_set_mlp_dbg(value);
-#endif
-  } else if (is("mlp_stagger")) {
-    hfl_internal_set_mlp_stagger(value);
-  } else if (is("window_attention")) {
-    g_window_variant = value;
-  } else if (is("window_bwd")) {
-    hfl_internal_set_window_bwd(value);
-  } else if (is("x3_dbg")) {
-    hfl_internal_set_x3_dbg(value);
-  } else if (is("cpe_chunk_rows")) {
-    hfl_internal_set_cpe_chunk(value);
-  } else if (is("window_debug")) {
-    g_window_dbg = value;
-  } else if (is("window_rpe_form1_max_depth")) {
-    g_rpe_form1_max_depth = value;
-  } else if (is("window_v4_wgs_per_cu")) {
-    g_window_v4_wgs_per_cu = value;
-  } else if (is("window_v2_wgs_per_cu")) {
-    g_window_v2_wgs_per_cu = value;
-  } else if (is("window_heads_per_wg")) {
-    g_window_heads_per_wg = value;
-  } else if (is("relay_fast")) {                      // probe: 0 = the general loop of relay_attn_f16_kernel for every length
-    g_relay_fast = value;
-  } else if (is("window_bwd_rt")) {                   // probe: 0 = scatter-add table gradient in the attention backward
-    g_window_bwd_rt = value;
-  } else {
-    return HFL_EINVAL;
-  }
-  return HFL_OK;
-}
 
 /* 1 when hfl_window_attention_fwd_ex accepts the fp16 (hi, lo) qkv operand layout (flag 0x100) for this launch
- * configuration: the v5 kernel needs the expanded RPE table (depth <= 5, no clamp) and <= 72 KiB of LDS */
+ * configuration: what the v5 launcher itself asks (v5_geometry), for a problem with an RPE table */
 int hfl_window_attention_f16_ok(const hfl_window_attn_desc* d, int64_t n_rows_total) {
   if (d == nullptr || d->n_heads <= 0 || d->patch_size % 16 != 0) return 0;
-  if (rpe_form(d->depth, d->pos_bnd, 1) == 0) return 0;
   if (g_window_variant != 4) return 0;
   const int T = d->patch_size / 16 + d->n_relay;
-  if (T < 1 || T > 5) return 0;
-  int hpw = g_window_heads_per_wg;
-  if (hpw < 1 || hpw > 4 || d->n_heads % hpw != 0) hpw = (d->n_heads % 4 == 0) ? 4 : (d->n_heads % 2 == 0) ? 2 : 1;
-  const int LP = T * 16;
-  const size_t ts5 = rpe_form_floats(d->depth, d->pos_bnd, 1);
-  size_t lds5 = 0;
-  for (;; hpw >>= 1) {        // as the launcher: 4 heads per workgroup, or 2 when their tables crowd the LDS
-    lds5 = (size_t)2 * LP * (16 + 8 + 4) + (size_t)hpw * ts5 * 4 + (size_t)hpw * (2 * ((T + 1) / 2) * 16) * 64;
-    if (lds5 <= 72 * 1024 || hpw <= 2 || d->n_heads % (hpw / 2) != 0) break;
-  }
-  const int W5 = 2 * ((1 << d->depth) - 1) + 1;
-  if (rpe_form(d->depth, d->pos_bnd, 1) == 2 && (size_t)hpw * ts5 * 4 + 12 * (size_t)W5 >= 65536) return 0;
-  if (lds5 > 72 * 1024 || hpw * 64 < LP) return 0;
-  if (n_rows_total * 3 * d->n_heads * 16 * 4 >= (int64_t)1 << 32) return 0;
-  return 1;
+  if (win_dispatch(T, d->n_relay, 0, [](auto, auto) { return 1; }) == 0) return 0;       // no kernel of that shape
+  V5Geom g;
+  return v5_geometry(T, d->n_heads, d->depth, d->pos_bnd, true, n_rows_total, &g) ? 1 : 0;
 }
 
 int hfl_window_attention_fwd(float* out, const float* qkv, const uint32_t* tok_meta,
@@ -1842,7 +1696,6 @@ static int win_params(WinParams& p, bool* empty, void* out, const float* qkv, co
   p.qkv_f16 = (out_split3 >> 8) & 1;
   p.rpe2 = rpe_table != nullptr ? d->rpe_expanded : nullptr;
   p.depth = d->depth;
-  p.dbg = g_window_dbg;
   p.n_tokens = d->n_tokens; p.rt_row0 = d->rt_row0; p.n_windows = d->n_windows;
   p.K = d->patch_size; p.D = d->dilation; p.H = d->n_heads; p.bnd = d->pos_bnd;
   p.batch = d->batch_size; p.scale = d->scale;
@@ -1875,24 +1728,9 @@ int hfl_window_attention_fwd_multi(int n, void* const* out, const float* const* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = HFL_EINVAL;
   if (same && live > 1) {
-    const int T = ps[0].K / 16 + desc[0]->n_relay;
-    if (desc[0]->n_relay == 0) {
-      switch (T) {
-        case 1: rc = launch_window_v5<1, 0>(ps, live, s); break;
-        case 2: rc = launch_window_v5<2, 0>(ps, live, s); break;
-        case 3: rc = launch_window_v5<3, 0>(ps, live, s); break;
-        case 4: rc = launch_window_v5<4, 0>(ps, live, s); break;
-        default: break;
-      }
-    } else {
-      switch (T) {
-        case 2: rc = launch_window_v5<2, 1>(ps, live, s); break;
-        case 3: rc = launch_window_v5<3, 1>(ps, live, s); break;
-        case 4: rc = launch_window_v5<4, 1>(ps, live, s); break;
-        case 5: rc = launch_window_v5<5, 1>(ps, live, s); break;
-        default: break;
-      }
-    }
+    rc = win_dispatch(ps[0].K / 16 + desc[0]->n_relay, desc[0]->n_relay, HFL_EINVAL, [&](auto t, auto g) {
+      return launch_window_v5<decltype(t)::value, decltype(g)::value>(ps, live, s);
+    });
     if (rc != HFL_EINVAL) return rc;
   }
   for (int i = 0; i < n; ++i) {          // not one shape (or a single problem): one launch each
@@ -1910,23 +1748,9 @@ int hfl_window_attention_fwd_ex(void* out, const float* qkv, const float* qkv_bi
   const int rc0 = win_params(p, &empty, out, qkv, qkv_bias, tok_meta, rpe_table, d, out_split3);
   if (rc0 != HFL_OK || empty) return rc0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int T = d->patch_size / 16 + d->n_relay;
-  if (d->n_relay == 0) {
-    switch (T) {
-      case 1: return launch_window<1, 0>(p, s);
-      case 2: return launch_window<2, 0>(p, s);
-      case 3: return launch_window<3, 0>(p, s);
-      case 4: return launch_window<4, 0>(p, s);
-      default: return HFL_EINVAL;
-    }
-  }
-  switch (T) {
-    case 2: return launch_window<2, 1>(p, s);
-    case 3: return launch_window<3, 1>(p, s);
-    case 4: return launch_window<4, 1>(p, s);
-    case 5: return launch_window<5, 1>(p, s);
-    default: return HFL_EINVAL;
-  }
+  return win_dispatch(d->patch_size / 16 + d->n_relay, d->n_relay, HFL_EINVAL, [&](auto t, auto g) {
+    return launch_window<decltype(t)::value, decltype(g)::value>(p, s);
+  });
 }
 
 int64_t hfl_window_rpe_expand_size(int n_heads, int pos_bnd, int depth, int f16_operand) {
@@ -2794,8 +2618,6 @@ __global__ void __launch_bounds__(256) window_dtable_reduce_kernel(float* __rest
   dtable[idx] = acc;
 }
 
-static int g_window_bwd_variant = 2;
-
 // table gradient on the matrix cores when the level's coordinates fit 16 or 32 (desc.depth is the octree depth of the token rows;
 // 0 = not given) and F fits the wave's image block; the fixed-point LDS scatter-add otherwise
 template <int T>
@@ -2896,7 +2718,7 @@ static int launch_window_bwd(const WinBwdParams& p, hipStream_t s) {
   const size_t lds = (size_t)LP * (16 + 16 + 4) + (size_t)NHW * 4 * LP * 16 * 4 + (size_t)NHW * 3 * LP * 4 +
                      (p.table ? (size_t)2 * NHW * 3 * nrpe * 4 : 0);
   if (p.H % NHW != 0) return HFL_EINVAL;
-  if (g_window_bwd_variant >= 2 && 3 * (2 * p.bnd + 1) <= 1023) {
+  if (3 * (2 * p.bnd + 1) <= 1023) {
     // (replicated fixed-point tables, NREP = 4 / 16, measured slower: the LDS they take costs more occupancy than the
     // equal-address conflicts they remove -- tools/attn_bwd_bench.py history in DESIGN.md)
     const int rc = launch_window_bwd2<T, G, 1>(p, s);
@@ -2915,30 +2737,12 @@ static int launch_window_bwd(const WinBwdParams& p, hipStream_t s) {
 
 }  // namespace
 
-extern "C" void hfl_internal_set_window_bwd(int v) { g_window_bwd_variant = v; }
-extern "C" void hfl_internal_set_window_bwd_rt(int v) { g_window_bwd_rt = v; }
-
 static int window_bwd_columns(const hfl_window_attn_desc* d) {
   if (d == nullptr || d->n_heads <= 0 || d->patch_size % 16 != 0 || d->n_relay < 0 || d->n_relay > 1) return 0;
-  if (g_window_bwd_variant < 2 || 3 * (2 * d->pos_bnd + 1) > 1023) return 0;
-  const int T = d->patch_size / 16 + d->n_relay;
-  const int W = d->n_windows, H = d->n_heads, b = d->pos_bnd;
-  if (d->n_relay == 0) {
-    switch (T) {
-      case 1: return window_bwd2_columns<1, 0, 1>(W, H, b, d->depth);
-      case 2: return window_bwd2_columns<2, 0, 1>(W, H, b, d->depth);
-      case 3: return window_bwd2_columns<3, 0, 1>(W, H, b, d->depth);
-      case 4: return window_bwd2_columns<4, 0, 1>(W, H, b, d->depth);
-      default: return 0;
-    }
-  }
-  switch (T) {
-    case 2: return window_bwd2_columns<2, 1, 1>(W, H, b, d->depth);
-    case 3: return window_bwd2_columns<3, 1, 1>(W, H, b, d->depth);
-    case 4: return window_bwd2_columns<4, 1, 1>(W, H, b, d->depth);
-    case 5: return window_bwd2_columns<5, 1, 1>(W, H, b, d->depth);
-    default: return 0;
-  }
+  if (3 * (2 * d->pos_bnd + 1) > 1023) return 0;
+  return win_dispatch(d->patch_size / 16 + d->n_relay, d->n_relay, 0, [&](auto t, auto g) {
+    return window_bwd2_columns<decltype(t)::value, decltype(g)::value, 1>(d->n_windows, d->n_heads, d->pos_bnd, d->depth);
+  });
 }
 
 extern "C" int64_t hfl_window_attention_bwd_workspace(const hfl_window_attn_desc* d) {
@@ -2990,23 +2794,9 @@ static int window_attention_bwd_impl(float* dqkv, float* drpe_table, const float
   p.out_split = out_split;
   p.depth = d->depth;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int T = d->patch_size / 16 + d->n_relay;
-  if (d->n_relay == 0) {
-    switch (T) {
-      case 1: return launch_window_bwd<1, 0>(p, s);
-      case 2: return launch_window_bwd<2, 0>(p, s);
-      case 3: return launch_window_bwd<3, 0>(p, s);
-      case 4: return launch_window_bwd<4, 0>(p, s);
-      default: return HFL_EINVAL;
-    }
-  }
-  switch (T) {
-    case 2: return launch_window_bwd<2, 1>(p, s);
-    case 3: return launch_window_bwd<3, 1>(p, s);
-    case 4: return launch_window_bwd<4, 1>(p, s);
-    case 5: return launch_window_bwd<5, 1>(p, s);
-    default: return HFL_EINVAL;
-  }
+  return win_dispatch(d->patch_size / 16 + d->n_relay, d->n_relay, HFL_EINVAL, [&](auto t, auto g) {
+    return launch_window_bwd<decltype(t)::value, decltype(g)::value>(p, s);
+  });
 }
 
 // ======================================================================================

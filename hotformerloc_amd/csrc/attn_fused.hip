@@ -486,9 +486,6 @@ static int g_fused_timing = 0;
 static std::vector<FusedTimingRec> g_fused_recs;
 static std::mutex g_fused_mu;
 
-extern "C" int hfl_internal_rpe_form(int depth, int bnd, int f16);
-static int g_attn_fused_split = 1;      // probe knob 'attn_fused_split'
-extern "C" void hfl_internal_set_attn_fused_split(int v) { g_attn_fused_split = v ? 1 : 0; }
 
 extern "C" {
 
@@ -521,14 +518,12 @@ int hfl_attn_fused_fwd(void* out_split2, const float* x, const float* gamma, con
   // whole rounds of the grid take whole tiles; the tiles left over are cut by head pairs when that lets them share a round
   p.full_tiles = p.n_tiles;
   p.tail_parts = 1;
-  if (g_attn_fused_split) {
-    const int full = p.n_tiles / cus * cus, rem = p.n_tiles - full;
-    int parts = 1;
-    while (parts * 2 <= FSPR && rem * parts * 2 <= cus) parts *= 2;
-    if (rem > 0 && parts > 1) {
-      p.full_tiles = full;
-      p.tail_parts = parts;
-    }
+  const int full = p.n_tiles / cus * cus, rem = p.n_tiles - full;
+  int parts = 1;
+  while (parts * 2 <= FSPR && rem * parts * 2 <= cus) parts *= 2;
+  if (rem > 0 && parts > 1) {
+    p.full_tiles = full;
+    p.tail_parts = parts;
   }
   const int n_units = p.full_tiles + (p.n_tiles - p.full_tiles) * p.tail_parts;
   const int grid = n_units < cus ? n_units : cus;

@@ -49,9 +49,8 @@ constexpr int WFT = 3;               // 16-row tiles per window
 constexpr int WNWIN = 2;             // windows per workgroup tile
 constexpr int WROWS = 96;            // token rows per workgroup tile
 constexpr int WGW = 6;               // GEMM waves
-constexpr int WAW = 8;               // attention waves (two per SIMD: a unit is a chain of LDS round trips, two waves cover each other)
-constexpr int WW = WGW + WAW;
-constexpr int WLAUNCH = 16;           // waves launched (four per SIMD): two of them leave at once, see WsParams::map
+constexpr int WAW = 8;               // attention waves (a unit is a chain of LDS round trips: the waves of a SIMD cover each other)
+constexpr int WLAUNCH = 16;           // waves launched (four per SIMD): two of them leave at once, see the role map in the kernel
 constexpr int WKS = WC / 32;         // k-steps of the qkv GEMM
 constexpr int WSTAGE = WC * 64;      // bytes of a weight stage: 8 k-steps x 16 features x 128 B
 constexpr int WNSLOT = 3;
@@ -62,11 +61,6 @@ constexpr int WIMREG = WIMROWS * 64; // bytes of one region (Q, K or V) of one h
 constexpr int WIMHEAD = 3 * WIMREG;  // one head's image
 constexpr int WIMG = 2 * WIMHEAD;    // a head pair's image
 
-#ifdef HFL_PROBES
-#define WS_DBG(bit) ((p.dbg & (bit)) != 0)
-#else
-#define WS_DBG(bit) false
-#endif
 struct WsParams {
   unsigned char* out;              // (rows, 2 C) bf16 split2: token rows, relay rows at rt_row0 + window
   const float* x;                  // (n_tokens, C) f32 token rows
@@ -89,10 +83,6 @@ struct WsParams {
   int batch;
   float eps;
   float q_scale;
-  int map;                         // wave -> role map (see the kernel)
-#ifdef HFL_PROBES
-  int dbg;                         // timing ablations (wrong results): 1 no attention work, 2 no GEMM k-loop, 4 no weight stream, 8 no relay units
-#endif
 };
 
 __device__ __forceinline__ float ws_max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
@@ -164,17 +154,12 @@ attn_ws_kernel(const WsParams p) {
   typedef __attribute__((address_space(3))) const float lds_f32;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  // role of the hardware wave (waves go to SIMD id % 4 in launch order): map 0 = GEMM waves 0..5 (two on SIMDs 0 / 1, one on
-  // 2 / 3), attention waves 6..13 (two per SIMD); map 1 = the attention waves where the GEMM waves are not: three on SIMDs 2 / 3
-  // (hardware waves 6, 7, 10, 11, 14, 15), one on SIMDs 0 / 1 (8, 9).  The two waves without a role leave after the
-  // first barrier.
-  int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (p.map == 1) {
-    const int hw = wave;
-    wave = hw < 8 ? hw : hw < 10 ? hw + 4 : hw < 12 ? hw - 2 : hw < 14 ? -1 : hw - 4;
-  } else if (wave >= WW) {
-    wave = -1;
-  }
+  // role of the hardware wave (waves go to SIMD id % 4 in launch order): GEMM waves 0..5 (two on SIMDs 0 / 1, one on 2 / 3), the
+  // attention waves where the GEMM waves are not: three on SIMDs 2 / 3 (hardware waves 6, 7, 10, 11, 14, 15), one on SIMDs 0 / 1
+  // (8, 9).  (Two attention waves per SIMD measured 173 us against 160 at depth 4: profiles/r05_v_attn_ws_wave_map.log.)  The
+  // two waves without a role leave after the first barrier.
+  const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = hw_wave < 8 ? hw_wave : hw_wave < 10 ? hw_wave + 4 : hw_wave < 12 ? hw_wave - 2 : hw_wave < 14 ? -1 : hw_wave - 4;
   const bool gemm_wave = wave >= 0 && wave < WGW;
   const int fr = lane & 15, fq = lane >> 4;          // GEMM: row of the wave's tile, k / feature quarter
   const int c = lane & 15, g = lane >> 4;            // attention: column of a 16-tile, 4-row group
@@ -220,7 +205,7 @@ attn_ws_kernel(const WsParams p) {
     const uint32_t lane_off = (uint32_t)lane * 16u;
     int pr0 = 0, nst_cur = 0;                  // current unit: first pair, stages (6 per pair)
     auto issue = [&](int n, int slot) {
-      if (!loader || WS_DBG(4)) return;
+      if (!loader) return;
       const int pr = pr0 + n / 6, j = n % 6;       // stage j of the pair: region j >> 1, head 2 pr + (j & 1)
       const unsigned char* s = p.pack + (int64_t)((j >> 1) * WSPR + pr) * (WC * 128) + wave * 8192 + (j & 1) * 2048 + lane_off;
       unsigned char* d = w_ring + slot * WSTAGE + wave * 4096;
@@ -344,7 +329,6 @@ attn_ws_kernel(const WsParams p) {
           f32x4 b;
           const uint32_t baddr = (uint32_t)(uintptr_t)(bs + reg * WC + hd * 16 + fq * 4);
           asm volatile("ds_read_b128 %0, %1" : "=&v"(b) : "v"(baddr));
-          if (!WS_DBG(2)) {
           WS_LDS_READ2(wf[0][0], wf[0][1], ahi, alo, 0);
           WS_LDS_READ2(wf[1][0], wf[1][1], ahi, alo, 2048);
           hfl_static_for(std::make_integer_sequence<int, WKS>{}, [&](auto kc) {
@@ -361,7 +345,6 @@ attn_ws_kernel(const WsParams p) {
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks & 3][1], xh[ks], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks & 3][0], xh[ks], acc, 0, 0, 0);
           });
-          }
           // epilogue: bias, query scale, fp16 (hi, lo) split (csrc/qkv_fused.hip / gemm_x3's EPI 2) into the head's image: row
           // 16 wave + fr, features 4 fq .. 4 fq + 3: hi 8 B of chunk fq >> 1, lo of chunk 2 + (fq >> 1)
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b), "+v"(acc));
@@ -612,11 +595,10 @@ attn_ws_kernel(const WsParams p) {
   auto attn_step = [&](const WsJob& jb, bool producing, int ptile, int ppair, int pipar) {
     UnitState us;
     uint4 held;
-    const bool work = jb.valid && !WS_DBG(1);
+    const bool work = jb.valid;
     const int v0 = aw, v1 = aw + 8;
     const int w0 = v0 / 6, h0_ = (v0 / 3) & 1, q0 = v0 % 3;
     const int w1 = v1 < 12 ? v1 / 6 : (v1 - 12) >> 1, h1_ = v1 < 12 ? (v1 / 3) & 1 : (v1 - 12) & 1, q1 = v1 < 12 ? v1 % 3 : WFT;
-    const bool work1 = work && !(q1 == WFT && WS_DBG(8));
     step_barrier();                                   // B0: the image of the step before is complete
     side_fetch(producing, ptile, ppair, held);
     if (work) unit_scores(jb, w0, h0_, q0, us);
@@ -625,11 +607,11 @@ attn_ws_kernel(const WsParams p) {
     step_barrier();                                   // B2
     if (work) unit_output(jb, w0, h0_, q0, us);
     step_barrier();                                   // B3
-    if (work1) unit_scores(jb, w1, h1_, q1, us);
+    if (work) unit_scores(jb, w1, h1_, q1, us);
     step_barrier();                                   // B4
-    if (work1) unit_softmax(us);
+    if (work) unit_softmax(us);
     step_barrier();                                   // B5
-    if (work1) unit_output(jb, w1, h1_, q1, us);
+    if (work) unit_output(jb, w1, h1_, q1, us);
     side_store(producing, ppair, pipar, held);
   };
 
@@ -661,12 +643,6 @@ struct WsTimingRec {
   double bytes, flops_gemm, flops_attn;
 };
 static int g_ws_timing = 0;
-static int g_ws_map = 1;     // measured at depth 4: 160 us against 173 for map 0 (profiles/r05_v_attn_ws_wave_map.log)
-extern "C" void hfl_internal_set_ws_map(int v) { g_ws_map = v == 1 ? 1 : 0; }
-#ifdef HFL_PROBES
-static int g_ws_dbg = 0;
-extern "C" void hfl_internal_set_ws_dbg(int v) { g_ws_dbg = v; }
-#endif
 static std::vector<WsTimingRec> g_ws_recs;
 static std::mutex g_ws_mu;
 
@@ -700,10 +676,7 @@ int hfl_attn_ws_fwd(void* out_split2, const float* x, const float* gamma, const 
   // of K x the stage dilation, models/octree.py:73-75 -- have a relay row too)
   const int64_t t_tok = hfl_cdiv(d->n_tokens, WROWS), t_win = hfl_cdiv(d->n_windows, WNWIN);
   p.n_tiles = (int)(t_tok > t_win ? t_tok : t_win); p.depth = d->depth;
-  p.batch = d->batch_size; p.eps = eps; p.q_scale = q_scale; p.map = g_ws_map;
-#ifdef HFL_PROBES
-  p.dbg = g_ws_dbg;
-#endif
+  p.batch = d->batch_size; p.eps = eps; p.q_scale = q_scale;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int cus = hfl_stream_cus(s);
   // whole rounds of the grid take whole tiles; the tiles left over are cut by head pairs when that lets them share a round

@@ -1,6 +1,7 @@
-// Library identification entry points of libhotformerloc_hip.so.
+// Library identification entry points of libhotformerloc_hip.so, the variant hook and the native block calls.
 #include "hfl_common.h"
 
+#include <cstring>
 
 extern "C" {
 
@@ -13,6 +14,40 @@ int hfl_internal_stream_cus(void* stream) {
 int hfl_version(void) { return 100; }   // 1.00
 
 const char* hfl_arch(void) { return "gfx950"; }
+
+// The seams that the tests and bench.py use (include/hotformerloc_hip.h lists them); everything else is a constant in the code.
+int hfl_set_variant(const char* key, int value) {
+  if (key == nullptr) return HFL_EINVAL;
+  auto is = [key](const char* name) { return strcmp(key, name) == 0; };
+  if (is("reset")) {                                   // the tests call it around each case
+    hfl_internal_set_window_variant(4);
+    hfl_internal_set_rpe_form1_max_depth(4);
+    hfl_internal_set_relay_fast(1);
+    hfl_internal_set_window_bwd_rt(-1);
+    hfl_internal_set_x3_nt(0);
+    hfl_internal_set_mlp_tail_split(1);
+    hfl_internal_set_qkv_tail_split(1);
+    hfl_internal_attn_timing(0);
+    hfl_internal_fused_timing(0);
+    hfl_internal_ws_timing(0);
+  } else if (is("window_attention")) {
+    hfl_internal_set_window_variant(value);
+  } else if (is("window_rpe_form1_max_depth")) {
+    hfl_internal_set_rpe_form1_max_depth(value);
+  } else if (is("relay_fast")) {
+    hfl_internal_set_relay_fast(value);
+  } else if (is("window_bwd_rt")) {
+    hfl_internal_set_window_bwd_rt(value);
+  } else if (is("tail_split")) {
+    hfl_internal_set_mlp_tail_split(value);
+    hfl_internal_set_qkv_tail_split(value);
+  } else if (is("x3_dbg")) {                           // bench.py --x3-nt; the other values set knobs that are gone
+    if ((value & ~3) == 0x100) hfl_internal_set_x3_nt(value & 3);
+  } else {
+    return HFL_EINVAL;
+  }
+  return HFL_OK;
+}
 
 // upper bound of hfl_ln_mlp_fused_workspace over every row count <= n_rows (the executor launches the fused MLP on all rows
 // or on the token rows alone): parts x left-over rows <= min(16 n_rows, one round of the whole chip)

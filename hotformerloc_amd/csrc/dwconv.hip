@@ -319,8 +319,6 @@ __global__ void dwconv_wgrad_scalar(float* __restrict__ out, const float* __rest
   out[i] = acc;
 }
 
-int g_wgrad_batch = 9;      // gathers in flight per lane (probe: hfl_internal_set_wgrad_batch)
-
 static int wgrad_blocks(int64_t n_rows, int rpb) {
   const int64_t need = hfl_cdiv(n_rows, (int64_t)rpb * 8);
   // 3 workgroups per CU: the gathers of a row are only hidden by other waves (one workgroup per CU ran at a quarter of
@@ -340,15 +338,8 @@ static int launch_wgrad(float* out, const float* grad, const float* data, const 
     const size_t lds = (((size_t)g.rpb * K * sizeof(IdxT) + 15) & ~(size_t)15) +
                        (size_t)(g.rpb - 1) * 9 * C * sizeof(float);          // row tables | the row reduction's nine-tap block
     float* partial = static_cast<float*>(workspace);
-    if (g_wgrad_batch == 6)
-      dwconv_wgrad_partial<IdxT, 6><<<blocks, g.tpr * g.rpb, lds, s>>>(partial, grad, data, neigh, n_rows, (int)C, K, g.tpr,
-                                                                       g.rpb);
-    else if (g_wgrad_batch == 3)
-      dwconv_wgrad_partial<IdxT, 3><<<blocks, g.tpr * g.rpb, lds, s>>>(partial, grad, data, neigh, n_rows, (int)C, K, g.tpr,
-                                                                       g.rpb);
-    else
-      dwconv_wgrad_partial<IdxT, 9><<<blocks, g.tpr * g.rpb, lds, s>>>(partial, grad, data, neigh, n_rows, (int)C, K, g.tpr,
-                                                                       g.rpb);
+    // nine gathers in flight per lane (six and three were measured and lost)
+    dwconv_wgrad_partial<IdxT, 9><<<blocks, g.tpr * g.rpb, lds, s>>>(partial, grad, data, neigh, n_rows, (int)C, K, g.tpr, g.rpb);
     const int64_t kc = (int64_t)K * C;
     dwconv_wgrad_reduce<<<(int)hfl_cdiv(kc, 64), 1024, 0, s>>>(out, partial, blocks, kc);
   } else {
@@ -381,7 +372,7 @@ __global__ void __launch_bounds__(256) cpe_fwd_kernel(float* __restrict__ out, f
                                const float* __restrict__ x, const float* __restrict__ add,
                                const float* __restrict__ weight, const float* __restrict__ gamma,
                                const float* __restrict__ beta, const int32_t* __restrict__ neigh,
-                               int64_t n_rows, int K, float eps, int residual, int chunk_rows) {
+                               int64_t n_rows, int K, float eps, int residual) {
   constexpr int C = TPR * 4;
   constexpr int RPB = 256 / TPR;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -394,31 +385,16 @@ __global__ void __launch_bounds__(256) cpe_fwd_kernel(float* __restrict__ out, f
   const float4 gm = NORM ? reinterpret_cast<const float4*>(gamma)[tx] : make_float4(1.f, 1.f, 1.f, 1.f);
   const float4 bt = NORM ? reinterpret_cast<const float4*>(beta)[tx] : make_float4(0.f, 0.f, 0.f, 0.f);
 
-  // iteration space: `it` enumerates groups of RPB rows.  chunk_rows == 0: group it of block b is
-  // b + it*gridDim (interleaved).  chunk_rows > 0: a block owns chunk_rows consecutive rows at a time
-  // (z-order neighbours -> its gathers revisit lines still in L1/L2), chunks dealt round-robin.
-  // chunk_rows < 0 (default): XCD-contiguous.  Workgroups b and b + 8 share an XCD (round-robin dispatch), so XCD
-  // x = b & 7 walks its own contiguous eighth of the z-ordered rows with its gridDim / 8 workgroups interleaved inside it:
-  // a row's 27 neighbours are z-order neighbours of the same cloud, so the lines a gather touches are (re)used through ONE
-  // L2 instead of being fetched into all eight (the interleaved map: L2 hit 47 %, 3.7x the algorithmic fabric traffic).
+  // iteration space: groups of RPB rows, XCD-contiguous.  Workgroups b and b + 8 share an XCD (round-robin
+  // dispatch), so XCD x = b & 7 walks its own contiguous eighth of the z-ordered rows with its gridDim / 8 workgroups
+  // interleaved inside it: a row's 27 neighbours are z-order neighbours of the same cloud, so the lines a gather touches are
+  // (re)used through ONE L2 instead of being fetched into all eight (groups b, b + gridDim, ..., the interleaved map: L2 hit 47 %,
+  // 3.7x the algorithmic fabric traffic).  The launcher rounds the grid up to whole groups of eight workgroups.
   const int64_t groups = (n_rows + RPB - 1) / RPB;
-  const int64_t gpc = chunk_rows > 0 ? (chunk_rows + RPB - 1) / RPB : 1;     // groups per chunk
   const int64_t per_xcd = (groups + 7) >> 3;
   const int64_t xg0 = (int64_t)(blockIdx.x & 7) * per_xcd;
   const int64_t xg1 = xg0 + per_xcd < groups ? xg0 + per_xcd : groups;
-  for (int64_t it = 0;; ++it) {
-    int64_t grp;
-    if (chunk_rows < 0) {
-      grp = xg0 + (blockIdx.x >> 3) + it * (gridDim.x >> 3);
-      if (grp >= xg1) break;
-    } else if (chunk_rows > 0) {
-      const int64_t chunk = (it / gpc) * gridDim.x + blockIdx.x;
-      grp = chunk * gpc + it % gpc;
-      if (chunk * gpc >= groups) break;
-    } else {
-      grp = (int64_t)blockIdx.x + it * gridDim.x;
-      if (grp >= groups) break;
-    }
+  for (int64_t grp = xg0 + (blockIdx.x >> 3); grp < xg1; grp += gridDim.x >> 3) {
     const int64_t base = grp * RPB;
     const int64_t h = base + ty;
     const bool live = h < n_rows;
@@ -505,8 +481,6 @@ __global__ void __launch_bounds__(256) cpe_fwd_kernel(float* __restrict__ out, f
 }
 
 
-static int g_cpe_chunk_rows = -1;  // < 0: XCD-contiguous (default); 0: rows interleaved over blocks; > 0: contiguous chunk per block
-
 template <int TPR, bool NORM>
 static int launch_cpe(float* out, float* conv_out, const float* x, const float* add, const float* w, const float* gamma,
                       const float* beta, const int32_t* neigh, int64_t n, int K, float eps,
@@ -519,9 +493,8 @@ static int launch_cpe(float* out, float* conv_out, const float* x, const float* 
   const int per_cu = persistent_per_cu(reinterpret_cast<const void*>(cpe_fwd_kernel<TPR, NORM>), 256, lds, 8, &nb, &nb_lds);
   const int64_t cap = (int64_t)hfl_stream_cus(s) * per_cu;
   int blocks = (int)(need < cap ? need : cap);
-  if (g_cpe_chunk_rows < 0) blocks = (blocks + 7) & ~7;          // the XCD map deals whole groups of eight workgroups
-  cpe_fwd_kernel<TPR, NORM><<<blocks, 256, lds, s>>>(out, conv_out, x, add, w, gamma, beta, neigh, n, K, eps, residual,
-                                                     g_cpe_chunk_rows);
+  blocks = (blocks + 7) & ~7;          // the XCD map deals whole groups of eight workgroups
+  cpe_fwd_kernel<TPR, NORM><<<blocks, 256, lds, s>>>(out, conv_out, x, add, w, gamma, beta, neigh, n, K, eps, residual);
   HFL_RETURN_LAST_ERROR();
 }
 
@@ -644,9 +617,4 @@ int hfl_slot_sum(float* out, const float* part, const int32_t* slot, const float
                                                                                g.tpr, g.rpb);
   HFL_RETURN_LAST_ERROR();
 }
-
-/* internal tuning hook used by hfl_set_variant("cpe_chunk_rows", n) */
-void hfl_internal_set_cpe_chunk(int rows) { g_cpe_chunk_rows = rows; }
-/* probe: gathers in flight per lane of the depth-wise weight gradient (9, 6 or 3) */
-void hfl_internal_set_wgrad_batch(int taps) { g_wgrad_batch = taps; }
 }  // extern "C"

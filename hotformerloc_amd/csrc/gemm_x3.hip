@@ -61,13 +61,8 @@ struct X3Params {
   int qk_channels;          // EPI 2: C (= out_features / 3); features < C are queries
   float q_scale;            // EPI 2: factor folded into the queries (softmax scale * log2 e)
   int nt;                   // bit 0: non-temporal stores of the f32 output, bit 1: of the split2 output
-  int dbg;                  // unused (kept for the probe tools)
 };
 
-static int g_x3_dbg = 0;
-                            // Off: alone it halves the time of the relay tokens' K = 1024 GEMM, inside the step it loses 3 %
-                            // (2361 -> 2442 clouds/s without it): its 128 KB of LDS need a nearly empty CU, the one-stage kernel's
-                            // 32 KB slip in beside the finest level's workgroups
 static int g_x3_nt = 0;     // measured: no end-to-end difference (the consumer kernel re-reads the output anyway)
 
 // Epilogue shared by the kernels below.  acc[i][j]: features 16 i + 4 fq .. +3 (registers) of row 16 j + frow of the
@@ -336,11 +331,7 @@ split2_kernel(uint16_t* __restrict__ out, const float* __restrict__ x, const flo
 
 extern "C" {
 
-void hfl_internal_set_x3_dbg(int v) {
-  if (v >= 0x200) return;                   // (knobs of removed tile variants)
-  if (v >= 0x100) g_x3_nt = v & 3;          // 0x100 | nt bits
-  else g_x3_dbg = v;
-}
+void hfl_internal_set_x3_nt(int nt) { g_x3_nt = nt & 3; }     // hfl_set_variant "x3_dbg", 0x100 | nt (bench.py --x3-nt)
 
 static int x3_launch(void* out, const uint16_t* x_split2, const uint16_t* w_split2, const float* bias,
                      const float* residual, int64_t n_rows, int in_features, int out_features, int epi,
@@ -435,12 +426,11 @@ static int x3_launch(void* out, const uint16_t* x_split2, const uint16_t* w_spli
   // 128-row tiles, 3 workgroups per CU.  (A 256-row tile and a 128 x 256 eight-wave tile were built and measured 10 - 120 %
   // slower on every shape of the model: DESIGN.md section 4; they are gone from the library.)
   p.n_wg = (tiles != nullptr ? n_tiles : hfl_cdiv(n_rows, 128)) * p.tiles_n;
-  p.dbg = g_x3_dbg;
   p.nt = g_x3_nt;
   p.qk_channels = out_features / 3;
   p.q_scale = q_scale;
   if (p.n_wg > 0x7fffffffLL) return HFL_ECAPACITY;
-  const size_t lds = (size_t)(128 + XT) * 128 + (size_t)(g_x3_dbg & 0xFF) * 1024;   // (+ probe: extra KiB to cut occupancy)
+  const size_t lds = (size_t)(128 + XT) * 128;
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define HFL_X3_LAUNCH(E, M)                                                                              \
   {                                                                                                      \

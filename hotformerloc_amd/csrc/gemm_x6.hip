@@ -187,19 +187,6 @@ __device__ __forceinline__ void x6_epilogue(const X6Params& p, f32x4 (&acc)[4][M
   }
 }
 
-// probe build (-DHFL_X6_STAMPS): s_memtime of wave 0 (group A) and wave 4 (group B) of workgroup 0 at every barrier arrival and
-// release of its first tile (tools/x6_stamps.py)
-#ifdef HFL_X6_STAMPS
-__device__ unsigned long long g_x6_stamps[2][512];
-#define X6_STAMP()                                                                                         \
-  do {                                                                                                     \
-    if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 4) && stamp_n < 512)                         \
-      g_x6_stamps[wave >> 2][stamp_n++] = __builtin_amdgcn_s_memtime();                                    \
-  } while (0)
-#else
-#define X6_STAMP() do { } while (0)
-#endif
-
 // s_waitcnt with the gfx9 immediate: vmcnt(v) lgkmcnt(l), no wait on expcnt
 #define X6_WAIT(v, l) __builtin_amdgcn_s_waitcnt(((v) & 15) | (((v) >> 4) << 14) | (7 << 4) | ((l) << 8))
 #define X6_WAIT_LGKM0() X6_WAIT(63, 0)
@@ -353,35 +340,27 @@ gemm_x6_kernel(const X6Params p) {
   // s_barrier into the other half-step, where the SIMD's partner wave has ITS MFMA phase)
   // Priority: the wave in its read / split half runs beside its SIMD partner's back-to-back MFMAs and, at equal priority, gets
   // about ONE instruction issued per MFMA (16 cycles): its ~180 instructions took ~2900 cycles against the partner's 1536
-  // (s_memtime stamps, probe build).  Raised to priority 1 for that half it issues at once; the MFMA stream needs one issue slot
+  // (s_memtime stamps of an earlier probe build).  Raised to priority 1 for that half it issues at once; the MFMA stream needs one issue slot
   // per 16 cycles and loses nothing.
   auto prio_hi = [&]() { __builtin_amdgcn_s_setprio(1); };
   auto prio_lo = [&]() { __builtin_amdgcn_s_setprio(0); };
-  int stamp_n = 0;
-  (void)stamp_n;
   auto bar_full = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     X6_WAIT_ALL();
-    X6_STAMP();
     __builtin_amdgcn_s_barrier();
-    X6_STAMP();
     __builtin_amdgcn_sched_barrier(0);
   };
   auto bar_lds = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     X6_WAIT_LGKM0();
-    X6_STAMP();
     __builtin_amdgcn_s_barrier();
-    X6_STAMP();
     __builtin_amdgcn_sched_barrier(0);
   };
   // all but this wave's MTL youngest vector-memory operations done (its x requests stay in flight, its LDS-DMA has landed)
   auto bar_keep = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     X6_WAIT(MTL, 0);
-    X6_STAMP();
     __builtin_amdgcn_s_barrier();
-    X6_STAMP();
     __builtin_amdgcn_sched_barrier(0);
   };
 
@@ -524,11 +503,6 @@ static int g_x6_mt = 0;      // 0: tile shape chosen per launch; probe: 1 .. 4 =
 extern "C" {
 
 void hfl_internal_set_x6_mt(int v) { g_x6_mt = v; }
-#ifdef HFL_X6_STAMPS
-int hfl_internal_x6_stamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_x6_stamps), sizeof(g_x6_stamps));
-}
-#endif
 
 int64_t hfl_linear_x6_padded_k(int64_t in_features) { return (in_features + 63) / 64 * 64; }
 

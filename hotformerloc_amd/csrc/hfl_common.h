@@ -30,6 +30,22 @@ static inline int hfl_num_cus() {
 extern "C" int hfl_internal_stream_cus(void* stream);
 static inline int hfl_stream_cus(hipStream_t s) { return hfl_internal_stream_cus(static_cast<void*>(s)); }
 
+// The seams behind hfl_set_variant (csrc/capi.hip), each defined next to the state it sets, and the switches of the per-launch
+// timing recorders that its "reset" turns off.
+extern "C" {
+void hfl_internal_set_window_variant(int v);          // csrc/attention.hip
+void hfl_internal_set_rpe_form1_max_depth(int v);
+void hfl_internal_set_relay_fast(int v);
+void hfl_internal_set_window_bwd_rt(int v);
+void hfl_internal_set_x3_nt(int nt);                  // csrc/gemm_x3.hip
+void hfl_internal_set_mlp_tail_split(int v);          // csrc/mlp_fused.hip
+void hfl_internal_set_qkv_tail_split(int v);          // csrc/qkv_fused.hip
+int hfl_internal_attn_timing(int on);                 // csrc/attention.hip, attn_fused.hip, attn_ws.hip
+int hfl_internal_fused_timing(int on);
+int hfl_internal_ws_timing(int on);
+int hfl_internal_rpe_form(int depth, int bnd, int f16);      // csrc/attention.hip: table form of a (depth, pos_bnd) pair
+}
+
 static inline int64_t hfl_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // A logical (rows, C) f32 matrix whose rows live in up to four separate arrays (hfl_row_segments of the C-ABI): rows

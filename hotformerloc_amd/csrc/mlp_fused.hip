@@ -73,15 +73,7 @@ struct MlpFusedParams {
   unsigned int* ticket;
 };
 
-static int g_mlp_stagger = 1;      // probe knob 'mlp_stagger': naps per group step | groups << 8
-static int g_mlp_stagger_groups = 8;
-#ifdef HFL_PROBES
-static int g_mlp_dbg = 0;          // probe knob 'mlp_dbg': timing ablations (see the kernel), 0 = off
-#endif
-
-// DBG (probe knob 'mlp_dbg', timing ablations only -- results are wrong): 1 GELU -> identity, 2 no bias / GELU / split at all,
-// 4 no refill of the weight ring, 8 no barrier at the stage boundaries
-template <int C, int NT, int PF, int NW, int LAG, int DBG = 0, int HID = 4 * C>
+template <int C, int NT, int PF, int NW, int LAG, int HID = 4 * C>
 __global__ void __launch_bounds__(NW * 64, NW == 8 ? 2 : 1)
 ln_mlp_fused_kernel(const MlpFusedParams p) {
   static_assert(LAG == 0 || (PF == 2 && NW == 8), "the late half keeps a stage one step longer: two stages ahead, not three");
@@ -161,7 +153,7 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
     if (n + PF - 1 < nst) HFL_WAIT_VM((PF - 1) * DPW);
     else if (n + 1 < nst) HFL_WAIT_VM((PF - 2) * DPW > 0 ? (PF - 2) * DPW : 0);
     else HFL_WAIT_VM(0);
-    if constexpr (!(DBG & 8)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     dma_n = n + PF;
     dma_slot = (seq + PF) % NSLOT;
     // the refill's addresses once per stage: its pieces differ in the instruction's immediate offset only (which advances
@@ -174,7 +166,6 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
   };
   auto dma_piece = [&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    if constexpr (DBG & 4) return;
     if (dma_n < nst)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)dma_src,
                                        (__attribute__((address_space(3))) void*)dma_dst, 16, i * 1024, 0);
@@ -291,16 +282,11 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
     auto gelu_pair = [&](int pidx, f32x4 (&hp)[2][NT], int chunk) {
       const int t = pidx >> 2, d = pidx & 3;
       const int i = d >> 1, r0 = 2 * (d & 1);
-      if constexpr (DBG & 2) {
-        gh[t][d] = __float_as_uint(hp[i][t][r0]);
-        gl[t][d] = __float_as_uint(hp[i][t][r0 + 1]);
-        return;
-      }
       (void)chunk;                  // (the bias is in the accumulators already: gemm1_half)
       // SCALAR f32 math on purpose (and -fno-slp-vectorize for this file): beside MFMAs a v_pk_*_f32 costs ~12 extra
       // cycles of the matrix pipe each (MI355X_MICROARCH.md, cycle constants), a plain VALU op hides in the MFMA's shadow
-      const float g0 = (DBG & 1) ? hp[i][t][r0] : x3_gelu(hp[i][t][r0]);
-      const float g1 = (DBG & 1) ? hp[i][t][r0 + 1] : x3_gelu(hp[i][t][r0 + 1]);
+      const float g0 = x3_gelu(hp[i][t][r0]);
+      const float g1 = x3_gelu(hp[i][t][r0 + 1]);
       uint32_t hi, lo;
       x3_split_pair_scalar(g0, g1, hi, lo);
       gh[t][d] = hi;
@@ -315,8 +301,7 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
         // for the fragment prefetch issued just before, i.e. it serialised every k-step's LDS round trip with its MFMAs
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          const f32x4 bi = (DBG & 2) ? (f32x4){0.f, 0.f, 0.f, 0.f}
-                                     : *reinterpret_cast<const f32x4*>(b1s + (c0 + prev_chunk + (with_gelu ? 1 : 0)) * 32 + i * 16 + fq * 4);
+          const f32x4 bi = *reinterpret_cast<const f32x4*>(b1s + (c0 + prev_chunk + (with_gelu ? 1 : 0)) * 32 + i * 16 + fq * 4);
 #pragma unroll
           for (int t = 0; t < NT; ++t) h[i][t] = bi;
         }
@@ -561,15 +546,6 @@ static int grid_guess(int n_tiles, int cus) { return n_tiles < cus ? n_tiles : c
 
 extern "C" {
 
-#ifdef HFL_PROBES
-void hfl_internal_set_mlp_dbg(int v) { g_mlp_dbg = v; }      // timing ablations (tools/mlp_ablate.py), probe builds only
-#endif
-
-void hfl_internal_set_mlp_stagger(int v) {
-  g_mlp_stagger = v & 0xFF;
-  g_mlp_stagger_groups = (v >> 8) > 0 ? (v >> 8) : 2;
-}
-
 static bool mlp_shape_ok(int channels, int hidden) {
   return (channels == 128 || channels == 256) && (hidden == 4 * channels || (channels == 256 && hidden == 256));
 }
@@ -596,8 +572,7 @@ int hfl_mlp_fused_pack(void* pack, const float* w1, const float* w2, int channel
 struct MlpTailPlan {
   int full, tile0, sets, parts;
 };
-static int g_mlp_tail_split = 1;   // probe knob 'mlp_tail_split'
-static int g_mlp_dynamic = 1;      // probe knob 'mlp_dynamic': work units by atomic ticket (0: static, strided by workgroup)
+static int g_mlp_tail_split = 1;   // hfl_set_variant "tail_split" (0: plain passes, the tests' reference for the split)
 
 // Ticket slots (two counters each, one 128-B line per slot), one table per DEVICE, zero-initialised once; a device's launches
 // take its slots round-robin and the last workgroup of a launch leaves its slot zeroed.  A slot comes round again 256 ticketed
@@ -640,7 +615,6 @@ static MlpTailPlan mlp_tail_plan(int64_t n_rows, int channels, int cus, int hidd
 }
 
 extern "C" void hfl_internal_set_mlp_tail_split(int v) { g_mlp_tail_split = v ? 1 : 0; }
-extern "C" void hfl_internal_set_mlp_dynamic(int v) { g_mlp_dynamic = v ? 1 : 0; }
 
 static int64_t mlp_tail_bytes(const MlpTailPlan& t, int64_t n_rows, int channels) {
   return t.parts == 0 ? 0 : (int64_t)t.parts * (n_rows - (int64_t)t.tile0 * 16) * channels * 4;
@@ -696,10 +670,11 @@ int hfl_ln_mlp_fused_h(float* out, const float* x, const float* gamma, const flo
   p.out = out; p.x = x; p.gamma = gamma; p.beta = beta; p.pack = static_cast<const unsigned char*>(pack);
   p.b1 = b1; p.b2 = b2; p.M = n_rows; p.eps = eps;
   p.n_tiles = (int)hfl_cdiv(n_rows, 16);
-  // stagger only launches in which a workgroup walks several passes (a single pass has nothing to alternate with)
+  // stagger only launches in which a workgroup walks several passes (a single pass has nothing to alternate with): eight
+  // groups of workgroups, one nap apart
   int cus = hfl_stream_cus(static_cast<hipStream_t>(stream));
-  p.stagger = p.n_tiles > (int64_t)grid_guess(p.n_tiles, cus) * 8 * (channels == 256 ? 1 : 2) ? g_mlp_stagger : 0;
-  p.stagger_groups = g_mlp_stagger_groups;
+  p.stagger = p.n_tiles > (int64_t)grid_guess(p.n_tiles, cus) * 8 * (channels == 256 ? 1 : 2) ? 1 : 0;
+  p.stagger_groups = 8;
   int grid = p.n_tiles < cus ? p.n_tiles : cus;
   p.full_passes = 0; p.tail_tile0 = 0; p.tail_sets = 0; p.tail_parts = 0; p.part = nullptr;
   MlpTailPlan tp = mlp_tail_plan(n_rows, channels, cus, hidden);
@@ -716,7 +691,7 @@ int hfl_ln_mlp_fused_h(float* out, const float* x, const float* gamma, const flo
   if (grid > n_units) grid = n_units;
   if (tp.parts > 0 && tp.full > 0 && grid < cus) grid = cus < n_units ? cus : n_units;
   // tickets only when a workgroup can get more than one unit (else the static deal is the same thing without the atomics)
-  p.ticket = (g_mlp_dynamic && n_units > grid) ? ticket_slot() : nullptr;
+  p.ticket = n_units > grid ? ticket_slot() : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t lds = (size_t)4 * channels * 128 + (size_t)(hidden + 3 * channels) * 4;
 #define HFL_MLP_LAUNCH(CC, NT, PF, NW, LAG)                                                                     \
@@ -727,28 +702,10 @@ int hfl_ln_mlp_fused_h(float* out, const float* x, const float* gamma, const flo
     ln_mlp_fused_kernel<CC, NT, PF, NW, LAG><<<grid, NW * 64, lds, s>>>(p);                                     \
   }
   if (hidden != 4 * channels) {               // the Mixer's layers: hidden = C = 256
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ln_mlp_fused_kernel<256, 1, 3, 8, 0, 0, 256>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ln_mlp_fused_kernel<256, 1, 3, 8, 0, 256>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    ln_mlp_fused_kernel<256, 1, 3, 8, 0, 0, 256><<<grid, 512, lds, s>>>(p);
-#ifdef HFL_PROBES
-  } else if (g_mlp_dbg && channels == 256) {
-#define HFL_MLP_DBG(D)                                                                                          \
-  {                                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_mlp_fused_kernel<256, 1, 3, 8, 0, D>),           \
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-    ln_mlp_fused_kernel<256, 1, 3, 8, 0, D><<<grid, 512, lds, s>>>(p);                                          \
-  }
-    switch (g_mlp_dbg) {
-      case 1: HFL_MLP_DBG(1) break;
-      case 3: HFL_MLP_DBG(3) break;
-      case 4: HFL_MLP_DBG(4) break;
-      case 7: HFL_MLP_DBG(7) break;
-      case 8: HFL_MLP_DBG(8) break;
-      default: HFL_MLP_DBG(15) break;
-    }
-#undef HFL_MLP_DBG
-#endif
+    ln_mlp_fused_kernel<256, 1, 3, 8, 0, 256><<<grid, 512, lds, s>>>(p);
   } else {
     // 8 waves (two per SIMD, 256 registers each), three stages of the weight stream ahead of the consumed one: the measured
     // best of the variants tried in rounds 3-4 (4 waves x 512 registers, two stages ahead, the second wave of a SIMD one stage

@@ -405,7 +405,7 @@ qkv_pack_kernel(unsigned char* __restrict__ pack, const float* __restrict__ w, i
 
 }  // namespace
 
-static int g_qkv_tail_split = 1;    // probe knob 'tail_split'
+static int g_qkv_tail_split = 1;    // hfl_set_variant "tail_split"
 
 extern "C" {
 

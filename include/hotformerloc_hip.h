@@ -303,13 +303,18 @@ int hfl_gemm_bf16(float* out, const uint16_t* a, const uint16_t* w, const float*
 int hfl_gemm_bf16_tn(float* out, const uint16_t* a, const uint16_t* b, int64_t n_rows_stacked, int n_out,
                      int k_out, hfl_stream_t stream);
 
-/* Test / measurement hook: select a kernel variant at run time; "reset" restores every default.  Keys kept in the product
- * build: "window_attention" (4 = default, 2 = three-lookup fp32 kernel), "window_rpe_form1_max_depth" (table form of the fp16
- * kernel), "window_bwd", "window_heads_per_wg", "window_v4_wgs_per_cu" / "window_v2_wgs_per_cu", "window_debug",
- * "tail_split" / "dynamic_units" / "mlp_stagger" (left-over rows, work tickets and start stagger of the row-tile kernels),
- * "attn_fused_split", "cpe_chunk_rows", "x3_dbg".  The variants that lost their A/B measurements in rounds
- * 2-4 (per-round launches, relay rows first, CU-masked streams, device-flag hops, the x3 ring kernel, 4-wave row tiles) are
- * gone from the library; their logs are under profiles/.  Returns HFL_EINVAL for an unknown key. */
+/* Test / measurement hook: select a kernel variant at run time.  The keys are the seams that the test suite and bench.py use:
+ *   "reset"                       every key below back to its default, the per-launch timing recorders off
+ *   "window_attention"            4 = default; any other value selects the three-lookup fp32 kernels and makes
+ *                                 hfl_window_attention_f16_ok return 0
+ *   "window_rpe_form1_max_depth"  deepest level at which the fp16 window kernel takes table form 1 (default 4; 0 = form 2 always)
+ *   "relay_fast"                  0 = the general loop of the fp16 relay-token attention for every sequence length
+ *   "window_bwd_rt"               0 = scatter-add table gradient in the window attention backward (-1 = by depth)
+ *   "tail_split"                  0 = no split of the left-over rows in the fused MLP and the fused LN -> qkv launches
+ *   "x3_dbg"                      0x100 | nt: non-temporal stores of the x3 GEMM output (bit 0 f32, bit 1 split2); any other
+ *                                 value is accepted and ignored
+ * Every variant that lost its A/B measurement is gone from the library together with its key (knob history); the logs
+ * are under profiles/.  Returns HFL_EINVAL for an unknown key. */
 int hfl_set_variant(const char* key, int value);
 
 /* ------------------------------------------------------------------------

@@ -162,6 +162,34 @@ def test_package_reads_only_the_product_and_build_variables():
                     'HFL_EXTRA_HIPCC_FLAGS', 'TENSILE_STREAMK_DATA_PARALLEL'}, read
 
 
+def test_native_variant_hook_keeps_only_the_used_seams():
+    """The native library has no probe builds and no in-kernel ablation fields, and `hfl_set_variant` knows exactly the keys
+    that the test suite and bench.py use: each is accepted at its default value (no GPU needed), every retired key is
+    HFL_EINVAL."""
+    csrc = os.path.join(ROOT, 'hotformerloc_amd', 'csrc')
+    for f in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, f)).read()
+        for word in ('HFL_PROBES', 'HFL_ATT_TRACE', 'HFL_X6_STAMPS'):
+            assert word not in src, (f, word)
+        assert not re.search(r'\bint\s+dbg\s*;|(?:\.|->)\s*dbg\b', src), (f, 'a dbg struct field')
+    lib = _native.load()
+    kept = {'reset': 0, 'window_attention': 4, 'x3_dbg': 0x100, 'relay_fast': 1, 'window_bwd_rt': -1, 'tail_split': 1,
+            'window_rpe_form1_max_depth': 4}
+    retired = ['window_debug', 'window_v4_wgs_per_cu', 'window_v2_wgs_per_cu', 'window_heads_per_wg', 'window_bwd',
+               'attn_fused_split', 'ws_map', 'ws_dbg', 'dynamic_units', 'mlp_dbg', 'mlp_stagger', 'cpe_chunk_rows']
+    try:
+        for key, default in kept.items():
+            assert lib.hfl_set_variant(key.encode(), default) == 0, key
+        assert lib.hfl_set_variant(b'x3_dbg', 7) == 0           # accepted and ignored
+        for key in retired:
+            assert lib.hfl_set_variant(key.encode(), 0) == -1, key          # HFL_EINVAL
+        for name in ('hfl_internal_set_wgrad_batch', 'hfl_internal_set_cpe_chunk', 'hfl_internal_set_ws_map',
+                     'hfl_internal_set_mlp_stagger', 'hfl_internal_set_window_bwd', 'hfl_internal_set_x3_dbg'):
+            assert not hasattr(lib, name), name
+    finally:
+        lib.hfl_set_variant(b'reset', 0)
+
+
 def test_synthetic_generators_are_pinned():
     u = syn.hash_uniform(12345, 4)
     assert np.allclose(u, syn.hash_uniform(12345, 6)[:4]) and np.all(np.abs(u) < 1)

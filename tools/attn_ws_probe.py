@@ -1,7 +1,6 @@
 """hfl_attn_ws_fwd (LayerNorm -> qkv -> window attention of a relay-token block in one launch, specialised waves) against hfl_ln_qkv_fused +
 the fp16 window kernel at the pyramid depths of the bench workload (Wild-Places cfg, 32 clouds) and of the CS-Wild-Places cfg
-(K = 64): equality and timing.  `python tools/attn_ws_probe.py [cfg]`; HFL_WS_ABLATE=1 adds the timing ablations (needs a
-library built with HFL_EXTRA_HIPCC_FLAGS=-DHFL_PROBES), HFL_WS_ONLY=1 runs the one kernel for tools/attn_ws_counters.sh."""
+(K = 64): equality and timing.  `python tools/attn_ws_probe.py [cfg]`; HFL_WS_ONLY=1 runs the one kernel for tools/attn_ws_counters.sh."""
 import os
 import sys
 
@@ -61,8 +60,6 @@ def main(cfg):
                                      plan.B, d, out=out)
         if os.environ.get('HFL_WS_ONLY', '0') != '0':           # counter runs: the one kernel at the deepest level
             if d == plan.pyramid_depths[0]:
-                if os.environ.get('HFL_WS_DBG'):
-                    lib.hfl_set_variant(b'ws_dbg', int(os.environ['HFL_WS_DBG']))
                 for _ in range(10):
                     one()
                 torch.cuda.synchronize()
@@ -79,19 +76,6 @@ def main(cfg):
             return (v[:, :, 0] + v[:, :, 1]).reshape(W, C)
         rerr = (val(a) - val(f)).abs().max().item()
         t2, t1, tr = timeit(two), timeit(one), timeit(relay_qkv)
-        lib.hfl_set_variant(b'ws_map', 0)             # attention waves two per SIMD (map 1, the default: where the GEMM waves are not)
-        f1 = one()
-        same = torch.equal(f1.view(torch.int16), f.view(torch.int16))
-        t1b = timeit(one)
-        lib.hfl_set_variant(b'ws_map', 1)
-        print('   wave map 0: %.1f us (map 1: %.1f), output identical: %s' % (t1b, t1, same), flush=True)
-        if os.environ.get('HFL_WS_ABLATE', '0') != '0':        # timing ablations (wrong results): see WsParams::dbg
-            abl = []
-            for dbg in (1, 2, 3, 4, 7, 8):
-                lib.hfl_set_variant(b'ws_dbg', dbg)
-                abl.append((dbg, round(timeit(one), 1)))
-            lib.hfl_set_variant(b'ws_dbg', 0)
-            print('   ablations (bits: 1 no attention work, 2 no GEMM k-loop, 4 no weight stream, 8 no relay units) us:', abl, flush=True)
         flop = (6.0 * nt * C * C * 3 + 4.0 * (K + 1) * (K + 1) * C * W * 3.5)
         print('%s depth %d rows %d + %d relay: fused %.1f us (+ relay qkv %.1f us)  two launches %.1f us  x%.2f | token rows differ: %d, '
               'relay rows max err %.2e | %.0f TF/s issued, %.2f TB/s of x + out' % (cfg, d, nt, W, t1, tr, t2, t2 / (t1 + tr), nbad, rerr,

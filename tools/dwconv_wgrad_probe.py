@@ -1,13 +1,11 @@
-"""hfl_dwconv_weight_backward at the training step's shapes: error against an fp64 contraction and time per launch for the
-gather batch sizes of the kernel (csrc/dwconv.hip: dwconv_wgrad_partial<.., B>)."""
-import ctypes, os, sys
+"""hfl_dwconv_weight_backward at the training step's shapes: error against an fp64 contraction and time per launch
+(csrc/dwconv.hip: dwconv_wgrad_partial), beside the CPE forward."""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from hotformerloc_amd import build_batch_octree, load_config, ops, synthetic as syn, _native
+from hotformerloc_amd import build_batch_octree, load_config, ops, synthetic as syn
 from hotformerloc_amd.plan import WindowPlan
 
-lib = _native.load()
-lib.hfl_internal_set_wgrad_batch.argtypes = [ctypes.c_int]
 params, depth = load_config('wild-places')
 octree = build_batch_octree(syn.make_clouds(2, 32, 4096, params.coordinates), depth, 2, 'cuda')
 plan = WindowPlan(octree, 48, 4, 5, 2, 3, 1, None)
@@ -38,13 +36,10 @@ for d, C in ((4, 256), (5, 128), (3, 256)):
         ok = idx >= 0
         ref[k] = (x[idx[ok]].double() * dy[ok].double()).sum(0)
     line = 'depth %d  rows %6d  C %3d  live taps %.1f |' % (d, n, C, float((neigh >= 0).float().sum(1).mean()))
-    for b in (9, 6, 3):
-        lib.hfl_internal_set_wgrad_batch(b)
-        dw = ops.dwconv_weight_backward(dy, x, neigh).view(27, C)
-        err = ((dw.double() - ref).norm() / ref.norm()).item()
-        t = timeit(lambda: ops.dwconv_weight_backward(dy, x, neigh))
-        line += '  B=%d: %.1f us (err %.1e)' % (b, t, err)
-    lib.hfl_internal_set_wgrad_batch(9)
+    dw = ops.dwconv_weight_backward(dy, x, neigh).view(27, C)
+    err = ((dw.double() - ref).norm() / ref.norm()).item()
+    t = timeit(lambda: ops.dwconv_weight_backward(dy, x, neigh))
+    line += '  %.1f us (err %.1e)' % (t, err)
     w = torch.randn(27, 1, C, device='cuda', generator=g)
     gm = torch.ones(C, device='cuda'); bt = torch.zeros(C, device='cuda')
     tf = timeit(lambda: ops.cpe_forward(x, w, gm, bt, neigh, True))
