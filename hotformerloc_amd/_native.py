@@ -215,6 +215,10 @@ SIGNATURES = {
     'hfl_ln_qkv_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_int64, c_int,
                          c_void_p]),
     'hfl_segment_softmax': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    'hfl_row_sq_norms': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    'hfl_flat_l2_topk_workspace': (c_int64, [c_int64, c_int64, c_int64, c_int]),
+    'hfl_flat_l2_topk': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p,
+                                 c_int64, c_void_p]),
 }
 
 _lib = None

@@ -1412,3 +1412,58 @@ def kd_rows(y: torch.Tensor, t: torch.Tensor, temperature: float):
     check(_native.load().hfl_kd_rows(kl.data_ptr(), dkl.data_ptr(), y.data_ptr(), t.data_ptr(), b, d, float(temperature),
                                      _stream()), 'hfl_kd_rows')
     return kl, dkl
+
+
+def _flat_l2_check(what: str, x: torch.Tensor):
+    if x.dim() != 2:
+        raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))
+    d = x.shape[1]
+    if d % 4 != 0 or d < 4 or d > 1024:
+        raise ValueError('%s: D must be a multiple of 4 in 4..1024, got %d' % (what, d))
+
+
+def row_sq_norms(x: torch.Tensor):
+    """Squared L2 norm of every row of x (n, D) fp32, one fmaf chain per row (`hfl_row_sq_norms`)."""
+    _dev(x)
+    _flat_l2_check('row_sq_norms', x)
+    x = _f32c(x)
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    if x.shape[0] > 0:
+        check(_native.load().hfl_row_sq_norms(out.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1], _stream()), 'hfl_row_sq_norms')
+    return out
+
+
+def flat_l2_topk(queries: torch.Tensor, database: torch.Tensor, k: int, database_sq_norms: torch.Tensor = None):
+    """The min(k, N) nearest database rows of every query by squared L2 distance, nearest first, equal distances by lower
+    index, without a (Q, N) matrix (`hfl_flat_l2_topk`).  queries (Q, D), database (N, D) fp32, D a multiple of 4 in 4..1024,
+    1 <= k <= 32; database_sq_norms: `row_sq_norms(database)` to reuse it.  Returns (dist (Q, kc) fp32, idx (Q, kc) int32)."""
+    _dev(queries, database, database_sq_norms)
+    _flat_l2_check('flat_l2_topk queries', queries)
+    _flat_l2_check('flat_l2_topk database', database)
+    if queries.shape[1] != database.shape[1]:
+        raise ValueError('flat_l2_topk: queries have D = %d, the database D = %d' % (queries.shape[1], database.shape[1]))
+    k = int(k)
+    if k < 1 or k > 32:
+        raise ValueError('flat_l2_topk: 1 <= k <= 32 expected, got %d' % k)
+    q_rows, n_rows, d = queries.shape[0], database.shape[0], queries.shape[1]
+    if n_rows < 1:
+        raise ValueError('flat_l2_topk: the database is empty')
+    queries, database = _f32c(queries), _f32c(database)
+    if database_sq_norms is not None:
+        database_sq_norms = _f32c(database_sq_norms)
+        if tuple(database_sq_norms.shape) != (n_rows,):
+            raise ValueError('flat_l2_topk: %d database norms expected, got %s' % (n_rows, tuple(database_sq_norms.shape)))
+    kc = min(k, n_rows)
+    dist = torch.empty((q_rows, kc), dtype=torch.float32, device=queries.device)
+    idx = torch.empty((q_rows, kc), dtype=torch.int32, device=queries.device)
+    if q_rows == 0:
+        return dist, idx
+    lib = _native.load()
+    ws_bytes = lib.hfl_flat_l2_topk_workspace(q_rows, n_rows, d, k)
+    if ws_bytes < 0:
+        raise ValueError('flat_l2_topk: unsupported shape Q = %d, N = %d, D = %d, k = %d' % (q_rows, n_rows, d, k))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=queries.device)
+    check(lib.hfl_flat_l2_topk(dist.data_ptr(), idx.data_ptr(), queries.data_ptr(), database.data_ptr(),
+                               None if database_sq_norms is None else database_sq_norms.data_ptr(), q_rows, n_rows, d, k,
+                               ws.data_ptr(), ws_bytes, _stream()), 'hfl_flat_l2_topk')
+    return dist, idx

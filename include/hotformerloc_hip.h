@@ -807,6 +807,29 @@ int hfl_ema_update(const hfl_ema_chunk* table, int n_chunks, float w, hfl_stream
 int hfl_kd_rows(float* kl, float* dkl_dy, const float* y, const float* t, int batch, int dim, float temperature,
                 hfl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * 13. Retrieval: streamed flat-L2 top-k search (eval/pnv_evaluate.py:199-223, the FAISS GpuIndexFlatL2 search)
+ * ---------------------------------------------------------------------- */
+/* out (n_rows): squared L2 norm of every row of x (n_rows, dim) fp32 row-major, one fmaf chain per row in column order (a
+ * row's value does not depend on n_rows or on the launch).  dim a multiple of 4 in 4..1024, else HFL_EINVAL. */
+int hfl_row_sq_norms(float* out, const float* x, int64_t n_rows, int dim, hfl_stream_t stream);
+
+/* For every row of queries (Q, D) the kc = min(k, N) nearest rows of database (N, D) by ||q||^2 + ||d||^2 - 2 q.d, both fp32
+ * row-major and 16-byte aligned: dist (Q, kc) fp32 and idx (Q, kc) int32, nearest first, ordered by the lexicographic key
+ * (distance, index) -- equal distances by lower index -- in every selection and merge step.  The dot products run on the
+ * fp32-input MFMA as one fmaf chain per pair in ascending column order from zero, so a pair's distance is bitwise the same
+ * for every Q, N partition and launch shape; it differs from the f64 distance of the same inputs by at most
+ * 2^-23 (D + 4) (||q||^2 + ||d||^2).  No (Q, N) matrix is stored: the only device memory besides inputs and outputs is the
+ * caller's workspace of hfl_flat_l2_topk_workspace(Q, N, D, k) bytes (both norm vectors and, when the database is split
+ * into segments over workgroups, Q x segments x 32 partial entries, segments <= 64; -1 for an unsupported shape).
+ * database_sq_norms: hfl_row_sq_norms of the database, or NULL to compute them here.  1 <= k <= 32, D a multiple of 4 in
+ * 4..1024, N >= 1, else HFL_EINVAL.  Launches on `stream`, no synchronisation, no host read.  Non-finite inputs: undefined
+ * order. */
+int64_t hfl_flat_l2_topk_workspace(int64_t n_queries, int64_t n_database, int64_t dim, int k);
+int hfl_flat_l2_topk(float* dist, int32_t* idx, const float* queries, const float* database, const float* database_sq_norms,
+                     int64_t n_queries, int64_t n_database, int dim, int k, void* workspace, int64_t workspace_bytes,
+                     hfl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
