@@ -1662,7 +1662,8 @@ int hfl_internal_attn_timing_read(double* ms, double* bytes, double* flops, int 
 /* 1 when hfl_window_attention_fwd_ex accepts the fp16 (hi, lo) qkv operand layout (flag 0x100) for this launch
  * configuration: what the v5 launcher itself asks (v5_geometry), for a problem with an RPE table */
 int hfl_window_attention_f16_ok(const hfl_window_attn_desc* d, int64_t n_rows_total) {
-  if (d == nullptr || d->n_heads <= 0 || d->patch_size % 16 != 0) return 0;
+  if (d == nullptr || d->n_heads <= 0 || d->n_heads > 16 || d->patch_size % 16 != 0) return 0;
+  if (d->dilation < 1 || d->n_relay < 0 || d->n_relay > 1 || (d->n_relay == 1 && d->dilation != 1)) return 0;   // (win_params)
   if (g_window_variant != 4) return 0;
   const int T = d->patch_size / 16 + d->n_relay;
   if (win_dispatch(T, d->n_relay, 0, [](auto, auto) { return 1; }) == 0) return 0;       // no kernel of that shape

@@ -19,6 +19,8 @@ from oracle.ocnn_ref import nn as onn
 from oracle.ocnn_ref.octree import Octree as OOctree, Points as OPoints, merge_octrees as omerge
 from oracle.testing import oracle_octree
 
+from attention_cases import octrees, pack_qkv_f16 as _pack_qkv_f16, window_plans
+
 DEV = 'cuda'
 
 
@@ -412,28 +414,12 @@ def test_cpe_training_function_matches_fp64_autograd_of_the_reference_formula():
 # ---------------------------------------------------------------------- attention
 def _plans(clouds, cfg, octree_depth):
     params, _ = load_config(cfg)
-    ref = oracle_octree(clouds, octree_depth)
-    dev = build_batch_octree(clouds, octree_depth, 2, DEV)
+    ref, dev = octrees(clouds, octree_depth)
     md = octree_depth - 2
     args = dict(patch_size=params.patch_size, dilation=params.dilation, max_depth=md,
                 start_depth=md - 3, num_pyramid_levels=3, num_octf_levels=1,
                 adape_mode=params.ADaPE_mode)
-    return params, ref, dev, hotformer_ref.WindowPlan(ref, **args), WindowPlan(dev, **args)
-
-
-def _pack_qkv_f16(qkv: torch.Tensor, H: int, q_scale: float) -> torch.Tensor:
-    """fp32 (rows, 3C) [q | k | v] -> the operand layout of hfl_linear_x3_qkv (csrc/gemm_x3.hip EPI 2): per region and
-    head [16 x hi | 16 x lo] fp16 (any split with hi + lo = v to 22 bits is valid), q times q_scale; returned as an
-    opaque float32 (rows, 3C) buffer."""
-    rows, c3 = qkv.shape
-    C = c3 // 3
-    x = qkv.clone().float()
-    x[:, :C] *= q_scale
-    x = x.view(rows, 3, H, 16)
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    packed = torch.stack([hi, lo], dim=3).contiguous()            # (rows, 3, H, 2, 16) fp16 = 12 C bytes per row
-    return packed.view(rows, -1).view(torch.float32).view(rows, c3).contiguous()
+    return (params, ref, dev) + window_plans(ref, dev, **args)
 
 
 def test_linear_x3_qkv_epilogue_writes_the_attention_operand_layout():
