@@ -17,5 +17,6 @@ _os.environ.setdefault('TENSILE_STREAMK_DATA_PARALLEL', '1')
 from .params import ModelParams, load_config            # noqa: F401,E402
 from .model_factory import model_factory                 # noqa: F401,E402
 from .octree import Octree, Points, merge_octrees, build_batch_octree   # noqa: F401,E402
+from .optim import FusedAdam                             # noqa: F401,E402
 
 __version__ = '0.1.0'

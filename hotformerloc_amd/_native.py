@@ -67,6 +67,18 @@ class BlockIO(ctypes.Structure):
                 ('phase', c_int32)]
 
 
+class AdamChunk(ctypes.Structure):
+    """hfl_adam_chunk (the device table is written as int64 rows of this layout: ops.adam_chunk_rows)"""
+    _fields_ = [('param', c_void_p), ('grad', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p), ('ema', c_void_p),
+                ('count', c_int32), ('slot', c_int32)]
+
+
+class AdamSlot(ctypes.Structure):
+    """hfl_adam_slot"""
+    _fields_ = [('step_size', c_float), ('bias_correction2_sqrt', c_float), ('one_minus_beta1', c_float), ('beta2', c_float),
+                ('one_minus_beta2', c_float), ('eps', c_float), ('decay', c_float), ('decoupled', c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/hotformerloc_hip.h declares
 SIGNATURES = {
     'hfl_version': (c_int, []),
@@ -174,6 +186,7 @@ SIGNATURES = {
     'hfl_smoothap_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_float, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
+    'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     'hfl_gemm_bf16_tn': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     'hfl_gemm_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),

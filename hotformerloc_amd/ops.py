@@ -1396,6 +1396,155 @@ def ema_update(table, n_chunks: int, w: float):
     check(_native.load().hfl_ema_update(table.data_ptr(), n_chunks, float(w), _stream()), 'hfl_ema_update')
 
 
+ADAM_CHUNK = 8192         # HFL_ADAM_CHUNK
+ADAM_MAX_SLOTS = 16       # HFL_ADAM_MAX_SLOTS
+
+
+def adam_slot(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, decoupled: bool, step: int):
+    """The fields of one `hfl_adam_slot` as Python floats (doubles), in the structure's order; ctypes rounds each once to
+    float.  The formulas are torch's `_single_tensor_adam` with its Python scalars: the bias corrections from the integer
+    step count, `step_size = lr / bias_correction1`, `bias_correction2 ** 0.5`."""
+    if step < 1:
+        raise ValueError('adam_slot: the step count starts at 1, got %r' % (step,))
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    decay = 1 - lr * weight_decay if decoupled else weight_decay
+    return (lr / bias_correction1, bias_correction2 ** 0.5, 1 - beta1, beta2, 1 - beta2, eps, decay, int(bool(decoupled)))
+
+
+def adam_chunk_rows(numels, param_ptrs, grad_ptrs, exp_avg_ptrs, exp_avg_sq_ptrs, ema_ptrs, slots):
+    """Host half of `adam_table`, on plain integers (no device needed): tensor i has numels[i] fp32 elements at the given
+    addresses, 0 = null (grad: the parameter takes no step this time; ema: it has no average).  Every tensor is cut at
+    multiples of ADAM_CHUNK elements; a tensor with neither gradient nor average, or without elements, emits nothing.
+    Returns (rows, owner, launches): rows (n, 6) int64 in the layout of `hfl_adam_chunk` (five addresses, then
+    count | slot % ADAM_MAX_SLOTS << 32), owner (n,) the index of each row's tensor, launches a list of (first row, rows,
+    first slot): rows are ordered so that every run of ADAM_MAX_SLOTS consecutive slots is one contiguous launch."""
+    import numpy as np
+    rows, owner = [], []
+    for i, n in enumerate(numels):
+        if n == 0 or (not grad_ptrs[i] and not ema_ptrs[i]):
+            continue
+        slot = int(slots[i]) if grad_ptrs[i] else 0
+        if slot < 0:
+            raise ValueError('adam_chunk_rows: negative slot %d' % slot)
+        off = np.arange(0, n, ADAM_CHUNK, dtype=np.int64)
+        chunk = np.empty((off.shape[0], 7), dtype=np.int64)
+        for col, base in enumerate((param_ptrs[i], grad_ptrs[i], exp_avg_ptrs[i], exp_avg_sq_ptrs[i], ema_ptrs[i])):
+            chunk[:, col] = base + 4 * off if base and (col in (0, 4) or grad_ptrs[i]) else 0
+        chunk[:, 5] = np.minimum(n - off, ADAM_CHUNK) | ((slot % ADAM_MAX_SLOTS) << 32)
+        chunk[:, 6] = slot // ADAM_MAX_SLOTS
+        rows.append(chunk)
+        owner.append(np.full(off.shape[0], i, dtype=np.int64))
+    if not rows:
+        return np.empty((0, 6), dtype=np.int64), np.empty((0,), dtype=np.int64), []
+    rows, owner = np.concatenate(rows, 0), np.concatenate(owner, 0)
+    order = np.argsort(rows[:, 6], kind='stable')
+    rows, owner = rows[order], owner[order]
+    launches = []
+    for group in np.unique(rows[:, 6]):
+        idx = np.nonzero(rows[:, 6] == group)[0]
+        launches.append((int(idx[0]), int(idx.shape[0]), int(group) * ADAM_MAX_SLOTS))
+    return np.ascontiguousarray(rows[:, :6]), owner, launches
+
+
+class AdamTable:
+    """Device table of `adam_table` with what the host needs to refresh its gradient column."""
+    __slots__ = ('table', 'n_chunks', 'launches', 'grad_rows', 'grad_owner', 'grad_offset')
+
+
+def _adam_operands(params, grads, exp_avgs, exp_avg_sqs, emas):
+    lists = [list(params), list(grads), list(exp_avgs), list(exp_avg_sqs), list(emas)]
+    if len({len(x) for x in lists}) != 1:
+        raise ValueError('adam_table: lists of %s entries' % '/'.join(str(len(x)) for x in lists))
+    _dev(*(t for col in lists for t in col))
+    for row in zip(*lists):
+        p = row[0]
+        for t in row:
+            if t is None:
+                continue
+            if t.is_sparse:
+                raise TypeError('adam_step takes dense tensors (sparse gradients are not supported)')
+            if t.dtype != torch.float32:
+                raise TypeError('adam_step takes float32 tensors, got %s' % t.dtype)
+            if t.shape != p.shape:
+                raise ValueError('adam_step: shapes %s and %s differ' % (tuple(t.shape), tuple(p.shape)))
+            if not t.is_contiguous():
+                raise ValueError('adam_step needs contiguous tensors')
+        if row[1] is not None and (row[2] is None or row[3] is None):
+            raise ValueError('adam_step: a parameter with a gradient needs exp_avg and exp_avg_sq')
+    return lists
+
+
+def adam_table(params, grads, exp_avgs, exp_avg_sqs, emas, slots) -> AdamTable:
+    """Device table of `hfl_adam_chunk` entries for `adam_step`.  Six lists of one length: fp32 contiguous device tensors of
+    the parameter's shape, `grads[i]` / `emas[i]` None where the parameter takes no step / has no average (the moments may
+    then be None too), `slots[i]` the index of parameter i's hyper-parameters in the list `adam_step` receives.  Empty tensors
+    are skipped.  The table holds raw pointers: it is valid only while every tensor keeps its `data_ptr()` (the caller
+    revalidates; moved gradients alone are followed by `adam_refresh_grads`)."""
+    params, grads, exp_avgs, exp_avg_sqs, emas = _adam_operands(params, grads, exp_avgs, exp_avg_sqs, emas)
+
+    def ptrs(col):
+        return [0 if t is None else t.data_ptr() for t in col]
+    gp = ptrs(grads)
+    rows, owner, launches = adam_chunk_rows([p.numel() for p in params], ptrs(params), gp, ptrs(exp_avgs), ptrs(exp_avg_sqs),
+                                            ptrs(emas), slots)
+    t = AdamTable()
+    t.n_chunks, t.launches = int(rows.shape[0]), launches
+    t.table = torch.from_numpy(rows).to(params[0].device) if t.n_chunks else None
+    import numpy as np
+    t.grad_rows = np.nonzero(rows[:, 1])[0]
+    t.grad_owner = owner[t.grad_rows]
+    t.grad_offset = rows[t.grad_rows, 1] - np.asarray(gp, dtype=np.int64)[t.grad_owner]
+    if t.n_chunks and t.grad_rows.shape[0] != t.n_chunks:
+        t.grad_rows = torch.from_numpy(t.grad_rows).to(params[0].device)
+    else:
+        t.grad_rows = None                                     # every row has a gradient: the column is written whole
+    return t
+
+
+def adam_refresh_grads(t: AdamTable, grads):
+    """Rewrite the gradient column of `t` for gradient tensors at new addresses: the same parameters have gradients as when
+    the table was built (the caller checks), of the same shapes; nothing else of the table changes."""
+    import numpy as np
+    grads = list(grads)
+    _dev(*grads)
+    for g in grads:
+        if g is None:
+            continue
+        if g.is_sparse:
+            raise TypeError('adam_step takes dense tensors (sparse gradients are not supported)')
+        if g.dtype != torch.float32:
+            raise TypeError('adam_step takes float32 tensors, got %s' % g.dtype)
+        if not g.is_contiguous():
+            raise ValueError('adam_step needs contiguous tensors')
+    if t.n_chunks == 0 or t.grad_owner.shape[0] == 0:
+        return
+    base = np.asarray([0 if g is None else g.data_ptr() for g in grads], dtype=np.int64)[t.grad_owner]
+    if (base == 0).any():
+        raise ValueError('adam_refresh_grads: a parameter of the table lost its gradient; build a new table')
+    col = torch.from_numpy(base + t.grad_offset).to(t.table.device)
+    if t.grad_rows is None:
+        t.table[:, 1] = col
+    else:
+        t.table[t.grad_rows, 1] = col
+
+
+def adam_step(t: AdamTable, slots, w: float = 0.0):
+    """One Adam / AdamW step (and EMA line, weight `w`) over every chunk of an `adam_table`: one launch per run of
+    ADAM_MAX_SLOTS slots, i.e. one launch unless the parameters sit at more than ADAM_MAX_SLOTS distinct (group, step count)
+    combinations.  `slots`: a list of `adam_slot(...)` tuples, indexed by the table's slot numbers."""
+    if t.n_chunks == 0:
+        return
+    _dev(t.table)
+    assert t.table.dtype == torch.int64 and t.table.is_contiguous() and tuple(t.table.shape) == (t.n_chunks, 6)
+    lib, stream = _native.load(), _stream()
+    for first, n, slot0 in t.launches:
+        part = slots[slot0:slot0 + ADAM_MAX_SLOTS]
+        arr = (_native.AdamSlot * max(len(part), 1))(*[_native.AdamSlot(*s) for s in part])
+        check(lib.hfl_adam_step(t.table.data_ptr() + 48 * first, n, ctypes.addressof(arr) if part else None, len(part),
+                                float(w), stream), 'hfl_adam_step')
+
+
 def kd_rows(y: torch.Tensor, t: torch.Tensor, temperature: float):
     """Per row: KL(softmax(t / T) || softmax(y / T)) and its derivative (p - q) / T with respect to y.  y, t: (B, D) fp32,
     D a multiple of 64 up to 1024.  Returns (kl (B,), dkl_dy (B, D))."""

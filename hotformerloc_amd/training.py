@@ -285,7 +285,8 @@ def multistaged_training_step(model: torch.nn.Module, minibatches: List[dict], p
     the student rows, and stage 2 adds `mesa * kdloss(embeddings, embeddings_ema)` to the loss before the backward.  `stats`
     is what `loss_fn` returned (its 'loss' is the listwise loss alone, as in the reference, which takes it before the sum)
     plus `stats['mesa_kd']`, the value of `kdloss`, only when the term was evaluated.  Whenever `model_ema` is given the
-    training phase ends with `model_ema.update(model)` after the optimizer step, also with `mesa == 0`.  The EMA needs no
+    training phase ends with `model_ema.update(model)` after the optimizer step, also with `mesa == 0` (skipped when the
+    optimizer is a `FusedAdam` with this very teacher attached: its `step()` has then applied the update already).  The EMA needs no
     communication: after the gradient all-reduce every rank holds identical weights, hence identical averages.
     `phase='val'` touches neither the teacher nor the EMA.  The reference does run the teacher and the distillation term in
     its validation phase (`trainer.py:315-334, 434`), but nothing it returns depends on them: `stats` is taken before the sum
@@ -354,6 +355,6 @@ def multistaged_training_step(model: torch.nn.Module, minibatches: List[dict], p
         allreduce_gradients(model.parameters(), group, force=force_collectives)
     if optimizer is not None:
         optimizer.step()
-    if model_ema is not None:
-        model_ema.update(model)
+    if model_ema is not None and getattr(optimizer, 'ema', None) is not model_ema:
+        model_ema.update(model)                            # a FusedAdam with this teacher attached moved it in its launch
     return stats

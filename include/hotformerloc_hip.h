@@ -808,6 +808,50 @@ int hfl_kd_rows(float* kl, float* dkl_dy, const float* y, const float* t, int ba
                 hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 12b. Optimizer step: Adam / AdamW with the weight EMA in the same launch (training/trainer.py:140-156, 356, 360-361)
+ * ---------------------------------------------------------------------- */
+/* One chunk of one parameter: `count` (1..HFL_ADAM_CHUNK) fp32 elements at every non-null pointer.  The host cuts each
+ * parameter at multiples of HFL_ADAM_CHUNK elements, so a chunk is 16-byte aligned exactly when its tensors are.
+ * grad == NULL: the parameter takes no optimizer step (exp_avg / exp_avg_sq are not touched); ema == NULL: no average.
+ * With both NULL the chunk does nothing. */
+#define HFL_ADAM_CHUNK 8192
+#define HFL_ADAM_MAX_SLOTS 16
+typedef struct hfl_adam_chunk {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* ema;
+  int32_t count;
+  int32_t slot; /* index into the launch's slots, 0..HFL_ADAM_MAX_SLOTS-1 */
+} hfl_adam_chunk;
+/* Hyper-parameters of one (param group, step count) combination.  The host computes every field in double precision from
+ * the Python scalars and rounds once to float, as torch's single-tensor path does when it hands its scalars to an op:
+ * 1 - beta is therefore its own field (1.f - (float)beta is another number).
+ * decay: weight_decay when decoupled == 0 (L2: g += decay * p), 1 - lr * weight_decay when decoupled != 0 (p *= decay). */
+typedef struct hfl_adam_slot {
+  float step_size; /* lr / (1 - beta1^step) */
+  float bias_correction2_sqrt; /* sqrt(1 - beta2^step) */
+  float one_minus_beta1;
+  float beta2;
+  float one_minus_beta2;
+  float eps;
+  float decay;
+  int32_t decoupled;
+} hfl_adam_slot;
+/* One optimizer step over every chunk of the DEVICE table (n_chunks entries), one launch, one workgroup per chunk; the
+ * n_slots (0..HFL_ADAM_MAX_SLOTS) entries of the HOST array `slots` travel by value in the kernel arguments.  Per element,
+ * in the order and with the roundings of torch's _single_tensor_adam: decay (see hfl_adam_slot), m += (1 - beta1)(g - m),
+ * v = beta2 v + (1 - beta2) g g, p -= step_size m / (sqrt(v) / bias_correction2_sqrt + eps) with correctly rounded sqrt
+ * and division; then, where ema != NULL, ema <- ema + w * (p - ema) on the value just stored: bitwise what hfl_ema_update
+ * would produce if run afterwards.  The table is trusted as hfl_ema_update's is: every chunk lies inside its tensors, no
+ * written chunk overlaps another, every slot index is below n_slots.  n_chunks < 0, a NULL table with chunks present,
+ * n_slots outside 0..HFL_ADAM_MAX_SLOTS, NULL slots with n_slots > 0, or w outside [0, 1]: HFL_EINVAL.  Zero chunks:
+ * HFL_OK without a launch. */
+int hfl_adam_step(const hfl_adam_chunk* table, int n_chunks, const hfl_adam_slot* slots, int n_slots, float w,
+                  hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 13. Retrieval: streamed flat-L2 top-k search (eval/pnv_evaluate.py:199-223, the FAISS GpuIndexFlatL2 search)
  * ---------------------------------------------------------------------- */
 /* out (n_rows): squared L2 norm of every row of x (n_rows, dim) fp32 row-major, one fmaf chain per row in column order (a
