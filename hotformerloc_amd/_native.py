@@ -7,7 +7,7 @@ this module raises.  Build it with `python -m hotformerloc_amd.build`
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libhotformerloc_hip.so')
@@ -79,6 +79,19 @@ class AdamSlot(ctypes.Structure):
                 ('one_minus_beta2', c_float), ('eps', c_float), ('decay', c_float), ('decoupled', c_int32)]
 
 
+class AugmentCloud(ctypes.Structure):
+    """hfl_augment_cloud (the device table is written as 12-word rows of this layout: augment.AugmentParams.rows)"""
+    _fields_ = [('remove_k', c_int32), ('block', c_int32), ('rot_cos', c_float), ('rot_sin', c_float), ('trans', c_float * 3),
+                ('block_u', c_float * 4), ('reserved', c_float)]
+
+
+class AugmentConfig(ctypes.Structure):
+    """hfl_augment_config"""
+    _fields_ = [('normalize', c_int32), ('cylindrical_mask', c_int32), ('cylindrical_transform', c_int32),
+                ('augment', c_int32), ('rotate', c_int32), ('set_rotate', c_int32), ('flip_axis', c_int32),
+                ('set_cos', c_float), ('set_sin', c_float), ('jitter_sigma', c_float), ('jitter_clip', c_float)]
+
+
 # name -> (restype, argtypes): every symbol include/hotformerloc_hip.h declares
 SIGNATURES = {
     'hfl_version': (c_int, []),
@@ -105,6 +118,8 @@ SIGNATURES = {
     'hfl_token_meta': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'hfl_octree_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]),
     'hfl_prepare_clouds': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'hfl_augment_clouds': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   ctypes.POINTER(AugmentConfig), c_uint64, c_int64, c_void_p, c_void_p]),
     'hfl_tap_lists_workspace': (c_int64, [c_int64, c_int]),
     'hfl_tap_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'hfl_tap_lists_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

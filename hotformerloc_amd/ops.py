@@ -1616,3 +1616,34 @@ def flat_l2_topk(queries: torch.Tensor, database: torch.Tensor, k: int, database
                                None if database_sq_norms is None else database_sq_norms.data_ptr(), q_rows, n_rows, d, k,
                                ws.data_ptr(), ws_bytes, _stream()), 'hfl_flat_l2_topk')
     return dist, idx
+
+
+def augment_clouds(points, sizes, table_rows, config, seed: int, cloud_base: int = 0, selection_keys=None,
+                   return_index: bool = False):
+    """`hfl_augment_clouds` on a concatenated batch: points (P, 3) fp32 on the GPU, `sizes` the clouds' point counts (host
+    integers), `table_rows` the (B, 12) uint32 host table of `hfl_augment_cloud` rows, `config` a `_native.AugmentConfig`,
+    `selection_keys` an optional (P,) int32 device tensor holding uint32 bit patterns.  Returns (out (P, 3), counts (B,)
+    int32, index (P,) int32 or None): the kept points of cloud b start at its input offset."""
+    import numpy as np
+    _dev(points, selection_keys)
+    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3:
+        raise TypeError('augment_clouds takes a contiguous (P, 3) float32 tensor')
+    off_host = np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]), dtype=np.int64)
+    rows = np.ascontiguousarray(table_rows, dtype=np.uint32)
+    batch = len(off_host) - 1
+    if rows.shape != (batch, 12) or int(off_host[-1]) != points.shape[0]:
+        raise ValueError('augment_clouds: %d clouds of %d points, table %r, points %r'
+                         % (batch, int(off_host[-1]), rows.shape, tuple(points.shape)))
+    if selection_keys is not None and (selection_keys.dtype != torch.int32 or selection_keys.numel() != points.shape[0]
+                                       or not selection_keys.is_contiguous()):
+        raise TypeError('augment_clouds: selection keys are one contiguous int32 word per point')
+    off = torch.from_numpy(off_host).to(points.device, non_blocking=True)
+    table = torch.from_numpy(rows.view(np.int32)).to(points.device, non_blocking=True)
+    out = torch.empty_like(points)
+    counts = torch.empty(batch, dtype=torch.int32, device=points.device)
+    index = torch.empty(points.shape[0], dtype=torch.int32, device=points.device) if return_index else None
+    check(_native.load().hfl_augment_clouds(
+        out.data_ptr(), counts.data_ptr(), index.data_ptr() if return_index else None, points.data_ptr(), off.data_ptr(),
+        off_host.ctypes.data, batch, table.data_ptr(), rows.ctypes.data, ctypes.byref(config), int(seed) & (2 ** 64 - 1),
+        int(cloud_base), selection_keys.data_ptr() if selection_keys is not None else None, _stream()), 'hfl_augment_clouds')
+    return out, counts, index

@@ -358,3 +358,33 @@ def multistaged_training_step(model: torch.nn.Module, minibatches: List[dict], p
     if model_ema is not None and getattr(optimizer, 'ema', None) is not model_ema:
         model_ema.update(model)                            # a FusedAdam with this teacher attached moved it in its launch
     return stats
+
+
+def make_training_minibatches(clouds, split_size: Optional[int], cfg, depth: int, full_depth: int = 2, seed: int = 0,
+                              generator=None, params=None, cylindrical: str = 'device', device='cuda') -> List[dict]:
+    """Raw clouds of one (local) batch -> the `minibatches` argument of `multistaged_training_step`: the reference's
+    `TrainTransform`, masks, `TrainSetTransform` and quantizer (`hotformerloc_amd.augment`, one launch per minibatch), then
+    `build_batch_octree` per chunk of `split_size` clouds (`dataset_utils.py:126-134`; None or 0 = one minibatch).
+
+    The scalar table is drawn ONCE for the whole batch (`augment.draw_params(sizes, cfg, generator)`, or `params`), so the
+    batch-wide rotation and flip are the same in every minibatch as in the reference, and each chunk is augmented with its
+    slice of the table and `cloud_base` = index of its first cloud: every cloud's points are those it would get in one
+    call over the whole batch, whatever `split_size` is."""
+    from . import augment
+    from .octree import build_batch_octree
+    clouds = list(clouds)
+    if not clouds:
+        return []
+    sizes = [int(torch.as_tensor(c).reshape(-1, 3).shape[0]) for c in clouds]
+    if params is None:
+        params = augment.draw_params(sizes, cfg, generator)
+    if len(params) != len(clouds):
+        raise ValueError('params holds %d clouds, the batch %d' % (len(params), len(clouds)))
+    step = len(clouds) if not split_size else int(split_size)
+    out = []
+    for start in range(0, len(clouds), step):
+        stop = min(start + step, len(clouds))
+        pts = augment.augment_clouds(clouds[start:stop], cfg, seed=seed, params=params.slice(start, stop), cloud_base=start,
+                                     cylindrical=cylindrical, device=device)
+        out.append({'octree': build_batch_octree(pts, depth, full_depth, device)})
+    return out

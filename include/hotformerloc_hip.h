@@ -170,6 +170,49 @@ int hfl_prepare_clouds(float* out_points, int32_t* out_counts, const float* poin
                        const int64_t* cloud_offsets, int batch, int normalize, int cylindrical_mask,
                        int cylindrical_transform, hfl_stream_t stream);
 
+/* The training augmentation of the reference for a whole batch, fused with the pre-steps above (csrc/augment.hip):
+ * per cloud Normalize, JitterPoints(0.001, clip 0.002), RemoveRandomPoints, [RandomRotation about z],
+ * RandomTranslation, RemoveRandomBlock (datasets/CSWildPlaces/CSWildPlaces_train.py:19-57, datasets/augmentation.py)
+ * and the masks of datasets/base_datasets.py:77-83; then the batch-wide TrainSetTransform (z rotation, flip;
+ * datasets/dataset_utils.py:111-116) and the cylindrical transform.
+ *
+ * The random scalars come in a table, one row per cloud (hotformerloc_amd/augment.py draws them): */
+typedef struct hfl_augment_cloud {
+  int32_t remove_k;      /* RemoveRandomPoints: int(n * r) points are set to (0,0,0); 0 <= remove_k <= n */
+  int32_t block;         /* RemoveRandomBlock's coin: 1 = erase */
+  float rot_cos, rot_sin;/* RandomRotation: float32(cos theta), float32(sin theta); x' = x cos + y sin, y' = y cos - x sin */
+  float trans[3];        /* RandomTranslation: float32(max_delta * N(0,1)) */
+  float block_u[4];      /* RemoveRandomBlock: U(scale), U(ratio), U(0,1) for x, U(0,1) for y, rounded to float32 */
+  float reserved;
+} hfl_augment_cloud;
+
+typedef struct hfl_augment_config {
+  int32_t normalize;             /* bounding-box Normalize first */
+  int32_t cylindrical_mask;      /* also drop |xy| > 1 */
+  int32_t cylindrical_transform; /* (x,y,z) -> (rho,phi,z) last */
+  int32_t augment;               /* 0: none of jitter / removal / rotation / translation / block (aug_mode 0) */
+  int32_t rotate;                /* the per-cloud z rotation (aug_mode 2) */
+  int32_t set_rotate;            /* the batch-wide z rotation (set_aug_mode 1) */
+  int32_t flip_axis;             /* batch-wide flip: -1 none, 0 x, 1 y, 2 z */
+  float set_cos, set_sin;
+  float jitter_sigma, jitter_clip;
+} hfl_augment_config;
+
+/* points (P,3) with cloud b at rows [cloud_offsets[b], cloud_offsets[b+1]); the kept points of cloud b are written, in
+ * order, from row cloud_offsets[b] of out_points (P,3) on, out_counts[b] says how many, and out_index (P, may be null)
+ * receives the index within its cloud of every kept point.  cloud_offsets and table are device memory;
+ * host_cloud_offsets and host_table are the same values in host memory, which the launcher validates
+ * (HFL_EINVAL: a null or aliased buffer, a negative cloud size, remove_k outside [0, n]).
+ * Per-point random numbers are Philox4x32-10 keyed by `seed` with counter (point index in its cloud, cloud index +
+ * cloud_base, stream, 0): a point's numbers depend on (seed, cloud, point) only.  RemoveRandomPoints removes the
+ * remove_k points with the smallest 32-bit selection keys, ties to the lower index; selection_keys (P, device, may be
+ * null = Philox stream 1) lets a caller with a generator of its own supply the keys. */
+int hfl_augment_clouds(float* out_points, int32_t* out_counts, int32_t* out_index, const float* points,
+                       const int64_t* cloud_offsets, const int64_t* host_cloud_offsets, int batch,
+                       const hfl_augment_cloud* table, const hfl_augment_cloud* host_table,
+                       const hfl_augment_config* config, uint64_t seed, int64_t cloud_base,
+                       const uint32_t* selection_keys, hfl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * 3. Octree convolution gather  (ocnn.nn.OctreeConv's octree2col; call sites
  *    models/layers/octformer_layers.py:89-95, models/octformer_backbone.py:470-475)
