@@ -200,6 +200,8 @@ SIGNATURES = {
     'hfl_set_variant': (c_int, [c_char_p, c_int]),
     'hfl_smoothap_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_float, c_void_p]),
+    'hfl_pairwise_dist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'hfl_pairwise_dist_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

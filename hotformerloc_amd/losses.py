@@ -3,8 +3,12 @@
 `tau1`, `similarity`, `positives_per_query` of the training config).  Same constructor, same call
 signature `(embeddings, positives_mask, negatives_mask) -> (loss, stats)`, same `stats` keys.
 
-The (B, P, B) ranking algebra and its gradient run in one HIP kernel per call (`hfl_smoothap_rows`);
-the affinity matrix, the top-k selection of positives and dE = (dS + dS^T) E are dense torch ops.
+The (B, P, B) ranking algebra and its gradient run in one HIP kernel per call (`hfl_smoothap_rows`).
+`similarity='euclidean'` is what every shipped training config resolves to (none sets the key and `TrainingParams` defaults
+it, `misc/utils.py:204`): the affinity is `-cdist(E, E)` (`loss_utils.py:55-60`), here `euclidean_affinity`, two HIP kernels
+that sum the differences themselves (`hfl_pairwise_dist`, `hfl_pairwise_dist_bwd`).  `similarity='cosine'`, the class's
+own default, keeps the affinity E E^T and dE = (dS + dS^T) E as dense torch ops.  The top-k selection of positives is a
+torch op in both.  `make_losses(params)` is the reference's factory (`models/losses/loss.py:10-24`).
 
 `kdloss` is the distillation term of the reference's MESA step (`models/losses/loss.py:138-147`): KL rows and their gradient in
 one HIP launch (`hfl_kd_rows`)."""
@@ -35,10 +39,32 @@ class _SmoothAPRows(torch.autograd.Function):
         return dap * grad_ap[:, None], None, None, None, None
 
 
+class _EuclideanAffinity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb):
+        dist = ops.pairwise_dist(emb)
+        ctx.save_for_backward(dist, emb)
+        return -dist
+
+    @staticmethod
+    def backward(ctx, grad_aff):
+        dist, emb = ctx.saved_tensors
+        return ops.pairwise_dist_bwd(-grad_aff, dist, emb)
+
+
+def euclidean_affinity(emb):
+    """`compute_aff(emb, similarity='euclidean')` of the reference (`loss_utils.py:55-60`): -||e_i - e_j|| as a (B, B) matrix,
+    differentiable for an arbitrary (B, B) gradient.  emb: (B, D) fp32 rows on the GPU.  Rows at distance 0 (the diagonal
+    among them) receive no gradient from each other, as in `torch.cdist`."""
+    if emb.device.type != 'cuda':
+        raise _native.NativeLibraryError('euclidean_affinity runs on the GPU only (no CPU fallback)')
+    return _EuclideanAffinity.apply(emb.float().contiguous())
+
+
 class TruncatedSmoothAP:
     def __init__(self, tau1: float = 0.01, similarity: str = 'cosine', positives_per_query: int = 4):
-        if similarity != 'cosine':
-            raise NotImplementedError("similarity=%r: every shipped training config uses 'cosine'" % similarity)
+        if similarity not in ('cosine', 'euclidean'):
+            raise NotImplementedError('Incorrect similarity measure: %s' % (similarity,))       # loss_utils.py:62
         self.tau1 = tau1
         self.similarity = similarity
         self.positives_per_query = positives_per_query
@@ -50,7 +76,10 @@ class TruncatedSmoothAP:
         positives_mask = positives_mask.to(device)
         negatives_mask = negatives_mask.to(device)
         emb = embeddings.float()
-        s_qz = emb @ emb.t()                                                       # compute_aff, cosine
+        if self.similarity == 'cosine':
+            s_qz = emb @ emb.t()                                                   # compute_aff, cosine
+        else:
+            s_qz = euclidean_affinity(emb)                                         # compute_aff, euclidean
         s_pos = s_qz.detach().clone()
         s_pos.masked_fill_(torch.logical_not(positives_mask), -np.inf)
         idx = torch.topk(s_pos, k=self.positives_per_query, dim=1, largest=True, sorted=True)[1]
@@ -71,6 +100,18 @@ class TruncatedSmoothAP:
                      'loss': loss.item(), 'ap': ap.item(),
                      'avg_embedding_norm': embeddings.norm(dim=1).mean().item()}
         return loss, stats
+
+
+def make_losses(params):
+    """The reference's loss factory (`models/losses/loss.py:10-24`).  `params`: any object with `.loss` and, for
+    'truncatedsmoothap', `.tau1`, `.similarity` and `.positives_per_query` (what `TrainingParams` resolves from a training
+    config).  The two batch-hard losses, which no shipped config selects, are not built."""
+    if params.loss in ('batchhardtripletmarginloss', 'batchhardcontrastiveloss'):
+        raise NotImplementedError('loss %r is not built: every shipped training config selects TruncatedSmoothAP' % params.loss)
+    if params.loss == 'truncatedsmoothap':
+        return TruncatedSmoothAP(tau1=params.tau1, similarity=params.similarity,
+                                 positives_per_query=params.positives_per_query)
+    raise NotImplementedError('Unknown loss: {}'.format(params.loss))
 
 
 class _KdRows(torch.autograd.Function):

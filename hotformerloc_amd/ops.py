@@ -1563,6 +1563,37 @@ def kd_rows(y: torch.Tensor, t: torch.Tensor, temperature: float):
     return kl, dkl
 
 
+def pairwise_dist(emb: torch.Tensor):
+    """dist[i, j] = ||emb[i] - emb[j]||, summed over the differences themselves (`hfl_pairwise_dist`).  emb: (B, D) fp32,
+    any B >= 1 and D >= 1.  Returns (B, B) fp32: bitwise symmetric, exactly 0 on the diagonal and between equal rows."""
+    _dev(emb)
+    if emb.dim() != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise ValueError('pairwise_dist: a (B, D) matrix with B >= 1 and D >= 1 expected, got %s' % (tuple(emb.shape),))
+    emb = _f32c(emb)
+    b, d = emb.shape
+    dist = torch.empty((b, b), dtype=torch.float32, device=emb.device)
+    check(_native.load().hfl_pairwise_dist(dist.data_ptr(), emb.data_ptr(), b, d, _stream()), 'hfl_pairwise_dist')
+    return dist
+
+
+def pairwise_dist_bwd(grad_dist: torch.Tensor, dist: torch.Tensor, emb: torch.Tensor):
+    """Gradient of sum(grad_dist * pairwise_dist(emb)) with respect to emb (`hfl_pairwise_dist_bwd`): row i is
+    sum_j (grad_dist[i, j] + grad_dist[j, i]) (emb[i] - emb[j]) / dist[i, j], pairs at distance 0 contributing nothing.
+    grad_dist: any (B, B) fp32 matrix; dist: `pairwise_dist(emb)`; emb: (B, D) fp32.  Returns (B, D) fp32."""
+    _dev(grad_dist, dist, emb)
+    if emb.dim() != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise ValueError('pairwise_dist_bwd: a (B, D) matrix with B >= 1 and D >= 1 expected, got %s' % (tuple(emb.shape),))
+    b, d = emb.shape
+    if tuple(grad_dist.shape) != (b, b) or tuple(dist.shape) != (b, b):
+        raise ValueError('pairwise_dist_bwd: (%d, %d) grad_dist and dist expected for %d rows, got %s and %s'
+                         % (b, b, b, tuple(grad_dist.shape), tuple(dist.shape)))
+    grad_dist, dist, emb = _f32c(grad_dist), _f32c(dist), _f32c(emb)
+    d_emb = torch.empty((b, d), dtype=torch.float32, device=emb.device)
+    check(_native.load().hfl_pairwise_dist_bwd(d_emb.data_ptr(), grad_dist.data_ptr(), dist.data_ptr(), emb.data_ptr(), b, d,
+                                               _stream()), 'hfl_pairwise_dist_bwd')
+    return d_emb
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

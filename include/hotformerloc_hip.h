@@ -828,6 +828,23 @@ int hfl_smoothap_rows(float* ap, float* dap_ds, const float* sim, const uint8_t*
                       float tau, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11b. Euclidean affinity of TruncatedSmoothAP (models/losses/loss_utils.py:55-60: -torch.cdist(E, E), the similarity
+ *      every shipped training config resolves to, misc/utils.py:204)
+ * ---------------------------------------------------------------------- */
+/* dist (B,B) f32: dist[i,j] = sqrt(sum_k (emb[i,k] - emb[j,k])^2), summed over the differences themselves (never
+ * |x|^2 + |y|^2 - 2 x.y, which cancels for the near pairs the loss depends on).  The diagonal and every pair of equal rows
+ * are exactly 0, dist is bitwise symmetric, every element has one writer (two launches agree bitwise).  emb (B,D) f32
+ * row-major; any B >= 1 and D >= 1, else HFL_EINVAL. */
+int hfl_pairwise_dist(float* dist, const float* emb, int batch, int dim, hfl_stream_t stream);
+
+/* d_emb (B,D) f32: d_emb[i] = sum_j (grad_dist[i,j] + grad_dist[j,i]) (emb[i] - emb[j]) / dist[i,j], the gradient of
+ * sum_ij grad_dist[i,j] dist[i,j] for an arbitrary (B,B) grad_dist; terms with dist[i,j] == 0 contribute 0 (torch.cdist's
+ * convention for coincident rows).  dist: what hfl_pairwise_dist wrote for emb.  j ascending in a fixed order, one writer
+ * per element, no atomics.  Any B >= 1 and D >= 1, else HFL_EINVAL. */
+int hfl_pairwise_dist_bwd(float* d_emb, const float* grad_dist, const float* dist, const float* emb, int batch, int dim,
+                          hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
