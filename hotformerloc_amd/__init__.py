@@ -18,5 +18,6 @@ from .params import ModelParams, load_config            # noqa: F401,E402
 from .model_factory import model_factory                 # noqa: F401,E402
 from .octree import Octree, Points, merge_octrees, build_batch_octree   # noqa: F401,E402
 from .optim import FusedAdam                             # noqa: F401,E402
+from .batch_masks import TupleIndex, batch_masks, batch_masks_host     # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -1594,6 +1594,41 @@ def pairwise_dist_bwd(grad_dist: torch.Tensor, dist: torch.Tensor, emb: torch.Te
     return d_emb
 
 
+BATCH_MASKS_LDS_ENTRIES = 4096         # HFL_BATCH_MASKS_LDS_ENTRIES: entries of each list a workgroup stages in LDS
+
+
+def batch_masks(labels: torch.Tensor, pos_off: torch.Tensor, pos_idx: torch.Tensor, nn_off: torch.Tensor, nn_idx: torch.Tensor,
+                n_elems: int, return_counts: bool = False, out=None):
+    """`hfl_batch_masks`: pos[i, j] = labels[j] in positives[labels[i]], neg[i, j] = labels[j] not in non_negatives[labels[i]].
+    labels (B,) int64 on the GPU with every value in [0, n_elems) (the caller checks); the two CSRs as (n_elems + 1,) int64
+    offsets and int32 ids, each id tensor with at least one element of storage.  `out`: a pair of contiguous (B, B) bool or
+    uint8 tensors to write into.  Returns (pos (B, B) bool, neg (B, B) bool, counts (B, 2) int32 or None)."""
+    _dev(labels, pos_off, pos_idx, nn_off, nn_idx)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] < 1 or not labels.is_contiguous():
+        raise TypeError('batch_masks: a contiguous (B,) int64 label tensor with B >= 1 expected')
+    n_elems = int(n_elems)
+    for off, idx in ((pos_off, pos_idx), (nn_off, nn_idx)):
+        if off.dtype != torch.int64 or idx.dtype != torch.int32 or not off.is_contiguous() or not idx.is_contiguous() \
+                or off.dim() != 1 or idx.dim() != 1 or off.shape[0] != n_elems + 1 or idx.shape[0] < 1:
+            raise TypeError('batch_masks: CSR of %d lists as (%d,) int64 offsets and non-empty int32 ids expected'
+                            % (n_elems, n_elems + 1))
+    b = labels.shape[0]
+    if out is None:
+        pos = torch.empty((b, b), dtype=torch.bool, device=labels.device)
+        neg = torch.empty((b, b), dtype=torch.bool, device=labels.device)
+    else:
+        pos, neg = out
+        _dev(pos, neg)
+        for m in (pos, neg):
+            if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (b, b) or not m.is_contiguous():
+                raise TypeError('batch_masks: out is a pair of contiguous (%d, %d) bool or uint8 tensors' % (b, b))
+    counts = torch.empty((b, 2), dtype=torch.int32, device=labels.device) if return_counts else None
+    check(_native.load().hfl_batch_masks(pos.data_ptr(), neg.data_ptr(), counts.data_ptr() if return_counts else None,
+                                         labels.data_ptr(), b, pos_off.data_ptr(), pos_idx.data_ptr(), nn_off.data_ptr(),
+                                         nn_idx.data_ptr(), n_elems, _stream()), 'hfl_batch_masks')
+    return pos, neg, counts
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

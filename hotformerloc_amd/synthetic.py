@@ -184,3 +184,25 @@ def kd_case(seed: int, batch: int, dim: int, scale: float = 1.0):
     t = y + 0.05 * np.sqrt(3.0) * hash_uniform(seed + 1, batch * dim).reshape(batch, dim)
     t /= np.linalg.norm(t, axis=1, keepdims=True)
     return (scale * y).astype(np.float32), (scale * t).astype(np.float32)
+
+
+def tuple_lists(n: int, seed: int, pos_len: int = 30, nn_len: int = 300):
+    """Closed-form `positives` / `non_negatives` lists of a synthetic training set of n elements, as CSR
+    (pos_off, pos_idx, nn_off, nn_idx): element i's non-negatives are about nn_len (0.5x .. 1.5x) ids around i at a stride
+    of 1..3 (cyclic, sorted), its positives the middle ~pos_len of them.  For `batch_masks` tests and probes."""
+    u = 0.5 * (hash_uniform(seed, 3 * n).reshape(3, n) + 1.0)                 # (0, 1)
+    pos, nn = [], []
+    for i in range(n):
+        ln = min(int(nn_len * (0.5 + u[0, i])), n)
+        lp = min(int(pos_len * (0.5 + u[1, i])), ln)
+        stride = 1 + int(3 * u[2, i])
+        if ln * stride > n:
+            stride = 1
+        ids = (i - (ln // 2) * stride + stride * np.arange(ln, dtype=np.int64)) % n
+        nn.append(np.sort(ids))
+        pos.append(np.sort(ids[(ln - lp) // 2:(ln - lp) // 2 + lp]))
+    out = []
+    for lists in (pos, nn):
+        out.append(np.concatenate([[0], np.cumsum([len(a) for a in lists])]).astype(np.int64))
+        out.append(np.concatenate(lists).astype(np.int32))
+    return tuple(out)

@@ -388,3 +388,25 @@ def make_training_minibatches(clouds, split_size: Optional[int], cfg, depth: int
                                      cylindrical=cylindrical, device=device)
         out.append({'octree': build_batch_octree(pts, depth, full_depth, device)})
     return out
+
+
+def make_training_batch(clouds, labels, index, split_size: Optional[int], cfg, depth: int, **kwargs):
+    """The reference collate function's whole triple (`dataset_utils.py:105-139`), ready for `multistaged_training_step`:
+    `(minibatches, positives_mask, negatives_mask)` = `make_training_minibatches(clouds, split_size, cfg, depth, **kwargs)`
+    (every further keyword of that function passes through) and `batch_masks.batch_masks(index, labels)`, one launch over a
+    `TupleIndex` built once per dataset.  `labels`: the element ids of the batch, on either device.
+
+    Under data parallelism each rank passes its LOCAL clouds and the GLOBAL label list: the masks are over the whole
+    batch, in rank order, as `multistaged_training_step` requires.  On a single rank the two lengths must agree:
+    ValueError if `len(labels) != len(clouds)` (with `world_size > 1` the labels of all ranks are expected instead)."""
+    from .batch_masks import batch_masks
+    clouds = list(clouds)
+    n_labels = int(labels.shape[0]) if hasattr(labels, 'shape') and len(labels.shape) == 1 else len(labels)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    if world == 1 and n_labels != len(clouds):
+        raise ValueError('%d labels for %d clouds' % (n_labels, len(clouds)))
+    if world > 1 and n_labels < len(clouds):
+        raise ValueError('%d labels for %d local clouds: pass the labels of the whole batch' % (n_labels, len(clouds)))
+    positives_mask, negatives_mask = batch_masks(index, labels)            # first: bad labels stop the batch early
+    minibatches = make_training_minibatches(clouds, split_size, cfg, depth, **kwargs)
+    return minibatches, positives_mask, negatives_mask

@@ -845,6 +845,24 @@ int hfl_pairwise_dist_bwd(float* d_emb, const float* grad_dist, const float* dis
                           hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11c. The batch's positives / negatives masks (datasets/dataset_utils.py:118-123, the collate function's two nested list
+ *      comprehensions over in_sorted_array, :201-206; the lists are TrainingTuple.positives / .non_negatives,
+ *      datasets/base_datasets.py:11-28)
+ * ---------------------------------------------------------------------- */
+/* Entries of EACH of a row's two lists that the kernel stages in LDS; a longer list is searched in global memory. */
+#define HFL_BATCH_MASKS_LDS_ENTRIES 4096
+/* pos_mask[i][j] = labels[j] in positives[labels[i]], neg_mask[i][j] = labels[j] not in non_negatives[labels[i]], both (B,B)
+ * bytes that are exactly 0 or 1 (they may be the storage of bool tensors); no special case for the diagonal or for repeated
+ * labels.  counts (B,2) int32 or NULL: the row sums of pos_mask and of neg_mask.  labels (B) int64 element ids, may repeat.
+ * The lists of all n_elems elements as CSR: pos_off / nn_off (n_elems + 1) int64 offsets into pos_idx / nn_idx, int32 ids,
+ * every list non-decreasing (repeats allowed).  The CSR is trusted; a row whose label lies outside [0, n_elems) is treated as
+ * having two empty lists and nothing is read out of bounds for it.  One launch on `stream`, no synchronisation.  batch <= 0,
+ * n_elems <= 0 or a NULL pointer other than counts: HFL_EINVAL. */
+int hfl_batch_masks(uint8_t* pos_mask, uint8_t* neg_mask, int32_t* counts, const int64_t* labels, int batch,
+                    const int64_t* pos_off, const int32_t* pos_idx, const int64_t* nn_off, const int32_t* nn_idx, int n_elems,
+                    hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
