@@ -19,5 +19,7 @@ from .model_factory import model_factory                 # noqa: F401,E402
 from .octree import Octree, Points, merge_octrees, build_batch_octree   # noqa: F401,E402
 from .optim import FusedAdam                             # noqa: F401,E402
 from .batch_masks import TupleIndex, batch_masks, batch_masks_host     # noqa: F401,E402
+from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_downsample_host,   # noqa: F401,E402
+                    normalise_submaps_host)
 
 __version__ = '0.1.0'

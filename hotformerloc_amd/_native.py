@@ -7,7 +7,7 @@ this module raises.  Build it with `python -m hotformerloc_amd.build`
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libhotformerloc_hip.so')
@@ -120,6 +120,11 @@ SIGNATURES = {
     'hfl_prepare_clouds': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'hfl_augment_clouds': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    ctypes.POINTER(AugmentConfig), c_uint64, c_int64, c_void_p, c_void_p]),
+    'hfl_voxel_keys': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_double, c_void_p]),
+    'hfl_voxel_reduce_workspace': (c_int64, [c_int64]),
+    'hfl_voxel_reduce': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                 c_int64, c_void_p]),
+    'hfl_submap_normalise': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'hfl_tap_lists_workspace': (c_int64, [c_int64, c_int]),
     'hfl_tap_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'hfl_tap_lists_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

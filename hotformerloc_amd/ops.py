@@ -1629,6 +1629,76 @@ def batch_masks(labels: torch.Tensor, pos_off: torch.Tensor, pos_idx: torch.Tens
     return pos, neg, counts
 
 
+VOXEL_MAX_CLOUDS = 32767               # HFL_VOXEL_MAX_CLOUDS
+VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
+VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
+
+
+def _voxel_check(what: str, points: torch.Tensor, offsets: torch.Tensor):
+    _dev(points, offsets)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise TypeError('%s: contiguous (P, 3) float32 points expected' % what)
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
+        raise TypeError('%s: (B + 1,) int64 cloud offsets with B >= 1 expected' % what)
+    return int(offsets.shape[0]) - 1
+
+
+def voxel_keys(points: torch.Tensor, offsets: torch.Tensor, voxel_size: float):
+    """`hfl_voxel_keys`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU, every cloud non-empty and offsets[B] == P
+    (the caller checks) -> (keys (P,) int64 = cloud << 48 | ix << 32 | iy << 16 | iz, flags (B,) int32: 1 where a cloud
+    spans 65 536 or more cells along an axis)."""
+    batch = _voxel_check('voxel_keys', points, offsets)
+    n = int(points.shape[0])
+    if n < batch:
+        raise ValueError('voxel_keys: %d points for %d non-empty clouds' % (n, batch))
+    keys = torch.empty(n, dtype=torch.int64, device=points.device)
+    flags = torch.empty(batch, dtype=torch.int32, device=points.device)
+    bounds = torch.empty((batch, 6), dtype=torch.int32, device=points.device)
+    check(_native.load().hfl_voxel_keys(keys.data_ptr(), flags.data_ptr(), bounds.data_ptr(), points.data_ptr(),
+                                        offsets.data_ptr(), batch, n, float(voxel_size), _stream()), 'hfl_voxel_keys')
+    return keys, flags
+
+
+def voxel_reduce(sorted_keys: torch.Tensor, perm: torch.Tensor, points: torch.Tensor, batch: int,
+                 return_counts: bool = False, return_keys: bool = False):
+    """`hfl_voxel_reduce`: the ascending keys of `voxel_keys`, the stable sort's permutation and the points -> (out (P, 3)
+    fp32 whose first M rows are the cell means in key order, out_offsets (B + 1,) int64 on the GPU with cloud b at rows
+    [out_offsets[b], out_offsets[b + 1]) and out_offsets[B] = M, cell_counts (P,) int32 or None, out_keys (P,) int64 or
+    None).  Nothing is read back."""
+    _dev(sorted_keys, perm, points)
+    n = int(points.shape[0])
+    for t in (sorted_keys, perm):
+        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise TypeError('voxel_reduce: contiguous (%d,) int64 keys and permutation expected' % n)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise TypeError('voxel_reduce: contiguous (P, 3) float32 points expected')
+    lib = _native.load()
+    nbytes = int(lib.hfl_voxel_reduce_workspace(n))
+    if nbytes <= 0:
+        raise ValueError('voxel_reduce: 1..%d points expected, got %d' % (VOXEL_MAX_POINTS, n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    out = torch.empty_like(points)
+    out_off = torch.empty(int(batch) + 1, dtype=torch.int64, device=points.device)
+    counts = torch.empty(n, dtype=torch.int32, device=points.device) if return_counts else None
+    okeys = torch.empty(n, dtype=torch.int64, device=points.device) if return_keys else None
+    check(lib.hfl_voxel_reduce(out.data_ptr(), out_off.data_ptr(), counts.data_ptr() if return_counts else None,
+                               okeys.data_ptr() if return_keys else None, sorted_keys.data_ptr(), perm.data_ptr(),
+                               points.data_ptr(), n, int(batch), ws.data_ptr(), nbytes, _stream()), 'hfl_voxel_reduce')
+    return out, out_off, counts, okeys
+
+
+def submap_normalise(points: torch.Tensor, offsets: torch.Tensor):
+    """`hfl_submap_normalise`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU (offsets[B] <= P) -> (out (P, 3) with
+    cloud b's kept rows from row offsets[b] on, counts (B,) int32, flags (B,) int32: 1 where the mean radius is not > 0)."""
+    batch = _voxel_check('submap_normalise', points, offsets)
+    out = torch.empty_like(points)
+    counts = torch.empty(batch, dtype=torch.int32, device=points.device)
+    flags = torch.empty(batch, dtype=torch.int32, device=points.device)
+    check(_native.load().hfl_submap_normalise(out.data_ptr(), counts.data_ptr(), flags.data_ptr(), points.data_ptr(),
+                                              offsets.data_ptr(), batch, _stream()), 'hfl_submap_normalise')
+    return out, counts, flags
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

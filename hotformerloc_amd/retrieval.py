@@ -182,19 +182,29 @@ def recall_from_indices(idx, truth_offsets, truth_indices, n_database: int, num_
 
 # ------------------------------------------------------------------------------------------------ whole-dataset evaluation
 def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesian', normalize: bool = True,
-                  octree_depth: int = 7, full_depth: int = 2, device='cuda', **prepare_kwargs):
+                  octree_depth: int = 7, full_depth: int = 2, device='cuda', voxel_size=None,
+                  normalise_submaps: bool = False, **prepare_kwargs):
     """`get_latent_vectors` (`eval/pnv_evaluate.py:129-187`) without the file loading: raw (n, 3) clouds (a sequence or any
     iterable) -> (len, output_dim) fp32 descriptors on the GPU, `batch_size` clouds per forward (the last batch may be
-    short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`."""
+    short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`.  With `voxel_size` and / or
+    `normalise_submaps` the clouds are raw submaps in a metric frame: every batch first goes through the CS-Wild-Places
+    submap post-processing on the device (`voxel.prepare_submaps`: voxel-grid downsample at `voxel_size`, then the
+    PointNetVLAD normalisation); with the defaults nothing changes."""
     from .octree import build_batch_octree
     from .preprocess import prepare_clouds
+    from . import voxel
     if batch_size < 1:
         raise ValueError('encode_clouds: batch_size >= 1 expected, got %d' % batch_size)
     model.eval()
     out, batch = [], []
 
     def flush():
-        pts = prepare_clouds(batch, coordinates=coordinates, normalize=normalize, device=device, **prepare_kwargs)
+        src = batch
+        if voxel_size is not None:
+            src = voxel.prepare_submaps(batch, voxel_size, normalise=normalise_submaps, device=device)
+        elif normalise_submaps:
+            src = voxel.normalise_submaps(batch, device=device)
+        pts = prepare_clouds(src, coordinates=coordinates, normalize=normalize, device=device, **prepare_kwargs)
         octree = build_batch_octree(pts, octree_depth, full_depth, device)
         out.append(model({'octree': octree})['global'].float())
         batch.clear()

@@ -206,3 +206,11 @@ def tuple_lists(n: int, seed: int, pos_len: int = 30, nn_len: int = 300):
         out.append(np.concatenate([[0], np.cumsum([len(a) for a in lists])]).astype(np.int64))
         out.append(np.concatenate(lists).astype(np.int32))
     return tuple(out)
+
+
+def raw_submap(seed: int, n: int, extent: float = 100.0, offset=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """A raw lidar-like submap in a metric frame, (n, 3) float32: the 'forest' cloud (a thin ground slab and 40 trunks)
+    stretched to an `extent`-metre box and moved by `offset` (a UTM-like offset makes the fp32 spacing centimetres to
+    decimetres).  The sum is formed in float64 and rounded once.  For the `voxel` tests and probe."""
+    p = forest_cloud(seed, n).astype(np.float64) * (0.5 * extent)
+    return (p + np.asarray(offset, dtype=np.float64)).astype(np.float32)

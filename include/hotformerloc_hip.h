@@ -214,6 +214,48 @@ int hfl_augment_clouds(float* out_points, int32_t* out_counts, int32_t* out_inde
                        const uint32_t* selection_keys, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 2b. Raw submaps: voxel-grid downsampling and the PointNetVLAD normalisation (csrc/voxel.hip; replaces
+ *     datasets/CSWildPlaces/postprocess_submaps.py's processing_utils.voxel_down_sample -- open3d's
+ *     PointCloud.voxel_down_sample -- and processing_utils.normalise_pcl with downsample_number=None)
+ * ---------------------------------------------------------------------- */
+#define HFL_VOXEL_MAX_CLOUDS 32767        /* the cloud id has 15 bits of a positive int64 key          */
+#define HFL_VOXEL_MAX_CELLS 65535         /* cells a cloud may span along an axis (16 bits, see below) */
+#define HFL_VOXEL_MAX_POINTS 2147483646LL /* points of a batch: sorted positions are kept as int32     */
+/* keys[i] = cloud << 48 | ix << 32 | iy << 16 | iz for every point of points (P,3), cloud b at rows
+ * [cloud_offsets[b], cloud_offsets[b+1]), every cloud non-empty and cloud_offsets[batch] == n_points.  Per cloud
+ * origin = double(min p) - 0.5 v and cell = floor((double(p) - origin) / v) per axis, a float64 subtract and divide as open3d
+ * computes them, so membership is bit-identical to a float64 restatement, points on a cell face included.  bounds
+ * (batch, 6) uint32 is workspace (ordered-integer images of the per-cloud minimum and maximum, found with integer atomics
+ * by as many workgroups as the cloud needs).  flags[b] = 1 when cloud b spans HFL_VOXEL_MAX_CELLS + 1 = 65 536 or more
+ * cells along an axis: its keys are then clamped, still carry its own cloud id, and its output must be discarded.
+ * points and keys 16-byte aligned.  A memset and two launches on `stream`, no synchronisation.  Non-finite coordinates:
+ * undefined values, nothing out of bounds.  voxel_size <= 0 or not finite, batch < 1, n_points < batch or a NULL pointer:
+ * HFL_EINVAL; more than HFL_VOXEL_MAX_CLOUDS clouds or HFL_VOXEL_MAX_POINTS points: HFL_ECAPACITY. */
+int hfl_voxel_keys(int64_t* keys, int32_t* flags, uint32_t* bounds, const float* points, const int64_t* cloud_offsets,
+                   int batch, int64_t n_points, double voxel_size, hfl_stream_t stream);
+/* bytes of workspace hfl_voxel_reduce needs for n_points points (0 for n_points outside 1..HFL_VOXEL_MAX_POINTS) */
+int64_t hfl_voxel_reduce_workspace(int64_t n_points);
+/* sorted_keys = the keys of hfl_voxel_keys in ascending order, perm[j] = the row of `points` that sorted position j came from
+ * (a stable sort: members of a cell stay in input order).  One output row per distinct key, in key order, i.e. per cloud
+ * in ascending (ix, iy, iz): the mean of the cell's points, summed in float64 in a fixed order, divided by the count and
+ * rounded once to fp32.  out_points (P,3) receives M <= P rows; out_offsets (batch + 1) int64: cloud b's rows are
+ * [out_offsets[b], out_offsets[b+1]), so its output count is their difference and out_offsets[batch] = M;
+ * out_cell_counts (P, may be NULL): members per output row; out_keys (P, may be NULL): the row's key.  No floating-point
+ * atomics: the same input gives the same bits, and a cloud gives the same bits alone or in a batch.  Four launches on
+ * `stream`, no synchronisation.  perm is trusted (values in [0, n_points)).  out_points must not alias points;
+ * workspace 16-byte aligned, workspace_bytes >= hfl_voxel_reduce_workspace(n_points), else HFL_EINVAL. */
+int hfl_voxel_reduce(float* out_points, int64_t* out_offsets, int32_t* out_cell_counts, int64_t* out_keys,
+                     const int64_t* sorted_keys, const int64_t* perm, const float* points, int64_t n_points, int batch,
+                     void* workspace, int64_t workspace_bytes, hfl_stream_t stream);
+/* normalise_pcl without padding, in float64 per cloud: c = mean q, d = mean |q - c|, s = 0.5 / d, q' = s (q - c); the rows
+ * with every |q'| <= 1 are written in order, rounded once to fp32, from row cloud_offsets[b] of out_points (P,3) on and
+ * out_counts[b] says how many.  flags[b] = 1 when d is not > 0 (a single point, coincident points) or the cloud is empty:
+ * its output is then meaningless.  cloud_offsets (batch + 1) int64 may be hfl_voxel_reduce's out_offsets.  One workgroup
+ * per cloud, fixed-order float64 reductions (no atomics), one launch on `stream`.  out_points must not alias points. */
+int hfl_submap_normalise(float* out_points, int32_t* out_counts, int32_t* flags, const float* points,
+                         const int64_t* cloud_offsets, int batch, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 3. Octree convolution gather  (ocnn.nn.OctreeConv's octree2col; call sites
  *    models/layers/octformer_layers.py:89-95, models/octformer_backbone.py:470-475)
  * ---------------------------------------------------------------------- */
