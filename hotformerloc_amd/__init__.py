@@ -21,5 +21,7 @@ from .optim import FusedAdam                             # noqa: F401,E402
 from .batch_masks import TupleIndex, batch_masks, batch_masks_host     # noqa: F401,E402
 from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_downsample_host,   # noqa: F401,E402
                     normalise_submaps_host)
+from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
+                     tuple_index_from_poses, truth_from_poses)
 
 __version__ = '0.1.0'

@@ -209,6 +209,8 @@ SIGNATURES = {
     'hfl_pairwise_dist_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'hfl_batch_masks': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p]),
+    'hfl_radius_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_double,
+                                 c_double, c_int, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -1629,7 +1629,54 @@ def batch_masks(labels: torch.Tensor, pos_off: torch.Tensor, pos_idx: torch.Tens
     return pos, neg, counts
 
 
-VOXEL_MAX_CLOUDS = 32767               # HFL_VOXEL_MAX_CLOUDS
+RADIUS_ROWS = 8                        # HFL_RADIUS_ROWS: query rows (one wave each) of a workgroup
+RADIUS_TILE = 2048                     # HFL_RADIUS_TILE: database positions of the LDS tile those rows share
+
+
+def _radius_check(queries: torch.Tensor, database: torch.Tensor):
+    _dev(queries, database)
+    for x in (queries, database):
+        if x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != 2 or x.shape[0] < 1 or not x.is_contiguous():
+            raise TypeError('radius_lists: contiguous (rows >= 1, 2) float64 positions expected')
+    if database.shape[0] >= 2 ** 31:
+        raise ValueError('radius_lists: %d database positions, ids must fit int32' % database.shape[0])
+
+
+def radius_counts(queries: torch.Tensor, database: torch.Tensor, r_a: float, r_b: float, exclude_self: bool = False):
+    """The count pass of `hfl_radius_lists`: (Q, 2) int32, per query the number of database positions with
+    dx*dx + dy*dy <= r_a*r_a and <= r_b*r_b in float64 (`exclude_self`: without j == i in the first column)."""
+    _radius_check(queries, database)
+    counts = torch.empty((queries.shape[0], 2), dtype=torch.int32, device=queries.device)
+    check(_native.load().hfl_radius_lists(counts.data_ptr(), None, None, None, None, queries.data_ptr(), queries.shape[0],
+                                          database.data_ptr(), database.shape[0], float(r_a), float(r_b), int(exclude_self),
+                                          _stream()), 'hfl_radius_lists (count)')
+    return counts
+
+
+def radius_lists(queries: torch.Tensor, database: torch.Tensor, r_a: float, r_b: float, exclude_self: bool = False,
+                 want_b: bool = True):
+    """Both passes of `hfl_radius_lists` around one `torch.cumsum`: (off_a, idx_a, off_b, idx_b), (Q + 1,) int64 offsets and
+    int32 ids ascending within every list (`want_b=False`: the second family is None, None and is not written).  A family
+    without any entry keeps one element of storage (a (1,) id tensor holding 0, as `TupleIndex` pads its own): kernels take
+    no null pointer; `off[-1]` is the number of entries.  One device-to-host read (the totals) between the passes."""
+    counts = radius_counts(queries, database, r_a, r_b, exclude_self)
+    n_q = queries.shape[0]
+    off = torch.zeros((2, n_q + 1), dtype=torch.int64, device=queries.device)
+    off[:, 1:] = torch.cumsum(counts.t(), dim=1)
+    total_a, total_b = (int(v) for v in off[:, -1].tolist())
+    ids = lambda total: (torch.empty(total, dtype=torch.int32, device=queries.device) if total      # noqa: E731
+                         else torch.zeros(1, dtype=torch.int32, device=queries.device))
+    idx_a, idx_b = ids(total_a), ids(total_b) if want_b else None
+    off_a, off_b = off[0], off[1]
+    if total_a > 0 or (want_b and total_b > 0):
+        check(_native.load().hfl_radius_lists(None, idx_a.data_ptr(), idx_b.data_ptr() if want_b else None, off_a.data_ptr(),
+                                              off_b.data_ptr() if want_b else None, queries.data_ptr(), n_q,
+                                              database.data_ptr(), database.shape[0], float(r_a), float(r_b),
+                                              int(exclude_self), _stream()), 'hfl_radius_lists (fill)')
+    return (off_a, idx_a, off_b, idx_b) if want_b else (off_a, idx_a, None, None)
+
+
+VOXEL_MAX_CLOUDS = 32767              # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
 

@@ -905,6 +905,27 @@ int hfl_batch_masks(uint8_t* pos_mask, uint8_t* neg_mask, int32_t* counts, const
                     hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11d. Tuple lists / evaluation truth from poses: a fixed-radius join of 2-D positions in float64 (the KDTree.query_radius
+ *      calls and the per-anchor np.setdiff1d / np.sort loop of datasets/{pointnetvlad,WildPlaces}/generate_training_tuples*.py,
+ *      generate_test_sets.py and datasets/CSWildPlaces/generate_train_test_tuples.py:92-212)
+ * ---------------------------------------------------------------------- */
+/* Query rows (one wave each) of a workgroup, and database positions of the LDS tile they share (16 B each). */
+#define HFL_RADIUS_ROWS 8
+#define HFL_RADIUS_TILE 2048
+/* Two CSR list families over queries (Q,2) and database (N,2), float64 row-major: list A of query i holds the ids j with
+ * dx*dx + dy*dy <= r_a*r_a, list B the same at r_b, every operation rounded to float64 (no FMA); a NaN coordinate is in no
+ * list.  exclude_self != 0 drops j == i from list A only (for queries == database).  Every list is strictly ascending in j.
+ * Count pass (ids_a == NULL and ids_b == NULL): counts (Q,2) int32 = the lengths of A and B.  Fill pass (either ids pointer
+ * set): each non-NULL ids_x receives the int32 ids of list x of query i from off_x[i] on, off_x (Q+1) int64 being the
+ * exclusive prefix sum of that family's counts; an id that would land at or past off_x[i+1] is dropped, so nothing is
+ * written outside [off_x[0], off_x[Q]).  No atomics: two runs give the same bits.  One launch on `stream`, no
+ * synchronisation.  Q < 1, N < 1, N >= 2^31, a radius that is negative or NaN, r_a > r_b, NULL positions, NULL counts in the
+ * count pass or ids_x without off_x in the fill pass: HFL_EINVAL. */
+int hfl_radius_lists(int32_t* counts, int32_t* ids_a, int32_t* ids_b, const int64_t* off_a, const int64_t* off_b,
+                     const double* queries, int64_t n_queries, const double* database, int64_t n_database, double r_a,
+                     double r_b, int exclude_self, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
