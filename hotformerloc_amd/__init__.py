@@ -20,7 +20,9 @@ from .octree import Octree, Points, merge_octrees, build_batch_octree   # noqa: 
 from .optim import FusedAdam                             # noqa: F401,E402
 from .batch_masks import TupleIndex, batch_masks, batch_masks_host     # noqa: F401,E402
 from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_downsample_host,   # noqa: F401,E402
-                    normalise_submaps_host)
+                    normalise_submaps_host, voxel_occupancy, voxel_occupancy_host, pnvlad_downsample,
+                    pnvlad_downsample_host, random_downsample, random_downsample_host, normalise_submaps_padded,
+                    normalise_submaps_padded_host, prepare_submaps_fixed)
 from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
                      tuple_index_from_poses, truth_from_poses)
 

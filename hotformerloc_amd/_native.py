@@ -125,6 +125,12 @@ SIGNATURES = {
     'hfl_voxel_reduce': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                  c_int64, c_void_p]),
     'hfl_submap_normalise': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'hfl_submap_normalise_rows': (c_int, [c_void_p] * 8 + [c_int, c_void_p]),
+    'hfl_voxel_gather_rows': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'hfl_voxel_bounds': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    'hfl_voxel_occupancy_workspace': (c_int64, [c_int, c_int64]),
+    'hfl_voxel_occupancy': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64,
+                                    c_void_p, c_int64, c_void_p]),
     'hfl_tap_lists_workspace': (c_int64, [c_int64, c_int]),
     'hfl_tap_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'hfl_tap_lists_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

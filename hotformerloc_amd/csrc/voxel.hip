@@ -330,22 +330,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return r;
 }
 
-__global__ void __launch_bounds__(kPrepThreads)
-submap_normalise_kernel(float* __restrict__ out, int32_t* __restrict__ counts, int32_t* __restrict__ flags,
-                        const float* __restrict__ pts, const int64_t* __restrict__ off) {
-  __shared__ double red[kPrepThreads / 64];
-  __shared__ int wave_cnt[kPrepThreads / 64];
-  __shared__ int running;
-  const int b = blockIdx.x;
-  const int64_t p0 = off[b];
-  const int64_t n = off[b + 1] - p0;
-  const float* p = pts + p0 * 3;
-  float* o = out + p0 * 3;
-  if (n < 1) {                                               // uniform over the workgroup
-    if (threadIdx.x == 0) { counts[b] = 0; flags[b] = 1; }
-    return;
-  }
-  double c[3];
+// centroid c and scale s = 0.5 / d (d = mean |q - c|) of the n >= 1 points at p, float64 in a fixed order, in every lane;
+// true when d is not > 0 (a single point, coincident points or a non-finite input), and then s = 0
+__device__ __forceinline__ bool submap_stats(const float* __restrict__ p, int64_t n, double* red, double (&c)[3], double& scale) {
   {
     double s[3] = {0.0, 0.0, 0.0};
     for (int64_t i = threadIdx.x; i < n; i += kPrepThreads) {
@@ -362,7 +349,36 @@ submap_normalise_kernel(float* __restrict__ out, int32_t* __restrict__ counts, i
   }
   const double d = __ddiv_rn(block_sum(rs, red), (double)n);
   const bool degenerate = !(d > 0.0);                        // a single point, coincident points or a non-finite input
-  const double scale = degenerate ? 0.0 : __ddiv_rn(0.5, d);
+  scale = degenerate ? 0.0 : __ddiv_rn(0.5, d);
+  return degenerate;
+}
+
+// q' = s (q - c) of one row in float64; true when every |q'| <= 1
+__device__ __forceinline__ bool submap_scaled_row(const float* __restrict__ q, const double (&c)[3], double scale, double& x,
+                                                  double& y, double& z) {
+  x = __dmul_rn(scale, (double)q[0] - c[0]);
+  y = __dmul_rn(scale, (double)q[1] - c[1]);
+  z = __dmul_rn(scale, (double)q[2] - c[2]);
+  return fabs(x) <= 1.0 && fabs(y) <= 1.0 && fabs(z) <= 1.0;
+}
+
+__global__ void __launch_bounds__(kPrepThreads)
+submap_normalise_kernel(float* __restrict__ out, int32_t* __restrict__ counts, int32_t* __restrict__ flags,
+                        const float* __restrict__ pts, const int64_t* __restrict__ off) {
+  __shared__ double red[kPrepThreads / 64];
+  __shared__ int wave_cnt[kPrepThreads / 64];
+  __shared__ int running;
+  const int b = blockIdx.x;
+  const int64_t p0 = off[b];
+  const int64_t n = off[b + 1] - p0;
+  const float* p = pts + p0 * 3;
+  float* o = out + p0 * 3;
+  if (n < 1) {                                               // uniform over the workgroup
+    if (threadIdx.x == 0) { counts[b] = 0; flags[b] = 1; }
+    return;
+  }
+  double c[3], scale;
+  const bool degenerate = submap_stats(p, n, red, c, scale);
   if (threadIdx.x == 0) running = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -371,12 +387,7 @@ submap_normalise_kernel(float* __restrict__ out, int32_t* __restrict__ counts, i
     const int64_t i = base + threadIdx.x;
     double x = 0.0, y = 0.0, z = 0.0;
     bool keep = false;
-    if (i < n) {
-      x = __dmul_rn(scale, (double)p[i * 3 + 0] - c[0]);
-      y = __dmul_rn(scale, (double)p[i * 3 + 1] - c[1]);
-      z = __dmul_rn(scale, (double)p[i * 3 + 2] - c[2]);
-      keep = fabs(x) <= 1.0 && fabs(y) <= 1.0 && fabs(z) <= 1.0;
-    }
+    if (i < n) keep = submap_scaled_row(p + i * 3, c, scale, x, y, z);
     const unsigned long long m = __ballot(keep);
     if (lane == 0) wave_cnt[wave] = __popcll(m);
     __syncthreads();
@@ -399,6 +410,143 @@ submap_normalise_kernel(float* __restrict__ out, int32_t* __restrict__ counts, i
   if (threadIdx.x == 0) {
     counts[b] = running;
     flags[b] = degenerate ? 1 : 0;
+  }
+}
+
+// the same c, s and transform for rows drawn from another cloud (the padding loop of normalise_pcl): row j of cloud b,
+// j in [row_off[b], row_off[b + 1]), is raw row raw_off[b] + row_index[j]; an index outside the raw cloud, or a cloud
+// that cannot be normalised, gives a zero row with keep = 0
+__global__ void __launch_bounds__(kPrepThreads)
+submap_normalise_rows_kernel(float* __restrict__ out_rows, int32_t* __restrict__ keep, const float* __restrict__ pts,
+                             const int64_t* __restrict__ off, const float* __restrict__ raw,
+                             const int64_t* __restrict__ raw_off, const int64_t* __restrict__ row_index,
+                             const int64_t* __restrict__ row_off) {
+  __shared__ double red[kPrepThreads / 64];
+  const int b = blockIdx.x;
+  const int64_t p0 = off[b];
+  const int64_t n = off[b + 1] - p0;
+  const int64_t j0 = row_off[b], j1 = row_off[b + 1];
+  const int64_t r0 = raw_off[b];
+  const int64_t n_raw = raw_off[b + 1] - r0;
+  double c[3] = {0.0, 0.0, 0.0}, scale = 0.0;
+  bool degenerate = true;
+  if (n >= 1) degenerate = submap_stats(pts + p0 * 3, n, red, c, scale);      // uniform over the workgroup
+  for (int64_t j = j0 + threadIdx.x; j < j1; j += kPrepThreads) {
+    const int64_t idx = row_index[j];
+    double x = 0.0, y = 0.0, z = 0.0;
+    bool ok = false;
+    if (!degenerate && idx >= 0 && idx < n_raw) ok = submap_scaled_row(raw + (r0 + idx) * 3, c, scale, x, y, z);
+    else x = y = z = 0.0;
+    out_rows[j * 3 + 0] = (float)x;
+    out_rows[j * 3 + 1] = (float)y;
+    out_rows[j * 3 + 2] = (float)z;
+    keep[j] = ok ? 1 : 0;
+  }
+}
+
+// out[r] = points[index[r]]; an index outside [0, n_points) gives a zero row
+__global__ void __launch_bounds__(kVoxThreads)
+voxel_gather_rows_kernel(float* __restrict__ out, const float* __restrict__ pts, int64_t n_points,
+                         const int64_t* __restrict__ index, int64_t n_rows) {
+  const int64_t r = (int64_t)blockIdx.x * kVoxThreads + threadIdx.x;
+  if (r >= n_rows) return;
+  const int64_t i = index[r];
+  const bool ok = i >= 0 && i < n_points;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[r * 3 + a] = ok ? pts[i * 3 + a] : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------ occupancy
+// How many cells does cloud c occupy at voxel size v, for many (c, v) candidates in one launch: every candidate owns a
+// bitmap of nx ny nz bits (cell (ix, iy, iz) is bit (ix ny + iy) nz + iz) in a zeroed workspace.  gridDim.x workgroups per
+// candidate stream the cloud's points with a stride; bits are set with integer OR atomics, so the bitmap -- and the count
+// -- is the same whatever the arrival order, and no workgroup waits for another.
+//
+// A bitmap of up to kOccLdsWords words is built in LDS first and only its non-zero words are merged into the global one
+// (one global atomic per touched word and workgroup, not per point).  32 KiB: five workgroups of four waves share a CU's
+// 160 KiB, i.e. 20 of its 32 wave slots, which is what the float64 divides of this kernel can use; 262 144 cells covers
+// every candidate of the PointNetVLAD search on a 100 m submap down to v = 1 m.  A larger bitmap is set in global memory,
+// testing the word first: most points fall into a cell that is already marked.
+constexpr int kOccLdsWords = 8192;
+constexpr int kOccPointsPerGroup = 8192;        // the least a workgroup should stream to pay for zeroing and merging
+constexpr int kOccMaxGroups = 64;               // per candidate
+
+__global__ void __launch_bounds__(kVoxThreads)
+voxel_occupancy_kernel(uint32_t* __restrict__ bitmaps, const hfl_voxel_candidate* __restrict__ cand,
+                       const uint32_t* __restrict__ bounds, const float* __restrict__ pts, const int64_t* __restrict__ off,
+                       int64_t n) {
+  __shared__ uint32_t lds[kOccLdsWords];
+  const hfl_voxel_candidate cd = cand[blockIdx.y];
+  const int c = cd.cloud;
+  const int64_t p0 = max(off[c], (int64_t)0), p1 = min(off[c + 1], n);
+  // the quads of the whole array that overlap the cloud: a quad starts 16-byte aligned only in the array's numbering
+  const int64_t q0 = p0 / kVoxQuad, q1 = (p1 + kVoxQuad - 1) / kVoxQuad;
+  const int64_t first = q0 + (int64_t)blockIdx.x * kVoxThreads;
+  if (first >= q1) return;                                   // uniform: the cloud is too short to need this workgroup
+  const int64_t stride = (int64_t)gridDim.x * kVoxThreads;
+  const int64_t nx = cd.nx, ny = cd.ny, nz = cd.nz;
+  const int64_t n_words = (nx * ny * nz + 31) >> 5;
+  const bool in_lds = n_words <= kOccLdsWords;               // uniform
+  uint32_t* g = bitmaps + cd.word_offset;
+  if (in_lds) {
+    for (int w = threadIdx.x; w < (int)n_words; w += kVoxThreads) lds[w] = 0u;
+    __syncthreads();
+  }
+  const double voxel = cd.voxel;
+  const double gx = grid_origin(bounds, c, 0, voxel), gy = grid_origin(bounds, c, 1, voxel),
+               gz = grid_origin(bounds, c, 2, voxel);
+  const volatile uint32_t* lds_seen = lds;
+  const volatile uint32_t* g_seen = g;
+  for (int64_t q = first + threadIdx.x; q < q1; q += stride) {
+    float v[12];
+    const int64_t i0 = q * kVoxQuad;
+    const int cnt = load_quad(pts, i0, n, v);
+#pragma unroll
+    for (int k = 0; k < kVoxQuad; ++k) {
+      const int64_t i = i0 + k;
+      if (k >= cnt || i < p0 || i >= p1) continue;
+      bool ox, oy, oz;
+      const int64_t ix = cell_of(v[3 * k + 0], gx, voxel, ox);
+      const int64_t iy = cell_of(v[3 * k + 1], gy, voxel, oy);
+      const int64_t iz = cell_of(v[3 * k + 2], gz, voxel, oz);
+      if (ix >= nx || iy >= ny || iz >= nz) continue;        // never for a table built from the same bounds; no write
+      const int64_t bit = (ix * ny + iy) * nz + iz;          // outside the bitmap whatever the table says
+      const int64_t w = bit >> 5;
+      const uint32_t m = 1u << (bit & 31);
+      if (in_lds) {
+        if (!(lds_seen[w] & m)) atomicOr(lds + w, m);
+      } else {
+        if (!(g_seen[w] & m)) atomicOr(g + w, m);
+      }
+    }
+  }
+  if (in_lds) {
+    __syncthreads();
+    for (int w = threadIdx.x; w < (int)n_words; w += kVoxThreads) {
+      const uint32_t m = lds[w];
+      if (m != 0u) atomicOr(g + w, m);
+    }
+  }
+}
+
+// counts[candidate] = set bits of its bitmap; one workgroup per candidate, integer sums
+__global__ void __launch_bounds__(kVoxThreads)
+voxel_popcount_kernel(int32_t* __restrict__ counts, const uint32_t* __restrict__ bitmaps,
+                      const hfl_voxel_candidate* __restrict__ cand) {
+  __shared__ int wave_cnt[kVoxThreads / 64];
+  const hfl_voxel_candidate cd = cand[blockIdx.x];
+  const int64_t n_words = ((int64_t)cd.nx * cd.ny * cd.nz + 31) >> 5;
+  const uint32_t* g = bitmaps + cd.word_offset;
+  int t = 0;
+  for (int64_t w = threadIdx.x; w < n_words; w += kVoxThreads) t += __popc(g[w]);
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m, 64);
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+    for (int w = 0; w < kVoxThreads / 64; ++w) total += wave_cnt[w];
+    counts[blockIdx.x] = total;
   }
 }
 
@@ -459,5 +607,87 @@ extern "C" int hfl_submap_normalise(float* out_points, int32_t* out_counts, int3
   if (batch == 0) return HFL_OK;
   submap_normalise_kernel<<<batch, kPrepThreads, 0, static_cast<hipStream_t>(stream)>>>(out_points, out_counts, flags, points,
                                                                                        cloud_offsets);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_submap_normalise_rows(float* out_rows, int32_t* keep, const float* points, const int64_t* cloud_offsets,
+                                         const float* raw_points, const int64_t* raw_offsets, const int64_t* row_index,
+                                         const int64_t* row_offsets, int batch, hfl_stream_t stream) {
+  if (batch < 0 || out_rows == nullptr || keep == nullptr || points == nullptr || cloud_offsets == nullptr ||
+      raw_points == nullptr || raw_offsets == nullptr || row_index == nullptr || row_offsets == nullptr)
+    return HFL_EINVAL;
+  if (batch == 0) return HFL_OK;
+  submap_normalise_rows_kernel<<<batch, kPrepThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      out_rows, keep, points, cloud_offsets, raw_points, raw_offsets, row_index, row_offsets);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_voxel_gather_rows(float* out_points, const float* points, int64_t n_points, const int64_t* index,
+                                     int64_t n_rows, hfl_stream_t stream) {
+  if (n_rows < 0 || n_points < 0 || out_points == nullptr || points == nullptr || index == nullptr || out_points == points)
+    return HFL_EINVAL;
+  if (n_rows > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  if (n_rows == 0) return HFL_OK;
+  voxel_gather_rows_kernel<<<(unsigned)hfl_cdiv(n_rows, kVoxThreads), kVoxThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      out_points, points, n_points, index, n_rows);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_voxel_bounds(uint32_t* bounds, const float* points, const int64_t* cloud_offsets, int batch,
+                                int64_t n_points, hfl_stream_t stream) {
+  if (bounds == nullptr || points == nullptr || cloud_offsets == nullptr) return HFL_EINVAL;
+  if (batch < 1 || n_points < batch) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  if (reinterpret_cast<uintptr_t>(points) & 15) return HFL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(bounds, 0, sizeof(uint32_t) * 6 * (size_t)batch, s);
+  if (e != hipSuccess) return (int)e;
+  const unsigned blocks = (unsigned)hfl_cdiv(n_points, (int64_t)kVoxThreads * kVoxQuad);
+  voxel_bounds_kernel<<<blocks, kVoxThreads, 0, s>>>(bounds, points, cloud_offsets, batch, n_points);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int64_t hfl_voxel_occupancy_workspace(int n_candidates, int64_t bitmap_words) {
+  if (n_candidates < 1 || n_candidates > HFL_VOXEL_OCC_MAX_CANDIDATES || bitmap_words < 1 ||
+      bitmap_words > HFL_VOXEL_OCC_MAX_WORDS)
+    return 0;
+  return align16((int64_t)sizeof(hfl_voxel_candidate) * n_candidates) + align16(4 * bitmap_words);
+}
+
+extern "C" int hfl_voxel_occupancy(int32_t* counts, const hfl_voxel_candidate* candidates, int n_candidates,
+                                   int64_t bitmap_words, const uint32_t* bounds, const float* points,
+                                   const int64_t* cloud_offsets, int batch, int64_t n_points, int64_t max_cloud_points,
+                                   void* workspace, int64_t workspace_bytes, hfl_stream_t stream) {
+  if (counts == nullptr || candidates == nullptr || bounds == nullptr || points == nullptr || cloud_offsets == nullptr ||
+      workspace == nullptr)
+    return HFL_EINVAL;
+  if (batch < 1 || n_points < batch || max_cloud_points < 1) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  if (n_candidates < 1 || bitmap_words < 1) return HFL_EINVAL;
+  if (n_candidates > HFL_VOXEL_OCC_MAX_CANDIDATES || bitmap_words > HFL_VOXEL_OCC_MAX_WORDS) return HFL_ECAPACITY;
+  if ((reinterpret_cast<uintptr_t>(points) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
+      workspace_bytes < hfl_voxel_occupancy_workspace(n_candidates, bitmap_words))
+    return HFL_EINVAL;
+  for (int k = 0; k < n_candidates; ++k) {                   // every bitmap inside the workspace, before anything runs
+    const hfl_voxel_candidate& cd = candidates[k];
+    if (cd.cloud < 0 || cd.cloud >= batch || !(cd.voxel > 0.0) || !(cd.voxel <= 1.7976931348623157e308)) return HFL_EINVAL;
+    if (cd.nx < 1 || cd.ny < 1 || cd.nz < 1 || cd.nx > HFL_VOXEL_MAX_CELLS || cd.ny > HFL_VOXEL_MAX_CELLS ||
+        cd.nz > HFL_VOXEL_MAX_CELLS)
+      return HFL_EINVAL;
+    const int64_t words = ((int64_t)cd.nx * cd.ny * cd.nz + 31) >> 5;     // < 2^43: no overflow
+    if (cd.word_offset < 0 || cd.word_offset > bitmap_words || words > bitmap_words - cd.word_offset) return HFL_EINVAL;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t table_bytes = (int64_t)sizeof(hfl_voxel_candidate) * n_candidates;
+  hfl_voxel_candidate* table = static_cast<hfl_voxel_candidate*>(workspace);
+  uint32_t* bitmaps = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + align16(table_bytes));
+  hipError_t e = hipMemcpyAsync(table, candidates, (size_t)table_bytes, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemsetAsync(bitmaps, 0, sizeof(uint32_t) * (size_t)bitmap_words, s);
+  if (e != hipSuccess) return (int)e;
+  const int64_t groups = hfl_cdiv(max_cloud_points, kOccPointsPerGroup);
+  const dim3 grid((unsigned)(groups < kOccMaxGroups ? groups : kOccMaxGroups), (unsigned)n_candidates);
+  voxel_occupancy_kernel<<<grid, kVoxThreads, 0, s>>>(bitmaps, table, bounds, points, cloud_offsets, n_points);
+  voxel_popcount_kernel<<<n_candidates, kVoxThreads, 0, s>>>(counts, bitmaps, table);
   HFL_RETURN_LAST_ERROR();
 }

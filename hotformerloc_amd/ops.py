@@ -1746,6 +1746,94 @@ def submap_normalise(points: torch.Tensor, offsets: torch.Tensor):
     return out, counts, flags
 
 
+def submap_normalise_rows(points: torch.Tensor, offsets: torch.Tensor, raw: torch.Tensor, raw_offsets: torch.Tensor,
+                          row_index: torch.Tensor, row_offsets: torch.Tensor):
+    """`hfl_submap_normalise_rows`: the centroid and scale of cloud b of `points` / `offsets` (as `submap_normalise` computes
+    them) applied to raw rows raw_offsets[b] + row_index[j], j in [row_offsets[b], row_offsets[b + 1]) -> (rows (R, 3) fp32,
+    keep (R,) int32: 1 where every |q'| <= 1).  All tensors on the GPU; the index and offset tensors int64."""
+    batch = _voxel_check('submap_normalise_rows', points, offsets)
+    if _voxel_check('submap_normalise_rows', raw, raw_offsets) != batch:
+        raise ValueError('submap_normalise_rows: the raw batch and the downsampled batch differ in size')
+    _dev(row_index, row_offsets)
+    for t, shape in ((row_index, None), (row_offsets, (batch + 1,))):
+        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or (shape and tuple(t.shape) != shape):
+            raise TypeError('submap_normalise_rows: contiguous int64 row_index (R,) and row_offsets (B + 1,) expected')
+    rows = int(row_index.shape[0])
+    out = torch.empty((rows, 3), dtype=torch.float32, device=points.device)
+    keep = torch.empty(rows, dtype=torch.int32, device=points.device)
+    if rows:
+        check(_native.load().hfl_submap_normalise_rows(out.data_ptr(), keep.data_ptr(), points.data_ptr(), offsets.data_ptr(),
+                                                       raw.data_ptr(), raw_offsets.data_ptr(), row_index.data_ptr(),
+                                                       row_offsets.data_ptr(), batch, _stream()), 'hfl_submap_normalise_rows')
+    return out, keep
+
+
+def voxel_gather_rows(points: torch.Tensor, index: torch.Tensor):
+    """`hfl_voxel_gather_rows`: points (P, 3) fp32 and index (R,) int64 on the GPU -> points[index] (R, 3); an index outside
+    [0, P) gives a zero row."""
+    _dev(points, index)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise TypeError('voxel_gather_rows: contiguous (P, 3) float32 points expected')
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+        raise TypeError('voxel_gather_rows: contiguous (R,) int64 index expected')
+    out = torch.empty((int(index.shape[0]), 3), dtype=torch.float32, device=points.device)
+    if index.shape[0]:
+        check(_native.load().hfl_voxel_gather_rows(out.data_ptr(), points.data_ptr(), int(points.shape[0]), index.data_ptr(),
+                                                   int(index.shape[0]), _stream()), 'hfl_voxel_gather_rows')
+    return out
+
+
+def voxel_bounds(points: torch.Tensor, offsets: torch.Tensor):
+    """`hfl_voxel_bounds`: -> bounds (B, 6) int32 on the GPU, the ordered-integer images of every cloud's minimum and maximum
+    that `voxel_occupancy` takes; `decode_voxel_bounds` turns a host copy into floats."""
+    batch = _voxel_check('voxel_bounds', points, offsets)
+    n = int(points.shape[0])
+    if n < batch:
+        raise ValueError('voxel_bounds: %d points for %d non-empty clouds' % (n, batch))
+    bounds = torch.empty((batch, 6), dtype=torch.int32, device=points.device)
+    check(_native.load().hfl_voxel_bounds(bounds.data_ptr(), points.data_ptr(), offsets.data_ptr(), batch, n, _stream()),
+          'hfl_voxel_bounds')
+    return bounds
+
+
+def decode_voxel_bounds(bounds):
+    """a host copy of `voxel_bounds` -> (B, 6) float32 numpy: min x, y, z, max x, y, z"""
+    import numpy as np
+    e = np.ascontiguousarray(bounds).view(np.uint32).reshape(-1, 6).copy()
+    e[:, :3] = ~e[:, :3]
+    return np.where(e & 0x80000000, e & 0x7FFFFFFF, ~e).astype(np.uint32).view(np.float32)
+
+
+VOXEL_CANDIDATE_DTYPE = [('cloud', '<i4'), ('nx', '<i4'), ('ny', '<i4'), ('nz', '<i4'), ('voxel', '<f8'), ('word_offset', '<i8')]
+VOXEL_OCC_MAX_CANDIDATES = 65535       # HFL_VOXEL_OCC_MAX_CANDIDATES
+VOXEL_OCC_MAX_WORDS = 67108863         # HFL_VOXEL_OCC_MAX_WORDS
+
+
+def voxel_occupancy(points: torch.Tensor, offsets: torch.Tensor, bounds: torch.Tensor, candidates, bitmap_words: int,
+                    max_cloud_points: int):
+    """`hfl_voxel_occupancy`: `candidates` is a host numpy array of `VOXEL_CANDIDATE_DTYPE` (hfl_voxel_candidate) whose
+    bitmaps take `bitmap_words` words together -> counts (n_cand,) int32 on the GPU.  Nothing is read back."""
+    import numpy as np
+    batch = _voxel_check('voxel_occupancy', points, offsets)
+    _dev(bounds)
+    if bounds.dtype != torch.int32 or tuple(bounds.shape) != (batch, 6) or not bounds.is_contiguous():
+        raise TypeError('voxel_occupancy: (B, 6) int32 bounds expected')
+    table = np.ascontiguousarray(candidates, dtype=np.dtype(VOXEL_CANDIDATE_DTYPE))
+    n_cand = int(table.shape[0])
+    lib = _native.load()
+    nbytes = int(lib.hfl_voxel_occupancy_workspace(n_cand, int(bitmap_words)))
+    if table.ndim != 1 or nbytes <= 0:
+        raise ValueError('voxel_occupancy: 1..%d candidates and 1..%d bitmap words expected, got %d and %d'
+                         % (VOXEL_OCC_MAX_CANDIDATES, VOXEL_OCC_MAX_WORDS, n_cand, bitmap_words))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    counts = torch.empty(n_cand, dtype=torch.int32, device=points.device)
+    check(lib.hfl_voxel_occupancy(counts.data_ptr(), table.ctypes.data, n_cand, int(bitmap_words), bounds.data_ptr(),
+                                  points.data_ptr(), offsets.data_ptr(), batch, int(points.shape[0]), int(max_cloud_points),
+                                  ws.data_ptr(), nbytes, _stream()), 'hfl_voxel_occupancy')
+    counts._hfl_candidates = table      # the host table outlives the asynchronous copy: it goes when the counts go
+    return counts
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

@@ -183,24 +183,34 @@ def recall_from_indices(idx, truth_offsets, truth_indices, n_database: int, num_
 # ------------------------------------------------------------------------------------------------ whole-dataset evaluation
 def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesian', normalize: bool = True,
                   octree_depth: int = 7, full_depth: int = 2, device='cuda', voxel_size=None,
-                  normalise_submaps: bool = False, **prepare_kwargs):
+                  normalise_submaps: bool = False, downsample_target=None, downsample_type: str = 'pnvlad',
+                  **prepare_kwargs):
     """`get_latent_vectors` (`eval/pnv_evaluate.py:129-187`) without the file loading: raw (n, 3) clouds (a sequence or any
     iterable) -> (len, output_dim) fp32 descriptors on the GPU, `batch_size` clouds per forward (the last batch may be
     short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`.  With `voxel_size` and / or
     `normalise_submaps` the clouds are raw submaps in a metric frame: every batch first goes through the CS-Wild-Places
     submap post-processing on the device (`voxel.prepare_submaps`: voxel-grid downsample at `voxel_size`, then the
-    PointNetVLAD normalisation); with the defaults nothing changes."""
+    PointNetVLAD normalisation); with the defaults nothing changes.  With `downsample_target` = N the raw submaps become
+    fixed-size clouds of N points instead (the Oxford / CS-Campus3D format, `voxel.prepare_submaps_fixed`: the
+    `downsample_type` 'pnvlad' or 'random' downsampler, then, when `normalise_submaps`, the normalisation with padding);
+    it cannot be combined with `voxel_size`."""
     from .octree import build_batch_octree
     from .preprocess import prepare_clouds
     from . import voxel
     if batch_size < 1:
         raise ValueError('encode_clouds: batch_size >= 1 expected, got %d' % batch_size)
+    if downsample_target is not None and voxel_size is not None:
+        raise ValueError('encode_clouds: downsample_target (fixed-size clouds) and voxel_size (one voxel grid) exclude '
+                         'each other')
     model.eval()
     out, batch = [], []
 
     def flush():
         src = batch
-        if voxel_size is not None:
+        if downsample_target is not None:
+            src = voxel.prepare_submaps_fixed(batch, downsample_target, downsample=downsample_type,
+                                              normalise=normalise_submaps, device=device)
+        elif voxel_size is not None:
             src = voxel.prepare_submaps(batch, voxel_size, normalise=normalise_submaps, device=device)
         elif normalise_submaps:
             src = voxel.normalise_submaps(batch, device=device)

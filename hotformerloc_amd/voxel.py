@@ -31,8 +31,30 @@ Limits: a cloud may span at most 65 535 cells along an axis (16 bits per axis in
 32 767 clouds (15 bits, so the key stays a positive int64); both raise `ValueError`.  Non-finite coordinates give
 undefined output (nothing is read or written out of bounds).
 
-Out of scope: CSF ground removal (`postprocess_submaps.py --remove_ground`), the `random` and `pnvlad` downsamplers
-(`--downsample_type`), and the padding branch of `normalise_pcl` (`downsample_number` set)."""
+Fixed-size clouds (the Oxford / CS-Campus3D format, `target` = 4096 points; `postprocess_submaps.py --downsample_type
+pnvlad|random --downsample_target N --normalise`):
+
+    pnvlad   `processing_utils.pnvlad_down_sample`: v = 3.001, then v -= 0.01 until a voxel grid of size v has at least
+             `target` occupied cells, then v += 0.01 / 5 until it has at most `target`; the cell means at that v, then
+             `target - m` raw rows drawn by `np.random.default_rng(seed)`, a fresh generator per cloud.  The candidate sizes
+             are formed on the host in float64 by the same repeated operations.  Counts are not monotone in v: the sequence
+             is followed, never bisected.
+    random   `random_down_sample`: `target` raw rows drawn with replacement by a fresh generator per cloud.
+    padding  `normalise_pcl` with `downsample_number` set: after the normalisation above, raw rows are drawn, sent through
+             the same c and s, kept when every |q'| <= 1 and appended, until the cloud has `target` rows; the generator
+             continues across the iterations.  At most `PAD_MAX_ITERATIONS` iterations (the reference would loop for ever
+             on a raw cloud that has no row inside), then `ValueError`.
+
+Device route of the search: `hfl_voxel_bounds` once and one host read of the (B, 6) bounds; then rounds.  In a round the
+host writes down the next `PNVLAD_K_ONE` = 64 phase-one (or `PNVLAD_K_TWO` = 8 phase-two, doubled per round up to 64)
+candidates of every unfinished cloud with their grid dimensions, `hfl_voxel_occupancy` counts the occupied cells of all of them in one launch pair (a
+bitmap per candidate, integer OR atomics, a popcount), and the counts come back in one read.  Launches of a round share a
+bitmap budget of `OCCUPANCY_BUDGET_BYTES` = 64 MiB each; a single candidate whose bitmap is larger than the budget is
+counted by the keys -> sort -> reduce route instead.  Random indices are drawn on the host (`rng.choice(points, size=k)`
+and `points[rng.choice(len(points), size=k)]` draw the same rows) and gathered on the device (`hfl_voxel_gather_rows`);
+padded rows are transformed by `hfl_submap_normalise_rows`, which shares its device code with `hfl_submap_normalise`.
+
+Out of scope: CSF ground removal (`postprocess_submaps.py --remove_ground`)."""
 
 import math
 from typing import List, Sequence
@@ -240,3 +262,459 @@ def prepare_submaps(clouds: Sequence, voxel_size: float, normalise: bool = True,
     kept, starts = host[2 * batch:3 * batch], host[3 * batch:]
     _raise_normalise(host[batch:2 * batch], kept)
     return [out[s:s + k] for s, k in zip(starts[:-1], kept)]
+
+
+# ================================================================================================ fixed-size clouds
+PNVLAD_START = 3.001                   # processing_utils.pnvlad_down_sample
+PNVLAD_STEP = 0.01                     # VOXEL_STEP
+PNVLAD_K_ONE = 64                      # candidates per unfinished cloud and round while v steps down by 0.01 ...
+PNVLAD_K_TWO = 8                       # ... and while it steps back up by 0.002 (five steps undo one phase-one step);
+                                       # doubled every round a cloud stays in phase two, up to PNVLAD_K_ONE
+OCCUPANCY_BUDGET_BYTES = 64 << 20      # bitmap bytes of one hfl_voxel_occupancy call
+PAD_MAX_ITERATIONS = 64                # of the padding loop of normalise_pcl
+
+
+def _check_target(target) -> int:
+    t = int(target)
+    if t < 1 or t != target:
+        raise ValueError('target must be a positive integer, got %r' % (target,))
+    return t
+
+
+def _check_enough_points(sizes, target):
+    for i, n in enumerate(sizes):
+        if n < target:
+            raise ValueError('cloud %d has %d points, fewer than target = %d: no voxel size gives %d occupied cells'
+                             % (i, n, target, target))
+
+
+def _unreachable_error(i: int, target: int, why: str):
+    return ValueError('cloud %d never reaches %d occupied voxels: %s' % (i, target, why))
+
+
+def _as_arrays(clouds):
+    arrays = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3) for c in clouds]
+    _check_batch([a.shape[0] for a in arrays])
+    return arrays
+
+
+def _pad_indices(seed, n: int, k: int) -> np.ndarray:
+    """`rng.choice(points, size=k)` of a fresh generator, as row indices"""
+    return np.random.default_rng(seed).choice(n, size=k).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ host route
+def _host_counter(cloud: np.ndarray, index: int):
+    """v -> the number of cells the cloud occupies at voxel size v (`_cell_means` without the means)"""
+    p = cloud.astype(np.float64)
+    low = p.min(axis=0)
+
+    def count(v: float) -> int:
+        cell = np.floor((p - (low - 0.5 * v)) / v)
+        if not cell.max() < MAX_CELLS:
+            raise _span_error(index)
+        cell = cell.astype(np.int64)
+        return int(np.unique((cell[:, 0] << 32) | (cell[:, 1] << 16) | cell[:, 2]).size)
+    return count
+
+
+def voxel_occupancy_host(clouds: Sequence, sizes: Sequence[float]) -> np.ndarray:
+    """(B, S) int32: the number of occupied cells of every cloud at every voxel size, i.e.
+    `len(voxel_downsample_host([cloud], v)[0])`, in numpy float64."""
+    vs = [_check_voxel_size(v) for v in sizes]
+    arrays = _as_arrays(clouds)
+    out = np.zeros((len(arrays), len(vs)), np.int32)
+    for i, a in enumerate(arrays):
+        count = _host_counter(a, i)
+        for j, v in enumerate(vs):
+            out[i, j] = count(v)
+    return out
+
+
+def pnvlad_search_host(clouds: Sequence, target: int = 4096) -> List[dict]:
+    """The voxel-size search of `pnvlad_down_sample`, probe by probe as the reference runs it.  Per cloud a dict: 'voxel_size'
+    (the float64 the search ends on), 'count' (occupied cells there, <= target), 'trace' (every (v, count) probed, in
+    order), 'phase_one_steps', 'phase_two_steps'."""
+    target = _check_target(target)
+    arrays = _as_arrays(clouds)
+    _check_enough_points([a.shape[0] for a in arrays], target)
+    res = []
+    for i, a in enumerate(arrays):
+        count = _host_counter(a, i)
+        v = PNVLAD_START
+        n = count(v)
+        trace, one, two = [(v, n)], 0, 0
+        while n < target:
+            v -= PNVLAD_STEP
+            one += 1
+            if v <= 0:
+                raise _unreachable_error(i, target, 'the voxel size reached zero')
+            try:
+                n = count(v)
+            except ValueError:
+                raise _unreachable_error(i, target, 'at voxel size %.3f it spans more than %d cells along an axis'
+                                         % (v, MAX_CELLS)) from None
+            trace.append((v, n))
+        while n > target:
+            v += PNVLAD_STEP / 5
+            two += 1
+            n = count(v)
+            trace.append((v, n))
+        res.append({'voxel_size': v, 'count': n, 'trace': trace, 'phase_one_steps': one, 'phase_two_steps': two})
+    return res
+
+
+def pnvlad_downsample_host(clouds: Sequence, target: int = 4096, seed=42, return_voxel_sizes: bool = False):
+    """`pnvlad_down_sample` per cloud in numpy float64 (module docstring) -> list of (target, 3) float32 arrays: the cell
+    means at the voxel size the search ends on, in ascending (ix, iy, iz), then `target - m` raw rows drawn by a fresh
+    `default_rng(seed)`.  With `return_voxel_sizes` also the list of those sizes."""
+    arrays = _as_arrays(clouds)
+    found = pnvlad_search_host(arrays, target)
+    outs = []
+    for i, (a, f) in enumerate(zip(arrays, found)):
+        mean, _, _ = _cell_means(a, f['voxel_size'], i)
+        idx = _pad_indices(seed, a.shape[0], target - mean.shape[0])
+        outs.append(np.concatenate([mean.astype(np.float32), a[idx]]))
+    return (outs, [f['voxel_size'] for f in found]) if return_voxel_sizes else outs
+
+
+def random_downsample_host(clouds: Sequence, target: int, seed=42) -> List[np.ndarray]:
+    """`random_down_sample`: `target` rows of every cloud drawn with replacement by a fresh `default_rng(seed)`."""
+    target = _check_target(target)
+    arrays = _as_arrays(clouds)
+    return [a[_pad_indices(seed, a.shape[0], target)] for a in arrays]
+
+
+def _padding_error(i: int, target: int):
+    return ValueError('cloud %d is still short of %d points after %d rounds of padding: hardly any raw point lies inside '
+                      '[-1, 1]^3 after normalisation' % (i, target, PAD_MAX_ITERATIONS))
+
+
+def _too_many_error(i: int, kept: int, target: int):
+    return ValueError('cloud %d keeps %d points after normalisation, more than target = %d' % (i, kept, target))
+
+
+def normalise_submaps_padded_host(downsampled: Sequence, raw: Sequence, target: int, seed=42) -> List[np.ndarray]:
+    """`normalise_pcl` with `downsample_number = target` in numpy float64 -> list of (target, 3) float32 arrays: the rows of
+    `normalise_submaps_host(downsampled)`, then rows of `raw` drawn by `default_rng(seed)` (one generator per cloud, carried
+    across the iterations), sent through the same centroid and scale and kept when every |q'| <= 1."""
+    target = _check_target(target)
+    down, raws = _as_arrays(downsampled), _as_arrays(raw)
+    if len(down) != len(raws):
+        raise ValueError('%d downsampled clouds but %d raw clouds' % (len(down), len(raws)))
+    outs = []
+    for i, (a, r) in enumerate(zip(down, raws)):
+        q = a.astype(np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            c = q.mean(axis=0)
+            d = np.sqrt(((q - c) ** 2).sum(axis=1)).mean()
+        if not d > 0.0:
+            raise _degenerate_error(i)
+        scaled = (0.5 / d) * (q - c)
+        kept = scaled[np.all(np.abs(scaled) <= 1.0, axis=1)]
+        if kept.shape[0] < 1:
+            raise _empty_error(i)
+        if kept.shape[0] > target:
+            raise _too_many_error(i, kept.shape[0], target)
+        rng = np.random.default_rng(seed)
+        r64 = r.astype(np.float64)
+        extra, added, rounds, parts = target - kept.shape[0], 0, 0, [kept]
+        while kept.shape[0] + added < target:
+            if rounds == PAD_MAX_ITERATIONS:
+                raise _padding_error(i, target)
+            rounds += 1
+            rows = (0.5 / d) * (r64[rng.choice(r.shape[0], size=extra - added)] - c)
+            rows = rows[np.all(np.abs(rows) <= 1.0, axis=1)]
+            added += rows.shape[0]
+            parts.append(rows)
+        outs.append(np.concatenate(parts).astype(np.float32))
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------ device route
+def _grid_dims(lo_hi: np.ndarray, v: float):
+    """(nx, ny, nz) of a cloud with bounds `lo_hi` = (min x, y, z, max x, y, z) fp32 at voxel size v, by the formula of the
+    kernels, or None when it spans more than MAX_CELLS cells along an axis"""
+    low, high = lo_hi[:3].astype(np.float64), lo_hi[3:].astype(np.float64)
+    top = np.floor((high - (low - 0.5 * v)) / v)
+    if not top.max() < MAX_CELLS:
+        return None
+    return tuple(int(t) + 1 for t in top)
+
+
+def _count_by_sort(pts, start: int, end: int, v: float):
+    """one cloud's occupied cells at v through keys -> sort -> reduce, as a (1,) int64 device tensor"""
+    cloud = pts[start:end]
+    if (start * 12) % 16:
+        cloud = cloud.clone()                                                     # the kernels load 16 bytes at a time
+    off = torch.tensor([0, end - start], dtype=torch.int64, device=pts.device)
+    _, out_off, _, _, _ = _downsample_launch(cloud, off, 1, v, False, False)
+    return out_off[1:] - out_off[:1]
+
+
+def _count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes: int, stats=None) -> List[int]:
+    """cands: list of (cloud, v, (nx, ny, nz)) -> their occupied-cell counts, one host read.  Candidates are packed into
+    `hfl_voxel_occupancy` calls of at most `budget_bytes` of bitmaps; one whose own bitmap is larger goes to the sort route."""
+    budget_words = max(min(int(budget_bytes) // 4, ops.VOXEL_OCC_MAX_WORDS), 1)
+    biggest = int(np.diff(off_host).max())
+    parts, order, held = [], [], []
+    table, words, members = [], 0, []
+
+    def launch():
+        nonlocal table, words, members
+        if table:
+            arr = np.array(table, dtype=np.dtype(ops.VOXEL_CANDIDATE_DTYPE))
+            held.append(ops.voxel_occupancy(pts, off, bounds, arr, words, biggest))     # alive until the host read
+            parts.append(held[-1].to(torch.int64))
+            order.extend(members)
+            if stats is not None:
+                stats['occupancy_calls'] = stats.get('occupancy_calls', 0) + 1
+        table, words, members = [], 0, []
+
+    for k, (c, v, (nx, ny, nz)) in enumerate(cands):
+        w = (nx * ny * nz + 31) // 32
+        if w > budget_words:
+            parts.append(_count_by_sort(pts, int(off_host[c]), int(off_host[c + 1]), v))
+            order.append(k)
+            if stats is not None:
+                stats['sort_fallbacks'] = stats.get('sort_fallbacks', 0) + 1
+            continue
+        if words + w > budget_words or len(table) == ops.VOXEL_OCC_MAX_CANDIDATES:
+            launch()
+        table.append((c, nx, ny, nz, v, words))
+        members.append(k)
+        words += w
+    launch()
+    got = torch.cat(parts).cpu().tolist() if parts else []                        # the one host read
+    counts = [0] * len(cands)
+    for k, n in zip(order, got):
+        counts[k] = int(n)
+    return counts
+
+
+def _bounds_host(pts, off):
+    bounds = ops.voxel_bounds(pts, off)
+    return bounds, ops.decode_voxel_bounds(bounds.cpu().numpy())                  # the one host read of the bounds
+
+
+def voxel_occupancy(clouds: Sequence, sizes: Sequence[float], device='cuda', budget_bytes: int = OCCUPANCY_BUDGET_BYTES):
+    """(B, S) int32 device tensor: the number of occupied cells of every cloud at every voxel size -- what
+    `voxel_downsample` would return rows for -- counted by `hfl_voxel_occupancy` without a sort.  `budget_bytes` bounds the
+    bitmaps of one call (module docstring).  `ValueError` as `voxel_downsample`, the span limit included."""
+    vs = [_check_voxel_size(v) for v in sizes]
+    clouds = _as_tensors(clouds)
+    device = _device(device)
+    if not clouds or not vs:
+        return torch.zeros((len(clouds), len(vs)), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        pts, off, off_host = _upload(clouds, device)
+        bounds, lo_hi = _bounds_host(pts, off)
+        cands = []
+        for c in range(len(clouds)):
+            for v in vs:
+                dims = _grid_dims(lo_hi[c], v)
+                if dims is None:
+                    raise _span_error(c)
+                cands.append((c, v, dims))
+        counts = _count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes)
+        return torch.tensor(counts, dtype=torch.int32).reshape(len(clouds), len(vs)).to(device)
+
+
+def _pnvlad_search_device(pts, off, off_host, target: int, budget_bytes: int):
+    """the search of `pnvlad_search_host` with the counts from the device, K candidates per cloud and round -> (per-cloud
+    dicts as `pnvlad_search_host` returns them, stats: 'rounds', 'candidates' evaluated per cloud, calls and fallbacks)"""
+    batch = len(off_host) - 1
+    bounds, lo_hi = _bounds_host(pts, off)
+    state = [{'phase': 1, 'v': None, 'trace': [], 'one': 0, 'two': 0, 'count': None, 'k_two': PNVLAD_K_TWO} for _ in range(batch)]
+    stats = {'rounds': 0, 'candidates': [0] * batch}
+    while any(st['phase'] for st in state):
+        cands, plan = [], []
+        for c, st in enumerate(state):
+            if not st['phase']:
+                continue
+            vs, end, v = [], None, st['v']
+            ahead = PNVLAD_K_ONE
+            if st['phase'] == 2:
+                ahead, st['k_two'] = st['k_two'], min(2 * st['k_two'], PNVLAD_K_ONE)
+            for _ in range(ahead):
+                if st['phase'] == 2:
+                    v += PNVLAD_STEP / 5
+                elif v is None:
+                    v = PNVLAD_START
+                else:
+                    v -= PNVLAD_STEP
+                    if v <= 0:
+                        end = 'the voxel size reached zero'
+                        break
+                dims = _grid_dims(lo_hi[c], v)
+                if dims is None:
+                    end = 'at voxel size %.3f it spans more than %d cells along an axis' % (v, MAX_CELLS)
+                    break
+                vs.append(v)
+                cands.append((c, v, dims))
+            plan.append((c, vs, end))
+        counts = iter(_count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes, stats))
+        stats['rounds'] += 1
+        for c, vs, end in plan:
+            st = state[c]
+            stats['candidates'][c] += len(vs)
+            got = [next(counts) for _ in vs]
+            for v, n in zip(vs, got):
+                if st['phase'] == 1:
+                    st['one'] += bool(st['trace'])
+                    st['trace'].append((v, n))
+                    st['v'] = v
+                    if n >= target:
+                        st['phase'], st['count'] = (2 if n > target else 0), n
+                        break                                                     # the rest was speculation
+                else:
+                    st['two'] += 1
+                    st['trace'].append((v, n))
+                    st['v'] = v
+                    if n <= target:
+                        st['phase'], st['count'] = 0, n
+                        break
+            else:
+                if end is not None:
+                    raise _unreachable_error(c, target, end)
+    found = [{'voxel_size': st['v'], 'count': st['count'], 'trace': st['trace'], 'phase_one_steps': st['one'],
+              'phase_two_steps': st['two']} for st in state]
+    return found, stats
+
+
+def pnvlad_search(clouds: Sequence, target: int = 4096, device='cuda', budget_bytes: int = OCCUPANCY_BUDGET_BYTES,
+                  return_stats: bool = False):
+    """`pnvlad_search_host` with the occupied cells counted on the device (module docstring): the same per-cloud dicts, the
+    trace holding the probes the reference would have made (not the speculative ones past a stop).  With `return_stats` also
+    {'rounds', 'candidates' (evaluated per cloud, speculation included), 'occupancy_calls', 'sort_fallbacks'}."""
+    target = _check_target(target)
+    clouds = _as_tensors(clouds)
+    _check_enough_points([int(t.shape[0]) for t in clouds], target)
+    device = _device(device)
+    if not clouds:
+        return ([], {'rounds': 0, 'candidates': []}) if return_stats else []
+    with torch.cuda.device(device):
+        pts, off, off_host = _upload(clouds, device)
+        found, stats = _pnvlad_search_device(pts, off, off_host, target, budget_bytes)
+    return (found, stats) if return_stats else found
+
+
+def pnvlad_downsample(clouds: Sequence, target: int = 4096, seed=42, device='cuda', return_voxel_sizes: bool = False,
+                      budget_bytes: int = OCCUPANCY_BUDGET_BYTES):
+    """`pnvlad_down_sample` for a ragged batch on the device -> list of (target, 3) float32 device tensors: the cell means
+    at the voxel size the reference's search ends on (the rows `voxel_downsample([cloud], v)` returns, bit for bit), then
+    `target - m` raw rows at the indices a fresh `default_rng(seed)` draws per cloud.  With `return_voxel_sizes` also the
+    list of float64 sizes.  `ValueError`, naming the cloud: fewer than `target` points (raised before any launch), or no
+    voxel size down to zero / to the 65 535-cell span limit that gives `target` occupied cells."""
+    target = _check_target(target)
+    clouds = _as_tensors(clouds)
+    _check_enough_points([int(t.shape[0]) for t in clouds], target)
+    device = _device(device)
+    if not clouds:
+        return ([], []) if return_voxel_sizes else []
+    with torch.cuda.device(device):
+        pts, off, off_host = _upload(clouds, device)
+        found, _ = _pnvlad_search_device(pts, off, off_host, target, budget_bytes)
+        means, index = [], []
+        for c, f in enumerate(found):
+            s, e = int(off_host[c]), int(off_host[c + 1])
+            cloud = pts[s:e].clone() if (s * 12) % 16 else pts[s:e]
+            one = torch.tensor([0, e - s], dtype=torch.int64, device=device)
+            out, _, _, _, _ = _downsample_launch(cloud, one, 1, f['voxel_size'], False, False)
+            means.append(out[:f['count']])                                        # the count is the number of output rows
+            index.append(s + _pad_indices(seed, e - s, target - f['count']))
+        lens = [len(i) for i in index]
+        rows = ops.voxel_gather_rows(pts, torch.from_numpy(np.concatenate(index)).to(device)) if sum(lens) else None
+        outs, at = [], 0
+        for m, k in zip(means, lens):
+            outs.append(torch.cat([m, rows[at:at + k]]) if k else m.clone())
+            at += k
+    return (outs, [f['voxel_size'] for f in found]) if return_voxel_sizes else outs
+
+
+def random_downsample(clouds: Sequence, target: int, seed=42, device='cuda') -> List[torch.Tensor]:
+    """`random_down_sample` for a batch -> list of (target, 3) float32 device tensors: rows drawn with replacement by a
+    fresh `default_rng(seed)` per cloud (indices on the host, one gather launch on the device)."""
+    target = _check_target(target)
+    clouds = _as_tensors(clouds)
+    device = _device(device)
+    if not clouds:
+        return []
+    with torch.cuda.device(device):
+        pts, _, off_host = _upload(clouds, device)
+        index = np.concatenate([int(off_host[c]) + _pad_indices(seed, int(t.shape[0]), target) for c, t in enumerate(clouds)])
+        rows = ops.voxel_gather_rows(pts, torch.from_numpy(index).to(device))
+    return list(rows.reshape(len(clouds), target, 3).unbind(0))
+
+
+def normalise_submaps_padded(downsampled: Sequence, raw: Sequence, target: int, seed=42, device='cuda') -> List[torch.Tensor]:
+    """`normalise_pcl` with `downsample_number = target` for a batch -> list of (target, 3) float32 device tensors.  The
+    first rows are `normalise_submaps(downsampled)` bit for bit; the rest are rows of `raw` drawn by `default_rng(seed)`
+    (one generator per cloud, carried across the iterations), transformed by the same device code with the same centroid
+    and scale, and kept when every |q'| <= 1.  One host read for the normalisation and one per padding iteration.
+    `ValueError` as `normalise_submaps`, and when a cloud keeps more than `target` rows or the padding does not end."""
+    target = _check_target(target)
+    down, raws = _as_tensors(downsampled), _as_tensors(raw)
+    if len(down) != len(raws):
+        raise ValueError('%d downsampled clouds but %d raw clouds' % (len(down), len(raws)))
+    device = _device(device)
+    if not down:
+        return []
+    batch = len(down)
+    with torch.cuda.device(device):
+        dpts, doff, doff_host = _upload(down, device)
+        rpts, roff, roff_host = _upload(raws, device)
+        out, counts, flags = ops.submap_normalise(dpts, doff)
+        host = torch.cat([flags, counts]).cpu().tolist()
+        kept = host[batch:]
+        _raise_normalise(host[:batch], kept)
+        for i, k in enumerate(kept):
+            if k > target:
+                raise _too_many_error(i, k, target)
+        rngs = [np.random.default_rng(seed) for _ in range(batch)]
+        n_raw = np.diff(roff_host)
+        added, parts = [0] * batch, [[out[s:s + k]] for s, k in zip(doff_host.tolist(), kept)]
+        for _ in range(PAD_MAX_ITERATIONS):
+            want = [target - k - a for k, a in zip(kept, added)]                  # extra - added of the reference
+            if not any(want):
+                break
+            index = [rngs[i].choice(int(n_raw[i]), size=w).astype(np.int64) if w else np.zeros(0, np.int64)
+                     for i, w in enumerate(want)]
+            row_off = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
+            rows, keep = ops.submap_normalise_rows(dpts, doff, rpts, roff, torch.from_numpy(np.concatenate(index)).to(device),
+                                                   torch.from_numpy(row_off).to(device))
+            mask = keep.cpu().numpy() != 0                                        # the one host read of the iteration
+            picked = ops.voxel_gather_rows(rows, torch.from_numpy(np.flatnonzero(mask)).to(device))
+            at = 0
+            for i in range(batch):
+                n = int(mask[row_off[i]:row_off[i + 1]].sum())
+                if n:
+                    parts[i].append(picked[at:at + n])
+                at += n
+                added[i] += n
+        else:
+            if any(k + a < target for k, a in zip(kept, added)):
+                raise _padding_error([k + a < target for k, a in zip(kept, added)].index(True), target)
+        return [torch.cat(p) if len(p) > 1 else p[0].clone() for p in parts]
+
+
+def prepare_submaps_fixed(clouds: Sequence, target: int = 4096, downsample: str = 'pnvlad', normalise: bool = True, seed=42,
+                          device='cuda') -> List[torch.Tensor]:
+    """Raw submaps -> fixed-size clouds of `target` points (the Oxford / CS-Campus3D format): `pnvlad_downsample` or
+    `random_downsample`, then (when `normalise`) `normalise_submaps_padded` against the raw clouds.  The batch is uploaded
+    once and stays on the device between the steps; the result equals the chained calls bit for bit."""
+    if downsample not in ('pnvlad', 'random'):
+        raise ValueError("downsample must be 'pnvlad' or 'random', got %r" % (downsample,))
+    target = _check_target(target)
+    clouds = _as_tensors(clouds)
+    if downsample == 'pnvlad':
+        _check_enough_points([int(t.shape[0]) for t in clouds], target)
+    device = _device(device)
+    if not clouds:
+        return []
+    with torch.cuda.device(device):
+        resident = [t.to(device, non_blocking=True) for t in clouds] if any(t.is_cuda for t in clouds) else \
+            list(torch.cat(clouds).to(device, non_blocking=True).split([int(t.shape[0]) for t in clouds]))
+        down = pnvlad_downsample(resident, target, seed=seed, device=device) if downsample == 'pnvlad' else \
+            random_downsample(resident, target, seed=seed, device=device)
+        return normalise_submaps_padded(down, resident, target, seed=seed, device=device) if normalise else down

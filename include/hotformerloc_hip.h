@@ -254,6 +254,49 @@ int hfl_voxel_reduce(float* out_points, int64_t* out_offsets, int32_t* out_cell_
  * per cloud, fixed-order float64 reductions (no atomics), one launch on `stream`.  out_points must not alias points. */
 int hfl_submap_normalise(float* out_points, int32_t* out_counts, int32_t* flags, const float* points,
                          const int64_t* cloud_offsets, int batch, hfl_stream_t stream);
+/* The padding loop of normalise_pcl (downsample_number set): rows drawn from the raw cloud go through the transform of
+ * hfl_submap_normalise -- the same device code, so the same bits: c and s come from the same fixed-order float64
+ * reductions over cloud b of `points`, q' = s (q - c) in float64 rounded once to fp32.  Row j of cloud b, j in
+ * [row_offsets[b], row_offsets[b+1]), is raw row raw_offsets[b] + row_index[j]; out_rows (R,3) receives q' and keep[j] = 1
+ * when every |q'| <= 1.  An index outside the raw cloud, or a cloud whose d is not > 0, gives a zero row with keep = 0.
+ * One workgroup per cloud, one launch on `stream`. */
+int hfl_submap_normalise_rows(float* out_rows, int32_t* keep, const float* points, const int64_t* cloud_offsets,
+                              const float* raw_points, const int64_t* raw_offsets, const int64_t* row_index,
+                              const int64_t* row_offsets, int batch, hfl_stream_t stream);
+/* out_points[r] = points[index[r]] for r < n_rows (the random rows of the fixed-size downsamplers); an index outside
+ * [0, n_points) gives a zero row.  One launch on `stream`. */
+int hfl_voxel_gather_rows(float* out_points, const float* points, int64_t n_points, const int64_t* index, int64_t n_rows,
+                          hfl_stream_t stream);
+/* The first half of hfl_voxel_keys alone: bounds (batch, 6) uint32 receives the ordered-integer images of every cloud's
+ * minimum and maximum ([0..2] = ~enc(min), [3..5] = enc(max); enc(f) = bits(f) ^ (sign ? ~0 : 1 << 31)).  Same argument
+ * rules as hfl_voxel_keys.  A memset and one launch on `stream`. */
+int hfl_voxel_bounds(uint32_t* bounds, const float* points, const int64_t* cloud_offsets, int batch, int64_t n_points,
+                     hfl_stream_t stream);
+/* One candidate of hfl_voxel_occupancy: cloud `cloud` on a grid of voxel size `voxel`, nx x ny x nz cells (each
+ * 1..HFL_VOXEL_MAX_CELLS; the caller derives them from the cloud's bounds with the formula of hfl_voxel_keys), whose bitmap
+ * of nx ny nz bits starts at 32-bit word `word_offset` of the call's bitmap area.  Bitmaps must not overlap. */
+typedef struct {
+  int32_t cloud;
+  int32_t nx, ny, nz;
+  double voxel;
+  int64_t word_offset;
+} hfl_voxel_candidate;
+#define HFL_VOXEL_OCC_MAX_CANDIDATES 65535    /* one grid row per candidate                       */
+#define HFL_VOXEL_OCC_MAX_WORDS 67108863LL    /* < 2^31 bits per call, so a count fits its int32 */
+/* bytes of workspace for n_candidates candidates whose bitmaps take bitmap_words 32-bit words together (0 when out of range) */
+int64_t hfl_voxel_occupancy_workspace(int n_candidates, int64_t bitmap_words);
+/* counts[k] = the number of distinct cells that candidate k's cloud occupies at its voxel size, with a point's cell exactly
+ * the one hfl_voxel_keys computes (same device functions), so counts[k] = the rows hfl_voxel_reduce would return for that
+ * cloud and size.  `candidates` is HOST memory (n_candidates rows): it is checked here -- every bitmap inside the bitmap
+ * area -- and copied into the workspace; bounds is what hfl_voxel_bounds / hfl_voxel_keys left for the same points.  A point
+ * whose cell lies outside a candidate's nx x ny x nz (a table that does not match the bounds) is skipped, never written.
+ * max_cloud_points (the largest cloud) only sizes the grid.  Integer OR atomics on bitmaps (in LDS when a bitmap fits
+ * 32 KiB, else in global memory), then a popcount: exact and order-independent, no workgroup waits for another.  A copy,
+ * a memset and two launches on `stream`.  workspace 16-byte aligned, workspace_bytes >= hfl_voxel_occupancy_workspace. */
+int hfl_voxel_occupancy(int32_t* counts, const hfl_voxel_candidate* candidates, int n_candidates, int64_t bitmap_words,
+                        const uint32_t* bounds, const float* points, const int64_t* cloud_offsets, int batch,
+                        int64_t n_points, int64_t max_cloud_points, void* workspace, int64_t workspace_bytes,
+                        hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 3. Octree convolution gather  (ocnn.nn.OctreeConv's octree2col; call sites
