@@ -25,5 +25,8 @@ from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_
                     normalise_submaps_padded_host, prepare_submaps_fixed)
 from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
                      tuple_index_from_poses, truth_from_poses)
+from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_points, nn_distances,   # noqa: F401,E402
+                      chamfer_distance, overlap_ratio, submap_overlap, transform_points_host, nn_distances_host,
+                      chamfer_distance_host, overlap_ratio_host, submap_overlap_host, ChamferResult, SubmapOverlap)
 
 __version__ = '0.1.0'

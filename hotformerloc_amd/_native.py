@@ -217,6 +217,11 @@ SIGNATURES = {
                                 c_void_p]),
     'hfl_radius_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                  c_double, c_int, c_void_p]),
+    'hfl_transform_points': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    'hfl_nn_dist': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                            c_int64, c_void_p]),
+    'hfl_pair_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.POINTER(c_float), c_int,
+                               c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -1676,6 +1676,94 @@ def radius_lists(queries: torch.Tensor, database: torch.Tensor, r_a: float, r_b:
     return (off_a, idx_a, off_b, idx_b) if want_b else (off_a, idx_a, None, None)
 
 
+OVERLAP_ROWS = 512                     # HFL_OVERLAP_ROWS: query rows of a workgroup of hfl_nn_dist (two per thread)
+OVERLAP_TILE = 2048                    # HFL_OVERLAP_TILE: target points of the LDS tile those rows share
+OVERLAP_MAX_TAUS = 8                   # HFL_OVERLAP_MAX_TAUS: thresholds of one hfl_pair_stats launch
+
+
+def _overlap_check(what: str, points: torch.Tensor, offsets: torch.Tensor):
+    _dev(points, offsets)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise TypeError('%s: contiguous (N, 3) float32 points expected' % what)
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
+        raise TypeError('%s: (P + 1,) int64 cloud offsets with P >= 1 expected' % what)
+    return int(offsets.shape[0]) - 1
+
+
+def _some(t: torch.Tensor):
+    """`t`, or one zero row of its kind where it has none: kernels take no null pointer (the row is never read)."""
+    return t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+
+
+def overlap_tiles(lengths):
+    """The tile table of `hfl_nn_dist` from the query clouds' lengths on the host: (n_tiles, 2) int64 numpy rows of (pair,
+    first query row), OVERLAP_ROWS rows of one pair per workgroup, pairs in order; an empty cloud has no tile."""
+    import numpy as np
+    lengths = np.asarray(lengths, dtype=np.int64)
+    per = -(-lengths // OVERLAP_ROWS)
+    pair = np.repeat(np.arange(lengths.shape[0], dtype=np.int64), per)
+    first = np.cumsum(per) - per                                   # the first tile of every pair
+    start = np.cumsum(lengths) - lengths
+    row = start[pair] + (np.arange(pair.shape[0], dtype=np.int64) - first[pair]) * OVERLAP_ROWS
+    return np.stack([pair, row], 1)
+
+
+def transform_points(points: torch.Tensor, offsets: torch.Tensor, transforms: torch.Tensor):
+    """`hfl_transform_points`: points (N, 3) fp32, offsets (P + 1,) int64 with offsets[0] = 0 and offsets[P] = N (the caller
+    checks) and transforms (P, 12) fp32, a row-major (R | t) per pair, all on the GPU -> R_p x + t_p for every row."""
+    pairs = _overlap_check('transform_points', points, offsets)
+    _dev(transforms)
+    if transforms.dtype != torch.float32 or tuple(transforms.shape) != (pairs, 12) or not transforms.is_contiguous():
+        raise TypeError('transform_points: contiguous (%d, 12) float32 transforms expected' % pairs)
+    out = torch.empty_like(points)
+    if points.shape[0]:
+        check(_native.load().hfl_transform_points(out.data_ptr(), points.data_ptr(), offsets.data_ptr(), transforms.data_ptr(),
+                                                  pairs, int(points.shape[0]), _stream()), 'hfl_transform_points')
+    return out
+
+
+def nn_dist(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
+            tiles: torch.Tensor):
+    """`hfl_nn_dist`: two ragged batches of the same P pairs and the (n_tiles, 2) int64 device copy of `overlap_tiles` ->
+    (dist (Nq,) fp32, idx (Nq,) int32): every query's distance to the nearest point of its pair's target cloud and that
+    point's index within the cloud, +inf and -1 where the cloud is empty.  Rows the table does not cover stay unwritten."""
+    pairs = _overlap_check('nn_dist', queries, q_offsets)
+    if _overlap_check('nn_dist', targets, t_offsets) != pairs:
+        raise ValueError('nn_dist: the query batch and the target batch differ in their number of pairs')
+    _dev(tiles)
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('nn_dist: contiguous (n_tiles, 2) int64 tile table expected')
+    n_q = int(queries.shape[0])
+    dist = torch.empty(n_q, dtype=torch.float32, device=queries.device)
+    idx = torch.empty(n_q, dtype=torch.int32, device=queries.device)
+    if n_q and tiles.shape[0]:
+        check(_native.load().hfl_nn_dist(dist.data_ptr(), idx.data_ptr(), queries.data_ptr(), q_offsets.data_ptr(), n_q,
+                                         _some(targets).data_ptr(), t_offsets.data_ptr(), int(targets.shape[0]),
+                                         tiles.data_ptr(), int(tiles.shape[0]), pairs, _stream()), 'hfl_nn_dist')
+    return dist, idx
+
+
+def pair_stats(dist: torch.Tensor, offsets: torch.Tensor, taus=()):
+    """`hfl_pair_stats`: dist (N,) fp32 and offsets (P + 1,) int64 on the GPU, up to OVERLAP_MAX_TAUS thresholds ->
+    (sums (P, 2) float64: the sum of a pair's distances and of their squares, counts (P, K + 1) int64: the distances
+    <= taus[k] compared in fp32, and in the last column the +inf ones, which are in no other figure)."""
+    _dev(dist, offsets)
+    if dist.dtype != torch.float32 or dist.dim() != 1 or not dist.is_contiguous():
+        raise TypeError('pair_stats: contiguous (N,) float32 distances expected')
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
+        raise TypeError('pair_stats: (P + 1,) int64 offsets with P >= 1 expected')
+    taus = [float(t) for t in taus]
+    if len(taus) > OVERLAP_MAX_TAUS:
+        raise ValueError('pair_stats: at most %d thresholds in one launch, got %d' % (OVERLAP_MAX_TAUS, len(taus)))
+    pairs = int(offsets.shape[0]) - 1
+    sums = torch.empty((pairs, 2), dtype=torch.float64, device=dist.device)
+    counts = torch.empty((pairs, len(taus) + 1), dtype=torch.int64, device=dist.device)
+    host_taus = (ctypes.c_float * OVERLAP_MAX_TAUS)(*taus)
+    check(_native.load().hfl_pair_stats(sums.data_ptr(), counts.data_ptr(), _some(dist).data_ptr(), offsets.data_ptr(),
+                                        int(dist.shape[0]), pairs, host_taus, len(taus), _stream()), 'hfl_pair_stats')
+    return sums, counts
+
+
 VOXEL_MAX_CLOUDS = 32767              # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS

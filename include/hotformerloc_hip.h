@@ -952,7 +952,7 @@ int hfl_batch_masks(uint8_t* pos_mask, uint8_t* neg_mask, int32_t* counts, const
  *      calls and the per-anchor np.setdiff1d / np.sort loop of datasets/{pointnetvlad,WildPlaces}/generate_training_tuples*.py,
  *      generate_test_sets.py and datasets/CSWildPlaces/generate_train_test_tuples.py:92-212)
  * ---------------------------------------------------------------------- */
-/* Query rows (one wave each) of a workgroup, and database positions of the LDS tile they share (16 B each). */
+/* Query rows (one wave each) of a workgroup, and database positions of the LDS tile they share (12 B each). */
 #define HFL_RADIUS_ROWS 8
 #define HFL_RADIUS_TILE 2048
 /* Two CSR list families over queries (Q,2) and database (N,2), float64 row-major: list A of query i holds the ids j with
@@ -967,6 +967,41 @@ int hfl_batch_masks(uint8_t* pos_mask, uint8_t* neg_mask, int32_t* counts, const
 int hfl_radius_lists(int32_t* counts, int32_t* ids_a, int32_t* ids_b, const int64_t* off_a, const int64_t* off_b,
                      const double* queries, int64_t n_queries, const double* database, int64_t n_database, double r_a,
                      double r_b, int exclude_self, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * 11e. Ground-to-aerial submap overlap: align, nearest neighbours, Chamfer sums (misc/compute_ground_aerial_overlap.py:
+ *      apply_transform and the chamfer_distance the script leaves as a TODO)
+ * ---------------------------------------------------------------------- */
+/* Query rows of a 256-thread workgroup of hfl_nn_dist (HFL_OVERLAP_ROWS / 256 per thread, in registers), target points of
+ * the LDS tile they share (12 B each), and the most thresholds hfl_pair_stats counts in one launch. */
+#define HFL_OVERLAP_ROWS 512
+#define HFL_OVERLAP_TILE 2048
+#define HFL_OVERLAP_MAX_TAUS 8
+/* All three take a ragged batch of P pairs: the points of all clouds concatenated as (N, 3) fp32 row-major and (P + 1)
+ * int64 DEVICE offsets, cloud p at rows [offsets[p], offsets[p + 1]), offsets[0] = 0, non-decreasing, offsets[P] = N (the
+ * caller checks; the kernels clamp what they read of them to the arrays).  Inputs must be finite; this is not checked.  No
+ * atomics, one writer per output element, a fixed evaluation order: two runs give the same bits.  One launch each on
+ * `stream`, no synchronisation.  A NULL pointer, a negative count or P < 1: HFL_EINVAL; a total that does not fit (P, a
+ * grid or the targets of hfl_nn_dist at 2^31 or more): HFL_ECAPACITY. */
+/* out[i] = R_p x[i] + t_p for the pair p that owns row i; transforms (P, 12) fp32, a row-major 3 x 4 (R | t) per pair.  Per
+ * coordinate c one fmaf chain: acc = fmaf(R[c][0], x, t[c]); acc = fmaf(R[c][1], y, acc); out = fmaf(R[c][2], z, acc). */
+int hfl_transform_points(float* out, const float* points, const int64_t* offsets, const float* transforms, int64_t n_pairs,
+                         int64_t n_points, hfl_stream_t stream);
+/* For every query row of pair p: dist = the distance to the nearest point of pair p's target cloud, idx = that point's
+ * index within the cloud (int32); +inf and -1 where the target cloud is empty.  d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in
+ * fp32 on the differences, one correctly rounded square root of the minimum; of equal d2 the lowest index wins.  tiles
+ * (n_tiles, 2) int64 on the DEVICE, built by the host from the query offsets: (pair, first query row) per workgroup, which
+ * then owns the rows [first, min(first + HFL_OVERLAP_ROWS, q_offsets[pair + 1])).  Rows no tile covers are not written. */
+int hfl_nn_dist(float* dist, int32_t* idx, const float* queries, const int64_t* q_offsets, int64_t n_queries,
+                const float* targets, const int64_t* t_offsets, int64_t n_targets, const int64_t* tiles, int64_t n_tiles,
+                int64_t n_pairs, hfl_stream_t stream);
+/* Per pair p over dist[offsets[p] .. offsets[p + 1]): sums (P, 2) float64 = the sum of the distances and of their squares,
+ * both from the stored fp32 values widened to float64; counts (P, K + 1) int64 = for each of the K thresholds of the HOST
+ * array taus (0 <= K <= HFL_OVERLAP_MAX_TAUS, by value in the kernel arguments) how many distances are <= taus[k], compared
+ * in fp32, and in column K how many are +inf.  +inf distances are in no sum and no threshold count.  One workgroup per
+ * pair, a fixed reduction order. */
+int hfl_pair_stats(double* sums, int64_t* counts, const float* dist, const int64_t* offsets, int64_t n_dist, int64_t n_pairs,
+                   const float* taus, int n_taus, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
