@@ -23,6 +23,7 @@ from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_
                     normalise_submaps_host, voxel_occupancy, voxel_occupancy_host, pnvlad_downsample,
                     pnvlad_downsample_host, random_downsample, random_downsample_host, normalise_submaps_padded,
                     normalise_submaps_padded_host, prepare_submaps_fixed)
+from .ground import remove_ground, remove_ground_host                                              # noqa: F401,E402
 from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
                      tuple_index_from_poses, truth_from_poses)
 from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_points, nn_distances,   # noqa: F401,E402

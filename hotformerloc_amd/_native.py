@@ -131,6 +131,12 @@ SIGNATURES = {
     'hfl_voxel_occupancy_workspace': (c_int64, [c_int, c_int64]),
     'hfl_voxel_occupancy': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64,
                                     c_void_p, c_int64, c_void_p]),
+    'hfl_cloth_raster': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_float,
+                                 c_void_p]),
+    'hfl_cloth_simulate': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float, c_float,
+                                   c_float, c_float, c_int, c_int, c_void_p]),
+    'hfl_cloth_classify': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_float,
+                                   c_float, c_void_p]),
     'hfl_tap_lists_workspace': (c_int64, [c_int64, c_int]),
     'hfl_tap_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'hfl_tap_lists_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

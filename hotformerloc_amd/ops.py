@@ -1922,6 +1922,78 @@ def voxel_occupancy(points: torch.Tensor, offsets: torch.Tensor, bounds: torch.T
     return counts
 
 
+CLOTH_MAX_PARTICLES = 10240            # HFL_CLOTH_MAX_PARTICLES: width * height of one cloth
+CLOTH_DESC_DTYPE = [('ox', '<f4'), ('oy', '<f4'), ('u0', '<f4'), ('width', '<i4'), ('height', '<i4'), ('reserved', '<i4'),
+                    ('cell_offset', '<i8')]                                          # hfl_cloth_desc
+
+
+class ClothTable:
+    """One `hfl_cloth_desc` per cloud on both sides: `host` (numpy, what the library checks before a launch) and `device`
+    (the same bytes, what the kernels read); `cells` particles in all, cloud b's at `host['cell_offset'][b]`."""
+
+    def __init__(self, descs, device):
+        import numpy as np
+        self.host = np.ascontiguousarray(descs, dtype=np.dtype(CLOTH_DESC_DTYPE))
+        if self.host.ndim != 1 or self.host.shape[0] < 1:
+            raise ValueError('ClothTable: one hfl_cloth_desc per cloud expected')
+        self.batch = int(self.host.shape[0])
+        self.cells = int((self.host['width'].astype(np.int64) * self.host['height']).sum())
+        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+
+
+def _cloth_check(what: str, table: ClothTable, points=None, offsets=None):
+    _dev(table.device)
+    if points is not None and _voxel_check(what, points, offsets) != table.batch:
+        raise ValueError('%s: %d clouds but %d cloths' % (what, int(offsets.shape[0]) - 1, table.batch))
+    if table.cells < 1:
+        raise ValueError('%s: the cloths hold no particle' % what)
+
+
+def cloth_raster(points: torch.Tensor, offsets: torch.Tensor, table: ClothTable, resolution: float):
+    """`hfl_cloth_raster`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU -> terrain (cells,) fp32: every particle's
+    t, rastered or filled.  Nothing is read back."""
+    _cloth_check('cloth_raster', table, points, offsets)
+    terrain = torch.empty(table.cells, dtype=torch.float32, device=points.device)
+    keys = torch.empty(table.cells, dtype=torch.int64, device=points.device)
+    check(_native.load().hfl_cloth_raster(terrain.data_ptr(), keys.data_ptr(), table.host.ctypes.data, table.device.data_ptr(),
+                                          table.batch, table.cells, points.data_ptr(), offsets.data_ptr(),
+                                          int(points.shape[0]), float(resolution), _stream()), 'hfl_cloth_raster')
+    return terrain
+
+
+def cloth_simulate(terrain: torch.Tensor, table: ClothTable, f_one: float, f_two: float, gravity_step: float,
+                   velocity_keep: float, iterations: int, slope_smooth: bool):
+    """`hfl_cloth_simulate`: terrain (cells,) fp32 -> (heights (cells,) fp32, movable (cells,) uint8, steps_run (B,) int32),
+    one workgroup per cloud.  The four factors are passed as the fp32 values the host route uses."""
+    _cloth_check('cloth_simulate', table)
+    _dev(terrain)
+    if terrain.dtype != torch.float32 or tuple(terrain.shape) != (table.cells,) or not terrain.is_contiguous():
+        raise TypeError('cloth_simulate: contiguous (%d,) float32 terrain expected' % table.cells)
+    heights = torch.empty_like(terrain)
+    movable = torch.empty(table.cells, dtype=torch.uint8, device=terrain.device)
+    steps = torch.empty(table.batch, dtype=torch.int32, device=terrain.device)
+    check(_native.load().hfl_cloth_simulate(heights.data_ptr(), movable.data_ptr(), steps.data_ptr(), terrain.data_ptr(),
+                                            table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
+                                            float(f_one), float(f_two), float(gravity_step), float(velocity_keep),
+                                            int(iterations), int(bool(slope_smooth)), _stream()), 'hfl_cloth_simulate')
+    return heights, movable, steps
+
+
+def cloth_classify(points: torch.Tensor, offsets: torch.Tensor, heights: torch.Tensor, table: ClothTable, resolution: float,
+                   threshold: float):
+    """`hfl_cloth_classify`: -> keep (P,) uint8 on the GPU, 0 where a point lies within `threshold` of the cloth (ground)."""
+    _cloth_check('cloth_classify', table, points, offsets)
+    _dev(heights)
+    if heights.dtype != torch.float32 or tuple(heights.shape) != (table.cells,) or not heights.is_contiguous():
+        raise TypeError('cloth_classify: contiguous (%d,) float32 heights expected' % table.cells)
+    keep = torch.empty(int(points.shape[0]), dtype=torch.uint8, device=points.device)
+    check(_native.load().hfl_cloth_classify(keep.data_ptr(), heights.data_ptr(), table.host.ctypes.data,
+                                            table.device.data_ptr(), table.batch, table.cells, points.data_ptr(),
+                                            offsets.data_ptr(), int(points.shape[0]), float(resolution), float(threshold),
+                                            _stream()), 'hfl_cloth_classify')
+    return keep
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

@@ -184,7 +184,7 @@ def recall_from_indices(idx, truth_offsets, truth_indices, n_database: int, num_
 def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesian', normalize: bool = True,
                   octree_depth: int = 7, full_depth: int = 2, device='cuda', voxel_size=None,
                   normalise_submaps: bool = False, downsample_target=None, downsample_type: str = 'pnvlad',
-                  **prepare_kwargs):
+                  remove_ground: bool = False, ground_params=None, **prepare_kwargs):
     """`get_latent_vectors` (`eval/pnv_evaluate.py:129-187`) without the file loading: raw (n, 3) clouds (a sequence or any
     iterable) -> (len, output_dim) fp32 descriptors on the GPU, `batch_size` clouds per forward (the last batch may be
     short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`.  With `voxel_size` and / or
@@ -193,10 +193,11 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
     PointNetVLAD normalisation); with the defaults nothing changes.  With `downsample_target` = N the raw submaps become
     fixed-size clouds of N points instead (the Oxford / CS-Campus3D format, `voxel.prepare_submaps_fixed`: the
     `downsample_type` 'pnvlad' or 'random' downsampler, then, when `normalise_submaps`, the normalisation with padding);
-    it cannot be combined with `voxel_size`."""
+    it cannot be combined with `voxel_size`.  With `remove_ground` every batch of raw submaps first goes through the cloth
+    filter on the device (`ground.remove_ground(**ground_params)`), before whichever of the steps above is asked for."""
     from .octree import build_batch_octree
     from .preprocess import prepare_clouds
-    from . import voxel
+    from . import ground, voxel
     if batch_size < 1:
         raise ValueError('encode_clouds: batch_size >= 1 expected, got %d' % batch_size)
     if downsample_target is not None and voxel_size is not None:
@@ -204,14 +205,19 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
                          'each other')
     model.eval()
     out, batch = [], []
+    filtered = {'remove_ground': True, 'ground_params': ground_params} if remove_ground else {}
 
     def flush():
         src = batch
         if downsample_target is not None:
             src = voxel.prepare_submaps_fixed(batch, downsample_target, downsample=downsample_type,
-                                              normalise=normalise_submaps, device=device)
+                                              normalise=normalise_submaps, device=device, **filtered)
         elif voxel_size is not None:
-            src = voxel.prepare_submaps(batch, voxel_size, normalise=normalise_submaps, device=device)
+            src = voxel.prepare_submaps(batch, voxel_size, normalise=normalise_submaps, device=device, **filtered)
+        elif remove_ground:
+            src = ground.filter_batch(batch, device, ground_params)
+            if normalise_submaps:
+                src = voxel.normalise_submaps(src, device=device)
         elif normalise_submaps:
             src = voxel.normalise_submaps(batch, device=device)
         pts = prepare_clouds(src, coordinates=coordinates, normalize=normalize, device=device, **prepare_kwargs)

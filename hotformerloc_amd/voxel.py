@@ -54,7 +54,8 @@ counted by the keys -> sort -> reduce route instead.  Random indices are drawn o
 and `points[rng.choice(len(points), size=k)]` draw the same rows) and gathered on the device (`hfl_voxel_gather_rows`);
 padded rows are transformed by `hfl_submap_normalise_rows`, which shares its device code with `hfl_submap_normalise`.
 
-Out of scope: CSF ground removal (`postprocess_submaps.py --remove_ground`)."""
+Ground removal (`postprocess_submaps.py --remove_ground`, the step before the downsample) is `ground.py`; the entry points
+`prepare_submaps` and `prepare_submaps_fixed` run it first with `remove_ground=True`."""
 
 import math
 from typing import List, Sequence
@@ -239,10 +240,18 @@ def normalise_submaps(clouds: Sequence, device='cuda') -> List[torch.Tensor]:
     return [out[s:s + k] for s, k in zip(off_host.tolist(), host[batch:])]
 
 
-def prepare_submaps(clouds: Sequence, voxel_size: float, normalise: bool = True, device='cuda') -> List[torch.Tensor]:
+def prepare_submaps(clouds: Sequence, voxel_size: float, normalise: bool = True, device='cuda', *, remove_ground: bool = False,
+                    ground_params=None) -> List[torch.Tensor]:
     """`voxel_downsample` then (when `normalise`) `normalise_submaps` without leaving the device: the normalisation reads
     the downsampled batch and its per-cloud offsets where the reduction left them, and flags, offsets and counts come back
-    in one host read.  The result is what `prepare_clouds` takes; it equals the two calls chained bit for bit."""
+    in one host read.  The result is what `prepare_clouds` takes; it equals the two calls chained bit for bit.  With
+    `remove_ground` the raw batch first goes through `ground.remove_ground(**ground_params)` and stays on the device: the
+    documented CS-Wild-Places order, remove the ground, downsample, normalise.  `ValueError`, naming the cloud, when the
+    filter leaves a cloud no point."""
+    if remove_ground:
+        from . import ground
+        _check_voxel_size(voxel_size)
+        clouds = ground.filter_batch(clouds, device, ground_params)
     if not normalise:
         return voxel_downsample(clouds, voxel_size, device=device)
     v = _check_voxel_size(voxel_size)
@@ -699,13 +708,19 @@ def normalise_submaps_padded(downsampled: Sequence, raw: Sequence, target: int, 
 
 
 def prepare_submaps_fixed(clouds: Sequence, target: int = 4096, downsample: str = 'pnvlad', normalise: bool = True, seed=42,
-                          device='cuda') -> List[torch.Tensor]:
+                          device='cuda', *, remove_ground: bool = False, ground_params=None) -> List[torch.Tensor]:
     """Raw submaps -> fixed-size clouds of `target` points (the Oxford / CS-Campus3D format): `pnvlad_downsample` or
     `random_downsample`, then (when `normalise`) `normalise_submaps_padded` against the raw clouds.  The batch is uploaded
-    once and stays on the device between the steps; the result equals the chained calls bit for bit."""
+    once and stays on the device between the steps; the result equals the chained calls bit for bit.  With `remove_ground`
+    the batch first goes through `ground.remove_ground(**ground_params)`; the filtered cloud is then also the raw cloud the
+    padding draws from, as in the reference, which reassigns its points.  `ValueError`, naming the cloud, when the filter
+    leaves a cloud fewer than `target` points."""
     if downsample not in ('pnvlad', 'random'):
         raise ValueError("downsample must be 'pnvlad' or 'random', got %r" % (downsample,))
     target = _check_target(target)
+    if remove_ground:
+        from . import ground
+        clouds = ground.filter_batch(clouds, device, ground_params, at_least=target)
     clouds = _as_tensors(clouds)
     if downsample == 'pnvlad':
         _check_enough_points([int(t.shape[0]) for t in clouds], target)

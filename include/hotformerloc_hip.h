@@ -299,6 +299,49 @@ int hfl_voxel_occupancy(int32_t* counts, const hfl_voxel_candidate* candidates, 
                         hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 2c. Raw submaps: ground removal by the Cloth Simulation Filter (csrc/ground.hip; replaces
+ *     datasets/CSWildPlaces/postprocess_submaps.py --remove_ground, i.e. processing_utils.remove_ground and the pip CSF
+ *     package behind it).  The filter is defined in hotformerloc_amd/ground.py and DESIGN.md section 7f: fp32, z up,
+ *     u = -z, every operation rounded once; bit parity with the pip package is not claimed.
+ * ---------------------------------------------------------------------- */
+#define HFL_CLOTH_MAX_PARTICLES 10240     /* width * height of one cloth: u, u_prev, t and the flags stay in LDS (130 KiB) */
+/* One cloud's cloth: particle (i, j), i < width, j < height, stands at (ox + i r, oy + j r) and is element
+ * cell_offset + j * width + i of the particle arrays; u0 is the start height max(-z) + 0.05.  The caller derives the
+ * fields from the cloud's fp32 bounds (hfl_voxel_bounds) as the definition says. */
+typedef struct {
+  float ox, oy, u0;
+  int32_t width, height;
+  int32_t reserved;
+  int64_t cell_offset;
+} hfl_cloth_desc;
+/* Every hfl_cloth_* call takes the table twice: descs_host (HOST memory, batch rows) is checked before anything runs --
+ * 2 <= width, height, width * height <= HFL_CLOTH_MAX_PARTICLES, the cloth inside [0, n_cells), finite ox, oy, u0, else
+ * HFL_EINVAL -- and descs is the same table in device memory, which the kernels read.
+ *
+ * terrain (n_cells) receives every particle's terrain value t: -z of the point that maps to the particle
+ * (col = int((x - ox) / r + 0.5), likewise row, clamped into the cloth) with the smallest squared horizontal distance to
+ * it, ties to the lowest point index -- one 64-bit integer atomic min per point on keys (n_cells, scratch), exact and
+ * order-independent -- and for a particle no point maps to, the value of the rastered particle the definition names
+ * (same row towards larger i, then smaller i, same column towards smaller j, then larger j, then the nearest in index
+ * distance with ties to the lowest j, then i).  A memset and two launches on `stream`. */
+int hfl_cloth_raster(float* terrain, uint64_t* keys, const hfl_cloth_desc* descs_host, const hfl_cloth_desc* descs, int batch,
+                     int64_t n_cells, const float* points, const int64_t* cloud_offsets, int64_t n_points, float resolution,
+                     hfl_stream_t stream);
+/* The simulation and (slope_smooth != 0) the slope smoothing, one workgroup per cloud with its state in LDS: heights
+ * (n_cells) fp32 receives u, movable (n_cells) uint8 the flags and steps_run (batch) the number of steps.  f_one and f_two
+ * are the one- and two-sided pair factors, gravity_step = -(0.2 dt^2) and velocity_keep = 1 - damping, all rounded to
+ * fp32 by the caller.  One launch on `stream`; no workgroup waits for another. */
+int hfl_cloth_simulate(float* heights, uint8_t* movable, int32_t* steps_run, const float* terrain,
+                       const hfl_cloth_desc* descs_host, const hfl_cloth_desc* descs, int batch, int64_t n_cells, float f_one,
+                       float f_two, float gravity_step, float velocity_keep, int iterations, int slope_smooth,
+                       hfl_stream_t stream);
+/* keep[p] = 0 where point p is ground -- |(-z) - h| < threshold, h the bilinear cloth height at the point -- else 1.
+ * One launch on `stream`.  Non-finite coordinates: undefined values, nothing out of bounds. */
+int hfl_cloth_classify(uint8_t* keep, const float* heights, const hfl_cloth_desc* descs_host, const hfl_cloth_desc* descs,
+                       int batch, int64_t n_cells, const float* points, const int64_t* cloud_offsets, int64_t n_points,
+                       float resolution, float threshold, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 3. Octree convolution gather  (ocnn.nn.OctreeConv's octree2col; call sites
  *    models/layers/octformer_layers.py:89-95, models/octformer_backbone.py:470-475)
  * ---------------------------------------------------------------------- */
