@@ -45,7 +45,7 @@ class RelayBlockWeights(ctypes.Structure):
                 ('norm1_gamma', c_void_p), ('norm1_beta', c_void_p), ('norm2_gamma', c_void_p), ('norm2_beta', c_void_p),
                 ('qkv_w', c_void_p), ('proj_w', c_void_p), ('fc1_w', c_void_p), ('fc2_w', c_void_p),
                 ('qkv_b', c_void_p), ('proj_b', c_void_p), ('fc1_b', c_void_p), ('fc2_b', c_void_p), ('mlp_pack', c_void_p),
-                ('qkv_pack', c_void_p)]
+                ('qkv_pack', c_void_p), ('relay_pack', c_void_p)]
 
 
 class RelayBlockIO(ctypes.Structure):
@@ -192,6 +192,10 @@ SIGNATURES = {
     'hfl_block_attention_x3_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'hfl_relay_block_forward_x3_arena': (c_int64, [c_int64, c_int64]),
     'hfl_relay_block_forward_x3': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'hfl_relay_block_fused_ok': (c_int, [c_void_p, c_void_p]),
+    'hfl_relay_block_fused_x3': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'hfl_relay_block_pack_bytes': (c_int64, [c_int]),
+    'hfl_relay_block_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'hfl_linear_x3_grouped': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
     'hfl_linear_x3_grouped_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                      c_int, c_void_p]),

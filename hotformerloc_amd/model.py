@@ -110,7 +110,14 @@ _ATTN_WS = True
 _ATTN_WS_MIN_ROWS = 40000
 _ATTN_WS_EARLY = False         # keep the early-phase schedule beside it
 _MERGED_ATTN = True            # window attention of an iteration's levels as one launch
-_NATIVE_BLOCK = True           # inference blocks as one native call (hfl_block_forward_x3)
+# Inference blocks as one native call (hfl_block_forward_x3, hfl_relay_block_forward_x3); False: the same launches issued one
+# by one through the Python wrappers.  The flag says WHO issues a block's launches, not which kernels run: where the
+# relay-token block is ONE launch (_RELAY_FUSED) there is nothing to issue one by one, and both settings run that launch.
+_NATIVE_BLOCK = True
+# The relay-token block as ONE launch (hfl_relay_block_fused_x3, csrc/relay_block.hip) where hfl_relay_block_fused_ok takes the
+# shape (C = 256, 16 heads, at most 64 relay tokens per cloud); False: the five launches of hfl_relay_block_forward_x3
+# everywhere (and then _NATIVE_BLOCK = False issues those five through the Python wrappers).
+_RELAY_FUSED = True
 
 
 def set_train_split(enabled: bool):
@@ -236,6 +243,22 @@ def _qkv_pack(att: 'OctreeAttention', rows: int):
         return None
     w = lin.weight
     return derived('qkvpack', (w,), lambda: ops.qkv_fused_pack(w))
+
+
+def _relay_pack(att: 'RTAttention', mlp: 'MLP'):
+    """Weight image of the one-launch relay-token block (csrc/relay_block.hip), or None when the launch does not apply
+    (C = 256 with 16 heads, every bias present).  Cached per parameter set like `_mlp_pack`."""
+    lins = (att.qkv, att.proj, mlp.fc1, mlp.fc2)
+    c = att.dim
+    if not (c == 256 and att.num_heads == 16 and mlp.fc1.out_features == 4 * c and all(l.bias is not None for l in lins)):
+        return None
+    ws = tuple(l.weight for l in lins)
+    return derived('relaypack', ws, lambda: ops.relay_block_pack(*ws))
+
+
+def _relay_fused_wanted(plan) -> bool:
+    """The one-launch relay-token block is switched on and this batch is one it takes (hfl_relay_block_fused_ok's length rule)."""
+    return _RELAY_FUSED and plan.max_seq_len <= 64
 
 
 def _block_tail_x3(x, attn_out2, attn: 'OctreeAttention', norm2: nn.LayerNorm, mlp: 'MLP', fused_any_rows: bool = False):
@@ -1059,8 +1082,9 @@ class RelayTokenTransformerBlock(nn.Module):
         self.drop_path = OctreeDropPath(drop_path)
         _init_layer_scale(self, dim, layer_scale)                       # hotformerloc_backbone.py:260-272
 
-    def _native_static(self, device):
-        """(RelayBlockWeights, tensors it points to) or None, cached and revalidated like _native_block_static."""
+    def _native_static(self, device, with_relay_pack: bool):
+        """(RelayBlockWeights, tensors it points to) or None, cached and revalidated like _native_block_static.
+        `with_relay_pack`: also the weight image of the one-launch block (built only for callers that can use it)."""
         att, mlp = self.rt_attention, self.mlp
         plist = (self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, att.qkv.bias, att.proj.bias,
                  mlp.fc1.bias, mlp.fc2.bias, att.qkv.weight, att.proj.weight, mlp.fc1.weight, mlp.fc2.weight)
@@ -1076,17 +1100,20 @@ class RelayTokenTransformerBlock(nn.Module):
             mpack = _mlp_pack(mlp, _MLP_FUSED_MIN_ROWS)
             # (LN1 -> qkv as one launch and the attention writing proj's operand: six launches -> three, see forward)
             qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS)
-            keep = (_w2(att.qkv), _w2(att.proj), _w2(mlp.fc1), _w2(mlp.fc2), mpack, qpack)
+            # (the whole block as one launch: csrc/relay_block.hip)
+            rpack = _relay_pack(att, mlp) if with_relay_pack else None
+            keep = (_w2(att.qkv), _w2(att.proj), _w2(mlp.fc1), _w2(mlp.fc2), mpack, qpack, rpack)
             w = RelayBlockWeights(channels=att.dim, n_heads=att.num_heads, eps=self.norm1.eps,
                                   mlp_pack=None if mpack is None else mpack.data_ptr(),
                                   qkv_pack=None if qpack is None else qpack.data_ptr(),
+                                  relay_pack=None if rpack is None else rpack.data_ptr(),
                                   norm1_gamma=self.norm1.weight.data_ptr(), norm1_beta=self.norm1.bias.data_ptr(),
                                   norm2_gamma=self.norm2.weight.data_ptr(), norm2_beta=self.norm2.bias.data_ptr(),
                                   qkv_w=keep[0].data_ptr(), proj_w=keep[1].data_ptr(), fc1_w=keep[2].data_ptr(),
                                   fc2_w=keep[3].data_ptr(), qkv_b=att.qkv.bias.data_ptr(), proj_b=att.proj.bias.data_ptr(),
                                   fc1_b=mlp.fc1.bias.data_ptr(), fc2_b=mlp.fc2.bias.data_ptr())
             return w, keep
-        return derived('native-relay', plist, build)
+        return derived(('native-relay', with_relay_pack), plist, build)
 
     def forward_parts(self, parts, plan):
         """forward(torch.cat(parts)) -- without the concatenation launch when the native call can read the rows where they are
@@ -1095,19 +1122,27 @@ class RelayTokenTransformerBlock(nn.Module):
         if (len(parts) <= 4 and _GEMM_MODE == 'x3' and _split_path(p0) and not self.use_layer_scale
                 and not _drops(self) and _NATIVE_BLOCK and ops.KernelTimer.active is None
                 and all(p.dtype == torch.float32 and p.is_contiguous() and p.shape[0] > 0 for p in parts)):
-            static = self._native_static(p0.device)
+            static = self._native_static(p0.device, _relay_fused_wanted(plan))
             if static is not None and static[0].qkv_pack:
                 return ops.relay_block_forward_x3(static[0], static[1], list(parts), plan.seq_rows, plan.seq_off, plan.B,
-                                                  plan.max_seq_len, plan.orphan_rows)
+                                                  plan.max_seq_len, plan.orphan_rows, fused=_RELAY_FUSED)
         return self(torch.cat(list(parts), 0), plan)
 
     def forward(self, rt, plan):
         if _GEMM_MODE == 'x3' and _split_path(rt) and not self.use_layer_scale and not _drops(self) and rt.shape[0] > 0:
-            if _NATIVE_BLOCK and ops.KernelTimer.active is None and rt.dtype == torch.float32 and rt.is_contiguous():
-                static = self._native_static(rt.device)          # the same nine launches from ONE native call
-                if static is not None:
+            if ((_NATIVE_BLOCK or _relay_fused_wanted(plan)) and ops.KernelTimer.active is None and rt.dtype == torch.float32
+                    and rt.is_contiguous()):
+                static = self._native_static(rt.device, _relay_fused_wanted(plan))
+                if static is not None and _NATIVE_BLOCK:           # one launch where it applies, else the launches below
                     return ops.relay_block_forward_x3(static[0], static[1], rt, plan.seq_rows, plan.seq_off, plan.B,
-                                                      plan.max_seq_len, plan.orphan_rows)
+                                                      plan.max_seq_len, plan.orphan_rows, fused=_RELAY_FUSED)
+                if static is not None:
+                    # the launches are issued from Python (_NATIVE_BLOCK off): the one-launch block is the same single launch
+                    # whoever issues it (see the flags); where it does not apply, the Python launch sequence below
+                    out = ops.relay_block_fused_x3(static[0], static[1], rt, plan.seq_rows, plan.seq_off, plan.B,
+                                                   plan.max_seq_len, plan.orphan_rows)
+                    if out is not None:
+                        return out
             att = self.rt_attention
             # LN1 -> qkv as ONE launch (csrc/qkv_fused.hip, output features split over the chip for the ~2 k rows) and the
             # ragged attention reading its fp16 (hi, lo) rows and writing attention.proj's split2 operand itself

@@ -764,10 +764,25 @@ def row_segments(parts):
     return seg, r
 
 
-def relay_block_forward_x3(weights, keep_alive, rt, seq_rows, seq_off, batch: int, max_seq_len: int, orphan_rows=None):
-    """The relay-token transformer block (RTSA) of the inference path in ONE native call (hfl_relay_block_forward_x3).  rt: the
-    (rows, C) relay rows, or a list of up to four tensors whose row-wise concatenation they are (the pyramid levels' relay rows
-    where the levels left them: needs weights.qkv_pack)."""
+def relay_block_pack(w_qkv, w_proj, w_fc1, w_fc2) -> torch.Tensor:
+    """Weight image of the one-launch relay-token block (hfl_relay_block_pack) from the fp32 Linear weights qkv (3C, C), proj
+    (C, C), fc1 (4C, C), fc2 (C, 4C), C = 256: the bf16 (hi, lo) split of `split2_weight`, cut into the 16-feature x 32-k MFMA
+    fragments a wave loads whole.  Once per parameter set."""
+    _dev(w_qkv, w_proj, w_fc1, w_fc2)
+    ws = [_f32c(w.detach()) for w in (w_qkv, w_proj, w_fc1, w_fc2)]
+    c = ws[1].shape[0]
+    assert [tuple(w.shape) for w in ws] == [(3 * c, c), (c, c), (4 * c, c), (c, 4 * c)]
+    lib = _native.load()
+    n = int(lib.hfl_relay_block_pack_bytes(c))
+    if n <= 0:
+        raise _native.NativeLibraryError('hfl_relay_block_pack: unsupported channel count %d' % c)
+    pack = torch.empty(n, dtype=torch.uint8, device=ws[0].device)
+    check(lib.hfl_relay_block_pack(pack.data_ptr(), *(w.data_ptr() for w in ws), c, _stream()), 'hfl_relay_block_pack')
+    return pack
+
+
+def _relay_block_io(rt, seq_rows, seq_off, batch, max_seq_len, orphan_rows):
+    """(hfl_relay_block_io with a fresh `out`, out, what the struct points to) for the relay-token block calls."""
     seg = None
     if isinstance(rt, (list, tuple)):
         seg, rows = row_segments(rt)
@@ -776,14 +791,41 @@ def relay_block_forward_x3(weights, keep_alive, rt, seq_rows, seq_off, batch: in
         _dev(rt)
         (rows, c), dev, x_ptr = rt.shape, rt.device, rt.data_ptr()
     _dev(seq_rows, seq_off, orphan_rows)
-    lib = _native.load()
     out = torch.empty((rows, c), dtype=torch.float32, device=dev)
-    arena = torch.empty(int(lib.hfl_relay_block_forward_x3_arena(rows, c)), dtype=torch.uint8, device=dev)
     io = _native.RelayBlockIO(x_in=x_ptr, x_segments=None if seg is None else ctypes.addressof(seg),
-                              out=out.data_ptr(), arena=arena.data_ptr(), seq_rows=seq_rows.data_ptr(),
+                              out=out.data_ptr(), arena=None, seq_rows=seq_rows.data_ptr(),
                               seq_off=seq_off.data_ptr(), n_rows=rows, batch=batch, max_seq_len=max_seq_len,
                               orphan_rows=None if orphan_rows is None or orphan_rows.numel() == 0 else orphan_rows.data_ptr(),
                               n_orphans=0 if orphan_rows is None else orphan_rows.numel())
+    return io, out, (seg, rt)
+
+
+def relay_block_fused_x3(weights, keep_alive, rt, seq_rows, seq_off, batch: int, max_seq_len: int, orphan_rows=None):
+    """The relay-token transformer block (RTSA) of the inference path as ONE launch (hfl_relay_block_fused_x3, no arena), or
+    None when hfl_relay_block_fused_ok refuses the problem (it takes C = 256, 16 heads, weights.relay_pack, at most 64 relay
+    tokens per cloud).  rt as in `relay_block_forward_x3`."""
+    lib = _native.load()
+    io, out, _keep = _relay_block_io(rt, seq_rows, seq_off, batch, max_seq_len, orphan_rows)
+    if not lib.hfl_relay_block_fused_ok(ctypes.byref(weights), ctypes.byref(io)):
+        return None
+    check(lib.hfl_relay_block_fused_x3(ctypes.byref(weights), ctypes.byref(io), _stream()), 'hfl_relay_block_fused_x3')
+    return out
+
+
+def relay_block_forward_x3(weights, keep_alive, rt, seq_rows, seq_off, batch: int, max_seq_len: int, orphan_rows=None,
+                           fused: bool = True):
+    """The relay-token transformer block (RTSA) of the inference path in ONE native call.  rt: the (rows, C) relay rows, or a
+    list of up to four tensors whose row-wise concatenation they are (the pyramid levels' relay rows where the levels left
+    them: needs weights.qkv_pack).  With `fused`, the one launch of `relay_block_fused_x3` where it applies; otherwise the five
+    launches of hfl_relay_block_forward_x3."""
+    if fused:
+        out = relay_block_fused_x3(weights, keep_alive, rt, seq_rows, seq_off, batch, max_seq_len, orphan_rows)
+        if out is not None:
+            return out
+    lib = _native.load()
+    io, out, _keep = _relay_block_io(rt, seq_rows, seq_off, batch, max_seq_len, orphan_rows)
+    arena = torch.empty(int(lib.hfl_relay_block_forward_x3_arena(io.n_rows, out.shape[1])), dtype=torch.uint8, device=out.device)
+    io.arena = arena.data_ptr()
     check(lib.hfl_relay_block_forward_x3(ctypes.byref(weights), ctypes.byref(io), _stream()), 'hfl_relay_block_forward_x3')
     return out
 

@@ -884,6 +884,8 @@ typedef struct hfl_relay_block_weights {
                                                           (hfl_ln_qkv_fused) and the attention reads its fp16 (hi, lo) rows and
                                                           writes proj's split2 operand itself (hfl_relay_attention_f16_fwd): three
                                                           launches up to proj's input instead of six */
+  const void* relay_pack;                              /* hfl_relay_block_pack image of (qkv, proj, fc1, fc2) or NULL: what
+                                                          hfl_relay_block_fused_x3 reads; hfl_relay_block_forward_x3 ignores it */
 } hfl_relay_block_weights;
 typedef struct hfl_relay_block_io {
   const float* x_in;
@@ -901,6 +903,18 @@ typedef struct hfl_relay_block_io {
 } hfl_relay_block_io;
 int64_t hfl_relay_block_forward_x3_arena(int64_t n_rows, int64_t channels);
 int hfl_relay_block_forward_x3(const hfl_relay_block_weights* w, const hfl_relay_block_io* io, hfl_stream_t stream);
+/* The same block as ONE launch (csrc/relay_block.hip): a workgroup per (cloud, 16-row query tile) and per 16 orphan rows, no
+ * communication between workgroups, arithmetic at every hand-off as in the five launches of hfl_relay_block_forward_x3 (only
+ * f32 summation orders differ).  hfl_relay_block_fused_ok: 1 when the launch takes the problem -- channels = 256, 16 heads,
+ * relay_pack, every bias and LayerNorm parameter present, max_seq_len <= 64.  io->arena is not used.  out must not overlap any
+ * input rows (the other rows of a cloud are read after some were written): HFL_EINVAL.
+ * hfl_relay_block_pack: the weight image (hfl_relay_block_pack_bytes(channels) bytes; 0 = unsupported width) from the fp32
+ * Linear weights qkv (3C, C), proj (C, C), fc1 (4C, C), fc2 (C, 4C): bf16 (hi, lo) MFMA fragments, once per parameter set. */
+int hfl_relay_block_fused_ok(const hfl_relay_block_weights* w, const hfl_relay_block_io* io);
+int hfl_relay_block_fused_x3(const hfl_relay_block_weights* w, const hfl_relay_block_io* io, hfl_stream_t stream);
+int64_t hfl_relay_block_pack_bytes(int channels);
+int hfl_relay_block_pack(void* pack, const float* qkv_w, const float* proj_w, const float* fc1_w, const float* fc2_w, int channels,
+                         hfl_stream_t stream);
 
 /* Weight gradient of an octree convolution over its live (row, tap) pairs (csrc/tapconv.hip; replaces autograd over
  * ocnn's octree2col + mm, models/layers/octformer_layers.py:89-95): dw[k] (cin, cout) = g_k^T dpart_k over the pairs of tap

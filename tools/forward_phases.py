@@ -51,7 +51,8 @@ def main():
     t_init = first(lambda n: 'relay_init' in n)
     if t_init:
         marks.append(('pyramid init (downsamples, relay tokens)', t_init))
-    ra = [int(r['Start_Timestamp']) for r in fwd if 'relay_attn' in r['Kernel_Name']]
+    # (the relay-token block of the iteration: its attention launch, or the one-launch block of csrc/relay_block.hip)
+    ra = [int(r['Start_Timestamp']) for r in fwd if 'relay_attn' in r['Kernel_Name'] or 'relay_block_fused' in r['Kernel_Name']]
     # an iteration starts with the finest level's CPE issued BEFORE its RTSA: take the last cpe_fwd_kernel<64> start before each relay_attn
     prev = t_init or t0
     for i, t in enumerate(ra):
