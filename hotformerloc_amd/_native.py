@@ -60,6 +60,17 @@ class RowSegments(ctypes.Structure):
     _fields_ = [('n', c_int32), ('ptr', c_void_p * 4), ('row0', c_int64 * 4)]
 
 
+# hfl_block_io.phase: which part of a transformer block one hfl_block_forward_x3 call issues
+PHASE_WHOLE = 0         # the whole block
+PHASE_TOKENS = 1        # what reads token rows only: CPE, their LN1 and qkv projection
+PHASE_REST = 2          # the rest: relay rows in, their LN1 / qkv, window attention, proj, MLP
+PHASE_RELAY_QKV = 3     # PHASE_REST up to the window attention: relay rows in, their LN1 / qkv
+PHASE_TAIL = 4          # PHASE_REST after the window attention: proj + residual, MLP
+# bits of hfl_block_weights.fuse_attention (both need qkv_pack): LN1 -> qkv -> window attention as ONE launch ...
+FUSE_ATTN_NO_RELAY = 1  # ... in a whole-block call of a block without relay tokens (csrc/attn_fused.hip)
+FUSE_ATTN_WS = 2        # ... of a relay-token block's token rows (csrc/attn_ws.hip; PHASE_TOKENS is then the CPE alone)
+
+
 class BlockIO(ctypes.Structure):
     """hfl_block_io"""
     _fields_ = [('x_in', c_void_p), ('relay', c_void_p), ('out', c_void_p), ('arena', c_void_p),

@@ -21,7 +21,7 @@ from . import ops
 # Per-module caches of launch state that the encoder keeps in a module's __dict__ (ctypes structures of raw device pointers,
 # HIP streams; the packed weights live in `weight_cache`, keyed by the parameters, so the copy's are its own).  They describe the ORIGINAL's tensors and some cannot be copied at all; the copy rebuilds its
 # own on its first forward.
-_DERIVED_STATE = ('_rtsa_st', '_streams', '_unit_taps', '_drop_path_mods', '_drop_path_cache')
+_DERIVED_STATE = ('_stream_cache', '_unit_taps', '_drop_path_mods', '_drop_path_cache')
 
 
 def _copy_model(model: nn.Module) -> nn.Module:
@@ -29,11 +29,7 @@ def _copy_model(model: nn.Module) -> nn.Module:
     for m in model.modules():
         for name in _DERIVED_STATE:
             if name in m.__dict__:
-                held.append((m, name, m.__dict__[name]))
-                if name == '_streams':
-                    m.__dict__[name] = None            # a constructor-made attribute: keep it, empty
-                else:
-                    del m.__dict__[name]
+                held.append((m, name, m.__dict__.pop(name)))
     try:
         return copy.deepcopy(model)
     finally:

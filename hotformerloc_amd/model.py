@@ -22,6 +22,7 @@ Only the options the shipped configs use are implemented; anything else raises.
 """
 
 import contextlib
+import functools
 import os
 from typing import Dict, List, Optional
 
@@ -33,6 +34,8 @@ from torch.utils.checkpoint import checkpoint
 from . import autograd as ag
 from . import dwconv as hdw
 from . import ops
+from ._native import (BlockWeights, RelayBlockWeights, WindowAttnDesc, FUSE_ATTN_NO_RELAY, FUSE_ATTN_WS, PHASE_WHOLE,
+                      PHASE_TOKENS, PHASE_REST, PHASE_RELAY_QKV, PHASE_TAIL)
 from .plan import WindowPlan
 from .weight_cache import _STORE as _W3_CACHE, derived     # the one store of weight images
 
@@ -111,13 +114,12 @@ _ATTN_WS_MIN_ROWS = 40000
 _ATTN_WS_EARLY = False         # keep the early-phase schedule beside it
 _MERGED_ATTN = True            # window attention of an iteration's levels as one launch
 # Inference blocks as one native call (hfl_block_forward_x3, hfl_relay_block_forward_x3); False: the same launches issued one
-# by one through the Python wrappers.  The flag says WHO issues a block's launches, not which kernels run: where the
-# relay-token block is ONE launch (_RELAY_FUSED) there is nothing to issue one by one, and both settings run that launch.
+# by one through the Python wrappers.  The flag says WHO issues a block's launches, not which kernels run.
 _NATIVE_BLOCK = True
 # The relay-token block as ONE launch (hfl_relay_block_fused_x3, csrc/relay_block.hip) where hfl_relay_block_fused_ok takes the
-# shape (C = 256, 16 heads, at most 64 relay tokens per cloud); False: the five launches of hfl_relay_block_forward_x3
-# everywhere (and then _NATIVE_BLOCK = False issues those five through the Python wrappers).
+# shape (C = 256, 16 heads, at most 64 relay tokens per cloud); False: its five launches everywhere (routes: _native_route).
 _RELAY_FUSED = True
+_Q_PRESCALE = 16 ** -0.5 * 1.4426950408889634    # folded into q for the fp16-MFMA attention kernels: head dim 16's scale x log2 e
 
 
 def set_train_split(enabled: bool):
@@ -254,11 +256,6 @@ def _relay_pack(att: 'RTAttention', mlp: 'MLP'):
         return None
     ws = tuple(l.weight for l in lins)
     return derived('relaypack', ws, lambda: ops.relay_block_pack(*ws))
-
-
-def _relay_fused_wanted(plan) -> bool:
-    """The one-launch relay-token block is switched on and this batch is one it takes (hfl_relay_block_fused_ok's length rule)."""
-    return _RELAY_FUSED and plan.max_seq_len <= 64
 
 
 def _block_tail_x3(x, attn_out2, attn: 'OctreeAttention', norm2: nn.LayerNorm, mlp: 'MLP', fused_any_rows: bool = False):
@@ -746,11 +743,15 @@ class OctreeAttention(nn.Module):
         self.proj = SplitLinear(dim, dim)
         self.rpe = RPE(patch_size, num_heads, dilation) if use_rpe else None
 
-    def core(self, qkv, plan: WindowPlan, depth: int, qkv_bias=None, out_split=False, qkv_f16=False):
+    def _cfg(self, plan: WindowPlan, depth: int) -> dict:
+        """The window-attention problem of this module at one depth, as the keyword arguments of the attention ops."""
         nt = plan.n_tokens[depth]
-        cfg = dict(n_tokens=nt, n_windows=plan.n_windows[depth], patch_size=self.patch_size,
-                   dilation=self.dilation, n_relay=self.rt_per_window, n_heads=self.num_heads,
-                   batch_size=plan.B, rt_row0=nt, depth=depth)
+        return dict(n_tokens=nt, n_windows=plan.n_windows[depth], patch_size=self.patch_size,
+                    dilation=self.dilation, n_relay=self.rt_per_window, n_heads=self.num_heads,
+                    batch_size=plan.B, rt_row0=nt, depth=depth)
+
+    def core(self, qkv, plan: WindowPlan, depth: int, qkv_bias=None, out_split=False, qkv_f16=False):
+        cfg = self._cfg(plan, depth)
         table = None if self.rpe is None else self.rpe.rpe_table
         if _grad_path(qkv):
             return ag.window_attention(qkv, table, plan.meta[depth], **cfg)
@@ -765,36 +766,30 @@ class OctreeAttention(nn.Module):
         """x + attention(LN(x)) on the training path: one fused autograd Function when the shapes allow."""
         C = self.dim
         if _TRAIN_MLP and _x3_train(x, self.qkv, self.proj) and C in ops._LN_CHANNELS and self.proj.bias is not None:
-            nt = plan.n_tokens[depth]
-            cfg = dict(n_tokens=nt, n_windows=plan.n_windows[depth], patch_size=self.patch_size,
-                       dilation=self.dilation, n_relay=self.rt_per_window, n_heads=self.num_heads,
-                       batch_size=plan.B, rt_row0=nt, depth=depth)
             table = None if self.rpe is None else self.rpe.rpe_table
             return ag.ln_attn_residual_x3(x, norm1.weight, norm1.bias, norm1.eps, self.qkv.weight, self.qkv.bias, table,
-                                          plan.meta[depth], cfg, self.proj.weight, self.proj.bias, row_scale)
+                                          plan.meta[depth], self._cfg(plan, depth), self.proj.weight, self.proj.bias, row_scale)
         y = self.forward(_ln(x, norm1), plan, depth)
         return x + (y if row_scale is None else y * row_scale.unsqueeze(1))
 
     def forward_split(self, x, norm1: nn.LayerNorm, plan: WindowPlan, depth: int):
         """LN1 -> qkv -> attention, split-precision path; returns the bf16 operand of `proj`."""
         if _GEMM_MODE == 'x3':         # qkv bias folded into the GEMM epilogue, attention writes split2 rows
-            f16 = ops.window_attention_f16_ok(x.shape[0], self.patch_size, self.dilation,
-                                              self.rt_per_window, self.num_heads, depth)
-            qs = 16 ** -0.5 * 1.4426950408889634
+            f16 = _attn_f16_ok(x.shape[0], self, depth)
             nt = plan.n_tokens[depth]
             qpack = _qkv_pack(self, nt) if (f16 and x.dtype == torch.float32 and x.is_contiguous()) else None
             if qpack is not None:
                 # as hfl_block_forward_x3 does it: LN1 -> qkv of the token rows in one launch, the relay rows through
                 # LayerNorm + the qkv GEMM
                 qkv = torch.empty((x.shape[0], 3 * x.shape[1]), dtype=torch.float32, device=x.device)
-                ops.ln_qkv_fused(x[:nt], norm1.weight, norm1.bias, norm1.eps, qpack, self.qkv.bias, qs, out=qkv[:nt])
+                ops.ln_qkv_fused(x[:nt], norm1.weight, norm1.bias, norm1.eps, qpack, self.qkv.bias, _Q_PRESCALE, out=qkv[:nt])
                 if x.shape[0] > nt:          # the relay rows: the same launch, output features split over the workgroups
-                    ops.ln_qkv_fused(x[nt:], norm1.weight, norm1.bias, norm1.eps, qpack, self.qkv.bias, qs, out=qkv[nt:])
+                    ops.ln_qkv_fused(x[nt:], norm1.weight, norm1.bias, norm1.eps, qpack, self.qkv.bias, _Q_PRESCALE, out=qkv[nt:])
                 return self.core(qkv, plan, depth, out_split=2, qkv_f16=True)
             a2 = ops.layer_norm_split2(x, norm1.weight, norm1.bias, norm1.eps)
             if f16:
                 # the projection writes q, k, v as fp16 (hi, lo) MFMA operands (q pre-scaled): fp16-MFMA window kernel
-                qkv = ops.linear_x3_qkv(a2, _w2(self.qkv), self.qkv.bias, qs)
+                qkv = ops.linear_x3_qkv(a2, _w2(self.qkv), self.qkv.bias, _Q_PRESCALE)
                 return self.core(qkv, plan, depth, out_split=2, qkv_f16=True)
             qkv = ops.linear_x3(a2, _w2(self.qkv), bias=self.qkv.bias)
             return self.core(qkv, plan, depth, out_split=2)
@@ -808,6 +803,19 @@ def _drops(block) -> bool:
     return block.training and block.drop_path.drop_prob > 0.0
 
 
+def _fused_inference(block, x) -> bool:
+    """Eligibility for the hand-written inference path, first layer: the fused split-precision kernels apply to this block on
+    these rows (they know neither layer scale nor stochastic depth)."""
+    return _split_path(x) and not block.use_layer_scale and not _drops(block)
+
+
+def _native_rows(block, x) -> bool:
+    """... second layer: the block's 'x3' launches can go out on the raw pointers of these rows, from a native call or as one
+    launch (no kernel timer: it brackets launches issued from Python).  What one site adds stands there with its reason."""
+    return (_fused_inference(block, x) and _GEMM_MODE == 'x3' and ops.KernelTimer.active is None
+            and x.dtype == torch.float32 and x.is_contiguous())
+
+
 def _init_layer_scale(block, dim, layer_scale):
     """`gamma1` / `gamma2`: learnable channel-wise multipliers of the attention / MLP branches when `layer_scale` is a
     number (models/octformer_backbone.py:214-229), the constant 1 otherwise (not parameters then, as in the reference)."""
@@ -819,17 +827,11 @@ def _init_layer_scale(block, dim, layer_scale):
         block.gamma1 = block.gamma2 = 1
 
 
-_F16_OK_CACHE = {}
+_f16_ok = functools.lru_cache(maxsize=4096)(lambda *key: ops.window_attention_f16_ok(*key))
 
 
 def _attn_f16_ok(rows, att, depth) -> bool:
-    key = (rows, att.patch_size, att.dilation, att.rt_per_window, att.num_heads, depth)
-    hit = _F16_OK_CACHE.get(key)
-    if hit is None:
-        if len(_F16_OK_CACHE) > 4096:
-            _F16_OK_CACHE.clear()
-        hit = _F16_OK_CACHE[key] = ops.window_attention_f16_ok(*key)
-    return hit
+    return _f16_ok(rows, att.patch_size, att.dilation, att.rt_per_window, att.num_heads, depth)
 
 
 def _native_block_static(block, device):
@@ -844,7 +846,6 @@ def _native_block_static(block, device):
              mlp.fc1.weight, mlp.fc2.weight, table)
 
     def build():
-        from ._native import BlockWeights
         # the native call reads raw pointers: every parameter must be what the Python wrappers would have checked (fp32,
         # contiguous, on this device), the biases must exist and the three LayerNorms must share one eps
         ok = (all(p is not None for p in plist[:-1]) and block.norm1.eps == block.norm2.eps == cpe.norm.eps
@@ -852,7 +853,7 @@ def _native_block_static(block, device):
         if not ok:
             return None
         keep = [_w2(att.qkv), _w2(att.proj), None, None]
-        w = BlockWeights(channels=att.dim, eps=block.norm1.eps, q_scale=16 ** -0.5 * 1.4426950408889634,
+        w = BlockWeights(channels=att.dim, eps=block.norm1.eps, q_scale=_Q_PRESCALE,
                          cpe_weight=cpe.conv.weights.data_ptr(), cpe_gamma=cpe.norm.weight.data_ptr(),
                          cpe_beta=cpe.norm.bias.data_ptr(), norm1_gamma=block.norm1.weight.data_ptr(),
                          norm1_beta=block.norm1.bias.data_ptr(), norm2_gamma=block.norm2.weight.data_ptr(),
@@ -864,71 +865,60 @@ def _native_block_static(block, device):
     return derived('native-block', plist, build)
 
 
-def _attn_ws_wanted(att, rows: int, nt: int, n_windows: int, depth: int) -> bool:
-    """Whether a relay-token block of this shape takes the one-launch LN1 -> qkv -> window attention (csrc/attn_ws.hip)."""
-    return (_ATTN_WS and att.rpe is not None and rows > nt >= _ATTN_WS_MIN_ROWS and att.dilation == 1
-            and att.rt_per_window == 1 and ops.attn_ws_ok(nt, n_windows, att.patch_size, att.num_heads, depth, att.dim))
-
-
-def _native_block_call(block, x_in, plan: WindowPlan, depth: int):
-    """A prepared native call for the block's inference forward (ops.BlockCall), or None when this block / launch is not
-    eligible (then the Python sequence of the same kernels runs).  Same kernels, same order, same results; only the host
-    work differs."""
-    att = block.attention
-    C = att.dim
-    if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _split_path(x_in) and ops.KernelTimer.active is None
-            and not block.use_layer_scale and not _drops(block) and not block.cpe.xcpe and C % 128 == 0
-            and x_in.dtype == torch.float32 and x_in.is_contiguous()):
+def _native_block_forms(block, x_in, plan: WindowPlan, depth: int):
+    """DECIDE: whether the block's inference forward on these rows is a native call (else None: the Python sequence of the same
+    kernels runs) and which forms its launches take: (the block's BlockWeights with the forms written in, the cached weight
+    images they point to, the expanded RPE table).  Allocates nothing but those cached images."""
+    # (xCPE is a full convolution + Linear: not in the native call)
+    if not (_NATIVE_BLOCK and _native_rows(block, x_in) and not block.cpe.xcpe):
         return None
-    nt = plan.n_tokens[depth]
-    rows = x_in.shape[0]
-    if not _attn_f16_ok(rows, att, depth):
-        return None
-    static = _native_block_static(block, x_in.device)
+    att, mlp, nt, rows = block.attention, block.mlp, plan.n_tokens[depth], x_in.shape[0]
+    static = _native_block_static(block, x_in.device) if _attn_f16_ok(rows, att, depth) else None
     if static is None:
         return None
     w, keep = static
-    from ._native import WindowAttnDesc
     table = None if att.rpe is None else att.rpe.rpe_table
     bnd = int(0.8 * att.patch_size * att.dilation ** 0.5)
     expanded = None if table is None else ops.rpe_expand(table, att.num_heads, bnd, depth, True)
     if table is not None and expanded is None:
         return None
-    mlp = block.mlp
     qpack = _qkv_pack(att, nt)
     w.qkv_pack = None if qpack is None else qpack.data_ptr()
-    # LN1 -> qkv -> window attention of the blocks without relay tokens (OctFormer stage) as one launch (csrc/attn_fused.hip)
-    w.fuse_attention = 1
-    tables3 = None
-    if qpack is not None and _attn_ws_wanted(att, rows, nt, plan.n_windows[depth], depth):
+    w.fuse_attention, tables3 = FUSE_ATTN_NO_RELAY, None
+    # a relay-token block of this shape takes the one-launch LN1 -> qkv -> window attention (csrc/attn_ws.hip)
+    if (qpack is not None and _ATTN_WS and table is not None and rows > nt >= _ATTN_WS_MIN_ROWS and att.dilation == 1
+            and att.rt_per_window == 1
+            and ops.attn_ws_ok(nt, plan.n_windows[depth], att.patch_size, att.num_heads, depth, att.dim)):
         tables3 = ops.rpe_expand(table, att.num_heads, bnd, depth, 2)
-        w.fuse_attention |= 2
+        w.fuse_attention |= FUSE_ATTN_WS
     w.rpe_tables3 = None if tables3 is None else tables3.data_ptr()
     pack = _mlp_pack(mlp, rows)
-    if pack is not None:
-        w.mlp_pack, w.fc1_w, w.fc2_w = pack.data_ptr(), None, None
-    else:
-        if keep[2] is None:
-            keep[2], keep[3] = _w2(mlp.fc1), _w2(mlp.fc2)
-        w.mlp_pack, w.fc1_w, w.fc2_w = None, keep[2].data_ptr(), keep[3].data_ptr()
+    if pack is None and keep[2] is None:                # the operands of the three-launch form, on first use
+        keep[2], keep[3] = _w2(mlp.fc1), _w2(mlp.fc2)
+    w.mlp_pack = None if pack is None else pack.data_ptr()
+    w.fc1_w, w.fc2_w = (keep[2].data_ptr(), keep[3].data_ptr()) if pack is None else (None, None)
+    return w, (keep, expanded, pack, qpack, tables3), expanded
+
+
+def _native_block_call(block, x_in, plan: WindowPlan, depth: int):
+    """PREPARE: the native call for the block's inference forward (ops.BlockCall) from the decision above, or None when there is
+    none.  Same kernels, same order, same results as the Python sequence; only the host work differs."""
+    forms = _native_block_forms(block, x_in, plan, depth)
+    if forms is None:
+        return None
+    (w, images, expanded), att, nt = forms, block.attention, plan.n_tokens[depth]
     desc = WindowAttnDesc(n_tokens=nt, rt_row0=nt, n_windows=plan.n_windows[depth], patch_size=att.patch_size,
-                          dilation=att.dilation, n_relay=att.rt_per_window, n_heads=att.num_heads, pos_bnd=bnd,
-                          batch_size=plan.B, scale=16 ** -0.5, depth=depth,
-                          rpe_expanded=None if expanded is None else expanded.data_ptr())
-    return ops.BlockCall(w, (keep, expanded, pack, qpack, tables3), x_in, plan.neigh(depth), plan.meta[depth], nt, desc)
-
-
-def _native_block(block, x_in, relay, plan: WindowPlan, depth: int):
-    """The block's inference forward as ONE native call, or None when not eligible (see _native_block_call)."""
-    call = _native_block_call(block, x_in, plan, depth)
-    return None if call is None else call.run(0, relay)
+                          dilation=att.dilation, n_relay=att.rt_per_window, n_heads=att.num_heads,
+                          pos_bnd=int(0.8 * att.patch_size * att.dilation ** 0.5), batch_size=plan.B, scale=16 ** -0.5,
+                          depth=depth, rpe_expanded=None if expanded is None else expanded.data_ptr())
+    return ops.BlockCall(w, images, x_in, plan.neigh(depth), plan.meta[depth], nt, desc)
 
 
 def _block_body(block, x, plan: WindowPlan, depth: int, with_relay: bool):
     """What OctFormerBlock and HOTFormerBlock do after their CPE heads: x + attention(LN1(x)), then x + mlp(LN2(x)), on the
     first path that applies (the order is the behaviour: the split path is tested before layer scale, and so on down).
     with_relay: x is the [tokens | relay rows] buffer of a HOTFormer level."""
-    if _split_path(x) and not block.use_layer_scale and not _drops(block):
+    if _fused_inference(block, x):
         o3 = block.attention.forward_split(x, block.norm1, plan, depth)
         return _block_tail_split(x, o3, block.attention, block.norm2, block.mlp)
     if block.use_layer_scale:
@@ -964,10 +954,9 @@ class OctFormerBlock(nn.Module):
         _init_layer_scale(self, dim, layer_scale)
 
     def forward(self, x, plan: WindowPlan, depth: int):
-        if not _grad_path(x):
-            y = _native_block(self, x, None, plan, depth)
-            if y is not None:
-                return y
+        call = _native_block_call(self, x, plan, depth)
+        if call is not None:                        # the block as ONE native call (never on the training path)
+            return call.run(PHASE_WHOLE)
         x = self.cpe(x, plan, depth, residual=True)
         return _block_body(self, x, plan, depth, with_relay=False)
 
@@ -1040,9 +1029,9 @@ class HOTFormerBlock(nn.Module):
             else:
                 buf = torch.cat([self.cpe(buf[:nt], plan, depth, residual=True), buf[nt:] if relay is None else relay], 0)
         else:                                   # CPE writes straight into the new buffer's token rows
-            y = _native_block(self, buf, relay, plan, depth)
-            if y is not None:
-                return y
+            call = _native_block_call(self, buf, plan, depth)
+            if call is not None:                    # the block as ONE native call
+                return call.run(PHASE_WHOLE, relay)
             new = torch.empty_like(buf)
             self.cpe(buf[:nt], plan, depth, residual=True, out=new[:nt])
             new[nt:].copy_(buf[nt:] if relay is None else relay)
@@ -1093,7 +1082,6 @@ class RelayTokenTransformerBlock(nn.Module):
             if not (all(p is not None and p.dtype == torch.float32 and p.is_contiguous() and p.device == device for p in plist)
                     and self.norm1.eps == self.norm2.eps and att.dim % 128 == 0 and att.num_heads * 16 == att.dim):
                 return None
-            from ._native import RelayBlockWeights
             # (the MLP branch as the fused launch with the hidden dimension split over the chip: 27 us against 48 us for the
             # three launches alone, and inside the step the relay tokens' fc2 -- K = 1024 over 28 workgroups -- took 120 us:
             # 2361 -> 2417 clouds/s, three alternating runs each)
@@ -1115,43 +1103,44 @@ class RelayTokenTransformerBlock(nn.Module):
             return w, keep
         return derived(('native-relay', with_relay_pack), plist, build)
 
+    def _native_route(self, rows, plan):
+        """The native and one-launch routes of the inference forward on the (n, C) relay rows, or on the list of tensors whose
+        concatenation they are (hfl_relay_block_io.x_segments); None: the Python launch sequence of `forward` runs.
+        With `_native_rows`, non-empty rows (the kernels take no empty launch) and qualifying parameters:
+            _NATIVE_BLOCK on                                    ops.relay_block_forward_x3(..., fused=_RELAY_FUSED)
+            _NATIVE_BLOCK off, one launch wanted and accepted   that single launch (the same one, whoever issues it)
+            otherwise                                           None"""
+        parts = rows if isinstance(rows, list) else (rows,)
+        fused = _RELAY_FUSED and plan.max_seq_len <= 64  # wanted, and a batch it takes (hfl_relay_block_fused_ok's length rule)
+        if not ((_NATIVE_BLOCK or fused) and all(p.shape[0] > 0 and _native_rows(self, p) for p in parts)):
+            return None
+        static = self._native_static(parts[0].device, fused)
+        # (the row-segment table is read by the fused LN1 -> qkv launch and by proj's residual)
+        if static is None or (parts is rows and not static[0].qkv_pack):
+            return None
+        args = (static[0], static[1], rows, plan.seq_rows, plan.seq_off, plan.B, plan.max_seq_len, plan.orphan_rows)
+        if _NATIVE_BLOCK:
+            return ops.relay_block_forward_x3(*args, fused=_RELAY_FUSED)
+        return ops.relay_block_fused_x3(*args)              # None where hfl_relay_block_fused_ok refuses the problem
+
     def forward_parts(self, parts, plan):
-        """forward(torch.cat(parts)) -- without the concatenation launch when the native call can read the rows where they are
-        (hfl_relay_block_io.x_segments: the fused LN1 -> qkv launch and proj's residual take a row-segment table)."""
-        p0 = parts[0]
-        if (len(parts) <= 4 and _GEMM_MODE == 'x3' and _split_path(p0) and not self.use_layer_scale
-                and not _drops(self) and _NATIVE_BLOCK and ops.KernelTimer.active is None
-                and all(p.dtype == torch.float32 and p.is_contiguous() and p.shape[0] > 0 for p in parts)):
-            static = self._native_static(p0.device, _relay_fused_wanted(plan))
-            if static is not None and static[0].qkv_pack:
-                return ops.relay_block_forward_x3(static[0], static[1], list(parts), plan.seq_rows, plan.seq_off, plan.B,
-                                                  plan.max_seq_len, plan.orphan_rows, fused=_RELAY_FUSED)
-        return self(torch.cat(list(parts), 0), plan)
+        """forward(torch.cat(parts)), without the concatenation launch where the native call reads the rows in place (<= 4)"""
+        out = self._native_route(list(parts), plan) if _NATIVE_BLOCK and len(parts) <= 4 else None
+        return self(torch.cat(list(parts), 0), plan) if out is None else out
 
     def forward(self, rt, plan):
-        if _GEMM_MODE == 'x3' and _split_path(rt) and not self.use_layer_scale and not _drops(self) and rt.shape[0] > 0:
-            if ((_NATIVE_BLOCK or _relay_fused_wanted(plan)) and ops.KernelTimer.active is None and rt.dtype == torch.float32
-                    and rt.is_contiguous()):
-                static = self._native_static(rt.device, _relay_fused_wanted(plan))
-                if static is not None and _NATIVE_BLOCK:           # one launch where it applies, else the launches below
-                    return ops.relay_block_forward_x3(static[0], static[1], rt, plan.seq_rows, plan.seq_off, plan.B,
-                                                      plan.max_seq_len, plan.orphan_rows, fused=_RELAY_FUSED)
-                if static is not None:
-                    # the launches are issued from Python (_NATIVE_BLOCK off): the one-launch block is the same single launch
-                    # whoever issues it (see the flags); where it does not apply, the Python launch sequence below
-                    out = ops.relay_block_fused_x3(static[0], static[1], rt, plan.seq_rows, plan.seq_off, plan.B,
-                                                   plan.max_seq_len, plan.orphan_rows)
-                    if out is not None:
-                        return out
-            att = self.rt_attention
+        att, out = self.rt_attention, self._native_route(rt, plan)
+        if out is not None:
+            return out
+        # (the launch sequence below is made of the 'x3' kernels, which take no empty launch)
+        if _fused_inference(self, rt) and _GEMM_MODE == 'x3' and rt.shape[0] > 0:
             # LN1 -> qkv as ONE launch (csrc/qkv_fused.hip, output features split over the chip for the ~2 k rows) and the
             # ragged attention reading its fp16 (hi, lo) rows and writing attention.proj's split2 operand itself
             # (hfl_relay_attention_f16_fwd): LayerNorm, qkv GEMM, memset, attention, split2 -> two launches.  The block is a
             # chain of tiny launches on the cycle every H-OSA iteration waits for (DESIGN.md, round 5).
             qpack = _qkv_pack(att, _QKV_FUSED_MIN_ROWS)
             if qpack is not None:
-                qkv = ops.ln_qkv_fused(rt, self.norm1.weight, self.norm1.bias, self.norm1.eps, qpack, att.qkv.bias,
-                                       0.25 * 1.4426950408889634)
+                qkv = ops.ln_qkv_fused(rt, self.norm1.weight, self.norm1.bias, self.norm1.eps, qpack, att.qkv.bias, _Q_PRESCALE)
                 o2 = ops.relay_attention_f16(qkv, plan.seq_rows, plan.seq_off, plan.B, att.num_heads, plan.max_seq_len,
                                              plan.orphan_rows)
             else:
@@ -1163,7 +1152,6 @@ class RelayTokenTransformerBlock(nn.Module):
             bid = plan.relay_cloud()
             rt = rt + self.drop_path(self.gamma1 * self.rt_attention(_ln(rt, self.norm1), plan), bid, plan.B)
             return rt + self.drop_path(self.gamma2 * self.mlp(_ln(rt, self.norm2)), bid, plan.B)
-        att = self.rt_attention
         if _x6_path(rt, att.qkv, att.proj, self.mlp.fc1, self.mlp.fc2) and rt.shape[-1] in ops._LN_CHANNELS:
             o = ops.relay_attention(att.qkv(_ln(rt, self.norm1)), plan.seq_rows, plan.seq_off, plan.B, att.num_heads,
                                     plan.max_seq_len)
@@ -1199,6 +1187,43 @@ class ADaPE(nn.Module):
 
     def forward(self, plan: WindowPlan, depth: int):
         return self.mlp(plan.window_stats[depth])
+
+
+class _PyramidLevels:
+    """What a HOTFormerStage forward carries from H-OSA iteration to iteration, per pyramid level j (depth depths[j]): the token
+    counts `nts`, the [tokens | relay] buffers `bufs[d]`, the relay rows as RTSA sees them `rts[d]` (each level's own rows or,
+    with per-level widths, their projection to the widest level), whether the blocks are checkpointed, and which levels are
+    `small`: the ones that run on side streams.  The early schedule adds its streams, calls and outputs (`_run_early`)."""
+
+    def __init__(self, stage, plan: WindowPlan, depths, bufs, ckpt: bool):
+        self.stage, self.plan, self.depths, self.bufs, self.ckpt = stage, plan, depths, bufs, ckpt
+        self.proj = stage.use_projections
+        self.nts = [plan.n_tokens[d] for d in depths]
+        self.rts = {d: (stage.init_up_projections[j](bufs[d][nt:]) if self.proj else bufs[d][nt:])          # 585-591
+                    for j, (d, nt) in enumerate(zip(depths, self.nts))}
+        self.small = [j > 0 and bufs[d].shape[0] <= _SIDE_STREAM_MAX_ROWS for j, d in enumerate(depths)]
+
+    def rtsa(self, i):
+        """RTSA of iteration i over all levels' relay rows: (its rows, the fresh relay rows of every depth)"""
+        blk, parts = self.stage.rtsa_blocks[i], [self.rts[d] for d in self.depths]
+        rt_all = _checkpoint_block(blk, torch.cat(parts, 0), self.plan) if self.ckpt else blk.forward_parts(parts, self.plan)
+        off, nw = self.plan.rt_offset, self.plan.n_windows                      # 596-601
+        return rt_all, {d: rt_all[off[d]:off[d] + nw[d]] for d in self.depths}
+
+    def relay_in(self, j, i, fresh_d):
+        """a level's fresh relay rows at the level's own width (the down-projection of per-level-width configurations)"""
+        return self.stage.down_projections[j][i](fresh_d) if self.proj else fresh_d
+
+    def hand_over(self, j, i, out):
+        """block i's output becomes level j's buffer, its relay rows (up-projected) what RTSA i + 1 reads"""
+        d, relay = self.depths[j], out[self.nts[j]:]
+        self.bufs[d], self.rts[d] = out, (self.stage.up_projections[j][i](relay) if self.proj else relay)
+
+    def hosa(self, j, i, fresh_d):
+        """down-projection -> H-OSA block -> up-projection of one level (610-630)"""
+        blk, d, rin = self.stage.hosa_blocks[j][i], self.depths[j], self.relay_in(j, i, fresh_d)
+        out = _checkpoint_block(blk, self.bufs[d], self.plan, d, rin) if self.ckpt else blk(self.bufs[d], self.plan, d, rin)
+        self.hand_over(j, i, out)
 
 
 class HOTFormerStage(nn.Module):
@@ -1261,19 +1286,16 @@ class HOTFormerStage(nn.Module):
                     self.rt_adape_projections = nn.ModuleList([nn.Linear(Cm, channels[j]) for j in range(L)])
         self.downsamples = nn.ModuleList([Downsample(channels[j], channels[j + 1], conv_norm)
                                           for j in range(L - 1)])
-        self._streams = None
 
-    def _side_streams(self, device):
-        if self._streams is None:
-            self._streams = [torch.cuda.Stream(device=device) for _ in range(self.num_pyramid_levels - 1)]
-        return self._streams
-
-    def _rtsa_stream(self, device):
-        if self.__dict__.get('_rtsa_st') is None:
+    def _streams(self, device):
+        """(side streams of the coarser levels, RTSA's stream), made on first use (`ema._DERIVED_STATE`: not part of a copy)"""
+        made = self.__dict__.get('_stream_cache')
+        if made is None:
+            side = [torch.cuda.Stream(device=device) for _ in range(self.num_pyramid_levels - 1)]
             # high priority: RTSA is a chain of eight tiny launches that must slip in between the chip-filling kernels of the
             # token-row phase; at equal priority each of them queues behind a full round of workgroups
-            self.__dict__['_rtsa_st'] = torch.cuda.Stream(device=device, priority=-1)
-        return self.__dict__['_rtsa_st']
+            made = self.__dict__['_stream_cache'] = (side, torch.cuda.Stream(device=device, priority=-1))
+        return made
 
     def _forward_without_relay_tokens(self, data, plan: WindowPlan, depths):
         feats = {depths[0]: data}
@@ -1290,7 +1312,6 @@ class HOTFormerStage(nn.Module):
         depths = [depth - j for j in range(self.num_pyramid_levels)]
         if self.disable_rt:
             return self._forward_without_relay_tokens(data, plan, depths)
-        octree = plan.octree
         feats = {depths[0]: data}
         bufs: Dict[int, torch.Tensor] = {}
         proj = self.use_projections
@@ -1302,177 +1323,156 @@ class HOTFormerStage(nn.Module):
                 rt = rt + (self.rt_adape_projections[j](pe) if proj else pe)
             bufs[d] = torch.cat([feats[d], rt], 0)
             if j < self.num_pyramid_levels - 1:
-                feats[d - 1] = self.downsamples[j](feats[d], octree, d)
-        nts = [plan.n_tokens[d] for d in depths]
-        # relay rows as RTSA sees them: each level's own rows, or (per-level widths) their projection to the widest level
-        rts = {d: (self.init_up_projections[j](bufs[d][nt:]) if proj else bufs[d][nt:])          # 585-591
-               for j, (d, nt) in enumerate(zip(depths, nts))}
+                feats[d - 1] = self.downsamples[j](feats[d], plan.octree, d)
         ckpt = _use_checkpoint(self, sum(b.shape[0] * b.shape[1] for b in bufs.values()), self.num_blocks, data.device)
+        st = _PyramidLevels(self, plan, depths, bufs, ckpt)
+        getattr(self, '_run_' + self._schedule(bufs[depths[0]], plan, depths[0], ckpt))(st)               # 593-633
+        return {d: st.bufs[d][:nt] for d, nt in zip(depths, st.nts)}, st.rts
 
-        def hosa(j, d, i, buf, fresh_d):
-            """down-projection -> H-OSA block -> up-projection of one level (610-630); returns (buffer, relay rows for RTSA)"""
-            blk = self.hosa_blocks[j][i]
-            rin = self.down_projections[j][i](fresh_d) if proj else fresh_d
-            out = _checkpoint_block(blk, buf, plan, d, rin) if ckpt else blk(buf, plan, d, rin)
-            nt = plan.n_tokens[d]
-            return out, (self.up_projections[j][i](out[nt:]) if proj else out[nt:])
-
-        early = _EARLY_PHASE and _PYRAMID_STREAMS and not _grad_path(data) and data.is_cuda and not ckpt
-        if early and not _ATTN_WS_EARLY and self._finest_level_fuses_attention(bufs[depths[0]], plan, depths[0]):
+    def _schedule(self, buf, plan: WindowPlan, depth: int, ckpt: bool) -> str:
+        """Which schedule the H-OSA iterations of this forward run on ('early' | 'forked' | 'sequential'; the same kernels on
+        the same rows in each).  buf: the finest level's [tokens | relay] buffer, depth: its depth."""
+        streams = _PYRAMID_STREAMS and not _grad_path(buf) and buf.is_cuda
+        if _EARLY_PHASE and streams and not ckpt:
             # The finest level's LN1 -> qkv -> window attention is ONE launch there (csrc/attn_ws.hip) and needs the relay
             # rows: nothing but its CPE could run beside the relay-token block, and the persistent launch starves the coarse
             # levels' early phases.  RTSA first, then the levels side by side: +2-4 % on three boxes
             # (profiles/r05_w_ab_attn_ws_default.log); with the early phases kept the one-launch form gains nothing.
-            early = False
-        return self._iterations(data, plan, depths, bufs, rts, nts, proj, ckpt, early, hosa)
+            if _ATTN_WS_EARLY or not self._finest_level_fuses_attention(buf, plan, depth):
+                return 'early'
+        return 'forked' if streams and not _SERIAL_STREAMS else 'sequential'
 
     def _finest_level_fuses_attention(self, buf, plan: WindowPlan, depth: int) -> bool:
-        """The conditions under which _native_block_call gives the finest level's blocks the one-launch attention branch
-        (without preparing a call)."""
-        blk = self.hosa_blocks[0][0]
-        att = blk.attention
-        nt = plan.n_tokens[depth]
-        if not (_NATIVE_BLOCK and _GEMM_MODE == 'x3' and _split_path(buf) and ops.KernelTimer.active is None
-                and not blk.use_layer_scale and not _drops(blk) and not blk.cpe.xcpe and buf.dtype == torch.float32
-                and _attn_f16_ok(buf.shape[0], att, depth)):
-            return False
-        return _attn_ws_wanted(att, buf.shape[0], nt, plan.n_windows[depth], depth) and _qkv_pack(att, nt) is not None
+        """The native call of the finest level's blocks takes the one-launch LN1 -> qkv -> window attention branch."""
+        forms = _native_block_forms(self.hosa_blocks[0][0], buf, plan, depth)
+        return forms is not None and bool(forms[0].fuse_attention & FUSE_ATTN_WS)
 
-    def _iterations(self, data, plan, depths, bufs, rts, nts, proj, ckpt, early, hosa):
-        done = None          # early schedule: per-level end-of-iteration events of the previous iteration
-        first = None         # ... and the buffers the schedule started from (allocated on the main stream, read by the others)
-        for i in range(self.num_blocks):                                # 593-633
-            if early:
-                # RTSA of iteration i only feeds the relay rows: what a block does with its TOKEN rows before the window
-                # attention (CPE, LN1, qkv projection: a third of the block) does not wait for it.  Every level issues that
-                # part on its own stream first, RTSA runs beside it on a stream of its own, the rest of the block follows
-                # once both are done -- the ~120 us chain of eight tiny RTSA launches leaves the critical path.
-                main = torch.cuda.current_stream()
-                side = [main] * (len(depths) - 1) if _SERIAL_STREAMS else self._side_streams(data.device)
-                rs = main if _SERIAL_STREAMS else self._rtsa_stream(data.device)
-                small = [not (j == 0 or bufs[d].shape[0] > _SIDE_STREAM_MAX_ROWS) for j, d in enumerate(depths)]
-                sts = [side[j - 1] if small[j] else main for j in range(len(depths))]
-                # issue order = critical path first (the host runs only just ahead of the GPU here): the finest level's
-                # token phase, RTSA, then the small levels
-                order = sorted(range(len(depths)), key=lambda j: -bufs[depths[j]].shape[0])
-                # Who waits for whom.  A level's block i needs that level's block i - 1 (stream order) and, for its relay rows,
-                # RTSA i; RTSA i needs every level's block i - 1.  Nothing else: in particular the finest level's CPE / LN1 /
-                # qkv of iteration i do not wait for the coarse levels' MLP launches of iteration i - 1, which run (starved)
-                # beside and after the finest level's chip-filling fused MLP -- with a join of all streams at the end of every
-                # iteration (the schedule of rounds 2-3, since removed) the finest level's queue stood idle ~80 us per
-                # iteration there (kernel trace, profiles/r04_phases_iteration_timeline_join.log).
-                join = done is None
-                ev0 = main.record_event() if join else None
-                if first is None:
-                    first = (dict(bufs), dict(rts))
-                calls = {}
+    def _run_sequential(self, st: _PyramidLevels):
+        """RTSA, then the levels one after the other, all on the current stream."""
+        for i in range(self.num_blocks):
+            _, fresh = st.rtsa(i)
+            for j, d in enumerate(st.depths):
+                st.hosa(j, i, fresh[d])
 
-                def phase1(j):
-                    d = depths[j]
-                    if join and sts[j] is not main:
-                        sts[j].wait_event(ev0)
-                    with torch.cuda.stream(sts[j]):
-                        calls[d] = _native_block_call(self.hosa_blocks[j][i], bufs[d], plan, d)
-                        if calls[d] is not None:
-                            calls[d].run(1)
+    def _run_forked(self, st: _PyramidLevels):
+        """RTSA, then the levels side by side: the three depths are independent inside an iteration (the reference runs them on
+        three CUDA streams too, hotformerloc_backbone.py:604-633): the coarse depths' small GEMMs and kernels overlap the fine
+        depth's.  Fork/join discipline: side streams wait for the main stream's event, the main stream waits for theirs.
+        Only SMALL depths go to a side stream (_SIDE_STREAM_MAX_ROWS): they are the ones that cannot fill 256 CUs, and
+        hipBLASLt's stream-K GEMMs (workgroups that wait on their peers' partial tiles) dead-lock when several chip-filling
+        ones share the CUs."""
+        main = torch.cuda.current_stream()
+        side = self._streams(st.bufs[st.depths[0]].device)[0]
+        forked = [j for j, small in enumerate(st.small) if small]
+        for i in range(self.num_blocks):
+            rt_all, fresh = st.rtsa(i)
+            keep = [(st.bufs[st.depths[j]], rt_all) for j in forked]   # inputs allocated on the main stream live until the join
+            for j in forked:
+                side[j - 1].wait_stream(main)
+                with torch.cuda.stream(side[j - 1]):
+                    st.hosa(j, i, fresh[st.depths[j]])
+            for j, d in enumerate(st.depths):
+                if j not in forked:
+                    st.hosa(j, i, fresh[d])
+            for j in forked:
+                main.wait_stream(side[j - 1])
+            del keep
 
-                phase1(order[0])
-                if join:
-                    rs.wait_event(ev0)
+    def _run_early(self, st: _PyramidLevels):
+        """RTSA of iteration i only feeds the relay rows: what a block does with its TOKEN rows before the window attention (CPE,
+        LN1, qkv projection: a third of the block) does not wait for it.  Every level issues that part on its own stream first,
+        RTSA runs beside it on a stream of its own, the rest of the block follows once both are done -- the ~120 us chain of
+        eight tiny RTSA launches leaves the critical path.
+        Who waits for whom.  A level's block i needs that level's block i - 1 (stream order) and, for its relay rows, RTSA i;
+        RTSA i needs every level's block i - 1.  Nothing else: in particular the finest level's CPE / LN1 / qkv of iteration i
+        do not wait for the coarse levels' MLP launches of iteration i - 1, which run (starved) beside and after the finest
+        level's chip-filling fused MLP -- with a join of all streams at the end of every iteration (the schedule of rounds 2-3,
+        since removed) the finest level's queue stood idle ~80 us per iteration there (kernel trace,
+        profiles/r04_phases_iteration_timeline_join.log)."""
+        st.main = main = torch.cuda.current_stream()
+        side, st.rs = ([main] * len(st.small), main) if _SERIAL_STREAMS else self._streams(st.bufs[st.depths[0]].device)
+        st.sts = [side[j - 1] if small else main for j, small in enumerate(st.small)]
+        # issue order = critical path first (the host runs only just ahead of the GPU): finest level's token phase, RTSA, the rest
+        st.order = sorted(range(len(st.small)), key=lambda j: -st.bufs[st.depths[j]].shape[0])
+        done = None          # per-stream end-of-iteration events of the previous iteration
+        first = (dict(st.bufs), dict(st.rts))    # the buffers the schedule started from (allocated on main, read by the others)
+        for i in range(self.num_blocks):
+            ev0 = main.record_event() if done is None else None         # first iteration: everybody joins the main stream
+            st.calls, st.outs = {}, {}
+            self._token_phase(st, i, st.order[0], ev0)
+            for ev in ([ev0] if done is None else done):                # RTSA i, beside it: after every level's block i - 1
+                st.rs.wait_event(ev)
+            with torch.cuda.stream(st.rs):
+                rt_all, fresh = st.rtsa(i)
+                ev_rt = st.rs.record_event()
+            for j in st.order[1:]:
+                self._token_phase(st, i, j, ev0)
+            old = (dict(st.bufs), dict(st.rts))        # buffers other streams still read stay alive until the join
+            # The levels on SIDE streams (the small ones: 2 k and 14 k rows in the bench) send their window attention out as
+            # ONE launch: their windows are one or two per workgroup, latency-bound launches of 14 and 21 us alone.  The
+            # join is between those side streams only.  (Measured alternatives: all three levels in one launch joined
+            # on the main stream -3.5 % of the step; the small levels back to back on one side stream -3 %.)
+            # (blocks on the one-launch LN1 -> qkv -> attention path have no separate attention launch to merge)
+            group = [j for j in st.order if st.small[j] and st.calls[st.depths[j]] is not None
+                     and not st.calls[st.depths[j]].weights.fuse_attention & FUSE_ATTN_WS] if _MERGED_ATTN else []
+            group = group if len(group) >= 2 else []
+            self._relay_phase(st, i, fresh, ev_rt, group)
+            if group:
+                self._tails(st, i, group, self._merged_attention(st, group))
+            done = self._hand_over(st, i)
+            del old, fresh, rt_all, st.calls, st.outs
+
+    def _token_phase(self, st, i, j, ev0):
+        """level j's token-row half of block i (PHASE_TOKENS) on the level's stream"""
+        d = st.depths[j]
+        if ev0 is not None and st.sts[j] is not st.main:
+            st.sts[j].wait_event(ev0)
+        with torch.cuda.stream(st.sts[j]):
+            call = st.calls[d] = _native_block_call(self.hosa_blocks[j][i], st.bufs[d], st.plan, d)
+            if call is not None:
+                call.run(PHASE_TOKENS)
+
+    def _relay_phase(self, st, i, fresh, ev_rt, group):
+        """after RTSA i: every level's relay rows in and the rest of its block (the `group`'s levels: up to the attention)"""
+        for j in st.order:
+            d, blk = st.depths[j], self.hosa_blocks[j][i]
+            st.sts[j].wait_event(ev_rt)
+            with torch.cuda.stream(st.sts[j]):
+                rin = st.relay_in(j, i, fresh[d])
+                if j in group:
+                    st.calls[d].run(PHASE_RELAY_QKV, rin)                     # relay rows in, their LN1 / qkv
+                elif st.calls[d] is not None:
+                    st.outs[j] = blk._tail(st.calls[d].run(PHASE_REST, rin), st.plan, d)
                 else:
-                    for ev in done:
-                        rs.wait_event(ev)
-                with torch.cuda.stream(rs):
-                    rt_all = self.rtsa_blocks[i].forward_parts([rts[d] for d in depths], plan)
-                    ev_rt = rs.record_event()
-                for j in order[1:]:
-                    phase1(j)
-                fresh = {d: rt_all[plan.rt_offset[d]:plan.rt_offset[d] + plan.n_windows[d]] for d in depths}
-                old = (dict(bufs), dict(rts))        # buffers other streams still read stay alive until the join
-                # The levels on SIDE streams (the small ones: 2 k and 14 k rows in the bench) send their window attention out as
-                # ONE launch: their windows are one or two per workgroup, latency-bound launches of 14 and 21 us alone.  The
-                # join is between those side streams only.  (Measured alternatives: all three levels in one launch joined
-                # on the main stream -3.5 % of the step; the small levels back to back on one side stream -3 %.)
-                # (blocks on the one-launch LN1 -> qkv -> attention path have no separate attention launch to merge)
-                group = [j for j in order if small[j] and calls[depths[j]] is not None
-                         and not calls[depths[j]].weights.fuse_attention & 2] if _MERGED_ATTN else []
-                if len(group) < 2:
-                    group = []
-                outs = {}
+                    st.outs[j] = blk(st.bufs[d], st.plan, d, rin)
 
-                def relay_in(j):
-                    return self.down_projections[j][i](fresh[depths[j]]) if proj else fresh[depths[j]]
+    def _merged_attention(self, st, group):
+        """the window attention of the group's levels as one launch on the first one's stream; the event after it"""
+        lead = st.sts[group[0]]
+        for j in group[1:]:
+            lead.wait_event(st.sts[j].record_event())
+        with torch.cuda.stream(lead):
+            ops.block_attention_multi([st.calls[st.depths[j]] for j in group])
+            return lead.record_event()
 
-                for j in order:
-                    d = depths[j]
-                    sts[j].wait_event(ev_rt)
-                    with torch.cuda.stream(sts[j]):
-                        if j in group:
-                            calls[d].run(3, relay_in(j))                      # relay rows in, their LN1 / qkv
-                        elif calls[d] is not None:
-                            outs[j] = self.hosa_blocks[j][i]._tail(calls[d].run(2, relay_in(j)), plan, d)
-                        else:
-                            outs[j] = self.hosa_blocks[j][i](bufs[d], plan, d, relay_in(j))
-                if group:
-                    lead = sts[group[0]]
-                    for j in group[1:]:
-                        lead.wait_event(sts[j].record_event())
-                    with torch.cuda.stream(lead):
-                        ops.block_attention_multi([calls[depths[j]] for j in group])
-                        ev_att = lead.record_event()
-                    for j in group:
-                        if sts[j] is not lead:
-                            sts[j].wait_event(ev_att)
-                        with torch.cuda.stream(sts[j]):
-                            outs[j] = self.hosa_blocks[j][i]._tail(calls[depths[j]].run(4), plan, depths[j])      # proj + MLP
-                for j in order:
-                    with torch.cuda.stream(sts[j]):
-                        bufs[depths[j]] = outs[j]
-                        rts[depths[j]] = self.up_projections[j][i](outs[j][nts[j]:]) if proj else outs[j][nts[j]:]
-                if i + 1 == self.num_blocks:
-                    for j in range(len(depths)):
-                        if sts[j] is not main:
-                            main.wait_stream(sts[j])
-                else:
-                    done = [st.record_event() for st in dict.fromkeys(sts)]
-                del calls, old, fresh, rt_all
-                continue
-            if ckpt:                                                    # 596-601
-                rt_all = _checkpoint_block(self.rtsa_blocks[i], torch.cat([rts[d] for d in depths], 0), plan)
-            else:
-                rt_all = self.rtsa_blocks[i].forward_parts([rts[d] for d in depths], plan)
-            fresh = {d: rt_all[plan.rt_offset[d]:plan.rt_offset[d] + plan.n_windows[d]] for d in depths}
-            if _PYRAMID_STREAMS and not _SERIAL_STREAMS and not _grad_path(data) and data.is_cuda:
-                # the three depths are independent inside an iteration (the reference runs them on
-                # three CUDA streams too, hotformerloc_backbone.py:604-633): the coarse depths'
-                # small GEMMs and kernels overlap the fine depth's.  Fork/join discipline: side
-                # streams wait for the main stream's event, the main stream waits for theirs.
-                # Only SMALL depths go to a side stream (_SIDE_STREAM_MAX_ROWS): they are the ones
-                # that cannot fill 256 CUs, and hipBLASLt's stream-K GEMMs (workgroups that wait on
-                # their peers' partial tiles) dead-lock when several chip-filling ones share the CUs.
-                main = torch.cuda.current_stream()
-                side = self._side_streams(data.device)
-                keep = []         # inputs allocated on the main stream stay alive until the join
-                used = []
-                for j, d in enumerate(depths):
-                    if j == 0 or bufs[d].shape[0] > _SIDE_STREAM_MAX_ROWS:
-                        continue
-                    side[j - 1].wait_stream(main)
-                    keep.append((bufs[d], rt_all))
-                    with torch.cuda.stream(side[j - 1]):
-                        bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
-                    used.append(j)
-                for j, d in enumerate(depths):
-                    if j not in used:
-                        bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
-                for j in used:
-                    main.wait_stream(side[j - 1])
-                del keep
-            else:
-                for j, d in enumerate(depths):
-                    bufs[d], rts[d] = hosa(j, d, i, bufs[d], fresh[d])
-        local = {d: bufs[d][:nt] for d, nt in zip(depths, nts)}
-        return local, rts
+    def _tails(self, st, i, group, ev_att):
+        """what follows the merged attention, every level on its own stream again"""
+        for j in group:
+            d = st.depths[j]
+            if st.sts[j] is not st.sts[group[0]]:
+                st.sts[j].wait_event(ev_att)
+            with torch.cuda.stream(st.sts[j]):
+                st.outs[j] = self.hosa_blocks[j][i]._tail(st.calls[d].run(PHASE_TAIL), st.plan, d)      # proj + MLP
+
+    def _hand_over(self, st, i):
+        """the outputs become iteration i + 1's inputs; the per-stream events it waits for (last: main joins instead)"""
+        for j in st.order:
+            with torch.cuda.stream(st.sts[j]):
+                st.hand_over(j, i, st.outs[j])
+        if i + 1 < self.num_blocks:
+            return [s.record_event() for s in dict.fromkeys(st.sts)]
+        for s in (s for s in st.sts if s is not st.main):
+            st.main.wait_stream(s)
 
 
 class HOTFormerBase(nn.Module):

@@ -700,20 +700,16 @@ def ln_mlp_fused(x, gamma, beta, eps: float, pack, b1, b2, out=None):
     return out
 
 
-def block_forward_x3(weights, keep_alive, x_in, relay, neigh, tok_meta, n_tokens: int, desc: WindowAttnDesc):
-    """One transformer block of the inference path in ONE native call (hfl_block_forward_x3): CPE -> [relay rows] -> LN1 ->
-    qkv -> window attention -> proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual.  `weights` = a filled
-    `_native.BlockWeights` (see model._block_weights), `keep_alive` the tensors its pointers refer to."""
-    call = BlockCall(weights, keep_alive, x_in, neigh, tok_meta, n_tokens, desc)
-    return call.run(0, relay)
-
-
 class BlockCall:
-    """The same block in two phases (hfl_block_io.phase): `run(1)` issues what reads token rows only (CPE, their LN1 and
-    qkv projection) -- the caller may do that while the relay-token self-attention of the iteration is still running on
-    another stream -- `run(2, relay)` the rest, on whatever stream is current at that call; `run(0, relay)` = both.
-    `run(3, relay)` / `block_attention_multi([...])` / `run(4)` split phase 2 around the window attention, so that the
-    attention of several blocks goes out as one launch."""
+    """One transformer block of the inference path through the native call hfl_block_forward_x3 (CPE -> [relay rows] -> LN1 ->
+    qkv -> window attention -> proj + residual -> LN2 -> fc1 + GELU -> fc2 + residual); `weights` = a filled
+    `_native.BlockWeights` (model._native_block_forms), `keep_alive` the tensors its pointers refer to.
+    The same block in two phases (hfl_block_io.phase, named in `_native`): `run(PHASE_TOKENS)` issues what reads token rows
+    only (CPE, their LN1 and qkv projection) -- the caller may do that while the relay-token self-attention of the iteration is
+    still running on another stream -- `run(PHASE_REST, relay)` the rest, on whatever stream is current at that call;
+    `run(PHASE_WHOLE, relay)` = both.  `run(PHASE_RELAY_QKV, relay)` / `block_attention_multi([...])` / `run(PHASE_TAIL)` split
+    PHASE_REST around the window attention, so that the attention of several blocks goes out as one launch.  Which
+    attention launches the call uses is `weights.fuse_attention` (FUSE_ATTN_NO_RELAY, FUSE_ATTN_WS)."""
 
     def __init__(self, weights, keep_alive, x_in, neigh, tok_meta, n_tokens: int, desc: WindowAttnDesc):
         _dev(x_in, neigh, tok_meta)
@@ -724,10 +720,10 @@ class BlockCall:
         self.arena = torch.empty(int(self.lib.hfl_block_forward_x3_arena(rows, c)), dtype=torch.uint8, device=x_in.device)
         self.io = _native.BlockIO(x_in=x_in.data_ptr(), relay=None, out=self.out.data_ptr(), arena=self.arena.data_ptr(),
                                   neigh=neigh.data_ptr(), tok_meta=tok_meta.data_ptr(), n_rows=rows, n_tokens=n_tokens,
-                                  phase=0)
+                                  phase=_native.PHASE_WHOLE)
 
     def run(self, phase: int, relay=None):
-        if relay is not None:           # (stays set for the later phases of the call: phase 4's proj reads the relay rows there)
+        if relay is not None:           # (stays set for the later phases of the call: PHASE_TAIL's proj reads the relay rows)
             _dev(relay)
             assert relay.dtype == torch.float32 and relay.is_contiguous()
             self.keep = self.keep + (relay,)
@@ -739,8 +735,8 @@ class BlockCall:
 
 
 def block_attention_multi(calls):
-    """The window attention of several blocks that have run phases 1 and 3 (`BlockCall.run(1)`, `.run(3, relay)`), as one
-    launch when their attention shapes agree (hfl_block_attention_x3_multi); `.run(4)` of each block follows."""
+    """The window attention of several blocks that have run `BlockCall.run(PHASE_TOKENS)` and `.run(PHASE_RELAY_QKV, relay)`, as
+    one launch when their attention shapes agree (hfl_block_attention_x3_multi); `.run(PHASE_TAIL)` of each block follows."""
     n = len(calls)
     assert 1 <= n <= 4
     lib = _native.load()

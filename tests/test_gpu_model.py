@@ -4,6 +4,8 @@
 
 Tolerance (BASELINE.json north_star): relative L2 per descriptor <= 1e-3 in fp32."""
 
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -463,6 +465,44 @@ def test_early_phase_schedule_equals_the_sequential_one():
         assert torch.equal(out[True], out[False]), prop
 
 
+@contextlib.contextmanager
+def _recorded_schedules(M):
+    """What `HOTFormerStage._schedule` chose, forward by forward."""
+    seen, orig = [], M.HOTFormerStage._schedule
+    M.HOTFormerStage._schedule = lambda self, *a: (seen.append(orig(self, *a)), seen[-1])[1]
+    try:
+        yield seen
+    finally:
+        M.HOTFormerStage._schedule = orig
+
+
+@pytest.mark.gpu
+def test_every_stream_setting_runs_its_schedule_with_the_same_result():
+    """`set_pyramid_streams(True | 'serial' | False)` and the default streams without the early phase: the stage runs the
+    early schedule, the early schedule on one stream, the sequential one and the forked one -- the same kernels on the same
+    rows, bitwise equal descriptors."""
+    from hotformerloc_amd import model as M
+    params, depth = load_config('wild-places')
+    model = _device_model(params)
+    octree = build_batch_octree(syn.make_clouds(93, 4, 2500, params.coordinates), depth, 2, 'cuda')
+    out = []
+    with _recorded_schedules(M) as seen:
+        try:
+            for streams, early in ((True, True), ('serial', True), (False, True), (True, False)):
+                M.set_pyramid_streams(streams)
+                M._EARLY_PHASE = early
+                with torch.no_grad():
+                    out.append(model({'octree': octree})['global'])
+                torch.cuda.synchronize()
+        finally:
+            M.set_pyramid_streams(True)
+            M._EARLY_PHASE = True
+    assert seen == ['early', 'early', 'sequential', 'forked'], seen
+    assert torch.isfinite(out[0]).all()
+    for y in out[1:]:
+        assert torch.equal(out[0], y)
+
+
 @pytest.mark.gpu
 def test_attn_ws_block_path_matches_the_two_launch_path():
     """LN1 -> qkv -> window attention of the relay-token blocks' token rows as ONE launch (hfl_attn_ws_fwd behind
@@ -479,22 +519,19 @@ def test_attn_ws_block_path_matches_the_two_launch_path():
     octree = build_batch_octree(syn.make_clouds(93, 4, 2500, params.coordinates), depth, 2, 'cuda')
     out = {}
     saved = (M._ATTN_WS, M._ATTN_WS_MIN_ROWS, M._EARLY_PHASE, M._ATTN_WS_EARLY)
-    calls = []
-    orig = M.HOTFormerStage._iterations
-    M.HOTFormerStage._iterations = lambda self, *a: (calls.append(a[8]), orig(self, *a))[1]      # a[8] = `early`
-    try:
-        # (two launches, early) | (one launch, early phases forced: block phases 1 / 2 with the CPE alone in phase 1) |
-        # (one launch, sequential) | (one launch, default: the stage leaves the early-phase schedule by itself)
-        for key, ws, early, keep in (((False, True), False, True, False), ((True, True), True, True, True),
-                                     ((True, False), True, False, False), ('auto', True, True, False)):
-            M._ATTN_WS, M._ATTN_WS_MIN_ROWS, M._EARLY_PHASE, M._ATTN_WS_EARLY = ws, 0, early, keep
-            with torch.no_grad():
-                out[key] = model({'octree': octree})['global']
-            torch.cuda.synchronize()
-    finally:
-        M._ATTN_WS, M._ATTN_WS_MIN_ROWS, M._EARLY_PHASE, M._ATTN_WS_EARLY = saved
-        M.HOTFormerStage._iterations = orig
-    assert calls == [True, True, False, False], calls
+    with _recorded_schedules(M) as calls:
+        try:
+            # (two launches, early) | (one launch, early phases forced: block phases 1 / 2 with the CPE alone in phase 1) |
+            # (one launch, sequential) | (one launch, default: the stage leaves the early-phase schedule by itself)
+            for key, ws, early, keep in (((False, True), False, True, False), ((True, True), True, True, True),
+                                         ((True, False), True, False, False), ('auto', True, True, False)):
+                M._ATTN_WS, M._ATTN_WS_MIN_ROWS, M._EARLY_PHASE, M._ATTN_WS_EARLY = ws, 0, early, keep
+                with torch.no_grad():
+                    out[key] = model({'octree': octree})['global']
+                torch.cuda.synchronize()
+        finally:
+            M._ATTN_WS, M._ATTN_WS_MIN_ROWS, M._EARLY_PHASE, M._ATTN_WS_EARLY = saved
+    assert calls == ['early', 'early', 'forked', 'forked'], calls
     assert torch.equal(out['auto'], out[True, False])
     assert torch.equal(out[True, True], out[True, False])
     a, b = out[False, True].double(), out[True, True].double()

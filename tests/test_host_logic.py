@@ -347,3 +347,25 @@ def test_drop_path_replays_armed_factors_and_rejects_mismatched_ones():
             dp._draw(batch, dtype, torch.device('cpu'))
     dp._factors = None
     assert dp._draw(3, torch.float32, torch.device('cpu')).shape == (3,)
+
+
+def test_inference_path_eligibility_is_false_on_the_cpu_and_the_stage_runs_sequentially():
+    """The hand-written x3 inference path is for GPU rows only: on a CPU tensor both layers of its eligibility rule are false
+    for every kind of transformer block, and the H-OSA stage chooses the sequential schedule.  The names of the block phases
+    and of the attention-fusion bits carry the values of include/hotformerloc_hip.h."""
+    from hotformerloc_amd import model as M
+    params, depth = load_config('wild-places')
+    model = model_factory(params).eval()
+    blocks = {}
+    for m in model.modules():
+        blocks.setdefault(type(m), m)
+    with torch.no_grad():
+        for kind in (M.OctFormerBlock, M.HOTFormerBlock, M.RelayTokenTransformerBlock):
+            blk = blocks[kind]
+            x = torch.zeros(8, blk.norm1.normalized_shape[0])
+            assert not M._fused_inference(blk, x) and not M._native_rows(blk, x), kind
+        stage = blocks[M.HOTFormerStage]
+        assert stage._schedule(torch.zeros(8, stage.max_rt_channels), None, depth - 2, False) == 'sequential'
+    assert (_native.PHASE_WHOLE, _native.PHASE_TOKENS, _native.PHASE_REST, _native.PHASE_RELAY_QKV,
+            _native.PHASE_TAIL) == (0, 1, 2, 3, 4)
+    assert (_native.FUSE_ATTN_NO_RELAY, _native.FUSE_ATTN_WS) == (1, 2)
