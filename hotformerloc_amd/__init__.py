@@ -2,6 +2,11 @@
 
 Public surface (mirrors the reference's): `model_factory`, `ModelParams`, `Octree`, `Points`,
 `merge_octrees`, and the `dwconv` op module.  See DESIGN.md / INTEGRATION.md.
+
+Raw-submap post-processing on the device (the reference's open3d / CSF toolkit): `trim_radius`, `remove_outliers` (and
+`knn_mean_distance`, the exact k-nearest-neighbour mean distance behind it), `remove_ground`, `voxel_downsample` /
+`pnvlad_downsample` / `random_downsample`, `normalise_submaps`, chained by `prepare_submaps` / `prepare_submaps_fixed`;
+every step has a numpy `*_host` twin that states its definition.
 """
 
 import os as _os
@@ -24,6 +29,8 @@ from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_
                     pnvlad_downsample_host, random_downsample, random_downsample_host, normalise_submaps_padded,
                     normalise_submaps_padded_host, prepare_submaps_fixed)
 from .ground import remove_ground, remove_ground_host                                              # noqa: F401,E402
+from .outliers import (remove_outliers, remove_outliers_host, knn_mean_distance, knn_mean_distance_host,   # noqa: F401,E402
+                       trim_radius, trim_radius_host)
 from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
                      tuple_index_from_poses, truth_from_poses)
 from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_points, nn_distances,   # noqa: F401,E402

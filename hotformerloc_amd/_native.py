@@ -148,6 +148,12 @@ SIGNATURES = {
                                    c_float, c_float, c_int, c_int, c_void_p]),
     'hfl_cloth_classify': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_float,
                                    c_float, c_void_p]),
+    'hfl_cloud_nonfinite': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    'hfl_knn_cell_keys': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    'hfl_knn_mean_dist': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    'hfl_outlier_threshold': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_double, c_void_p]),
+    'hfl_outlier_mask': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    'hfl_radius_mask': (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
     'hfl_tap_lists_workspace': (c_int64, [c_int64, c_int]),
     'hfl_tap_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'hfl_tap_lists_multi': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

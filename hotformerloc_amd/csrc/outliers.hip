@@ -1,0 +1,413 @@
+// Statistical outlier removal and the radius trim for raw submaps, batched and ragged on the device: the cleaning steps in
+// front of the CS-Wild-Places post-processing (datasets/CSWildPlaces/processing_utils.py remove_outliers, i.e. open3d's
+// remove_statistical_outlier, and the radius cut of postprocess_wildplaces_ground.py).  The filter is DEFINED in
+// hotformerloc_amd/outliers.py (module docstring) and DESIGN.md section 7g; this file and the numpy route there follow that
+// definition operation for operation, every operation rounded once (the file is built with -ffp-contract=off), so the two
+// agree to the bit.
+//
+//   hfl_cloud_nonfinite    flags[b] = 1 when cloud b holds a coordinate that is not finite (integer OR)
+//   hfl_knn_cell_keys      one int64 key per point: the cloud's first cell + (iz ny + iy) nx + ix on the cloud's uniform grid
+//   hfl_knn_mean_dist      the mean distance to the k nearest points of the own cloud, the point itself included, exact:
+//                          (1) a dense cell-start table by one binary search per cell over the sorted keys; (2) one thread
+//                          per point in sorted order scans the 3 x 3 x 3 block of cells round its own and keeps the K
+//                          smallest squared distances in a sorted register list; the point is resolved when its k-th smallest
+//                          is strictly below the square of a conservative distance to the nearest face of the block that has
+//                          cells behind it, else it is appended to a list; (3) a wave per listed point scans the point's
+//                          whole cloud, a list per lane, and merges the 64 lists by k rounds of a wave minimum
+//   hfl_outlier_threshold  per cloud, in float64 in the order of hfl_pair_stats: mean, std, mean + ratio std, n_valid
+//   hfl_outlier_mask       keep = avg > 0 and double(avg) < threshold
+//   hfl_radius_mask        keep = sqrt(x x + y y) <= radius_max in float64
+//
+// The answer of (2) and (3) is a pure function of the multiset of the k smallest squared distances, which both find exactly,
+// so it does not depend on the cell size, on which of the two resolved a point, or on the order of the list.  No
+// floating-point atomics (one integer add per wave appends to the list); no workgroup waits for another.
+#include <math.h>
+
+#include "hfl_common.h"
+
+namespace {
+
+constexpr int kOutThreads = 256;
+constexpr int kOutWaves = kOutThreads / HFL_WAVE;
+constexpr float kFaceShrink = 1.f - 9.5367431640625e-07f;      // 1 - 2^-20: the relative part of the margin of the bound
+
+// the cloud that holds point i: the largest c in [0, batch) with off[c] <= i
+__device__ __forceinline__ int out_find_cloud(const int64_t* __restrict__ off, int batch, int64_t i) {
+  int lo = 0, hi = batch - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+cloud_nonfinite_kernel(int32_t* __restrict__ flags, const float* __restrict__ pts, const int64_t* __restrict__ off, int batch,
+                       int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (i >= n) return;
+  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  if (!(x - x == 0.f) || !(y - y == 0.f) || !(z - z == 0.f)) atomicOr(flags + out_find_cloud(off, batch, i), 1);
+}
+
+// int((p - origin) / cell) clamped into [0, top]; what is not >= 0 gives 0
+__device__ __forceinline__ int knn_cell(float p, float origin, float cell, int top) {
+  const float f = __fdiv_rn(__fsub_rn(p, origin), cell);
+  if (!(f >= 0.f)) return 0;
+  if (f >= 2147483520.f) return top;                         // the largest float an int holds
+  return min((int)f, top);                                   // compared as integers: (float)top may round up
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+knn_cell_keys_kernel(int64_t* __restrict__ keys, const hfl_knn_grid* __restrict__ grids, const float* __restrict__ pts,
+                     const int64_t* __restrict__ off, int batch, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (i >= n) return;
+  const hfl_knn_grid g = grids[out_find_cloud(off, batch, i)];
+  const int ix = knn_cell(pts[i * 3 + 0], g.ox, g.cell, g.nx - 1);
+  const int iy = knn_cell(pts[i * 3 + 1], g.oy, g.cell, g.ny - 1);
+  const int iz = knn_cell(pts[i * 3 + 2], g.oz, g.cell, g.nz - 1);
+  keys[i] = g.cell_base + ((int64_t)iz * g.ny + iy) * g.nx + ix;
+}
+
+// starts[t] = the first sorted position whose key is >= t, for t in [0, n_cells]: cell t holds [starts[t], starts[t + 1])
+__global__ void __launch_bounds__(kOutThreads)
+knn_cell_starts_kernel(int32_t* __restrict__ starts, const int64_t* __restrict__ skeys, int64_t n, int64_t n_cells) {
+  const int64_t t = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (t > n_cells) return;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (skeys[mid] < t) lo = mid + 1; else hi = mid;
+  }
+  starts[t] = (int32_t)lo;
+}
+
+// (dx dx + dy dy) + dz dz on the differences themselves, every operation rounded once
+__device__ __forceinline__ float knn_d2(float px, float py, float pz, const float* __restrict__ q) {
+  const float dx = __fsub_rn(px, q[0]), dy = __fsub_rn(py, q[1]), dz = __fsub_rn(pz, q[2]);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// The correctly rounded fp32 root.  Not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers map that name to the
+// native approximation, which is an ulp off now and then; sqrtf is correctly rounded (hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt), and so is the plain fp32 division behind __fdiv_rn.
+__device__ __forceinline__ float knn_sqrt(float x) { return __builtin_sqrtf(x); }
+
+// The K smallest values seen, ascending, in registers: every index is a compile-time constant after unrolling, so the list
+// never goes to scratch memory.  Inserting v into the sorted list and dropping the largest is, per slot, the median of
+// (left neighbour, own value, v).
+template <int K>
+struct KnnList {
+  float v[K];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int i = 0; i < K; ++i) v[i] = INFINITY;
+  }
+  __device__ __forceinline__ void insert(float d) {
+    if (d < v[K - 1]) {
+#pragma unroll
+      for (int i = K - 1; i > 0; --i) v[i] = fmaxf(v[i - 1], fminf(v[i], d));
+      v[0] = fminf(v[0], d);
+    }
+  }
+  __device__ __forceinline__ float kth(int k) const {         // v[k - 1] as the largest of the first k: the list ascends,
+    float r = -INFINITY;                                       // and no register is indexed by a run-time value
+#pragma unroll
+    for (int i = 0; i < K; ++i) r = fmaxf(r, i < k ? v[i] : -INFINITY);
+    return r;
+  }
+  __device__ __forceinline__ void pop() {
+#pragma unroll
+    for (int i = 0; i + 1 < K; ++i) v[i] = v[i + 1];
+    v[K - 1] = INFINITY;
+  }
+};
+
+// the distance from coordinate p to the nearest face of the scanned cells [c0, c1] that has cells behind it, less the
+// absolute margin; +inf when the block reaches both ends of the axis
+__device__ __forceinline__ float knn_face_gap(float p, float origin, float cell, int c0, int c1, int top, float margin) {
+  const float a = __fsub_rn(p, origin);
+  float gap = INFINITY;
+  if (c0 > 0) gap = fminf(gap, __fsub_rn(__fsub_rn(a, __fmul_rn((float)c0, cell)), margin));
+  if (c1 < top) gap = fminf(gap, __fsub_rn(__fsub_rn(__fmul_rn((float)(c1 + 1), cell), a), margin));
+  return gap;
+}
+
+template <int K>
+__global__ void __launch_bounds__(kOutThreads)
+knn_query_kernel(float* __restrict__ avg, int32_t* __restrict__ pending, int32_t* __restrict__ counter,
+                 const float* __restrict__ spts, const int64_t* __restrict__ skeys, const int64_t* __restrict__ perm,
+                 const int32_t* __restrict__ starts, const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off,
+                 int batch, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (j >= n) return;
+  const int c = out_find_cloud(off, batch, j);
+  const hfl_knn_grid g = grids[c];
+  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
+  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+  const int64_t local = skeys[j] - g.cell_base;
+  const int64_t row = perm[j];
+  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
+  const int k = g.k;
+  KnnList<K> list;
+  list.clear();
+  bool resolved = false;
+  if (local >= 0 && local < cells && k >= 1 && k <= K) {       // a key off its own grid goes to the whole-cloud scan
+    const int ix = (int)(local % g.nx), iy = (int)((local / g.nx) % g.ny), iz = (int)(local / ((int64_t)g.nx * g.ny));
+    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
+    const int y0 = max(iy - 1, 0), y1 = min(iy + 1, g.ny - 1);
+    const int z0 = max(iz - 1, 0), z1 = min(iz + 1, g.nz - 1);
+#pragma unroll 1
+    for (int z = z0; z <= z1; ++z)
+#pragma unroll 1
+      for (int y = y0; y <= y1; ++y) {
+        const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;      // the cells x0 .. x1 of a line are adjacent
+        const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
+#pragma unroll 1
+        for (int32_t q = s; q < e; ++q) list.insert(knn_d2(px, py, pz, spts + (int64_t)q * 3));
+      }
+    float gap = knn_face_gap(px, g.ox, g.cell, x0, x1, g.nx - 1, g.mx);
+    gap = fminf(gap, knn_face_gap(py, g.oy, g.cell, y0, y1, g.ny - 1, g.my));
+    gap = fminf(gap, knn_face_gap(pz, g.oz, g.cell, z0, z1, g.nz - 1, g.mz));
+    gap = __fmul_rn(fmaxf(gap, 0.f), kFaceShrink);
+    resolved = list.kth(k) < __fmul_rn(gap, gap);
+  }
+  if (resolved) {
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+      if (i < k) sum = __fadd_rn(sum, knn_sqrt(list.v[i]));
+    if (row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
+  } else {                                                     // one integer add per wave; the order of the list is free
+    const unsigned long long mask = __ballot(1);
+    const int lane = threadIdx.x & (HFL_WAVE - 1);
+    const int leader = __ffsll((long long)mask) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(counter, __popcll(mask));
+    base = __shfl(base, leader, HFL_WAVE);
+    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+    if (slot >= 0 && slot < n) pending[slot] = (int32_t)j;
+  }
+}
+
+// a wave per pending point, the waves striding over the list; every loop bound is the same in all lanes of a wave
+template <int K>
+__global__ void __launch_bounds__(kOutThreads)
+knn_fallback_kernel(float* __restrict__ avg, const int32_t* __restrict__ pending, const int32_t* __restrict__ counter,
+                    const float* __restrict__ spts, const int64_t* __restrict__ perm, const hfl_knn_grid* __restrict__ grids,
+                    const int64_t* __restrict__ off, int batch, int64_t n) {
+  const int lane = threadIdx.x & (HFL_WAVE - 1);
+  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
+  const int64_t count = min((int64_t)max(*counter, 0), n);
+  for (int64_t e = wave; e < count; e += waves) {
+    const int64_t j = pending[e];
+    if (j < 0 || j >= n) continue;
+    const int c = out_find_cloud(off, batch, j);
+    const int64_t first = off[c], last = min(off[c + 1], n);
+    const int k = min(max(grids[c].k, 1), K);
+    const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
+    KnnList<K> list;
+    list.clear();
+    for (int64_t q = first + lane; q < last; q += HFL_WAVE) list.insert(knn_d2(px, py, pz, spts + q * 3));
+    float sum = 0.f;
+    for (int r = 0; r < k; ++r) {                              // ascending: the smallest head of the 64 lists, k times
+      const float head = list.v[0];
+      float m = head;
+#pragma unroll
+      for (int s = HFL_WAVE / 2; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, HFL_WAVE));
+      const unsigned long long owners = __ballot(head == m);
+      if (lane == __ffsll((long long)owners) - 1) list.pop();  // one lane gives up one copy: equal values stay a multiset
+      sum = __fadd_rn(sum, knn_sqrt(m));
+    }
+    const int64_t row = perm[j];
+    if (lane == 0 && row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
+  }
+}
+
+__device__ __forceinline__ double out_wave_sum(double v) {
+#pragma unroll
+  for (int m = HFL_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, HFL_WAVE);
+  return v;
+}
+
+// the sum over the workgroup in the order of hfl_pair_stats: a thread's rows in ascending order, the xor butterfly 32 .. 1
+// in a wave, the waves in wave order; the same value in every thread.  Two barriers.
+__device__ __forceinline__ double out_block_sum(double v, double* s_part) {
+  v = out_wave_sum(v);
+  __syncthreads();                                             // the previous round's parts have been read
+  if ((threadIdx.x & (HFL_WAVE - 1)) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double a = s_part[0];
+#pragma unroll
+  for (int w = 1; w < kOutWaves; ++w) a += s_part[w];
+  return a;
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+outlier_threshold_kernel(double* __restrict__ stats, const float* __restrict__ avg, const int64_t* __restrict__ off,
+                         int64_t n, double ratio) {
+  __shared__ double s_part[kOutWaves];
+  const int b = blockIdx.x;
+  const int64_t begin = max(off[b], (int64_t)0), end = min(off[b + 1], n);
+  double sum = 0.0, cnt = 0.0;
+  for (int64_t i = begin + threadIdx.x; i < end; i += kOutThreads) {
+    const float a = avg[i];
+    if (a > 0.f) { sum += (double)a; cnt += 1.0; }
+  }
+  sum = out_block_sum(sum, s_part);
+  cnt = out_block_sum(cnt, s_part);                            // whole numbers below 2^53: exact in any order
+  const double mean = __ddiv_rn(sum, cnt);                     // 0 / 0 = NaN for a cloud without a valid point
+  double ss = 0.0;
+  for (int64_t i = begin + threadIdx.x; i < end; i += kOutThreads) {
+    const float a = avg[i];
+    if (a > 0.f) {
+      const double d = __dsub_rn((double)a, mean);
+      ss += __dmul_rn(d, d);
+    }
+  }
+  ss = out_block_sum(ss, s_part);
+  if (threadIdx.x == 0) {
+    const double sd = __dsqrt_rn(__ddiv_rn(ss, __dsub_rn(cnt, 1.0)));      // 0 / 0 = NaN for a single valid point
+    stats[4 * (int64_t)b + 0] = mean;
+    stats[4 * (int64_t)b + 1] = sd;
+    stats[4 * (int64_t)b + 2] = __dadd_rn(mean, __dmul_rn(ratio, sd));
+    stats[4 * (int64_t)b + 3] = cnt;
+  }
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+outlier_mask_kernel(uint8_t* __restrict__ keep, const float* __restrict__ avg, const double* __restrict__ stats,
+                    const int64_t* __restrict__ off, int batch, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (i >= n) return;
+  const float a = avg[i];
+  const double threshold = stats[4 * (int64_t)out_find_cloud(off, batch, i) + 2];
+  keep[i] = (a > 0.f && (double)a < threshold) ? 1 : 0;        // a NaN threshold keeps nothing
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+radius_mask_kernel(uint8_t* __restrict__ keep, const float* __restrict__ pts, int64_t n, double radius) {
+  const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (i >= n) return;
+  const double x = (double)pts[i * 3 + 0], y = (double)pts[i * 3 + 1];
+  keep[i] = __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y))) <= radius ? 1 : 0;
+}
+
+bool out_batch_ok(int batch, int64_t n_points) { return batch >= 1 && n_points >= batch; }
+
+// every grid inside the cell table and every field in range, before anything runs
+bool knn_grids_ok(const hfl_knn_grid* g, int batch, int64_t n_cells, int* k_max) {
+  int big = 0;
+  for (int b = 0; b < batch; ++b) {
+    const hfl_knn_grid& d = g[b];
+    if (d.nx < 1 || d.ny < 1 || d.nz < 1 || d.k < 1 || d.k > HFL_KNN_MAX_NEIGHBOURS) return false;
+    const int64_t cells = (int64_t)d.nx * d.ny;
+    if (cells > HFL_KNN_MAX_CELLS || cells * d.nz > HFL_KNN_MAX_CELLS) return false;
+    if (d.cell_base < 0 || d.cell_base > n_cells || cells * d.nz > n_cells - d.cell_base) return false;
+    if (!(d.ox - d.ox == 0.f) || !(d.oy - d.oy == 0.f) || !(d.oz - d.oz == 0.f)) return false;      // finite
+    if (!(d.cell > 0.f) || !(d.cell <= 3.4028234e38f)) return false;
+    if (!(d.mx >= 0.f) || !(d.my >= 0.f) || !(d.mz >= 0.f)) return false;
+    if (d.k > big) big = d.k;
+  }
+  *k_max = big;
+  return true;
+}
+
+template <int K>
+int knn_launch(float* avg, int32_t* pending, int32_t* counter, int32_t* starts, const float* spts, const int64_t* skeys,
+               const int64_t* perm, const hfl_knn_grid* grids, const int64_t* off, int batch, int64_t n, int64_t n_cells,
+               int phases, hipStream_t s) {
+  if (phases & HFL_KNN_PHASE_STARTS)
+    knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
+  if (phases & HFL_KNN_PHASE_QUERY) {
+    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return (int)e;
+    knn_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(avg, pending, counter, spts, skeys, perm,
+                                                                                  starts, grids, off, batch, n);
+  }
+  if (phases & HFL_KNN_PHASE_FALLBACK) {
+    const int64_t blocks = min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
+    knn_fallback_kernel<K><<<(unsigned)blocks, kOutThreads, 0, s>>>(avg, pending, counter, spts, perm, grids, off, batch, n);
+  }
+  HFL_RETURN_LAST_ERROR();
+}
+
+}  // namespace
+
+extern "C" int hfl_cloud_nonfinite(int32_t* flags, const float* points, const int64_t* cloud_offsets, int batch,
+                                   int64_t n_points, hfl_stream_t stream) {
+  if (flags == nullptr || points == nullptr || cloud_offsets == nullptr || !out_batch_ok(batch, n_points)) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)batch, s);
+  if (e != hipSuccess) return (int)e;
+  cloud_nonfinite_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, s>>>(flags, points, cloud_offsets, batch,
+                                                                                          n_points);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_knn_cell_keys(int64_t* keys, const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch,
+                                 int64_t n_cells, const float* points, const int64_t* cloud_offsets, int64_t n_points,
+                                 hfl_stream_t stream) {
+  if (keys == nullptr || grids_host == nullptr || grids == nullptr || points == nullptr || cloud_offsets == nullptr)
+    return HFL_EINVAL;
+  if (!out_batch_ok(batch, n_points) || n_cells < 1) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  int k_max = 0;
+  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  knn_cell_keys_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      keys, grids, points, cloud_offsets, batch, n_points);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_knn_mean_dist(float* avg, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                                 const float* sorted_points, const int64_t* sorted_keys, const int64_t* perm,
+                                 const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                                 const int64_t* cloud_offsets, int64_t n_points, int phases, hfl_stream_t stream) {
+  if (avg == nullptr || pending == nullptr || counter == nullptr || cell_starts == nullptr || sorted_points == nullptr ||
+      sorted_keys == nullptr || perm == nullptr || grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
+    return HFL_EINVAL;
+  if (!out_batch_ok(batch, n_points) || n_cells < 1 || phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  int k_max = 0;
+  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (k_max <= 8)
+    return knn_launch<8>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
+                         n_points, n_cells, phases, s);
+  if (k_max <= 16)
+    return knn_launch<16>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
+                          n_points, n_cells, phases, s);
+  return knn_launch<32>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
+                        n_points, n_cells, phases, s);
+}
+
+extern "C" int hfl_outlier_threshold(double* stats, const float* avg, const int64_t* cloud_offsets, int batch,
+                                     int64_t n_points, double std_ratio, hfl_stream_t stream) {
+  if (stats == nullptr || avg == nullptr || cloud_offsets == nullptr || batch < 1 || n_points < 0) return HFL_EINVAL;
+  if (!(std_ratio > 0.0) || !(std_ratio - std_ratio == 0.0)) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS) return HFL_ECAPACITY;
+  outlier_threshold_kernel<<<(unsigned)batch, kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(stats, avg, cloud_offsets,
+                                                                                                 n_points, std_ratio);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_outlier_mask(uint8_t* keep, const float* avg, const double* stats, const int64_t* cloud_offsets, int batch,
+                                int64_t n_points, hfl_stream_t stream) {
+  if (keep == nullptr || avg == nullptr || stats == nullptr || cloud_offsets == nullptr || !out_batch_ok(batch, n_points))
+    return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  outlier_mask_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      keep, avg, stats, cloud_offsets, batch, n_points);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_radius_mask(uint8_t* keep, const float* points, int64_t n_points, double radius_max, hfl_stream_t stream) {
+  if (keep == nullptr || points == nullptr || n_points < 1) return HFL_EINVAL;
+  if (!(radius_max > 0.0) || !(radius_max - radius_max == 0.0)) return HFL_EINVAL;
+  if (n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  radius_mask_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      keep, points, n_points, radius_max);
+  HFL_RETURN_LAST_ERROR();
+}

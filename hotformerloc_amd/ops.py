@@ -2032,6 +2032,135 @@ def cloth_classify(points: torch.Tensor, offsets: torch.Tensor, heights: torch.T
     return keep
 
 
+KNN_MAX_NEIGHBOURS = 32                # HFL_KNN_MAX_NEIGHBOURS
+KNN_MAX_CELLS = 268435455              # HFL_KNN_MAX_CELLS: cells of all grids of one call
+KNN_PHASE_STARTS, KNN_PHASE_QUERY, KNN_PHASE_FALLBACK, KNN_PHASE_ALL = 1, 2, 4, 7      # HFL_KNN_PHASE_*
+KNN_GRID_DTYPE = [('ox', '<f4'), ('oy', '<f4'), ('oz', '<f4'), ('cell', '<f4'), ('mx', '<f4'), ('my', '<f4'), ('mz', '<f4'),
+                  ('k', '<i4'), ('nx', '<i4'), ('ny', '<i4'), ('nz', '<i4'), ('reserved', '<i4'),
+                  ('cell_base', '<i8')]                                              # hfl_knn_grid
+
+
+class KnnGridTable:
+    """One `hfl_knn_grid` per cloud on both sides: `host` (numpy, what the library checks before a launch) and `device`
+    (the same bytes, what the kernels read); `cells` cells in all, cloud b's from `host['cell_base'][b]` on."""
+
+    def __init__(self, grids, device):
+        import numpy as np
+        self.host = np.ascontiguousarray(grids, dtype=np.dtype(KNN_GRID_DTYPE))
+        if self.host.ndim != 1 or self.host.shape[0] < 1:
+            raise ValueError('KnnGridTable: one hfl_knn_grid per cloud expected')
+        self.batch = int(self.host.shape[0])
+        h = self.host
+        self.cells = int((h['nx'].astype(np.int64) * h['ny'] * h['nz']).sum())
+        if self.cells < 1 or self.cells > KNN_MAX_CELLS:
+            raise ValueError('KnnGridTable: 1..%d cells expected, got %d' % (KNN_MAX_CELLS, self.cells))
+        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+
+
+def cloud_nonfinite(points: torch.Tensor, offsets: torch.Tensor):
+    """`hfl_cloud_nonfinite`: -> flags (B,) int32 on the GPU, 1 where a cloud holds a coordinate that is not finite."""
+    batch = _voxel_check('cloud_nonfinite', points, offsets)
+    flags = torch.empty(batch, dtype=torch.int32, device=points.device)
+    check(_native.load().hfl_cloud_nonfinite(flags.data_ptr(), points.data_ptr(), offsets.data_ptr(), batch,
+                                             int(points.shape[0]), _stream()), 'hfl_cloud_nonfinite')
+    return flags
+
+
+def _knn_check(what: str, table: KnnGridTable, points: torch.Tensor, offsets: torch.Tensor):
+    _dev(table.device)
+    if _voxel_check(what, points, offsets) != table.batch:
+        raise ValueError('%s: %d clouds but %d grids' % (what, int(offsets.shape[0]) - 1, table.batch))
+
+
+def knn_cell_keys(points: torch.Tensor, offsets: torch.Tensor, table: KnnGridTable):
+    """`hfl_knn_cell_keys`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU -> keys (P,) int64, every point's cell
+    on its cloud's grid, counted through the batch.  Nothing is read back."""
+    _knn_check('knn_cell_keys', table, points, offsets)
+    keys = torch.empty(int(points.shape[0]), dtype=torch.int64, device=points.device)
+    check(_native.load().hfl_knn_cell_keys(keys.data_ptr(), table.host.ctypes.data, table.device.data_ptr(), table.batch,
+                                           table.cells, points.data_ptr(), offsets.data_ptr(), int(points.shape[0]),
+                                           _stream()), 'hfl_knn_cell_keys')
+    return keys
+
+
+class KnnWorkspace:
+    """what `hfl_knn_mean_dist` keeps between its launches: the cell-start table, the list of pending points, its counter"""
+
+    def __init__(self, n_points: int, cells: int, device):
+        self.starts = torch.empty(cells + 1, dtype=torch.int32, device=device)
+        self.pending = torch.empty(n_points, dtype=torch.int32, device=device)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def knn_mean_dist(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
+                  table: KnnGridTable, phases: int = KNN_PHASE_ALL, workspace: KnnWorkspace = None, out: torch.Tensor = None):
+    """`hfl_knn_mean_dist`: the ascending keys of `knn_cell_keys`, the sort's permutation and `points[perm]` -> (avg (P,)
+    fp32 in INPUT order: the mean distance to the k nearest points of the own cloud, pending (1,) int32 on the GPU: how many
+    points the whole-cloud scan had to finish).  `phases` runs single launches on a `workspace` and an `out` kept from an
+    earlier call.  Nothing is read back."""
+    _knn_check('knn_mean_dist', table, sorted_points, offsets)
+    _dev(sorted_keys, perm)
+    n = int(sorted_points.shape[0])
+    for t in (sorted_keys, perm):
+        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise TypeError('knn_mean_dist: contiguous (%d,) int64 keys and permutation expected' % n)
+    ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
+    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
+        raise ValueError('knn_mean_dist: the workspace was made for another batch')
+    avg = out if out is not None else torch.empty(n, dtype=torch.float32, device=sorted_points.device)
+    if avg.dtype != torch.float32 or tuple(avg.shape) != (n,) or not avg.is_contiguous():
+        raise TypeError('knn_mean_dist: contiguous (%d,) float32 output expected' % n)
+    _dev(ws.starts, ws.pending, ws.counter, avg)
+    check(_native.load().hfl_knn_mean_dist(avg.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
+                                           sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(),
+                                           table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
+                                           offsets.data_ptr(), n, int(phases), _stream()), 'hfl_knn_mean_dist')
+    return avg, ws.counter
+
+
+def outlier_threshold(avg: torch.Tensor, offsets: torch.Tensor, std_ratio: float):
+    """`hfl_outlier_threshold`: avg (P,) fp32 and offsets (B + 1,) int64 on the GPU -> stats (B, 4) float64: mean, std,
+    mean + std_ratio std and the number of valid rows (avg > 0) of every cloud."""
+    _dev(avg, offsets)
+    if avg.dtype != torch.float32 or avg.dim() != 1 or not avg.is_contiguous():
+        raise TypeError('outlier_threshold: contiguous (P,) float32 distances expected')
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
+        raise TypeError('outlier_threshold: (B + 1,) int64 cloud offsets with B >= 1 expected')
+    batch = int(offsets.shape[0]) - 1
+    stats = torch.empty((batch, 4), dtype=torch.float64, device=avg.device)
+    check(_native.load().hfl_outlier_threshold(stats.data_ptr(), _some(avg).data_ptr(), offsets.data_ptr(), batch,
+                                               int(avg.shape[0]), float(std_ratio), _stream()), 'hfl_outlier_threshold')
+    return stats
+
+
+def outlier_mask(avg: torch.Tensor, offsets: torch.Tensor, stats: torch.Tensor):
+    """`hfl_outlier_mask`: -> keep (P,) uint8 on the GPU, 1 where avg > 0 and below the cloud's threshold (stats[:, 2])."""
+    _dev(avg, offsets, stats)
+    batch = int(offsets.shape[0]) - 1
+    if avg.dtype != torch.float32 or avg.dim() != 1 or not avg.is_contiguous() or avg.shape[0] < 1:
+        raise TypeError('outlier_mask: contiguous non-empty (P,) float32 distances expected')
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or batch < 1 or not offsets.is_contiguous():
+        raise TypeError('outlier_mask: (B + 1,) int64 cloud offsets with B >= 1 expected')
+    if stats.dtype != torch.float64 or tuple(stats.shape) != (batch, 4) or not stats.is_contiguous():
+        raise TypeError('outlier_mask: contiguous (%d, 4) float64 stats expected' % batch)
+    keep = torch.empty(int(avg.shape[0]), dtype=torch.uint8, device=avg.device)
+    check(_native.load().hfl_outlier_mask(keep.data_ptr(), avg.data_ptr(), stats.data_ptr(), offsets.data_ptr(), batch,
+                                          int(avg.shape[0]), _stream()), 'hfl_outlier_mask')
+    return keep
+
+
+def radius_mask(points: torch.Tensor, radius_max: float):
+    """`hfl_radius_mask`: points (P, 3) fp32 on the GPU, P >= 1 -> keep (P,) uint8, 1 where sqrt(x x + y y) <= radius_max in
+    float64."""
+    _dev(points)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise TypeError('radius_mask: contiguous (P, 3) float32 points expected')
+    keep = torch.empty(int(points.shape[0]), dtype=torch.uint8, device=points.device)
+    check(_native.load().hfl_radius_mask(keep.data_ptr(), points.data_ptr(), int(points.shape[0]), float(radius_max),
+                                         _stream()), 'hfl_radius_mask')
+    return keep
+
+
 def _flat_l2_check(what: str, x: torch.Tensor):
     if x.dim() != 2:
         raise ValueError('%s: a (rows, D) matrix expected, got %s' % (what, tuple(x.shape)))

@@ -1,0 +1,340 @@
+"""Statistical outlier removal and the radius trim for raw submaps, for a whole ragged batch on the device.
+
+The reference cleans CS-Wild-Places submaps offline, on the host, one at a time, through open3d
+(`datasets/CSWildPlaces/processing_utils.py:153-169` `remove_outliers`: `remove_statistical_outlier(nb_neighbors=20,
+std_ratio=3.0)`), and cuts a Wild-Places ground scan to the submap footprint before anything else
+(`postprocess_wildplaces_ground.py:146`: `pts[np.linalg.norm(pts[:, :2], axis=1) <= radius_max]`, 30 m).  Both sit in front
+of the chain of `ground.py` and `voxel.py`: trim, outliers, ground, downsample, normalise.  Here a batch of raw submaps goes
+to the GPU once; open3d is not needed.
+
+open3d's KD-tree works in float64 on float64 points, and it is not a dependency, so this module DEFINES the filter, as
+`ground.py` does for the cloth filter, following `PointCloud::RemoveStatisticalOutliers` step by step.  **Bit parity with
+open3d is not claimed.**  The numpy route below (`*_host`) and the device route follow the definition operation for
+operation and agree to the bit.
+
+Definition, for one cloud of n fp32 points with k = min(`nb_neighbors`, n):
+
+ 1. Squared distances: for every point i, to all n points of the cloud, itself included (open3d's `SearchKNN` on its own
+    tree includes it), in fp32 on the differences themselves, every operation rounded once, nothing fused:
+    d2 = (dx dx + dy dy) + dz dz.
+ 2. Mean neighbour distance: the k smallest d2 of the point (only the multiset matters: ties at the k-th place change
+    nothing), the correctly rounded fp32 root of each, added in ascending order in fp32 from 0, divided by float32(k):
+    avg[i].
+ 3. A point is valid when avg[i] > 0.  A point with k coincident copies, itself among them, has avg = 0 and is never kept,
+    as in open3d.
+ 4. Threshold, over the valid points in float64: mean = sum(avg) / n_valid, std = sqrt(sum((avg - mean)^2) / (n_valid - 1)),
+    threshold = mean + `std_ratio` std.  No valid point keeps nothing; a single valid point gives std = 0 / 0 = NaN, so the
+    threshold is NaN and nothing is kept either -- that is open3d's behaviour too.
+ 5. Keep i when it is valid and float64(avg[i]) < threshold.  The kept rows come back in input order, bit for bit.
+
+`nb_neighbors` is an integer in 1..32, `std_ratio` finite and > 0; a cloud with a coordinate that is not finite raises
+`ValueError` naming it.  The float64 sums of step 4 are taken in another order on the device (that of `hfl_pair_stats`,
+fixed, so two runs give the same bits) than numpy's pairwise sum: mean, std and threshold agree to about 1e-15 relative,
+the masks are equal unless a point's avg lies that close to the threshold.
+
+Radius trim: keep a row when sqrt(x x + y y) <= `radius_max`, in float64 from the fp32 coordinates, every operation rounded
+once -- exactly what `np.linalg.norm(pts[:, :2].astype(float64), axis=1) <= radius_max` computes, which the host route
+calls.  Rows stay in input order; a cloud may come back empty.
+
+Device route of steps 1 and 2 (`csrc/outliers.hip`).  The answer is a pure function of the input, so
+the search structure is free: `hfl_voxel_bounds` and `hfl_cloud_nonfinite` with one host read, from which the host lays a
+uniform grid of cubic cells over every cloud (`POINTS_PER_CELL` points per cell on average, the cell enlarged until the
+cell-start tables of the batch fit `CELL_BUDGET_BYTES`; `cell_size=` overrides the choice); `hfl_knn_cell_keys`,
+`torch.sort` (plumbing, as in `voxel.py`) and a gather put the points cell by cell; `hfl_knn_mean_dist` builds the dense
+cell-start table, lets one thread per point scan the 3 x 3 x 3 cells round its own with the k smallest d2 in a sorted
+register list, and proves the scan complete when the k-th smallest d2 lies strictly below the square of a conservative
+distance to the nearest face of the block that has cells behind it.  The points it cannot prove -- the isolated ones the
+filter exists to find, among others -- are finished by a whole-cloud scan, a wave per point.  With a cell so large that a
+cloud is one cell the first scan is the brute force.  Then `hfl_outlier_threshold`, `hfl_outlier_mask`, and the compaction
+of `ground.remove_ground`: `torch.nonzero`, `hfl_voxel_gather_rows`, one `searchsorted` on the host offsets.
+
+Batch limits as in `voxel.py`."""
+
+import math
+from typing import List, Sequence
+
+import numpy as np
+import torch
+
+from . import ops, voxel
+
+MAX_NEIGHBOURS = ops.KNN_MAX_NEIGHBOURS
+POINTS_PER_CELL = 2.0                  # the average the default cell size aims at, empty cells counted
+CELL_BUDGET_BYTES = 64 << 20           # the int32 cell-start tables of one batch
+FACE_MARGIN = 2.0 ** -20               # of the grid's extent along an axis: the absolute margin of the completeness bound
+_F = np.float32
+
+
+def _check_neighbours(nb_neighbors) -> int:
+    if isinstance(nb_neighbors, bool) or not isinstance(nb_neighbors, (int, np.integer)) or \
+            not 1 <= int(nb_neighbors) <= MAX_NEIGHBOURS:
+        raise ValueError('nb_neighbors must be an integer in 1..%d, got %r' % (MAX_NEIGHBOURS, nb_neighbors))
+    return int(nb_neighbors)
+
+
+def _check_positive(name: str, value) -> float:
+    v = float(value)
+    if not math.isfinite(v) or v <= 0.0:
+        raise ValueError('%s must be positive and finite, got %r' % (name, value))
+    return v
+
+
+def _nonfinite_error(i: int):
+    return ValueError('cloud %d holds a coordinate that is not finite' % i)
+
+
+def _no_point_error(i: int, step: str):
+    return ValueError('cloud %d has no point left after %s' % (i, step))
+
+
+def _as_arrays(clouds):
+    arrays = [np.ascontiguousarray(np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3))
+              for c in clouds]
+    voxel._check_batch([a.shape[0] for a in arrays])
+    return arrays
+
+
+def _pack(*parts):
+    """(result, optional extras...) -> the result alone, or the tuple of what was asked for"""
+    res = tuple(p for p in parts if p is not None)
+    return res[0] if len(res) == 1 else res
+
+
+# ------------------------------------------------------------------------------------------------ host route (numpy)
+def _knn_mean_host(a: np.ndarray, nb: int) -> np.ndarray:
+    """steps 1 and 2 for one (n, 3) fp32 cloud by brute force in row chunks -> (n,) fp32"""
+    n = a.shape[0]
+    k = min(nb, n)
+    x, y, z = a[:, 0], a[:, 1], a[:, 2]
+    out = np.empty(n, dtype=np.float32)
+    chunk = max(1, (1 << 23) // n)
+    with np.errstate(over='ignore', invalid='ignore'):
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
+            dx, dy, dz = x[s:e, None] - x[None, :], y[s:e, None] - y[None, :], z[s:e, None] - z[None, :]
+            d2 = (dx * dx + dy * dy) + dz * dz                   # fp32 arrays: every operation rounded once
+            near = np.partition(d2, k - 1, axis=1)[:, :k]
+            near.sort(axis=1)
+            root = np.sqrt(near)
+            acc = np.zeros(e - s, dtype=np.float32)
+            for i in range(k):                                   # ascending, one rounded add at a time (np.sum adds pairwise)
+                acc = acc + root[:, i]
+            out[s:e] = acc / _F(k)
+    return out
+
+
+def _threshold_host(avg: np.ndarray, std_ratio: float):
+    """steps 3 and 4 -> (mean, std, threshold, n_valid), float64"""
+    v = avg[avg > 0].astype(np.float64)
+    nv = int(v.shape[0])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = np.float64(v.sum()) / np.float64(nv)
+        std = np.sqrt(np.float64(((v - mean) ** 2).sum()) / np.float64(nv - 1))
+    return float(mean), float(std), float(mean + std_ratio * std), nv
+
+
+def _checked_arrays(clouds):
+    arrays = _as_arrays(clouds)
+    for i, a in enumerate(arrays):
+        if not np.isfinite(a).all():
+            raise _nonfinite_error(i)
+    return arrays
+
+
+def knn_mean_distance_host(clouds: Sequence, nb_neighbors: int = 20) -> List[np.ndarray]:
+    """Steps 1 and 2 of the module docstring in numpy fp32: per cloud the (n_i,) float32 mean distance to the
+    k = min(nb_neighbors, n_i) nearest points of the cloud, the point itself included.  Plain brute force, O(n^2): meant for
+    tests and small clouds."""
+    nb = _check_neighbours(nb_neighbors)
+    return [_knn_mean_host(a, nb) for a in _checked_arrays(clouds)]
+
+
+def remove_outliers_host(clouds: Sequence, nb_neighbors: int = 20, std_ratio: float = 3.0, *, return_mask: bool = False,
+                         return_distances: bool = False, return_stats: bool = False):
+    """The definition of the module docstring in numpy, fp32 for steps 1-2 and float64 for step 4: the route without a GPU
+    and the yardstick of the tests.  Brute force, O(n^2): meant for tests and small clouds.  List of (n_i, 3) clouds ->
+    list of (k_i, 3) float32 arrays, the kept rows in input order (k_i may be 0); with `return_mask` also the (n_i,) bool
+    masks, with `return_distances` the (n_i,) float32 avg, with `return_stats` per-cloud dicts 'mean', 'std', 'threshold'
+    (floats; NaN as step 4 says) and 'n_valid' (int).  A single valid point keeps nothing, as in open3d."""
+    nb = _check_neighbours(nb_neighbors)
+    ratio = _check_positive('std_ratio', std_ratio)
+    arrays = _checked_arrays(clouds)
+    avgs = [_knn_mean_host(a, nb) for a in arrays]
+    stats = [_threshold_host(avg, ratio) for avg in avgs]
+    with np.errstate(invalid='ignore'):
+        masks = [(avg > 0) & (avg.astype(np.float64) < s[2]) for avg, s in zip(avgs, stats)]
+    return _pack([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None, avgs if return_distances else None,
+                 [dict(mean=s[0], std=s[1], threshold=s[2], n_valid=s[3]) for s in stats] if return_stats else None)
+
+
+def trim_radius_host(clouds: Sequence, radius_max: float = 30.0, *, return_mask: bool = False):
+    """The radius trim in numpy float64 -> list of (k_i, 3) float32 arrays, the rows with sqrt(x x + y y) <= radius_max in
+    input order (k_i may be 0); with `return_mask` also the (n_i,) bool masks."""
+    r = _check_positive('radius_max', radius_max)
+    arrays = _as_arrays(clouds)
+    with np.errstate(over='ignore', invalid='ignore'):
+        masks = [np.linalg.norm(a[:, :2].astype(np.float64), axis=1) <= r for a in arrays]
+    return _pack([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None)
+
+
+# ------------------------------------------------------------------------------------------------ device route
+def _grid_dims(extent: np.ndarray, cell: float):
+    return np.floor(extent / cell).astype(np.int64) + 1
+
+
+def grid_layout(lo_hi: np.ndarray, sizes, nb: int, cell_size=None, budget_bytes: int = CELL_BUDGET_BYTES) -> np.ndarray:
+    """The search grids of a batch from the fp32 bounds (B, 6) and the cloud sizes -> `ops.KNN_GRID_DTYPE` rows.  The
+    default cell is the smallest at which a cloud has at most n / `POINTS_PER_CELL` cells; any cell, the caller's included,
+    is doubled until the cloud's cells fit its share of `budget_bytes`.  The grid only decides the speed."""
+    batch = len(sizes)
+    share = max(int(budget_bytes) // 4 // batch - 1, 1)
+    grids = np.zeros(batch, dtype=np.dtype(ops.KNN_GRID_DTYPE))
+    base = 0
+    for b, n in enumerate(sizes):
+        low = lo_hi[b, :3].astype(np.float64)
+        extent = lo_hi[b, 3:].astype(np.float64) - low
+        widest = float(extent.max())
+        if cell_size is not None:
+            cell = float(cell_size)
+        elif not widest > 0.0:
+            cell = 1.0
+        else:
+            want = max(min(n / POINTS_PER_CELL, share), 1.0)
+            small, large = widest * 2.0 ** -24, widest * 2.0             # bisect the monotone cell count in log space
+            for _ in range(48):
+                mid = math.sqrt(small * large)
+                if float(np.prod(_grid_dims(extent, mid).astype(np.float64))) <= want:
+                    large = mid
+                else:
+                    small = mid
+            cell = large
+        cell = float(_F(min(max(cell, 1e-30), 1e30)))
+        while float(np.prod(_grid_dims(extent, cell).astype(np.float64))) > share:
+            cell = float(_F(cell * 2.0))
+        nx, ny, nz = (int(d) for d in _grid_dims(extent, cell))
+        margin = [float(_F(FACE_MARGIN * d * cell)) for d in (nx, ny, nz)]
+        grids[b] = (lo_hi[b, 0], lo_hi[b, 1], lo_hi[b, 2], cell, margin[0], margin[1], margin[2], min(nb, n), nx, ny, nz, 0,
+                    base)
+        base += nx * ny * nz
+    return grids
+
+
+def _sorted_batch(pts, off, off_host, nb: int, cell_size):
+    """bounds and the finite check (the one host read before the search), the grids, keys, sort, gather"""
+    batch = len(off_host) - 1
+    bounds, flags = ops.voxel_bounds(pts, off), ops.cloud_nonfinite(pts, off)
+    host = torch.cat([bounds.reshape(-1), flags]).cpu().numpy()
+    lo_hi = ops.decode_voxel_bounds(host[:6 * batch])
+    for i in range(batch):
+        if host[6 * batch + i] or not np.isfinite(lo_hi[i]).all():
+            raise _nonfinite_error(i)
+    table = ops.KnnGridTable(grid_layout(lo_hi, np.diff(off_host).tolist(), nb, cell_size), pts.device)
+    keys = ops.knn_cell_keys(pts, off, table)
+    sorted_keys, perm = torch.sort(keys)
+    return table, ops.voxel_gather_rows(pts, perm), sorted_keys, perm
+
+
+def _knn_device(pts, off, off_host, nb: int, cell_size):
+    table, sorted_pts, sorted_keys, perm = _sorted_batch(pts, off, off_host, nb, cell_size)
+    return ops.knn_mean_dist(sorted_pts, sorted_keys, perm, off, table)
+
+
+def _check_cell(cell_size):
+    return None if cell_size is None else _check_positive('cell_size', cell_size)
+
+
+def knn_mean_distance(clouds: Sequence, nb_neighbors: int = 20, *, device='cuda', cell_size=None,
+                      return_pending: bool = False):
+    """`knn_mean_distance_host` on the device: list of (n_i,) float32 device tensors, bit for bit what the numpy route
+    returns, for any `cell_size` (the edge of the search grid's cells; the default is chosen per cloud).  With
+    `return_pending` also the number of points of the batch that the 3 x 3 x 3 scan could not prove complete and the
+    whole-cloud scan finished (a debug counter)."""
+    nb = _check_neighbours(nb_neighbors)
+    cell = _check_cell(cell_size)
+    ts = voxel._as_tensors(clouds)
+    device = voxel._device(device)
+    if not ts:
+        return ([], 0) if return_pending else []
+    with torch.cuda.device(device):
+        pts, off, off_host = voxel._upload(ts, device)
+        avg, pending = _knn_device(pts, off, off_host, nb, cell)
+        out = [avg[s:e] for s, e in zip(off_host[:-1], off_host[1:])]
+        return (out, int(pending.item())) if return_pending else out
+
+
+def _compact(pts, keep, off_host):
+    """the kept rows of every cloud in input order, as `ground.remove_ground` compacts its mask"""
+    index = torch.nonzero(keep).reshape(-1)                                  # ascending: the order of the input
+    rows = ops.voxel_gather_rows(pts, index)
+    ends = np.searchsorted(index.cpu().numpy(), off_host)                    # the kept rows before every cloud's first point
+    return [rows[s:e] for s, e in zip(ends[:-1], ends[1:])]
+
+
+def remove_outliers(clouds: Sequence, nb_neighbors: int = 20, std_ratio: float = 3.0, *, device='cuda',
+                    return_mask: bool = False, return_distances: bool = False, return_stats: bool = False, cell_size=None):
+    """List of raw (n_i, 3) clouds (numpy / torch, host or device) -> list of (k_i, 3) float32 device tensors: the rows the
+    statistical outlier filter of the module docstring keeps, in input order, bit for bit the rows `remove_outliers_host`
+    returns (k_i may be 0).  `return_mask`: also the (n_i,) bool masks; `return_distances`: the (n_i,) float32 avg;
+    `return_stats`: per-cloud dicts 'mean', 'std', 'threshold' (floats) and 'n_valid' (int).  A cloud with a single valid
+    point keeps nothing (std = 0 / 0 = NaN), as in open3d.  `cell_size` sets the edge of the search grid's cells and
+    changes no bit of any output.  `ValueError` for a bad parameter or an empty cloud (before the device is touched) and,
+    naming the cloud, for a coordinate that is not finite (before any kernel of the filter runs)."""
+    nb = _check_neighbours(nb_neighbors)
+    ratio = _check_positive('std_ratio', std_ratio)
+    cell = _check_cell(cell_size)
+    ts = voxel._as_tensors(clouds)
+    device = voxel._device(device)
+    if not ts:
+        return _pack([], [] if return_mask else None, [] if return_distances else None, [] if return_stats else None)
+    with torch.cuda.device(device):
+        pts, off, off_host = voxel._upload(ts, device)
+        avg, _ = _knn_device(pts, off, off_host, nb, cell)
+        stats = ops.outlier_threshold(avg, off, ratio)
+        keep = ops.outlier_mask(avg, off, stats)
+        split = list(zip(off_host[:-1], off_host[1:]))
+        return _pack(_compact(pts, keep, off_host),
+                     [keep[s:e].bool() for s, e in split] if return_mask else None,
+                     [avg[s:e] for s, e in split] if return_distances else None,
+                     [dict(mean=m, std=s, threshold=t, n_valid=int(v)) for m, s, t, v in stats.cpu().tolist()]
+                     if return_stats else None)
+
+
+def trim_radius(clouds: Sequence, radius_max: float = 30.0, *, device='cuda', return_mask: bool = False):
+    """`trim_radius_host` on the device: list of (k_i, 3) float32 device tensors, the rows with sqrt(x x + y y) <=
+    `radius_max` (float64) in input order, equal to the numpy route's; a cloud left empty comes back empty.  With
+    `return_mask` also the (n_i,) bool masks."""
+    r = _check_positive('radius_max', radius_max)
+    ts = voxel._as_tensors(clouds)
+    device = voxel._device(device)
+    if not ts:
+        return ([], []) if return_mask else []
+    with torch.cuda.device(device):
+        pts, _, off_host = voxel._upload(ts, device)
+        keep = ops.radius_mask(pts, r)
+        return _pack(_compact(pts, keep, off_host),
+                     [keep[s:e].bool() for s, e in zip(off_host[:-1], off_host[1:])] if return_mask else None)
+
+
+_remove_outliers = remove_outliers             # `clean_batch` takes a keyword of the same name
+
+
+def clean_batch(clouds: Sequence, device, radius_max=None, remove_outliers: bool = False, outlier_params=None,
+                at_least: int = 1) -> List[torch.Tensor]:
+    """The raw cleaning of the submap entry points of `voxel.py` and `retrieval.encode_clouds`: `trim_radius` (when
+    `radius_max` is given), then `remove_outliers(**outlier_params)`, the batch staying on the device between the two.
+    `ValueError` naming the first cloud a step leaves no point, or fewer than `at_least` points."""
+    out = clouds
+    steps = []
+    if radius_max is not None:
+        steps.append(('the radius trim', lambda c: trim_radius(c, radius_max, device=device)))
+    if remove_outliers:
+        steps.append(('outlier removal', lambda c: _remove_outliers(c, device=device, **(outlier_params or {}))))
+    for name, step in steps:
+        out = step(out)
+        for i, c in enumerate(out):
+            if c.shape[0] < 1:
+                raise _no_point_error(i, name)
+            if c.shape[0] < at_least:
+                raise ValueError('cloud %d has %d points left after %s, fewer than target = %d'
+                                 % (i, c.shape[0], name, at_least))
+    return out

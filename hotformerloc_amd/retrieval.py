@@ -184,7 +184,8 @@ def recall_from_indices(idx, truth_offsets, truth_indices, n_database: int, num_
 def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesian', normalize: bool = True,
                   octree_depth: int = 7, full_depth: int = 2, device='cuda', voxel_size=None,
                   normalise_submaps: bool = False, downsample_target=None, downsample_type: str = 'pnvlad',
-                  remove_ground: bool = False, ground_params=None, **prepare_kwargs):
+                  remove_ground: bool = False, ground_params=None, radius_max=None, remove_outliers: bool = False,
+                  outlier_params=None, **prepare_kwargs):
     """`get_latent_vectors` (`eval/pnv_evaluate.py:129-187`) without the file loading: raw (n, 3) clouds (a sequence or any
     iterable) -> (len, output_dim) fp32 descriptors on the GPU, `batch_size` clouds per forward (the last batch may be
     short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`.  With `voxel_size` and / or
@@ -194,10 +195,12 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
     fixed-size clouds of N points instead (the Oxford / CS-Campus3D format, `voxel.prepare_submaps_fixed`: the
     `downsample_type` 'pnvlad' or 'random' downsampler, then, when `normalise_submaps`, the normalisation with padding);
     it cannot be combined with `voxel_size`.  With `remove_ground` every batch of raw submaps first goes through the cloth
-    filter on the device (`ground.remove_ground(**ground_params)`), before whichever of the steps above is asked for."""
+    filter on the device (`ground.remove_ground(**ground_params)`), before whichever of the steps above is asked for.
+    With `radius_max` and / or `remove_outliers` every batch is cleaned before everything else (`outliers.clean_batch`:
+    the radius trim, then the statistical outlier filter with `outlier_params`)."""
     from .octree import build_batch_octree
     from .preprocess import prepare_clouds
-    from . import ground, voxel
+    from . import ground, outliers, voxel
     if batch_size < 1:
         raise ValueError('encode_clouds: batch_size >= 1 expected, got %d' % batch_size)
     if downsample_target is not None and voxel_size is not None:
@@ -209,17 +212,19 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
 
     def flush():
         src = batch
+        if radius_max is not None or remove_outliers:
+            src = outliers.clean_batch(batch, device, radius_max, remove_outliers, outlier_params)
         if downsample_target is not None:
-            src = voxel.prepare_submaps_fixed(batch, downsample_target, downsample=downsample_type,
+            src = voxel.prepare_submaps_fixed(src, downsample_target, downsample=downsample_type,
                                               normalise=normalise_submaps, device=device, **filtered)
         elif voxel_size is not None:
-            src = voxel.prepare_submaps(batch, voxel_size, normalise=normalise_submaps, device=device, **filtered)
+            src = voxel.prepare_submaps(src, voxel_size, normalise=normalise_submaps, device=device, **filtered)
         elif remove_ground:
-            src = ground.filter_batch(batch, device, ground_params)
+            src = ground.filter_batch(src, device, ground_params)
             if normalise_submaps:
                 src = voxel.normalise_submaps(src, device=device)
         elif normalise_submaps:
-            src = voxel.normalise_submaps(batch, device=device)
+            src = voxel.normalise_submaps(src, device=device)
         pts = prepare_clouds(src, coordinates=coordinates, normalize=normalize, device=device, **prepare_kwargs)
         octree = build_batch_octree(pts, octree_depth, full_depth, device)
         out.append(model({'octree': octree})['global'].float())

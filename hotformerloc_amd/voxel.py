@@ -55,7 +55,9 @@ and `points[rng.choice(len(points), size=k)]` draw the same rows) and gathered o
 padded rows are transformed by `hfl_submap_normalise_rows`, which shares its device code with `hfl_submap_normalise`.
 
 Ground removal (`postprocess_submaps.py --remove_ground`, the step before the downsample) is `ground.py`; the entry points
-`prepare_submaps` and `prepare_submaps_fixed` run it first with `remove_ground=True`."""
+`prepare_submaps` and `prepare_submaps_fixed` run it first with `remove_ground=True`.  The raw cleaning in front of it -- the
+radius trim and the statistical outlier filter -- is `outliers.py`; the same entry points run it before everything else with
+`radius_max=` / `remove_outliers=True`."""
 
 import math
 from typing import List, Sequence
@@ -241,13 +243,21 @@ def normalise_submaps(clouds: Sequence, device='cuda') -> List[torch.Tensor]:
 
 
 def prepare_submaps(clouds: Sequence, voxel_size: float, normalise: bool = True, device='cuda', *, remove_ground: bool = False,
-                    ground_params=None) -> List[torch.Tensor]:
+                    ground_params=None, radius_max=None, remove_outliers: bool = False,
+                    outlier_params=None) -> List[torch.Tensor]:
     """`voxel_downsample` then (when `normalise`) `normalise_submaps` without leaving the device: the normalisation reads
     the downsampled batch and its per-cloud offsets where the reduction left them, and flags, offsets and counts come back
     in one host read.  The result is what `prepare_clouds` takes; it equals the two calls chained bit for bit.  With
     `remove_ground` the raw batch first goes through `ground.remove_ground(**ground_params)` and stays on the device: the
     documented CS-Wild-Places order, remove the ground, downsample, normalise.  `ValueError`, naming the cloud, when the
-    filter leaves a cloud no point."""
+    filter leaves a cloud no point.  With `radius_max` and / or `remove_outliers` the raw batch is cleaned before all that
+    (`outliers.clean_batch`: `trim_radius`, then `remove_outliers(**outlier_params)`), as the reference trims and cleans
+    the raw points first; the result equals the chained public calls bit for bit, and a cloud left empty raises
+    `ValueError` naming it."""
+    if radius_max is not None or remove_outliers:
+        from . import outliers
+        _check_voxel_size(voxel_size)
+        clouds = outliers.clean_batch(clouds, device, radius_max, remove_outliers, outlier_params)
     if remove_ground:
         from . import ground
         _check_voxel_size(voxel_size)
@@ -708,16 +718,22 @@ def normalise_submaps_padded(downsampled: Sequence, raw: Sequence, target: int, 
 
 
 def prepare_submaps_fixed(clouds: Sequence, target: int = 4096, downsample: str = 'pnvlad', normalise: bool = True, seed=42,
-                          device='cuda', *, remove_ground: bool = False, ground_params=None) -> List[torch.Tensor]:
+                          device='cuda', *, remove_ground: bool = False, ground_params=None, radius_max=None,
+                          remove_outliers: bool = False, outlier_params=None) -> List[torch.Tensor]:
     """Raw submaps -> fixed-size clouds of `target` points (the Oxford / CS-Campus3D format): `pnvlad_downsample` or
     `random_downsample`, then (when `normalise`) `normalise_submaps_padded` against the raw clouds.  The batch is uploaded
     once and stays on the device between the steps; the result equals the chained calls bit for bit.  With `remove_ground`
     the batch first goes through `ground.remove_ground(**ground_params)`; the filtered cloud is then also the raw cloud the
     padding draws from, as in the reference, which reassigns its points.  `ValueError`, naming the cloud, when the filter
-    leaves a cloud fewer than `target` points."""
+    leaves a cloud fewer than `target` points.  With `radius_max` and / or `remove_outliers` the raw batch is cleaned before
+    all that (`outliers.clean_batch`), and the padding draws from the cleaned cloud."""
     if downsample not in ('pnvlad', 'random'):
         raise ValueError("downsample must be 'pnvlad' or 'random', got %r" % (downsample,))
     target = _check_target(target)
+    if radius_max is not None or remove_outliers:
+        from . import outliers
+        clouds = outliers.clean_batch(clouds, device, radius_max, remove_outliers, outlier_params,
+                                      at_least=target if downsample == 'pnvlad' else 1)
     if remove_ground:
         from . import ground
         clouds = ground.filter_batch(clouds, device, ground_params, at_least=target)

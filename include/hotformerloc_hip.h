@@ -342,6 +342,67 @@ int hfl_cloth_classify(uint8_t* keep, const float* heights, const hfl_cloth_desc
                        float resolution, float threshold, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 2d. Raw submaps: statistical outlier removal and the radius trim (csrc/outliers.hip; replaces
+ *     datasets/CSWildPlaces/processing_utils.py remove_outliers, i.e. open3d's remove_statistical_outlier, and the radius
+ *     cut of postprocess_wildplaces_ground.py).  The filter is defined in hotformerloc_amd/outliers.py and DESIGN.md
+ *     section 7g: fp32 squared distances (dx dx + dy dy) + dz dz, every operation rounded once; bit parity with open3d is
+ *     not claimed.
+ * ---------------------------------------------------------------------- */
+#define HFL_KNN_MAX_NEIGHBOURS 32         /* k of one cloud: the register list of the query is 8, 16 or 32 floats long */
+#define HFL_KNN_MAX_CELLS 268435455LL     /* cells of all grids of a call: the cell-start table holds one int32 per cell */
+#define HFL_KNN_PHASE_STARTS 1            /* the launches of hfl_knn_mean_dist, for running them one at a time */
+#define HFL_KNN_PHASE_QUERY 2
+#define HFL_KNN_PHASE_FALLBACK 4
+#define HFL_KNN_PHASE_ALL 7
+/* One cloud's search grid: nx x ny x nz cubic cells of edge `cell` from the corner (ox, oy, oz) = the cloud's fp32 minimum;
+ * a point's cell along an axis is int((p - o) / cell) in fp32, clamped into the grid; cell (ix, iy, iz) is entry
+ * cell_base + (iz ny + iy) nx + ix of the cell-start table.  k = min(nb_neighbors, points of the cloud).  mx, my, mz >= 0
+ * are the absolute margins by which the query shrinks its distance to a face of the scanned block along each axis
+ * (the caller sets 2^-20 of the grid's extent: sixteen times the worst rounding error of the cell assignment). */
+typedef struct {
+  float ox, oy, oz, cell;
+  float mx, my, mz;
+  int32_t k;
+  int32_t nx, ny, nz;
+  int32_t reserved;
+  int64_t cell_base;
+} hfl_knn_grid;
+/* flags[b] = 1 when cloud b holds a coordinate that is not finite, else 0 (the bounds of hfl_voxel_bounds cannot say: fminf
+ * and fmaxf drop a NaN).  A memset and one launch on `stream`; integer OR atomics. */
+int hfl_cloud_nonfinite(int32_t* flags, const float* points, const int64_t* cloud_offsets, int batch, int64_t n_points,
+                        hfl_stream_t stream);
+/* Every hfl_knn_* call takes the grids twice, as the hfl_cloth_* calls take their table: grids_host (HOST memory, batch
+ * rows) is checked before anything runs -- 1 <= nx, ny, nz, 1 <= k <= HFL_KNN_MAX_NEIGHBOURS, the grid inside
+ * [0, n_cells), finite corner, cell > 0, margins >= 0, else HFL_EINVAL -- and grids is the same table in device memory.
+ *
+ * keys[p] = the global cell of point p (cell_base of its cloud + its cell).  One launch on `stream`. */
+int hfl_knn_cell_keys(int64_t* keys, const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                      const float* points, const int64_t* cloud_offsets, int64_t n_points, hfl_stream_t stream);
+/* avg[p] = the mean over the k nearest points of p's own cloud, p itself included, of the distance to them: the k smallest
+ * fp32 squared distances, the correctly rounded root of each, added in ascending order from 0, divided by (float)k.  Exact
+ * (no approximate search) and a pure function of the input: the same bits for any grid.  sorted_keys / perm are the keys of
+ * hfl_knn_cell_keys in ascending order and the permutation of the sort (sorted position j came from row perm[j]);
+ * sorted_points (P,3) = points[perm].  cell_starts (n_cells + 1) int32, pending (P) int32 and counter (1) int32 are
+ * workspace; after the call *counter is the number of points the 3 x 3 x 3 block did not resolve, which the whole-cloud
+ * scan finished.  `phases` selects the launches (HFL_KNN_PHASE_ALL for the whole; a later phase needs the workspace an
+ * earlier one left).  A memset and three launches on `stream`, no synchronisation, no floating-point atomics. */
+int hfl_knn_mean_dist(float* avg, int32_t* pending, int32_t* counter, int32_t* cell_starts, const float* sorted_points,
+                      const int64_t* sorted_keys, const int64_t* perm, const hfl_knn_grid* grids_host,
+                      const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
+                      int phases, hfl_stream_t stream);
+/* stats (batch, 4) float64 = (mean, std, mean + std_ratio std, n_valid) over the valid rows (avg > 0) of every cloud, std
+ * with n_valid - 1 in the denominator; float64, summed in the order of hfl_pair_stats.  No valid row: mean = NaN; one: std =
+ * NaN.  One workgroup per cloud, one launch on `stream`.  std_ratio <= 0 or not finite: HFL_EINVAL. */
+int hfl_outlier_threshold(double* stats, const float* avg, const int64_t* cloud_offsets, int batch, int64_t n_points,
+                          double std_ratio, hfl_stream_t stream);
+/* keep[p] = 1 when avg[p] > 0 and double(avg[p]) < the threshold of p's cloud (stats[b][2]; NaN keeps nothing), else 0. */
+int hfl_outlier_mask(uint8_t* keep, const float* avg, const double* stats, const int64_t* cloud_offsets, int batch,
+                     int64_t n_points, hfl_stream_t stream);
+/* keep[p] = 1 when sqrt(x x + y y) <= radius_max, evaluated in float64 from the fp32 coordinates, every operation rounded
+ * once (what numpy's norm over the first two columns computes), else 0.  radius_max <= 0 or not finite: HFL_EINVAL. */
+int hfl_radius_mask(uint8_t* keep, const float* points, int64_t n_points, double radius_max, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 3. Octree convolution gather  (ocnn.nn.OctreeConv's octree2col; call sites
  *    models/layers/octformer_layers.py:89-95, models/octformer_backbone.py:470-475)
  * ---------------------------------------------------------------------- */
