@@ -10,6 +10,7 @@
 // LDS for the whole persistent block, and taps are issued in batches of independent
 // 16-B gathers so a CU keeps tens of KiB in flight (HBM/L2-latency bound op).
 #include "hfl_common.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -97,41 +98,94 @@ __global__ void __launch_bounds__(256) dwconv_fwd_vec4(float* __restrict__ out, 
 // (row, tap) pairs (model.OctreeConv._forward_live_taps: every output row adds its own partial products, in tap order, no
 // atomics).  Rounds 1-5 ran it as the depth-wise convolution above with unit weights -- 27 x C ones staged in LDS and a
 // multiply per element -- and added the convolution's bias in a separate pass; the sums are bitwise the same.
-template <int B>
+//
+// Only LIVE slots are loaded: 5.6 of 27 slots are live at depth 5, a stride-2 table has one live slot per child row, and a
+// dead slot used to cost a 16-B request per lane for a value that was thrown away (four requests of five).  The row's slots
+// become a bit mask -- TPR > 0: the row's TPR = C/4 lanes sit in one wave and classify slots tx, tx + TPR, ... with one
+// ballot per pass; TPR = 0 (any other width, rows may straddle waves): every lane reads the row's staged slots back -- and
+// the gather loop walks the set bits in ascending tap order, B gathers in flight per lane.  A row without a live slot reads
+// nothing from `part`.
+//
+// NORM > 0 (TPR > 0 only): the caller's LayerNorm [+ ReLU] over the sum that is sitting in the row's registers, instead of a
+// second launch that reads the (N, C) rows back: NORM = 1 stores f32 rows, NORM = 2 the split2 operand of the next GEMM.  The
+// row arithmetic is hfl_ln_row, the body of layer_norm_kernel: the same bits as the two launches.
+constexpr int kSlotMax = 32;
+
+template <int TPR, int NORM, int B>
 __global__ void __launch_bounds__(256) slot_sum_kernel(float* __restrict__ out, const float* __restrict__ part,
                                                         const int32_t* __restrict__ slot, const float* __restrict__ bias,
-                                                        int64_t n_out, int C, int K, int tpr, int rpb) {
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        int64_t n_out, int C_rt, int K, int tpr_rt, int rpb, float eps, int relu) {
+  static_assert(NORM == 0 || TPR > 0, "the fused norm needs the row inside one wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int32_t* s_idx = reinterpret_cast<int32_t*>(smem);
+  const int tpr = TPR > 0 ? TPR : tpr_rt;
+  const int C = TPR > 0 ? TPR * 4 : C_rt;
   const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr;
   const float4 bv = bias != nullptr ? reinterpret_cast<const float4*>(bias)[tx] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 gm[1], bt[1];
+  if (NORM) {
+    gm[0] = reinterpret_cast<const float4*>(gamma)[tx];
+    bt[0] = reinterpret_cast<const float4*>(beta)[tx];
+  }
+  int32_t* row_idx = s_idx + ty * K;
   for (int64_t base = (int64_t)blockIdx.x * rpb; base < n_out; base += (int64_t)gridDim.x * rpb) {
     const int64_t h = base + ty;
     const bool live = h < n_out;
-    __syncthreads();
-    if (live)
-      for (int k = tx; k < K; k += tpr) s_idx[ty * K + k] = slot[h * K + k];
-    __syncthreads();
-    if (!live) continue;
+    unsigned mask = 0;                                    // bit k: slot k of the row is live
+    if (TPR > 0) {
+      // the row's lanes are TPR consecutive lanes of one wave: its slot list is private to the wave (no block barrier)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();                    // the previous row's readers are done
+      const int shift = (threadIdx.x & 63) - tx;          // first lane of this row inside the wave
+      constexpr unsigned long long row_lanes = TPR >= 64 ? ~0ull : ((1ull << (TPR & 63)) - 1ull);
+#pragma unroll
+      for (int p = 0; p * TPR < kSlotMax; ++p) {
+        const int k = p * TPR + tx;
+        const bool in = live && k < K;
+        const int32_t ni = in ? slot[h * K + k] : -1;
+        if (in) row_idx[k] = ni;
+        const unsigned long long bal = __ballot(ni >= 0);
+        mask |= (unsigned)((bal >> shift) & row_lanes & 0xffffffffull) << (p * TPR);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      __syncthreads();
+      if (live)
+        for (int k = tx; k < K; k += tpr) row_idx[k] = slot[h * K + k];
+      __syncthreads();
+      if (live)
+        for (int k = 0; k < K; ++k) mask |= (unsigned)(row_idx[k] >= 0) << k;
+    }
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 1
-    for (int k0 = 0; k0 < K; k0 += B) {
+    while (mask != 0) {
+      int32_t ni[B];
       float4 v[B];
       bool ok[B];
 #pragma unroll
-      for (int j = 0; j < B; ++j) {
-        const int k = k0 + j;
-        int64_t ni = (k < K) ? (int64_t)s_idx[ty * K + k] : -1;
-        ok[j] = ni >= 0;
-        if (!ok[j]) ni = 0;
-        v[j] = reinterpret_cast<const float4*>(part + ni * C)[tx];
+      for (int j = 0; j < B; ++j) {                       // the next B live slots, ascending
+        ok[j] = mask != 0;
+        const int k = ok[j] ? __ffs(mask) - 1 : 0;
+        mask &= mask - 1;
+        ni[j] = row_idx[k];
       }
+#pragma unroll
+      for (int j = 0; j < B; ++j)
+        if (ok[j]) v[j] = reinterpret_cast<const float4*>(part + (int64_t)ni[j] * C)[tx];
 #pragma unroll
       for (int j = 0; j < B; ++j)
         if (ok[j]) { acc.x += v[j].x; acc.y += v[j].y; acc.z += v[j].z; acc.w += v[j].w; }
     }
     if (bias != nullptr) { acc.x += bv.x; acc.y += bv.y; acc.z += bv.z; acc.w += bv.w; }
-    reinterpret_cast<float4*>(out + h * C)[tx] = acc;
+    if constexpr (NORM > 0) {
+      // all lanes of the wave: the statistics are butterflies over the row's lanes (a row past the end holds zeros)
+      float4 a[1] = {live ? acc : make_float4(0.f, 0.f, 0.f, 0.f)};
+      hfl_ln_row<TPR, 1, NORM == 2 ? 2 : 0>(out, a, gm, bt, h, live, tx, eps, relu);
+    } else {
+      if (live) reinterpret_cast<float4*>(out + h * C)[tx] = acc;
+    }
   }
 }
 
@@ -498,6 +552,23 @@ static int launch_cpe(float* out, float* conv_out, const float* x, const float* 
   HFL_RETURN_LAST_ERROR();
 }
 
+
+// eight gathers in flight per lane: most rows (4-6 live slots) take one trip of the gather loop
+template <int TPR, int NORM>
+static int launch_slot_sum(float* out, const float* part, const int32_t* slot, const float* bias, const float* gamma,
+                           const float* beta, int64_t n_out, int64_t channels, int K, float eps, int relu, hipStream_t s) {
+  const RowGeom g = row_geom(channels);
+  const size_t lds = (size_t)g.rpb * K * sizeof(int32_t);
+  static int nb = 0;
+  static size_t nb_lds = 0;
+  const int per_cu = persistent_per_cu(reinterpret_cast<const void*>(slot_sum_kernel<TPR, NORM, 8>), g.tpr * g.rpb, lds, 8, &nb,
+                                       &nb_lds);
+  const int64_t need = hfl_cdiv(n_out, g.rpb), cap = (int64_t)hfl_stream_cus(s) * per_cu;
+  slot_sum_kernel<TPR, NORM, 8><<<(int)(need < cap ? need : cap), g.tpr * g.rpb, lds, s>>>(
+      out, part, slot, bias, gamma, beta, n_out, (int)channels, K, g.tpr, g.rpb, eps, relu);
+  HFL_RETURN_LAST_ERROR();
+}
+
 }  // namespace
 
 extern "C" {
@@ -603,18 +674,40 @@ int hfl_inverse_table(int32_t* inverse, int64_t n_src_rows, const int32_t* table
 /* see include/hotformerloc_hip.h */
 int hfl_slot_sum(float* out, const float* part, const int32_t* slot, const float* bias, int64_t n_out, int64_t channels, int kngh,
                  hfl_stream_t stream) {
-  if (n_out < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024 || kngh <= 0 || kngh > kMaxTaps) return HFL_EINVAL;
+  if (n_out < 0 || channels <= 0 || channels % 4 != 0 || channels > 1024 || kngh <= 0 || kngh > kSlotMax) return HFL_EINVAL;
   if (n_out == 0) return HFL_OK;
   if (out == nullptr || part == nullptr || slot == nullptr) return HFL_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const RowGeom g = row_geom(channels);
-  const size_t lds = (size_t)g.rpb * kngh * sizeof(int32_t);
-  static int nb = 0;
-  static size_t nb_lds = 0;
-  const int per_cu = persistent_per_cu(reinterpret_cast<const void*>(slot_sum_kernel<9>), g.tpr * g.rpb, lds, 8, &nb, &nb_lds);
-  const int64_t need = hfl_cdiv(n_out, g.rpb), cap = (int64_t)hfl_stream_cus(s) * per_cu;
-  slot_sum_kernel<9><<<(int)(need < cap ? need : cap), g.tpr * g.rpb, lds, s>>>(out, part, slot, bias, n_out, (int)channels, kngh,
-                                                                               g.tpr, g.rpb);
-  HFL_RETURN_LAST_ERROR();
+  switch (channels) {
+    case 256: return launch_slot_sum<64, 0>(out, part, slot, bias, nullptr, nullptr, n_out, channels, kngh, 0.f, 0, s);
+    case 128: return launch_slot_sum<32, 0>(out, part, slot, bias, nullptr, nullptr, n_out, channels, kngh, 0.f, 0, s);
+    case 64:  return launch_slot_sum<16, 0>(out, part, slot, bias, nullptr, nullptr, n_out, channels, kngh, 0.f, 0, s);
+    case 32:  return launch_slot_sum<8, 0>(out, part, slot, bias, nullptr, nullptr, n_out, channels, kngh, 0.f, 0, s);
+    default:  return launch_slot_sum<0, 0>(out, part, slot, bias, nullptr, nullptr, n_out, channels, kngh, 0.f, 0, s);
+  }
+}
+
+/* see include/hotformerloc_hip.h */
+int hfl_slot_sum_norm(float* out_f32, uint16_t* out_split2, const float* part, const int32_t* slot, const float* bias,
+                      const float* gamma, const float* beta, int64_t n_out, int64_t channels, int kngh, float eps, int relu,
+                      hfl_stream_t stream) {
+  if (n_out < 0 || kngh <= 0 || kngh > kSlotMax || (out_f32 == nullptr) == (out_split2 == nullptr)) return HFL_EINVAL;
+  if (channels != 32 && channels != 64 && channels != 128 && channels != 256) return HFL_EINVAL;
+  if (out_split2 != nullptr && channels % 32 != 0) return HFL_EINVAL;
+  if (n_out == 0) return HFL_OK;
+  if (part == nullptr || slot == nullptr || gamma == nullptr || beta == nullptr) return HFL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* out = out_f32 != nullptr ? out_f32 : reinterpret_cast<float*>(out_split2);
+  const int r = relu ? 1 : 0;
+#define HFL_SLOT_NORM(TPR)                                                                                                    \
+  return out_split2 != nullptr ? launch_slot_sum<TPR, 2>(out, part, slot, bias, gamma, beta, n_out, channels, kngh, eps, r, s) \
+                               : launch_slot_sum<TPR, 1>(out, part, slot, bias, gamma, beta, n_out, channels, kngh, eps, r, s)
+  switch (channels) {
+    case 256: HFL_SLOT_NORM(64);
+    case 128: HFL_SLOT_NORM(32);
+    case 64:  HFL_SLOT_NORM(16);
+    default:  HFL_SLOT_NORM(8);
+  }
+#undef HFL_SLOT_NORM
 }
 }  // extern "C"

@@ -385,7 +385,10 @@ __global__ void token_meta_kernel(uint32_t* __restrict__ meta, const int64_t* __
 //   edges (taps + 1)   pairs of tap k are [edges[k], edges[k+1])
 // Three launches, no atomics, fixed order: per-block per-tap counts (wave ballots), a scan over blocks
 // (one wave per tap), then the fill pass recomputes the ballots and writes.
-constexpr int kTapRows = 1024;         // rows per block (256 threads x 4)
+// rows per block: one row per thread.  (Rounds 2-6 gave a block four 256-row slices, walked one after the other with three
+// block barriers each: a few hundred four-wave blocks for 256 CUs, the launch bound by that serial walk and not by the few
+// tens of MB it moves.  One slice per block puts several blocks on every CU; the scan covers four times the block counts.)
+constexpr int kTapRows = 256;
 constexpr int kTapMax = 32;
 constexpr int kTapTables = 16;         // tables per launch (hfl_tap_lists_multi)
 
@@ -454,20 +457,17 @@ __device__ __forceinline__ void tap_count_body(const TapTable& t, int block, int
   __shared__ int32_t wave_cnt[4][kTapMax];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int taps = TAPS > 0 ? TAPS : t.taps;
-  int32_t acc[kTapMax];
-#pragma unroll
-  for (int k = 0; k < kTapMax; ++k) acc[k] = 0;
+  static_assert(kTapRows == 256, "one row per thread");
   const int64_t row0 = (int64_t)block * kTapRows;
   int32_t* lds_wave = lds + wave * (64 * (TAPS > 0 ? TAPS : 1));
-  for (int it = 0; it < kTapRows / 256; ++it) {
-    int32_t v[kTapMax];
-    tap_load_rows<TAPS>(t.table, t.rows, row0 + it * 256 + wave * 64, lds_wave, lane, v, taps);
+  int32_t v[kTapMax];
+  tap_load_rows<TAPS>(t.table, t.rows, row0 + wave * 64, lds_wave, lane, v, taps);
 #pragma unroll
-    for (int k = 0; k < kTapMax; ++k)
-      if (k < taps) acc[k] += __popcll(__ballot(v[k] >= 0));
-  }
-  if (lane == 0)
-    for (int k = 0; k < taps; ++k) wave_cnt[wave][k] = acc[k];
+  for (int k = 0; k < kTapMax; ++k)
+    if (k < taps) {
+      const int32_t c = __popcll(__ballot(v[k] >= 0));
+      if (lane == 0) wave_cnt[wave][k] = c;
+    }
   __syncthreads();
   if ((int)threadIdx.x < taps)
     t.block_counts[(int64_t)block * taps + threadIdx.x] =
@@ -531,57 +531,50 @@ __device__ __forceinline__ void tap_fill_body(const TapTable& t, int block, int3
   const int64_t row0 = (int64_t)block * kTapRows;
   const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   int32_t* lds_wave = lds + wave * (64 * (TAPS > 0 ? TAPS : 1));
-  for (int it = 0; it < kTapRows / 256; ++it) {
-    const int64_t rw = row0 + it * 256 + wave * 64;       // first row of this wave
-    const int64_t r = rw + lane;
-    const bool in = r < t.rows;
-    int32_t v[kTapMax];
-    unsigned long long mk[kTapMax];
-    tap_load_rows<TAPS>(t.table, t.rows, rw, lds_wave, lane, v, taps);
+  const int64_t rw = row0 + wave * 64;                    // first row of this wave
+  const int64_t r = rw + lane;
+  const bool in = r < t.rows;
+  int32_t v[kTapMax];
+  unsigned long long mk[kTapMax];
+  tap_load_rows<TAPS>(t.table, t.rows, rw, lds_wave, lane, v, taps);
+#pragma unroll
+  for (int k = 0; k < kTapMax; ++k)
+    if (k < taps) {
+      mk[k] = __ballot(v[k] >= 0);
+      if (lane == 0) wave_cnt[wave][k] = __popcll(mk[k]);
+    }
+  __syncthreads();                         // base[] and wave_cnt[] ready
+  int32_t pos[kTapMax];
+#pragma unroll
+  for (int k = 0; k < kTapMax; ++k) {
+    if (k < taps) {
+      int32_t off = base[k];
+      for (int w = 0; w < wave; ++w) off += wave_cnt[w][k];
+      pos[k] = v[k] >= 0 ? off + __popcll(mk[k] & lt) : -1;
+      if (in && v[k] >= 0) t.src[pos[k]] = v[k];
+    }
+  }
+  // slot rows leave the way the table rows came in: through the wave's LDS block, whole lines per store instruction
+  if constexpr (TAPS == 8) {
+    if (in) {
+      reinterpret_cast<int4*>(t.slot)[r * 2] = make_int4(pos[0], pos[1], pos[2], pos[3]);
+      reinterpret_cast<int4*>(t.slot)[r * 2 + 1] = make_int4(pos[4], pos[5], pos[6], pos[7]);
+    }
+  } else if constexpr (TAPS > 0) {
+#pragma unroll
+    for (int k = 0; k < TAPS; ++k) lds_wave[lane * TAPS + k] = pos[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int64_t w0 = rw * TAPS, wend = t.rows * TAPS;
+#pragma unroll
+    for (int j = 0; j < TAPS; ++j) {
+      const int64_t w = w0 + j * 64 + lane;
+      if (w < wend) t.slot[w] = lds_wave[j * 64 + lane];
+    }
+  } else {
 #pragma unroll
     for (int k = 0; k < kTapMax; ++k)
-      if (k < taps) mk[k] = __ballot(v[k] >= 0);
-    __syncthreads();                       // base[] ready (first pass) / updated (later passes)
-    if (lane == 0)
-      for (int k = 0; k < taps; ++k) wave_cnt[wave][k] = __popcll(mk[k]);
-    __syncthreads();
-    int32_t pos[kTapMax];
-#pragma unroll
-    for (int k = 0; k < kTapMax; ++k) {
-      if (k < taps) {
-        int32_t off = base[k];
-        for (int w = 0; w < wave; ++w) off += wave_cnt[w][k];
-        pos[k] = v[k] >= 0 ? off + __popcll(mk[k] & lt) : -1;
-        if (in && v[k] >= 0) t.src[pos[k]] = v[k];
-      }
-    }
-    // slot rows leave the way the table rows came in: through the wave's LDS block, whole lines per store instruction
-    if constexpr (TAPS == 8) {
-      if (in) {
-        reinterpret_cast<int4*>(t.slot)[r * 2] = make_int4(pos[0], pos[1], pos[2], pos[3]);
-        reinterpret_cast<int4*>(t.slot)[r * 2 + 1] = make_int4(pos[4], pos[5], pos[6], pos[7]);
-      }
-    } else if constexpr (TAPS > 0) {
-#pragma unroll
-      for (int k = 0; k < TAPS; ++k) lds_wave[lane * TAPS + k] = pos[k];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const int64_t w0 = rw * TAPS, wend = t.rows * TAPS;
-#pragma unroll
-      for (int j = 0; j < TAPS; ++j) {
-        const int64_t w = w0 + j * 64 + lane;
-        if (w < wend) t.slot[w] = lds_wave[j * 64 + lane];
-      }
-      __builtin_amdgcn_wave_barrier();
-    } else {
-#pragma unroll
-      for (int k = 0; k < kTapMax; ++k)
-        if (k < taps && in) t.slot[r * taps + k] = pos[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < taps)
-      base[threadIdx.x] += wave_cnt[0][threadIdx.x] + wave_cnt[1][threadIdx.x] + wave_cnt[2][threadIdx.x] +
-                           wave_cnt[3][threadIdx.x];
+      if (k < taps && in) t.slot[r * taps + k] = pos[k];
   }
 }
 

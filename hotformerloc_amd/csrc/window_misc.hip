@@ -2,6 +2,7 @@
 // (octree2col), relay-token initialisation (masked window mean), ADaPE window
 // statistics and the segment softmax of the attentional pooling head.
 #include "hfl_common.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -240,40 +241,8 @@ segment_softmax_kernel(float* __restrict__ scores, const int64_t* __restrict__ r
 // ------------------------------------------------------------------ LayerNorm
 // One row = TPR lanes x VPL float4 (C = 4*TPR*VPL); 256-thread blocks, grid-stride over rows.
 // Optional fused residual: xo = x + y (+ bias), h = LN(xo).  Pure streaming (HBM-bound).
-// fp32 -> (hi, lo) bf16 with hi = RNE(v), lo = RNE(v - hi): v ~= hi + lo to 2^-17 relative.
-__device__ __forceinline__ uint16_t hfl_bf16_rne(float v) {
-  uint32_t u = __float_as_uint(v);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ void hfl_split4(const float4 v, uint2& hi, uint2& lo) {
-  const uint16_t h0 = hfl_bf16_rne(v.x), h1 = hfl_bf16_rne(v.y), h2 = hfl_bf16_rne(v.z), h3 = hfl_bf16_rne(v.w);
-  const uint16_t l0 = hfl_bf16_rne(v.x - __uint_as_float((uint32_t)h0 << 16));
-  const uint16_t l1 = hfl_bf16_rne(v.y - __uint_as_float((uint32_t)h1 << 16));
-  const uint16_t l2 = hfl_bf16_rne(v.z - __uint_as_float((uint32_t)h2 << 16));
-  const uint16_t l3 = hfl_bf16_rne(v.w - __uint_as_float((uint32_t)h3 << 16));
-  hi = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16));
-  lo = make_uint2((uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2 | ((uint32_t)l3 << 16));
-}
-// row of the split-GEMM A operand: [hi (C) | hi (C) | lo (C)] bf16, so that one bf16 GEMM against
-// [w_hi | w_lo | w_hi] accumulates hi*hi + hi*lo + lo*hi in fp32
-__device__ __forceinline__ void hfl_store_split3(uint16_t* row, int C, int c4, const float4 v) {
-  uint2 hi, lo;
-  hfl_split4(v, hi, lo);
-  reinterpret_cast<uint2*>(row)[c4] = hi;
-  reinterpret_cast<uint2*>(row + C)[c4] = hi;
-  reinterpret_cast<uint2*>(row + 2 * C)[c4] = lo;
-}
-
-// row of the hand-written split GEMM's operand (csrc/gemm_x3.hip): per 32-channel block [32 x hi | 32 x lo]
-__device__ __forceinline__ void hfl_store_split2(uint16_t* row, int c4, const float4 v) {
-  uint2 hi, lo;
-  hfl_split4(v, hi, lo);
-  uint16_t* o = row + (c4 >> 3) * 64 + (c4 & 7) * 4;
-  *reinterpret_cast<uint2*>(o) = hi;
-  *reinterpret_cast<uint2*>(o + 32) = lo;
-}
-
+// The row arithmetic (statistics, affine, ReLU, the f32 / split stores) is hfl_ln_row of csrc/ln_row.h, shared with the
+// octree convolution's slot sum (csrc/dwconv.hip).
 // SPLIT: 0 = fp32 output, 1 = bf16 [hi|hi|lo] (K-concatenated, hipBLASLt route), 2 = bf16 split2 (gemm_x3 route)
 template <int TPR, int VPL, bool ADD, int SPLIT>
 __global__ void __launch_bounds__(256)
@@ -291,12 +260,10 @@ layer_norm_kernel(float* __restrict__ h_out, float* x_out, const float* x, const
     bs[v] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (ADD && bias != nullptr) bs[v] = reinterpret_cast<const float4*>(bias)[v * TPR + tx];
   }
-  const float inv_c = 1.0f / (float)C;
   for (int64_t base = (int64_t)blockIdx.x * RPB; base < n_rows; base += (int64_t)gridDim.x * RPB) {
     const int64_t r = base + ty;
     const bool live = r < n_rows;
     float4 a[VPL];
-    float sum = 0.f;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
       a[v] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -309,35 +276,8 @@ layer_norm_kernel(float* __restrict__ h_out, float* x_out, const float* x, const
           reinterpret_cast<float4*>(x_out + r * C)[v * TPR + tx] = a[v];
         }
       }
-      sum += (a[v].x + a[v].y) + (a[v].z + a[v].w);
     }
-    const float mean = hfl_group_sum<TPR>(sum) * inv_c;
-    float sq = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      a[v].x -= mean; a[v].y -= mean; a[v].z -= mean; a[v].w -= mean;
-      sq += (a[v].x * a[v].x + a[v].y * a[v].y) + (a[v].z * a[v].z + a[v].w * a[v].w);
-    }
-    const float rstd = 1.0f / sqrtf(hfl_group_sum<TPR>(sq) * inv_c + eps);
-    if (live) {
-#pragma unroll
-      for (int v = 0; v < VPL; ++v) {
-        float4 o;
-        o.x = fmaf(a[v].x * rstd, gm[v].x, bt[v].x);
-        o.y = fmaf(a[v].y * rstd, gm[v].y, bt[v].y);
-        o.z = fmaf(a[v].z * rstd, gm[v].z, bt[v].z);
-        o.w = fmaf(a[v].w * rstd, gm[v].w, bt[v].w);
-        if (relu) {                              // conv -> norm -> ReLU of the stem (octformer_layers.py:80-98) in one pass
-          o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        }
-        if (SPLIT == 1)
-          hfl_store_split3(reinterpret_cast<uint16_t*>(h_out) + r * 3 * C, C, v * TPR + tx, o);
-        else if (SPLIT == 2)
-          hfl_store_split2(reinterpret_cast<uint16_t*>(h_out) + r * 2 * C, v * TPR + tx, o);
-        else
-          reinterpret_cast<float4*>(h_out + r * C)[v * TPR + tx] = o;
-      }
-    }
+    hfl_ln_row<TPR, VPL, SPLIT>(h_out, a, gm, bt, r, live, tx, eps, relu);
   }
 }
 

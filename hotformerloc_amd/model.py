@@ -119,6 +119,9 @@ _NATIVE_BLOCK = True
 # The relay-token block as ONE launch (hfl_relay_block_fused_x3, csrc/relay_block.hip) where hfl_relay_block_fused_ok takes the
 # shape (C = 256, 16 heads, at most 64 relay tokens per cloud); False: its five launches everywhere (routes: _native_route).
 _RELAY_FUSED = True
+# The LayerNorm [+ ReLU] behind an octree convolution inside the convolution's last launch (hfl_slot_sum_norm) on the inference
+# live-tap routes; False: slot sum and norm as two launches everywhere.
+_CONV_NORM_FUSED = True
 _Q_PRESCALE = 16 ** -0.5 * 1.4426950408889634    # folded into q for the fp16-MFMA attention kernels: head dim 16's scale x log2 e
 
 
@@ -463,6 +466,15 @@ class OctreeDropPath(nn.Module):
 
 
 # --------------------------------------------------------------------------- convs
+class _NormTail:
+    """The caller's LayerNorm [+ ReLU] [+ split2 hand-over], offered to an OctreeConv for its last launch; the convolution
+    sets `done` where its route took it (the x3 / x6 live-tap routes), and the caller runs the norm itself where not."""
+    __slots__ = ('norm', 'relu', 'split2', 'done')
+
+    def __init__(self, norm: nn.LayerNorm, relu: bool, split2: bool = False):
+        self.norm, self.relu, self.split2, self.done = norm, relu, split2, False
+
+
 class OctreeConv(nn.Module):
     """`ocnn.nn.OctreeConv` (nempty=True): parameter `weights` (kdim, Cin, Cout) [+ `bias`].
     gather through the neighbour / child table (HIP) then one fp32 GEMM."""
@@ -487,14 +499,14 @@ class OctreeConv(nn.Module):
                 and _GEMM_MODE == 'x3' and self.in_channels % 32 == 0
                 and (self.out_channels % 128 == 0 or self.out_channels == 64) and not _grad_path())
 
-    def forward(self, data: torch.Tensor, octree, depth: int):
+    def forward(self, data: torch.Tensor, octree, depth: int, tail: Optional[_NormTail] = None):
         if data.dtype == torch.bfloat16:                 # split2 rows from the previous layer's fused norm + ReLU
             assert self.takes_split2() and data.shape[1] == 2 * self.in_channels
-            return self._forward_live_taps(data, octree, depth)
+            return self._forward_live_taps(data, octree, depth, tail)
         if (_SPARSE_CONV and (self.kernel, self.stride) in (('333', 1), ('222', 2)) and self.in_channels >= 32
                 and data.is_cuda):
             if not _grad_path(data):
-                return self._forward_live_taps(data, octree, depth)
+                return self._forward_live_taps(data, octree, depth, tail)
             if self.in_channels % 64 == 0 and self.out_channels % 64 == 0:      # tile shape of hfl_tap_wgrad
                 out = ag.live_tap_conv(data, self.weights, octree, depth, self.kernel, self.stride)
                 return out if self.bias is None else out + self.bias
@@ -508,7 +520,7 @@ class OctreeConv(nn.Module):
         return torch.mm(col, w)
 
 
-    def _forward_live_taps(self, data, octree, depth):
+    def _forward_live_taps(self, data, octree, depth, tail=None):
         """3x3x3 (stride 1) or 2x2x2 (stride 2) conv over the LIVE taps only.  The dense form gathers (N, 27*Cin) -- 80 % zeros on surface-like
         clouds (5.6 live taps of 27 at depth 5, 4 at depth 6) -- and multiplies all of it.  Here: gather one row
         per live (row, tap) pair in tap-major order, one GEMM per tap on its contiguous slice (W[k] is (Cin, Cout)),
@@ -530,7 +542,7 @@ class OctreeConv(nn.Module):
                 gs = ops.octree_gather(d2.view(torch.float32), src).view(torch.bfloat16)
                 part = ops.linear_x3_grouped(gs, ag._tap_blocks(self.weights, True, npad, ops.split2, 'taps2'),
                                              octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
-            return self._slot_sum(part, slot)
+            return self._slot_sum(part, slot, tail)
         if (_GEMM_MODE == 'x6' and not _grad_path() and data.dtype == torch.float32 and edges[-1] > 0
                 and self.in_channels % 32 == 0 and (self.out_channels % 128 == 0 or self.out_channels == 64)):
             # matched precision: the same grouped launch on hfl_linear_x6 (fp32-grade products; the tile loader gathers the pairs'
@@ -538,7 +550,7 @@ class OctreeConv(nn.Module):
             npad = max(self.out_channels, 128)
             part = ops.linear_x6_grouped_gather(data, src, ag._tap_blocks(self.weights, True, npad),
                                                 octree.tap_tiles(depth, self.kernel, self.stride, npad), self.out_channels)
-            return self._slot_sum(part, slot)
+            return self._slot_sum(part, slot, tail)
         g = ops.octree_gather(data, src)                                  # (P, Cin)
         part = torch.empty((g.shape[0], self.out_channels), dtype=torch.float32, device=data.device)
         w = self.weights
@@ -547,8 +559,14 @@ class OctreeConv(nn.Module):
                 torch.mm(g[edges[k]:edges[k + 1]], w[k], out=part[edges[k]:edges[k + 1]])
         return self._slot_sum(part, slot)
 
-    def _slot_sum(self, part, slot):
-        """every output row adds the partial products of its own live taps (+ the bias) in one pass (hfl_slot_sum)"""
+    def _slot_sum(self, part, slot, tail=None):
+        """every output row adds the partial products of its own live taps (+ the bias) in one pass (hfl_slot_sum); with the
+        caller's norm `tail` in the same pass where the kernel takes the width (hfl_slot_sum_norm)"""
+        if (tail is not None and _CONV_NORM_FUSED and part.shape[1] in ops._SLOT_NORM_CHANNELS and slot.shape[1] <= 32
+                and slot.dtype == torch.int32 and slot.shape[0] > 0):
+            tail.done = True
+            return ops.slot_sum_norm(part, slot, self.bias, tail.norm.weight, tail.norm.bias, tail.norm.eps, relu=tail.relu,
+                                     split2=tail.split2)
         if part.shape[1] % 4 == 0 and part.shape[1] <= 1024 and slot.shape[1] <= 27 and slot.dtype == torch.int32:
             return ops.slot_sum(part, slot, self.bias)
         out = ops.dwconv_forward_backward(part, self._unit(part.device), slot)
@@ -583,7 +601,10 @@ class OctreeConvNormRelu(nn.Module):
 
     def forward(self, data, octree, depth, split2_out: bool = False):
         """`split2_out` (inference): return the split2 operand of the next convolution's GEMM instead of fp32 rows."""
-        y = self.conv(data, octree, depth)
+        tail = _NormTail(self.norm, True, split2_out)
+        y = self.conv(data, octree, depth, tail)
+        if tail.done:
+            return y
         if y.is_cuda and not _grad_path(y) and y.shape[-1] in ops._LN_CHANNELS:
             return ops.layer_norm_relu(y, self.norm.weight, self.norm.bias, self.norm.eps, split2=split2_out)
         y = F.relu_(_ln(y, self.norm))
@@ -637,7 +658,9 @@ class Downsample(nn.Module):
         self.norm = nn.LayerNorm(out_channels)
 
     def forward(self, data, octree, depth):
-        return _ln(self.conv(data, octree, depth), self.norm)
+        tail = _NormTail(self.norm, False)
+        y = self.conv(data, octree, depth, tail)
+        return y if tail.done else _ln(y, self.norm)
 
 
 # ---------------------------------------------------------------- transformer parts

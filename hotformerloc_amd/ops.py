@@ -175,6 +175,30 @@ def slot_sum(part: torch.Tensor, slot: torch.Tensor, bias=None):
     return out
 
 
+_SLOT_NORM_CHANNELS = (32, 64, 128, 256)
+
+
+def slot_sum_norm(part: torch.Tensor, slot: torch.Tensor, bias, weight, norm_bias, eps: float = 1e-5, relu: bool = False,
+                  split2: bool = False):
+    """[relu](LN(slot_sum(part, slot, bias))) in the slot sum's own pass (hfl_slot_sum_norm): fp32 rows, or -- `split2` -- the
+    bf16 split2 operand (rows, 2C) of the next convolution's GEMM.  C in _SLOT_NORM_CHANNELS; bit for bit `slot_sum` followed
+    by `layer_norm` / `layer_norm_relu`."""
+    _dev(part, slot, bias, weight, norm_bias)
+    part = _f32c(part)
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2
+    n, k = slot.shape
+    c = part.shape[1]
+    if split2:
+        out = torch.empty((n, 2 * c), dtype=torch.bfloat16, device=part.device)
+    else:
+        out = torch.empty((n, c), dtype=torch.float32, device=part.device)
+    check(_native.load().hfl_slot_sum_norm(None if split2 else out.data_ptr(), out.data_ptr() if split2 else None,
+                                           part.data_ptr(), slot.data_ptr(), None if bias is None else _f32c(bias).data_ptr(),
+                                           _f32c(weight).data_ptr(), _f32c(norm_bias).data_ptr(), n, c, k, float(eps),
+                                           int(bool(relu)), _stream()), 'hfl_slot_sum_norm')
+    return out
+
+
 def dwconv_weight_backward(grad: torch.Tensor, data: torch.Tensor, neigh: torch.Tensor):
     """libs/dwconv/csrc/dwconv.h:14 -- -> (K,1,C)."""
     _dev(grad, data, neigh)

@@ -54,10 +54,20 @@ int hfl_dwconv_forward_backward(float* out, const float* data, const float* weig
 /* out[h,c] = sum_k [slot[h,k] >= 0] part[slot[h,k], c] [+ bias[c]]  (round 6): the per-row sum of the partial products of an
  * octree convolution over its live (row, tap) pairs -- ocnn's octree2col + mm scatters nothing, it multiplies the zero-padded
  * column matrix (models/layers/octformer_layers.py:89-95); here every output row adds the products of its own live taps in tap
- * order -- and the convolution's bias.  part (P, C) f32, slot (n_out, K) int32, -1 = no such neighbour, bias (C) or NULL.
+ * order -- and the convolution's bias.  part (P, C) f32, slot (n_out, K <= 32) int32, -1 = no such neighbour, bias (C) or
+ * NULL.  Only live slots are loaded; a row without one reads nothing from part.
  * Equals hfl_dwconv_forward_backward with unit weights (what rounds 1-5 launched) bit for bit. */
 int hfl_slot_sum(float* out, const float* part, const int32_t* slot, const float* bias, int64_t n_out, int64_t channels, int kngh,
                  hfl_stream_t stream);
+
+/* hfl_slot_sum with the caller's LayerNorm [+ ReLU] over the channel axis folded into the same pass: the norm that follows every
+ * stem convolution and every Downsample (models/layers/octformer_layers.py:80-98, models/octformer_backbone.py:464-477), on the
+ * sum while it is in registers.  f32 rows (out_f32, (n_out, C)) or the split2 operand of the next GEMM (out_split2, (n_out, 2C)
+ * bf16); exactly one of the two is non-NULL.  channels in {32, 64, 128, 256} (one 16-B cell per lane), kngh <= 32; anything
+ * else is HFL_EINVAL.  Bit for bit hfl_slot_sum followed by hfl_layer_norm (relu = 0) / hfl_layer_norm_relu (relu = 1). */
+int hfl_slot_sum_norm(float* out_f32, uint16_t* out_split2, const float* part, const int32_t* slot, const float* bias,
+                      const float* gamma, const float* beta, int64_t n_out, int64_t channels, int kngh, float eps, int relu,
+                      hfl_stream_t stream);
 
 /* gW[k,c] = sum_h [neigh[h,k] >= 0] data[neigh[h,k], c] * grad[h,c]
  *   replaces  Tensor dwconv_weight_backward(Tensor grad, Tensor data, Tensor neigh)
