@@ -14,7 +14,7 @@
 //
 // No floating-point atomics.  No workgroup waits for another.  Every barrier is reached by the whole workgroup: the loop
 // conditions are read from LDS by every lane, so all lanes leave a loop together.
-#include "hfl_common.h"
+#include "ragged_common.h"
 
 namespace {
 
@@ -24,16 +24,6 @@ constexpr int kSimWaves = kSimThreads / 64;
 constexpr int kSimSlots = HFL_CLOTH_MAX_PARTICLES / kSimThreads;      // particles per lane
 static_assert(kSimSlots * kSimThreads == HFL_CLOTH_MAX_PARTICLES, "the particle limit is a multiple of the workgroup");
 constexpr unsigned long long kNoPoint = ~0ull;
-
-// the cloud that holds point i: the largest c in [0, batch) with off[c] <= i
-__device__ __forceinline__ int ground_find_cloud(const int64_t* __restrict__ off, int batch, int64_t i) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // int(f) clamped into [0, top]; a NaN gives 0 (the host route: where(f >= 0, f, 0), minimum(f, top), truncate)
 __device__ __forceinline__ int cloth_index(float f, int top) {
@@ -52,7 +42,7 @@ cloth_raster_kernel(unsigned long long* __restrict__ keys, const hfl_cloth_desc*
                     const float* __restrict__ pts, const int64_t* __restrict__ off, int batch, int64_t n, float r) {
   const int64_t i = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x;
   if (i >= n) return;
-  const int c = ground_find_cloud(off, batch, i);
+  const int c = find_cloud(off, batch, i);
   const hfl_cloth_desc d = desc[c];
   const float x = pts[i * 3 + 0], y = pts[i * 3 + 1];
   const int col = cloth_index(__fadd_rn(cloth_coord(x, d.ox, r), 0.5f), d.width - 1);
@@ -279,7 +269,7 @@ cloth_classify_kernel(uint8_t* __restrict__ keep, const float* __restrict__ u, c
                       float threshold) {
   const int64_t i = (int64_t)blockIdx.x * kGroundThreads + threadIdx.x;
   if (i >= n) return;
-  const int cl = ground_find_cloud(off, batch, i);
+  const int cl = find_cloud(off, batch, i);
   const hfl_cloth_desc d = desc[cl];
   const int W = d.width;
   const float fx = cloth_coord(pts[i * 3 + 0], d.ox, r), fy = cloth_coord(pts[i * 3 + 1], d.oy, r);

@@ -23,7 +23,7 @@
 // floating-point atomics (one integer add per wave appends to the list); no workgroup waits for another.
 #include <math.h>
 
-#include "hfl_common.h"
+#include "ragged_common.h"
 
 namespace {
 
@@ -31,23 +31,13 @@ constexpr int kOutThreads = 256;
 constexpr int kOutWaves = kOutThreads / HFL_WAVE;
 constexpr float kFaceShrink = 1.f - 9.5367431640625e-07f;      // 1 - 2^-20: the relative part of the margin of the bound
 
-// the cloud that holds point i: the largest c in [0, batch) with off[c] <= i
-__device__ __forceinline__ int out_find_cloud(const int64_t* __restrict__ off, int batch, int64_t i) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ void __launch_bounds__(kOutThreads)
 cloud_nonfinite_kernel(int32_t* __restrict__ flags, const float* __restrict__ pts, const int64_t* __restrict__ off, int batch,
                        int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (i >= n) return;
   const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-  if (!(x - x == 0.f) || !(y - y == 0.f) || !(z - z == 0.f)) atomicOr(flags + out_find_cloud(off, batch, i), 1);
+  if (!(x - x == 0.f) || !(y - y == 0.f) || !(z - z == 0.f)) atomicOr(flags + find_cloud(off, batch, i), 1);
 }
 
 // int((p - origin) / cell) clamped into [0, top]; what is not >= 0 gives 0
@@ -63,7 +53,7 @@ knn_cell_keys_kernel(int64_t* __restrict__ keys, const hfl_knn_grid* __restrict_
                      const int64_t* __restrict__ off, int batch, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (i >= n) return;
-  const hfl_knn_grid g = grids[out_find_cloud(off, batch, i)];
+  const hfl_knn_grid g = grids[find_cloud(off, batch, i)];
   const int ix = knn_cell(pts[i * 3 + 0], g.ox, g.cell, g.nx - 1);
   const int iy = knn_cell(pts[i * 3 + 1], g.oy, g.cell, g.ny - 1);
   const int iz = knn_cell(pts[i * 3 + 2], g.oz, g.cell, g.nz - 1);
@@ -142,7 +132,7 @@ knn_query_kernel(float* __restrict__ avg, int32_t* __restrict__ pending, int32_t
                  int batch, int64_t n) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n) return;
-  const int c = out_find_cloud(off, batch, j);
+  const int c = find_cloud(off, batch, j);
   const hfl_knn_grid g = grids[c];
   const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
   const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
@@ -203,7 +193,7 @@ knn_fallback_kernel(float* __restrict__ avg, const int32_t* __restrict__ pending
   for (int64_t e = wave; e < count; e += waves) {
     const int64_t j = pending[e];
     if (j < 0 || j >= n) continue;
-    const int c = out_find_cloud(off, batch, j);
+    const int c = find_cloud(off, batch, j);
     const int64_t first = off[c], last = min(off[c + 1], n);
     const int k = min(max(grids[c].k, 1), K);
     const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
@@ -225,25 +215,8 @@ knn_fallback_kernel(float* __restrict__ avg, const int32_t* __restrict__ pending
   }
 }
 
-__device__ __forceinline__ double out_wave_sum(double v) {
-#pragma unroll
-  for (int m = HFL_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, HFL_WAVE);
-  return v;
-}
-
-// the sum over the workgroup in the order of hfl_pair_stats: a thread's rows in ascending order, the xor butterfly 32 .. 1
-// in a wave, the waves in wave order; the same value in every thread.  Two barriers.
-__device__ __forceinline__ double out_block_sum(double v, double* s_part) {
-  v = out_wave_sum(v);
-  __syncthreads();                                             // the previous round's parts have been read
-  if ((threadIdx.x & (HFL_WAVE - 1)) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double a = s_part[0];
-#pragma unroll
-  for (int w = 1; w < kOutWaves; ++w) a += s_part[w];
-  return a;
-}
-
+// the sums below are `block_sum` of ragged_common.h, the order of hfl_pair_stats: a thread's rows in ascending order, the
+// xor butterfly 32 .. 1 in a wave, the waves in wave order; the same value in every thread
 __global__ void __launch_bounds__(kOutThreads)
 outlier_threshold_kernel(double* __restrict__ stats, const float* __restrict__ avg, const int64_t* __restrict__ off,
                          int64_t n, double ratio) {
@@ -255,8 +228,8 @@ outlier_threshold_kernel(double* __restrict__ stats, const float* __restrict__ a
     const float a = avg[i];
     if (a > 0.f) { sum += (double)a; cnt += 1.0; }
   }
-  sum = out_block_sum(sum, s_part);
-  cnt = out_block_sum(cnt, s_part);                            // whole numbers below 2^53: exact in any order
+  sum = block_sum<kOutThreads>(sum, s_part);
+  cnt = block_sum<kOutThreads>(cnt, s_part);                   // whole numbers below 2^53: exact in any order
   const double mean = __ddiv_rn(sum, cnt);                     // 0 / 0 = NaN for a cloud without a valid point
   double ss = 0.0;
   for (int64_t i = begin + threadIdx.x; i < end; i += kOutThreads) {
@@ -266,7 +239,7 @@ outlier_threshold_kernel(double* __restrict__ stats, const float* __restrict__ a
       ss += __dmul_rn(d, d);
     }
   }
-  ss = out_block_sum(ss, s_part);
+  ss = block_sum<kOutThreads>(ss, s_part);
   if (threadIdx.x == 0) {
     const double sd = __dsqrt_rn(__ddiv_rn(ss, __dsub_rn(cnt, 1.0)));      // 0 / 0 = NaN for a single valid point
     stats[4 * (int64_t)b + 0] = mean;
@@ -282,7 +255,7 @@ outlier_mask_kernel(uint8_t* __restrict__ keep, const float* __restrict__ avg, c
   const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (i >= n) return;
   const float a = avg[i];
-  const double threshold = stats[4 * (int64_t)out_find_cloud(off, batch, i) + 2];
+  const double threshold = stats[4 * (int64_t)find_cloud(off, batch, i) + 2];
   keep[i] = (a > 0.f && (double)a < threshold) ? 1 : 0;        // a NaN threshold keeps nothing
 }
 

@@ -25,7 +25,7 @@
 // No atomics anywhere; every output element has one writer and a fixed evaluation order: two runs give the same bits.
 #include <math.h>
 
-#include "hfl_common.h"
+#include "ragged_common.h"
 
 namespace {
 
@@ -130,13 +130,6 @@ nn_dist_kernel(float* __restrict__ dist, int32_t* __restrict__ idx, const float*
 struct Taus {
   float v[OV_MAX_TAUS];
 };
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int m = HFL_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, HFL_WAVE);
-  return v;
-}
 
 __global__ void __launch_bounds__(OV_THREADS)
 pair_stats_kernel(double* __restrict__ sums, int64_t* __restrict__ counts, const float* __restrict__ dist,

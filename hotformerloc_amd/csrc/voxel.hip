@@ -15,6 +15,7 @@
 // launch boundary), and there is no floating-point atomic: every sum has a fixed order that depends only on a point's
 // position within its cloud / cell, so two runs give the same bits and a cloud gives the same bits alone or in a batch.
 #include "prep_common.h"
+#include "ragged_common.h"
 
 namespace {
 
@@ -32,16 +33,6 @@ __device__ __forceinline__ uint32_t enc_ordered(float f) {
 }
 __device__ __forceinline__ float dec_ordered(uint32_t e) {
   return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-
-// the cloud that holds point i: the largest c in [0, batch) with off[c] <= i
-__device__ __forceinline__ int find_cloud(const int64_t* __restrict__ off, int batch, int64_t i) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // the up to four points 4 t .. 4 t + 3 of a thread; a full quad is three aligned 16-byte loads (the array starts 16-B aligned)
@@ -317,19 +308,6 @@ voxel_mean_kernel(float* __restrict__ out, int32_t* __restrict__ cell_counts, in
 }
 
 // ------------------------------------------------------------------------------------------------ normalise
-// sum of `v` over the workgroup in a fixed order, returned to every lane; `red` holds kPrepThreads / 64 doubles
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double r = red[0];
-  for (int w = 1; w < kPrepThreads / 64; ++w) r += red[w];
-  return r;
-}
-
 // centroid c and scale s = 0.5 / d (d = mean |q - c|) of the n >= 1 points at p, float64 in a fixed order, in every lane;
 // true when d is not > 0 (a single point, coincident points or a non-finite input), and then s = 0
 __device__ __forceinline__ bool submap_stats(const float* __restrict__ p, int64_t n, double* red, double (&c)[3], double& scale) {
@@ -340,14 +318,14 @@ __device__ __forceinline__ bool submap_stats(const float* __restrict__ p, int64_
       for (int a = 0; a < 3; ++a) s[a] += (double)p[i * 3 + a];
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = __ddiv_rn(block_sum(s[a], red), (double)n);
+    for (int a = 0; a < 3; ++a) c[a] = __ddiv_rn(block_sum<kPrepThreads>(s[a], red), (double)n);
   }
   double rs = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += kPrepThreads) {
     const double dx = (double)p[i * 3 + 0] - c[0], dy = (double)p[i * 3 + 1] - c[1], dz = (double)p[i * 3 + 2] - c[2];
     rs += sqrt(dx * dx + dy * dy + dz * dz);
   }
-  const double d = __ddiv_rn(block_sum(rs, red), (double)n);
+  const double d = __ddiv_rn(block_sum<kPrepThreads>(rs, red), (double)n);
   const bool degenerate = !(d > 0.0);                        // a single point, coincident points or a non-finite input
   scale = degenerate ? 0.0 : __ddiv_rn(0.5, d);
   return degenerate;

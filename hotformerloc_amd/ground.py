@@ -49,21 +49,20 @@ particle", which changes no height.
 
 Device route: `hfl_voxel_bounds` and one host read of the (B, 6) bounds, from which the host lays out the cloths;
 `hfl_cloth_raster` (a 64-bit integer atomic min per point, then the fill), `hfl_cloth_simulate` (one workgroup per cloud, the
-state in LDS for the whole run) and `hfl_cloth_classify`; `csrc/ground.hip`.  The mask is compacted by `torch.nonzero`
-(plumbing, as `torch.sort` is in `voxel.py`) and `hfl_voxel_gather_rows`.
+state in LDS for the whole run) and `hfl_cloth_classify`; `csrc/ground.hip`.  The mask is compacted by `ragged.compact`
+(`torch.nonzero`, plumbing as `torch.sort` is in `voxel.py`, and `hfl_voxel_gather_rows`).
 
 Limits: a cloth holds at most `MAX_PARTICLES` = 10 240 particles (100 x 100 fits: a 96 m submap at r = 1 m), because its
 state stays in the 160 KiB of LDS of one compute unit; a larger one raises `ValueError` naming the cloud, after the bounds
-are known and before any cloth kernel runs.  Batch limits as in `voxel.py`.  Non-finite coordinates give undefined output
+are known and before any cloth kernel runs.  Batch limits as in `ragged.py`.  Non-finite coordinates give undefined output
 (nothing is read or written out of bounds) or that `ValueError`."""
 
-import math
 from typing import List, Sequence
 
 import numpy as np
 import torch
 
-from . import ops, voxel
+from . import ops, ragged
 
 MAX_PARTICLES = ops.CLOTH_MAX_PARTICLES
 GRAVITY = 0.2
@@ -83,10 +82,9 @@ class ClothParams:
                  iterations=500):
         if isinstance(rigidness, bool) or rigidness not in (1, 2, 3):
             raise ValueError('rigidness must be 1, 2 or 3, got %r' % (rigidness,))
-        for name, v in (('cloth_resolution', cloth_resolution), ('class_threshold', class_threshold), ('time_step', time_step)):
-            f = float(v)
-            if not math.isfinite(f) or f <= 0.0 or not math.isfinite(float(_F(f))) or float(_F(f)) <= 0.0:
-                raise ValueError('%s must be positive and finite, got %r' % (name, v))
+        ragged.check_positive('cloth_resolution', cloth_resolution, fp32=True)
+        ragged.check_positive('class_threshold', class_threshold, fp32=True)
+        ragged.check_positive('time_step', time_step, fp32=True)
         if int(iterations) != iterations or iterations < 0:
             raise ValueError('iterations must be a non-negative integer, got %r' % (iterations,))
         self.rigidness = int(rigidness)
@@ -103,10 +101,6 @@ class ClothParams:
 def _limit_error(i: int, w, h):
     return ValueError('cloud %d needs a cloth of %s x %s particles, more than the %d that fit the on-chip memory of one '
                       'compute unit; use a larger cloth_resolution or a smaller submap' % (i, w, h, MAX_PARTICLES))
-
-
-def _no_point_error(i: int):
-    return ValueError('cloud %d has no point left after ground removal' % i)
 
 
 def cloth_grid(lo_hi: np.ndarray, r, index: int = 0):
@@ -280,13 +274,6 @@ def classify_host(cloud: np.ndarray, u: np.ndarray, ox, oy, prm: ClothParams) ->
         return ~(np.abs(-cloud[:, 2] - h) < prm.threshold)
 
 
-def _as_arrays(clouds):
-    arrays = [np.ascontiguousarray(np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3))
-              for c in clouds]
-    voxel._check_batch([a.shape[0] for a in arrays])
-    return arrays
-
-
 def _cloth_host(arrays, prm):
     grids = [raster_host(a, prm.r, i) for i, a in enumerate(arrays)]         # every limit is checked before any simulation
     out = []
@@ -300,7 +287,7 @@ def cloth_surface_host(clouds: Sequence, **params):
     """The cloth of every cloud by the numpy route: a list of (u (H, W) fp32, movable (H, W) bool, t (H, W) fp32,
     steps_run)."""
     prm = ClothParams(**params)
-    return [c[:4] for c in _cloth_host(_as_arrays(clouds), prm)]
+    return [c[:4] for c in _cloth_host(ragged.as_arrays(clouds), prm)]
 
 
 def remove_ground_host(clouds: Sequence, *, return_mask: bool = False, return_cloth: bool = False, **params):
@@ -308,29 +295,26 @@ def remove_ground_host(clouds: Sequence, *, return_mask: bool = False, return_cl
     (n_i, 3) clouds -> list of (k_i, 3) float32 arrays, the non-ground points in input order (k_i may be 0); with
     `return_mask` also the (n_i,) bool masks of the kept points, with `return_cloth` also what `cloth_surface_host` returns."""
     prm = ClothParams(**params)
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     cloths = _cloth_host(arrays, prm)
     masks = [classify_host(a, c[0], c[4], c[5], prm) for a, c in zip(arrays, cloths)]
-    res = ([a[m] for a, m in zip(arrays, masks)],)
-    if return_mask:
-        res += (masks,)
-    if return_cloth:
-        res += ([c[:4] for c in cloths],)
-    return res[0] if len(res) == 1 else res
+    return ragged.results([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None,
+                          [c[:4] for c in cloths] if return_cloth else None)
 
 
 # ------------------------------------------------------------------------------------------------ device route
-def _cloth_device(pts, off, off_host, prm: ClothParams):
-    """bounds -> table -> raster -> simulate, everything but the bounds staying on the device"""
-    _, lo_hi = voxel._bounds_host(pts, off)                                   # the one host read before the cloths are laid out
-    descs = np.zeros(len(off_host) - 1, dtype=np.dtype(ops.CLOTH_DESC_DTYPE))
+def cloth_device(packed, prm: ClothParams):
+    """bounds -> table -> raster -> simulate, everything but the bounds staying on the device -> (table, terrain, heights,
+    movable, steps_run)"""
+    _, lo_hi = ragged.bounds_host(packed)                                     # the one host read before the cloths are laid out
+    descs = np.zeros(packed.batch, dtype=np.dtype(ops.CLOTH_DESC_DTYPE))
     at = 0
     for i in range(descs.shape[0]):
         w, h, ox, oy, u0 = cloth_grid(lo_hi[i], prm.r, i)
         descs[i] = (ox, oy, u0, w, h, 0, at)
         at += w * h
-    table = ops.ClothTable(descs, pts.device)
-    terrain = ops.cloth_raster(pts, off, table, float(prm.r))
+    table = ops.ClothTable(descs, packed.pts.device)
+    terrain = ops.cloth_raster(packed.pts, packed.off, table, float(prm.r))
     heights, movable, steps = ops.cloth_simulate(terrain, table, float(prm.f1), float(prm.f2), float(prm.gravity_step),
                                                  float(prm.keep), prm.iterations, prm.slope_smooth)
     return table, terrain, heights, movable, steps
@@ -352,13 +336,15 @@ def cloth_surface(clouds: Sequence, *, device='cuda', **params):
     """`cloth_surface_host` on the device: a list of (u (H, W) fp32, movable (H, W) bool, t (H, W) fp32 device tensors,
     steps_run), bit for bit what the numpy route returns."""
     prm = ClothParams(**params)
-    ts = voxel._as_tensors(clouds)
-    device = voxel._device(device)
-    if not ts:
-        return []
-    with torch.cuda.device(device):
-        pts, off, off_host = voxel._upload(ts, device)
-        return _split_cloths(*_cloth_device(pts, off, off_host, prm))
+    with ragged.intake(clouds, device) as packed:
+        return [] if packed is None else _split_cloths(*cloth_device(packed, prm))
+
+
+def remove_ground_packed(packed, prm: ClothParams):
+    """the filter on a packed batch -> (the kept rows as a `ragged.Packed`, keep (P,) uint8, what `cloth_device` returned)"""
+    cloth = cloth_device(packed, prm)
+    keep = ops.cloth_classify(packed.pts, packed.off, cloth[2], cloth[0], float(prm.r), float(prm.threshold))
+    return ragged.compact(packed, keep), keep, cloth
 
 
 def remove_ground(clouds: Sequence, *, device='cuda', return_mask: bool = False, return_cloth: bool = False, **params):
@@ -370,33 +356,16 @@ def remove_ground(clouds: Sequence, *, device='cuda', return_mask: bool = False,
     parameter or an empty cloud (before the device is touched) and, naming the cloud, for a cloth of more than 10 240
     particles (before any cloth kernel runs)."""
     prm = ClothParams(**params)
-    ts = voxel._as_tensors(clouds)
-    device = voxel._device(device)
-    if not ts:
-        return tuple([] for _ in range(1 + bool(return_mask) + bool(return_cloth))) if return_mask or return_cloth else []
-    with torch.cuda.device(device):
-        pts, off, off_host = voxel._upload(ts, device)
-        cloth = _cloth_device(pts, off, off_host, prm)
-        keep = ops.cloth_classify(pts, off, cloth[2], cloth[0], float(prm.r), float(prm.threshold))
-        index = torch.nonzero(keep).reshape(-1)                              # ascending: the order of the input
-        rows = ops.voxel_gather_rows(pts, index)
-        ends = np.searchsorted(index.cpu().numpy(), off_host)                # the kept rows before every cloud's first point
-        res = ([rows[s:e] for s, e in zip(ends[:-1], ends[1:])],)
-        if return_mask:
-            res += ([keep[s:e].bool() for s, e in zip(off_host[:-1], off_host[1:])],)
-        if return_cloth:
-            res += (_split_cloths(*cloth),)
-    return res[0] if len(res) == 1 else res
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ragged.empty_results(return_mask, return_cloth)
+        kept, keep, cloth = remove_ground_packed(packed, prm)
+        return ragged.results(kept.split(), packed.split(keep.bool()) if return_mask else None,
+                              _split_cloths(*cloth) if return_cloth else None)
 
 
 def filter_batch(clouds: Sequence, device, ground_params=None, at_least: int = 1) -> List[torch.Tensor]:
-    """`remove_ground` for the submap entry points of `voxel.py`: the filtered batch on the device, `ValueError` naming the
-    first cloud with no point left or with fewer than `at_least` points."""
-    out = remove_ground(clouds, device=device, **(ground_params or {}))
-    for i, c in enumerate(out):
-        if c.shape[0] < 1:
-            raise _no_point_error(i)
-        if c.shape[0] < at_least:
-            raise ValueError('cloud %d has %d points left after ground removal, fewer than target = %d'
-                             % (i, c.shape[0], at_least))
-    return out
+    """`remove_ground` alone, as the submap entry points of `voxel.py` run it: the filtered batch on the device, `ValueError`
+    naming the first cloud with no point left or with fewer than `at_least` points."""
+    from .voxel import submap_chain                  # a public alias kept for callers: voxel.py holds the chain
+    return submap_chain(clouds, device, remove_ground=True, ground_params=ground_params, at_least=at_least)

@@ -8,6 +8,7 @@ never synchronises.  Inputs must live on the GPU -- there is no CPU path.
 import ctypes
 import weakref
 
+import numpy as np
 import torch
 
 from . import _native
@@ -1420,7 +1421,6 @@ def ema_table(ema_tensors, src_tensors):
     """Device table of `hfl_ema_chunk` entries for `ema_update`: every (ema, src) pair of fp32 tensors cut into chunks of at
     most EMA_CHUNK elements.  Returns (table, n_chunks); the table holds raw pointers, so it is valid only while every
     tensor keeps its `data_ptr()` (the caller revalidates).  A tensor that appears twice (tied weights) is taken once."""
-    import numpy as np
     ema_tensors, src_tensors = list(ema_tensors), list(src_tensors)
     if len(ema_tensors) != len(src_tensors):
         raise ValueError('ema_table: %d ema tensors, %d source tensors' % (len(ema_tensors), len(src_tensors)))
@@ -1481,7 +1481,6 @@ def adam_chunk_rows(numels, param_ptrs, grad_ptrs, exp_avg_ptrs, exp_avg_sq_ptrs
     Returns (rows, owner, launches): rows (n, 6) int64 in the layout of `hfl_adam_chunk` (five addresses, then
     count | slot % ADAM_MAX_SLOTS << 32), owner (n,) the index of each row's tensor, launches a list of (first row, rows,
     first slot): rows are ordered so that every run of ADAM_MAX_SLOTS consecutive slots is one contiguous launch."""
-    import numpy as np
     rows, owner = [], []
     for i, n in enumerate(numels):
         if n == 0 or (not grad_ptrs[i] and not ema_ptrs[i]):
@@ -1553,7 +1552,6 @@ def adam_table(params, grads, exp_avgs, exp_avg_sqs, emas, slots) -> AdamTable:
     t = AdamTable()
     t.n_chunks, t.launches = int(rows.shape[0]), launches
     t.table = torch.from_numpy(rows).to(params[0].device) if t.n_chunks else None
-    import numpy as np
     t.grad_rows = np.nonzero(rows[:, 1])[0]
     t.grad_owner = owner[t.grad_rows]
     t.grad_offset = rows[t.grad_rows, 1] - np.asarray(gp, dtype=np.int64)[t.grad_owner]
@@ -1567,7 +1565,6 @@ def adam_table(params, grads, exp_avgs, exp_avg_sqs, emas, slots) -> AdamTable:
 def adam_refresh_grads(t: AdamTable, grads):
     """Rewrite the gradient column of `t` for gradient tensors at new addresses: the same parameters have gradients as when
     the table was built (the caller checks), of the same shapes; nothing else of the table changes."""
-    import numpy as np
     grads = list(grads)
     _dev(*grads)
     for g in grads:
@@ -1743,12 +1740,27 @@ OVERLAP_TILE = 2048                    # HFL_OVERLAP_TILE: target points of the 
 OVERLAP_MAX_TAUS = 8                   # HFL_OVERLAP_MAX_TAUS: thresholds of one hfl_pair_stats launch
 
 
-def _overlap_check(what: str, points: torch.Tensor, offsets: torch.Tensor):
-    _dev(points, offsets)
+def _points_check(what: str, points: torch.Tensor):
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise TypeError('%s: contiguous (N, 3) float32 points expected' % what)
+        raise TypeError('%s: contiguous (P, 3) float32 points expected' % what)
+
+
+def _vector_check(what: str, t: torch.Tensor, dtype, n=None, kind: str = 'vector'):
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.shape[0] != n):
+        raise TypeError('%s: contiguous (%s,) %s %s expected'
+                        % (what, 'n' if n is None else n, str(dtype).replace('torch.', ''), kind))
+
+
+def _offsets_check(what: str, offsets: torch.Tensor):
     if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
-        raise TypeError('%s: (P + 1,) int64 cloud offsets with P >= 1 expected' % what)
+        raise TypeError('%s: contiguous (B + 1,) int64 cloud offsets with B >= 1 expected' % what)
+
+
+def _ragged_check(what: str, points: torch.Tensor, offsets: torch.Tensor) -> int:
+    """a ragged batch (of clouds, or of the clouds of pairs) on the current device -> its number of clouds"""
+    _dev(points, offsets)
+    _points_check(what, points)
+    _offsets_check(what, offsets)
     return int(offsets.shape[0]) - 1
 
 
@@ -1760,7 +1772,6 @@ def _some(t: torch.Tensor):
 def overlap_tiles(lengths):
     """The tile table of `hfl_nn_dist` from the query clouds' lengths on the host: (n_tiles, 2) int64 numpy rows of (pair,
     first query row), OVERLAP_ROWS rows of one pair per workgroup, pairs in order; an empty cloud has no tile."""
-    import numpy as np
     lengths = np.asarray(lengths, dtype=np.int64)
     per = -(-lengths // OVERLAP_ROWS)
     pair = np.repeat(np.arange(lengths.shape[0], dtype=np.int64), per)
@@ -1773,7 +1784,7 @@ def overlap_tiles(lengths):
 def transform_points(points: torch.Tensor, offsets: torch.Tensor, transforms: torch.Tensor):
     """`hfl_transform_points`: points (N, 3) fp32, offsets (P + 1,) int64 with offsets[0] = 0 and offsets[P] = N (the caller
     checks) and transforms (P, 12) fp32, a row-major (R | t) per pair, all on the GPU -> R_p x + t_p for every row."""
-    pairs = _overlap_check('transform_points', points, offsets)
+    pairs = _ragged_check('transform_points', points, offsets)
     _dev(transforms)
     if transforms.dtype != torch.float32 or tuple(transforms.shape) != (pairs, 12) or not transforms.is_contiguous():
         raise TypeError('transform_points: contiguous (%d, 12) float32 transforms expected' % pairs)
@@ -1789,8 +1800,8 @@ def nn_dist(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tenso
     """`hfl_nn_dist`: two ragged batches of the same P pairs and the (n_tiles, 2) int64 device copy of `overlap_tiles` ->
     (dist (Nq,) fp32, idx (Nq,) int32): every query's distance to the nearest point of its pair's target cloud and that
     point's index within the cloud, +inf and -1 where the cloud is empty.  Rows the table does not cover stay unwritten."""
-    pairs = _overlap_check('nn_dist', queries, q_offsets)
-    if _overlap_check('nn_dist', targets, t_offsets) != pairs:
+    pairs = _ragged_check('nn_dist', queries, q_offsets)
+    if _ragged_check('nn_dist', targets, t_offsets) != pairs:
         raise ValueError('nn_dist: the query batch and the target batch differ in their number of pairs')
     _dev(tiles)
     if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
@@ -1810,10 +1821,8 @@ def pair_stats(dist: torch.Tensor, offsets: torch.Tensor, taus=()):
     (sums (P, 2) float64: the sum of a pair's distances and of their squares, counts (P, K + 1) int64: the distances
     <= taus[k] compared in fp32, and in the last column the +inf ones, which are in no other figure)."""
     _dev(dist, offsets)
-    if dist.dtype != torch.float32 or dist.dim() != 1 or not dist.is_contiguous():
-        raise TypeError('pair_stats: contiguous (N,) float32 distances expected')
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
-        raise TypeError('pair_stats: (P + 1,) int64 offsets with P >= 1 expected')
+    _vector_check('pair_stats', dist, torch.float32, kind='distances')
+    _offsets_check('pair_stats', offsets)
     taus = [float(t) for t in taus]
     if len(taus) > OVERLAP_MAX_TAUS:
         raise ValueError('pair_stats: at most %d thresholds in one launch, got %d' % (OVERLAP_MAX_TAUS, len(taus)))
@@ -1831,20 +1840,11 @@ VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span t
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
 
 
-def _voxel_check(what: str, points: torch.Tensor, offsets: torch.Tensor):
-    _dev(points, offsets)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise TypeError('%s: contiguous (P, 3) float32 points expected' % what)
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
-        raise TypeError('%s: (B + 1,) int64 cloud offsets with B >= 1 expected' % what)
-    return int(offsets.shape[0]) - 1
-
-
 def voxel_keys(points: torch.Tensor, offsets: torch.Tensor, voxel_size: float):
     """`hfl_voxel_keys`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU, every cloud non-empty and offsets[B] == P
     (the caller checks) -> (keys (P,) int64 = cloud << 48 | ix << 32 | iy << 16 | iz, flags (B,) int32: 1 where a cloud
     spans 65 536 or more cells along an axis)."""
-    batch = _voxel_check('voxel_keys', points, offsets)
+    batch = _ragged_check('voxel_keys', points, offsets)
     n = int(points.shape[0])
     if n < batch:
         raise ValueError('voxel_keys: %d points for %d non-empty clouds' % (n, batch))
@@ -1865,10 +1865,8 @@ def voxel_reduce(sorted_keys: torch.Tensor, perm: torch.Tensor, points: torch.Te
     _dev(sorted_keys, perm, points)
     n = int(points.shape[0])
     for t in (sorted_keys, perm):
-        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise TypeError('voxel_reduce: contiguous (%d,) int64 keys and permutation expected' % n)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise TypeError('voxel_reduce: contiguous (P, 3) float32 points expected')
+        _vector_check('voxel_reduce', t, torch.int64, n, 'keys and permutation')
+    _points_check('voxel_reduce', points)
     lib = _native.load()
     nbytes = int(lib.hfl_voxel_reduce_workspace(n))
     if nbytes <= 0:
@@ -1887,7 +1885,7 @@ def voxel_reduce(sorted_keys: torch.Tensor, perm: torch.Tensor, points: torch.Te
 def submap_normalise(points: torch.Tensor, offsets: torch.Tensor):
     """`hfl_submap_normalise`: points (P, 3) fp32 and offsets (B + 1,) int64 on the GPU (offsets[B] <= P) -> (out (P, 3) with
     cloud b's kept rows from row offsets[b] on, counts (B,) int32, flags (B,) int32: 1 where the mean radius is not > 0)."""
-    batch = _voxel_check('submap_normalise', points, offsets)
+    batch = _ragged_check('submap_normalise', points, offsets)
     out = torch.empty_like(points)
     counts = torch.empty(batch, dtype=torch.int32, device=points.device)
     flags = torch.empty(batch, dtype=torch.int32, device=points.device)
@@ -1901,13 +1899,12 @@ def submap_normalise_rows(points: torch.Tensor, offsets: torch.Tensor, raw: torc
     """`hfl_submap_normalise_rows`: the centroid and scale of cloud b of `points` / `offsets` (as `submap_normalise` computes
     them) applied to raw rows raw_offsets[b] + row_index[j], j in [row_offsets[b], row_offsets[b + 1]) -> (rows (R, 3) fp32,
     keep (R,) int32: 1 where every |q'| <= 1).  All tensors on the GPU; the index and offset tensors int64."""
-    batch = _voxel_check('submap_normalise_rows', points, offsets)
-    if _voxel_check('submap_normalise_rows', raw, raw_offsets) != batch:
+    batch = _ragged_check('submap_normalise_rows', points, offsets)
+    if _ragged_check('submap_normalise_rows', raw, raw_offsets) != batch:
         raise ValueError('submap_normalise_rows: the raw batch and the downsampled batch differ in size')
     _dev(row_index, row_offsets)
-    for t, shape in ((row_index, None), (row_offsets, (batch + 1,))):
-        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or (shape and tuple(t.shape) != shape):
-            raise TypeError('submap_normalise_rows: contiguous int64 row_index (R,) and row_offsets (B + 1,) expected')
+    _vector_check('submap_normalise_rows', row_index, torch.int64, kind='row_index')
+    _vector_check('submap_normalise_rows', row_offsets, torch.int64, batch + 1, 'row_offsets')
     rows = int(row_index.shape[0])
     out = torch.empty((rows, 3), dtype=torch.float32, device=points.device)
     keep = torch.empty(rows, dtype=torch.int32, device=points.device)
@@ -1922,10 +1919,8 @@ def voxel_gather_rows(points: torch.Tensor, index: torch.Tensor):
     """`hfl_voxel_gather_rows`: points (P, 3) fp32 and index (R,) int64 on the GPU -> points[index] (R, 3); an index outside
     [0, P) gives a zero row."""
     _dev(points, index)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise TypeError('voxel_gather_rows: contiguous (P, 3) float32 points expected')
-    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
-        raise TypeError('voxel_gather_rows: contiguous (R,) int64 index expected')
+    _points_check('voxel_gather_rows', points)
+    _vector_check('voxel_gather_rows', index, torch.int64, kind='index')
     out = torch.empty((int(index.shape[0]), 3), dtype=torch.float32, device=points.device)
     if index.shape[0]:
         check(_native.load().hfl_voxel_gather_rows(out.data_ptr(), points.data_ptr(), int(points.shape[0]), index.data_ptr(),
@@ -1936,7 +1931,7 @@ def voxel_gather_rows(points: torch.Tensor, index: torch.Tensor):
 def voxel_bounds(points: torch.Tensor, offsets: torch.Tensor):
     """`hfl_voxel_bounds`: -> bounds (B, 6) int32 on the GPU, the ordered-integer images of every cloud's minimum and maximum
     that `voxel_occupancy` takes; `decode_voxel_bounds` turns a host copy into floats."""
-    batch = _voxel_check('voxel_bounds', points, offsets)
+    batch = _ragged_check('voxel_bounds', points, offsets)
     n = int(points.shape[0])
     if n < batch:
         raise ValueError('voxel_bounds: %d points for %d non-empty clouds' % (n, batch))
@@ -1948,7 +1943,6 @@ def voxel_bounds(points: torch.Tensor, offsets: torch.Tensor):
 
 def decode_voxel_bounds(bounds):
     """a host copy of `voxel_bounds` -> (B, 6) float32 numpy: min x, y, z, max x, y, z"""
-    import numpy as np
     e = np.ascontiguousarray(bounds).view(np.uint32).reshape(-1, 6).copy()
     e[:, :3] = ~e[:, :3]
     return np.where(e & 0x80000000, e & 0x7FFFFFFF, ~e).astype(np.uint32).view(np.float32)
@@ -1963,8 +1957,7 @@ def voxel_occupancy(points: torch.Tensor, offsets: torch.Tensor, bounds: torch.T
                     max_cloud_points: int):
     """`hfl_voxel_occupancy`: `candidates` is a host numpy array of `VOXEL_CANDIDATE_DTYPE` (hfl_voxel_candidate) whose
     bitmaps take `bitmap_words` words together -> counts (n_cand,) int32 on the GPU.  Nothing is read back."""
-    import numpy as np
-    batch = _voxel_check('voxel_occupancy', points, offsets)
+    batch = _ragged_check('voxel_occupancy', points, offsets)
     _dev(bounds)
     if bounds.dtype != torch.int32 or tuple(bounds.shape) != (batch, 6) or not bounds.is_contiguous():
         raise TypeError('voxel_occupancy: (B, 6) int32 bounds expected')
@@ -1989,23 +1982,33 @@ CLOTH_DESC_DTYPE = [('ox', '<f4'), ('oy', '<f4'), ('u0', '<f4'), ('width', '<i4'
                     ('cell_offset', '<i8')]                                          # hfl_cloth_desc
 
 
-class ClothTable:
-    """One `hfl_cloth_desc` per cloud on both sides: `host` (numpy, what the library checks before a launch) and `device`
-    (the same bytes, what the kernels read); `cells` particles in all, cloud b's at `host['cell_offset'][b]`."""
+class _DescTable:
+    """One descriptor per cloud on both sides: `host` (a numpy array of the subclass's `DTYPE`, what the library checks
+    before a launch) and `device` (the same bytes, what the kernels read); `batch` clouds and `cells` cells in all, as the
+    subclass counts and bounds them (`_checked_cells`)."""
+    DTYPE = STRUCT = None
 
     def __init__(self, descs, device):
-        import numpy as np
-        self.host = np.ascontiguousarray(descs, dtype=np.dtype(CLOTH_DESC_DTYPE))
+        self.host = np.ascontiguousarray(descs, dtype=np.dtype(self.DTYPE))
         if self.host.ndim != 1 or self.host.shape[0] < 1:
-            raise ValueError('ClothTable: one hfl_cloth_desc per cloud expected')
+            raise ValueError('%s: one %s per cloud expected' % (type(self).__name__, self.STRUCT))
         self.batch = int(self.host.shape[0])
-        self.cells = int((self.host['width'].astype(np.int64) * self.host['height']).sum())
+        self.cells = self._checked_cells(self.host)
         self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+
+
+class ClothTable(_DescTable):
+    """`hfl_cloth_desc` per cloud; `cells` particles in all, cloud b's at `host['cell_offset'][b]`."""
+    DTYPE, STRUCT = CLOTH_DESC_DTYPE, 'hfl_cloth_desc'
+
+    @staticmethod
+    def _checked_cells(h):
+        return int((h['width'].astype(np.int64) * h['height']).sum())
 
 
 def _cloth_check(what: str, table: ClothTable, points=None, offsets=None):
     _dev(table.device)
-    if points is not None and _voxel_check(what, points, offsets) != table.batch:
+    if points is not None and _ragged_check(what, points, offsets) != table.batch:
         raise ValueError('%s: %d clouds but %d cloths' % (what, int(offsets.shape[0]) - 1, table.batch))
     if table.cells < 1:
         raise ValueError('%s: the cloths hold no particle' % what)
@@ -2029,8 +2032,7 @@ def cloth_simulate(terrain: torch.Tensor, table: ClothTable, f_one: float, f_two
     one workgroup per cloud.  The four factors are passed as the fp32 values the host route uses."""
     _cloth_check('cloth_simulate', table)
     _dev(terrain)
-    if terrain.dtype != torch.float32 or tuple(terrain.shape) != (table.cells,) or not terrain.is_contiguous():
-        raise TypeError('cloth_simulate: contiguous (%d,) float32 terrain expected' % table.cells)
+    _vector_check('cloth_simulate', terrain, torch.float32, table.cells, 'terrain')
     heights = torch.empty_like(terrain)
     movable = torch.empty(table.cells, dtype=torch.uint8, device=terrain.device)
     steps = torch.empty(table.batch, dtype=torch.int32, device=terrain.device)
@@ -2046,8 +2048,7 @@ def cloth_classify(points: torch.Tensor, offsets: torch.Tensor, heights: torch.T
     """`hfl_cloth_classify`: -> keep (P,) uint8 on the GPU, 0 where a point lies within `threshold` of the cloth (ground)."""
     _cloth_check('cloth_classify', table, points, offsets)
     _dev(heights)
-    if heights.dtype != torch.float32 or tuple(heights.shape) != (table.cells,) or not heights.is_contiguous():
-        raise TypeError('cloth_classify: contiguous (%d,) float32 heights expected' % table.cells)
+    _vector_check('cloth_classify', heights, torch.float32, table.cells, 'heights')
     keep = torch.empty(int(points.shape[0]), dtype=torch.uint8, device=points.device)
     check(_native.load().hfl_cloth_classify(keep.data_ptr(), heights.data_ptr(), table.host.ctypes.data,
                                             table.device.data_ptr(), table.batch, table.cells, points.data_ptr(),
@@ -2064,26 +2065,21 @@ KNN_GRID_DTYPE = [('ox', '<f4'), ('oy', '<f4'), ('oz', '<f4'), ('cell', '<f4'), 
                   ('cell_base', '<i8')]                                              # hfl_knn_grid
 
 
-class KnnGridTable:
-    """One `hfl_knn_grid` per cloud on both sides: `host` (numpy, what the library checks before a launch) and `device`
-    (the same bytes, what the kernels read); `cells` cells in all, cloud b's from `host['cell_base'][b]` on."""
+class KnnGridTable(_DescTable):
+    """`hfl_knn_grid` per cloud; `cells` cells in all (1..KNN_MAX_CELLS), cloud b's from `host['cell_base'][b]` on."""
+    DTYPE, STRUCT = KNN_GRID_DTYPE, 'hfl_knn_grid'
 
-    def __init__(self, grids, device):
-        import numpy as np
-        self.host = np.ascontiguousarray(grids, dtype=np.dtype(KNN_GRID_DTYPE))
-        if self.host.ndim != 1 or self.host.shape[0] < 1:
-            raise ValueError('KnnGridTable: one hfl_knn_grid per cloud expected')
-        self.batch = int(self.host.shape[0])
-        h = self.host
-        self.cells = int((h['nx'].astype(np.int64) * h['ny'] * h['nz']).sum())
-        if self.cells < 1 or self.cells > KNN_MAX_CELLS:
-            raise ValueError('KnnGridTable: 1..%d cells expected, got %d' % (KNN_MAX_CELLS, self.cells))
-        self.device = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
+    @staticmethod
+    def _checked_cells(h):
+        cells = int((h['nx'].astype(np.int64) * h['ny'] * h['nz']).sum())
+        if cells < 1 or cells > KNN_MAX_CELLS:
+            raise ValueError('KnnGridTable: 1..%d cells expected, got %d' % (KNN_MAX_CELLS, cells))
+        return cells
 
 
 def cloud_nonfinite(points: torch.Tensor, offsets: torch.Tensor):
     """`hfl_cloud_nonfinite`: -> flags (B,) int32 on the GPU, 1 where a cloud holds a coordinate that is not finite."""
-    batch = _voxel_check('cloud_nonfinite', points, offsets)
+    batch = _ragged_check('cloud_nonfinite', points, offsets)
     flags = torch.empty(batch, dtype=torch.int32, device=points.device)
     check(_native.load().hfl_cloud_nonfinite(flags.data_ptr(), points.data_ptr(), offsets.data_ptr(), batch,
                                              int(points.shape[0]), _stream()), 'hfl_cloud_nonfinite')
@@ -2092,7 +2088,7 @@ def cloud_nonfinite(points: torch.Tensor, offsets: torch.Tensor):
 
 def _knn_check(what: str, table: KnnGridTable, points: torch.Tensor, offsets: torch.Tensor):
     _dev(table.device)
-    if _voxel_check(what, points, offsets) != table.batch:
+    if _ragged_check(what, points, offsets) != table.batch:
         raise ValueError('%s: %d clouds but %d grids' % (what, int(offsets.shape[0]) - 1, table.batch))
 
 
@@ -2126,14 +2122,12 @@ def knn_mean_dist(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: 
     _dev(sorted_keys, perm)
     n = int(sorted_points.shape[0])
     for t in (sorted_keys, perm):
-        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise TypeError('knn_mean_dist: contiguous (%d,) int64 keys and permutation expected' % n)
+        _vector_check('knn_mean_dist', t, torch.int64, n, 'keys and permutation')
     ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
     if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
         raise ValueError('knn_mean_dist: the workspace was made for another batch')
     avg = out if out is not None else torch.empty(n, dtype=torch.float32, device=sorted_points.device)
-    if avg.dtype != torch.float32 or tuple(avg.shape) != (n,) or not avg.is_contiguous():
-        raise TypeError('knn_mean_dist: contiguous (%d,) float32 output expected' % n)
+    _vector_check('knn_mean_dist', avg, torch.float32, n, 'output')
     _dev(ws.starts, ws.pending, ws.counter, avg)
     check(_native.load().hfl_knn_mean_dist(avg.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
                                            sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(),
@@ -2146,10 +2140,8 @@ def outlier_threshold(avg: torch.Tensor, offsets: torch.Tensor, std_ratio: float
     """`hfl_outlier_threshold`: avg (P,) fp32 and offsets (B + 1,) int64 on the GPU -> stats (B, 4) float64: mean, std,
     mean + std_ratio std and the number of valid rows (avg > 0) of every cloud."""
     _dev(avg, offsets)
-    if avg.dtype != torch.float32 or avg.dim() != 1 or not avg.is_contiguous():
-        raise TypeError('outlier_threshold: contiguous (P,) float32 distances expected')
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2 or not offsets.is_contiguous():
-        raise TypeError('outlier_threshold: (B + 1,) int64 cloud offsets with B >= 1 expected')
+    _vector_check('outlier_threshold', avg, torch.float32, kind='distances')
+    _offsets_check('outlier_threshold', offsets)
     batch = int(offsets.shape[0]) - 1
     stats = torch.empty((batch, 4), dtype=torch.float64, device=avg.device)
     check(_native.load().hfl_outlier_threshold(stats.data_ptr(), _some(avg).data_ptr(), offsets.data_ptr(), batch,
@@ -2160,11 +2152,11 @@ def outlier_threshold(avg: torch.Tensor, offsets: torch.Tensor, std_ratio: float
 def outlier_mask(avg: torch.Tensor, offsets: torch.Tensor, stats: torch.Tensor):
     """`hfl_outlier_mask`: -> keep (P,) uint8 on the GPU, 1 where avg > 0 and below the cloud's threshold (stats[:, 2])."""
     _dev(avg, offsets, stats)
+    _vector_check('outlier_mask', avg, torch.float32, kind='distances')
+    if avg.shape[0] < 1:
+        raise TypeError('outlier_mask: non-empty distances expected')
+    _offsets_check('outlier_mask', offsets)
     batch = int(offsets.shape[0]) - 1
-    if avg.dtype != torch.float32 or avg.dim() != 1 or not avg.is_contiguous() or avg.shape[0] < 1:
-        raise TypeError('outlier_mask: contiguous non-empty (P,) float32 distances expected')
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or batch < 1 or not offsets.is_contiguous():
-        raise TypeError('outlier_mask: (B + 1,) int64 cloud offsets with B >= 1 expected')
     if stats.dtype != torch.float64 or tuple(stats.shape) != (batch, 4) or not stats.is_contiguous():
         raise TypeError('outlier_mask: contiguous (%d, 4) float64 stats expected' % batch)
     keep = torch.empty(int(avg.shape[0]), dtype=torch.uint8, device=avg.device)
@@ -2177,8 +2169,7 @@ def radius_mask(points: torch.Tensor, radius_max: float):
     """`hfl_radius_mask`: points (P, 3) fp32 on the GPU, P >= 1 -> keep (P,) uint8, 1 where sqrt(x x + y y) <= radius_max in
     float64."""
     _dev(points)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
-        raise TypeError('radius_mask: contiguous (P, 3) float32 points expected')
+    _points_check('radius_mask', points)
     keep = torch.empty(int(points.shape[0]), dtype=torch.uint8, device=points.device)
     check(_native.load().hfl_radius_mask(keep.data_ptr(), points.data_ptr(), int(points.shape[0]), float(radius_max),
                                          _stream()), 'hfl_radius_mask')
@@ -2246,7 +2237,6 @@ def augment_clouds(points, sizes, table_rows, config, seed: int, cloud_base: int
     integers), `table_rows` the (B, 12) uint32 host table of `hfl_augment_cloud` rows, `config` a `_native.AugmentConfig`,
     `selection_keys` an optional (P,) int32 device tensor holding uint32 bit patterns.  Returns (out (P, 3), counts (B,)
     int32, index (P,) int32 or None): the kept points of cloud b start at its input offset."""
-    import numpy as np
     _dev(points, selection_keys)
     if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3:
         raise TypeError('augment_clouds takes a contiguous (P, 3) float32 tensor')

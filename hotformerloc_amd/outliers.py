@@ -46,9 +46,9 @@ register list, and proves the scan complete when the k-th smallest d2 lies stric
 distance to the nearest face of the block that has cells behind it.  The points it cannot prove -- the isolated ones the
 filter exists to find, among others -- are finished by a whole-cloud scan, a wave per point.  With a cell so large that a
 cloud is one cell the first scan is the brute force.  Then `hfl_outlier_threshold`, `hfl_outlier_mask`, and the compaction
-of `ground.remove_ground`: `torch.nonzero`, `hfl_voxel_gather_rows`, one `searchsorted` on the host offsets.
+of `ragged.compact`: `torch.nonzero`, `hfl_voxel_gather_rows`, one `searchsorted` on the host offsets.
 
-Batch limits as in `voxel.py`."""
+Batch limits as in `ragged.py`."""
 
 import math
 from typing import List, Sequence
@@ -56,7 +56,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from . import ops, voxel
+from . import ops, ragged
 
 MAX_NEIGHBOURS = ops.KNN_MAX_NEIGHBOURS
 POINTS_PER_CELL = 2.0                  # the average the default cell size aims at, empty cells counted
@@ -72,32 +72,8 @@ def _check_neighbours(nb_neighbors) -> int:
     return int(nb_neighbors)
 
 
-def _check_positive(name: str, value) -> float:
-    v = float(value)
-    if not math.isfinite(v) or v <= 0.0:
-        raise ValueError('%s must be positive and finite, got %r' % (name, value))
-    return v
-
-
 def _nonfinite_error(i: int):
     return ValueError('cloud %d holds a coordinate that is not finite' % i)
-
-
-def _no_point_error(i: int, step: str):
-    return ValueError('cloud %d has no point left after %s' % (i, step))
-
-
-def _as_arrays(clouds):
-    arrays = [np.ascontiguousarray(np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3))
-              for c in clouds]
-    voxel._check_batch([a.shape[0] for a in arrays])
-    return arrays
-
-
-def _pack(*parts):
-    """(result, optional extras...) -> the result alone, or the tuple of what was asked for"""
-    res = tuple(p for p in parts if p is not None)
-    return res[0] if len(res) == 1 else res
 
 
 # ------------------------------------------------------------------------------------------------ host route (numpy)
@@ -134,7 +110,7 @@ def _threshold_host(avg: np.ndarray, std_ratio: float):
 
 
 def _checked_arrays(clouds):
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     for i, a in enumerate(arrays):
         if not np.isfinite(a).all():
             raise _nonfinite_error(i)
@@ -157,24 +133,25 @@ def remove_outliers_host(clouds: Sequence, nb_neighbors: int = 20, std_ratio: fl
     masks, with `return_distances` the (n_i,) float32 avg, with `return_stats` per-cloud dicts 'mean', 'std', 'threshold'
     (floats; NaN as step 4 says) and 'n_valid' (int).  A single valid point keeps nothing, as in open3d."""
     nb = _check_neighbours(nb_neighbors)
-    ratio = _check_positive('std_ratio', std_ratio)
+    ratio = ragged.check_positive('std_ratio', std_ratio)
     arrays = _checked_arrays(clouds)
     avgs = [_knn_mean_host(a, nb) for a in arrays]
     stats = [_threshold_host(avg, ratio) for avg in avgs]
     with np.errstate(invalid='ignore'):
         masks = [(avg > 0) & (avg.astype(np.float64) < s[2]) for avg, s in zip(avgs, stats)]
-    return _pack([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None, avgs if return_distances else None,
-                 [dict(mean=s[0], std=s[1], threshold=s[2], n_valid=s[3]) for s in stats] if return_stats else None)
+    return ragged.results([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None,
+                          avgs if return_distances else None,
+                          [dict(mean=s[0], std=s[1], threshold=s[2], n_valid=s[3]) for s in stats] if return_stats else None)
 
 
 def trim_radius_host(clouds: Sequence, radius_max: float = 30.0, *, return_mask: bool = False):
     """The radius trim in numpy float64 -> list of (k_i, 3) float32 arrays, the rows with sqrt(x x + y y) <= radius_max in
     input order (k_i may be 0); with `return_mask` also the (n_i,) bool masks."""
-    r = _check_positive('radius_max', radius_max)
-    arrays = _as_arrays(clouds)
+    r = ragged.check_positive('radius_max', radius_max)
+    arrays = ragged.as_arrays(clouds)
     with np.errstate(over='ignore', invalid='ignore'):
         masks = [np.linalg.norm(a[:, :2].astype(np.float64), axis=1) <= r for a in arrays]
-    return _pack([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None)
+    return ragged.results([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None)
 
 
 # ------------------------------------------------------------------------------------------------ device route
@@ -219,28 +196,31 @@ def grid_layout(lo_hi: np.ndarray, sizes, nb: int, cell_size=None, budget_bytes:
     return grids
 
 
-def _sorted_batch(pts, off, off_host, nb: int, cell_size):
-    """bounds and the finite check (the one host read before the search), the grids, keys, sort, gather"""
-    batch = len(off_host) - 1
+def check_params(nb_neighbors: int = 20, std_ratio: float = 3.0, cell_size=None):
+    """the keyword parameters of `remove_outliers`, checked -> (nb, ratio, cell)"""
+    return (_check_neighbours(nb_neighbors), ragged.check_positive('std_ratio', std_ratio),
+            None if cell_size is None else ragged.check_positive('cell_size', cell_size))
+
+
+def sorted_batch(packed, nb: int, cell_size=None):
+    """bounds and the finite check (the one host read before the search), the grids, keys, sort, gather -> (table, the points
+    cell by cell, their ascending keys, the sort's permutation)"""
+    pts, off, batch = packed.pts, packed.off, packed.batch
     bounds, flags = ops.voxel_bounds(pts, off), ops.cloud_nonfinite(pts, off)
     host = torch.cat([bounds.reshape(-1), flags]).cpu().numpy()
     lo_hi = ops.decode_voxel_bounds(host[:6 * batch])
     for i in range(batch):
         if host[6 * batch + i] or not np.isfinite(lo_hi[i]).all():
             raise _nonfinite_error(i)
-    table = ops.KnnGridTable(grid_layout(lo_hi, np.diff(off_host).tolist(), nb, cell_size), pts.device)
+    table = ops.KnnGridTable(grid_layout(lo_hi, packed.sizes(), nb, cell_size), pts.device)
     keys = ops.knn_cell_keys(pts, off, table)
     sorted_keys, perm = torch.sort(keys)
     return table, ops.voxel_gather_rows(pts, perm), sorted_keys, perm
 
 
-def _knn_device(pts, off, off_host, nb: int, cell_size):
-    table, sorted_pts, sorted_keys, perm = _sorted_batch(pts, off, off_host, nb, cell_size)
-    return ops.knn_mean_dist(sorted_pts, sorted_keys, perm, off, table)
-
-
-def _check_cell(cell_size):
-    return None if cell_size is None else _check_positive('cell_size', cell_size)
+def _knn_packed(packed, nb: int, cell_size):
+    table, sorted_pts, sorted_keys, perm = sorted_batch(packed, nb, cell_size)
+    return ops.knn_mean_dist(sorted_pts, sorted_keys, perm, packed.off, table)
 
 
 def knn_mean_distance(clouds: Sequence, nb_neighbors: int = 20, *, device='cuda', cell_size=None,
@@ -249,25 +229,21 @@ def knn_mean_distance(clouds: Sequence, nb_neighbors: int = 20, *, device='cuda'
     returns, for any `cell_size` (the edge of the search grid's cells; the default is chosen per cloud).  With
     `return_pending` also the number of points of the batch that the 3 x 3 x 3 scan could not prove complete and the
     whole-cloud scan finished (a debug counter)."""
-    nb = _check_neighbours(nb_neighbors)
-    cell = _check_cell(cell_size)
-    ts = voxel._as_tensors(clouds)
-    device = voxel._device(device)
-    if not ts:
-        return ([], 0) if return_pending else []
-    with torch.cuda.device(device):
-        pts, off, off_host = voxel._upload(ts, device)
-        avg, pending = _knn_device(pts, off, off_host, nb, cell)
-        out = [avg[s:e] for s, e in zip(off_host[:-1], off_host[1:])]
-        return (out, int(pending.item())) if return_pending else out
+    nb, _, cell = check_params(nb_neighbors, cell_size=cell_size)
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ([], 0) if return_pending else []
+        avg, pending = _knn_packed(packed, nb, cell)
+        return (packed.split(avg), int(pending.item())) if return_pending else packed.split(avg)
 
 
-def _compact(pts, keep, off_host):
-    """the kept rows of every cloud in input order, as `ground.remove_ground` compacts its mask"""
-    index = torch.nonzero(keep).reshape(-1)                                  # ascending: the order of the input
-    rows = ops.voxel_gather_rows(pts, index)
-    ends = np.searchsorted(index.cpu().numpy(), off_host)                    # the kept rows before every cloud's first point
-    return [rows[s:e] for s, e in zip(ends[:-1], ends[1:])]
+def remove_outliers_packed(packed, nb: int, ratio: float, cell=None):
+    """the filter on a packed batch, parameters as `check_params` returns them -> (the kept rows as a `ragged.Packed`,
+    keep (P,) uint8, avg (P,) fp32, stats (B, 4) float64), everything on the device"""
+    avg, _ = _knn_packed(packed, nb, cell)
+    stats = ops.outlier_threshold(avg, packed.off, ratio)
+    keep = ops.outlier_mask(avg, packed.off, stats)
+    return ragged.compact(packed, keep), keep, avg, stats
 
 
 def remove_outliers(clouds: Sequence, nb_neighbors: int = 20, std_ratio: float = 3.0, *, device='cuda',
@@ -279,62 +255,40 @@ def remove_outliers(clouds: Sequence, nb_neighbors: int = 20, std_ratio: float =
     point keeps nothing (std = 0 / 0 = NaN), as in open3d.  `cell_size` sets the edge of the search grid's cells and
     changes no bit of any output.  `ValueError` for a bad parameter or an empty cloud (before the device is touched) and,
     naming the cloud, for a coordinate that is not finite (before any kernel of the filter runs)."""
-    nb = _check_neighbours(nb_neighbors)
-    ratio = _check_positive('std_ratio', std_ratio)
-    cell = _check_cell(cell_size)
-    ts = voxel._as_tensors(clouds)
-    device = voxel._device(device)
-    if not ts:
-        return _pack([], [] if return_mask else None, [] if return_distances else None, [] if return_stats else None)
-    with torch.cuda.device(device):
-        pts, off, off_host = voxel._upload(ts, device)
-        avg, _ = _knn_device(pts, off, off_host, nb, cell)
-        stats = ops.outlier_threshold(avg, off, ratio)
-        keep = ops.outlier_mask(avg, off, stats)
-        split = list(zip(off_host[:-1], off_host[1:]))
-        return _pack(_compact(pts, keep, off_host),
-                     [keep[s:e].bool() for s, e in split] if return_mask else None,
-                     [avg[s:e] for s, e in split] if return_distances else None,
-                     [dict(mean=m, std=s, threshold=t, n_valid=int(v)) for m, s, t, v in stats.cpu().tolist()]
-                     if return_stats else None)
+    params = check_params(nb_neighbors, std_ratio, cell_size)
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ragged.empty_results(return_mask, return_distances, return_stats)
+        kept, keep, avg, stats = remove_outliers_packed(packed, *params)
+        return ragged.results(kept.split(), packed.split(keep.bool()) if return_mask else None,
+                              packed.split(avg) if return_distances else None,
+                              [dict(mean=m, std=s, threshold=t, n_valid=int(v)) for m, s, t, v in stats.cpu().tolist()]
+                              if return_stats else None)
+
+
+def trim_radius_packed(packed, radius_max: float):
+    """the radius trim on a packed batch -> (the kept rows as a `ragged.Packed`, keep (P,) uint8)"""
+    keep = ops.radius_mask(packed.pts, radius_max)
+    return ragged.compact(packed, keep), keep
 
 
 def trim_radius(clouds: Sequence, radius_max: float = 30.0, *, device='cuda', return_mask: bool = False):
     """`trim_radius_host` on the device: list of (k_i, 3) float32 device tensors, the rows with sqrt(x x + y y) <=
     `radius_max` (float64) in input order, equal to the numpy route's; a cloud left empty comes back empty.  With
     `return_mask` also the (n_i,) bool masks."""
-    r = _check_positive('radius_max', radius_max)
-    ts = voxel._as_tensors(clouds)
-    device = voxel._device(device)
-    if not ts:
-        return ([], []) if return_mask else []
-    with torch.cuda.device(device):
-        pts, _, off_host = voxel._upload(ts, device)
-        keep = ops.radius_mask(pts, r)
-        return _pack(_compact(pts, keep, off_host),
-                     [keep[s:e].bool() for s, e in zip(off_host[:-1], off_host[1:])] if return_mask else None)
-
-
-_remove_outliers = remove_outliers             # `clean_batch` takes a keyword of the same name
+    r = ragged.check_positive('radius_max', radius_max)
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ragged.empty_results(return_mask)
+        kept, keep = trim_radius_packed(packed, r)
+        return ragged.results(kept.split(), packed.split(keep.bool()) if return_mask else None)
 
 
 def clean_batch(clouds: Sequence, device, radius_max=None, remove_outliers: bool = False, outlier_params=None,
                 at_least: int = 1) -> List[torch.Tensor]:
-    """The raw cleaning of the submap entry points of `voxel.py` and `retrieval.encode_clouds`: `trim_radius` (when
-    `radius_max` is given), then `remove_outliers(**outlier_params)`, the batch staying on the device between the two.
-    `ValueError` naming the first cloud a step leaves no point, or fewer than `at_least` points."""
-    out = clouds
-    steps = []
-    if radius_max is not None:
-        steps.append(('the radius trim', lambda c: trim_radius(c, radius_max, device=device)))
-    if remove_outliers:
-        steps.append(('outlier removal', lambda c: _remove_outliers(c, device=device, **(outlier_params or {}))))
-    for name, step in steps:
-        out = step(out)
-        for i, c in enumerate(out):
-            if c.shape[0] < 1:
-                raise _no_point_error(i, name)
-            if c.shape[0] < at_least:
-                raise ValueError('cloud %d has %d points left after %s, fewer than target = %d'
-                                 % (i, c.shape[0], name, at_least))
-    return out
+    """The raw cleaning alone, as the submap entry points of `voxel.py` run it in front of everything else: `trim_radius`
+    (when `radius_max` is given), then `remove_outliers(**outlier_params)`, the batch staying packed on the device between
+    the two.  `ValueError` naming the first cloud a step leaves no point, or fewer than `at_least` points."""
+    from .voxel import submap_chain                  # a public alias kept for callers: voxel.py holds the chain
+    return submap_chain(clouds, device, radius_max=radius_max, remove_outliers=remove_outliers, outlier_params=outlier_params,
+                        at_least=at_least)

@@ -190,17 +190,18 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
     iterable) -> (len, output_dim) fp32 descriptors on the GPU, `batch_size` clouds per forward (the last batch may be
     short).  Puts the model in eval mode; `prepare_kwargs` go to `prepare_clouds`.  With `voxel_size` and / or
     `normalise_submaps` the clouds are raw submaps in a metric frame: every batch first goes through the CS-Wild-Places
-    submap post-processing on the device (`voxel.prepare_submaps`: voxel-grid downsample at `voxel_size`, then the
-    PointNetVLAD normalisation); with the defaults nothing changes.  With `downsample_target` = N the raw submaps become
-    fixed-size clouds of N points instead (the Oxford / CS-Campus3D format, `voxel.prepare_submaps_fixed`: the
-    `downsample_type` 'pnvlad' or 'random' downsampler, then, when `normalise_submaps`, the normalisation with padding);
+    submap post-processing on the device (`voxel.submap_chain`, as `voxel.prepare_submaps` runs it: voxel-grid downsample at
+    `voxel_size`, then the PointNetVLAD normalisation); with the defaults nothing changes and the clouds go to
+    `prepare_clouds` as they are.  With `downsample_target` = N the raw submaps become fixed-size clouds of N points
+    instead (the Oxford / CS-Campus3D format, `voxel.prepare_submaps_fixed`: the `downsample_type` 'pnvlad' or 'random'
+    downsampler, then, when `normalise_submaps`, the normalisation with padding);
     it cannot be combined with `voxel_size`.  With `remove_ground` every batch of raw submaps first goes through the cloth
     filter on the device (`ground.remove_ground(**ground_params)`), before whichever of the steps above is asked for.
-    With `radius_max` and / or `remove_outliers` every batch is cleaned before everything else (`outliers.clean_batch`:
-    the radius trim, then the statistical outlier filter with `outlier_params`)."""
+    With `radius_max` and / or `remove_outliers` every batch is cleaned before everything else (the radius trim, then the
+    statistical outlier filter with `outlier_params`)."""
     from .octree import build_batch_octree
     from .preprocess import prepare_clouds
-    from . import ground, outliers, voxel
+    from . import voxel
     if batch_size < 1:
         raise ValueError('encode_clouds: batch_size >= 1 expected, got %d' % batch_size)
     if downsample_target is not None and voxel_size is not None:
@@ -208,23 +209,12 @@ def encode_clouds(model, clouds, batch_size: int, *, coordinates: str = 'cartesi
                          'each other')
     model.eval()
     out, batch = [], []
-    filtered = {'remove_ground': True, 'ground_params': ground_params} if remove_ground else {}
 
     def flush():
-        src = batch
-        if radius_max is not None or remove_outliers:
-            src = outliers.clean_batch(batch, device, radius_max, remove_outliers, outlier_params)
-        if downsample_target is not None:
-            src = voxel.prepare_submaps_fixed(src, downsample_target, downsample=downsample_type,
-                                              normalise=normalise_submaps, device=device, **filtered)
-        elif voxel_size is not None:
-            src = voxel.prepare_submaps(src, voxel_size, normalise=normalise_submaps, device=device, **filtered)
-        elif remove_ground:
-            src = ground.filter_batch(src, device, ground_params)
-            if normalise_submaps:
-                src = voxel.normalise_submaps(src, device=device)
-        elif normalise_submaps:
-            src = voxel.normalise_submaps(src, device=device)
+        src = voxel.submap_chain(batch, device, radius_max=radius_max, remove_outliers=remove_outliers,
+                                 outlier_params=outlier_params, remove_ground=remove_ground, ground_params=ground_params,
+                                 voxel_size=voxel_size, target=downsample_target, downsample=downsample_type,
+                                 normalise=normalise_submaps)
         pts = prepare_clouds(src, coordinates=coordinates, normalize=normalize, device=device, **prepare_kwargs)
         octree = build_batch_octree(pts, octree_depth, full_depth, device)
         out.append(model({'octree': octree})['global'].float())

@@ -57,33 +57,22 @@ padded rows are transformed by `hfl_submap_normalise_rows`, which shares its dev
 Ground removal (`postprocess_submaps.py --remove_ground`, the step before the downsample) is `ground.py`; the entry points
 `prepare_submaps` and `prepare_submaps_fixed` run it first with `remove_ground=True`.  The raw cleaning in front of it -- the
 radius trim and the statistical outlier filter -- is `outliers.py`; the same entry points run it before everything else with
-`radius_max=` / `remove_outliers=True`."""
+`radius_max=` / `remove_outliers=True`.  The order of the whole chain is written once, in `submap_chain`; the batch plumbing
+under all three modules is `ragged.py`."""
 
-import math
 from typing import List, Sequence
 
 import numpy as np
 import torch
 
-from . import _native, ops
+from . import ground, ops, outliers, ragged
+from .ragged import MAX_CLOUDS
 
-MAX_CLOUDS = ops.VOXEL_MAX_CLOUDS
 MAX_CELLS = ops.VOXEL_MAX_CELLS
 
 
 def _check_voxel_size(voxel_size) -> float:
-    v = float(voxel_size)
-    if not math.isfinite(v) or v <= 0.0:
-        raise ValueError('voxel_size must be positive and finite, got %r' % (voxel_size,))
-    return v
-
-
-def _check_batch(sizes):
-    if len(sizes) > MAX_CLOUDS:
-        raise ValueError('a batch holds at most %d clouds, got %d' % (MAX_CLOUDS, len(sizes)))
-    for i, n in enumerate(sizes):
-        if n < 1:
-            raise ValueError('cloud %d is empty' % i)
+    return ragged.check_positive('voxel_size', voxel_size)
 
 
 def _span_error(i: int):
@@ -120,64 +109,42 @@ def voxel_downsample_host(clouds: Sequence, voxel_size: float, return_counts: bo
     clouds -> list of (m_i, 3) float32 arrays in ascending (ix, iy, iz); with `return_counts` also the members of every
     output point (int32), with `return_keys` also its cell as ix << 32 | iy << 16 | iz (int64)."""
     v = _check_voxel_size(voxel_size)
-    arrays = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3) for c in clouds]
-    _check_batch([a.shape[0] for a in arrays])
+    arrays = ragged.as_arrays(clouds)
     outs, counts, keys = [], [], []
     for i, a in enumerate(arrays):
         mean, cnt, uniq = _cell_means(a, v, i)
         outs.append(mean.astype(np.float32))
         counts.append(cnt.astype(np.int32))
         keys.append(uniq)
-    res = (outs,) + ((counts,) if return_counts else ()) + ((keys,) if return_keys else ())
-    return res[0] if len(res) == 1 else res
+    return ragged.results(outs, counts if return_counts else None, keys if return_keys else None)
+
+
+def _normalise_host(a: np.ndarray, index: int):
+    """one cloud -> (the kept rows of s (q - c) in float64, c, s)"""
+    q = a.astype(np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):               # non-finite input ends in one of the errors below
+        c = q.mean(axis=0)
+        d = np.sqrt(((q - c) ** 2).sum(axis=1)).mean()
+    if not d > 0.0:
+        raise _degenerate_error(index)
+    scaled = (0.5 / d) * (q - c)
+    kept = scaled[np.all(np.abs(scaled) <= 1.0, axis=1)]
+    if kept.shape[0] < 1:
+        raise _empty_error(index)
+    return kept, c, 0.5 / d
 
 
 def normalise_submaps_host(clouds: Sequence) -> List[np.ndarray]:
     """`normalise_pcl` without padding in numpy float64 (see the module docstring) -> list of (k_i, 3) float32 arrays."""
-    arrays = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3) for c in clouds]
-    _check_batch([a.shape[0] for a in arrays])
-    outs = []
-    for i, a in enumerate(arrays):
-        q = a.astype(np.float64)
-        with np.errstate(invalid='ignore', over='ignore'):           # non-finite input ends in one of the errors below
-            c = q.mean(axis=0)
-            d = np.sqrt(((q - c) ** 2).sum(axis=1)).mean()
-        if not d > 0.0:
-            raise _degenerate_error(i)
-        scaled = (0.5 / d) * (q - c)
-        kept = scaled[np.all(np.abs(scaled) <= 1.0, axis=1)]
-        if kept.shape[0] < 1:
-            raise _empty_error(i)
-        outs.append(kept.astype(np.float32))
-    return outs
+    return [_normalise_host(a, i)[0].astype(np.float32) for i, a in enumerate(ragged.as_arrays(clouds))]
 
 
 # ------------------------------------------------------------------------------------------------ device route
-def _device(device):
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise _native.NativeLibraryError('the device route runs on the GPU (no CPU fallback); use the *_host functions')
-    if device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
-    return device
+_upload = ragged.upload            # under the name the tests replace to prove that an error came before any upload
 
 
-def _as_tensors(clouds):
-    """the batch as (n_i, 3) fp32 tensors where they lie, checked before the device is touched"""
-    ts = [torch.as_tensor(c, dtype=torch.float32).reshape(-1, 3) for c in clouds]
-    _check_batch([int(t.shape[0]) for t in ts])
-    return ts
-
-
-def _upload(ts, device):
-    """one concatenated (P, 3) fp32 device tensor and the (B + 1,) offsets on both sides"""
-    sizes = [int(t.shape[0]) for t in ts]
-    off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    if all(not t.is_cuda for t in ts):
-        pts = torch.cat(ts).to(device, non_blocking=True).contiguous()           # one upload
-    else:
-        pts = torch.cat([t.to(device, non_blocking=True) for t in ts]).contiguous()
-    return pts, torch.from_numpy(off_host).to(device, non_blocking=True), off_host
+def _intake(clouds, device, check=None):
+    return ragged.intake(clouds, device, check, _upload)
 
 
 def _downsample_launch(pts, off, batch, v, return_counts, return_keys):
@@ -188,35 +155,6 @@ def _downsample_launch(pts, off, batch, v, return_counts, return_keys):
     return out, out_off, span_flags, counts, okeys
 
 
-def voxel_downsample(clouds: Sequence, voxel_size: float, device='cuda', return_counts: bool = False,
-                     return_keys: bool = False):
-    """List of raw (n_i, 3) clouds (numpy / torch) -> list of (m_i, 3) float32 device tensors, one point per occupied voxel
-    in ascending (ix, iy, iz) (module docstring).  `return_counts`: also the number of members of every output point
-    (list of (m_i,) int32 tensors); `return_keys`: also its cell as ix << 32 | iy << 16 | iz (list of (m_i,) int64).
-    `ValueError` for a bad `voxel_size`, more than 32 767 clouds, an empty cloud, or -- naming the first such cloud, and
-    returning none -- a cloud that spans 65 536 or more voxels along an axis."""
-    v = _check_voxel_size(voxel_size)
-    clouds = _as_tensors(clouds)
-    device = _device(device)
-    if not clouds:
-        return tuple([] for _ in range(1 + bool(return_counts) + bool(return_keys))) if return_counts or return_keys else []
-    with torch.cuda.device(device):
-        pts, off, _ = _upload(clouds, device)
-        batch = off.shape[0] - 1
-        out, out_off, span_flags, counts, okeys = _downsample_launch(pts, off, batch, v, return_counts, return_keys)
-        host = torch.cat([span_flags.to(torch.int64), out_off]).cpu().tolist()    # the one host read: flags and offsets
-    flags, starts = host[:batch], host[batch:]
-    for i, f in enumerate(flags):
-        if f:
-            raise _span_error(i)
-    res = ([out[s:e] for s, e in zip(starts[:-1], starts[1:])],)
-    if return_counts:
-        res += ([counts[s:e] for s, e in zip(starts[:-1], starts[1:])],)
-    if return_keys:
-        res += ([okeys[s:e] & ((1 << 48) - 1) for s, e in zip(starts[:-1], starts[1:])],)
-    return res[0] if len(res) == 1 else res
-
-
 def _raise_normalise(flags, kept):
     for i, (f, k) in enumerate(zip(flags, kept)):
         if f:
@@ -225,62 +163,128 @@ def _raise_normalise(flags, kept):
             raise _empty_error(i)
 
 
+def _downsample_packed(packed, v, normalise: bool = False, return_counts: bool = False, return_keys: bool = False):
+    """The voxel grid on a packed batch and, with `normalise`, the normalisation reading the downsampled rows and their
+    offsets where the reduction left them; span flags, offsets, and the normalisation's flags and counts come back in the
+    one host read.  -> (the rows as a `ragged.Packed`, kept (the rows of every cloud that the normalisation kept from its
+    first row on, or None), cell counts or None, keys or None)"""
+    batch = packed.batch
+    out, out_off, span_flags, counts, okeys = _downsample_launch(packed.pts, packed.off, batch, v, return_counts, return_keys)
+    parts = [span_flags.to(torch.int64), out_off]
+    if normalise:
+        out, kept, flags = ops.submap_normalise(out, out_off)
+        parts += [flags.to(torch.int64), kept.to(torch.int64)]
+    host = torch.cat(parts).cpu().tolist()                                        # the one host read
+    for i, f in enumerate(host[:batch]):
+        if f:
+            raise _span_error(i)
+    kept = None
+    if normalise:
+        kept = host[3 * batch + 1:]
+        _raise_normalise(host[2 * batch + 1:3 * batch + 1], kept)
+    return ragged.Packed(out, np.asarray(host[batch:2 * batch + 1], dtype=np.int64), out_off), kept, counts, okeys
+
+
+def voxel_downsample(clouds: Sequence, voxel_size: float, device='cuda', return_counts: bool = False,
+                     return_keys: bool = False):
+    """List of raw (n_i, 3) clouds (numpy / torch) -> list of (m_i, 3) float32 device tensors, one point per occupied voxel
+    in ascending (ix, iy, iz) (module docstring).  `return_counts`: also the number of members of every output point
+    (list of (m_i,) int32 tensors); `return_keys`: also its cell as ix << 32 | iy << 16 | iz (list of (m_i,) int64).
+    `ValueError` for a bad `voxel_size`, more than 32 767 clouds, an empty cloud, or -- naming the first such cloud, and
+    returning none -- a cloud that spans 65 536 or more voxels along an axis."""
+    v = _check_voxel_size(voxel_size)
+    with _intake(clouds, device) as packed:
+        if packed is None:
+            return ragged.empty_results(return_counts, return_keys)
+        down, _, counts, okeys = _downsample_packed(packed, v, False, return_counts, return_keys)
+        return ragged.results(down.split(), down.split(counts) if return_counts else None,
+                              down.split(okeys & ((1 << 48) - 1)) if return_keys else None)
+
+
+def _normalise_packed(packed):
+    """`hfl_submap_normalise` and its one host read -> (out (P, 3): cloud b's kept rows from row `off_host[b]` on, kept (B,))"""
+    out, counts, flags = ops.submap_normalise(packed.pts, packed.off)
+    host = torch.cat([flags, counts]).cpu().tolist()                              # the one host read
+    _raise_normalise(host[:packed.batch], host[packed.batch:])
+    return out, host[packed.batch:]
+
+
 def normalise_submaps(clouds: Sequence, device='cuda') -> List[torch.Tensor]:
     """List of (n_i, 3) clouds -> list of (k_i, 3) float32 device tensors: the PointNetVLAD normalisation of
     `normalise_pcl` without padding (module docstring), one HIP launch for the batch.  `ValueError`, naming the cloud, when
     a cloud's mean distance to its centroid is zero (a single point) or no point is left inside [-1, 1]^3."""
-    clouds = _as_tensors(clouds)
-    device = _device(device)
-    if not clouds:
+    with _intake(clouds, device) as packed:
+        if packed is None:
+            return []
+        out, kept = _normalise_packed(packed)
+        return packed.split(out, kept)
+
+
+def submap_chain(clouds: Sequence, device='cuda', *, radius_max=None, remove_outliers: bool = False, outlier_params=None,
+                 remove_ground: bool = False, ground_params=None, voxel_size=None, target=None, downsample: str = 'pnvlad',
+                 normalise: bool = False, seed=42, at_least=None) -> List[torch.Tensor]:
+    """The raw-submap chain, the one place its order is written: the radius trim (`radius_max`), outlier removal
+    (`remove_outliers`, `outlier_params`), ground removal (`remove_ground`, `ground_params`), then the voxel grid
+    (`voxel_size`) or the fixed-size downsample (`target`, `downsample`, `seed`), then the normalisation (`normalise`: padded
+    to `target` rows from the filtered cloud on the fixed-size path).  Every step is optional; with none the clouds come back
+    as they are.  The batch is uploaded once and stays packed on the device (`ragged.Packed`); the result equals the public
+    functions chained through lists bit for bit.  Parameters and emptiness are checked before the device is touched.  After a
+    filter `ValueError` names the first cloud, by its index in `clouds`, with no point left or with fewer than `at_least`
+    points: by default `target` where the 'pnvlad' search follows and after ground removal on the fixed-size path, else 1."""
+    v = None if voxel_size is None else _check_voxel_size(voxel_size)
+    if target is not None:
+        if downsample not in ('pnvlad', 'random'):
+            raise ValueError("downsample must be 'pnvlad' or 'random', got %r" % (downsample,))
+        target = _check_target(target)
+    r = None if radius_max is None else ragged.check_positive('radius_max', radius_max)
+    outlier_params = outliers.check_params(**(outlier_params or {})) if remove_outliers else None
+    cloth = ground.ClothParams(**(ground_params or {})) if remove_ground else None
+    filters = r is not None or remove_outliers or remove_ground
+    if not (filters or v is not None or target is not None or normalise):
+        return clouds                                                             # no step asked for: nothing is touched
+    cleaned_few = ground_few = at_least
+    if at_least is None:
+        cleaned_few = target if target is not None and downsample == 'pnvlad' else 1
+        ground_few = 1 if target is None else target
+    ts = ragged.as_tensors(clouds)
+    if target is not None and downsample == 'pnvlad' and not filters:
+        _check_enough_points([int(t.shape[0]) for t in ts], target)
+    device = ragged.device_of(device)
+    if not ts:
         return []
     with torch.cuda.device(device):
-        pts, off, off_host = _upload(clouds, device)
-        out, counts, flags = ops.submap_normalise(pts, off)
-        host = torch.cat([flags, counts]).cpu().tolist()                          # the one host read
-    batch = len(off_host) - 1
-    _raise_normalise(host[:batch], host[batch:])
-    return [out[s:s + k] for s, k in zip(off_host.tolist(), host[batch:])]
+        packed = _upload(ts, device)
+        if r is not None:
+            packed = outliers.trim_radius_packed(packed, r)[0]
+            ragged.require_points(packed, 'the radius trim', cleaned_few)
+        if remove_outliers:
+            packed = outliers.remove_outliers_packed(packed, *outlier_params)[0]
+            ragged.require_points(packed, 'outlier removal', cleaned_few)
+        if remove_ground:
+            packed = ground.remove_ground_packed(packed, cloth)[0]
+            ragged.require_points(packed, 'ground removal', ground_few)
+        if v is not None:
+            packed, kept, _, _ = _downsample_packed(packed, v, normalise)
+            return packed.split(counts=kept)
+        if target is not None:
+            raw = packed
+            packed = _pnvlad_packed(raw, target, seed)[0] if downsample == 'pnvlad' else _random_packed(raw, target, seed)
+            return _normalise_padded_packed(packed, raw, target, seed) if normalise else packed.split()
+        return packed.split(*_normalise_packed(packed)) if normalise else packed.split()
 
 
 def prepare_submaps(clouds: Sequence, voxel_size: float, normalise: bool = True, device='cuda', *, remove_ground: bool = False,
                     ground_params=None, radius_max=None, remove_outliers: bool = False,
                     outlier_params=None) -> List[torch.Tensor]:
-    """`voxel_downsample` then (when `normalise`) `normalise_submaps` without leaving the device: the normalisation reads
-    the downsampled batch and its per-cloud offsets where the reduction left them, and flags, offsets and counts come back
-    in one host read.  The result is what `prepare_clouds` takes; it equals the two calls chained bit for bit.  With
-    `remove_ground` the raw batch first goes through `ground.remove_ground(**ground_params)` and stays on the device: the
-    documented CS-Wild-Places order, remove the ground, downsample, normalise.  `ValueError`, naming the cloud, when the
-    filter leaves a cloud no point.  With `radius_max` and / or `remove_outliers` the raw batch is cleaned before all that
-    (`outliers.clean_batch`: `trim_radius`, then `remove_outliers(**outlier_params)`), as the reference trims and cleans
-    the raw points first; the result equals the chained public calls bit for bit, and a cloud left empty raises
+    """`submap_chain` with the voxel grid: `voxel_downsample` then (when `normalise`) `normalise_submaps` without leaving
+    the device, flags, offsets and counts coming back in one host read.  The result is what `prepare_clouds` takes.  With
+    `remove_ground` the raw batch first goes through `ground.remove_ground(**ground_params)` (the documented CS-Wild-Places
+    order), with `radius_max` and / or `remove_outliers` through `trim_radius` and `remove_outliers(**outlier_params)`
+    before that.  The result equals the public calls chained bit for bit; a cloud a filter leaves no point raises
     `ValueError` naming it."""
-    if radius_max is not None or remove_outliers:
-        from . import outliers
-        _check_voxel_size(voxel_size)
-        clouds = outliers.clean_batch(clouds, device, radius_max, remove_outliers, outlier_params)
-    if remove_ground:
-        from . import ground
-        _check_voxel_size(voxel_size)
-        clouds = ground.filter_batch(clouds, device, ground_params)
-    if not normalise:
-        return voxel_downsample(clouds, voxel_size, device=device)
-    v = _check_voxel_size(voxel_size)
-    clouds = _as_tensors(clouds)
-    device = _device(device)
-    if not clouds:
-        return []
-    with torch.cuda.device(device):
-        pts, off, _ = _upload(clouds, device)
-        batch = off.shape[0] - 1
-        down, down_off, span_flags, _, _ = _downsample_launch(pts, off, batch, v, False, False)
-        out, counts, flags = ops.submap_normalise(down, down_off)
-        host = torch.cat([span_flags.to(torch.int64), flags.to(torch.int64), counts.to(torch.int64), down_off]).cpu().tolist()
-    for i, f in enumerate(host[:batch]):
-        if f:
-            raise _span_error(i)
-    kept, starts = host[2 * batch:3 * batch], host[3 * batch:]
-    _raise_normalise(host[batch:2 * batch], kept)
-    return [out[s:s + k] for s, k in zip(starts[:-1], kept)]
+    return submap_chain(clouds, device, radius_max=radius_max, remove_outliers=remove_outliers, outlier_params=outlier_params,
+                        remove_ground=remove_ground, ground_params=ground_params, voxel_size=_check_voxel_size(voxel_size),
+                        normalise=normalise)
 
 
 # ================================================================================================ fixed-size clouds
@@ -311,12 +315,6 @@ def _unreachable_error(i: int, target: int, why: str):
     return ValueError('cloud %d never reaches %d occupied voxels: %s' % (i, target, why))
 
 
-def _as_arrays(clouds):
-    arrays = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 3) for c in clouds]
-    _check_batch([a.shape[0] for a in arrays])
-    return arrays
-
-
 def _pad_indices(seed, n: int, k: int) -> np.ndarray:
     """`rng.choice(points, size=k)` of a fresh generator, as row indices"""
     return np.random.default_rng(seed).choice(n, size=k).astype(np.int64)
@@ -341,7 +339,7 @@ def voxel_occupancy_host(clouds: Sequence, sizes: Sequence[float]) -> np.ndarray
     """(B, S) int32: the number of occupied cells of every cloud at every voxel size, i.e.
     `len(voxel_downsample_host([cloud], v)[0])`, in numpy float64."""
     vs = [_check_voxel_size(v) for v in sizes]
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     out = np.zeros((len(arrays), len(vs)), np.int32)
     for i, a in enumerate(arrays):
         count = _host_counter(a, i)
@@ -355,7 +353,7 @@ def pnvlad_search_host(clouds: Sequence, target: int = 4096) -> List[dict]:
     (the float64 the search ends on), 'count' (occupied cells there, <= target), 'trace' (every (v, count) probed, in
     order), 'phase_one_steps', 'phase_two_steps'."""
     target = _check_target(target)
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     _check_enough_points([a.shape[0] for a in arrays], target)
     res = []
     for i, a in enumerate(arrays):
@@ -387,7 +385,7 @@ def pnvlad_downsample_host(clouds: Sequence, target: int = 4096, seed=42, return
     """`pnvlad_down_sample` per cloud in numpy float64 (module docstring) -> list of (target, 3) float32 arrays: the cell
     means at the voxel size the search ends on, in ascending (ix, iy, iz), then `target - m` raw rows drawn by a fresh
     `default_rng(seed)`.  With `return_voxel_sizes` also the list of those sizes."""
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     found = pnvlad_search_host(arrays, target)
     outs = []
     for i, (a, f) in enumerate(zip(arrays, found)):
@@ -400,7 +398,7 @@ def pnvlad_downsample_host(clouds: Sequence, target: int = 4096, seed=42, return
 def random_downsample_host(clouds: Sequence, target: int, seed=42) -> List[np.ndarray]:
     """`random_down_sample`: `target` rows of every cloud drawn with replacement by a fresh `default_rng(seed)`."""
     target = _check_target(target)
-    arrays = _as_arrays(clouds)
+    arrays = ragged.as_arrays(clouds)
     return [a[_pad_indices(seed, a.shape[0], target)] for a in arrays]
 
 
@@ -418,21 +416,12 @@ def normalise_submaps_padded_host(downsampled: Sequence, raw: Sequence, target: 
     `normalise_submaps_host(downsampled)`, then rows of `raw` drawn by `default_rng(seed)` (one generator per cloud, carried
     across the iterations), sent through the same centroid and scale and kept when every |q'| <= 1."""
     target = _check_target(target)
-    down, raws = _as_arrays(downsampled), _as_arrays(raw)
+    down, raws = ragged.as_arrays(downsampled), ragged.as_arrays(raw)
     if len(down) != len(raws):
         raise ValueError('%d downsampled clouds but %d raw clouds' % (len(down), len(raws)))
     outs = []
     for i, (a, r) in enumerate(zip(down, raws)):
-        q = a.astype(np.float64)
-        with np.errstate(invalid='ignore', over='ignore'):
-            c = q.mean(axis=0)
-            d = np.sqrt(((q - c) ** 2).sum(axis=1)).mean()
-        if not d > 0.0:
-            raise _degenerate_error(i)
-        scaled = (0.5 / d) * (q - c)
-        kept = scaled[np.all(np.abs(scaled) <= 1.0, axis=1)]
-        if kept.shape[0] < 1:
-            raise _empty_error(i)
+        kept, c, scale = _normalise_host(a, i)
         if kept.shape[0] > target:
             raise _too_many_error(i, kept.shape[0], target)
         rng = np.random.default_rng(seed)
@@ -442,7 +431,7 @@ def normalise_submaps_padded_host(downsampled: Sequence, raw: Sequence, target: 
             if rounds == PAD_MAX_ITERATIONS:
                 raise _padding_error(i, target)
             rounds += 1
-            rows = (0.5 / d) * (r64[rng.choice(r.shape[0], size=extra - added)] - c)
+            rows = scale * (r64[rng.choice(r.shape[0], size=extra - added)] - c)
             rows = rows[np.all(np.abs(rows) <= 1.0, axis=1)]
             added += rows.shape[0]
             parts.append(rows)
@@ -451,7 +440,7 @@ def normalise_submaps_padded_host(downsampled: Sequence, raw: Sequence, target: 
 
 
 # ------------------------------------------------------------------------------------------------ device route
-def _grid_dims(lo_hi: np.ndarray, v: float):
+def grid_dims(lo_hi: np.ndarray, v: float):
     """(nx, ny, nz) of a cloud with bounds `lo_hi` = (min x, y, z, max x, y, z) fp32 at voxel size v, by the formula of the
     kernels, or None when it spans more than MAX_CELLS cells along an axis"""
     low, high = lo_hi[:3].astype(np.float64), lo_hi[3:].astype(np.float64)
@@ -471,9 +460,10 @@ def _count_by_sort(pts, start: int, end: int, v: float):
     return out_off[1:] - out_off[:1]
 
 
-def _count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes: int, stats=None) -> List[int]:
+def _count_candidates(packed, bounds, cands, budget_bytes: int, stats=None) -> List[int]:
     """cands: list of (cloud, v, (nx, ny, nz)) -> their occupied-cell counts, one host read.  Candidates are packed into
     `hfl_voxel_occupancy` calls of at most `budget_bytes` of bitmaps; one whose own bitmap is larger goes to the sort route."""
+    pts, off, off_host = packed.pts, packed.off, packed.off_host
     budget_words = max(min(int(budget_bytes) // 4, ops.VOXEL_OCC_MAX_WORDS), 1)
     biggest = int(np.diff(off_host).max())
     parts, order, held = [], [], []
@@ -511,39 +501,32 @@ def _count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes: in
     return counts
 
 
-def _bounds_host(pts, off):
-    bounds = ops.voxel_bounds(pts, off)
-    return bounds, ops.decode_voxel_bounds(bounds.cpu().numpy())                  # the one host read of the bounds
-
-
 def voxel_occupancy(clouds: Sequence, sizes: Sequence[float], device='cuda', budget_bytes: int = OCCUPANCY_BUDGET_BYTES):
     """(B, S) int32 device tensor: the number of occupied cells of every cloud at every voxel size -- what
     `voxel_downsample` would return rows for -- counted by `hfl_voxel_occupancy` without a sort.  `budget_bytes` bounds the
     bitmaps of one call (module docstring).  `ValueError` as `voxel_downsample`, the span limit included."""
     vs = [_check_voxel_size(v) for v in sizes]
-    clouds = _as_tensors(clouds)
-    device = _device(device)
-    if not clouds or not vs:
-        return torch.zeros((len(clouds), len(vs)), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        pts, off, off_host = _upload(clouds, device)
-        bounds, lo_hi = _bounds_host(pts, off)
+    ts = ragged.as_tensors(clouds)
+    if not ts or not vs:
+        return torch.zeros((len(ts), len(vs)), dtype=torch.int32, device=ragged.device_of(device))
+    with _intake(ts, device) as packed:
+        bounds, lo_hi = ragged.bounds_host(packed)
         cands = []
-        for c in range(len(clouds)):
+        for c in range(packed.batch):
             for v in vs:
-                dims = _grid_dims(lo_hi[c], v)
+                dims = grid_dims(lo_hi[c], v)
                 if dims is None:
                     raise _span_error(c)
                 cands.append((c, v, dims))
-        counts = _count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes)
-        return torch.tensor(counts, dtype=torch.int32).reshape(len(clouds), len(vs)).to(device)
+        counts = _count_candidates(packed, bounds, cands, budget_bytes)
+        return torch.tensor(counts, dtype=torch.int32).reshape(packed.batch, len(vs)).to(packed.pts.device)
 
 
-def _pnvlad_search_device(pts, off, off_host, target: int, budget_bytes: int):
+def _pnvlad_search_device(packed, target: int, budget_bytes: int):
     """the search of `pnvlad_search_host` with the counts from the device, K candidates per cloud and round -> (per-cloud
     dicts as `pnvlad_search_host` returns them, stats: 'rounds', 'candidates' evaluated per cloud, calls and fallbacks)"""
-    batch = len(off_host) - 1
-    bounds, lo_hi = _bounds_host(pts, off)
+    batch = packed.batch
+    bounds, lo_hi = ragged.bounds_host(packed)
     state = [{'phase': 1, 'v': None, 'trace': [], 'one': 0, 'two': 0, 'count': None, 'k_two': PNVLAD_K_TWO} for _ in range(batch)]
     stats = {'rounds': 0, 'candidates': [0] * batch}
     while any(st['phase'] for st in state):
@@ -565,14 +548,14 @@ def _pnvlad_search_device(pts, off, off_host, target: int, budget_bytes: int):
                     if v <= 0:
                         end = 'the voxel size reached zero'
                         break
-                dims = _grid_dims(lo_hi[c], v)
+                dims = grid_dims(lo_hi[c], v)
                 if dims is None:
                     end = 'at voxel size %.3f it spans more than %d cells along an axis' % (v, MAX_CELLS)
                     break
                 vs.append(v)
                 cands.append((c, v, dims))
             plan.append((c, vs, end))
-        counts = iter(_count_candidates(pts, off, off_host, bounds, lo_hi, cands, budget_bytes, stats))
+        counts = iter(_count_candidates(packed, bounds, cands, budget_bytes, stats))
         stats['rounds'] += 1
         for c, vs, end in plan:
             st = state[c]
@@ -607,15 +590,37 @@ def pnvlad_search(clouds: Sequence, target: int = 4096, device='cuda', budget_by
     trace holding the probes the reference would have made (not the speculative ones past a stop).  With `return_stats` also
     {'rounds', 'candidates' (evaluated per cloud, speculation included), 'occupancy_calls', 'sort_fallbacks'}."""
     target = _check_target(target)
-    clouds = _as_tensors(clouds)
-    _check_enough_points([int(t.shape[0]) for t in clouds], target)
-    device = _device(device)
-    if not clouds:
-        return ([], {'rounds': 0, 'candidates': []}) if return_stats else []
-    with torch.cuda.device(device):
-        pts, off, off_host = _upload(clouds, device)
-        found, stats = _pnvlad_search_device(pts, off, off_host, target, budget_bytes)
+    with _intake(clouds, device, lambda sizes: _check_enough_points(sizes, target)) as packed:
+        if packed is None:
+            return ([], {'rounds': 0, 'candidates': []}) if return_stats else []
+        found, stats = _pnvlad_search_device(packed, target, budget_bytes)
     return (found, stats) if return_stats else found
+
+
+def _pnvlad_packed(packed, target: int, seed, budget_bytes: int = OCCUPANCY_BUDGET_BYTES):
+    """the search, the cell means at the size it ends on and the raw rows that fill a cloud up to `target` -> (the batch of
+    B x `target` rows as a `ragged.Packed`, the per-cloud dicts of the search)"""
+    pts, off_host, device = packed.pts, packed.off_host, packed.pts.device
+    found, _ = _pnvlad_search_device(packed, target, budget_bytes)
+    means, index = [], []
+    for c, f in enumerate(found):
+        s, e = int(off_host[c]), int(off_host[c + 1])
+        cloud = pts[s:e].clone() if (s * 12) % 16 else pts[s:e]                   # the kernels load 16 bytes at a time
+        one = torch.tensor([0, e - s], dtype=torch.int64, device=device)
+        out, _, _, _, _ = _downsample_launch(cloud, one, 1, f['voxel_size'], False, False)
+        means.append(out[:f['count']])                                            # the count is the number of output rows
+        index.append(s + _pad_indices(seed, e - s, target - f['count']))
+    lens = [len(i) for i in index]
+    rows = ops.voxel_gather_rows(pts, torch.from_numpy(np.concatenate(index)).to(device)) if sum(lens) else None
+    parts, at = [], 0
+    for m, k in zip(means, lens):
+        parts += [m, rows[at:at + k]] if k else [m]
+        at += k
+    return _fixed(torch.cat(parts), packed.batch, target), found
+
+
+def _fixed(rows, batch: int, target: int):
+    return ragged.Packed(rows, np.arange(batch + 1, dtype=np.int64) * target)
 
 
 def pnvlad_downsample(clouds: Sequence, target: int = 4096, seed=42, device='cuda', return_voxel_sizes: bool = False,
@@ -626,44 +631,61 @@ def pnvlad_downsample(clouds: Sequence, target: int = 4096, seed=42, device='cud
     list of float64 sizes.  `ValueError`, naming the cloud: fewer than `target` points (raised before any launch), or no
     voxel size down to zero / to the 65 535-cell span limit that gives `target` occupied cells."""
     target = _check_target(target)
-    clouds = _as_tensors(clouds)
-    _check_enough_points([int(t.shape[0]) for t in clouds], target)
-    device = _device(device)
-    if not clouds:
-        return ([], []) if return_voxel_sizes else []
-    with torch.cuda.device(device):
-        pts, off, off_host = _upload(clouds, device)
-        found, _ = _pnvlad_search_device(pts, off, off_host, target, budget_bytes)
-        means, index = [], []
-        for c, f in enumerate(found):
-            s, e = int(off_host[c]), int(off_host[c + 1])
-            cloud = pts[s:e].clone() if (s * 12) % 16 else pts[s:e]
-            one = torch.tensor([0, e - s], dtype=torch.int64, device=device)
-            out, _, _, _, _ = _downsample_launch(cloud, one, 1, f['voxel_size'], False, False)
-            means.append(out[:f['count']])                                        # the count is the number of output rows
-            index.append(s + _pad_indices(seed, e - s, target - f['count']))
-        lens = [len(i) for i in index]
-        rows = ops.voxel_gather_rows(pts, torch.from_numpy(np.concatenate(index)).to(device)) if sum(lens) else None
-        outs, at = [], 0
-        for m, k in zip(means, lens):
-            outs.append(torch.cat([m, rows[at:at + k]]) if k else m.clone())
-            at += k
-    return (outs, [f['voxel_size'] for f in found]) if return_voxel_sizes else outs
+    with _intake(clouds, device, lambda sizes: _check_enough_points(sizes, target)) as packed:
+        if packed is None:
+            return ragged.empty_results(return_voxel_sizes)
+        down, found = _pnvlad_packed(packed, target, seed, budget_bytes)
+        return ragged.results(down.split(), [f['voxel_size'] for f in found] if return_voxel_sizes else None)
+
+
+def _random_packed(packed, target: int, seed):
+    """`target` rows of every cloud at the indices drawn on the host, one gather launch -> a `ragged.Packed`"""
+    index = np.concatenate([int(s) + _pad_indices(seed, int(n), target) for s, n in zip(packed.off_host, packed.sizes())])
+    rows = ops.voxel_gather_rows(packed.pts, torch.from_numpy(index).to(packed.pts.device))
+    return _fixed(rows, packed.batch, target)
 
 
 def random_downsample(clouds: Sequence, target: int, seed=42, device='cuda') -> List[torch.Tensor]:
     """`random_down_sample` for a batch -> list of (target, 3) float32 device tensors: rows drawn with replacement by a
     fresh `default_rng(seed)` per cloud (indices on the host, one gather launch on the device)."""
     target = _check_target(target)
-    clouds = _as_tensors(clouds)
-    device = _device(device)
-    if not clouds:
-        return []
-    with torch.cuda.device(device):
-        pts, _, off_host = _upload(clouds, device)
-        index = np.concatenate([int(off_host[c]) + _pad_indices(seed, int(t.shape[0]), target) for c, t in enumerate(clouds)])
-        rows = ops.voxel_gather_rows(pts, torch.from_numpy(index).to(device))
-    return list(rows.reshape(len(clouds), target, 3).unbind(0))
+    with _intake(clouds, device) as packed:
+        return [] if packed is None else _random_packed(packed, target, seed).split()
+
+
+def _normalise_padded_packed(down, raw, target: int, seed) -> List[torch.Tensor]:
+    """the normalisation of the packed batch `down` and its padding from the packed batch `raw` -> the per-cloud list"""
+    batch, device = down.batch, down.pts.device
+    out, kept = _normalise_packed(down)
+    for i, k in enumerate(kept):
+        if k > target:
+            raise _too_many_error(i, k, target)
+    rngs = [np.random.default_rng(seed) for _ in range(batch)]
+    n_raw = raw.sizes()
+    added, parts = [0] * batch, [[c] for c in down.split(out, kept)]
+    for _ in range(PAD_MAX_ITERATIONS):
+        want = [target - k - a for k, a in zip(kept, added)]                      # extra - added of the reference
+        if not any(want):
+            break
+        index = [rngs[i].choice(n_raw[i], size=w).astype(np.int64) if w else np.zeros(0, np.int64)
+                 for i, w in enumerate(want)]
+        row_off = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
+        rows, keep = ops.submap_normalise_rows(down.pts, down.off, raw.pts, raw.off,
+                                               torch.from_numpy(np.concatenate(index)).to(device),
+                                               torch.from_numpy(row_off).to(device))
+        mask = keep.cpu().numpy() != 0                                            # the one host read of the iteration
+        picked = ops.voxel_gather_rows(rows, torch.from_numpy(np.flatnonzero(mask)).to(device))
+        at = 0
+        for i in range(batch):
+            n = int(mask[row_off[i]:row_off[i + 1]].sum())
+            if n:
+                parts[i].append(picked[at:at + n])
+            at += n
+            added[i] += n
+    else:
+        if any(k + a < target for k, a in zip(kept, added)):
+            raise _padding_error([k + a < target for k, a in zip(kept, added)].index(True), target)
+    return [torch.cat(p) if len(p) > 1 else p[0].clone() for p in parts]
 
 
 def normalise_submaps_padded(downsampled: Sequence, raw: Sequence, target: int, seed=42, device='cuda') -> List[torch.Tensor]:
@@ -673,79 +695,23 @@ def normalise_submaps_padded(downsampled: Sequence, raw: Sequence, target: int, 
     and scale, and kept when every |q'| <= 1.  One host read for the normalisation and one per padding iteration.
     `ValueError` as `normalise_submaps`, and when a cloud keeps more than `target` rows or the padding does not end."""
     target = _check_target(target)
-    down, raws = _as_tensors(downsampled), _as_tensors(raw)
+    down, raws = ragged.as_tensors(downsampled), ragged.as_tensors(raw)
     if len(down) != len(raws):
         raise ValueError('%d downsampled clouds but %d raw clouds' % (len(down), len(raws)))
-    device = _device(device)
-    if not down:
-        return []
-    batch = len(down)
-    with torch.cuda.device(device):
-        dpts, doff, doff_host = _upload(down, device)
-        rpts, roff, roff_host = _upload(raws, device)
-        out, counts, flags = ops.submap_normalise(dpts, doff)
-        host = torch.cat([flags, counts]).cpu().tolist()
-        kept = host[batch:]
-        _raise_normalise(host[:batch], kept)
-        for i, k in enumerate(kept):
-            if k > target:
-                raise _too_many_error(i, k, target)
-        rngs = [np.random.default_rng(seed) for _ in range(batch)]
-        n_raw = np.diff(roff_host)
-        added, parts = [0] * batch, [[out[s:s + k]] for s, k in zip(doff_host.tolist(), kept)]
-        for _ in range(PAD_MAX_ITERATIONS):
-            want = [target - k - a for k, a in zip(kept, added)]                  # extra - added of the reference
-            if not any(want):
-                break
-            index = [rngs[i].choice(int(n_raw[i]), size=w).astype(np.int64) if w else np.zeros(0, np.int64)
-                     for i, w in enumerate(want)]
-            row_off = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
-            rows, keep = ops.submap_normalise_rows(dpts, doff, rpts, roff, torch.from_numpy(np.concatenate(index)).to(device),
-                                                   torch.from_numpy(row_off).to(device))
-            mask = keep.cpu().numpy() != 0                                        # the one host read of the iteration
-            picked = ops.voxel_gather_rows(rows, torch.from_numpy(np.flatnonzero(mask)).to(device))
-            at = 0
-            for i in range(batch):
-                n = int(mask[row_off[i]:row_off[i + 1]].sum())
-                if n:
-                    parts[i].append(picked[at:at + n])
-                at += n
-                added[i] += n
-        else:
-            if any(k + a < target for k, a in zip(kept, added)):
-                raise _padding_error([k + a < target for k, a in zip(kept, added)].index(True), target)
-        return [torch.cat(p) if len(p) > 1 else p[0].clone() for p in parts]
+    with _intake(down, device) as dpacked, _intake(raws, device) as rpacked:
+        return [] if dpacked is None else _normalise_padded_packed(dpacked, rpacked, target, seed)
 
 
 def prepare_submaps_fixed(clouds: Sequence, target: int = 4096, downsample: str = 'pnvlad', normalise: bool = True, seed=42,
                           device='cuda', *, remove_ground: bool = False, ground_params=None, radius_max=None,
                           remove_outliers: bool = False, outlier_params=None) -> List[torch.Tensor]:
-    """Raw submaps -> fixed-size clouds of `target` points (the Oxford / CS-Campus3D format): `pnvlad_downsample` or
-    `random_downsample`, then (when `normalise`) `normalise_submaps_padded` against the raw clouds.  The batch is uploaded
-    once and stays on the device between the steps; the result equals the chained calls bit for bit.  With `remove_ground`
-    the batch first goes through `ground.remove_ground(**ground_params)`; the filtered cloud is then also the raw cloud the
-    padding draws from, as in the reference, which reassigns its points.  `ValueError`, naming the cloud, when the filter
-    leaves a cloud fewer than `target` points.  With `radius_max` and / or `remove_outliers` the raw batch is cleaned before
-    all that (`outliers.clean_batch`), and the padding draws from the cleaned cloud."""
+    """`submap_chain` with fixed-size clouds of `target` points (the Oxford / CS-Campus3D format): `pnvlad_downsample` or
+    `random_downsample`, then (when `normalise`) `normalise_submaps_padded` against the raw clouds; the result equals the
+    chained calls bit for bit.  With `remove_ground`, `radius_max` and / or `remove_outliers` the batch is filtered first as
+    in `prepare_submaps`; the filtered cloud is then also the raw cloud the padding draws from, as in the reference, which
+    reassigns its points.  `ValueError`, naming the cloud, when a filter leaves a cloud fewer than `target` points."""
     if downsample not in ('pnvlad', 'random'):
         raise ValueError("downsample must be 'pnvlad' or 'random', got %r" % (downsample,))
-    target = _check_target(target)
-    if radius_max is not None or remove_outliers:
-        from . import outliers
-        clouds = outliers.clean_batch(clouds, device, radius_max, remove_outliers, outlier_params,
-                                      at_least=target if downsample == 'pnvlad' else 1)
-    if remove_ground:
-        from . import ground
-        clouds = ground.filter_batch(clouds, device, ground_params, at_least=target)
-    clouds = _as_tensors(clouds)
-    if downsample == 'pnvlad':
-        _check_enough_points([int(t.shape[0]) for t in clouds], target)
-    device = _device(device)
-    if not clouds:
-        return []
-    with torch.cuda.device(device):
-        resident = [t.to(device, non_blocking=True) for t in clouds] if any(t.is_cuda for t in clouds) else \
-            list(torch.cat(clouds).to(device, non_blocking=True).split([int(t.shape[0]) for t in clouds]))
-        down = pnvlad_downsample(resident, target, seed=seed, device=device) if downsample == 'pnvlad' else \
-            random_downsample(resident, target, seed=seed, device=device)
-        return normalise_submaps_padded(down, resident, target, seed=seed, device=device) if normalise else down
+    return submap_chain(clouds, device, radius_max=radius_max, remove_outliers=remove_outliers, outlier_params=outlier_params,
+                        remove_ground=remove_ground, ground_params=ground_params, target=_check_target(target),
+                        downsample=downsample, normalise=normalise, seed=seed)

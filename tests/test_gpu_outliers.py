@@ -217,6 +217,61 @@ def test_encode_clouds_cleans_the_raw_submaps_first():
     assert torch.equal(got, want)
 
 
+PACKED_SIZES = (257, 1031, 643)             # odd: packed, the clouds start at rows that are no multiple of 4 (16 bytes)
+PACKED_SHIFTS = ((6.0, 4.0, 0.0), (14.0, -30.0, 1.0), (-30.0, -28.0, 2.0))
+
+
+@functools.lru_cache(maxsize=None)
+def packed_submaps():
+    """three 20 m forests cut to `PACKED_SIZES` rows, three in ten of them floor so that more than 128 rows outlast the
+    cloth, and moved so that the 30 m trim cuts a part of each"""
+    from tests import ground_cases as gc
+    raw = []
+    for seed, (n, shift) in enumerate(zip(PACKED_SIZES, PACKED_SHIFTS)):
+        pts, is_ground, _ = gc.forest(seed, size=20.0, trunks_per_m2=10 / 400.0, blobs_per_m2=2 / 400.0)
+        floor = int(n * 0.3)
+        rows = np.sort(np.concatenate([np.flatnonzero(is_ground)[:floor], np.flatnonzero(~is_ground)[:n - floor]]))
+        raw.append(pts[rows] + np.array(shift, np.float32))
+    return raw
+
+
+def test_packed_chain_equals_the_calls_chained_through_lists():
+    """The chain keeps the batch packed between its steps, so a cloud starts wherever the compaction before it ends: after
+    the trim the clouds start at rows 0, 250, 792, after the outlier filter at 0, 247, 779, after the cloth at 0, 208, 645,
+    and a start at a row that is no multiple of 4 is not 16-byte aligned.  A chain through lists starts every cloud in a
+    tensor of its own."""
+    raw = packed_submaps()
+    trimmed = outliers.trim_radius(raw, 30)
+    assert all(128 < t.shape[0] < r.shape[0] for t, r in zip(trimmed, raw))   # the chain runs, no error path; some rows go
+    filtered = ground.remove_ground(outliers.remove_outliers(trimmed))
+    kw = dict(radius_max=30, remove_outliers=True, remove_ground=True)
+
+    def both(chain, **more):
+        """the batch through `chain`, after checking that every cloud alone gives the rows it gives in the batch"""
+        got = chain(raw, **more, **kw)
+        assert len(got) == 3 and all(torch.equal(chain([cloud], **more, **kw)[0], g) for cloud, g in zip(raw, got))
+        return got
+
+    got = both(voxel.prepare_submaps, voxel_size=0.8)
+    want = voxel.normalise_submaps(voxel.voxel_downsample(filtered, 0.8))
+    assert all(torch.equal(x, y) for x, y in zip(got, want))
+    got = both(voxel.prepare_submaps_fixed, target=128, downsample='pnvlad')
+    want = voxel.normalise_submaps_padded(voxel.pnvlad_downsample(filtered, 128), filtered, 128)
+    assert all(tuple(x.shape) == (128, 3) and torch.equal(x, y) for x, y in zip(got, want))
+    got = both(voxel.prepare_submaps_fixed, target=128, downsample='random')
+    want = voxel.normalise_submaps_padded(voxel.random_downsample(filtered, 128), filtered, 128)
+    assert all(tuple(x.shape) == (128, 3) and torch.equal(x, y) for x, y in zip(got, want))
+
+    params, depth = load_config('wild-places')                               # the branch only `encode_clouds` has: no downsample
+    model = model_factory(params)
+    syn.fill_synthetic_weights(model, 'stress')
+    model = model.cuda()
+    enc = dict(coordinates=params.coordinates, normalize=True, octree_depth=depth)
+    got = retrieval.encode_clouds(model, raw, 3, remove_ground=True, normalise_submaps=True, **enc)
+    want = retrieval.encode_clouds(model, voxel.normalise_submaps(ground.remove_ground(raw)), 3, **enc)
+    assert tuple(got.shape) == (3, 256) and bool(torch.isfinite(got).all()) and torch.equal(got, want)
+
+
 def test_pipeline_names_the_cloud_left_empty():
     raw = [raw_submaps()[0], raw_submaps()[1] + np.array([-100.0, 0.0, 0.0], np.float32)]
     with pytest.raises(ValueError, match='cloud 1 has no point left after the radius trim'):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hotformerloc_amd import ops, voxel                                         # noqa: E402
+from hotformerloc_amd import ops, ragged, voxel                                 # noqa: E402
 from hotformerloc_amd import synthetic as syn                                   # noqa: E402
 
 
@@ -62,14 +62,14 @@ def main():
     res['device_search_only'] = timed(lambda: voxel.pnvlad_search(raw, args.target), args.repeats, args.warmup)
 
     # one occupancy call: the first phase-one round of every cloud, on device-resident data
-    ts = voxel._as_tensors(raw)
-    pts, off, off_host = voxel._upload(ts, torch.device('cuda', torch.cuda.current_device()))
-    bounds, lo_hi = voxel._bounds_host(pts, off)
+    packed = ragged.upload(ragged.as_tensors(raw), torch.device('cuda', torch.cuda.current_device()))
+    pts, off = packed.pts, packed.off
+    bounds, lo_hi = ragged.bounds_host(packed)
     table, words, pairs = [], 0, 0
     for c in range(args.clouds):
         v = voxel.PNVLAD_START
         for _ in range(voxel.PNVLAD_K_ONE):
-            nx, ny, nz = voxel._grid_dims(lo_hi[c], v)
+            nx, ny, nz = voxel.grid_dims(lo_hi[c], v)
             table.append((c, nx, ny, nz, v, words))
             words += (nx * ny * nz + 31) // 32
             pairs += args.points
@@ -97,7 +97,7 @@ def main():
     assert [f['trace'] for f in host_found] == [f['trace'] for f in found[:k]]
     t0 = time.perf_counter()
     for i in range(k):
-        voxel._cell_means(raw[i], host_found[i]['voxel_size'], i)
+        voxel.voxel_downsample_host([raw[i]], host_found[i]['voxel_size'])
     means_s = time.perf_counter() - t0
     res['host'] = {'clouds': k, 'ms_per_cloud': round((search_s + means_s) * 1e3 / k, 1),
                    'search_ms_per_cloud': round(search_s * 1e3 / k, 1)}

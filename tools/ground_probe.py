@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hotformerloc_amd import ground, ops, voxel                                 # noqa: E402
+from hotformerloc_amd import ground, ops, ragged                                # noqa: E402
 from hotformerloc_amd import synthetic as syn                                   # noqa: E402
 
 
@@ -65,9 +65,10 @@ def main():
 
     # the launches alone, on device-resident data
     prm = ground.ClothParams()
-    ts = voxel._as_tensors(raw)
-    pts, off, off_host = voxel._upload(ts, torch.device('cuda', torch.cuda.current_device()))
-    table = ground._cloth_device(pts, off, off_host, prm)[0]
+    ts = ragged.as_tensors(raw)
+    packed = ragged.upload(ts, torch.device('cuda', torch.cuda.current_device()))
+    pts, off = packed.pts, packed.off
+    table = ground.cloth_device(packed, prm)[0]
     state = {}
 
     def stage_bounds():
@@ -104,7 +105,7 @@ def main():
     res['stages_total_ms'] = round(sum(s['median_ms'] for s in stages.values()), 4)
     steps = max(res['steps_run'])
     res['simulate_us_per_step'] = round(stages['cloth_simulate']['median_ms'] * 1e3 / max(steps, 1), 2)
-    res['upload'] = timed(lambda: voxel._upload(ts, pts.device), args.repeats, 1)
+    res['upload'] = timed(lambda: ragged.upload(ts, pts.device).off, args.repeats, 1)
     print(json.dumps(res))
 
 

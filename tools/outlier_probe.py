@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hotformerloc_amd import ops, outliers, voxel                               # noqa: E402
+from hotformerloc_amd import ops, outliers, ragged                              # noqa: E402
 from hotformerloc_amd import synthetic as syn                                   # noqa: E402
 
 
@@ -80,8 +80,9 @@ def probe(args, points):
                                                      max(args.repeats // 3, 1), 1)
 
     # the launches alone, on device-resident data
-    pts, off, off_host = voxel._upload(resident, device)
-    table, sorted_pts, sorted_keys, perm = outliers._sorted_batch(pts, off, off_host, 20, None)
+    packed = ragged.upload(resident, device)
+    pts, off, off_host = packed.pts, packed.off, packed.off_host
+    table, sorted_pts, sorted_keys, perm = outliers.sorted_batch(packed, 20)
     res['cell_m'] = [round(float(c), 4) for c in table.host['cell']]
     res['cells'] = int(table.cells)
     ws = ops.KnnWorkspace(int(pts.shape[0]), table.cells, device)

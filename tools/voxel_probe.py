@@ -18,7 +18,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hotformerloc_amd import ops, voxel                                         # noqa: E402
+from hotformerloc_amd import ops, ragged, voxel                                 # noqa: E402
 from hotformerloc_amd import synthetic as syn                                   # noqa: E402
 
 
@@ -60,8 +60,9 @@ def main():
     res['speedup_vs_host'] = round(res['host_call_and_upload']['median_ms'] / res['device_call']['median_ms'], 1)
 
     # the stages alone, on device-resident data
-    ts = voxel._as_tensors(raw)
-    pts, off, _ = voxel._upload(ts, torch.device('cuda', torch.cuda.current_device()))
+    ts = ragged.as_tensors(raw)
+    packed = ragged.upload(ts, torch.device('cuda', torch.cuda.current_device()))
+    pts, off = packed.pts, packed.off
     batch = len(raw)
     state = {}
 
@@ -96,7 +97,7 @@ def main():
     res['stages_total_ms'] = round(total, 4)
     res['sort_share'] = round(stages['sort']['median_ms'] / total, 3)
     res['kernels_ms'] = round(total - stages['sort']['median_ms'], 4)
-    upload = timed(lambda: voxel._upload(ts, pts.device), args.repeats, 1)
+    upload = timed(lambda: ragged.upload(ts, pts.device).off, args.repeats, 1)
     res['upload'] = upload
     print(json.dumps(res))
 
