@@ -298,6 +298,8 @@ SIGNATURES = {
     'hfl_flat_l2_topk_workspace': (c_int64, [c_int64, c_int64, c_int64, c_int]),
     'hfl_flat_l2_topk': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p,
                                  c_int64, c_void_p]),
+    'hfl_flat_l2_topk_prefix': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                        c_int, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -21,6 +21,13 @@
 // same key.  One segment writes the result directly.  Non-finite descriptors are undefined behaviour of the ORDER only (no
 // out-of-range access): indices stay in range because list slots start as (+inf, INT_MAX) and are never written out past
 // min(k, N).
+//
+// Prefix search (hfl_flat_l2_topk_prefix, the PREFIX instantiations).  Query q sees the database rows [0, limits[q]) only:
+// its limit takes the place of n_rows in the `pass` predicate and nowhere else, so a pair's distance is the value above and
+// query q's list is what the unrestricted search returns for it against database[:limits[q]].  The tile loop holds
+// __syncthreads(), so its bound is the workgroup's: the largest limit of the tile's 64 queries, read through LDS; with
+// time-ordered queries the tiles above the diagonal are never staged.  A segment beyond a query's limit leaves that
+// query's list at (+inf, INT_MAX), which the merge skips; the slots that stay unused leave as (+inf, -1).
 #include "hfl_common.h"
 
 #include <limits.h>
@@ -81,11 +88,13 @@ __device__ __forceinline__ void stage_chunk(float* __restrict__ s, const float* 
 }
 
 // grid (query tiles, segments), 256 threads.  out_d / out_i: (Q, kc) when n_seg == 1, else the workspace lists
-// (Q, n_seg, LIST).
+// (Q, n_seg, LIST).  PREFIX: limits (Q), query q takes rows below limits[q] clamped to [0, n_rows]; unused result slots get
+// index -1.
+template <bool PREFIX>
 __global__ void __launch_bounds__(256)
 flat_l2_topk_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const float* __restrict__ queries,
                     const float* __restrict__ database, const float* __restrict__ q_norm, const float* __restrict__ d_norm,
-                    int q_rows, int n_rows, int d, int kc, int tiles_per_seg, int n_seg) {
+                    int q_rows, int n_rows, int d, int kc, int tiles_per_seg, int n_seg, const int* __restrict__ limits) {
   __shared__ __attribute__((aligned(16))) float s_q[QT * LDS_STRIDE];
   __shared__ __attribute__((aligned(16))) float s_d[NT * LDS_STRIDE];
   __shared__ __attribute__((aligned(16))) float s_dn[NT];
@@ -98,7 +107,7 @@ flat_l2_topk_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const fl
   const int seg = blockIdx.y;
   const int n_tiles = (n_rows + NT - 1) / NT;
   const int tile_lo = seg * tiles_per_seg;
-  const int tile_hi = min(n_tiles, tile_lo + tiles_per_seg);
+  int tile_hi = min(n_tiles, tile_lo + tiles_per_seg);
 
   // the wavefront's 16 lists, and each lane's copy of the last key of its query's list
   float* ld = s_ld + wave * 16 * LIST;
@@ -111,6 +120,21 @@ flat_l2_topk_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const fl
   int thr_i = INT_MAX;
   const int64_t my_q = q0 + wave * 16 + c;
   const float qn = my_q < q_rows ? q_norm[my_q] : 0.f;
+
+  // the rows this lane's query may take; the tile loop ends at the largest limit of the workgroup's queries
+  int my_rows = n_rows;
+  if constexpr (PREFIX) {
+    __shared__ int s_lim[QT];
+    if (threadIdx.x < QT) {
+      const int64_t q = q0 + threadIdx.x;
+      s_lim[threadIdx.x] = q < q_rows ? min(max(limits[q], 0), n_rows) : 0;
+    }
+    __syncthreads();
+    int max_lim = 0;
+    for (int e = 0; e < QT; ++e) max_lim = max(max_lim, s_lim[e]);
+    my_rows = s_lim[wave * 16 + c];
+    tile_hi = min(tile_hi, (max_lim + NT - 1) / NT);
+  }
 
   for (int tile = tile_lo; tile < tile_hi; ++tile) {
     const int64_t row0 = (int64_t)tile * NT;
@@ -152,7 +176,7 @@ flat_l2_topk_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const fl
         const int64_t row = row0 + t * 16 + g * 4 + r;
         const int idx = (int)row;
         const float dist = fmaf(-2.f, acc[t][r], qn + dn[r]);
-        const bool pass = row < n_rows && key_less(dist, idx, thr_d, thr_i);
+        const bool pass = row < my_rows && key_less(dist, idx, thr_d, thr_i);
         unsigned long long mask = __ballot(pass);
         if (mask == 0) continue;
         while (mask != 0) {
@@ -187,13 +211,15 @@ flat_l2_topk_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const fl
     if (q < q_rows && slot < width) {
       const int64_t o = n_seg == 1 ? q * kc + slot : (q * n_seg + seg) * LIST + slot;
       out_d[o] = ld[e];
-      out_i[o] = li[e];
+      out_i[o] = PREFIX && n_seg == 1 && li[e] == INT_MAX ? -1 : li[e];
     }
   }
 }
 
 // One wavefront per query: lanes 0..31 hold the merged list; every segment's sorted list is fed in order and left as soon as
-// one of its entries no longer fits (the rest are larger still).
+// one of its entries no longer fits (the rest are larger still).  PREFIX: a query may have found fewer than kc rows, or none
+// in any segment; the slots left at (+inf, INT_MAX) get index -1.
+template <bool PREFIX>
 __global__ void __launch_bounds__(256)
 flat_l2_merge_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const float* __restrict__ part_d,
                      const int* __restrict__ part_i, int q_rows, int n_seg, int kc) {
@@ -222,7 +248,7 @@ flat_l2_merge_kernel(float* __restrict__ out_d, int* __restrict__ out_i, const f
   }
   if (lane < kc) {
     out_d[q * kc + lane] = md;
-    out_i[q * kc + lane] = mi;
+    out_i[q * kc + lane] = PREFIX && mi == INT_MAX ? -1 : mi;
   }
 }
 
@@ -267,15 +293,20 @@ extern "C" int64_t hfl_flat_l2_topk_workspace(int64_t n_queries, int64_t n_datab
   return bytes;
 }
 
-extern "C" int hfl_flat_l2_topk(float* dist, int32_t* idx, const float* queries, const float* database,
-                                 const float* database_sq_norms, int64_t n_queries, int64_t n_database, int dim, int k,
-                                 void* workspace, int64_t workspace_bytes, hfl_stream_t stream) {
+namespace {
+
+// Both entry points: the same plan, workspace layout and launches.  PREFIX: kc = k whatever N, and `limits` per query.
+template <bool PREFIX>
+int launch_topk(float* dist, int32_t* idx, const float* queries, const float* database, const float* database_sq_norms,
+                const int32_t* limits, int64_t n_queries, int64_t n_database, int dim, int k, void* workspace,
+                int64_t workspace_bytes, hfl_stream_t stream) {
   if (!shape_ok(n_queries, n_database, dim, k)) return HFL_EINVAL;
   if (n_queries == 0) return HFL_OK;
+  if (PREFIX && limits == nullptr) return HFL_EINVAL;
   if (workspace == nullptr || workspace_bytes < hfl_flat_l2_topk_workspace(n_queries, n_database, dim, k)) return HFL_EINVAL;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const Plan p = make_plan(n_queries, n_database);
-  const int kc = (int)(k < n_database ? k : n_database);
+  const int kc = PREFIX ? k : (int)(k < n_database ? k : n_database);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   float* q_norm = reinterpret_cast<float*>(ws);
   float* d_norm_ws = reinterpret_cast<float*>(ws + align16(n_queries * 4));
@@ -291,12 +322,30 @@ extern "C" int hfl_flat_l2_topk(float* dist, int32_t* idx, const float* queries,
   }
   const dim3 grid((unsigned)p.q_tiles, (unsigned)p.n_seg);
   if (p.n_seg == 1) {
-    flat_l2_topk_kernel<<<grid, 256, 0, st>>>(dist, idx, queries, database, q_norm, d_norm, (int)n_queries, (int)n_database, dim,
-                                              kc, p.tiles_per_seg, 1);
+    flat_l2_topk_kernel<PREFIX><<<grid, 256, 0, st>>>(dist, idx, queries, database, q_norm, d_norm, (int)n_queries,
+                                                      (int)n_database, dim, kc, p.tiles_per_seg, 1, limits);
   } else {
-    flat_l2_topk_kernel<<<grid, 256, 0, st>>>(part_d, part_i, queries, database, q_norm, d_norm, (int)n_queries, (int)n_database,
-                                              dim, kc, p.tiles_per_seg, p.n_seg);
-    flat_l2_merge_kernel<<<(unsigned)hfl_cdiv(n_queries, 4), 256, 0, st>>>(dist, idx, part_d, part_i, (int)n_queries, p.n_seg, kc);
+    flat_l2_topk_kernel<PREFIX><<<grid, 256, 0, st>>>(part_d, part_i, queries, database, q_norm, d_norm, (int)n_queries,
+                                                      (int)n_database, dim, kc, p.tiles_per_seg, p.n_seg, limits);
+    flat_l2_merge_kernel<PREFIX><<<(unsigned)hfl_cdiv(n_queries, 4), 256, 0, st>>>(dist, idx, part_d, part_i, (int)n_queries,
+                                                                                   p.n_seg, kc);
   }
   HFL_RETURN_LAST_ERROR();
+}
+
+}  // namespace
+
+extern "C" int hfl_flat_l2_topk(float* dist, int32_t* idx, const float* queries, const float* database,
+                                 const float* database_sq_norms, int64_t n_queries, int64_t n_database, int dim, int k,
+                                 void* workspace, int64_t workspace_bytes, hfl_stream_t stream) {
+  return launch_topk<false>(dist, idx, queries, database, database_sq_norms, nullptr, n_queries, n_database, dim, k, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" int hfl_flat_l2_topk_prefix(float* dist, int32_t* idx, const float* queries, const float* database,
+                                        const float* database_sq_norms, const int32_t* limits, int64_t n_queries,
+                                        int64_t n_database, int dim, int k, void* workspace, int64_t workspace_bytes,
+                                        hfl_stream_t stream) {
+  return launch_topk<true>(dist, idx, queries, database, database_sq_norms, limits, n_queries, n_database, dim, k, workspace,
+                           workspace_bytes, stream);
 }

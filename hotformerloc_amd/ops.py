@@ -2195,39 +2195,85 @@ def row_sq_norms(x: torch.Tensor):
     return out
 
 
-def flat_l2_topk(queries: torch.Tensor, database: torch.Tensor, k: int, database_sq_norms: torch.Tensor = None):
-    """The min(k, N) nearest database rows of every query by squared L2 distance, nearest first, equal distances by lower
-    index, without a (Q, N) matrix (`hfl_flat_l2_topk`).  queries (Q, D), database (N, D) fp32, D a multiple of 4 in 4..1024,
-    1 <= k <= 32; database_sq_norms: `row_sq_norms(database)` to reuse it.  Returns (dist (Q, kc) fp32, idx (Q, kc) int32)."""
+def _flat_l2_operands(name: str, queries, database, k, database_sq_norms):
+    """The argument rules both searches share -> (queries, database, database_sq_norms, k) ready for the library."""
     _dev(queries, database, database_sq_norms)
-    _flat_l2_check('flat_l2_topk queries', queries)
-    _flat_l2_check('flat_l2_topk database', database)
+    _flat_l2_check(name + ' queries', queries)
+    _flat_l2_check(name + ' database', database)
     if queries.shape[1] != database.shape[1]:
-        raise ValueError('flat_l2_topk: queries have D = %d, the database D = %d' % (queries.shape[1], database.shape[1]))
+        raise ValueError('%s: queries have D = %d, the database D = %d' % (name, queries.shape[1], database.shape[1]))
     k = int(k)
     if k < 1 or k > 32:
-        raise ValueError('flat_l2_topk: 1 <= k <= 32 expected, got %d' % k)
-    q_rows, n_rows, d = queries.shape[0], database.shape[0], queries.shape[1]
+        raise ValueError('%s: 1 <= k <= 32 expected, got %d' % (name, k))
+    n_rows = database.shape[0]
     if n_rows < 1:
-        raise ValueError('flat_l2_topk: the database is empty')
+        raise ValueError('%s: the database is empty' % name)
     queries, database = _f32c(queries), _f32c(database)
     if database_sq_norms is not None:
         database_sq_norms = _f32c(database_sq_norms)
         if tuple(database_sq_norms.shape) != (n_rows,):
-            raise ValueError('flat_l2_topk: %d database norms expected, got %s' % (n_rows, tuple(database_sq_norms.shape)))
+            raise ValueError('%s: %d database norms expected, got %s' % (name, n_rows, tuple(database_sq_norms.shape)))
+    return queries, database, database_sq_norms, k
+
+
+def _flat_l2_workspace(name: str, lib, q_rows, n_rows, d, k, device):
+    ws_bytes = lib.hfl_flat_l2_topk_workspace(q_rows, n_rows, d, k)
+    if ws_bytes < 0:
+        raise ValueError('%s: unsupported shape Q = %d, N = %d, D = %d, k = %d' % (name, q_rows, n_rows, d, k))
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device), ws_bytes
+
+
+def flat_l2_topk(queries: torch.Tensor, database: torch.Tensor, k: int, database_sq_norms: torch.Tensor = None):
+    """The min(k, N) nearest database rows of every query by squared L2 distance, nearest first, equal distances by lower
+    index, without a (Q, N) matrix (`hfl_flat_l2_topk`).  queries (Q, D), database (N, D) fp32, D a multiple of 4 in 4..1024,
+    1 <= k <= 32; database_sq_norms: `row_sq_norms(database)` to reuse it.  Returns (dist (Q, kc) fp32, idx (Q, kc) int32)."""
+    queries, database, database_sq_norms, k = _flat_l2_operands('flat_l2_topk', queries, database, k, database_sq_norms)
+    q_rows, n_rows, d = queries.shape[0], database.shape[0], queries.shape[1]
     kc = min(k, n_rows)
     dist = torch.empty((q_rows, kc), dtype=torch.float32, device=queries.device)
     idx = torch.empty((q_rows, kc), dtype=torch.int32, device=queries.device)
     if q_rows == 0:
         return dist, idx
     lib = _native.load()
-    ws_bytes = lib.hfl_flat_l2_topk_workspace(q_rows, n_rows, d, k)
-    if ws_bytes < 0:
-        raise ValueError('flat_l2_topk: unsupported shape Q = %d, N = %d, D = %d, k = %d' % (q_rows, n_rows, d, k))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=queries.device)
+    ws, ws_bytes = _flat_l2_workspace('flat_l2_topk', lib, q_rows, n_rows, d, k, queries.device)
     check(lib.hfl_flat_l2_topk(dist.data_ptr(), idx.data_ptr(), queries.data_ptr(), database.data_ptr(),
                                None if database_sq_norms is None else database_sq_norms.data_ptr(), q_rows, n_rows, d, k,
                                ws.data_ptr(), ws_bytes, _stream()), 'hfl_flat_l2_topk')
+    return dist, idx
+
+
+def flat_l2_topk_prefix(queries: torch.Tensor, database: torch.Tensor, limits, k: int,
+                        database_sq_norms: torch.Tensor = None):
+    """`flat_l2_topk` with a prefix per query (`hfl_flat_l2_topk_prefix`): query q sees database rows [0, limits[q]) only.
+    `limits`: (Q,) integers, a tensor on either device or a numpy array, every value in [0, N], else ValueError (one host
+    read).  Returns (dist (Q, k) fp32, idx (Q, k) int32) whatever N: row q holds what `flat_l2_topk(queries[q:q + 1],
+    database[:limits[q]], k)` returns, bit for bit, then distance +inf and index -1 in the slots past min(k, limits[q])."""
+    name = 'flat_l2_topk_prefix'
+    queries, database, database_sq_norms, k = _flat_l2_operands(name, queries, database, k, database_sq_norms)
+    q_rows, n_rows, d = queries.shape[0], database.shape[0], queries.shape[1]
+    if not isinstance(limits, torch.Tensor):
+        limits = np.asarray(limits)
+        if limits.dtype.kind not in 'iu':
+            raise ValueError('%s: integer limits expected, got %s' % (name, limits.dtype))
+        limits = torch.from_numpy(np.ascontiguousarray(limits, dtype=np.int64))
+    if limits.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise ValueError('%s: integer limits expected, got %s' % (name, limits.dtype))
+    if tuple(limits.shape) != (q_rows,):
+        raise ValueError('%s: (%d,) limits expected, one per query, got %s' % (name, q_rows, tuple(limits.shape)))
+    limits = limits.to(queries.device)
+    if q_rows > 0 and bool(((limits < 0) | (limits > n_rows)).any().item()):
+        raise ValueError('%s: limits outside [0, %d]' % (name, n_rows))
+    limits = limits.to(torch.int32).contiguous()
+    dist = torch.empty((q_rows, k), dtype=torch.float32, device=queries.device)
+    idx = torch.empty((q_rows, k), dtype=torch.int32, device=queries.device)
+    if q_rows == 0:
+        return dist, idx
+    lib = _native.load()
+    ws, ws_bytes = _flat_l2_workspace(name, lib, q_rows, n_rows, d, k, queries.device)
+    check(lib.hfl_flat_l2_topk_prefix(dist.data_ptr(), idx.data_ptr(), queries.data_ptr(), database.data_ptr(),
+                                      None if database_sq_norms is None else database_sq_norms.data_ptr(),
+                                      limits.data_ptr(), q_rows, n_rows, d, k, ws.data_ptr(), ws_bytes, _stream()),
+          'hfl_flat_l2_topk_prefix')
     return dist, idx
 
 

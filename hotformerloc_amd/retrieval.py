@@ -7,7 +7,12 @@ The whole evaluation loop of `eval/pnv_evaluate.py:76-225` sits beside it: `enco
 `val_batch_size` batches), `FlatL2Index` (the FAISS `GpuIndexFlatL2` role: a streamed HIP search, `hfl_flat_l2_topk`, that
 never stores the (Q, N) distance matrix, followed by an f64 re-ranking of its 32 candidates), `recall_from_indices` (the
 metric of `get_recall` from a CSR ground truth instead of a dense (Q, N) mask) and `evaluate_embeddings` /
-`evaluate_dataset` (the average over the (database set, query set) pairs)."""
+`evaluate_dataset` (the average over the (database set, query set) pairs).
+
+The intra-sequence (loop-closure) protocol of Wild-Places, for which the reference only writes the per-run pickles, is at the
+end: `causal_limits`, `FlatL2Index.search(limits=)` (every scan searched among the scans recorded at least `time_thresh`
+earlier, `hfl_flat_l2_topk_prefix`), `evaluate_intra_sequence` / `evaluate_intra_sequence_host`, `intra_sequence_arrays`
+and `evaluate_intra_dataset`."""
 
 import numpy as np
 import torch
@@ -99,12 +104,16 @@ class FlatL2Index:
     def dim(self):
         return self.database.shape[1]
 
-    def search(self, queries, k: int = 25, refine: bool = True):
+    def search(self, queries, k: int = 25, refine: bool = True, limits=None):
         """queries (Q, D) -> (squared distances, indices), both (Q, min(k, N)), nearest first, equal distances by lower index,
         on the GPU.  refine=False: the kernel's own fp32 distances and int32 indices.  refine=True: the kernel's min(32, N)
         candidates re-ranked by their f64 distance ((q - d)^2).sum() -- f64 distances, int64 indices; this is the exact f64
         ranking whenever the f64 top-k lie inside the fp32 top-32, i.e. when the k-th and the 33rd smallest distance differ
-        by more than 2^-22 (D + 4) (|q|^2 + |d|^2).  Non-finite descriptors: undefined order."""
+        by more than 2^-22 (D + 4) (|q|^2 + |d|^2).  Non-finite descriptors: undefined order.
+
+        limits (Q,) integers in [0, N]: query q sees the database rows [0, limits[q]) only (`ops.flat_l2_topk_prefix`), the
+        33rd smallest distance above being that of its prefix.  Both results are then (Q, k) whatever N: the slots past
+        min(k, limits[q]) hold distance +inf and index -1."""
         k = int(k)
         if k < 1 or k > MAX_K:
             raise ValueError('FlatL2Index.search: 1 <= k <= %d expected, got %d' % (MAX_K, k))
@@ -113,20 +122,33 @@ class FlatL2Index:
             raise ValueError('FlatL2Index.search: queries have D = %d, the index D = %d' % (queries.shape[1], self.dim))
         q = _device_f32(queries, self.database.device)
         n = len(self)
-        kk, kp = min(k, n), min(MAX_K, n)
+        if limits is None:
+            kk, kp = min(k, n), min(MAX_K, n)
+
+            def topk(width):
+                return ops.flat_l2_topk(q, self.database, width, self.sq_norms)
+        else:
+            kk, kp = k, MAX_K
+
+            def topk(width):
+                return ops.flat_l2_topk_prefix(q, self.database, limits, width, self.sq_norms)
         with torch.cuda.device(self.database.device):
             if not refine:
-                return ops.flat_l2_topk(q, self.database, kk, self.sq_norms)
-            _, cand = ops.flat_l2_topk(q, self.database, kp, self.sq_norms)
+                return topk(kk)
+            _, cand = topk(kp)
             cand = torch.sort(cand.long(), dim=1).values          # by index, so that the stable sort below breaks ties by it
+            # a prefix's unused slots (index -1, in front after the sort) are gathered as row 0 and sort last at +inf
+            rows = cand if limits is None else cand.clamp_min(0)
             d2 = torch.empty((q.shape[0], kp), dtype=torch.float64, device=q.device)
             # per query the gathered fp32 rows, their f64 copy and one more f64 temporary: 20 bytes an element
             chunk = max(1, REFINE_SCRATCH_BYTES // (kp * self.dim * 20))
             for s in range(0, q.shape[0], chunk):
-                diff = self.database[cand[s:s + chunk]].double()
+                diff = self.database[rows[s:s + chunk]].double()
                 diff -= q[s:s + chunk].double()[:, None, :]
                 diff *= diff
                 torch.sum(diff, dim=2, out=d2[s:s + chunk])
+            if limits is not None:
+                d2.masked_fill_(cand < 0, float('inf'))
             order = torch.argsort(d2, dim=1, stable=True)[:, :kk]
             return d2.gather(1, order), cand.gather(1, order)
 
@@ -274,3 +296,236 @@ def evaluate_dataset(model, database_clouds, query_clouds, query_sets, batch_siz
         return [None if s is None else encode_clouds(model, s, batch_size, **encode_kwargs) for s in sets]
     return evaluate_embeddings(encode(database_clouds), encode(query_clouds), query_sets, skip_same_run=skip_same_run,
                                only_database=only_database)
+
+
+# ------------------------------------------------------------------------------------------------ intra-sequence evaluation
+# The second Wild-Places protocol (loop closure inside one run): a scan may only be matched against scans of the same run
+# recorded at least `time_thresh` seconds earlier.  The reference writes the per-run pickles for it
+# (`datasets/WildPlaces/generate_test_sets.py:60-62`) and never reads them, so the protocol is defined here:
+# `evaluate_intra_sequence_host` is the definition in numpy float64, `evaluate_intra_sequence` the device route.
+_HOST_CHUNK_BYTES = 64 << 20
+
+
+def causal_limits(timestamps, time_thresh):
+    """(N,) int64: limits[i] = the number of j with t_j <= t_i - time_thresh, for non-decreasing timestamps -- scan i may be
+    matched against scans [0, limits[i]).  float64 throughout (epoch seconds have an fp32 ulp of minutes).  A tensor gives
+    a tensor on its device, anything else a numpy array.  time_thresh > 0, so that limits[i] <= i: no scan sees itself."""
+    if not float(time_thresh) > 0:
+        raise ValueError('causal_limits: time_thresh > 0 expected, got %r' % (time_thresh,))
+    if isinstance(timestamps, torch.Tensor):
+        t = timestamps.detach().to(torch.float64).contiguous()
+        if t.dim() != 1:
+            raise ValueError('causal_limits: (N,) timestamps expected, got %s' % (tuple(t.shape),))
+        if t.numel() > 1 and not bool((t[1:] >= t[:-1]).all().item()):
+            raise ValueError('causal_limits: timestamps must be non-decreasing (sort the run by time first)')
+        return torch.searchsorted(t, t - float(time_thresh), right=True)
+    t = np.ascontiguousarray(np.asarray(timestamps, dtype=np.float64))
+    if t.ndim != 1:
+        raise ValueError('causal_limits: (N,) timestamps expected, got %s' % (t.shape,))
+    if t.shape[0] > 1 and not bool((t[1:] >= t[:-1]).all()):
+        raise ValueError('causal_limits: timestamps must be non-decreasing (sort the run by time first)')
+    return np.searchsorted(t, t - np.float64(time_thresh), side='right').astype(np.int64)
+
+
+def intra_sequence_arrays(run_set):
+    """The reference's per-run dict {i: {'query', 'northing', 'easting', 'pose', 'timestamp'}} (one `<run>.pickle` of
+    `generate_test_sets.py`) -> (order (N,) int64, positions (N, 2) float64 as (easting, northing), timestamps (N,)
+    float64), positions and timestamps in time order: `order` is the stable sort of the ascending keys by timestamp, so
+    scan r of the ordered run is `run_set[order[r]]`."""
+    keys = np.asarray(sorted(run_set.keys()), dtype=np.int64)
+    t = np.asarray([run_set[int(i)]['timestamp'] for i in keys], dtype=np.float64)
+    by_time = np.argsort(t, kind='stable')
+    order = keys[by_time]
+    positions = np.asarray([[run_set[int(i)]['easting'], run_set[int(i)]['northing']] for i in order],
+                           dtype=np.float64).reshape(-1, 2)
+    return order, positions, t[by_time]
+
+
+def _intra_arguments(embeddings, positions, timestamps, num_neighbors):
+    n = int(embeddings.shape[0])
+    if tuple(positions.shape) != (n, 2) or tuple(timestamps.shape) != (n,):
+        raise ValueError('intra-sequence evaluation: %d embeddings, positions %s, timestamps %s'
+                         % (n, tuple(positions.shape), tuple(timestamps.shape)))
+    if n < 1:
+        raise ValueError('intra-sequence evaluation: the run is empty')
+    num_neighbors = int(num_neighbors)
+    if num_neighbors < 1 or num_neighbors > MAX_K:
+        raise ValueError('intra-sequence evaluation: 1 <= num_neighbors <= %d expected, got %d' % (MAX_K, num_neighbors))
+    return num_neighbors
+
+
+def _host_f64(x):
+    return np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+
+
+def _device_f64(x, device):
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.array(x, dtype=np.float64))
+    return x.detach().to(device=device, dtype=torch.float64).contiguous()
+
+
+def evaluate_intra_sequence(embeddings, positions, timestamps, time_thresh: float = 600.0, world_thresh: float = 3.0,
+                            num_neighbors: int = 25, thresholds=None) -> dict:
+    """Intra-sequence (loop-closure) evaluation of one run in time order on the GPU: `embeddings` (N, D), `positions`
+    (N, 2) easting / northing, `timestamps` (N,) non-decreasing.
+
+    limits = `causal_limits(timestamps, time_thresh)`; the evaluated scans E are those with limits[i] >= 1; "within
+    `world_thresh`" is dx*dx + dy*dy <= r*r in float64; the revisits R are the scans of E with some j < limits[i] within
+    `world_thresh` (`radius_lists`, whose lists ascend: the first listed index decides).  Every scan is searched in its own
+    prefix (`FlatL2Index.search(limits=)`, refined); hit[i, r]: the r-th result is valid and within `world_thresh` of i.
+
+    Returns numpy arrays and Python numbers:
+      'recall' (num_neighbors,) percent, recall[r] = 100 |{i in R: any hit[i, :r + 1]}| / |R|; 'mrr' = 100 mean(1 /
+      (first hit + 1)) over the i in R that have one; 'num_evaluated' |E|, 'num_revisits' |R|;
+      the sweep over cuts tau of the top-1 embedding distance s_i (square root of the f64 squared distance, i in E), with
+      predicted = s_i <= tau, TP = predicted and hit[i, 0], FP = predicted and not hit[i, 0], FN = not predicted and i in R,
+      TN the rest: 'thresholds', 'tp', 'fp', 'fn', 'tn' (int64), 'precision' = TP / (TP + FP) or 1, 'recall_curve' =
+      TP / (TP + FN) or 0, 'f1' = 2 P R / (P + R) or 0; 'f1_max' and 'f1_max_threshold', the smallest cut attaining it
+      (0 and NaN without cuts).  `thresholds=None`: the sorted distinct s_i, the exact curve.
+    Without revisits 'recall' and 'mrr' are NaN and 'f1_max' is 0.  After the search: one sort and cumulative sums on the
+    device."""
+    from . import tuples
+    if not torch.cuda.is_available():
+        raise NativeLibraryError('evaluate_intra_sequence runs on the GPU (evaluate_intra_sequence_host is the CPU route)')
+    index = FlatL2Index(embeddings)
+    dev = index.database.device
+    pos, ts = _device_f64(positions, dev), _device_f64(timestamps, dev)
+    k = _intra_arguments(index.database, pos, ts, num_neighbors)
+    limits = causal_limits(ts, time_thresh)
+    r2 = float(np.float64(world_thresh) * np.float64(world_thresh))
+    with torch.cuda.device(dev):
+        evaluated = limits >= 1
+        off, ids = tuples.radius_lists(pos, None, world_thresh)
+        count = off[1:] - off[:-1]
+        first_near = ids[off[:-1].clamp(max=ids.shape[0] - 1)].long()
+        revisit = evaluated & (count > 0) & (first_near < limits)
+        d2, idx = index.search(index.database, k=k, refine=True, limits=limits)
+        valid = idx >= 0
+        delta = pos[idx.clamp_min(0)] - pos[:, None, :]
+        dx, dy = delta[..., 0], delta[..., 1]
+        hit = valid & (dx * dx + dy * dy <= r2)
+
+        n_rev = int(revisit.sum().item())
+        n_eval = int(evaluated.sum().item())
+        hit_r = hit & revisit[:, None]
+        any_hit = hit_r.any(1)
+        first = hit_r.to(torch.uint8).argmax(1)[any_hit]
+        found = torch.zeros(k, dtype=torch.float64, device=dev)
+        found.index_add_(0, first, torch.ones(first.shape[0], dtype=torch.float64, device=dev))
+        nan = float('nan')
+        recall = (torch.cumsum(found, 0) / float(n_rev) * 100).cpu().numpy() if n_rev else np.full(k, nan)
+        mrr = float((1.0 / (first.double() + 1.0)).mean().item() * 100) if first.shape[0] else nan
+
+        s = torch.sqrt(d2[:, 0][evaluated])
+        hit0, in_r = hit[:, 0][evaluated], revisit[evaluated]
+        s, by_s = torch.sort(s)
+        zero = torch.zeros(1, dtype=torch.long, device=dev)
+        cum_hit = torch.cat([zero, torch.cumsum(hit0[by_s].long(), 0)])
+        cum_r = torch.cat([zero, torch.cumsum(in_r[by_s].long(), 0)])
+        cuts = torch.unique(s) if thresholds is None else _device_f64(thresholds, dev).reshape(-1)
+        predicted = torch.searchsorted(s, cuts, right=True)               # how many s_i <= tau
+        tp = cum_hit[predicted]
+        fp = predicted - tp
+        fn = n_rev - cum_r[predicted]
+        tn = n_eval - tp - fp - fn
+        out = _sweep_curves(cuts, tp, fp, fn, tn)
+    out = {key: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for key, v in out.items()}
+    out.update(recall=recall, mrr=mrr, num_evaluated=n_eval, num_revisits=n_rev)
+    return out
+
+
+def _sweep_curves(cuts, tp, fp, fn, tn):
+    """Precision, recall, F1 and the best cut from the four counts of every cut, on the counts' device."""
+    tpf, pred, pos = tp.double(), tp + fp, tp + fn
+    one, zero = torch.ones_like(tpf), torch.zeros_like(tpf)
+    precision = torch.where(pred > 0, tpf / pred.clamp_min(1).double(), one)
+    recall = torch.where(pos > 0, tpf / pos.clamp_min(1).double(), zero)
+    denom = precision + recall
+    f1 = torch.where(denom > 0, 2.0 * precision * recall / torch.where(denom > 0, denom, one), zero)
+    best = (float(f1.max()), float(cuts[f1 == f1.max()].min())) if f1.shape[0] else (0.0, float('nan'))
+    return {'thresholds': cuts, 'tp': tp, 'fp': fp, 'fn': fn, 'tn': tn, 'precision': precision, 'recall_curve': recall,
+            'f1': f1, 'f1_max': best[0], 'f1_max_threshold': best[1]}
+
+
+def _sweep_curves_host(cuts, tp, fp, fn, tn):
+    """`_sweep_curves` in numpy: the same float64 operations in the same order."""
+    tpf, pred, pos = tp.astype(np.float64), tp + fp, tp + fn
+    one, zero = np.ones_like(tpf), np.zeros_like(tpf)
+    precision = np.where(pred > 0, tpf / np.maximum(pred, 1).astype(np.float64), one)
+    recall = np.where(pos > 0, tpf / np.maximum(pos, 1).astype(np.float64), zero)
+    denom = precision + recall
+    f1 = np.where(denom > 0, 2.0 * precision * recall / np.where(denom > 0, denom, one), zero)
+    best = (float(f1.max()), float(cuts[f1 == f1.max()].min())) if f1.shape[0] else (0.0, float('nan'))
+    return {'thresholds': cuts, 'tp': tp, 'fp': fp, 'fn': fn, 'tn': tn, 'precision': precision, 'recall_curve': recall,
+            'f1': f1, 'f1_max': best[0], 'f1_max_threshold': best[1]}
+
+
+def evaluate_intra_sequence_host(embeddings, positions, timestamps, time_thresh: float = 600.0, world_thresh: float = 3.0,
+                                 num_neighbors: int = 25, thresholds=None) -> dict:
+    """`evaluate_intra_sequence` in numpy float64 on the CPU, the definition of the protocol: dense squared distances summed
+    over the differences of the fp32 descriptors (chunked over query rows), columns >= limits[i] masked, a stable argsort
+    (equal distances by lower index).  The same arguments, the same keys."""
+    emb = embeddings.detach().cpu().numpy() if isinstance(embeddings, torch.Tensor) else np.asarray(embeddings)
+    _check_descriptors('evaluate_intra_sequence_host embeddings', emb.shape)
+    emb = emb.astype(np.float32).astype(np.float64)
+    pos, ts = _host_f64(positions), _host_f64(timestamps)
+    k = _intra_arguments(emb, pos, ts, num_neighbors)
+    n, dim = emb.shape
+    limits = causal_limits(ts, time_thresh)
+    r2 = np.float64(world_thresh) * np.float64(world_thresh)
+    cols = np.arange(n)
+    d2 = np.full((n, k), np.inf)
+    idx = np.full((n, k), -1, dtype=np.int64)
+    near_before = np.zeros(n, dtype=bool)
+    rows = max(1, _HOST_CHUNK_BYTES // (n * dim * 8))
+    for r0 in range(0, n, rows):
+        diff = emb[r0:r0 + rows, None, :] - emb[None, :, :]
+        dist = (diff * diff).sum(-1)
+        allowed = cols[None, :] < limits[r0:r0 + rows, None]
+        dist[~allowed] = np.inf
+        order = np.argsort(dist, axis=1, kind='stable')[:, :k]
+        got = np.take_along_axis(dist, order, 1)
+        ok = np.arange(order.shape[1])[None, :] < limits[r0:r0 + rows, None]
+        d2[r0:r0 + rows, :order.shape[1]] = np.where(ok, got, np.inf)
+        idx[r0:r0 + rows, :order.shape[1]] = np.where(ok, order, -1)
+        dx = pos[r0:r0 + rows, None, 0] - pos[None, :, 0]
+        dy = pos[r0:r0 + rows, None, 1] - pos[None, :, 1]
+        near_before[r0:r0 + rows] = ((dx * dx + dy * dy <= r2) & allowed).any(1)
+    evaluated = limits >= 1
+    revisit = evaluated & near_before
+    valid = idx >= 0
+    delta = pos[np.maximum(idx, 0)] - pos[:, None, :]
+    dx, dy = delta[..., 0], delta[..., 1]
+    hit = valid & (dx * dx + dy * dy <= r2)
+
+    n_rev, n_eval = int(revisit.sum()), int(evaluated.sum())
+    hit_r = hit & revisit[:, None]
+    any_hit = hit_r.any(1)
+    first = hit_r.argmax(1)[any_hit]
+    found = np.bincount(first, minlength=k).astype(np.float64)
+    nan = float('nan')
+    recall = np.cumsum(found) / float(n_rev) * 100 if n_rev else np.full(k, nan)
+    mrr = float((1.0 / (first.astype(np.float64) + 1.0)).mean() * 100) if first.shape[0] else nan
+
+    s = np.sqrt(d2[evaluated, 0])
+    hit0, in_r = hit[evaluated, 0], revisit[evaluated]
+    cuts = np.unique(s) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    predicted = s[None, :] <= cuts[:, None]                                 # (cuts, |E|)
+    tp = (predicted & hit0[None, :]).sum(1).astype(np.int64)
+    fp = (predicted & ~hit0[None, :]).sum(1).astype(np.int64)
+    fn = (~predicted & in_r[None, :]).sum(1).astype(np.int64)
+    tn = n_eval - tp - fp - fn
+    out = _sweep_curves_host(cuts, tp, fp, fn, tn)
+    out.update(recall=recall, mrr=mrr, num_evaluated=n_eval, num_revisits=n_rev)
+    return out
+
+
+def evaluate_intra_dataset(model, clouds, run_set, batch_size: int, *, time_thresh: float = 600.0, world_thresh: float = 3.0,
+                           num_neighbors: int = 25, thresholds=None, **encode_kwargs) -> dict:
+    """Intra-sequence evaluation of one run from raw clouds: `run_set` the reference's per-run dict, `clouds[i]` the (n, 3)
+    cloud of `run_set[i]`; the clouds go through `encode_clouds` in time order (`intra_sequence_arrays`), `encode_kwargs`
+    to it, then `evaluate_intra_sequence`."""
+    order, positions, timestamps = intra_sequence_arrays(run_set)
+    emb = encode_clouds(model, (clouds[int(i)] for i in order), batch_size, **encode_kwargs)
+    return evaluate_intra_sequence(emb, positions, timestamps, time_thresh=time_thresh, world_thresh=world_thresh,
+                                   num_neighbors=num_neighbors, thresholds=thresholds)

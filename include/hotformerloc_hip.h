@@ -1221,6 +1221,17 @@ int hfl_flat_l2_topk(float* dist, int32_t* idx, const float* queries, const floa
                      int64_t n_queries, int64_t n_database, int dim, int k, void* workspace, int64_t workspace_bytes,
                      hfl_stream_t stream);
 
+/* The same search with a prefix per query: query q sees the database rows [0, limits[q]) only (limits (Q) int32 on the
+ * device, read clamped to [0, N], so no value causes an out-of-range access).  dist, idx are (Q, k) whatever N: the first
+ * min(k, limits[q]) slots hold the nearest rows of the prefix under the same key, the rest distance +inf and index -1.  A
+ * pair's distance is the value hfl_flat_l2_topk computes for it, so row q of the result is bitwise what hfl_flat_l2_topk
+ * returns for that query against the first limits[q] database rows.  The tiles of the database above the largest limit of a
+ * 64-query tile are skipped: time-ordered queries with causal limits cost the lower triangle.  Same workspace, same plan,
+ * same argument rules; limits NULL: HFL_EINVAL. */
+int hfl_flat_l2_topk_prefix(float* dist, int32_t* idx, const float* queries, const float* database,
+                            const float* database_sq_norms, const int32_t* limits, int64_t n_queries, int64_t n_database,
+                            int dim, int k, void* workspace, int64_t workspace_bytes, hfl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
