@@ -161,6 +161,11 @@ SIGNATURES = {
     'hfl_pad_index': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'hfl_pad_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     'hfl_mixer_tail': (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    'hfl_mixer_chain_ok': (c_int, [c_int, c_int, c_int, c_int]),
+    'hfl_mixer_chain_pack_bytes': (c_int64, [c_int]),
+    'hfl_mixer_chain_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'hfl_mixer_chain_x3': (c_int, [c_void_p] * 8 + [c_float, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    'hfl_descriptor_tail': (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     'hfl_attn_pool_ok': (c_int, [c_int]),
     'hfl_attn_pool_workspace': (c_int64, [c_int, c_int, c_int, c_int64]),
     'hfl_attn_pool': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_float, c_void_p,
@@ -324,6 +329,9 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+HFL_EINVAL, HFL_ECAPACITY = -1, -2        # include/hotformerloc_hip.h
 
 
 def check(rc: int, what: str):

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBNAME = 'libhotformerloc_hip.so'
 ARCH = 'gfx950'
-SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
+SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'mixer_chain.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc',
          '-Wall', '-Wno-unused-function']
 # hipBLASLt for hfl_gemm_bf16 (the ROCm copy that matches the headers; rpath so the loader finds it)
@@ -32,6 +32,7 @@ EXTRA_FLAGS = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                'attn_fused.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                'attn_ws.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                'relay_block.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'],
+               'mixer_chain.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                # radius.hip: membership must be dx*dx + dy*dy with every operation rounded to float64, bit for bit what numpy
                # computes; the _rn intrinsics alone do not stop hipcc from fusing the second product into the sum (v_fmac_f64)
                'radius.hip': ['-ffp-contract=off'],

@@ -503,3 +503,104 @@ extern "C" int hfl_mixer_tail(float* out, const float* x, const float* channel_w
                                                                                    k_tokens, channels, k_out, out_d);
   HFL_RETURN_LAST_ERROR();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The second half of mixer_tail_kernel as a launch of its own, for U that hfl_mixer_chain_x3 (csrc/mixer_chain.hip) already
+// computed, with the descriptor's L2 normalisation (models/hotformerloc.py: F.normalize(x, dim=1)) folded in:
+//     out[b, o * D + j] = sum_t Wc[o, t] u[b, t, j] + bc[o] sum_c Wr[j, c] + br[j]          then  out[b] /= max(||out[b]||_2, 1e-12)
+// Same statements and summation order as mixer_tail_kernel from its barrier on; the norm is summed in a fixed order (one wave,
+// lane-strided, butterfly), so a descriptor is the same bits from run to run.
+namespace {
+
+__global__ void __launch_bounds__(1024)
+descriptor_tail_kernel(float* __restrict__ out, const float* __restrict__ u, const float* __restrict__ wc,
+                       const float* __restrict__ bc, const float* __restrict__ wr, const float* __restrict__ br, int K, int C, int KO,
+                       int D, int normalize) {
+  extern __shared__ float tail_lds[];                 // U (K x D) | sw (D) | row (KO x D) | 1
+  float* U = tail_lds;
+  float* sw = tail_lds + K * D;
+  float* row = sw + D;
+  float* inv = row + KO * D;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = 16;
+  for (int i = tid; i < K * D; i += NW * 64) U[i] = u[(int64_t)b * K * D + i];
+  if (wave < D) {                                    // sw[j] = sum_c Wr[j, c], wave j (D <= 8 < NW)
+    const int j = wave;
+    float v = 0.f;
+    for (int c = lane; c < C; c += 64) v += wr[(int64_t)j * C + c];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    if (lane == 0) sw[j] = v;
+  }
+  __syncthreads();
+  // wave w takes output tokens o = w, w + 16, ..., four at a time (their channel_proj rows are loaded together; every sum keeps
+  // mixer_tail_kernel's order: lanes over the input tokens, then the butterfly)
+  for (int o0 = wave; o0 < KO; o0 += 4 * NW) {
+    float acc[4][kTailMaxD];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < kTailMaxD; ++j) acc[q][j] = 0.f;
+    for (int t = lane; t < K; t += 64) {
+      float wv[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int o = o0 + q * NW;
+        wv[q] = wc[(int64_t)(o < KO ? o : o0) * K + t];
+      }
+#pragma unroll
+      for (int j = 0; j < kTailMaxD; ++j) {
+        if (j < D) {
+          const float uv = U[t * D + j];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[q][j] = fmaf(wv[q], uv, acc[q][j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int o = o0 + q * NW;
+#pragma unroll
+      for (int j = 0; j < kTailMaxD; ++j) {
+        if (j < D) {
+          float v = acc[q][j];
+#pragma unroll
+          for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+          if (lane == 0 && o < KO) {
+            v = v + bc[o] * sw[j] + br[j];
+            if (normalize) row[o * D + j] = v;
+            else out[(int64_t)b * KO * D + o * D + j] = v;
+          }
+        }
+      }
+    }
+  }
+  if (!normalize) return;
+  __syncthreads();
+  if (wave == 0) {
+    float sq = 0.f;
+    for (int i = lane; i < KO * D; i += 64) sq = fmaf(row[i], row[i], sq);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) sq += __shfl_xor(sq, s, 64);
+    if (lane == 0) *inv = fmaxf(sqrtf(sq), 1e-12f);
+  }
+  __syncthreads();
+  const float den = *inv;
+  for (int i = tid; i < KO * D; i += NW * 64) out[(int64_t)b * KO * D + i] = row[i] / den;
+}
+
+}  // namespace
+
+extern "C" int hfl_descriptor_tail(float* out, const float* u, const float* channel_w, const float* channel_b, const float* row_w,
+                                   const float* row_b, int batch, int k_tokens, int channels, int k_out, int out_d, int normalize,
+                                   hfl_stream_t stream) {
+  if (out == nullptr || u == nullptr || channel_w == nullptr || channel_b == nullptr || row_w == nullptr || row_b == nullptr)
+    return HFL_EINVAL;
+  if (batch < 0 || k_tokens <= 0 || channels <= 0 || k_out <= 0 || out_d <= 0 || out_d > kTailMaxD) return HFL_EINVAL;
+  const size_t lds = ((size_t)(k_tokens + k_out) * out_d + out_d + 1) * sizeof(float);
+  if (lds > 64 * 1024) return HFL_ECAPACITY;
+  if (batch == 0) return HFL_OK;
+  descriptor_tail_kernel<<<(unsigned)batch, 1024, lds, static_cast<hipStream_t>(stream)>>>(out, u, channel_w, channel_b, row_w, row_b,
+                                                                                        k_tokens, channels, k_out, out_d, normalize);
+  HFL_RETURN_LAST_ERROR();
+}

@@ -28,13 +28,9 @@
 #include "hfl_common.h"
 #include "x3_math.h"
 #include "stage_stream.h"
+#include "wfrag.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int RC = 256;                     // channels
 constexpr int RH = 16;                      // heads
@@ -44,7 +40,7 @@ constexpr int RKS = RC / 32;                // k-steps of a C-deep product
 constexpr int RMAXSEQ = 64;                 // relay tokens per cloud
 constexpr float kRelayDead = -1e30f;        // (csrc/attention.hip: kDeadValue)
 
-// pack: per Linear [n-tile of 16 features][k-step of 32][hi | lo][lane = fq * 16 + fr][8 bf16: k = 32 ks + 8 fq ..], W[16 nt + fr][k]
+// pack: per Linear the fragment image of csrc/wfrag.h
 constexpr size_t PACK_QKV = 0;
 constexpr size_t PACK_PROJ = PACK_QKV + (size_t)3 * RC * RC * 4;
 constexpr size_t PACK_FC1 = PACK_PROJ + (size_t)RC * RC * 4;
@@ -147,12 +143,6 @@ __device__ __forceinline__ void relay_stream(Frag&& frag, Body&& body) {
   });
 }
 
-// acc += w_hi x_lo + w_lo x_hi + w_hi x_hi (the order of csrc/qkv_fused.hip and csrc/mlp_fused.hip)
-__device__ __forceinline__ f32x4 relay_x3(bf16x8 whi, bf16x8 wlo, bf16x8 xh, bf16x8 xl, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, xl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xh, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, xh, acc, 0, 0, 0);
-}
 // the same product with the activation rows as the A operand: the accumulator holds rows 4 fq + r, feature fr
 __device__ __forceinline__ f32x4 relay_x3_t(bf16x8 whi, bf16x8 wlo, bf16x8 xh, bf16x8 xl, f32x4 acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, whi, acc, 0, 0, 0);
@@ -324,8 +314,8 @@ relay_block_fused_kernel(const RelayFusedParams p) {
             const unsigned char* src = xa + (t * 16 + fr) * XROW_B + ks * 64 + fq * 16;
             const bf16x8 xh = *reinterpret_cast<const bf16x8*>(src);
             const bf16x8 xl = *reinterpret_cast<const bf16x8*>(src + RC * 2);
-            if (t == qt) qa = relay_x3(w[0], w[1], xh, xl, qa);
-            ka[t] = relay_x3(w[2], w[3], xh, xl, ka[t]);
+            if (t == qt) qa = wfrag_x3(w[0], w[1], xh, xl, qa);
+            ka[t] = wfrag_x3(w[2], w[3], xh, xl, ka[t]);
             va[t] = relay_x3_t(w[4], w[5], xh, xl, va[t]);
           }
         }
@@ -349,8 +339,8 @@ relay_block_fused_kernel(const RelayFusedParams p) {
         const unsigned char* src = ol + fr * XROW_B + ks * 64 + fq * 16;
         const bf16x8 oh = *reinterpret_cast<const bf16x8*>(src);
         const bf16x8 olo = *reinterpret_cast<const bf16x8*>(src + RC * 2);
-        acc[0] = relay_x3(w[0], w[1], oh, olo, acc[0]);
-        acc[1] = relay_x3(w[2], w[3], oh, olo, acc[1]);
+        acc[0] = wfrag_x3(w[0], w[1], oh, olo, acc[0]);
+        acc[1] = wfrag_x3(w[2], w[3], oh, olo, acc[1]);
       });
     }
 #pragma unroll
@@ -386,8 +376,8 @@ relay_block_fused_kernel(const RelayFusedParams p) {
     relay_stream<4 * RKS, 4, 6>(frag, [&](auto sc, bf16x8 (&w)[4]) {
       constexpr int s = decltype(sc)::value;
       constexpr int j = s / RKS, ks = s % RKS;
-      acc[2 * j] = relay_x3(w[0], w[1], xh[ks], xl[ks], acc[2 * j]);
-      acc[2 * j + 1] = relay_x3(w[2], w[3], xh[ks], xl[ks], acc[2 * j + 1]);
+      acc[2 * j] = wfrag_x3(w[0], w[1], xh[ks], xl[ks], acc[2 * j]);
+      acc[2 * j + 1] = wfrag_x3(w[2], w[3], xh[ks], xl[ks], acc[2 * j + 1]);
     });
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -412,8 +402,8 @@ relay_block_fused_kernel(const RelayFusedParams p) {
       const unsigned char* src = gl + fr * GROW_B + ks * 64 + fq * 16;
       const bf16x8 gh = *reinterpret_cast<const bf16x8*>(src);
       const bf16x8 glo = *reinterpret_cast<const bf16x8*>(src + RHID * 2);
-      acc[0] = relay_x3(w[0], w[1], gh, glo, acc[0]);
-      acc[1] = relay_x3(w[2], w[3], gh, glo, acc[1]);
+      acc[0] = wfrag_x3(w[0], w[1], gh, glo, acc[0]);
+      acc[1] = wfrag_x3(w[2], w[3], gh, glo, acc[1]);
     });
     if (my_row >= 0) {
 #pragma unroll
@@ -426,31 +416,6 @@ relay_block_fused_kernel(const RelayFusedParams p) {
         *reinterpret_cast<float4*>(p.out + (int64_t)my_row * RC + n) = v;
       }
     }
-  }
-}
-
-// fp32 Linear weight (N, K) -> its section of the pack: one lane per 16-B cell
-__global__ void __launch_bounds__(256)
-relay_block_pack_kernel(unsigned char* __restrict__ dst, const float* __restrict__ w, int N, int K) {
-  const int ks_n = K / 32;
-  const int64_t cells = (int64_t)N * K / 8;                    // per (hi | lo) half
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (int64_t)gridDim.x * blockDim.x) {
-    const int lane = (int)(i & 63);
-    const int64_t frag = i >> 6;                                // nt * ks_n + ks
-    const int ks = (int)(frag % ks_n), nt = (int)(frag / ks_n);
-    const float* src = w + (int64_t)(nt * 16 + (lane & 15)) * K + ks * 32 + (lane >> 4) * 8;
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t h0 = x3_bf16_rne(src[2 * j]), h1 = x3_bf16_rne(src[2 * j + 1]);
-      const uint32_t l0 = x3_bf16_rne(src[2 * j] - __uint_as_float(h0 << 16));
-      const uint32_t l1 = x3_bf16_rne(src[2 * j + 1] - __uint_as_float(h1 << 16));
-      hi[j] = h0 | (h1 << 16);
-      lo[j] = l0 | (l1 << 16);
-    }
-    unsigned char* d = dst + frag * 2048 + lane * 16;
-    *reinterpret_cast<u32x4*>(d) = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-    *reinterpret_cast<u32x4*>(d + 1024) = (u32x4){lo[0], lo[1], lo[2], lo[3]};
   }
 }
 
@@ -471,10 +436,10 @@ int hfl_relay_block_pack(void* pack, const float* qkv_w, const float* proj_w, co
     return HFL_EINVAL;
   unsigned char* d = static_cast<unsigned char*>(pack);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  relay_block_pack_kernel<<<384, 256, 0, s>>>(d + PACK_QKV, qkv_w, 3 * RC, RC);
-  relay_block_pack_kernel<<<128, 256, 0, s>>>(d + PACK_PROJ, proj_w, RC, RC);
-  relay_block_pack_kernel<<<512, 256, 0, s>>>(d + PACK_FC1, fc1_w, RHID, RC);
-  relay_block_pack_kernel<<<512, 256, 0, s>>>(d + PACK_FC2, fc2_w, RC, RHID);
+  wfrag_pack_kernel<<<384, 256, 0, s>>>(d + PACK_QKV, qkv_w, 3 * RC, RC);
+  wfrag_pack_kernel<<<128, 256, 0, s>>>(d + PACK_PROJ, proj_w, RC, RC);
+  wfrag_pack_kernel<<<512, 256, 0, s>>>(d + PACK_FC1, fc1_w, RHID, RC);
+  wfrag_pack_kernel<<<512, 256, 0, s>>>(d + PACK_FC2, fc2_w, RC, RHID);
   HFL_RETURN_LAST_ERROR();
 }
 

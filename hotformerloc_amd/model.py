@@ -122,6 +122,11 @@ _RELAY_FUSED = True
 # The LayerNorm [+ ReLU] behind an octree convolution inside the convolution's last launch (hfl_slot_sum_norm) on the inference
 # live-tap routes; False: slot sum and norm as two launches everywhere.
 _CONV_NORM_FUSED = True
+# Every FeatureMixerLayer of the Mixer aggregator plus row_proj as ONE launch (hfl_mixer_chain_x3, csrc/mixer_chain.hip) and the
+# rest of the head -- channel_proj, biases, flatten, the descriptor's L2 normalisation -- as a second (hfl_descriptor_tail), where
+# hfl_mixer_chain_ok takes the shapes (C = hidden = 256, at most 4 layers, out_d <= 8); False: a launch (+ its reduce) per
+# layer, hfl_mixer_tail and F.normalize, as before.
+_MIXER_CHAIN = True
 _Q_PRESCALE = 16 ** -0.5 * 1.4426950408889634    # folded into q for the fp16-MFMA attention kernels: head dim 16's scale x log2 e
 
 
@@ -1650,6 +1655,12 @@ def _mixer_pack(fc1: nn.Linear, fc2: nn.Linear):
     return derived('mixer', (w1, w2), lambda: ops.mlp_fused_pack(w1, w2))
 
 
+def _mixer_chain_pack(layers):
+    """`ops.mixer_chain_pack` image of all FeatureMixerLayers' Linears, cached per parameter set like `_mixer_pack`."""
+    w1s, w2s = [m.mix[1].weight for m in layers], [m.mix[3].weight for m in layers]
+    return derived('mixerchain', (*w1s, *w2s), lambda: ops.mixer_chain_pack(w1s, w2s))
+
+
 def _mixer_layer_fits(m) -> bool:
     ln, fc1, act, fc2 = m.mix
     return (isinstance(ln, nn.LayerNorm) and isinstance(act, nn.GELU) and fc1.in_features % 128 == 0
@@ -1665,7 +1676,41 @@ class Mixer(nn.Module):
         self.row_proj = nn.Linear(in_d, out_d)
         self.channel_proj = nn.Linear(k_input_tokens, k_output_tokens)
 
-    def forward(self, x):
+    def _tail_fits(self, x) -> bool:
+        """the inference conditions of `ops.mixer_tail` (and of `ops.descriptor_tail`)"""
+        return (_GEMM_MODE == 'x3' and x.is_cuda and not _grad_path() and x.dtype == torch.float32
+                and x.shape[-1] % 4 == 0 and self.row_proj.out_features <= 8 and self.channel_proj.bias is not None
+                and self.row_proj.bias is not None and x.shape[1] * self.row_proj.out_features <= 16000)
+
+    def chain_shapes_ok(self) -> bool:
+        """the part of the one-launch rule that depends on the module alone: hfl_mixer_chain_ok on its widths and depth, one
+        LayerNorm eps for all layers"""
+        if len(self.mix) == 0 or not all(_mixer_layer_fits(m) for m in self.mix):
+            return False
+        c, hidden = self.row_proj.in_features, self.mix[0].mix[1].out_features
+        return (all(m.mix[1].in_features == c and m.mix[1].out_features == hidden and m.mix[3].out_features == c
+                    and m.mix[0].eps == self.mix[0].mix[0].eps for m in self.mix)
+                and ops.mixer_chain_ok(c, hidden, len(self.mix), self.row_proj.out_features))
+
+    def forward(self, x, normalize=False):
+        """(B, k_out * out_d) descriptors; `normalize`: L2-normalised rows (the wrapper's `normalize_embeddings`)"""
+        if (_MIXER_CHAIN and _GEMM_MODE == 'x3' and _split_path(x) and x.dtype == torch.float32 and self._tail_fits(x)
+                and ops.mlp_fused_shape_ok(x.shape[-1], self.mix[0].mix[1].out_features if len(self.mix) else 0)
+                and (x.shape[1] + self.channel_proj.out_features + 1) * self.row_proj.out_features < 16384   # the tail's LDS
+                and self.chain_shapes_ok()):
+            # the aggregator as two launches: all layers + row_proj (csrc/mixer_chain.hip: the token matrix stays in LDS
+            # between layers), then channel_proj, biases, flatten and the normalisation on the (B, K, out_d) result
+            b, k, c = x.shape
+            lns, fc1s, fc2s = ([m.mix[i] for m in self.mix] for i in (0, 1, 3))
+            _, u = ops.mixer_chain(x.reshape(b * k, c).contiguous(), _mixer_chain_pack(self.mix), [l.weight for l in lns],
+                                   [l.bias for l in lns], [f.bias for f in fc1s], [f.bias for f in fc2s], lns[0].eps,
+                                   row_w=self.row_proj.weight, want_x=False)
+            return ops.descriptor_tail(u.view(b, k, -1), self.channel_proj.weight, self.channel_proj.bias, self.row_proj.weight,
+                                       self.row_proj.bias, normalize)
+        x = self._forward_launches(x)
+        return F.normalize(x, dim=1) if normalize else x
+
+    def _forward_launches(self, x):
         if _split_path(x) and x.shape[-1] % 128 == 0 and all(_mixer_layer_fits(m) for m in self.mix):
             # inference: every FeatureMixerLayer as LayerNorm -> split2, fc1 + GELU, fc2 + residual on the hand-written split GEMM
             # (three launches instead of LayerNorm, addmm, GELU, addmm, add: the (B k, C) token matrix is 8 k rows, every one of
@@ -1704,9 +1749,7 @@ class Mixer(nn.Module):
             x = x2.view(b, k, c)
         else:
             x = self.mix(x)
-        if (_GEMM_MODE == 'x3' and x.is_cuda and not _grad_path() and x.dtype == torch.float32
-                and x.shape[-1] % 4 == 0 and self.row_proj.out_features <= 8 and self.channel_proj.bias is not None
-                and self.row_proj.bias is not None and x.shape[1] * self.row_proj.out_features <= 16000):
+        if self._tail_fits(x):
             # channel_proj, row_proj and the flatten as one small launch (row_proj first: the maps commute)
             return ops.mixer_tail(x, self.channel_proj.weight, self.channel_proj.bias, self.row_proj.weight, self.row_proj.bias)
         x = self.channel_proj(x.permute(0, 2, 1)).permute(0, 2, 1)
@@ -1738,7 +1781,8 @@ class PyramidAttnPoolWrapper(nn.Module):
             f'Invalid k for k_pooled_tokens: {k_pooled_tokens}, not compatible with output dim {output_dim}'
         self.descriptor_extractor = Mixer(total, k_out, feature_size, mix_depth, mlp_ratio, out_d)
 
-    def forward(self, local_feat_dict, plan: WindowPlan, depth=None):
+    def forward(self, local_feat_dict, plan: WindowPlan, depth=None, normalize=False):
+        """`normalize`: the Mixer returns L2-normalised descriptors (one launch with its tail where that applies)"""
         feats = list(local_feat_dict.items())
         if (not self.use_projections and not _grad_path() and feats and feats[0][1].is_cuda
                 and all(f.shape[1] == feats[0][1].shape[1] and f.dtype == torch.float32 for _, f in feats)):
@@ -1752,12 +1796,12 @@ class PyramidAttnPoolWrapper(nn.Module):
                 if t.data_ptr() != all_t[:, off:off + k].data_ptr():
                     all_t[:, off:off + k].copy_(t)
                 off += k
-            return self.descriptor_extractor(all_t)
+            return self.descriptor_extractor(all_t, normalize)
         toks = []
         for j, d in enumerate(local_feat_dict.keys()):
             t = self.attpool[j](local_feat_dict[d], plan, d)
             toks.append(self.local_projections[j](t) if self.use_projections else t)
-        return self.descriptor_extractor(torch.cat(toks, 1))
+        return self.descriptor_extractor(torch.cat(toks, 1), normalize)
 
 
 class OctGeM(nn.Module):
@@ -1910,8 +1954,12 @@ class PoolingWrapper(nn.Module):
         else:
             raise NotImplementedError('Unknown pooling method: {}'.format(pool_method))
 
-    def forward(self, x, octree=None, depth=None):
-        return self.pooling(x, octree, depth)
+    def forward(self, x, octree=None, depth=None, normalize=False):
+        """`normalize`: F.normalize(., dim=1) of the descriptors; the Mixer head folds it into its last launch"""
+        if normalize and isinstance(self.pooling, PyramidAttnPoolWrapper):
+            return self.pooling(x, octree, depth, normalize=True)
+        x = self.pooling(x, octree, depth)
+        return F.normalize(x, dim=1) if normalize else x
 
 
 # ------------------------------------------------------------------------- wrapper
@@ -1950,10 +1998,8 @@ class HOTFormerLoc(nn.Module):
             x = relay
         else:
             raise ValueError(f"Invalid option for pooled features: '{self.pooling.pooled_feats}'")
-        x = self.pooling(x, octree=plan)
+        x = self.pooling(x, octree=plan, normalize=self.normalize_embeddings)
         assert x.dim() == 2 and x.shape[1] == self.pooling.output_dim
-        if self.normalize_embeddings:
-            x = F.normalize(x, dim=1)
         return {'global': x}
 
     def print_info(self):

@@ -1200,6 +1200,78 @@ def mixer_tail(x: torch.Tensor, channel_w, channel_b, row_w, row_b):
     return out
 
 
+def mixer_chain_ok(channels: int, hidden: int, layers: int, out_d: int) -> bool:
+    return bool(_native.load().hfl_mixer_chain_ok(int(channels), int(hidden), int(layers), int(out_d)))
+
+
+def mixer_chain_pack(w1s, w2s) -> torch.Tensor:
+    """Weight image of `mixer_chain` (hfl_mixer_chain_pack) from the fp32 weights fc1 (C, C) and fc2 (C, C) of every layer, in
+    layer order: bf16 (hi, lo) MFMA fragments.  Once per parameter set."""
+    w1s, w2s = [_f32c(w.detach()) for w in w1s], [_f32c(w.detach()) for w in w2s]
+    _dev(*w1s, *w2s)
+    lib = _native.load()
+    layers = len(w1s)
+    ok = len(w2s) == layers and all(tuple(w.shape) == (256, 256) for w in w1s + w2s)
+    n = int(lib.hfl_mixer_chain_pack_bytes(layers)) if ok else 0
+    if n <= 0:
+        raise _native.NativeLibraryError('hfl_mixer_chain_pack: unsupported layer count or shape')
+    pack = torch.empty(n, dtype=torch.uint8, device=w1s[0].device)
+    check(lib.hfl_mixer_chain_pack(pack.data_ptr(), _native.ptr_array([w.data_ptr() for w in w1s]),
+                                   _native.ptr_array([w.data_ptr() for w in w2s]), layers, _stream()), 'hfl_mixer_chain_pack')
+    return pack
+
+
+def mixer_chain(x, pack, gammas, betas, b1s, b2s, eps: float, row_w=None, want_x: bool = True):
+    """L FeatureMixerLayers x = x + fc2(gelu(fc1(LN(x)))) on the rows of x (M, 256), then u = x @ row_w^T (row_w (D, 256), D <= 8,
+    optional), in ONE launch (hfl_mixer_chain_x3); `pack` from `mixer_chain_pack`, the other lists hold one tensor per layer.
+    Returns (x after the last layer or None, u (M, D) or None): each is written only when asked for.  A problem the launch
+    does not take (hfl_mixer_chain_ok, or rows that are not contiguous) raises with the library's HFL_EINVAL: nothing runs."""
+    vecs = [list(gammas), list(betas), list(b1s), list(b2s)]
+    _dev(x, pack, row_w, *[v for vs in vecs for v in vs])
+    layers = len(vecs[0])
+    lib = _native.load()
+    if x.dtype != torch.float32:
+        raise TypeError('float32 expected, got %s' % x.dtype)
+    hidden = vecs[2][0].numel() if layers > 0 else 0
+    d = 0 if row_w is None else int(row_w.shape[0])
+    fits = (x.dim() == 2 and x.is_contiguous() and all(len(v) == layers for v in vecs[1:])
+            and lib.hfl_mixer_chain_ok(x.shape[-1], hidden, layers, d)
+            and all(v.numel() == x.shape[1] for vs in vecs for v in vs)
+            and (row_w is None or row_w.shape[1] == x.shape[1]) and (row_w is not None or want_x))
+    if not fits:
+        check(_native.HFL_EINVAL, 'hfl_mixer_chain_x3')
+    assert pack.numel() == int(lib.hfl_mixer_chain_pack_bytes(layers)), 'pack does not belong to this layer count'
+    m, c = x.shape
+    vecs = [[_f32c(v) for v in vs] for vs in vecs]
+    row_w = None if row_w is None else _f32c(row_w)
+    out_x = torch.empty_like(x) if want_x else None
+    out_u = torch.empty((m, d), dtype=torch.float32, device=x.device) if d > 0 else None
+    # algorithmic bytes: read x, write what was asked for; 2 GEMMs of 2 M C C flop per layer
+    with _timed('hfl_mixer_chain_x3', m * c * (8 if want_x else 4) + m * d * 4, layers * 4 * m * c * c + 2 * m * c * d):
+        check(lib.hfl_mixer_chain_x3(None if out_x is None else out_x.data_ptr(), None if out_u is None else out_u.data_ptr(),
+                                     x.data_ptr(), pack.data_ptr(), *[_native.ptr_array([v.data_ptr() for v in vs]) for vs in vecs],
+                                     float(eps), None if row_w is None else row_w.data_ptr(), m, layers, d, _stream()),
+              'hfl_mixer_chain_x3')
+    return out_x, out_u
+
+
+def descriptor_tail(u: torch.Tensor, channel_w, channel_b, row_w, row_b, normalize: bool):
+    """(B, k_out * D) descriptors from u (B, K, D) = row_proj without its bias (`mixer_chain`): channel_proj over the token axis,
+    both biases, the flatten, and with `normalize` F.normalize(., dim=1), in one launch (hfl_descriptor_tail); channel_w
+    (k_out, K), row_w (D, C)."""
+    _dev(u, channel_w, channel_b, row_w, row_b)
+    u = _f32c(u)
+    b, k, d = u.shape
+    ko, c = channel_w.shape[0], row_w.shape[1]
+    assert tuple(channel_w.shape) == (ko, k) and tuple(row_w.shape) == (d, c)
+    out = torch.empty((b, ko * d), dtype=torch.float32, device=u.device)
+    with _timed('hfl_descriptor_tail', u.numel() * 4 + out.numel() * 4 + ko * k * 4, 2 * b * ko * k * d):
+        check(_native.load().hfl_descriptor_tail(out.data_ptr(), u.data_ptr(), _f32c(channel_w).data_ptr(),
+                                                 _f32c(channel_b).data_ptr(), _f32c(row_w).data_ptr(), _f32c(row_b).data_ptr(),
+                                                 b, k, c, ko, d, 1 if normalize else 0, _stream()), 'hfl_descriptor_tail')
+    return out
+
+
 def attn_pool_ok(channels: int) -> bool:
     return bool(_native.load().hfl_attn_pool_ok(int(channels)))
 

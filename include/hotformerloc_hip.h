@@ -459,6 +459,28 @@ int hfl_pad_rows(float* out, const float* x, const int64_t* row_off, int batch, 
  * order. */
 int hfl_mixer_tail(float* out, const float* x, const float* channel_w, const float* channel_b, const float* row_w,
                    const float* row_b, int batch, int k_tokens, int channels, int k_out, int out_d, hfl_stream_t stream);
+/* Every FeatureMixerLayer of the Mixer aggregator (models/layers/salsa.py:58-111) and row_proj as ONE launch
+ * (csrc/mixer_chain.hip), x (M, 256) f32 rows:
+ *     for l < layers:  x = x + fc2_l(gelu(fc1_l(LN_l(x))))        u[row, j] = sum_c x[row, c] row_w[j, c],  j < out_d
+ * with the arithmetic of `layers` calls of hfl_ln_mlp_fused_h at every hand-off (only f32 summation orders differ) and the
+ * f32 dot of hfl_mixer_tail.  hfl_mixer_chain_ok: 1 for channels = hidden = 256, 1 <= layers <= 4, 0 <= out_d <= 8.
+ * packs: hfl_mixer_chain_pack_bytes(layers) bytes (0 = unsupported) written by hfl_mixer_chain_pack from the fp32 weights
+ * w1[l] (256, 256), w2[l] (256, 256), once per parameter set.  gamma / beta / b1 / b2 / w1 / w2: host arrays of `layers` device
+ * pointers.  out_x (M, 256) and out_u (M, out_d) are each written only when given: out_d > 0 needs out_u and row_w, out_d = 0
+ * needs out_x and no out_u.  out_x may be x.  Anything else: HFL_EINVAL, nothing launched. */
+int hfl_mixer_chain_ok(int channels, int hidden, int layers, int out_d);
+int64_t hfl_mixer_chain_pack_bytes(int layers);
+int hfl_mixer_chain_pack(void* dst, const float* const* w1, const float* const* w2, int layers, hfl_stream_t stream);
+int hfl_mixer_chain_x3(float* out_x, float* out_u, const float* x, const void* packs, const float* const* gamma,
+                       const float* const* beta, const float* const* b1, const float* const* b2, float eps, const float* row_w,
+                       int64_t M, int layers, int out_d, hfl_stream_t stream);
+/* The rest of hfl_mixer_tail for u (batch, k_tokens, out_d) = row_proj without its bias (hfl_mixer_chain_x3's out_u):
+ *     out[b, o * out_d + j] = sum_t channel_w[o, t] u[b, t, j] + channel_b[o] sum_c row_w[j, c] + row_b[j]
+ * in hfl_mixer_tail's order and arithmetic; normalize != 0: the row divided by max(||row||_2, 1e-12) (F.normalize(out, dim=1)),
+ * the norm summed in a fixed order.  One workgroup per cloud. */
+int hfl_descriptor_tail(float* out, const float* u, const float* channel_w, const float* channel_b, const float* row_w,
+                        const float* row_b, int batch, int k_tokens, int channels, int k_out, int out_d, int normalize,
+                        hfl_stream_t stream);
 int hfl_attn_pool_ok(int channels);
 int64_t hfl_attn_pool_workspace(int batch, int n_queries, int channels, int64_t n_rows);
 int hfl_attn_pool(float* out, int64_t out_cloud_stride, const float* x, const int64_t* row_off, const float* query, int batch,
