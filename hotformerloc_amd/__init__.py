@@ -36,5 +36,8 @@ from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_coun
 from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_points, nn_distances,   # noqa: F401,E402
                       chamfer_distance, overlap_ratio, submap_overlap, transform_points_host, nn_distances_host,
                       chamfer_distance_host, overlap_ratio_host, submap_overlap_host, ChamferResult, SubmapOverlap)
+from .registration import (icp_refine, icp_refine_host, icp_correspondences, icp_correspondences_host,  # noqa: F401,E402
+                           evaluate_registration, evaluate_registration_host, kabsch_update, kabsch_update_host,
+                           RegistrationResult)
 
 __version__ = '0.1.0'

@@ -256,6 +256,10 @@ SIGNATURES = {
                             c_int64, c_void_p]),
     'hfl_pair_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.POINTER(c_float), c_int,
                                c_void_p]),
+    'hfl_icp_correspond': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
+    'hfl_icp_solve': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double,
+                              c_double, c_int, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -1,0 +1,327 @@
+// Rigid point-to-point ICP for a ragged batch of P (source, target) pairs: the definition is in
+// hotformerloc_amd/registration.py and DESIGN.md section 7i.  The layout is that of overlap.hip: the points of all clouds
+// concatenated as (N, 3) fp32 with (P + 1) int64 offsets.  One iteration is two launches, and a whole batch runs to
+// convergence without a host read: the state of a pair lives in two plain device arrays,
+//     state  (P, 16) float64: the pose as a row-major 3 x 4 (R | t), fitness, rmse, previous fitness, previous rmse
+//     istate (P, 2)  int32:   iterations, status (HFL_ICP_RUNNING .. HFL_ICP_DEGENERATE).
+//
+// hfl_icp_correspond: hfl_nn_dist with the transform in front of it and the reduction behind it.  A workgroup of 256 threads
+// owns RG_ROWS consecutive source rows of one pair (the tile table of hfl_nn_dist).  A pair that is no longer RUNNING makes
+// its workgroups return at once.  Otherwise the workgroup rounds the pair's float64 pose to fp32, moves its rows by the fmaf
+// chain of hfl_transform_points, scans the pair's target cloud through LDS exactly as nn_dist_kernel does (the same
+// expressions in the same order, so dist and idx have the bits of hfl_nn_dist on the transformed cloud), reads the winner's
+// coordinates from global memory once the scan is over, and sums over its inlier rows (d <= max_dist in fp32) the 17
+// float64 quantities
+//     n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2         p' the moved source point, q its target.
+// Every product of two fp32 values is exact in float64, so contracting a product into its sum changes no bit.  Order: a
+// thread adds its rows in row order, a wave combines its lanes by the xor butterfly 32 .. 1, and the four wave results are
+// added in wave order (threads 0 .. 16, one quantity each): the order of pair_stats_kernel.  The result is row blockIdx.x of
+// the (n_tiles, 17) partials.
+//
+// hfl_icp_solve: one wave per pair.  Lanes 0 .. 16 add the pair's tile partials in ascending tile order, one quantity each;
+// lane 0 then applies the stop rules, solves for the rigid update and composes the pose, all in float64.  The solve is a
+// one-sided cyclic Jacobi on H = Spq - Sp Sq^T / n with a fixed number of sweeps: column pairs (0,1), (0,2), (1,2) of G = H V
+// are rotated until they are orthogonal, the column norms are the singular values, G's normalised columns are U.  With u1, u2
+// and v1, v2 the columns of the two largest singular values,
+//     R = v1 u1^T + v2 u2^T + (v1 x v2) (u1 x u2)^T,
+// which is V diag(1, 1, det(V U^T)) U^T without ever dividing by the smallest singular value: det R = +1 whether or not the
+// unconstrained optimum is a reflection, and a planar cloud needs no special case.
+//
+// No atomics; every output element has one writer and a fixed evaluation order: two runs give the same bits.
+#include <math.h>
+
+#include "ragged_common.h"
+
+namespace {
+
+constexpr int RG_THREADS = 256;
+constexpr int RG_ROWS = HFL_OVERLAP_ROWS;                        // source rows of a workgroup
+constexpr int RG_QPT = RG_ROWS / RG_THREADS;                     // source points a thread keeps in registers
+constexpr int RG_TILE = HFL_OVERLAP_TILE;                        // target points of an LDS tile
+constexpr int RG_SUMS = HFL_ICP_SUMS;
+constexpr int RG_WAVES = RG_THREADS / HFL_WAVE;
+constexpr int RG_SWEEPS = 12;                                    // a 3 x 3 converges quadratically: 5 or 6 suffice
+constexpr double RG_RANK_TOL = 1e-12;                            // second singular value <= this x the largest: degenerate
+static_assert(RG_ROWS % RG_THREADS == 0 && RG_QPT >= 1, "whole source points per thread");
+// 3 x 2048 x 4 B = 24 KiB of static LDS as in nn_dist_kernel; the wave results of the reduction reuse the x plane
+static_assert(RG_TILE % 4 == 0 && RG_TILE * 12 <= 32 * 1024, "static LDS stays at 32 KiB or less");
+static_assert(RG_WAVES * RG_SUMS * sizeof(double) <= RG_TILE * sizeof(float), "the wave results fit the x plane");
+static_assert(RG_SUMS == 17, "n, Sp, Sq, Spq, sum d^2");
+
+// six waves per SIMD, the residency of nn_dist_kernel (six workgroups of 24 KiB per CU): 80 VGPRs, which the reduction's 17
+// float64 sums beside the gathered coordinates would otherwise exceed by two
+__global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(6)))
+icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, int32_t* __restrict__ idx,
+                      const float* __restrict__ source, const int64_t* __restrict__ s_off, int64_t n_source,
+                      const float* __restrict__ targets, const int64_t* __restrict__ t_off, int64_t n_targets,
+                      const int64_t* __restrict__ tiles, const double* __restrict__ state,
+                      const int32_t* __restrict__ istate, float max_dist, int n_pairs) {
+  __shared__ __align__(16) float s_x[RG_TILE], s_y[RG_TILE], s_z[RG_TILE];
+  const int64_t p = tiles[2 * (int64_t)blockIdx.x], row0 = tiles[2 * (int64_t)blockIdx.x + 1];
+  if (p < 0 || p >= n_pairs || row0 < 0) return;                 // uniform over the workgroup
+  if (istate[2 * p + 1] != HFL_ICP_RUNNING) return;              // the pair has stopped: its partials are not read again
+  // the offsets are clamped to the arrays, so a wrong table or offset cannot make the kernel read or write outside them
+  const int64_t q_end = min(s_off[p + 1], n_source);
+  const int64_t t_begin = max(t_off[p], (int64_t)0), t_end = min(t_off[p + 1], n_targets);
+
+  float m[12];                                                   // the pose, rounded once to fp32
+#pragma unroll
+  for (int k = 0; k < 12; ++k) m[k] = (float)state[16 * p + k];
+
+  float qx[RG_QPT], qy[RG_QPT], qz[RG_QPT], best[RG_QPT];
+  int32_t at[RG_QPT];
+#pragma unroll
+  for (int r = 0; r < RG_QPT; ++r) {
+    const int64_t row = row0 + r * RG_THREADS + threadIdx.x;
+    const bool valid = row < q_end;
+    const float x = valid ? source[3 * row] : 0.f, y = valid ? source[3 * row + 1] : 0.f, z = valid ? source[3 * row + 2] : 0.f;
+    float c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {                                // the chain of transform_points_kernel
+      float acc = fmaf(m[4 * a], x, m[4 * a + 3]);
+      acc = fmaf(m[4 * a + 1], y, acc);
+      c[a] = fmaf(m[4 * a + 2], z, acc);
+    }
+    qx[r] = c[0];
+    qy[r] = c[1];
+    qz[r] = c[2];
+    best[r] = INFINITY;
+    at[r] = -1;
+  }
+
+  // the scan of nn_dist_kernel (overlap.hip), expression for expression
+  for (int64_t tile = t_begin; tile < t_end; tile += RG_TILE) {
+    const int len = (int)min((int64_t)RG_TILE, t_end - tile);
+    const int len4 = (len + 3) & ~3;                             // the last tile is padded to whole groups of four
+    __syncthreads();                                             // the previous tile has been read by every wave
+    for (int k = threadIdx.x; k < len4; k += RG_THREADS) {
+      const int64_t j = tile + k;
+      const bool real = k < len;                                 // padding lies at +inf: its d2 is +inf, never `<` a best
+      s_x[k] = real ? targets[3 * j] : INFINITY;
+      s_y[k] = real ? targets[3 * j + 1] : INFINITY;
+      s_z[k] = real ? targets[3 * j + 2] : INFINITY;
+    }
+    __syncthreads();
+    const int32_t base = (int32_t)(tile - t_begin);              // < 2^31: the entry point bounds n_targets
+#pragma unroll 2
+    for (int k = 0; k < len4; k += 4) {
+      // the same address in every lane: three broadcast ds_read_b128 bring four target points
+      const float4 cx = *reinterpret_cast<const float4*>(&s_x[k]);
+      const float4 cy = *reinterpret_cast<const float4*>(&s_y[k]);
+      const float4 cz = *reinterpret_cast<const float4*>(&s_z[k]);
+      const float tx[4] = {cx.x, cx.y, cx.z, cx.w}, ty[4] = {cy.x, cy.y, cy.z, cy.w}, tz[4] = {cz.x, cz.y, cz.z, cz.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {                              // ascending target index
+#pragma unroll
+        for (int r = 0; r < RG_QPT; ++r) {
+          const float dx = qx[r] - tx[u], dy = qy[r] - ty[u], dz = qz[r] - tz[u];
+          const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+          const bool closer = d2 < best[r];                      // strict: of equal distances the lowest index stays
+          best[r] = closer ? d2 : best[r];
+          at[r] = closer ? base + k + u : at[r];
+        }
+      }
+    }
+  }
+
+  double acc[RG_SUMS];
+#pragma unroll
+  for (int k = 0; k < RG_SUMS; ++k) acc[k] = 0.0;
+#pragma unroll
+  for (int r = 0; r < RG_QPT; ++r) {                             // a thread's rows in row order
+    const int64_t row = row0 + r * RG_THREADS + threadIdx.x;
+    if (row < q_end) {
+      const float d = __fsqrt_rn(best[r]);                       // sqrt(+inf) = +inf: an empty target cloud
+      if (dist != nullptr) dist[row] = d;
+      if (idx != nullptr) idx[row] = at[r];
+      if (at[r] >= 0 && d <= max_dist) {                         // 0 <= at < t_end - t_begin: the gather stays in the cloud
+        const float* w = targets + 3 * (t_begin + at[r]);
+        const double pc[3] = {(double)qx[r], (double)qy[r], (double)qz[r]};
+        const double qc[3] = {(double)w[0], (double)w[1], (double)w[2]};
+        const double dd = (double)d;
+        acc[0] += 1.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          acc[1 + a] += pc[a];
+          acc[4 + a] += qc[a];
+#pragma unroll
+          for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += pc[a] * qc[b];
+        }
+        acc[16] += dd * dd;
+      }
+    }
+  }
+
+  double* red = reinterpret_cast<double*>(s_x);                  // (RG_WAVES, RG_SUMS)
+  const int lane = threadIdx.x & (HFL_WAVE - 1), wave = threadIdx.x / HFL_WAVE;
+#pragma unroll
+  for (int k = 0; k < RG_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  __syncthreads();                                               // the last tile has been read by every wave
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < RG_SUMS; ++k) red[wave * RG_SUMS + k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < RG_SUMS) {
+    double v = red[threadIdx.x];
+    for (int w = 1; w < RG_WAVES; ++w) v += red[w * RG_SUMS + threadIdx.x];
+    partials[(int64_t)blockIdx.x * RG_SUMS + threadIdx.x] = v;
+  }
+}
+
+// columns P and Q of G = H V made orthogonal by one plane rotation, applied to V as well
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rotate(double (&g)[3][3], double (&v)[3][3]) {
+  const double alpha = g[0][P] * g[0][P] + g[1][P] * g[1][P] + g[2][P] * g[2][P];
+  const double beta = g[0][Q] * g[0][Q] + g[1][Q] * g[1][Q] + g[2][Q] * g[2][Q];
+  const double gamma = g[0][P] * g[0][Q] + g[1][P] * g[1][Q] + g[2][P] * g[2][Q];
+  if (gamma == 0.0) return;
+  const double zeta = (beta - alpha) / (2.0 * gamma);
+  const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));    // zeta = +-inf: t = 0
+  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double gp = g[i][P], gq = g[i][Q], vp = v[i][P], vq = v[i][Q];
+    g[i][P] = c * gp - s * gq;
+    g[i][Q] = s * gp + c * gq;
+    v[i][P] = c * vp - s * vq;
+    v[i][Q] = s * vp + c * vq;
+  }
+}
+
+__device__ __forceinline__ double pick(const double (&a)[3][3], int i, int j) {
+  return j == 0 ? a[i][0] : (j == 1 ? a[i][1] : a[i][2]);
+}
+
+// the rigid update (R | t) of the 17 sums; false where the correspondences are collinear or coincident
+__device__ bool kabsch_solve(const double* s, double (&r)[3][3], double (&t)[3]) {
+  const double n = s[0];
+  double g[3][3], v[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      g[a][b] = s[7 + 3 * a + b] - s[1 + a] * s[4 + b] / n;      // H
+      v[a][b] = a == b ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < RG_SWEEPS; ++sweep) {
+    jacobi_rotate<0, 1>(g, v);
+    jacobi_rotate<0, 2>(g, v);
+    jacobi_rotate<1, 2>(g, v);
+  }
+  double w[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) w[j] = sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]);
+  // the largest and the second largest, the lowest column on a tie
+  const int i1 = (w[0] >= w[1] && w[0] >= w[2]) ? 0 : (w[1] >= w[2] ? 1 : 2);
+  const int ja = i1 == 0 ? 1 : 0, jb = i1 == 2 ? 1 : 2;
+  const int i2 = w[ja] >= w[jb] ? ja : jb;
+  const double w1 = i1 == 0 ? w[0] : (i1 == 1 ? w[1] : w[2]), w2 = i2 == 0 ? w[0] : (i2 == 1 ? w[1] : w[2]);
+  if (!(w2 > RG_RANK_TOL * w1)) return false;                    // also a NaN, and H = 0
+  double u1[3], u2[3], v1[3], v2[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    u1[i] = pick(g, i, i1) / w1;
+    u2[i] = pick(g, i, i2) / w2;
+    v1[i] = pick(v, i, i1);
+    v2[i] = pick(v, i, i2);
+  }
+  const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+  const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+  const double mp[3] = {s[1] / n, s[2] / n, s[3] / n}, mq[3] = {s[4] / n, s[5] / n, s[6] / n};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) r[a][b] = v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b];
+    t[a] = mq[a] - (r[a][0] * mp[0] + r[a][1] * mp[1] + r[a][2] * mp[2]);
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(HFL_WAVE)
+icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, double* __restrict__ sums,
+                 const double* __restrict__ partials, const int64_t* __restrict__ tile_off, int64_t n_tiles,
+                 const int64_t* __restrict__ s_off, int min_corr, double rel_fitness, double rel_rmse, int is_last) {
+  const int64_t p = blockIdx.x;
+  if (istate[2 * p + 1] != HFL_ICP_RUNNING) return;              // uniform: one wave per pair
+  const int lane = threadIdx.x;
+  const int64_t first = max(tile_off[p], (int64_t)0), last = min(tile_off[p + 1], n_tiles);
+  double mine = 0.0;
+  if (lane < RG_SUMS)
+    for (int64_t tile = first; tile < last; ++tile) mine += partials[tile * RG_SUMS + lane];   // ascending tile order
+  if (sums != nullptr && lane < RG_SUMS) sums[p * RG_SUMS + lane] = mine;
+  double s[RG_SUMS];
+#pragma unroll
+  for (int k = 0; k < RG_SUMS; ++k) s[k] = __shfl(mine, k, HFL_WAVE);
+  if (lane != 0) return;
+
+  double* st = state + 16 * p;
+  const int k_iter = istate[2 * p];
+  const double n = s[0], n_src = (double)max(s_off[p + 1] - s_off[p], (int64_t)0);
+  const double fitness = n / n_src;                              // an empty source cloud: 0 / 0 = NaN
+  const bool few = n < (double)min_corr;
+  const double rmse = (few || n <= 0.0) ? (double)NAN : sqrt(s[16] / n);
+  st[12] = fitness;
+  st[13] = rmse;
+  if (few) {
+    istate[2 * p + 1] = HFL_ICP_TOO_FEW;
+    return;
+  }
+  if (k_iter >= 1 && fabs(fitness - st[14]) < rel_fitness && fabs(rmse - st[15]) < rel_rmse) {
+    istate[2 * p + 1] = HFL_ICP_CONVERGED;
+    return;
+  }
+  if (is_last) {
+    istate[2 * p + 1] = HFL_ICP_MAX_ITERATIONS;
+    return;
+  }
+  double r[3][3], t[3];
+  if (!kabsch_solve(s, r, t)) {
+    istate[2 * p + 1] = HFL_ICP_DEGENERATE;
+    return;
+  }
+  double next[12];                                               // (R | t) . T_k
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      next[4 * a + b] = r[a][0] * st[b] + r[a][1] * st[4 + b] + r[a][2] * st[8 + b] + (b == 3 ? t[a] : 0.0);
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) st[k] = next[k];
+  st[14] = fitness;
+  st[15] = rmse;
+  istate[2 * p] = k_iter + 1;
+}
+
+}  // namespace
+
+extern "C" int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
+                                  int64_t n_source, const float* targets, const int64_t* t_offsets, int64_t n_targets,
+                                  const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
+                                  float max_dist, int64_t n_pairs, hfl_stream_t stream) {
+  if (partials == nullptr || source == nullptr || s_offsets == nullptr || targets == nullptr || t_offsets == nullptr ||
+      tiles == nullptr || state == nullptr || istate == nullptr || n_source < 0 || n_targets < 0 || n_tiles < 0 || n_pairs < 1)
+    return HFL_EINVAL;
+  // a target index is an int32, the grid is one-dimensional
+  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
+  if (n_tiles == 0) return HFL_OK;
+  icp_correspond_kernel<<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      partials, dist, idx, source, s_offsets, n_source, targets, t_offsets, n_targets, tiles, state, istate, max_dist,
+      (int)n_pairs);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials,
+                             const int64_t* tile_offsets, int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs,
+                             int min_correspondences, double relative_fitness, double relative_rmse, int is_last,
+                             hfl_stream_t stream) {
+  if (state == nullptr || istate == nullptr || partials == nullptr || tile_offsets == nullptr || s_offsets == nullptr ||
+      n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
+    return HFL_EINVAL;
+  if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
+  icp_solve_kernel<<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
+      state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
+      is_last);
+  HFL_RETURN_LAST_ERROR();
+}

@@ -1907,7 +1907,76 @@ def pair_stats(dist: torch.Tensor, offsets: torch.Tensor, taus=()):
     return sums, counts
 
 
-VOXEL_MAX_CLOUDS = 32767              # HFL_VOXEL_MAX_CLOUDS
+ICP_SUMS = 17                          # HFL_ICP_SUMS: n, Sp (3), Sq (3), Spq (9), sum d^2
+
+
+def _icp_state_check(what: str, state: torch.Tensor, istate: torch.Tensor, pairs: int):
+    _dev(state, istate)
+    if state.dtype != torch.float64 or tuple(state.shape) != (pairs, 16) or not state.is_contiguous():
+        raise TypeError('%s: contiguous (%d, 16) float64 state expected' % (what, pairs))
+    if istate.dtype != torch.int32 or tuple(istate.shape) != (pairs, 2) or not istate.is_contiguous():
+        raise TypeError('%s: contiguous (%d, 2) int32 iterations / status expected' % (what, pairs))
+
+
+def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
+                   tiles: torch.Tensor, state: torch.Tensor, istate: torch.Tensor, max_dist: float, partials=None,
+                   want_rows: bool = False):
+    """`hfl_icp_correspond`: one evaluation of every RUNNING pair.  source / targets: two ragged batches of the same P pairs;
+    tiles: the device copy of `overlap_tiles` of the source lengths; state (P, 16) float64 and istate (P, 2) int32 as the
+    header lays them out.  -> (partials (n_tiles, ICP_SUMS) float64, dist, idx): `partials` is written in place where one is
+    given (the iteration loop allocates once), dist (Ns,) fp32 and idx (Ns,) int32 are None unless `want_rows`.  Rows of
+    pairs that are not RUNNING stay unwritten."""
+    pairs = _ragged_check('icp_correspond', source, s_offsets)
+    if _ragged_check('icp_correspond', targets, t_offsets) != pairs:
+        raise ValueError('icp_correspond: the source batch and the target batch differ in their number of pairs')
+    _icp_state_check('icp_correspond', state, istate, pairs)
+    _dev(tiles)
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('icp_correspond: contiguous (n_tiles, 2) int64 tile table expected')
+    n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
+    if partials is None:
+        partials = torch.empty((max(n_tiles, 1), ICP_SUMS), dtype=torch.float64, device=source.device)
+    _dev(partials)
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
+            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
+        raise TypeError('icp_correspond: contiguous (>= %d, %d) float64 partials expected' % (n_tiles, ICP_SUMS))
+    dist = torch.empty(n_s, dtype=torch.float32, device=source.device) if want_rows else None
+    idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
+    if n_tiles:
+        check(_native.load().hfl_icp_correspond(partials.data_ptr(), dist.data_ptr() if want_rows else None,
+                                                idx.data_ptr() if want_rows else None, source.data_ptr(),
+                                                s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), t_offsets.data_ptr(),
+                                                int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(),
+                                                istate.data_ptr(), float(max_dist), pairs, _stream()), 'hfl_icp_correspond')
+    return partials, dist, idx
+
+
+def icp_solve(state: torch.Tensor, istate: torch.Tensor, partials: torch.Tensor, tile_offsets: torch.Tensor, n_tiles: int,
+              s_offsets: torch.Tensor, min_correspondences: int, relative_fitness: float, relative_rmse: float, is_last: bool,
+              want_sums: bool = False):
+    """`hfl_icp_solve`: the stop rules and the rigid update of every RUNNING pair, in place in state / istate.  partials: at
+    least `n_tiles` rows; tile_offsets (P + 1,) int64: the rows of every pair; s_offsets: the source offsets (the
+    denominator of the fitness).  -> sums (P, ICP_SUMS) float64 with `want_sums` (a pair that is not RUNNING keeps zeros),
+    else None."""
+    _offsets_check('icp_solve', tile_offsets)
+    _offsets_check('icp_solve', s_offsets)
+    pairs = int(s_offsets.shape[0]) - 1
+    _icp_state_check('icp_solve', state, istate, pairs)
+    _dev(partials, tile_offsets, s_offsets)
+    if tile_offsets.shape[0] != pairs + 1:
+        raise TypeError('icp_solve: (%d,) tile offsets expected' % (pairs + 1))
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < max(int(n_tiles), 1) or \
+            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
+        raise TypeError('icp_solve: contiguous (>= %d, %d) float64 partials expected' % (max(int(n_tiles), 1), ICP_SUMS))
+    sums = torch.zeros((pairs, ICP_SUMS), dtype=torch.float64, device=state.device) if want_sums else None
+    check(_native.load().hfl_icp_solve(state.data_ptr(), istate.data_ptr(), sums.data_ptr() if want_sums else None,
+                                       partials.data_ptr(), tile_offsets.data_ptr(), int(n_tiles), s_offsets.data_ptr(), pairs,
+                                       int(min_correspondences), float(relative_fitness), float(relative_rmse), int(bool(is_last)),
+                                       _stream()), 'hfl_icp_solve')
+    return sums
+
+
+VOXEL_MAX_CLOUDS = 32767             # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
 

@@ -1,0 +1,394 @@
+"""Rigid point-to-point ICP registration of a ragged batch of submap pairs, on the GPU.
+
+Retrieval names a place; the query scan is useful once it is registered against it.  `submap_overlap` aligns a ground submap
+to an aerial one by the surveyed poses alone, so its Chamfer distance mixes pose error with real disagreement between the
+clouds; `icp_refine` takes such an alignment (or the identity, for a retrieved top-1 candidate) and refines it against the
+points themselves.  The reference has no such step and open3d is not a dependency: parity with open3d's `registration_icp`
+(a float64 k-d tree search) is not claimed.  What is computed is stated here, and `icp_refine_host` is this text in numpy.
+
+    icp_refine             a batch of P pairs run to convergence on the device, one read of the results at the end
+    icp_correspondences    one evaluation: every source point's distance, target, inlier flag, and the 17 sums of a pair
+    evaluate_registration  fitness and inlier rmse of a given alignment (the k = 0 evaluation alone)
+    kabsch_update          the rigid update (R, t) of given sums
+
+Definition (DESIGN.md section 7i has the reasons).  Per pair, T_0 = init (float64 4 x 4, the identity by default;
+`SubmapOverlap.transforms` feeds in directly).  For k = 0 .. max_iterations: evaluate, decide, update.
+
+  Evaluate.  p' = fp32(T_k[:3]) . p for every ORIGINAL source point p, the fmaf chain of `hfl_transform_points`
+  (acc = fmaf(r0, x, t); acc = fmaf(r1, y, acc); fmaf(r2, z, acc)); the cloud is never moved incrementally.  j(p') is the
+  nearest target by d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in fp32, the lowest index on a tie, and d = sqrt(d2) rounded
+  once: what `hfl_nn_dist` computes.  A source point is an inlier when it has a target and d <= fp32(max_correspondence_
+  distance), compared in fp32 (the convention of `hfl_pair_stats`).  n is the inlier count, fitness_k = n / N_source,
+  rmse_k = sqrt(sum d^2 / n) with the sum in float64 over the stored fp32 d.
+
+  Stop.  The first rule that holds ends the pair, and its pose stays T_k, so the returned fitness and rmse always belong to
+  the returned pose:  n < min_correspondences: TOO_FEW, rmse = NaN;  k >= 1 and |fitness_k - fitness_{k-1}| < relative_fitness
+  and |rmse_k - rmse_{k-1}| < relative_rmse: CONVERGED;  k == max_iterations: MAX_ITERATIONS.
+
+  Update.  Over the inliers, in float64 (a product of two fp32 values is exact there): Sp = sum p', Sq = sum q, Spq = sum
+  p' q^T, q = target[j(p')].  H = Spq - Sp Sq^T / n = U S V^T;  R = V diag(1, 1, det(V U^T)) U^T;  t = Sq / n - R Sp / n;
+  T_{k+1} = [R | t] . T_k in float64.  Where the second-largest singular value of H is <= 1e-12 x the largest (collinear or
+  coincident correspondences) the pair is DEGENERATE and its pose stays T_k.  The decomposition is a one-sided cyclic Jacobi
+  with 12 sweeps over the column pairs (0,1), (0,2), (1,2) of G = H V; with u1, u2 / v1, v2 the normalised columns of G / the
+  columns of V at the two largest column norms, R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T, which is the formula above
+  without a division by the smallest singular value: det R = +1 always, and a planar cloud is no special case.
+
+`iterations` is the k at which the pair stopped: the number of updates its pose received.  An empty source cloud is TOO_FEW
+with fitness NaN (0 / 0), an empty target cloud TOO_FEW with fitness 0.
+
+Layouts are those of `overlap.py`: a list of (N_i, 3) float32 clouds or `(points (N, 3), offsets (P + 1,))`.  Coordinates
+must be finite; this is not checked.  The device functions raise `NativeLibraryError` on CPU tensors and launch on the
+current stream: an iteration is two launches (csrc/registration.hip) -- `hfl_icp_correspond` moves the source, finds the
+correspondences and reduces them to per-workgroup sums in a fixed order, `hfl_icp_solve` adds those, decides and updates --
+and the loop is max_iterations + 1 such pairs of launches with no host read; a pair that has stopped costs its workgroups
+one load.  No atomics, one writer per element: two runs give the same bits.
+
+The host twins emulate the fp32 steps (fmaf through one float64 operation rounded to fp32, which differs from a fused
+operation only by a double rounding in about one of 2^29 cases) and sum in numpy's order; the device sums run in the order
+of `hfl_pair_stats`.  The two routes therefore agree in correspondences and counts wherever no two candidates and no
+threshold lie within rounding of each other, and in poses to rounding.
+"""
+
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _native
+from .overlap import _HOST_CHUNK_PAIRS, _host_ragged, _matrices, _ragged, _same_pairs
+
+RUNNING, CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE = range(5)     # HFL_ICP_*: a pair's status
+N_SUMS = 17                            # n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2
+JACOBI_SWEEPS = 12                     # RG_SWEEPS of csrc/registration.hip
+RANK_TOL = 1e-12                       # second singular value <= RANK_TOL x the largest: DEGENERATE
+
+RegistrationResult = namedtuple('RegistrationResult', ['transforms', 'fitness', 'inlier_rmse', 'iterations', 'status'])
+RegistrationResult.__doc__ = """What `icp_refine` returns, numpy arrays on the host.  transforms: (P, 4, 4) float64, source
+frame -> target frame; fitness: (P,) float64, the share of source points with a target within the distance; inlier_rmse:
+(P,) float64 over those points, NaN where the pair is TOO_FEW; iterations: (P,) int64, the updates the pose received; status:
+(P,) int64, one of CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE."""
+
+
+# ----------------------------------------------------------------------------------------------------------------- arguments
+def _init_matrices(init, pairs, what):
+    if init is None:
+        return np.tile(np.eye(4)[:3], (pairs, 1, 1))
+    return _matrices(init, pairs, what)
+
+
+def _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse, min_correspondences, what):
+    d = float(max_correspondence_distance)
+    if not d >= 0.0:
+        raise ValueError('%s: max_correspondence_distance must be a number >= 0' % what)
+    if int(max_iterations) != max_iterations or max_iterations < 0:
+        raise ValueError('%s: max_iterations must be an integer >= 0' % what)
+    if int(min_correspondences) != min_correspondences or min_correspondences < 0:
+        raise ValueError('%s: min_correspondences must be an integer >= 0' % what)
+    return d, int(max_iterations), float(relative_fitness), float(relative_rmse), int(min_correspondences)
+
+
+def _full(m34):
+    """(P, 3, 4) -> (P, 4, 4) with the row 0 0 0 1"""
+    out = np.zeros((m34.shape[0], 4, 4), np.float64)
+    out[:, :3] = m34
+    out[:, 3, 3] = 1.0
+    return out
+
+
+# -------------------------------------------------------------------------------------------------------------- device route
+class _Batch:
+    """A batch of pairs on the device with everything an iteration needs: both clouds, their offsets, the tile table of the
+    source clouds and its per-pair offsets, the partials."""
+
+    def __init__(self, source, target, what):
+        from . import ops
+        self.s, self.s_off, _ = _ragged(source, what, True)
+        self.t, self.t_off, _ = _ragged(target, what, True)
+        _same_pairs(self.s_off, self.t_off, what)
+        self.pairs = self.s_off.shape[0] - 1
+        dev = self.s.device
+        lengths = np.diff(self.s_off)
+        tiles = ops.overlap_tiles(lengths)
+        tile_off = np.zeros(self.pairs + 1, np.int64)
+        np.cumsum(-(-lengths // ops.OVERLAP_ROWS), out=tile_off[1:])
+        self.n_tiles = int(tiles.shape[0])
+        with torch.cuda.device(dev):
+            self.s_dev, self.t_dev = torch.from_numpy(self.s_off).to(dev), torch.from_numpy(self.t_off).to(dev)
+            self.tiles, self.tile_off = torch.from_numpy(tiles).to(dev), torch.from_numpy(tile_off).to(dev)
+            self.partials = torch.zeros((max(self.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=dev)
+
+    def state(self, m34):
+        """(state, istate) on the device: the given poses, every pair RUNNING at iteration 0"""
+        st = np.zeros((self.pairs, 16), np.float64)
+        st[:, :12] = m34.reshape(self.pairs, 12)
+        return torch.from_numpy(st).to(self.s.device), torch.zeros((self.pairs, 2), dtype=torch.int32, device=self.s.device)
+
+    def correspond(self, state, istate, max_dist, want_rows=False):
+        from . import ops
+        return ops.icp_correspond(self.s, self.s_dev, self.t, self.t_dev, self.tiles, state, istate, max_dist,
+                                  partials=self.partials, want_rows=want_rows)
+
+    def solve(self, state, istate, min_corr, rel_fitness, rel_rmse, is_last, want_sums=False):
+        from . import ops
+        return ops.icp_solve(state, istate, self.partials, self.tile_off, self.n_tiles, self.s_dev, min_corr, rel_fitness,
+                             rel_rmse, is_last, want_sums=want_sums)
+
+
+def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
+               relative_rmse=1e-6, min_correspondences=3):
+    """Point-to-point ICP of P (source, target) pairs, as the module's docstring defines it -> `RegistrationResult`.  `init`:
+    (P, 4, 4) or (P, 3, 4) float64, numpy or tensor, source frame -> target frame; None is the identity.  The whole loop is
+    enqueued on the current stream without a host read; the results are read once at the end."""
+    what = 'icp_refine'
+    dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
+                                                   min_correspondences, what)
+    b = _Batch(source, target, what)
+    with torch.cuda.device(b.s.device):
+        state, istate = b.state(_init_matrices(init, b.pairs, what))
+        for k in range(iters + 1):
+            b.correspond(state, istate, dist)
+            b.solve(state, istate, min_corr, rel_f, rel_r, k == iters)
+        state, istate = state.cpu().numpy(), istate.cpu().numpy().astype(np.int64)
+    return RegistrationResult(_full(state[:, :12].reshape(-1, 3, 4)), state[:, 12].copy(), state[:, 13].copy(),
+                              istate[:, 0].copy(), istate[:, 1].copy())
+
+
+def _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences, what, want_rows):
+    dist, _, _, _, min_corr = _options(max_correspondence_distance, 0, 0.0, 0.0, min_correspondences, what)
+    b = _Batch(source, target, what)
+    with torch.cuda.device(b.s.device):
+        state, istate = b.state(_matrices(transforms, b.pairs, what))
+        _, d, j = b.correspond(state, istate, dist, want_rows=want_rows)
+        sums = b.solve(state, istate, min_corr, 0.0, 0.0, True, want_sums=True)
+    return d, j, sums, state, dist
+
+
+def icp_correspondences(source, target, transforms, max_correspondence_distance):
+    """One evaluation at the given poses, on the device: `(dist (Ns,) float32, idx (Ns,) int32, inlier (Ns,) bool, sums
+    (P, 17) float64)`.  dist and idx have the bits of `nn_distances(transform_points(source, transforms), target)`; inlier is
+    `dist <= fp32(max_correspondence_distance)` where there is a target; sums are n, Sp, Sq, Spq (row-major) and sum d^2
+    over a pair's inliers, in the device's fixed order."""
+    d, j, sums, _, dist = _evaluate(source, target, transforms, max_correspondence_distance, 0, 'icp_correspondences', True)
+    return d, j, (j >= 0) & (d <= float(np.float32(dist))), sums
+
+
+def evaluate_registration(source, target, transforms, max_correspondence_distance, min_correspondences=3):
+    """`(fitness (P,), inlier_rmse (P,))` float64 on the device: what iteration 0 of `icp_refine` reports for `init =
+    transforms`, without iterating."""
+    _, _, _, state, _ = _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences,
+                                  'evaluate_registration', False)
+    return state[:, 12].contiguous(), state[:, 13].contiguous()
+
+
+def kabsch_update(sums, min_correspondences=3):
+    """The update step of `hfl_icp_solve` on given sums (P, 17) float64 on the device -> `(R (P, 3, 3), t (P, 3), status
+    (P,) int32)` on the device.  status is RUNNING where (R, t) is the update, TOO_FEW where n < min_correspondences and
+    DEGENERATE where H has rank < 2; there R = I and t = 0."""
+    from . import ops
+    sums = torch.as_tensor(sums)
+    if not sums.is_cuda:
+        raise _native.NativeLibraryError('kabsch_update runs on the GPU and takes GPU tensors (kabsch_update_host is the CPU route)')
+    if sums.dtype != torch.float64 or sums.dim() != 2 or sums.shape[1] != N_SUMS or sums.shape[0] < 1:
+        raise TypeError('kabsch_update: (P >= 1, %d) float64 sums expected, got %s %s' % (N_SUMS, sums.dtype, tuple(sums.shape)))
+    pairs = int(sums.shape[0])
+    with torch.cuda.device(sums.device):
+        st = np.zeros((pairs, 16), np.float64)
+        st[:, :12] = np.eye(4)[:3].reshape(12)                         # (R | t) . identity = (R | t), exactly
+        state = torch.from_numpy(st).to(sums.device)
+        istate = torch.zeros((pairs, 2), dtype=torch.int32, device=sums.device)
+        one_each = torch.arange(pairs + 1, dtype=torch.int64, device=sums.device)       # one tile, one source point per pair
+        ops.icp_solve(state, istate, sums.contiguous(), one_each, pairs, one_each, int(min_correspondences), 0.0, 0.0, False)
+    pose = state[:, :12].reshape(pairs, 3, 4)
+    return pose[:, :, :3].contiguous(), pose[:, :, 3].contiguous(), istate[:, 1].contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------- host route
+def _fmaf(a, b, c):
+    """fmaf on float32 arrays: the product is exact in float64, the sum is rounded there and then to float32"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _host_move(points, m34):
+    """the fmaf chain of `hfl_transform_points` with the float32 rounding of one (3, 4) float64 pose"""
+    m = m34.astype(np.float32)
+    x, y, z = points[:, 0], points[:, 1], points[:, 2]
+    out = np.empty_like(points)
+    for c in range(3):
+        out[:, c] = _fmaf(m[c, 2], z, _fmaf(m[c, 1], y, _fmaf(m[c, 0], x, m[c, 3])))
+    return out
+
+
+def _host_nn32(q, t, chunk_pairs=_HOST_CHUNK_PAIRS // 2):
+    """(dist (n,) float32, idx (n,) int32) of one pair with the arithmetic of `hfl_nn_dist`, brute force, chunked over rows"""
+    dist = np.full(q.shape[0], np.inf, np.float32)
+    idx = np.full(q.shape[0], -1, np.int32)
+    if q.shape[0] == 0 or t.shape[0] == 0:
+        return dist, idx
+    rows = max(1, int(chunk_pairs) // t.shape[0])
+    for r0 in range(0, q.shape[0], rows):
+        c = q[r0:r0 + rows]
+        dx = c[:, None, 0] - t[None, :, 0]                              # float32 throughout
+        dy = c[:, None, 1] - t[None, :, 1]
+        dz = c[:, None, 2] - t[None, :, 2]
+        d2 = _fmaf(dz, dz, _fmaf(dy, dy, dx * dx))
+        k = d2.argmin(1)                                               # the first of equal minima: the lowest index
+        dist[r0:r0 + rows] = np.sqrt(d2[np.arange(k.shape[0]), k])     # float32 sqrt, correctly rounded
+        idx[r0:r0 + rows] = k
+    return dist, idx
+
+
+def _host_evaluate_one(src, dst, m34, max_dist32):
+    """one pair, one evaluation: (dist float32, idx int32, inlier bool, sums (17,) float64)"""
+    moved = _host_move(src, m34)
+    dist, idx = _host_nn32(moved, dst)
+    inl = (idx >= 0) & (dist <= max_dist32)
+    sums = np.zeros(N_SUMS, np.float64)
+    if inl.any():
+        p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
+        sums[0] = p.shape[0]
+        sums[1:4], sums[4:7] = p.sum(0), q.sum(0)
+        sums[7:16] = (p[:, :, None] * q[:, None, :]).sum(0).reshape(9)
+        sums[16] = (d * d).sum()
+    return dist, idx, inl, sums
+
+
+def _jacobi_rotate(g, v, p, q):
+    alpha = g[0][p] * g[0][p] + g[1][p] * g[1][p] + g[2][p] * g[2][p]
+    beta = g[0][q] * g[0][q] + g[1][q] * g[1][q] + g[2][q] * g[2][q]
+    gamma = g[0][p] * g[0][q] + g[1][p] * g[1][q] + g[2][p] * g[2][q]
+    if gamma == 0.0:
+        return
+    zeta = (beta - alpha) / (2.0 * gamma)
+    t = (1.0 if zeta >= 0.0 else -1.0) / (abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+    c = 1.0 / np.sqrt(1.0 + t * t)
+    s = c * t
+    for i in range(3):
+        gp, gq, vp, vq = g[i][p], g[i][q], v[i][p], v[i][q]
+        g[i][p], g[i][q] = c * gp - s * gq, s * gp + c * gq
+        v[i][p], v[i][q] = c * vp - s * vq, s * vp + c * vq
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def _host_kabsch_one(s):
+    """(R (3, 3), t (3,)) of one pair's sums, or None where H has rank < 2: `kabsch_solve` of csrc/registration.hip, line by
+    line, on numpy float64 scalars"""
+    with np.errstate(all='ignore'):
+        s = [np.float64(x) for x in s]
+        n = s[0]
+        g = [[s[7 + 3 * a + b] - s[1 + a] * s[4 + b] / n for b in range(3)] for a in range(3)]
+        v = [[np.float64(a == b) for b in range(3)] for a in range(3)]
+        for _ in range(JACOBI_SWEEPS):
+            _jacobi_rotate(g, v, 0, 1)
+            _jacobi_rotate(g, v, 0, 2)
+            _jacobi_rotate(g, v, 1, 2)
+        w = [np.sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]) for j in range(3)]
+        i1 = 0 if (w[0] >= w[1] and w[0] >= w[2]) else (1 if w[1] >= w[2] else 2)
+        ja, jb = (1 if i1 == 0 else 0), (1 if i1 == 2 else 2)
+        i2 = ja if w[ja] >= w[jb] else jb
+        if not w[i2] > RANK_TOL * w[i1]:
+            return None
+        u1, u2 = [g[i][i1] / w[i1] for i in range(3)], [g[i][i2] / w[i2] for i in range(3)]
+        v1, v2 = [v[i][i1] for i in range(3)], [v[i][i2] for i in range(3)]
+        u3, v3 = _cross(u1, u2), _cross(v1, v2)
+        mp, mq = [s[1 + a] / n for a in range(3)], [s[4 + a] / n for a in range(3)]
+        r = np.array([[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)], np.float64)
+        t = np.array([mq[a] - (r[a, 0] * mp[0] + r[a, 1] * mp[1] + r[a, 2] * mp[2]) for a in range(3)], np.float64)
+    return r, t
+
+
+def kabsch_update_host(sums, min_correspondences=3):
+    """`kabsch_update` on the CPU: `(R (P, 3, 3) float64, t (P, 3) float64, status (P,) int32)` numpy arrays."""
+    sums = np.asarray(sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
+    if sums.ndim != 2 or sums.shape[1] != N_SUMS or sums.shape[0] < 1:
+        raise TypeError('kabsch_update: (P >= 1, %d) float64 sums expected, got shape %s' % (N_SUMS, sums.shape))
+    pairs = sums.shape[0]
+    r, t, status = np.tile(np.eye(3), (pairs, 1, 1)), np.zeros((pairs, 3), np.float64), np.zeros(pairs, np.int32)
+    for p in range(pairs):
+        if sums[p, 0] < min_correspondences:
+            status[p] = TOO_FEW
+            continue
+        solved = _host_kabsch_one(sums[p])
+        if solved is None:
+            status[p] = DEGENERATE
+        else:
+            r[p], t[p] = solved
+    return r, t, status
+
+
+def _host_batch(source, target, what):
+    s, s_off, _ = _host_ragged(source, what)
+    t, t_off, _ = _host_ragged(target, what)
+    _same_pairs(s_off, t_off, what)
+    pairs = s_off.shape[0] - 1
+    return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
+
+
+def _host_figures(sums, n_source, min_corr):
+    """(fitness, rmse, too few) of one evaluation"""
+    n = sums[0]
+    with np.errstate(all='ignore'):
+        fitness = np.float64(n) / np.float64(n_source)                 # an empty source cloud: 0 / 0 = NaN
+        few = n < min_corr
+        rmse = np.float64(np.nan) if (few or n <= 0) else np.sqrt(sums[16] / n)
+    return float(fitness), float(rmse), bool(few)
+
+
+def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
+                    relative_rmse=1e-6, min_correspondences=3):
+    """`icp_refine` on the CPU: the module's definition in numpy, pair by pair -> `RegistrationResult`."""
+    what = 'icp_refine'
+    dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
+                                                   min_correspondences, what)
+    batch, _ = _host_batch(source, target, what)
+    pose = _init_matrices(init, len(batch), what).copy()
+    fitness, rmse = np.zeros(len(batch), np.float64), np.zeros(len(batch), np.float64)
+    iterations, status = np.zeros(len(batch), np.int64), np.zeros(len(batch), np.int64)
+    for p, (src, dst) in enumerate(batch):
+        prev = None
+        for k in range(iters + 1):
+            sums = _host_evaluate_one(src, dst, pose[p], np.float32(dist))[3]
+            fitness[p], rmse[p], few = _host_figures(sums, src.shape[0], min_corr)
+            iterations[p] = k
+            if few:
+                status[p] = TOO_FEW
+                break
+            if k >= 1 and abs(fitness[p] - prev[0]) < rel_f and abs(rmse[p] - prev[1]) < rel_r:
+                status[p] = CONVERGED
+                break
+            if k == iters:
+                status[p] = MAX_ITERATIONS
+                break
+            solved = _host_kabsch_one(sums)
+            if solved is None:
+                status[p] = DEGENERATE
+                break
+            r, t = solved
+            step = np.concatenate([r, t[:, None]], 1)                  # (R | t) . T_k, the bottom row 0 0 0 1 implied
+            pose[p] = np.concatenate([step[:, :3] @ pose[p][:, :3], (step[:, :3] @ pose[p][:, 3] + step[:, 3])[:, None]], 1)
+            prev = (fitness[p], rmse[p])
+    return RegistrationResult(_full(pose), fitness, rmse, iterations, status)
+
+
+def icp_correspondences_host(source, target, transforms, max_correspondence_distance):
+    """`icp_correspondences` on the CPU: `(dist float32, idx int32, inlier bool, sums (P, 17) float64)` numpy arrays."""
+    what = 'icp_correspondences'
+    dist = _options(max_correspondence_distance, 0, 0.0, 0.0, 0, what)[0]
+    batch, _ = _host_batch(source, target, what)
+    m = _matrices(transforms, len(batch), what)
+    parts = [_host_evaluate_one(src, dst, m[p], np.float32(dist)) for p, (src, dst) in enumerate(batch)]
+    return (np.concatenate([x[0] for x in parts]), np.concatenate([x[1] for x in parts]), np.concatenate([x[2] for x in parts]),
+            np.stack([x[3] for x in parts]))
+
+
+def evaluate_registration_host(source, target, transforms, max_correspondence_distance, min_correspondences=3):
+    """`evaluate_registration` on the CPU: `(fitness (P,), inlier_rmse (P,))` float64 numpy arrays."""
+    what = 'evaluate_registration'
+    dist, _, _, _, min_corr = _options(max_correspondence_distance, 0, 0.0, 0.0, min_correspondences, what)
+    batch, _ = _host_batch(source, target, what)
+    m = _matrices(transforms, len(batch), what)
+    figures = [_host_figures(_host_evaluate_one(src, dst, m[p], np.float32(dist))[3], src.shape[0], min_corr)
+               for p, (src, dst) in enumerate(batch)]
+    return np.array([f[0] for f in figures], np.float64), np.array([f[1] for f in figures], np.float64)

@@ -1154,6 +1154,48 @@ int hfl_pair_stats(double* sums, int64_t* counts, const float* dist, const int64
                    const float* taus, int n_taus, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11f. Rigid point-to-point ICP registration of submap pairs (csrc/registration.hip; the "6-DoF metric localisation" step
+ *      that follows retrieval; no counterpart in the reference).  Definition: hotformerloc_amd/registration.py, DESIGN.md
+ *      section 7i.
+ * ---------------------------------------------------------------------- */
+/* The float64 quantities a workgroup of hfl_icp_correspond reduces its inlier rows to: n, Sp (3), Sq (3), Spq (9, row-major,
+ * p' down and q across), sum d^2; and what a pair's status says. */
+#define HFL_ICP_SUMS 17
+#define HFL_ICP_RUNNING 0
+#define HFL_ICP_CONVERGED 1
+#define HFL_ICP_MAX_ITERATIONS 2
+#define HFL_ICP_TOO_FEW 3
+#define HFL_ICP_DEGENERATE 4
+/* Both take the ragged batches of section 11e (source and target clouds of P pairs, DEVICE offsets, clamped to the arrays)
+ * and the state of the P pairs in two DEVICE arrays: state (P, 16) float64 = the pose as a row-major 3 x 4 (R | t), fitness,
+ * rmse, previous fitness, previous rmse; istate (P, 2) int32 = iterations, status.  A pair whose status is not
+ * HFL_ICP_RUNNING is left alone by both.  No atomics, one writer per output element, a fixed evaluation order: two runs give
+ * the same bits.  One launch each on `stream`, no synchronisation, no host read.  A NULL pointer (but for the outputs named
+ * optional), a negative count or P < 1: HFL_EINVAL; P, the tiles or the targets at 2^31 or more: HFL_ECAPACITY. */
+/* One evaluation.  Every source row of a RUNNING pair p is moved by the fp32 rounding of the pair's pose with the fmaf chain
+ * of hfl_transform_points, and its nearest target is found exactly as hfl_nn_dist finds it (the same bits; tiles is that
+ * function's table, built from the source offsets).  dist and idx are optional: where not NULL they receive what
+ * hfl_nn_dist would write for the moved cloud.  A row is an inlier when it has a target and dist <= max_dist, compared in
+ * fp32.  partials (n_tiles, HFL_ICP_SUMS) float64: row i holds the sums over the inlier rows of tile i -- a thread adds its
+ * rows in row order, a wave its lanes by the xor butterfly 32 .. 1, the four waves are added in wave order.  The rows of a
+ * pair that is not RUNNING are not written. */
+int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
+                       int64_t n_source, const float* targets, const int64_t* t_offsets, int64_t n_targets,
+                       const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate, float max_dist,
+                       int64_t n_pairs, hfl_stream_t stream);
+/* One decision and update per RUNNING pair p, one wave each, in float64.  The pair's partials, rows [tile_offsets[p],
+ * tile_offsets[p + 1]) (DEVICE, (P + 1) int64), are added in ascending order; sums (P, HFL_ICP_SUMS) is optional and
+ * receives them.  With k = iterations, n the inlier count and N = s_offsets[p + 1] - s_offsets[p]: fitness = n / N and
+ * rmse = sqrt(sum d^2 / n) are stored; n < min_correspondences: rmse = NaN, status TOO_FEW; k >= 1 and |fitness - previous
+ * fitness| < relative_fitness and |rmse - previous rmse| < relative_rmse: CONVERGED; is_last != 0: MAX_ITERATIONS;
+ * otherwise H = Spq - Sp Sq^T / n is decomposed by a one-sided cyclic Jacobi of fixed sweep count, R = V diag(1, 1,
+ * det(V U^T)) U^T, t = Sq / n - R Sp / n, and pose <- (R | t) . pose, iterations <- k + 1, previous <- (fitness, rmse); a
+ * second singular value <= 1e-12 x the largest: DEGENERATE, pose unchanged. */
+int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials, const int64_t* tile_offsets,
+                  int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs, int min_correspondences, double relative_fitness,
+                  double relative_rmse, int is_last, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
