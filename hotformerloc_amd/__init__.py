@@ -4,7 +4,8 @@ Public surface (mirrors the reference's): `model_factory`, `ModelParams`, `Octre
 `merge_octrees`, and the `dwconv` op module.  See DESIGN.md / INTEGRATION.md.
 
 Raw-submap post-processing on the device (the reference's open3d / CSF toolkit): `trim_radius`, `remove_outliers` (and
-`knn_mean_distance`, the exact k-nearest-neighbour mean distance behind it), `remove_ground`, `voxel_downsample` /
+`knn_mean_distance`, the exact k-nearest-neighbour mean distance behind it; `estimate_normals` on the same search),
+`remove_ground`, `voxel_downsample` /
 `pnvlad_downsample` / `random_downsample`, `normalise_submaps`, chained by `prepare_submaps` / `prepare_submaps_fixed`;
 every step has a numpy `*_host` twin that states its definition.
 """
@@ -38,6 +39,7 @@ from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_
                       chamfer_distance_host, overlap_ratio_host, submap_overlap_host, ChamferResult, SubmapOverlap)
 from .registration import (icp_refine, icp_refine_host, icp_correspondences, icp_correspondences_host,  # noqa: F401,E402
                            evaluate_registration, evaluate_registration_host, kabsch_update, kabsch_update_host,
-                           RegistrationResult)
+                           plane_update, plane_update_host, RegistrationResult)
+from .normals import estimate_normals, estimate_normals_host                                            # noqa: F401,E402
 
 __version__ = '0.1.0'

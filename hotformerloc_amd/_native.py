@@ -151,6 +151,7 @@ SIGNATURES = {
     'hfl_cloud_nonfinite': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'hfl_knn_cell_keys': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     'hfl_knn_mean_dist': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    'hfl_knn_normals': (c_int, [c_void_p] * 11 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     'hfl_outlier_threshold': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_double, c_void_p]),
     'hfl_outlier_mask': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'hfl_radius_mask': (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
@@ -260,6 +261,11 @@ SIGNATURES = {
                                    c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     'hfl_icp_solve': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double,
                               c_double, c_int, c_void_p]),
+    'hfl_icp_correspond_plane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64,
+                                         c_void_p]),
+    'hfl_icp_solve_plane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                    c_double, c_double, c_int, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

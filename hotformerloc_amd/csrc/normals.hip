@@ -1,0 +1,281 @@
+// Surface normals and the surface variation of every point of a ragged batch of clouds: the covariance of the point's k
+// nearest neighbours and its smallest eigenvector (open3d's estimate_normals with KDTreeSearchParamKNN, plus a curvature).
+// The estimate is DEFINED in hotformerloc_amd/normals.py (module docstring) and DESIGN.md section 7j; this file and the
+// numpy route there follow that definition.  The search is the exact grid search of csrc/outliers.hip (knn_common.h), on
+// the batch that `outliers.sorted_batch` lays out; what is new is the accumulation on top of it.
+//
+//   hfl_knn_normals   (1) the dense cell-start table (knn_cell_starts_kernel); (2) one thread per point in sorted order
+//                     scans the 3 x 3 x 3 block of cells round its own twice: the first scan keeps the K smallest fp32
+//                     squared distances in the sorted register list and gives r2, the k-th smallest; when r2 lies strictly
+//                     below the square of the conservative distance to the nearest face with cells behind it, every point
+//                     with d2 <= r2 is in the block, and the second scan adds, in float64 and in sorted-position order, the
+//                     count, sum e and sum e e^T of e = p_j - p_i over those points; else the point is appended to a list;
+//                     (3) a wave per listed point scans the point's whole cloud twice: r2 by the merge of the 64 lists, then
+//                     the sums, a lane's points in ascending order and the lanes by the xor butterfly 32 .. 1.
+//                     Whoever holds the sums finishes: C = S2 / m - (S1 / m)(S1 / m)^T, a one-sided cyclic Jacobi of fixed
+//                     sweep count, the eigenvalues in order, the degenerate rule, the sign rule, three stores at perm[j].
+//
+// The neighbourhood { j : d2(i, j) <= r2 } is a pure function of the input, so counts are the same for any grid; the
+// float64 sums run in an order that follows the sort and the grid, fixed for given inputs: two runs give the same bits.  No
+// floating-point atomics (one integer add per wave appends to the list); no workgroup waits for another.
+#include <math.h>
+
+#include "jacobi3.h"
+#include "knn_common.h"
+
+namespace {
+
+constexpr int NR_SWEEPS = 12;                                    // RG_SWEEPS of registration.hip
+constexpr double NR_RANK_TOL = 1e-12;                            // middle eigenvalue <= this x the largest: no normal
+constexpr int NR_SUMS = 9;                                       // S1 (3), S2 (xx, xy, xz, yy, yz, zz)
+
+// one neighbour's contribution, e = p_j - p_i in float64
+__device__ __forceinline__ void normal_add(double (&s)[NR_SUMS], float px, float py, float pz, const float* __restrict__ q) {
+  const double ex = (double)q[0] - (double)px, ey = (double)q[1] - (double)py, ez = (double)q[2] - (double)pz;
+  s[0] += ex;
+  s[1] += ey;
+  s[2] += ez;
+  s[3] += ex * ex;
+  s[4] += ex * ey;
+  s[5] += ex * ez;
+  s[6] += ey * ey;
+  s[7] += ey * ez;
+  s[8] += ez * ez;
+}
+
+// steps 3 to 7 of the definition for one point: from the sums over its m neighbours to the stores at `row`
+__device__ void normal_finish(float* __restrict__ normals, float* __restrict__ curvature, int32_t* __restrict__ counts,
+                              int64_t row, int64_t n, const double (&s)[NR_SUMS], int m, float px, float py, float pz,
+                              const double* __restrict__ view) {
+  if (row < 0 || row >= n) return;
+  double nx = 0.0, ny = 0.0, nz = 0.0, curv = 0.0;
+  if (m >= 3) {
+    const double dm = (double)m;
+    const double mu[3] = {s[0] / dm, s[1] / dm, s[2] / dm};
+    double g[3][3], v[3][3];
+    g[0][0] = s[3] / dm - mu[0] * mu[0];
+    g[0][1] = s[4] / dm - mu[0] * mu[1];
+    g[0][2] = s[5] / dm - mu[0] * mu[2];
+    g[1][1] = s[6] / dm - mu[1] * mu[1];
+    g[1][2] = s[7] / dm - mu[1] * mu[2];
+    g[2][2] = s[8] / dm - mu[2] * mu[2];
+    g[1][0] = g[0][1];
+    g[2][0] = g[0][2];
+    g[2][1] = g[1][2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) v[a][b] = a == b ? 1.0 : 0.0;
+    // G = C V with orthogonal columns: their norms are the eigenvalues of the positive semi-definite C, V's columns the
+    // eigenvectors
+    for (int sweep = 0; sweep < NR_SWEEPS; ++sweep) {
+      jacobi_rotate<0, 1>(g, v);
+      jacobi_rotate<0, 2>(g, v);
+      jacobi_rotate<1, 2>(g, v);
+    }
+    double w[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) w[j] = sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]);
+    // the largest, then the larger of the other two, the lowest column on a tie
+    const int i2 = (w[0] >= w[1] && w[0] >= w[2]) ? 0 : (w[1] >= w[2] ? 1 : 2);
+    const int ja = i2 == 0 ? 1 : 0, jb = i2 == 2 ? 1 : 2;
+    const int i1 = w[ja] >= w[jb] ? ja : jb, i0 = w[ja] >= w[jb] ? jb : ja;
+    const double l0 = i0 == 0 ? w[0] : (i0 == 1 ? w[1] : w[2]);
+    const double l1 = i1 == 0 ? w[0] : (i1 == 1 ? w[1] : w[2]);
+    const double l2 = i2 == 0 ? w[0] : (i2 == 1 ? w[1] : w[2]);
+    if (l1 > NR_RANK_TOL * l2) {                                 // false for a NaN and for C = 0 as well
+      nx = pick(v, 0, i0);
+      ny = pick(v, 1, i0);
+      nz = pick(v, 2, i0);
+      const double sum = (l0 + l1) + l2;
+      curv = sum > 0.0 ? l0 / sum : 0.0;
+      // one number decides the sign in either mode: n . (viewpoint - p), or the first of n_z, n_y, n_x that is not zero
+      double facing = nz != 0.0 ? nz : (ny != 0.0 ? ny : nx);
+      if (view != nullptr)
+        facing = (nx * (view[0] - (double)px) + ny * (view[1] - (double)py)) + nz * (view[2] - (double)pz);
+      const double turn = facing < 0.0 ? -1.0 : 1.0;             // a product by +-1 is exact
+      nx *= turn;
+      ny *= turn;
+      nz *= turn;
+    }
+  }
+  normals[row * 3 + 0] = (float)nx;
+  normals[row * 3 + 1] = (float)ny;
+  normals[row * 3 + 2] = (float)nz;
+  curvature[row] = (float)curv;
+  counts[row] = m;
+}
+
+template <int K>
+__global__ void __launch_bounds__(kOutThreads)
+normals_query_kernel(float* __restrict__ normals, float* __restrict__ curvature, int32_t* __restrict__ counts,
+                     int32_t* __restrict__ pending, int32_t* __restrict__ counter, const float* __restrict__ spts,
+                     const int64_t* __restrict__ skeys, const int64_t* __restrict__ perm, const int32_t* __restrict__ starts,
+                     const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, const double* __restrict__ views,
+                     int batch, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (j >= n) return;
+  const int c = find_cloud(off, batch, j);
+  const hfl_knn_grid g = grids[c];
+  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
+  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+  const int64_t local = skeys[j] - g.cell_base;
+  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
+  const int k = g.k;
+  bool resolved = false;
+  if (local >= 0 && local < cells && k >= 1 && k <= K) {       // a key off its own grid goes to the whole-cloud scan
+    const int ix = (int)(local % g.nx), iy = (int)((local / g.nx) % g.ny), iz = (int)(local / ((int64_t)g.nx * g.ny));
+    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
+    const int y0 = max(iy - 1, 0), y1 = min(iy + 1, g.ny - 1);
+    const int z0 = max(iz - 1, 0), z1 = min(iz + 1, g.nz - 1);
+    KnnList<K> list;
+    list.clear();
+#pragma unroll 1
+    for (int z = z0; z <= z1; ++z)
+#pragma unroll 1
+      for (int y = y0; y <= y1; ++y) {
+        const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;      // the cells x0 .. x1 of a line are adjacent
+        const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
+#pragma unroll 1
+        for (int32_t q = s; q < e; ++q) list.insert(knn_d2(px, py, pz, spts + (int64_t)q * 3));
+      }
+    float gap = knn_face_gap(px, g.ox, g.cell, x0, x1, g.nx - 1, g.mx);
+    gap = fminf(gap, knn_face_gap(py, g.oy, g.cell, y0, y1, g.ny - 1, g.my));
+    gap = fminf(gap, knn_face_gap(pz, g.oz, g.cell, z0, z1, g.nz - 1, g.mz));
+    gap = __fmul_rn(fmaxf(gap, 0.f), kFaceShrink);
+    const float r2 = list.kth(k);
+    resolved = r2 < __fmul_rn(gap, gap);
+    if (resolved) {                                            // the list is dead from here on: the sums take its registers
+      double sums[NR_SUMS];
+#pragma unroll
+      for (int i = 0; i < NR_SUMS; ++i) sums[i] = 0.0;
+      int m = 0;
+#pragma unroll 1
+      for (int z = z0; z <= z1; ++z)
+#pragma unroll 1
+        for (int y = y0; y <= y1; ++y) {
+          const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;
+          const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
+#pragma unroll 1
+          for (int32_t q = s; q < e; ++q) {                    // sorted-position order
+            const float* w = spts + (int64_t)q * 3;
+            if (knn_d2(px, py, pz, w) <= r2) {
+              normal_add(sums, px, py, pz, w);
+              ++m;
+            }
+          }
+        }
+      normal_finish(normals, curvature, counts, perm[j], n, sums, m, px, py, pz,
+                    views != nullptr ? views + 3 * (int64_t)c : nullptr);
+    }
+  }
+  if (!resolved) {                                             // one integer add per wave; the order of the list is free
+    const unsigned long long mask = __ballot(1);
+    const int lane = threadIdx.x & (HFL_WAVE - 1);
+    const int leader = __ffsll((long long)mask) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(counter, __popcll(mask));
+    base = __shfl(base, leader, HFL_WAVE);
+    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+    if (slot >= 0 && slot < n) pending[slot] = (int32_t)j;
+  }
+}
+
+// a wave per pending point, the waves striding over the list; every loop bound is the same in all lanes of a wave
+template <int K>
+__global__ void __launch_bounds__(kOutThreads)
+normals_fallback_kernel(float* __restrict__ normals, float* __restrict__ curvature, int32_t* __restrict__ counts,
+                        const int32_t* __restrict__ pending, const int32_t* __restrict__ counter,
+                        const float* __restrict__ spts, const int64_t* __restrict__ perm,
+                        const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off,
+                        const double* __restrict__ views, int batch, int64_t n) {
+  const int lane = threadIdx.x & (HFL_WAVE - 1);
+  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
+  const int64_t count = min((int64_t)max(*counter, 0), n);
+  for (int64_t e = wave; e < count; e += waves) {
+    const int64_t j = pending[e];
+    if (j < 0 || j >= n) continue;
+    const int c = find_cloud(off, batch, j);
+    const int64_t first = max(off[c], (int64_t)0), last = min(off[c + 1], n);
+    const int k = min(max(grids[c].k, 1), K);
+    const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
+    float r2 = INFINITY;
+    {
+      KnnList<K> list;
+      list.clear();
+      for (int64_t q = first + lane; q < last; q += HFL_WAVE) list.insert(knn_d2(px, py, pz, spts + q * 3));
+      for (int r = 0; r < k; ++r) {                            // ascending: the smallest head of the 64 lists, k times
+        const float head = list.v[0];
+        float m = head;
+#pragma unroll
+        for (int s = HFL_WAVE / 2; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, HFL_WAVE));
+        const unsigned long long owners = __ballot(head == m);
+        if (lane == __ffsll((long long)owners) - 1) list.pop();  // one lane gives up one copy: equal values stay a multiset
+        r2 = m;                                                // after k rounds: the k-th smallest
+      }
+    }
+    double sums[NR_SUMS];
+#pragma unroll
+    for (int i = 0; i < NR_SUMS; ++i) sums[i] = 0.0;
+    int m = 0;
+    for (int64_t q = first + lane; q < last; q += HFL_WAVE) {  // a lane's points in ascending order
+      const float* w = spts + q * 3;
+      if (knn_d2(px, py, pz, w) <= r2) {
+        normal_add(sums, px, py, pz, w);
+        ++m;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NR_SUMS; ++i) sums[i] = wave_sum(sums[i]);
+    m = wave_sum(m);
+    if (lane == 0)
+      normal_finish(normals, curvature, counts, perm[j], n, sums, m, px, py, pz,
+                    views != nullptr ? views + 3 * (int64_t)c : nullptr);
+  }
+}
+
+template <int K>
+int normals_launch(float* normals, float* curvature, int32_t* counts, int32_t* pending, int32_t* counter, int32_t* starts,
+                   const float* spts, const int64_t* skeys, const int64_t* perm, const hfl_knn_grid* grids, const int64_t* off,
+                   const double* views, int batch, int64_t n, int64_t n_cells, int phases, hipStream_t s) {
+  if (phases & HFL_KNN_PHASE_STARTS)
+    knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
+  if (phases & HFL_KNN_PHASE_QUERY) {
+    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return (int)e;
+    normals_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+        normals, curvature, counts, pending, counter, spts, skeys, perm, starts, grids, off, views, batch, n);
+  }
+  if (phases & HFL_KNN_PHASE_FALLBACK) {
+    const int64_t blocks = min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
+    normals_fallback_kernel<K><<<(unsigned)blocks, kOutThreads, 0, s>>>(normals, curvature, counts, pending, counter, spts,
+                                                                        perm, grids, off, views, batch, n);
+  }
+  HFL_RETURN_LAST_ERROR();
+}
+
+}  // namespace
+
+extern "C" int hfl_knn_normals(float* normals, float* curvature, int32_t* counts, int32_t* pending, int32_t* counter,
+                               int32_t* cell_starts, const float* sorted_points, const int64_t* sorted_keys,
+                               const int64_t* perm, const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch,
+                               int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points, const double* viewpoints,
+                               int phases, hfl_stream_t stream) {
+  if (normals == nullptr || curvature == nullptr || counts == nullptr || pending == nullptr || counter == nullptr ||
+      cell_starts == nullptr || sorted_points == nullptr || sorted_keys == nullptr || perm == nullptr ||
+      grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
+    return HFL_EINVAL;
+  if (batch < 1 || n_points < batch || n_cells < 1 || phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  int k_max = 0;
+  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (k_max <= 8)
+    return normals_launch<8>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
+                             cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
+  if (k_max <= 16)
+    return normals_launch<16>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
+                              cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
+  return normals_launch<32>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
+                            cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
+}

@@ -1,4 +1,4 @@
-// Rigid point-to-point ICP for a ragged batch of P (source, target) pairs: the definition is in
+// Rigid ICP, point-to-point and point-to-plane, for a ragged batch of P (source, target) pairs: the definition is in
 // hotformerloc_amd/registration.py and DESIGN.md section 7i.  The layout is that of overlap.hip: the points of all clouds
 // concatenated as (N, 3) fp32 with (P + 1) int64 offsets.  One iteration is two launches, and a whole batch runs to
 // convergence without a host read: the state of a pair lives in two plain device arrays,
@@ -27,9 +27,17 @@
 // which is V diag(1, 1, det(V U^T)) U^T without ever dividing by the smallest singular value: det R = +1 whether or not the
 // unconstrained optimum is a reflection, and a planar cloud needs no special case.
 //
+// hfl_icp_correspond_plane / hfl_icp_solve_plane: the point-to-plane estimator, the same two kernels
+// instantiated with PLANE.  The scan, dist, idx and the inlier rule are the same text; the winner's normal nq is read from
+// global memory beside its coordinates, and the sums are the 29 float64 quantities
+//     n, sum d^2, g = sum J r (6), the upper triangle of A = sum J J^T row-major (21),   r = (p' - q) . nq, J = (p' x nq, nq),
+// reduced in the same order.  The solve factorises A = L D L^T without pivoting in a fixed order, solves A x = -g for
+// x = (alpha, beta, gamma, tx, ty, tz) and builds R = Rz(gamma) Ry(beta) Rx(alpha): det R = +1 by construction.
+//
 // No atomics; every output element has one writer and a fixed evaluation order: two runs give the same bits.
 #include <math.h>
 
+#include "jacobi3.h"
 #include "ragged_common.h"
 
 namespace {
@@ -39,23 +47,31 @@ constexpr int RG_ROWS = HFL_OVERLAP_ROWS;                        // source rows 
 constexpr int RG_QPT = RG_ROWS / RG_THREADS;                     // source points a thread keeps in registers
 constexpr int RG_TILE = HFL_OVERLAP_TILE;                        // target points of an LDS tile
 constexpr int RG_SUMS = HFL_ICP_SUMS;
+constexpr int RG_PLANE_SUMS = HFL_ICP_PLANE_SUMS;
 constexpr int RG_WAVES = RG_THREADS / HFL_WAVE;
 constexpr int RG_SWEEPS = 12;                                    // a 3 x 3 converges quadratically: 5 or 6 suffice
 constexpr double RG_RANK_TOL = 1e-12;                            // second singular value <= this x the largest: degenerate
+constexpr double RG_PIVOT_TOL = 1e-12;                           // a pivot of the LDL^T <= this x its diagonal entry: degenerate
 static_assert(RG_ROWS % RG_THREADS == 0 && RG_QPT >= 1, "whole source points per thread");
 // 3 x 2048 x 4 B = 24 KiB of static LDS as in nn_dist_kernel; the wave results of the reduction reuse the x plane
 static_assert(RG_TILE % 4 == 0 && RG_TILE * 12 <= 32 * 1024, "static LDS stays at 32 KiB or less");
 static_assert(RG_WAVES * RG_SUMS * sizeof(double) <= RG_TILE * sizeof(float), "the wave results fit the x plane");
+static_assert(RG_WAVES * RG_PLANE_SUMS * sizeof(double) <= RG_TILE * sizeof(float), "the wave results fit the x plane");
 static_assert(RG_SUMS == 17, "n, Sp, Sq, Spq, sum d^2");
+static_assert(RG_PLANE_SUMS == 29, "n, sum d^2, g, the upper triangle of A");
 
 // six waves per SIMD, the residency of nn_dist_kernel (six workgroups of 24 KiB per CU): 80 VGPRs, which the reduction's 17
-// float64 sums beside the gathered coordinates would otherwise exceed by two
-__global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(6)))
+// float64 sums beside the gathered coordinates would otherwise exceed by two.  PLANE is the point-to-plane estimator: the
+// same scan, the winner's normal gathered beside its coordinates, 29 sums; those do not fit 80 VGPRs, so that instantiation
+// asks for four waves per SIMD.
+template <bool PLANE>
+__global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(PLANE ? 4 : 6)))
 icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, int32_t* __restrict__ idx,
                       const float* __restrict__ source, const int64_t* __restrict__ s_off, int64_t n_source,
-                      const float* __restrict__ targets, const int64_t* __restrict__ t_off, int64_t n_targets,
-                      const int64_t* __restrict__ tiles, const double* __restrict__ state,
-                      const int32_t* __restrict__ istate, float max_dist, int n_pairs) {
+                      const float* __restrict__ targets, const float* __restrict__ t_normals,
+                      const int64_t* __restrict__ t_off, int64_t n_targets, const int64_t* __restrict__ tiles,
+                      const double* __restrict__ state, const int32_t* __restrict__ istate, float max_dist, int n_pairs) {
+  constexpr int NS = PLANE ? RG_PLANE_SUMS : RG_SUMS;
   __shared__ __align__(16) float s_x[RG_TILE], s_y[RG_TILE], s_z[RG_TILE];
   const int64_t p = tiles[2 * (int64_t)blockIdx.x], row0 = tiles[2 * (int64_t)blockIdx.x + 1];
   if (p < 0 || p >= n_pairs || row0 < 0) return;                 // uniform over the workgroup
@@ -124,9 +140,9 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
     }
   }
 
-  double acc[RG_SUMS];
+  double acc[NS];
 #pragma unroll
-  for (int k = 0; k < RG_SUMS; ++k) acc[k] = 0.0;
+  for (int k = 0; k < NS; ++k) acc[k] = 0.0;
 #pragma unroll
   for (int r = 0; r < RG_QPT; ++r) {                             // a thread's rows in row order
     const int64_t row = row0 + r * RG_THREADS + threadIdx.x;
@@ -140,57 +156,54 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
         const double qc[3] = {(double)w[0], (double)w[1], (double)w[2]};
         const double dd = (double)d;
         acc[0] += 1.0;
+        if constexpr (PLANE) {
+          // the normal at the winner, read once per source row; r, a = p' x n and J = (a, n) with every operation rounded
+          // once, so the rows are the host route's to the bit and only the order of the sums differs
+          const float* v = t_normals + 3 * (t_begin + at[r]);
+          const double nc[3] = {(double)v[0], (double)v[1], (double)v[2]};
+          const double res = __dadd_rn(__dadd_rn(__dmul_rn(__dsub_rn(pc[0], qc[0]), nc[0]),
+                                                 __dmul_rn(__dsub_rn(pc[1], qc[1]), nc[1])),
+                                       __dmul_rn(__dsub_rn(pc[2], qc[2]), nc[2]));
+          const double jac[6] = {__dsub_rn(__dmul_rn(pc[1], nc[2]), __dmul_rn(pc[2], nc[1])),
+                                 __dsub_rn(__dmul_rn(pc[2], nc[0]), __dmul_rn(pc[0], nc[2])),
+                                 __dsub_rn(__dmul_rn(pc[0], nc[1]), __dmul_rn(pc[1], nc[0])), nc[0], nc[1], nc[2]};
+          acc[1] += dd * dd;
+          int slot = 8;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          acc[1 + a] += pc[a];
-          acc[4 + a] += qc[a];
+          for (int a = 0; a < 6; ++a) {
+            acc[2 + a] += jac[a] * res;
 #pragma unroll
-          for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += pc[a] * qc[b];
+            for (int b = a; b < 6; ++b) acc[slot++] += jac[a] * jac[b];     // a zero normal adds zeros
+          }
+        } else {
+#pragma unroll
+          for (int a = 0; a < 3; ++a) {
+            acc[1 + a] += pc[a];
+            acc[4 + a] += qc[a];
+#pragma unroll
+            for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += pc[a] * qc[b];
+          }
+          acc[16] += dd * dd;
         }
-        acc[16] += dd * dd;
       }
     }
   }
 
-  double* red = reinterpret_cast<double*>(s_x);                  // (RG_WAVES, RG_SUMS)
+  double* red = reinterpret_cast<double*>(s_x);                  // (RG_WAVES, NS)
   const int lane = threadIdx.x & (HFL_WAVE - 1), wave = threadIdx.x / HFL_WAVE;
 #pragma unroll
-  for (int k = 0; k < RG_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < NS; ++k) acc[k] = wave_sum(acc[k]);
   __syncthreads();                                               // the last tile has been read by every wave
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < RG_SUMS; ++k) red[wave * RG_SUMS + k] = acc[k];
+    for (int k = 0; k < NS; ++k) red[wave * NS + k] = acc[k];
   }
   __syncthreads();
-  if (threadIdx.x < RG_SUMS) {
+  if (threadIdx.x < NS) {
     double v = red[threadIdx.x];
-    for (int w = 1; w < RG_WAVES; ++w) v += red[w * RG_SUMS + threadIdx.x];
-    partials[(int64_t)blockIdx.x * RG_SUMS + threadIdx.x] = v;
+    for (int w = 1; w < RG_WAVES; ++w) v += red[w * NS + threadIdx.x];
+    partials[(int64_t)blockIdx.x * NS + threadIdx.x] = v;
   }
-}
-
-// columns P and Q of G = H V made orthogonal by one plane rotation, applied to V as well
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&g)[3][3], double (&v)[3][3]) {
-  const double alpha = g[0][P] * g[0][P] + g[1][P] * g[1][P] + g[2][P] * g[2][P];
-  const double beta = g[0][Q] * g[0][Q] + g[1][Q] * g[1][Q] + g[2][Q] * g[2][Q];
-  const double gamma = g[0][P] * g[0][Q] + g[1][P] * g[1][Q] + g[2][P] * g[2][Q];
-  if (gamma == 0.0) return;
-  const double zeta = (beta - alpha) / (2.0 * gamma);
-  const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));    // zeta = +-inf: t = 0
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double gp = g[i][P], gq = g[i][Q], vp = v[i][P], vq = v[i][Q];
-    g[i][P] = c * gp - s * gq;
-    g[i][Q] = s * gp + c * gq;
-    v[i][P] = c * vp - s * vq;
-    v[i][Q] = s * vp + c * vq;
-  }
-}
-
-__device__ __forceinline__ double pick(const double (&a)[3][3], int i, int j) {
-  return j == 0 ? a[i][0] : (j == 1 ? a[i][1] : a[i][2]);
 }
 
 // the rigid update (R | t) of the 17 sums; false where the correspondences are collinear or coincident
@@ -238,21 +251,89 @@ __device__ bool kabsch_solve(const double* s, double (&r)[3][3], double (&t)[3])
   return true;
 }
 
+// the point-to-plane update (R | t) of the 29 sums: A x = -g by an LDL^T factorisation without pivoting in a fixed operation
+// order, x = (alpha, beta, gamma, tx, ty, tz), R = Rz(gamma) Ry(beta) Rx(alpha); false where a pivot is <= RG_PIVOT_TOL x
+// its diagonal entry (the correspondences do not determine the six unknowns) or not a number.  Every loop unrolls, so no
+// array is indexed by a run-time value.
+__device__ bool plane_solve(const double* s, double (&r)[3][3], double (&t)[3]) {
+  double a[6][6], d[6], x[6];                                    // the lower triangle of `a` becomes L
+  {
+    int slot = 8;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) {
+        a[i][j] = s[slot];
+        a[j][i] = s[slot++];
+      }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double diag = a[j][j];
+    double dj = diag;
+#pragma unroll
+    for (int k = 0; k < j; ++k) dj -= a[j][k] * a[j][k] * d[k];
+    if (!(dj > RG_PIVOT_TOL * diag)) ok = false;
+    d[j] = dj;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double v = a[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= a[i][k] * a[j][k] * d[k];
+      a[i][j] = v / dj;
+    }
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {                                  // L y = -g
+    double v = -s[2 + i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= a[i][k] * x[k];
+    x[i] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = x[i] / d[i];
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {                                 // L^T x = z
+    double v = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) v -= a[k][i] * x[k];
+    x[i] = v;
+  }
+  const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+  r[0][0] = cb * cg;
+  r[0][1] = sa * sb * cg - ca * sg;
+  r[0][2] = ca * sb * cg + sa * sg;
+  r[1][0] = cb * sg;
+  r[1][1] = sa * sb * sg + ca * cg;
+  r[1][2] = ca * sb * sg - sa * cg;
+  r[2][0] = -sb;
+  r[2][1] = sa * cb;
+  r[2][2] = ca * cb;
+  t[0] = x[3];
+  t[1] = x[4];
+  t[2] = x[5];
+  return true;
+}
+
+template <bool PLANE>
 __global__ void __launch_bounds__(HFL_WAVE)
 icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, double* __restrict__ sums,
                  const double* __restrict__ partials, const int64_t* __restrict__ tile_off, int64_t n_tiles,
                  const int64_t* __restrict__ s_off, int min_corr, double rel_fitness, double rel_rmse, int is_last) {
   const int64_t p = blockIdx.x;
   if (istate[2 * p + 1] != HFL_ICP_RUNNING) return;              // uniform: one wave per pair
+  constexpr int NS = PLANE ? RG_PLANE_SUMS : RG_SUMS, SUM_D2 = PLANE ? 1 : 16;
   const int lane = threadIdx.x;
   const int64_t first = max(tile_off[p], (int64_t)0), last = min(tile_off[p + 1], n_tiles);
   double mine = 0.0;
-  if (lane < RG_SUMS)
-    for (int64_t tile = first; tile < last; ++tile) mine += partials[tile * RG_SUMS + lane];   // ascending tile order
-  if (sums != nullptr && lane < RG_SUMS) sums[p * RG_SUMS + lane] = mine;
-  double s[RG_SUMS];
+  if (lane < NS)
+    for (int64_t tile = first; tile < last; ++tile) mine += partials[tile * NS + lane];        // ascending tile order
+  if (sums != nullptr && lane < NS) sums[p * NS + lane] = mine;
+  double s[NS];
 #pragma unroll
-  for (int k = 0; k < RG_SUMS; ++k) s[k] = __shfl(mine, k, HFL_WAVE);
+  for (int k = 0; k < NS; ++k) s[k] = __shfl(mine, k, HFL_WAVE);
   if (lane != 0) return;
 
   double* st = state + 16 * p;
@@ -260,7 +341,7 @@ icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, doubl
   const double n = s[0], n_src = (double)max(s_off[p + 1] - s_off[p], (int64_t)0);
   const double fitness = n / n_src;                              // an empty source cloud: 0 / 0 = NaN
   const bool few = n < (double)min_corr;
-  const double rmse = (few || n <= 0.0) ? (double)NAN : sqrt(s[16] / n);
+  const double rmse = (few || n <= 0.0) ? (double)NAN : sqrt(s[SUM_D2] / n);
   st[12] = fitness;
   st[13] = rmse;
   if (few) {
@@ -276,7 +357,9 @@ icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, doubl
     return;
   }
   double r[3][3], t[3];
-  if (!kabsch_solve(s, r, t)) {
+  bool solved;
+  if constexpr (PLANE) solved = plane_solve(s, r, t); else solved = kabsch_solve(s, r, t);
+  if (!solved) {
     istate[2 * p + 1] = HFL_ICP_DEGENERATE;
     return;
   }
@@ -306,9 +389,26 @@ extern "C" int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, c
   // a target index is an int32, the grid is one-dimensional
   if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
   if (n_tiles == 0) return HFL_OK;
-  icp_correspond_kernel<<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      partials, dist, idx, source, s_offsets, n_source, targets, t_offsets, n_targets, tiles, state, istate, max_dist,
+  icp_correspond_kernel<false><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets, tiles, state, istate, max_dist,
       (int)n_pairs);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const float* source,
+                                        const int64_t* s_offsets, int64_t n_source, const float* targets,
+                                        const float* target_normals, const int64_t* t_offsets, int64_t n_targets,
+                                        const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
+                                        float max_dist, int64_t n_pairs, hfl_stream_t stream) {
+  if (partials == nullptr || source == nullptr || s_offsets == nullptr || targets == nullptr || target_normals == nullptr ||
+      t_offsets == nullptr || tiles == nullptr || state == nullptr || istate == nullptr || n_source < 0 || n_targets < 0 ||
+      n_tiles < 0 || n_pairs < 1)
+    return HFL_EINVAL;
+  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
+  if (n_tiles == 0) return HFL_OK;
+  icp_correspond_kernel<true><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
+      max_dist, (int)n_pairs);
   HFL_RETURN_LAST_ERROR();
 }
 
@@ -320,7 +420,21 @@ extern "C" int hfl_icp_solve(double* state, int32_t* istate, double* sums, const
       n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
     return HFL_EINVAL;
   if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  icp_solve_kernel<<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
+  icp_solve_kernel<false><<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
+      state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
+      is_last);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_icp_solve_plane(double* state, int32_t* istate, double* sums, const double* partials,
+                                   const int64_t* tile_offsets, int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs,
+                                   int min_correspondences, double relative_fitness, double relative_rmse, int is_last,
+                                   hfl_stream_t stream) {
+  if (state == nullptr || istate == nullptr || partials == nullptr || tile_offsets == nullptr || s_offsets == nullptr ||
+      n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
+    return HFL_EINVAL;
+  if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
+  icp_solve_kernel<true><<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
       state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
       is_last);
   HFL_RETURN_LAST_ERROR();

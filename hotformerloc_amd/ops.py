@@ -1908,6 +1908,7 @@ def pair_stats(dist: torch.Tensor, offsets: torch.Tensor, taus=()):
 
 
 ICP_SUMS = 17                          # HFL_ICP_SUMS: n, Sp (3), Sq (3), Spq (9), sum d^2
+ICP_PLANE_SUMS = 29                    # HFL_ICP_PLANE_SUMS: n, sum d^2, g (6), the upper triangle of A row-major (21)
 
 
 def _icp_state_check(what: str, state: torch.Tensor, istate: torch.Tensor, pairs: int):
@@ -1920,12 +1921,16 @@ def _icp_state_check(what: str, state: torch.Tensor, istate: torch.Tensor, pairs
 
 def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
                    tiles: torch.Tensor, state: torch.Tensor, istate: torch.Tensor, max_dist: float, partials=None,
-                   want_rows: bool = False):
+                   want_rows: bool = False, target_normals: torch.Tensor = None):
     """`hfl_icp_correspond`: one evaluation of every RUNNING pair.  source / targets: two ragged batches of the same P pairs;
     tiles: the device copy of `overlap_tiles` of the source lengths; state (P, 16) float64 and istate (P, 2) int32 as the
     header lays them out.  -> (partials (n_tiles, ICP_SUMS) float64, dist, idx): `partials` is written in place where one is
     given (the iteration loop allocates once), dist (Ns,) fp32 and idx (Ns,) int32 are None unless `want_rows`.  Rows of
-    pairs that are not RUNNING stay unwritten."""
+    pairs that are not RUNNING stay unwritten.  With `target_normals` ((Nt, 3) fp32, the rows of `targets`) it is
+    `hfl_icp_correspond_plane` and the partials have ICP_PLANE_SUMS columns."""
+    if target_normals is not None:
+        return _icp_correspond_plane(source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate, max_dist,
+                                     partials, want_rows)
     pairs = _ragged_check('icp_correspond', source, s_offsets)
     if _ragged_check('icp_correspond', targets, t_offsets) != pairs:
         raise ValueError('icp_correspond: the source batch and the target batch differ in their number of pairs')
@@ -1951,13 +1956,46 @@ def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch
     return partials, dist, idx
 
 
+def _icp_correspond_plane(source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate, max_dist, partials,
+                          want_rows):
+    what = 'icp_correspond_plane'
+    pairs = _ragged_check(what, source, s_offsets)
+    if _ragged_check(what, targets, t_offsets) != pairs:
+        raise ValueError('%s: the source batch and the target batch differ in their number of pairs' % what)
+    _ragged_check(what, target_normals, t_offsets)
+    if target_normals.shape[0] != targets.shape[0]:
+        raise ValueError('%s: %d target normals for %d target points' % (what, target_normals.shape[0], targets.shape[0]))
+    _icp_state_check(what, state, istate, pairs)
+    _dev(tiles)
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('%s: contiguous (n_tiles, 2) int64 tile table expected' % what)
+    n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
+    if partials is None:
+        partials = torch.empty((max(n_tiles, 1), ICP_PLANE_SUMS), dtype=torch.float64, device=source.device)
+    _dev(partials)
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
+            partials.shape[1] != ICP_PLANE_SUMS or not partials.is_contiguous():
+        raise TypeError('%s: contiguous (>= %d, %d) float64 partials expected' % (what, n_tiles, ICP_PLANE_SUMS))
+    dist = torch.empty(n_s, dtype=torch.float32, device=source.device) if want_rows else None
+    idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
+    if n_tiles:
+        check(_native.load().hfl_icp_correspond_plane(
+            partials.data_ptr(), dist.data_ptr() if want_rows else None, idx.data_ptr() if want_rows else None,
+            source.data_ptr(), s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), _some(target_normals).data_ptr(),
+            t_offsets.data_ptr(), int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(),
+            float(max_dist), pairs, _stream()), 'hfl_icp_correspond_plane')
+    return partials, dist, idx
+
+
 def icp_solve(state: torch.Tensor, istate: torch.Tensor, partials: torch.Tensor, tile_offsets: torch.Tensor, n_tiles: int,
               s_offsets: torch.Tensor, min_correspondences: int, relative_fitness: float, relative_rmse: float, is_last: bool,
-              want_sums: bool = False):
+              want_sums: bool = False, plane: bool = False):
     """`hfl_icp_solve`: the stop rules and the rigid update of every RUNNING pair, in place in state / istate.  partials: at
     least `n_tiles` rows; tile_offsets (P + 1,) int64: the rows of every pair; s_offsets: the source offsets (the
     denominator of the fitness).  -> sums (P, ICP_SUMS) float64 with `want_sums` (a pair that is not RUNNING keeps zeros),
-    else None."""
+    else None.  `plane`: `hfl_icp_solve_plane` on partials of ICP_PLANE_SUMS columns."""
+    n_sums = ICP_PLANE_SUMS if plane else ICP_SUMS
+    name = 'hfl_icp_solve_plane' if plane else 'hfl_icp_solve'
     _offsets_check('icp_solve', tile_offsets)
     _offsets_check('icp_solve', s_offsets)
     pairs = int(s_offsets.shape[0]) - 1
@@ -1966,13 +2004,13 @@ def icp_solve(state: torch.Tensor, istate: torch.Tensor, partials: torch.Tensor,
     if tile_offsets.shape[0] != pairs + 1:
         raise TypeError('icp_solve: (%d,) tile offsets expected' % (pairs + 1))
     if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < max(int(n_tiles), 1) or \
-            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
-        raise TypeError('icp_solve: contiguous (>= %d, %d) float64 partials expected' % (max(int(n_tiles), 1), ICP_SUMS))
-    sums = torch.zeros((pairs, ICP_SUMS), dtype=torch.float64, device=state.device) if want_sums else None
-    check(_native.load().hfl_icp_solve(state.data_ptr(), istate.data_ptr(), sums.data_ptr() if want_sums else None,
-                                       partials.data_ptr(), tile_offsets.data_ptr(), int(n_tiles), s_offsets.data_ptr(), pairs,
-                                       int(min_correspondences), float(relative_fitness), float(relative_rmse), int(bool(is_last)),
-                                       _stream()), 'hfl_icp_solve')
+            partials.shape[1] != n_sums or not partials.is_contiguous():
+        raise TypeError('icp_solve: contiguous (>= %d, %d) float64 partials expected' % (max(int(n_tiles), 1), n_sums))
+    sums = torch.zeros((pairs, n_sums), dtype=torch.float64, device=state.device) if want_sums else None
+    check(getattr(_native.load(), name)(state.data_ptr(), istate.data_ptr(), sums.data_ptr() if want_sums else None,
+                                        partials.data_ptr(), tile_offsets.data_ptr(), int(n_tiles), s_offsets.data_ptr(), pairs,
+                                        int(min_correspondences), float(relative_fitness), float(relative_rmse),
+                                        int(bool(is_last)), _stream()), name)
     return sums
 
 
@@ -2275,6 +2313,37 @@ def knn_mean_dist(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: 
                                            table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
                                            offsets.data_ptr(), n, int(phases), _stream()), 'hfl_knn_mean_dist')
     return avg, ws.counter
+
+
+def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
+                table: KnnGridTable, viewpoints: torch.Tensor = None, phases: int = KNN_PHASE_ALL,
+                workspace: KnnWorkspace = None):
+    """`hfl_knn_normals`: the arguments of `knn_mean_dist` -> (normals (P, 3) fp32, curvature (P,) fp32, counts (P,) int32,
+    all in INPUT order, pending (1,) int32 on the GPU).  `viewpoints`: (B, 3) float64 on the GPU, one per cloud, or None for
+    the upward rule.  Nothing is read back."""
+    _knn_check('knn_normals', table, sorted_points, offsets)
+    _dev(sorted_keys, perm)
+    n = int(sorted_points.shape[0])
+    for t in (sorted_keys, perm):
+        _vector_check('knn_normals', t, torch.int64, n, 'keys and permutation')
+    if viewpoints is not None:
+        _dev(viewpoints)
+        if viewpoints.dtype != torch.float64 or tuple(viewpoints.shape) != (table.batch, 3) or not viewpoints.is_contiguous():
+            raise TypeError('knn_normals: contiguous (%d, 3) float64 viewpoints expected' % table.batch)
+    ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
+    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
+        raise ValueError('knn_normals: the workspace was made for another batch')
+    normals = torch.empty((n, 3), dtype=torch.float32, device=sorted_points.device)
+    curvature = torch.empty(n, dtype=torch.float32, device=sorted_points.device)
+    counts = torch.empty(n, dtype=torch.int32, device=sorted_points.device)
+    _dev(ws.starts, ws.pending, ws.counter)
+    check(_native.load().hfl_knn_normals(normals.data_ptr(), curvature.data_ptr(), counts.data_ptr(), ws.pending.data_ptr(),
+                                         ws.counter.data_ptr(), ws.starts.data_ptr(), sorted_points.data_ptr(),
+                                         sorted_keys.data_ptr(), perm.data_ptr(), table.host.ctypes.data,
+                                         table.device.data_ptr(), table.batch, table.cells, offsets.data_ptr(), n,
+                                         viewpoints.data_ptr() if viewpoints is not None else None, int(phases), _stream()),
+          'hfl_knn_normals')
+    return normals, curvature, counts, ws.counter
 
 
 def outlier_threshold(avg: torch.Tensor, offsets: torch.Tensor, std_ratio: float):

@@ -1,4 +1,4 @@
-"""Rigid point-to-point ICP registration of a ragged batch of submap pairs, on the GPU.
+"""Rigid ICP registration, point-to-point or point-to-plane, of a ragged batch of submap pairs, on the GPU.
 
 Retrieval names a place; the query scan is useful once it is registered against it.  `submap_overlap` aligns a ground submap
 to an aerial one by the surveyed poses alone, so its Chamfer distance mixes pose error with real disagreement between the
@@ -10,6 +10,7 @@ points themselves.  The reference has no such step and open3d is not a dependenc
     icp_correspondences    one evaluation: every source point's distance, target, inlier flag, and the 17 sums of a pair
     evaluate_registration  fitness and inlier rmse of a given alignment (the k = 0 evaluation alone)
     kabsch_update          the rigid update (R, t) of given sums
+    plane_update           the point-to-plane update (R, t) of given sums
 
 Definition (DESIGN.md section 7i has the reasons).  Per pair, T_0 = init (float64 4 x 4, the identity by default;
 `SubmapOverlap.transforms` feeds in directly).  For k = 0 .. max_iterations: evaluate, decide, update.
@@ -32,6 +33,24 @@ Definition (DESIGN.md section 7i has the reasons).  Per pair, T_0 = init (float6
   with 12 sweeps over the column pairs (0,1), (0,2), (1,2) of G = H V; with u1, u2 / v1, v2 the normalised columns of G / the
   columns of V at the two largest column norms, R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T, which is the formula above
   without a division by the smallest singular value: det R = +1 always, and a planar cloud is no special case.
+
+Point-to-plane (`estimation='point_to_plane'`, `target_normals` in the layout of `target`, for instance from
+`estimate_normals`).  Point-to-point ICP on sparse lidar submaps slides along the ground and along trunks: source and target
+sample the same surface at different places, so the nearest target point is not the same physical point; the distance to the
+target's tangent plane does not care.  Evaluate, fitness, `inlier_rmse` (it stays the point-to-point distance rmse, as in
+open3d), the stop rules, `iterations` and the status codes are exactly as above, so a result is comparable across the two
+modes.  Only the update differs:
+
+  Update.  Over the inliers, in float64 from the fp32 values p' (moved source), q = target[j(p')], n = target_normals[j(p')],
+  every operation rounded once: r = ((p'x - qx) nx + (p'y - qy) ny) + (p'z - qz) nz, a = p' x n, J = (a, n) (6 entries),
+  A = sum J J^T, g = sum J r.  A zero normal (the "no normal" marker of `normals.py`) contributes nothing.  The sums of a
+  pair are `N_SUMS_PLANE` = 29: n, sum d^2, g (6), the upper triangle of A row-major (21).
+
+  Solve.  A x = -g for x = (alpha, beta, gamma, tx, ty, tz) by an LDL^T factorisation in float64 without pivoting, in a
+  fixed operation order (column by column, the inner sums from k = 0 upwards).  A pivot d_i <= 1e-12 A_ii (a NaN too): the
+  pair is DEGENERATE and its pose stays T_k -- parallel normals, or too few correspondences for six unknowns.  Otherwise
+  R = Rz(gamma) Ry(beta) Rx(alpha) (open3d's `TransformVector6dToMatrix4d`), t = (tx, ty, tz), T_{k+1} = [R | t] . T_k in
+  float64; R is a product of three rotations, so det R = +1 by construction.
 
 `iterations` is the k at which the pair stopped: the number of updates its pose received.  An empty source cloud is TOO_FEW
 with fitness NaN (0 / 0), an empty target cloud TOO_FEW with fitness 0.
@@ -59,8 +78,11 @@ from .overlap import _HOST_CHUNK_PAIRS, _host_ragged, _matrices, _ragged, _same_
 
 RUNNING, CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE = range(5)     # HFL_ICP_*: a pair's status
 N_SUMS = 17                            # n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2
+N_SUMS_PLANE = 29                      # n, sum d^2, g (6), the upper triangle of A row-major (21)
 JACOBI_SWEEPS = 12                     # RG_SWEEPS of csrc/registration.hip
 RANK_TOL = 1e-12                       # second singular value <= RANK_TOL x the largest: DEGENERATE
+PIVOT_TOL = 1e-12                      # a pivot of the LDL^T <= PIVOT_TOL x its diagonal entry of A: DEGENERATE
+ESTIMATIONS = ('point_to_point', 'point_to_plane')
 
 RegistrationResult = namedtuple('RegistrationResult', ['transforms', 'fitness', 'inlier_rmse', 'iterations', 'status'])
 RegistrationResult.__doc__ = """What `icp_refine` returns, numpy arrays on the host.  transforms: (P, 4, 4) float64, source
@@ -87,6 +109,28 @@ def _options(max_correspondence_distance, max_iterations, relative_fitness, rela
     return d, int(max_iterations), float(relative_fitness), float(relative_rmse), int(min_correspondences)
 
 
+def _estimation(estimation, target_normals, what):
+    """True for point-to-plane; the normals go with that estimator and with no other"""
+    if estimation not in ESTIMATIONS:
+        raise ValueError('%s: estimation must be one of %s, got %r' % (what, ', '.join(ESTIMATIONS), estimation))
+    plane = estimation == 'point_to_plane'
+    if plane and target_normals is None:
+        raise ValueError("%s: estimation='point_to_plane' needs target_normals" % what)
+    if not plane and target_normals is not None:
+        raise ValueError("%s: target_normals go with estimation='point_to_plane'" % what)
+    return plane
+
+
+def _normals_of(target, target_normals, t_off, what, ragged):
+    """the (M, 3) float32 normals of the target batch: a list like `target`, or the packed array under the target's offsets"""
+    if isinstance(target, list) != isinstance(target_normals, list):
+        raise ValueError('%s: target_normals must come in the layout of target' % what)
+    nrm, n_off, _ = ragged(target_normals if isinstance(target_normals, list) else (target_normals, t_off), what)
+    if not np.array_equal(n_off, t_off):
+        raise ValueError('%s: target_normals must hold one normal per target point, cloud by cloud' % what)
+    return nrm
+
+
 def _full(m34):
     """(P, 3, 4) -> (P, 4, 4) with the row 0 0 0 1"""
     out = np.zeros((m34.shape[0], 4, 4), np.float64)
@@ -100,11 +144,14 @@ class _Batch:
     """A batch of pairs on the device with everything an iteration needs: both clouds, their offsets, the tile table of the
     source clouds and its per-pair offsets, the partials."""
 
-    def __init__(self, source, target, what):
+    def __init__(self, source, target, what, target_normals=None):
         from . import ops
         self.s, self.s_off, _ = _ragged(source, what, True)
         self.t, self.t_off, _ = _ragged(target, what, True)
         _same_pairs(self.s_off, self.t_off, what)
+        self.plane = target_normals is not None
+        self.normals = _normals_of(target, target_normals, self.t_off, what, lambda b, w: _ragged(b, w, True)) \
+            if self.plane else None
         self.pairs = self.s_off.shape[0] - 1
         dev = self.s.device
         lengths = np.diff(self.s_off)
@@ -115,7 +162,8 @@ class _Batch:
         with torch.cuda.device(dev):
             self.s_dev, self.t_dev = torch.from_numpy(self.s_off).to(dev), torch.from_numpy(self.t_off).to(dev)
             self.tiles, self.tile_off = torch.from_numpy(tiles).to(dev), torch.from_numpy(tile_off).to(dev)
-            self.partials = torch.zeros((max(self.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=dev)
+            self.partials = torch.zeros((max(self.n_tiles, 1), ops.ICP_PLANE_SUMS if self.plane else ops.ICP_SUMS),
+                                        dtype=torch.float64, device=dev)
 
     def state(self, m34):
         """(state, istate) on the device: the given poses, every pair RUNNING at iteration 0"""
@@ -126,23 +174,26 @@ class _Batch:
     def correspond(self, state, istate, max_dist, want_rows=False):
         from . import ops
         return ops.icp_correspond(self.s, self.s_dev, self.t, self.t_dev, self.tiles, state, istate, max_dist,
-                                  partials=self.partials, want_rows=want_rows)
+                                  partials=self.partials, want_rows=want_rows, target_normals=self.normals)
 
     def solve(self, state, istate, min_corr, rel_fitness, rel_rmse, is_last, want_sums=False):
         from . import ops
         return ops.icp_solve(state, istate, self.partials, self.tile_off, self.n_tiles, self.s_dev, min_corr, rel_fitness,
-                             rel_rmse, is_last, want_sums=want_sums)
+                             rel_rmse, is_last, want_sums=want_sums, plane=self.plane)
 
 
 def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
-               relative_rmse=1e-6, min_correspondences=3):
-    """Point-to-point ICP of P (source, target) pairs, as the module's docstring defines it -> `RegistrationResult`.  `init`:
-    (P, 4, 4) or (P, 3, 4) float64, numpy or tensor, source frame -> target frame; None is the identity.  The whole loop is
-    enqueued on the current stream without a host read; the results are read once at the end."""
+               relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None):
+    """ICP of P (source, target) pairs, as the module's docstring defines it -> `RegistrationResult`.  `init`: (P, 4, 4) or
+    (P, 3, 4) float64, numpy or tensor, source frame -> target frame; None is the identity.  `estimation`:
+    'point_to_point', or 'point_to_plane' with `target_normals` in the layout of `target` (a list of (M_i, 3) float32, or the
+    packed (M, 3) tensor under the target's offsets).  The whole loop is enqueued on the current stream without a host read;
+    the results are read once at the end."""
     what = 'icp_refine'
     dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
                                                    min_correspondences, what)
-    b = _Batch(source, target, what)
+    _estimation(estimation, target_normals, what)
+    b = _Batch(source, target, what, target_normals)
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_init_matrices(init, b.pairs, what))
         for k in range(iters + 1):
@@ -153,9 +204,10 @@ def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_i
                               istate[:, 0].copy(), istate[:, 1].copy())
 
 
-def _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences, what, want_rows):
+def _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences, what, want_rows,
+              target_normals=None):
     dist, _, _, _, min_corr = _options(max_correspondence_distance, 0, 0.0, 0.0, min_correspondences, what)
-    b = _Batch(source, target, what)
+    b = _Batch(source, target, what, target_normals)
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_matrices(transforms, b.pairs, what))
         _, d, j = b.correspond(state, istate, dist, want_rows=want_rows)
@@ -163,12 +215,14 @@ def _evaluate(source, target, transforms, max_correspondence_distance, min_corre
     return d, j, sums, state, dist
 
 
-def icp_correspondences(source, target, transforms, max_correspondence_distance):
+def icp_correspondences(source, target, transforms, max_correspondence_distance, target_normals=None):
     """One evaluation at the given poses, on the device: `(dist (Ns,) float32, idx (Ns,) int32, inlier (Ns,) bool, sums
     (P, 17) float64)`.  dist and idx have the bits of `nn_distances(transform_points(source, transforms), target)`; inlier is
     `dist <= fp32(max_correspondence_distance)` where there is a target; sums are n, Sp, Sq, Spq (row-major) and sum d^2
-    over a pair's inliers, in the device's fixed order."""
-    d, j, sums, _, dist = _evaluate(source, target, transforms, max_correspondence_distance, 0, 'icp_correspondences', True)
+    over a pair's inliers, in the device's fixed order.  With `target_normals` (the layout of `target`) the sums are the
+    (P, 29) of the point-to-plane update -- n, sum d^2, g, the upper triangle of A -- and the rest keeps its bits."""
+    d, j, sums, _, dist = _evaluate(source, target, transforms, max_correspondence_distance, 0, 'icp_correspondences', True,
+                                    target_normals)
     return d, j, (j >= 0) & (d <= float(np.float32(dist))), sums
 
 
@@ -184,12 +238,16 @@ def kabsch_update(sums, min_correspondences=3):
     """The update step of `hfl_icp_solve` on given sums (P, 17) float64 on the device -> `(R (P, 3, 3), t (P, 3), status
     (P,) int32)` on the device.  status is RUNNING where (R, t) is the update, TOO_FEW where n < min_correspondences and
     DEGENERATE where H has rank < 2; there R = I and t = 0."""
+    return _update_on_device(sums, min_correspondences, N_SUMS, 'kabsch_update', False)
+
+
+def _update_on_device(sums, min_correspondences, n_sums, what, plane):
     from . import ops
     sums = torch.as_tensor(sums)
     if not sums.is_cuda:
-        raise _native.NativeLibraryError('kabsch_update runs on the GPU and takes GPU tensors (kabsch_update_host is the CPU route)')
-    if sums.dtype != torch.float64 or sums.dim() != 2 or sums.shape[1] != N_SUMS or sums.shape[0] < 1:
-        raise TypeError('kabsch_update: (P >= 1, %d) float64 sums expected, got %s %s' % (N_SUMS, sums.dtype, tuple(sums.shape)))
+        raise _native.NativeLibraryError('%s runs on the GPU and takes GPU tensors (%s_host is the CPU route)' % (what, what))
+    if sums.dtype != torch.float64 or sums.dim() != 2 or sums.shape[1] != n_sums or sums.shape[0] < 1:
+        raise TypeError('%s: (P >= 1, %d) float64 sums expected, got %s %s' % (what, n_sums, sums.dtype, tuple(sums.shape)))
     pairs = int(sums.shape[0])
     with torch.cuda.device(sums.device):
         st = np.zeros((pairs, 16), np.float64)
@@ -197,9 +255,17 @@ def kabsch_update(sums, min_correspondences=3):
         state = torch.from_numpy(st).to(sums.device)
         istate = torch.zeros((pairs, 2), dtype=torch.int32, device=sums.device)
         one_each = torch.arange(pairs + 1, dtype=torch.int64, device=sums.device)       # one tile, one source point per pair
-        ops.icp_solve(state, istate, sums.contiguous(), one_each, pairs, one_each, int(min_correspondences), 0.0, 0.0, False)
+        ops.icp_solve(state, istate, sums.contiguous(), one_each, pairs, one_each, int(min_correspondences), 0.0, 0.0, False,
+                      plane=plane)
     pose = state[:, :12].reshape(pairs, 3, 4)
     return pose[:, :, :3].contiguous(), pose[:, :, 3].contiguous(), istate[:, 1].contiguous()
+
+
+def plane_update(sums, min_correspondences=6):
+    """The update step of `hfl_icp_solve_plane` on given sums (P, 29) float64 on the device -> `(R (P, 3, 3), t (P, 3),
+    status (P,) int32)` on the device: the twin of `kabsch_update`.  status is RUNNING where (R, t) is the update, TOO_FEW
+    where n < min_correspondences and DEGENERATE where a pivot of the LDL^T fails; there R = I and t = 0."""
+    return _update_on_device(sums, min_correspondences, N_SUMS_PLANE, 'plane_update', True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- host route
@@ -237,11 +303,33 @@ def _host_nn32(q, t, chunk_pairs=_HOST_CHUNK_PAIRS // 2):
     return dist, idx
 
 
-def _host_evaluate_one(src, dst, m34, max_dist32):
-    """one pair, one evaluation: (dist float32, idx int32, inlier bool, sums (17,) float64)"""
+def _host_plane_sums(p, q, n, d):
+    """the 29 sums of given inlier rows, float64 (n, 3) each and the distances (n,)"""
+    sums = np.zeros(N_SUMS_PLANE, np.float64)
+    sums[0] = p.shape[0]
+    sums[1] = (d * d).sum()
+    e = p - q
+    r = (e[:, 0] * n[:, 0] + e[:, 1] * n[:, 1]) + e[:, 2] * n[:, 2]
+    jac = np.stack([p[:, 1] * n[:, 2] - p[:, 2] * n[:, 1], p[:, 2] * n[:, 0] - p[:, 0] * n[:, 2],
+                    p[:, 0] * n[:, 1] - p[:, 1] * n[:, 0], n[:, 0], n[:, 1], n[:, 2]], 1)
+    sums[2:8] = (jac * r[:, None]).sum(0)
+    slot = 8
+    for a in range(6):
+        for b in range(a, 6):
+            sums[slot] = (jac[:, a] * jac[:, b]).sum()
+            slot += 1
+    return sums
+
+
+def _host_evaluate_one(src, dst, m34, max_dist32, normals=None):
+    """one pair, one evaluation: (dist float32, idx int32, inlier bool, sums (17,) float64, or (29,) with the target's
+    normals)"""
     moved = _host_move(src, m34)
     dist, idx = _host_nn32(moved, dst)
     inl = (idx >= 0) & (dist <= max_dist32)
+    if normals is not None:
+        p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
+        return dist, idx, inl, _host_plane_sums(p, q, normals[idx[inl]].astype(np.float64).reshape(-1, 3), d)
     sums = np.zeros(N_SUMS, np.float64)
     if inl.any():
         p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
@@ -301,16 +389,20 @@ def _host_kabsch_one(s):
 
 def kabsch_update_host(sums, min_correspondences=3):
     """`kabsch_update` on the CPU: `(R (P, 3, 3) float64, t (P, 3) float64, status (P,) int32)` numpy arrays."""
+    return _update_on_host(sums, min_correspondences, N_SUMS, 'kabsch_update', _host_kabsch_one)
+
+
+def _update_on_host(sums, min_correspondences, n_sums, what, solve_one):
     sums = np.asarray(sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
-    if sums.ndim != 2 or sums.shape[1] != N_SUMS or sums.shape[0] < 1:
-        raise TypeError('kabsch_update: (P >= 1, %d) float64 sums expected, got shape %s' % (N_SUMS, sums.shape))
+    if sums.ndim != 2 or sums.shape[1] != n_sums or sums.shape[0] < 1:
+        raise TypeError('%s: (P >= 1, %d) float64 sums expected, got shape %s' % (what, n_sums, sums.shape))
     pairs = sums.shape[0]
     r, t, status = np.tile(np.eye(3), (pairs, 1, 1)), np.zeros((pairs, 3), np.float64), np.zeros(pairs, np.int32)
     for p in range(pairs):
         if sums[p, 0] < min_correspondences:
             status[p] = TOO_FEW
             continue
-        solved = _host_kabsch_one(sums[p])
+        solved = solve_one(sums[p])
         if solved is None:
             status[p] = DEGENERATE
         else:
@@ -318,38 +410,91 @@ def kabsch_update_host(sums, min_correspondences=3):
     return r, t, status
 
 
-def _host_batch(source, target, what):
+def _host_plane_one(s):
+    """(R (3, 3), t (3,)) of one pair's 29 sums, or None where a pivot fails: `plane_solve` of csrc/registration.hip, line by
+    line, on numpy float64 scalars"""
+    with np.errstate(all='ignore'):
+        s = [np.float64(x) for x in s]
+        a = [[np.float64(0.0)] * 6 for _ in range(6)]                  # the lower triangle becomes L
+        slot = 8
+        for i in range(6):
+            for j in range(i, 6):
+                a[i][j] = a[j][i] = s[slot]
+                slot += 1
+        d = [np.float64(0.0)] * 6
+        for j in range(6):
+            diag = a[j][j]
+            dj = diag
+            for k in range(j):
+                dj = dj - a[j][k] * a[j][k] * d[k]
+            if not dj > PIVOT_TOL * diag:
+                return None
+            d[j] = dj
+            for i in range(j + 1, 6):
+                v = a[i][j]
+                for k in range(j):
+                    v = v - a[i][k] * a[j][k] * d[k]
+                a[i][j] = v / dj
+        x = [np.float64(0.0)] * 6
+        for i in range(6):                                             # L y = -g
+            v = -s[2 + i]
+            for k in range(i):
+                v = v - a[i][k] * x[k]
+            x[i] = v
+        x = [x[i] / d[i] for i in range(6)]
+        for i in range(5, -1, -1):                                     # L^T x = z
+            v = x[i]
+            for k in range(i + 1, 6):
+                v = v - a[k][i] * x[k]
+            x[i] = v
+        ca, sa, cb, sb, cg, sg = np.cos(x[0]), np.sin(x[0]), np.cos(x[1]), np.sin(x[1]), np.cos(x[2]), np.sin(x[2])
+        r = np.array([[cb * cg, sa * sb * cg - ca * sg, ca * sb * cg + sa * sg],
+                      [cb * sg, sa * sb * sg + ca * cg, ca * sb * sg - sa * cg],
+                      [-sb, sa * cb, ca * cb]], np.float64)
+    return r, np.array(x[3:], np.float64)
+
+
+def plane_update_host(sums, min_correspondences=6):
+    """`plane_update` on the CPU: `(R (P, 3, 3) float64, t (P, 3) float64, status (P,) int32)` numpy arrays."""
+    return _update_on_host(sums, min_correspondences, N_SUMS_PLANE, 'plane_update', _host_plane_one)
+
+
+def _host_batch(source, target, what, target_normals=None):
     s, s_off, _ = _host_ragged(source, what)
     t, t_off, _ = _host_ragged(target, what)
     _same_pairs(s_off, t_off, what)
     pairs = s_off.shape[0] - 1
-    return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
+    if target_normals is None:
+        return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
+    n = _normals_of(target, target_normals, t_off, what, _host_ragged)
+    return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]], n[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
 
 
 def _host_figures(sums, n_source, min_corr):
-    """(fitness, rmse, too few) of one evaluation"""
-    n = sums[0]
+    """(fitness, rmse, too few) of one evaluation, from the 17 sums or the 29"""
+    n, sum_d2 = sums[0], sums[1] if sums.shape[0] == N_SUMS_PLANE else sums[16]
     with np.errstate(all='ignore'):
         fitness = np.float64(n) / np.float64(n_source)                 # an empty source cloud: 0 / 0 = NaN
         few = n < min_corr
-        rmse = np.float64(np.nan) if (few or n <= 0) else np.sqrt(sums[16] / n)
+        rmse = np.float64(np.nan) if (few or n <= 0) else np.sqrt(sum_d2 / n)
     return float(fitness), float(rmse), bool(few)
 
 
 def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
-                    relative_rmse=1e-6, min_correspondences=3):
+                    relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None):
     """`icp_refine` on the CPU: the module's definition in numpy, pair by pair -> `RegistrationResult`."""
     what = 'icp_refine'
     dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
                                                    min_correspondences, what)
-    batch, _ = _host_batch(source, target, what)
+    solve_one = _host_plane_one if _estimation(estimation, target_normals, what) else _host_kabsch_one
+    batch, _ = _host_batch(source, target, what, target_normals)
     pose = _init_matrices(init, len(batch), what).copy()
     fitness, rmse = np.zeros(len(batch), np.float64), np.zeros(len(batch), np.float64)
     iterations, status = np.zeros(len(batch), np.int64), np.zeros(len(batch), np.int64)
-    for p, (src, dst) in enumerate(batch):
+    for p, (src, dst, *nrm) in enumerate(batch):
         prev = None
         for k in range(iters + 1):
-            sums = _host_evaluate_one(src, dst, pose[p], np.float32(dist))[3]
+            sums = _host_evaluate_one(src, dst, pose[p], np.float32(dist), *nrm)[3]
             fitness[p], rmse[p], few = _host_figures(sums, src.shape[0], min_corr)
             iterations[p] = k
             if few:
@@ -361,7 +506,7 @@ def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, 
             if k == iters:
                 status[p] = MAX_ITERATIONS
                 break
-            solved = _host_kabsch_one(sums)
+            solved = solve_one(sums)
             if solved is None:
                 status[p] = DEGENERATE
                 break
@@ -372,13 +517,14 @@ def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, 
     return RegistrationResult(_full(pose), fitness, rmse, iterations, status)
 
 
-def icp_correspondences_host(source, target, transforms, max_correspondence_distance):
-    """`icp_correspondences` on the CPU: `(dist float32, idx int32, inlier bool, sums (P, 17) float64)` numpy arrays."""
+def icp_correspondences_host(source, target, transforms, max_correspondence_distance, target_normals=None):
+    """`icp_correspondences` on the CPU: `(dist float32, idx int32, inlier bool, sums (P, 17) float64)` numpy arrays; with
+    `target_normals` the sums are (P, 29)."""
     what = 'icp_correspondences'
     dist = _options(max_correspondence_distance, 0, 0.0, 0.0, 0, what)[0]
-    batch, _ = _host_batch(source, target, what)
+    batch, _ = _host_batch(source, target, what, target_normals)
     m = _matrices(transforms, len(batch), what)
-    parts = [_host_evaluate_one(src, dst, m[p], np.float32(dist)) for p, (src, dst) in enumerate(batch)]
+    parts = [_host_evaluate_one(pair[0], pair[1], m[p], np.float32(dist), *pair[2:]) for p, pair in enumerate(batch)]
     return (np.concatenate([x[0] for x in parts]), np.concatenate([x[1] for x in parts]), np.concatenate([x[2] for x in parts]),
             np.stack([x[3] for x in parts]))
 

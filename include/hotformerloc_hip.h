@@ -400,6 +400,21 @@ int hfl_knn_mean_dist(float* avg, int32_t* pending, int32_t* counter, int32_t* c
                       const int64_t* sorted_keys, const int64_t* perm, const hfl_knn_grid* grids_host,
                       const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
                       int phases, hfl_stream_t stream);
+/* Surface normals by the same search (csrc/normals.hip; defined in hotformerloc_amd/normals.py and DESIGN.md section 7j).
+ * With r2 the k-th smallest fp32 squared distance of point p and N(p) every point of its cloud with d2 <= r2 (ties at the
+ * k-th place all included, p itself too): counts[p] = |N(p)|; in float64 about p itself S1 = sum e, S2 = sum e e^T over
+ * e = q - p, C = S2 / m - (S1 / m)(S1 / m)^T; a one-sided cyclic Jacobi of fixed sweep count gives the eigenvalues
+ * l0 <= l1 <= l2; normals[p] (3 floats) = the unit eigenvector of l0, curvature[p] = l0 / (l0 + l1 + l2).  m < 3 or
+ * l1 <= 1e-12 l2: normal (0, 0, 0), curvature 0 -- a zero normal says "no normal".  Sign: viewpoints (DEVICE, batch x 3
+ * float64, one per cloud) not NULL: n . (viewpoint - p) >= 0; NULL: n_z > 0, else n_y > 0, else n_x > 0.  The other
+ * arguments, the workspace and `phases` are those of hfl_knn_mean_dist; outputs are in INPUT order (row perm[j]).  counts is
+ * a pure function of the input; the float64 sums run in an order fixed by the sort and the grid, so two calls give the
+ * same bits and two grids agree to rounding.  A memset and three launches on `stream`, no floating-point atomics. */
+int hfl_knn_normals(float* normals, float* curvature, int32_t* counts, int32_t* pending, int32_t* counter,
+                    int32_t* cell_starts, const float* sorted_points, const int64_t* sorted_keys, const int64_t* perm,
+                    const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                    const int64_t* cloud_offsets, int64_t n_points, const double* viewpoints, int phases,
+                    hfl_stream_t stream);
 /* stats (batch, 4) float64 = (mean, std, mean + std_ratio std, n_valid) over the valid rows (avg > 0) of every cloud, std
  * with n_valid - 1 in the denominator; float64, summed in the order of hfl_pair_stats.  No valid row: mean = NaN; one: std =
  * NaN.  One workgroup per cloud, one launch on `stream`.  std_ratio <= 0 or not finite: HFL_EINVAL. */
@@ -1194,6 +1209,23 @@ int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, const float*
 int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials, const int64_t* tile_offsets,
                   int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs, int min_correspondences, double relative_fitness,
                   double relative_rmse, int is_last, hfl_stream_t stream);
+/* The point-to-plane estimator: the same two launches with 29 sums per tile and pair -- n, sum d^2, g (6), the upper
+ * triangle of A row-major (21), where over the inliers r = (p' - q) . nq, J = (p' x nq, nq), A = sum J J^T, g = sum J r,
+ * nq = target_normals[idx] (DEVICE, (n_targets, 3) fp32, the rows of `targets`; a zero normal adds nothing to A and g). */
+#define HFL_ICP_PLANE_SUMS 29
+/* hfl_icp_correspond with the normal gathered at the winning index once the scan is over; dist, idx, the inlier rule and
+ * the order of the reduction are unchanged.  partials is (n_tiles, HFL_ICP_PLANE_SUMS). */
+int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
+                             int64_t n_source, const float* targets, const float* target_normals, const int64_t* t_offsets,
+                             int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state,
+                             const int32_t* istate, float max_dist, int64_t n_pairs, hfl_stream_t stream);
+/* hfl_icp_solve on those partials: the same stop rules; the update solves A x = -g, x = (alpha, beta, gamma, tx, ty, tz),
+ * by an LDL^T factorisation without pivoting in a fixed order, R = Rz(gamma) Ry(beta) Rx(alpha), t = (tx, ty, tz),
+ * pose <- (R | t) . pose; a pivot <= 1e-12 x its diagonal entry of A (or not a number): DEGENERATE, pose unchanged.  sums
+ * (optional) is (P, HFL_ICP_PLANE_SUMS). */
+int hfl_icp_solve_plane(double* state, int32_t* istate, double* sums, const double* partials, const int64_t* tile_offsets,
+                        int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs, int min_correspondences,
+                        double relative_fitness, double relative_rmse, int is_last, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
