@@ -8,6 +8,10 @@ Raw-submap post-processing on the device (the reference's open3d / CSF toolkit):
 `remove_ground`, `voxel_downsample` /
 `pnvlad_downsample` / `random_downsample`, `normalise_submaps`, chained by `prepare_submaps` / `prepare_submaps_fixed`;
 every step has a numpy `*_host` twin that states its definition.
+
+Towards a pose for a retrieved candidate: `estimate_normals`, then `compute_fpfh` (33-bin FPFH descriptors per point on the
+same search) and `feature_correspondences` (nearest rows in descriptor space, optionally mutual) give the point pairs a
+robust estimator needs before `icp_refine`; `compute_fpfh_host` / `feature_correspondences_host` define them.
 """
 
 import os as _os
@@ -41,5 +45,7 @@ from .registration import (icp_refine, icp_refine_host, icp_correspondences, icp
                            evaluate_registration, evaluate_registration_host, kabsch_update, kabsch_update_host,
                            plane_update, plane_update_host, RegistrationResult)
 from .normals import estimate_normals, estimate_normals_host                                            # noqa: F401,E402
+from .fpfh import (compute_fpfh, compute_fpfh_host, feature_correspondences,                            # noqa: F401,E402
+                   feature_correspondences_host)
 
 __version__ = '0.1.0'

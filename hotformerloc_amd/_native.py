@@ -152,6 +152,11 @@ SIGNATURES = {
     'hfl_knn_cell_keys': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     'hfl_knn_mean_dist': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     'hfl_knn_normals': (c_int, [c_void_p] * 11 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    'hfl_fpfh_radius': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    'hfl_fpfh_spfh': (c_int, [c_void_p] * 12 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hfl_fpfh_combine': (c_int, [c_void_p] * 13 + [c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    'hfl_feature_nn': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                               c_int64, c_int64, c_void_p]),
     'hfl_outlier_threshold': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_double, c_void_p]),
     'hfl_outlier_mask': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     'hfl_radius_mask': (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),

@@ -2346,6 +2346,121 @@ def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: to
     return normals, curvature, counts, ws.counter
 
 
+FPFH_DIM = 33                          # three groups of 11 bins
+FEATURE_ROWS = 512                     # HFL_FEATURE_ROWS: query rows of a workgroup of hfl_feature_nn (two per thread)
+FEATURE_MAX_DIM = 64                   # HFL_FEATURE_MAX_DIM
+
+
+class FpfhWorkspace(KnnWorkspace):
+    """what the three hfl_fpfh_* calls hand to each other, all by SORTED position: the workspace of the search, every
+    point's r2 and whether the 3 x 3 x 3 block proves it, the integer histograms and the pair counts"""
+
+    def __init__(self, n_points: int, cells: int, device):
+        super().__init__(n_points, cells, device)
+        self.r2 = torch.empty(n_points, dtype=torch.float32, device=device)
+        self.proven = torch.empty(n_points, dtype=torch.uint8, device=device)
+        self.hist = torch.empty((n_points, FPFH_DIM), dtype=torch.int32, device=device)
+        self.pairs = torch.empty(n_points, dtype=torch.int32, device=device)
+
+
+def _fpfh_check(what: str, ws: FpfhWorkspace, table: KnnGridTable, sorted_points: torch.Tensor, offsets: torch.Tensor,
+                sorted_keys: torch.Tensor) -> int:
+    _knn_check(what, table, sorted_points, offsets)
+    n = int(sorted_points.shape[0])
+    _dev(sorted_keys, ws.starts, ws.pending, ws.counter, ws.r2, ws.proven, ws.hist, ws.pairs)
+    _vector_check(what, sorted_keys, torch.int64, n, 'keys')
+    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
+        raise ValueError('%s: the workspace was made for another batch' % what)
+    return n
+
+
+def fpfh_radius(ws: FpfhWorkspace, sorted_points: torch.Tensor, sorted_keys: torch.Tensor, offsets: torch.Tensor,
+                table: KnnGridTable):
+    """`hfl_fpfh_radius`: the sorted batch of `knn_mean_dist` -> ws.r2, ws.proven and the pending list filled; returns the
+    (1,) int32 counter of points the whole-cloud scan finished.  Nothing is read back."""
+    n = _fpfh_check('fpfh_radius', ws, table, sorted_points, offsets, sorted_keys)
+    check(_native.load().hfl_fpfh_radius(ws.r2.data_ptr(), ws.proven.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(),
+                                         ws.starts.data_ptr(), sorted_points.data_ptr(), sorted_keys.data_ptr(),
+                                         table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
+                                         offsets.data_ptr(), n, _stream()), 'hfl_fpfh_radius')
+    return ws.counter
+
+
+def fpfh_spfh(ws: FpfhWorkspace, sorted_points: torch.Tensor, sorted_normals: torch.Tensor, sorted_keys: torch.Tensor,
+              offsets: torch.Tensor, table: KnnGridTable, theta_table: np.ndarray):
+    """`hfl_fpfh_spfh` after `fpfh_radius` on the same workspace: sorted_normals (P, 3) fp32 = normals[perm] and the (10, 2)
+    float64 numpy table of (cos e_k, sin e_k) -> (ws.hist (P, 33) int32, ws.pairs (P,) int32), by SORTED position."""
+    n = _fpfh_check('fpfh_spfh', ws, table, sorted_points, offsets, sorted_keys)
+    _dev(sorted_normals)
+    _points_check('fpfh_spfh', sorted_normals)
+    if int(sorted_normals.shape[0]) != n:
+        raise TypeError('fpfh_spfh: %d normals for %d points' % (int(sorted_normals.shape[0]), n))
+    if not isinstance(theta_table, np.ndarray) or theta_table.dtype != np.float64 or theta_table.shape != (10, 2) or \
+            not theta_table.flags['C_CONTIGUOUS']:
+        raise TypeError('fpfh_spfh: contiguous (10, 2) float64 numpy table of the theta edges expected')
+    check(_native.load().hfl_fpfh_spfh(ws.hist.data_ptr(), ws.pairs.data_ptr(), ws.r2.data_ptr(), ws.proven.data_ptr(),
+                                       ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
+                                       sorted_points.data_ptr(), sorted_normals.data_ptr(), sorted_keys.data_ptr(),
+                                       table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
+                                       offsets.data_ptr(), n, theta_table.ctypes.data, _stream()), 'hfl_fpfh_spfh')
+    return ws.hist, ws.pairs
+
+
+def fpfh_combine(ws: FpfhWorkspace, sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor,
+                 offsets: torch.Tensor, table: KnnGridTable, out: torch.Tensor = None):
+    """`hfl_fpfh_combine` after `fpfh_spfh` on the same workspace -> fpfh (P, 33) fp32 in INPUT order."""
+    n = _fpfh_check('fpfh_combine', ws, table, sorted_points, offsets, sorted_keys)
+    _dev(perm)
+    _vector_check('fpfh_combine', perm, torch.int64, n, 'permutation')
+    fpfh = out if out is not None else torch.empty((n, FPFH_DIM), dtype=torch.float32, device=sorted_points.device)
+    _dev(fpfh)
+    if fpfh.dtype != torch.float32 or tuple(fpfh.shape) != (n, FPFH_DIM) or not fpfh.is_contiguous():
+        raise TypeError('fpfh_combine: contiguous (%d, %d) float32 output expected' % (n, FPFH_DIM))
+    check(_native.load().hfl_fpfh_combine(fpfh.data_ptr(), ws.hist.data_ptr(), ws.pairs.data_ptr(), ws.r2.data_ptr(),
+                                          ws.proven.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(),
+                                          ws.starts.data_ptr(), sorted_points.data_ptr(), sorted_keys.data_ptr(),
+                                          perm.data_ptr(), table.host.ctypes.data, table.device.data_ptr(), table.batch,
+                                          table.cells, offsets.data_ptr(), n, _stream()), 'hfl_fpfh_combine')
+    return fpfh
+
+
+def feature_tiles(lengths):
+    """The tile table of `hfl_feature_nn` from the query lengths of the pairs on the host: `overlap_tiles`, whose
+    OVERLAP_ROWS rows per workgroup are the FEATURE_ROWS of this kernel."""
+    return overlap_tiles(lengths)
+
+
+def feature_nn(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
+               tiles: torch.Tensor):
+    """`hfl_feature_nn`: two ragged batches of (N, D) fp32 feature rows of the same P pairs, 1 <= D <= FEATURE_MAX_DIM, and
+    the (n_tiles, 2) int64 device copy of `feature_tiles` -> (dist2 (Nq,) fp32, idx (Nq,) int32): every query row's smallest
+    squared distance to a target row of its pair and that row's index within the pair, +inf and -1 where the pair has no
+    target.  Rows the table does not cover stay unwritten."""
+    _dev(queries, q_offsets, targets, t_offsets, tiles)
+    for t in (queries, targets):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise TypeError('feature_nn: contiguous (N, D) float32 rows expected')
+    dim = int(queries.shape[1])
+    if int(targets.shape[1]) != dim or not 1 <= dim <= FEATURE_MAX_DIM:
+        raise ValueError('feature_nn: both sides need the same D in 1..%d, got %d and %d'
+                         % (FEATURE_MAX_DIM, dim, int(targets.shape[1])))
+    _offsets_check('feature_nn', q_offsets)
+    _offsets_check('feature_nn', t_offsets)
+    pairs = int(q_offsets.shape[0]) - 1
+    if int(t_offsets.shape[0]) - 1 != pairs:
+        raise ValueError('feature_nn: the query batch and the target batch differ in their number of pairs')
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('feature_nn: contiguous (n_tiles, 2) int64 tile table expected')
+    n_q = int(queries.shape[0])
+    dist2 = torch.empty(n_q, dtype=torch.float32, device=queries.device)
+    idx = torch.empty(n_q, dtype=torch.int32, device=queries.device)
+    if n_q and tiles.shape[0]:
+        check(_native.load().hfl_feature_nn(dist2.data_ptr(), idx.data_ptr(), queries.data_ptr(), q_offsets.data_ptr(), n_q,
+                                            _some(targets).data_ptr(), t_offsets.data_ptr(), int(targets.shape[0]), dim,
+                                            tiles.data_ptr(), int(tiles.shape[0]), pairs, _stream()), 'hfl_feature_nn')
+    return dist2, idx
+
+
 def outlier_threshold(avg: torch.Tensor, offsets: torch.Tensor, std_ratio: float):
     """`hfl_outlier_threshold`: avg (P,) fp32 and offsets (B + 1,) int64 on the GPU -> stats (B, 4) float64: mean, std,
     mean + std_ratio std and the number of valid rows (avg > 0) of every cloud."""

@@ -415,6 +415,48 @@ int hfl_knn_normals(float* normals, float* curvature, int32_t* counts, int32_t* 
                     const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
                     const int64_t* cloud_offsets, int64_t n_points, const double* viewpoints, int phases,
                     hfl_stream_t stream);
+/* FPFH descriptors by the same search (csrc/fpfh.hip; defined in hotformerloc_amd/fpfh.py and DESIGN.md section 7k), in
+ * three calls that share the workspace of hfl_knn_mean_dist.  Everything but the last output is indexed by SORTED position.
+ *
+ * hfl_fpfh_radius: r2[j] = the k-th smallest fp32 squared distance of sorted point j within its cloud (itself included);
+ * proven[j] = 1 when the 3 x 3 x 3 block of cells round j holds every point with d2 <= r2[j], else 0 and j is in pending;
+ * *counter = the number of such points.  The cell-start table, a memset and two launches on `stream`. */
+int hfl_fpfh_radius(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                    const float* sorted_points, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
+                    const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
+                    hfl_stream_t stream);
+/* hist (P, 33) int32 and pairs (P) int32: the SPFH histogram of every point over N(j) = { q : d2 <= r2[j] } and the number
+ * of pairs binned; three groups of 11 bins (theta, f2, f3 of the Darboux frame).  sorted_normals (P, 3) = normals[perm]; a
+ * zero row, or one with a component that is not finite, is "no normal".  theta_table_host: HOST memory, 10 rows of
+ * (cos e_k, sin e_k) float64 for the bin edges e_k = -pi + 2 pi k / 11, k = 1 .. 10 (passed on by value; not finite:
+ * HFL_EINVAL).  r2, proven, pending, counter and cell_starts as hfl_fpfh_radius left them.  Integers only: the result
+ * depends on no order and no grid.  Two launches on `stream`, 33 KiB of LDS a workgroup. */
+int hfl_fpfh_spfh(int32_t* hist, int32_t* pairs, const float* r2, const uint8_t* proven, const int32_t* pending,
+                  const int32_t* counter, const int32_t* cell_starts, const float* sorted_points,
+                  const float* sorted_normals, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
+                  const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
+                  const double* theta_table_host, hfl_stream_t stream);
+/* fpfh (P, 33) fp32 in INPUT order (row perm[j]): SPFH_j(b) = 100 hist[j][b] / pairs[j] (0 without pairs) plus, per group,
+ * (100 / s) W(b) when s > 0, with W(b) = the sum over q in N(j), q != j, d2 > 0, pairs[q] > 0 of
+ * hist[q][b] ((100 / pairs[q]) / d2) in float64 and s the sum of W over the group.  The sums run in an order fixed by the
+ * sort and the grid: two calls give the same bits, two grids agree to an fp32 ulp.  Two launches on `stream`. */
+int hfl_fpfh_combine(float* fpfh, const int32_t* hist, const int32_t* pairs, const float* r2, const uint8_t* proven,
+                     const int32_t* pending, const int32_t* counter, const int32_t* cell_starts, const float* sorted_points,
+                     const int64_t* sorted_keys, const int64_t* perm, const hfl_knn_grid* grids_host,
+                     const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
+                     hfl_stream_t stream);
+#define HFL_FEATURE_ROWS 512              /* query rows of a 256-thread workgroup of hfl_feature_nn (two per thread) */
+#define HFL_FEATURE_MAX_DIM 64            /* columns of a feature row */
+/* Nearest neighbour in feature space for ragged pairs, brute force (csrc/fpfh.hip): queries (Nq, dim) and targets (Nt, dim)
+ * fp32 with (n_pairs + 1) int64 offsets each, 1 <= dim <= HFL_FEATURE_MAX_DIM; tiles (n_tiles, 2) int64 rows of (pair, first
+ * query row), HFL_FEATURE_ROWS rows of one pair per workgroup.  dist2[r] = the smallest squared distance from query row r to
+ * a target row of its pair, in fp32 on the differences: d0 d0, then fmaf(dc, dc, .) for c = 1 .. dim - 1; idx[r] = that
+ * row's index within the pair's targets, the lowest of equal distances; +inf and -1 for an empty target.  Inputs must be
+ * finite (a query whose every d2 is +inf or NaN reports -1).  Rows the table does not cover stay unwritten.  One launch on
+ * `stream`, no atomics.  n_targets, n_tiles or n_pairs at 2^31 or more: HFL_ECAPACITY. */
+int hfl_feature_nn(float* dist2, int32_t* idx, const float* queries, const int64_t* q_offsets, int64_t n_queries,
+                   const float* targets, const int64_t* t_offsets, int64_t n_targets, int dim, const int64_t* tiles,
+                   int64_t n_tiles, int64_t n_pairs, hfl_stream_t stream);
 /* stats (batch, 4) float64 = (mean, std, mean + std_ratio std, n_valid) over the valid rows (avg > 0) of every cloud, std
  * with n_valid - 1 in the denominator; float64, summed in the order of hfl_pair_stats.  No valid row: mean = NaN; one: std =
  * NaN.  One workgroup per cloud, one launch on `stream`.  std_ratio <= 0 or not finite: HFL_EINVAL. */
