@@ -1,8 +1,8 @@
 // FPFH descriptors of every point of a ragged batch of clouds, and nearest-neighbour correspondences in descriptor space.
 // Both are DEFINED in hotformerloc_amd/fpfh.py (module docstring) and DESIGN.md section 7k; this file and the numpy routes
-// there follow that definition.  The search is the exact grid search of csrc/outliers.hip and csrc/normals.hip
-// (knn_common.h), on the batch that `outliers.sorted_batch` lays out; everything here works on SORTED positions and only the
-// last kernel un-permutes.
+// there follow that definition.  The search is the exact grid search of knn_common.h, which csrc/outliers.hip and
+// csrc/normals.hip run as well, on the batch that `outliers.sorted_batch` lays out; everything here works on SORTED
+// positions and only the last kernel un-permutes.
 //
 //   hfl_fpfh_radius    the cell-start table; one thread per point scans the 3 x 3 x 3 block of cells round its own for r2,
 //                      the k-th smallest fp32 squared distance (the sorted register list), and notes whether the
@@ -102,50 +102,26 @@ fpfh_radius_kernel(float* __restrict__ r2s, uint8_t* __restrict__ proven, int32_
                    const int64_t* __restrict__ off, int batch, int64_t n) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n) return;
-  const int c = find_cloud(off, batch, j);
-  const hfl_knn_grid g = grids[c];
-  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
-  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
-  const int64_t local = skeys[j] - g.cell_base;
-  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
-  bool resolved = false;
-  float r2 = INFINITY;
-  if (local >= 0 && local < cells && g.k >= 1 && g.k <= K) {   // a key off its own grid goes to the whole-cloud scan
-    const KnnBlock blk = knn_block(g, local);
-    KnnList<K> list;
-    list.clear();
-    knn_block_scan(g, blk, starts, first, last,
-                   [&](int32_t q) { list.insert(knn_d2(px, py, pz, spts + (int64_t)q * 3)); });
-    r2 = list.kth(g.k);
-    resolved = r2 < knn_block_bound(px, py, pz, g, blk);
-  }
-  r2s[j] = r2;
-  proven[j] = resolved ? 1 : 0;
-  if (!resolved) knn_append_pending(pending, counter, j, n);
+  const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
+  KnnList<K> list;
+  const KnnFirst f = knn_first_scan(list, p, spts, starts);
+  r2s[j] = f.r2;
+  proven[j] = f.resolved ? 1 : 0;
+  if (!f.resolved) knn_append_pending(pending, counter, j, n);
 }
 
-// a wave per pending point, the waves striding over the list; every loop bound is the same in all lanes of a wave
 template <int K>
 __global__ void __launch_bounds__(kOutThreads)
 fpfh_radius_fallback_kernel(float* __restrict__ r2s, const int32_t* __restrict__ pending,
                             const int32_t* __restrict__ counter, const float* __restrict__ spts,
                             const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, int batch, int64_t n) {
-  const int lane = threadIdx.x & (HFL_WAVE - 1);
-  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
-  const int64_t count = min((int64_t)max(*counter, 0), n);
-  for (int64_t e = wave; e < count; e += waves) {
-    const int64_t j = pending[e];
-    if (j < 0 || j >= n) continue;
-    const int c = find_cloud(off, batch, j);
-    const int64_t first = max(off[c], (int64_t)0), last = min(off[c + 1], n);
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int c, int64_t first, int64_t last) {
     const int k = min(max(grids[c].k, 1), K);
-    const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
     KnnList<K> list;
-    list.clear();
-    for (int64_t q = first + lane; q < last; q += HFL_WAVE) list.insert(knn_d2(px, py, pz, spts + q * 3));
-    const float r2 = knn_wave_kth<K>(list, k, lane);
-    if (lane == 0) r2s[j] = r2;
-  }
+    knn_cloud_first(list, spts[j * 3 + 0], spts[j * 3 + 1], spts[j * 3 + 2], spts, first, last);
+    const float r2 = knn_wave_kth(list, k);
+    if (knn_lane() == 0) r2s[j] = r2;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------ SPFH
@@ -153,6 +129,15 @@ fpfh_radius_fallback_kernel(float* __restrict__ r2s, const int32_t* __restrict__
 struct SpfhPoint {
   float px, py, pz, nx, ny, nz, r2;
 };
+
+__device__ __forceinline__ SpfhPoint spfh_point(const float* __restrict__ spts, const float* __restrict__ snrm,
+                                                const float* __restrict__ r2s, int64_t j) {
+  SpfhPoint p;
+  p.px = spts[j * 3 + 0], p.py = spts[j * 3 + 1], p.pz = spts[j * 3 + 2];
+  p.nx = snrm[j * 3 + 0], p.ny = snrm[j * 3 + 1], p.nz = snrm[j * 3 + 2];
+  p.r2 = r2s[j];
+  return p;
+}
 
 __device__ __forceinline__ int spfh_visit(int32_t (*s_hist)[kOutThreads], int col, const SpfhPoint& p, int64_t j, int64_t q,
                                           const float* __restrict__ spts, const float* __restrict__ snrm,
@@ -180,23 +165,15 @@ fpfh_spfh_kernel(int32_t* __restrict__ hist, int32_t* __restrict__ pairs, const 
   const int col = threadIdx.x;
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n || !proven[j]) return;
-  const int c = find_cloud(off, batch, j);
-  const hfl_knn_grid g = grids[c];
-  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
-  const int64_t local = skeys[j] - g.cell_base;
-  if (local < 0 || local >= (int64_t)g.nx * g.ny * g.nz) return;   // never with proven[j] set by hfl_fpfh_radius
+  const KnnPoint at = knn_point(spts, skeys, grids, off, batch, n, j);
+  if (!at.on_grid<HFL_KNN_MAX_NEIGHBOURS>()) return;             // never with proven[j] set by hfl_fpfh_radius
 #pragma unroll
   for (int b = 0; b < FP_DIM; ++b) s_hist[b][col] = 0;
-  SpfhPoint p;
-  p.px = spts[j * 3 + 0], p.py = spts[j * 3 + 1], p.pz = spts[j * 3 + 2];
-  p.nx = snrm[j * 3 + 0], p.ny = snrm[j * 3 + 1], p.nz = snrm[j * 3 + 2];
-  p.r2 = r2s[j];
+  const SpfhPoint p = spfh_point(spts, snrm, r2s, j);
   int m = 0;
-  if (has_normal(p.nx, p.ny, p.nz)) {
-    const KnnBlock blk = knn_block(g, local);
-    knn_block_scan(g, blk, starts, first, last,
+  if (has_normal(p.nx, p.ny, p.nz))
+    knn_block_scan(at.g, knn_block(at.g, at.local), starts, at.first, at.last,
                    [&](int32_t q) { m += spfh_visit(s_hist, col, p, j, (int64_t)q, spts, snrm, tab); });
-  }
 #pragma unroll
   for (int b = 0; b < FP_DIM; ++b) hist[j * FP_DIM + b] = s_hist[b][col];
   pairs[j] = m;
@@ -208,23 +185,14 @@ fpfh_spfh_fallback_kernel(int32_t* __restrict__ hist, int32_t* __restrict__ pair
                           const float* __restrict__ spts, const float* __restrict__ snrm,
                           const int64_t* __restrict__ off, ThetaTable tab, int batch, int64_t n) {
   __shared__ int32_t s_hist[FP_DIM][kOutThreads];
-  const int col = threadIdx.x, lane = threadIdx.x & (HFL_WAVE - 1);
-  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
-  const int64_t count = min((int64_t)max(*counter, 0), n);
-  for (int64_t e = wave; e < count; e += waves) {
-    const int64_t j = pending[e];
-    if (j < 0 || j >= n) continue;
-    const int c = find_cloud(off, batch, j);
-    const int64_t first = max(off[c], (int64_t)0), last = min(off[c + 1], n);
+  const int col = threadIdx.x, lane = knn_lane();
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int, int64_t first, int64_t last) {
 #pragma unroll
     for (int b = 0; b < FP_DIM; ++b) s_hist[b][col] = 0;
-    SpfhPoint p;
-    p.px = spts[j * 3 + 0], p.py = spts[j * 3 + 1], p.pz = spts[j * 3 + 2];
-    p.nx = snrm[j * 3 + 0], p.ny = snrm[j * 3 + 1], p.nz = snrm[j * 3 + 2];
-    p.r2 = r2s[j];
+    const SpfhPoint p = spfh_point(spts, snrm, r2s, j);
     int m = 0;
     if (has_normal(p.nx, p.ny, p.nz))                          // the same in every lane
-      for (int64_t q = first + lane; q < last; q += HFL_WAVE) m += spfh_visit(s_hist, col, p, j, q, spts, snrm, tab);
+      knn_cloud_scan(first, last, [&](int64_t q) { m += spfh_visit(s_hist, col, p, j, q, spts, snrm, tab); });
 #pragma unroll
     for (int b = 0; b < FP_DIM; ++b) {                         // integers: any order gives the same sum
       const int32_t v = wave_sum(s_hist[b][col]);
@@ -232,7 +200,7 @@ fpfh_spfh_fallback_kernel(int32_t* __restrict__ hist, int32_t* __restrict__ pair
     }
     m = wave_sum(m);
     if (lane == 0) pairs[j] = m;
-  }
+  });
 }
 
 // --------------------------------------------------------------------------------------------------------------- combine
@@ -276,18 +244,14 @@ fpfh_combine_kernel(float* __restrict__ fpfh, const int32_t* __restrict__ hist, 
                     const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, int batch, int64_t n) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n || !proven[j]) return;
-  const int c = find_cloud(off, batch, j);
-  const hfl_knn_grid g = grids[c];
-  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
-  const int64_t local = skeys[j] - g.cell_base;
-  if (local < 0 || local >= (int64_t)g.nx * g.ny * g.nz) return;
-  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2], r2 = r2s[j];
+  const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
+  if (!p.on_grid<HFL_KNN_MAX_NEIGHBOURS>()) return;
+  const float r2 = r2s[j];
   double w[FP_DIM];
 #pragma unroll
   for (int b = 0; b < FP_DIM; ++b) w[b] = 0.0;
-  const KnnBlock blk = knn_block(g, local);
-  knn_block_scan(g, blk, starts, first, last,                  // sorted-position order
-                 [&](int32_t q) { combine_visit(w, px, py, pz, r2, j, (int64_t)q, spts, hist, pairs); });
+  knn_block_scan(p.g, knn_block(p.g, p.local), starts, p.first, p.last,      // sorted-position order
+                 [&](int32_t q) { combine_visit(w, p.px, p.py, p.pz, r2, j, (int64_t)q, spts, hist, pairs); });
   combine_finish(fpfh, perm[j], n, w, hist + j * FP_DIM, pairs[j]);
 }
 
@@ -296,48 +260,17 @@ fpfh_combine_fallback_kernel(float* __restrict__ fpfh, const int32_t* __restrict
                              const float* __restrict__ r2s, const int32_t* __restrict__ pending,
                              const int32_t* __restrict__ counter, const float* __restrict__ spts,
                              const int64_t* __restrict__ perm, const int64_t* __restrict__ off, int batch, int64_t n) {
-  const int lane = threadIdx.x & (HFL_WAVE - 1);
-  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
-  const int64_t count = min((int64_t)max(*counter, 0), n);
-  for (int64_t e = wave; e < count; e += waves) {
-    const int64_t j = pending[e];
-    if (j < 0 || j >= n) continue;
-    const int c = find_cloud(off, batch, j);
-    const int64_t first = max(off[c], (int64_t)0), last = min(off[c + 1], n);
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int, int64_t first, int64_t last) {
     const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2], r2 = r2s[j];
     double w[FP_DIM];
 #pragma unroll
     for (int b = 0; b < FP_DIM; ++b) w[b] = 0.0;
-    for (int64_t q = first + lane; q < last; q += HFL_WAVE)    // a lane's points in ascending order
-      combine_visit(w, px, py, pz, r2, j, q, spts, hist, pairs);
+    knn_cloud_scan(first, last,                                // a lane's points in ascending order
+                   [&](int64_t q) { combine_visit(w, px, py, pz, r2, j, q, spts, hist, pairs); });
 #pragma unroll
     for (int b = 0; b < FP_DIM; ++b) w[b] = wave_sum(w[b]);     // the lanes by the xor butterfly 32 .. 1
-    if (lane == 0) combine_finish(fpfh, perm[j], n, w, hist + j * FP_DIM, pairs[j]);
-  }
-}
-
-bool fpfh_args_ok(int batch, int64_t n_points, int64_t n_cells) { return batch >= 1 && n_points >= batch && n_cells >= 1; }
-
-bool fpfh_capacity_ok(int batch, int64_t n_points, int64_t n_cells) {
-  return batch <= HFL_VOXEL_MAX_CLOUDS && n_points <= HFL_VOXEL_MAX_POINTS && n_cells <= HFL_KNN_MAX_CELLS;
-}
-
-unsigned fallback_blocks(int64_t n, hipStream_t s) {
-  return (unsigned)min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
-}
-
-template <int K>
-int radius_launch(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* starts, const float* spts,
-                  const int64_t* skeys, const hfl_knn_grid* grids, const int64_t* off, int batch, int64_t n, int64_t n_cells,
-                  hipStream_t s) {
-  knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
-  hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
-  if (e != hipSuccess) return (int)e;
-  fpfh_radius_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(r2, proven, pending, counter, spts, skeys,
-                                                                                   starts, grids, off, batch, n);
-  fpfh_radius_fallback_kernel<K><<<fallback_blocks(n, s), kOutThreads, 0, s>>>(r2, pending, counter, spts, grids, off, batch,
-                                                                               n);
-  HFL_RETURN_LAST_ERROR();
+    if (knn_lane() == 0) combine_finish(fpfh, perm[j], n, w, hist + j * FP_DIM, pairs[j]);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------ feature NN
@@ -436,19 +369,19 @@ extern "C" int hfl_fpfh_radius(float* r2, uint8_t* proven, int32_t* pending, int
       sorted_points == nullptr || sorted_keys == nullptr || grids_host == nullptr || grids == nullptr ||
       cloud_offsets == nullptr)
     return HFL_EINVAL;
-  if (!fpfh_args_ok(batch, n_points, n_cells)) return HFL_EINVAL;
-  if (!fpfh_capacity_ok(batch, n_points, n_cells)) return HFL_ECAPACITY;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (k_max <= 8)
-    return radius_launch<8>(r2, proven, pending, counter, cell_starts, sorted_points, sorted_keys, grids, cloud_offsets, batch,
-                            n_points, n_cells, s);
-  if (k_max <= 16)
-    return radius_launch<16>(r2, proven, pending, counter, cell_starts, sorted_points, sorted_keys, grids, cloud_offsets,
-                             batch, n_points, n_cells, s);
-  return radius_launch<32>(r2, proven, pending, counter, cell_starts, sorted_points, sorted_keys, grids, cloud_offsets, batch,
-                           n_points, n_cells, s);
+  const int64_t n = n_points;
+  if (const int rc = knn_launch_starts(cell_starts, counter, sorted_keys, n, n_cells, HFL_KNN_PHASE_ALL, s)) return rc;
+  return knn_dispatch_k(k_max, [&](auto kc) -> int {
+    constexpr int K = decltype(kc)::value;
+    fpfh_radius_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+        r2, proven, pending, counter, sorted_points, sorted_keys, cell_starts, grids, cloud_offsets, batch, n);
+    fpfh_radius_fallback_kernel<K><<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(r2, pending, counter, sorted_points,
+                                                                                     grids, cloud_offsets, batch, n);
+    HFL_RETURN_LAST_ERROR();
+  });
 }
 
 extern "C" int hfl_fpfh_spfh(int32_t* hist, int32_t* pairs, const float* r2, const uint8_t* proven, const int32_t* pending,
@@ -461,10 +394,8 @@ extern "C" int hfl_fpfh_spfh(int32_t* hist, int32_t* pairs, const float* r2, con
       sorted_keys == nullptr || grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr ||
       theta_table_host == nullptr)
     return HFL_EINVAL;
-  if (!fpfh_args_ok(batch, n_points, n_cells)) return HFL_EINVAL;
-  if (!fpfh_capacity_ok(batch, n_points, n_cells)) return HFL_ECAPACITY;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   ThetaTable tab;
   for (int k = 0; k < FP_EDGES; ++k) {                           // rows of (cos e_k, sin e_k)
     tab.c[k] = theta_table_host[2 * k];
@@ -475,7 +406,7 @@ extern "C" int hfl_fpfh_spfh(int32_t* hist, int32_t* pairs, const float* r2, con
   fpfh_spfh_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, s>>>(
       hist, pairs, r2, proven, sorted_points, sorted_normals, sorted_keys, cell_starts, grids, cloud_offsets, tab, batch,
       n_points);
-  fpfh_spfh_fallback_kernel<<<fallback_blocks(n_points, s), kOutThreads, 0, s>>>(
+  fpfh_spfh_fallback_kernel<<<knn_fallback_blocks(n_points, s), kOutThreads, 0, s>>>(
       hist, pairs, r2, pending, counter, sorted_points, sorted_normals, cloud_offsets, tab, batch, n_points);
   HFL_RETURN_LAST_ERROR();
 }
@@ -489,14 +420,12 @@ extern "C" int hfl_fpfh_combine(float* fpfh, const int32_t* hist, const int32_t*
       counter == nullptr || cell_starts == nullptr || sorted_points == nullptr || sorted_keys == nullptr ||
       perm == nullptr || grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
     return HFL_EINVAL;
-  if (!fpfh_args_ok(batch, n_points, n_cells)) return HFL_EINVAL;
-  if (!fpfh_capacity_ok(batch, n_points, n_cells)) return HFL_ECAPACITY;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   fpfh_combine_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, s>>>(
       fpfh, hist, pairs, r2, proven, sorted_points, sorted_keys, perm, cell_starts, grids, cloud_offsets, batch, n_points);
-  fpfh_combine_fallback_kernel<<<fallback_blocks(n_points, s), kOutThreads, 0, s>>>(
+  fpfh_combine_fallback_kernel<<<knn_fallback_blocks(n_points, s), kOutThreads, 0, s>>>(
       fpfh, hist, pairs, r2, pending, counter, sorted_points, perm, cloud_offsets, batch, n_points);
   HFL_RETURN_LAST_ERROR();
 }

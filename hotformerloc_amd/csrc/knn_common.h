@@ -1,13 +1,15 @@
-// What the exact grid k-nearest-neighbour searches share (csrc/outliers.hip: the mean neighbour distance; csrc/normals.hip:
-// the neighbourhood covariance; csrc/fpfh.hip: the descriptor's three passes): the launch shape, the cell-start table, the
-// fp32 squared distance, the sorted register list, the completeness bound and the host check of the grids; and, as
-// functions, the search itself -- the 3 x 3 x 3 block and its scan, the bound of a block, the merge of a wave's lists, the
-// list of unresolved points (`knn_block` .. `knn_append_pending`, which csrc/fpfh.hip runs three times over; the two older
-// files spell the same steps out in their query kernels and stay as they are, so that their code objects do not change).
-// hotformerloc_amd/outliers.py and DESIGN.md section 7g define the search; every file that includes this is built with
-// -ffp-contract=off.
+// The exact grid k-nearest-neighbour search over a ragged batch, once, for everything that runs it (csrc/outliers.hip: the
+// mean neighbour distance; csrc/normals.hip: the neighbourhood covariance; csrc/fpfh.hip: the descriptor's three passes).
+// Here are the launch shape, the cell-start table, the fp32 squared distance, the sorted register list and the host checks;
+// what a thread knows of its point (`KnnPoint`); the first scan of the 3 x 3 x 3 block with its completeness bound
+// (`knn_first_scan` on `knn_block`, `knn_block_scan`, `knn_block_bound`); the list of unresolved points
+// (`knn_append_pending`) and the wave-per-point walk over it (`knn_for_pending`, `knn_cloud_scan`, `knn_wave_merge`).  The
+// kernels of the three files keep only what they do with a neighbour.  hotformerloc_amd/outliers.py and DESIGN.md section
+// 7g define the search; every file that includes this is built with -ffp-contract=off.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "ragged_common.h"
 
@@ -59,10 +61,10 @@ struct KnnList {
     for (int i = 0; i < K; ++i) r = fmaxf(r, i < k ? v[i] : -INFINITY);
     return r;
   }
-  __device__ __forceinline__ void pop() {
+  __device__ __forceinline__ void pop_if(bool mine) {          // selects, not a branch: a wave runs both sides anyway
 #pragma unroll
-    for (int i = 0; i + 1 < K; ++i) v[i] = v[i + 1];
-    v[K - 1] = INFINITY;
+    for (int i = 0; i + 1 < K; ++i) v[i] = mine ? v[i + 1] : v[i];
+    v[K - 1] = mine ? INFINITY : v[K - 1];
   }
 };
 
@@ -116,20 +118,78 @@ __device__ __forceinline__ float knn_block_bound(float px, float py, float pz, c
   return __fmul_rn(gap, gap);
 }
 
-// the k-th smallest value of the 64 lists of a wave, the same in every lane: the smallest head of the lists, k times; one
-// lane gives up one copy per round, so equal values stay a multiset.  The lists are consumed.
-template <int K>
-__device__ __forceinline__ float knn_wave_kth(KnnList<K>& list, int k, int lane) {
+// What a thread of a query kernel knows of the point at sorted position j: its cloud, the cloud's grid and range of sorted
+// positions (clamped to the arrays), its cell on that grid, its coordinates
+struct KnnPoint {
+  int c;
+  hfl_knn_grid g;
+  int32_t first, last;
+  int64_t local;
+  float px, py, pz;
+  template <int K>
+  __device__ __forceinline__ bool on_grid() const {            // a key off its own grid goes to the whole-cloud scan
+    return local >= 0 && local < (int64_t)g.nx * g.ny * g.nz && g.k >= 1 && g.k <= K;
+  }
+};
+
+__device__ __forceinline__ KnnPoint knn_point(const float* __restrict__ spts, const int64_t* __restrict__ skeys,
+                                              const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off,
+                                              int batch, int64_t n, int64_t j) {
+  KnnPoint p;
+  p.c = find_cloud(off, batch, j);
+  p.g = grids[p.c];
+  p.first = (int32_t)max(off[p.c], (int64_t)0), p.last = (int32_t)min(off[p.c + 1], n);
+  p.local = skeys[j] - p.g.cell_base;
+  p.px = spts[j * 3 + 0], p.py = spts[j * 3 + 1], p.pz = spts[j * 3 + 2];
+  return p;
+}
+
+// The first scan of a point: the K smallest squared distances of its block in `list`, r2 the k-th smallest of them, and
+// whether the bound proves that every point with d2 <= r2 lies in the block.  Off the grid: +inf, not resolved, no block.
+struct KnnFirst {
+  KnnBlock blk = {};
   float r2 = INFINITY;
+  bool resolved = false;
+};
+
+template <int K>
+__device__ __forceinline__ KnnFirst knn_first_scan(KnnList<K>& list, const KnnPoint& p, const float* __restrict__ spts,
+                                                   const int32_t* __restrict__ starts) {
+  KnnFirst f;
+  list.clear();
+  if (p.on_grid<K>()) {
+    f.blk = knn_block(p.g, p.local);
+    knn_block_scan(p.g, f.blk, starts, p.first, p.last,
+                   [&](int32_t q) { list.insert(knn_d2(p.px, p.py, p.pz, spts + (int64_t)q * 3)); });
+    f.r2 = list.kth(p.g.k);
+    f.resolved = f.r2 < knn_block_bound(p.px, p.py, p.pz, p.g, f.blk);
+  }
+  return f;
+}
+
+__device__ __forceinline__ int knn_lane() { return threadIdx.x & (HFL_WAVE - 1); }
+
+// f(m) for the k smallest values of the 64 lists of a wave in ascending order, m the same in every lane: the smallest head
+// of the lists, k times; one lane gives up one copy per round, so equal values stay a multiset.  The lists are consumed.
+template <int K, typename F>
+__device__ __forceinline__ void knn_wave_merge(KnnList<K>& list, int k, F&& f) {
+  const int lane = knn_lane();
   for (int r = 0; r < k; ++r) {
     const float head = list.v[0];
     float m = head;
 #pragma unroll
     for (int s = HFL_WAVE / 2; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, HFL_WAVE));
     const unsigned long long owners = __ballot(head == m);
-    if (lane == __ffsll((long long)owners) - 1) list.pop();
-    r2 = m;
+    list.pop_if(lane == __ffsll((long long)owners) - 1);
+    f(m);
   }
+}
+
+// the k-th smallest value of the 64 lists: the last of the k rounds
+template <int K>
+__device__ __forceinline__ float knn_wave_kth(KnnList<K>& list, int k) {
+  float r2 = INFINITY;
+  knn_wave_merge(list, k, [&](float m) { r2 = m; });
   return r2;
 }
 
@@ -138,13 +198,42 @@ __device__ __forceinline__ float knn_wave_kth(KnnList<K>& list, int k, int lane)
 __device__ __forceinline__ void knn_append_pending(int32_t* __restrict__ pending, int32_t* __restrict__ counter, int64_t j,
                                                    int64_t n) {
   const unsigned long long mask = __ballot(1);
-  const int lane = threadIdx.x & (HFL_WAVE - 1);
+  const int lane = knn_lane();
   const int leader = __ffsll((long long)mask) - 1;
   int base = 0;
   if (lane == leader) base = atomicAdd(counter, __popcll(mask));
   base = __shfl(base, leader, HFL_WAVE);
   const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
   if (slot >= 0 && slot < n) pending[slot] = (int32_t)j;
+}
+
+// f(q) for the sorted positions [first, last) of a cloud, dealt to the lanes of a wave: a lane's points in ascending order
+template <typename F>
+__device__ __forceinline__ void knn_cloud_scan(int64_t first, int64_t last, F&& f) {
+  for (int64_t q = first + knn_lane(); q < last; q += HFL_WAVE) f(q);
+}
+
+// the first pass of a fallback kernel: every lane's K smallest squared distances from p to its share of the cloud
+template <int K>
+__device__ __forceinline__ void knn_cloud_first(KnnList<K>& list, float px, float py, float pz,
+                                                const float* __restrict__ spts, int64_t first, int64_t last) {
+  list.clear();
+  knn_cloud_scan(first, last, [&](int64_t q) { list.insert(knn_d2(px, py, pz, spts + q * 3)); });
+}
+
+// The fallback kernels: a wave per pending point, the waves striding over the list; every loop bound is the same in all
+// lanes of a wave.  f(j, c, first, last): the sorted position, its cloud and the cloud's range clamped to the arrays.
+template <typename F>
+__device__ __forceinline__ void knn_for_pending(const int32_t* __restrict__ pending, const int32_t* __restrict__ counter,
+                                                const int64_t* __restrict__ off, int batch, int64_t n, F&& f) {
+  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
+  const int64_t count = min((int64_t)max(*counter, 0), n);
+  for (int64_t e = wave; e < count; e += waves) {
+    const int64_t j = pending[e];
+    if (j < 0 || j >= n) continue;
+    const int c = find_cloud(off, batch, j);
+    f(j, c, max(off[c], (int64_t)0), min(off[c + 1], n));
+  }
 }
 
 // every grid inside the cell table and every field in range, before anything runs
@@ -163,6 +252,35 @@ bool knn_grids_ok(const hfl_knn_grid* g, int batch, int64_t n_cells, int* k_max)
   }
   *k_max = big;
   return true;
+}
+
+// what every entry point of the search checks after its pointers, in this order: the arguments, the capacity, the grids
+int knn_call_check(int batch, int64_t n_points, int64_t n_cells, const hfl_knn_grid* grids_host, int* k_max) {
+  if (batch < 1 || n_points < batch || n_cells < 1) return HFL_EINVAL;
+  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  return knn_grids_ok(grids_host, batch, n_cells, k_max) ? HFL_OK : HFL_EINVAL;
+}
+
+// the workgroups of a fallback kernel: a wave per point at the most, eight workgroups a CU
+unsigned knn_fallback_blocks(int64_t n, hipStream_t s) {
+  return (unsigned)min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
+}
+
+// f(std::integral_constant<int, K>) for the smallest list length K that holds k_max
+template <typename F>
+int knn_dispatch_k(int k_max, F&& f) {
+  if (k_max <= 8) return f(std::integral_constant<int, 8>());
+  if (k_max <= 16) return f(std::integral_constant<int, 16>());
+  return f(std::integral_constant<int, 32>());
+}
+
+// what a search launches before its query kernel: the cell-start table, and the counter of the pending list at zero
+int knn_launch_starts(int32_t* starts, int32_t* counter, const int64_t* skeys, int64_t n, int64_t n_cells, int phases,
+                      hipStream_t s) {
+  if (phases & HFL_KNN_PHASE_STARTS)
+    knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
+  if (phases & HFL_KNN_PHASE_QUERY) return (int)hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+  return HFL_OK;
 }
 
 }  // namespace

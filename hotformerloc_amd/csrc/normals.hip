@@ -1,8 +1,9 @@
 // Surface normals and the surface variation of every point of a ragged batch of clouds: the covariance of the point's k
 // nearest neighbours and its smallest eigenvector (open3d's estimate_normals with KDTreeSearchParamKNN, plus a curvature).
 // The estimate is DEFINED in hotformerloc_amd/normals.py (module docstring) and DESIGN.md section 7j; this file and the
-// numpy route there follow that definition.  The search is the exact grid search of csrc/outliers.hip (knn_common.h), on
-// the batch that `outliers.sorted_batch` lays out; what is new is the accumulation on top of it.
+// numpy route there follow that definition.  The search is the exact grid search of knn_common.h, which csrc/outliers.hip
+// and csrc/fpfh.hip run as well, on the batch that `outliers.sorted_batch` lays out; this file holds the accumulation on
+// top of it.
 //
 //   hfl_knn_normals   (1) the dense cell-start table (knn_cell_starts_kernel); (2) one thread per point in sorted order
 //                     scans the 3 x 3 x 3 block of cells round its own twice: the first scan keeps the K smallest fp32
@@ -115,73 +116,28 @@ normals_query_kernel(float* __restrict__ normals, float* __restrict__ curvature,
                      int batch, int64_t n) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n) return;
-  const int c = find_cloud(off, batch, j);
-  const hfl_knn_grid g = grids[c];
-  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
-  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
-  const int64_t local = skeys[j] - g.cell_base;
-  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
-  const int k = g.k;
-  bool resolved = false;
-  if (local >= 0 && local < cells && k >= 1 && k <= K) {       // a key off its own grid goes to the whole-cloud scan
-    const int ix = (int)(local % g.nx), iy = (int)((local / g.nx) % g.ny), iz = (int)(local / ((int64_t)g.nx * g.ny));
-    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
-    const int y0 = max(iy - 1, 0), y1 = min(iy + 1, g.ny - 1);
-    const int z0 = max(iz - 1, 0), z1 = min(iz + 1, g.nz - 1);
-    KnnList<K> list;
-    list.clear();
-#pragma unroll 1
-    for (int z = z0; z <= z1; ++z)
-#pragma unroll 1
-      for (int y = y0; y <= y1; ++y) {
-        const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;      // the cells x0 .. x1 of a line are adjacent
-        const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
-#pragma unroll 1
-        for (int32_t q = s; q < e; ++q) list.insert(knn_d2(px, py, pz, spts + (int64_t)q * 3));
-      }
-    float gap = knn_face_gap(px, g.ox, g.cell, x0, x1, g.nx - 1, g.mx);
-    gap = fminf(gap, knn_face_gap(py, g.oy, g.cell, y0, y1, g.ny - 1, g.my));
-    gap = fminf(gap, knn_face_gap(pz, g.oz, g.cell, z0, z1, g.nz - 1, g.mz));
-    gap = __fmul_rn(fmaxf(gap, 0.f), kFaceShrink);
-    const float r2 = list.kth(k);
-    resolved = r2 < __fmul_rn(gap, gap);
-    if (resolved) {                                            // the list is dead from here on: the sums take its registers
-      double sums[NR_SUMS];
+  const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
+  KnnList<K> list;
+  const KnnFirst f = knn_first_scan(list, p, spts, starts);
+  if (f.resolved) {                                            // the list is dead from here on: the sums take its registers
+    double sums[NR_SUMS];
 #pragma unroll
-      for (int i = 0; i < NR_SUMS; ++i) sums[i] = 0.0;
-      int m = 0;
-#pragma unroll 1
-      for (int z = z0; z <= z1; ++z)
-#pragma unroll 1
-        for (int y = y0; y <= y1; ++y) {
-          const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;
-          const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
-#pragma unroll 1
-          for (int32_t q = s; q < e; ++q) {                    // sorted-position order
-            const float* w = spts + (int64_t)q * 3;
-            if (knn_d2(px, py, pz, w) <= r2) {
-              normal_add(sums, px, py, pz, w);
-              ++m;
-            }
-          }
-        }
-      normal_finish(normals, curvature, counts, perm[j], n, sums, m, px, py, pz,
-                    views != nullptr ? views + 3 * (int64_t)c : nullptr);
-    }
-  }
-  if (!resolved) {                                             // one integer add per wave; the order of the list is free
-    const unsigned long long mask = __ballot(1);
-    const int lane = threadIdx.x & (HFL_WAVE - 1);
-    const int leader = __ffsll((long long)mask) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(counter, __popcll(mask));
-    base = __shfl(base, leader, HFL_WAVE);
-    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-    if (slot >= 0 && slot < n) pending[slot] = (int32_t)j;
+    for (int i = 0; i < NR_SUMS; ++i) sums[i] = 0.0;
+    int m = 0;
+    knn_block_scan(p.g, f.blk, starts, p.first, p.last, [&](int32_t q) {      // sorted-position order
+      const float* w = spts + (int64_t)q * 3;
+      if (knn_d2(p.px, p.py, p.pz, w) <= f.r2) {
+        normal_add(sums, p.px, p.py, p.pz, w);
+        ++m;
+      }
+    });
+    normal_finish(normals, curvature, counts, perm[j], n, sums, m, p.px, p.py, p.pz,
+                  views != nullptr ? views + 3 * (int64_t)p.c : nullptr);
+  } else {
+    knn_append_pending(pending, counter, j, n);
   }
 }
 
-// a wave per pending point, the waves striding over the list; every loop bound is the same in all lanes of a wave
 template <int K>
 __global__ void __launch_bounds__(kOutThreads)
 normals_fallback_kernel(float* __restrict__ normals, float* __restrict__ curvature, int32_t* __restrict__ counts,
@@ -189,69 +145,33 @@ normals_fallback_kernel(float* __restrict__ normals, float* __restrict__ curvatu
                         const float* __restrict__ spts, const int64_t* __restrict__ perm,
                         const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off,
                         const double* __restrict__ views, int batch, int64_t n) {
-  const int lane = threadIdx.x & (HFL_WAVE - 1);
-  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
-  const int64_t count = min((int64_t)max(*counter, 0), n);
-  for (int64_t e = wave; e < count; e += waves) {
-    const int64_t j = pending[e];
-    if (j < 0 || j >= n) continue;
-    const int c = find_cloud(off, batch, j);
-    const int64_t first = max(off[c], (int64_t)0), last = min(off[c + 1], n);
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int c, int64_t first, int64_t last) {
     const int k = min(max(grids[c].k, 1), K);
     const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
-    float r2 = INFINITY;
+    float r2;
     {
       KnnList<K> list;
-      list.clear();
-      for (int64_t q = first + lane; q < last; q += HFL_WAVE) list.insert(knn_d2(px, py, pz, spts + q * 3));
-      for (int r = 0; r < k; ++r) {                            // ascending: the smallest head of the 64 lists, k times
-        const float head = list.v[0];
-        float m = head;
-#pragma unroll
-        for (int s = HFL_WAVE / 2; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, HFL_WAVE));
-        const unsigned long long owners = __ballot(head == m);
-        if (lane == __ffsll((long long)owners) - 1) list.pop();  // one lane gives up one copy: equal values stay a multiset
-        r2 = m;                                                // after k rounds: the k-th smallest
-      }
+      knn_cloud_first(list, px, py, pz, spts, first, last);
+      r2 = knn_wave_kth(list, k);
     }
     double sums[NR_SUMS];
 #pragma unroll
     for (int i = 0; i < NR_SUMS; ++i) sums[i] = 0.0;
     int m = 0;
-    for (int64_t q = first + lane; q < last; q += HFL_WAVE) {  // a lane's points in ascending order
+    knn_cloud_scan(first, last, [&](int64_t q) {               // a lane's points in ascending order
       const float* w = spts + q * 3;
       if (knn_d2(px, py, pz, w) <= r2) {
         normal_add(sums, px, py, pz, w);
         ++m;
       }
-    }
+    });
 #pragma unroll
-    for (int i = 0; i < NR_SUMS; ++i) sums[i] = wave_sum(sums[i]);
+    for (int i = 0; i < NR_SUMS; ++i) sums[i] = wave_sum(sums[i]);    // the lanes by the xor butterfly 32 .. 1
     m = wave_sum(m);
-    if (lane == 0)
+    if (knn_lane() == 0)
       normal_finish(normals, curvature, counts, perm[j], n, sums, m, px, py, pz,
                     views != nullptr ? views + 3 * (int64_t)c : nullptr);
-  }
-}
-
-template <int K>
-int normals_launch(float* normals, float* curvature, int32_t* counts, int32_t* pending, int32_t* counter, int32_t* starts,
-                   const float* spts, const int64_t* skeys, const int64_t* perm, const hfl_knn_grid* grids, const int64_t* off,
-                   const double* views, int batch, int64_t n, int64_t n_cells, int phases, hipStream_t s) {
-  if (phases & HFL_KNN_PHASE_STARTS)
-    knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
-  if (phases & HFL_KNN_PHASE_QUERY) {
-    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return (int)e;
-    normals_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
-        normals, curvature, counts, pending, counter, spts, skeys, perm, starts, grids, off, views, batch, n);
-  }
-  if (phases & HFL_KNN_PHASE_FALLBACK) {
-    const int64_t blocks = min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
-    normals_fallback_kernel<K><<<(unsigned)blocks, kOutThreads, 0, s>>>(normals, curvature, counts, pending, counter, spts,
-                                                                        perm, grids, off, views, batch, n);
-  }
-  HFL_RETURN_LAST_ERROR();
+  });
 }
 
 }  // namespace
@@ -265,17 +185,21 @@ extern "C" int hfl_knn_normals(float* normals, float* curvature, int32_t* counts
       cell_starts == nullptr || sorted_points == nullptr || sorted_keys == nullptr || perm == nullptr ||
       grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
     return HFL_EINVAL;
-  if (batch < 1 || n_points < batch || n_cells < 1 || phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
-  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  if (phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (k_max <= 8)
-    return normals_launch<8>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
-                             cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
-  if (k_max <= 16)
-    return normals_launch<16>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
-                              cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
-  return normals_launch<32>(normals, curvature, counts, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids,
-                            cloud_offsets, viewpoints, batch, n_points, n_cells, phases, s);
+  const int64_t n = n_points;
+  if (const int rc = knn_launch_starts(cell_starts, counter, sorted_keys, n, n_cells, phases, s)) return rc;
+  return knn_dispatch_k(k_max, [&](auto kc) -> int {
+    constexpr int K = decltype(kc)::value;
+    if (phases & HFL_KNN_PHASE_QUERY)
+      normals_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+          normals, curvature, counts, pending, counter, sorted_points, sorted_keys, perm, cell_starts, grids, cloud_offsets,
+          viewpoints, batch, n);
+    if (phases & HFL_KNN_PHASE_FALLBACK)
+      normals_fallback_kernel<K><<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(
+          normals, curvature, counts, pending, counter, sorted_points, perm, grids, cloud_offsets, viewpoints, batch, n);
+    HFL_RETURN_LAST_ERROR();
+  });
 }

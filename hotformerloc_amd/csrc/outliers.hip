@@ -18,9 +18,11 @@
 //   hfl_outlier_mask       keep = avg > 0 and double(avg) < threshold
 //   hfl_radius_mask        keep = sqrt(x x + y y) <= radius_max in float64
 //
-// The answer of (2) and (3) is a pure function of the multiset of the k smallest squared distances, which both find exactly,
-// so it does not depend on the cell size, on which of the two resolved a point, or on the order of the list.  No
-// floating-point atomics (one integer add per wave appends to the list); no workgroup waits for another.
+// The search of (1) to (3) is written in knn_common.h, for this file, csrc/normals.hip and csrc/fpfh.hip; here is what is
+// done with the k smallest distances.  The answer of (2) and (3) is a pure function of the multiset of the k smallest
+// squared distances, which both find exactly, so it does not depend on the cell size, on which of the two resolved a point,
+// or on the order of the list.  No floating-point atomics (one integer add per wave appends to the list); no workgroup
+// waits for another.
 #include <math.h>
 
 #include "knn_common.h"
@@ -69,87 +71,36 @@ knn_query_kernel(float* __restrict__ avg, int32_t* __restrict__ pending, int32_t
                  int batch, int64_t n) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n) return;
-  const int c = find_cloud(off, batch, j);
-  const hfl_knn_grid g = grids[c];
-  const int32_t first = (int32_t)max(off[c], (int64_t)0), last = (int32_t)min(off[c + 1], n);
-  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
-  const int64_t local = skeys[j] - g.cell_base;
+  const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
   const int64_t row = perm[j];
-  const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
-  const int k = g.k;
+  const int k = p.g.k;
   KnnList<K> list;
-  list.clear();
-  bool resolved = false;
-  if (local >= 0 && local < cells && k >= 1 && k <= K) {       // a key off its own grid goes to the whole-cloud scan
-    const int ix = (int)(local % g.nx), iy = (int)((local / g.nx) % g.ny), iz = (int)(local / ((int64_t)g.nx * g.ny));
-    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
-    const int y0 = max(iy - 1, 0), y1 = min(iy + 1, g.ny - 1);
-    const int z0 = max(iz - 1, 0), z1 = min(iz + 1, g.nz - 1);
-#pragma unroll 1
-    for (int z = z0; z <= z1; ++z)
-#pragma unroll 1
-      for (int y = y0; y <= y1; ++y) {
-        const int64_t line = g.cell_base + ((int64_t)z * g.ny + y) * g.nx;      // the cells x0 .. x1 of a line are adjacent
-        const int32_t s = max(starts[line + x0], first), e = min(starts[line + x1 + 1], last);
-#pragma unroll 1
-        for (int32_t q = s; q < e; ++q) list.insert(knn_d2(px, py, pz, spts + (int64_t)q * 3));
-      }
-    float gap = knn_face_gap(px, g.ox, g.cell, x0, x1, g.nx - 1, g.mx);
-    gap = fminf(gap, knn_face_gap(py, g.oy, g.cell, y0, y1, g.ny - 1, g.my));
-    gap = fminf(gap, knn_face_gap(pz, g.oz, g.cell, z0, z1, g.nz - 1, g.mz));
-    gap = __fmul_rn(fmaxf(gap, 0.f), kFaceShrink);
-    resolved = list.kth(k) < __fmul_rn(gap, gap);
-  }
-  if (resolved) {
+  if (knn_first_scan(list, p, spts, starts).resolved) {
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < K; ++i)
       if (i < k) sum = __fadd_rn(sum, knn_sqrt(list.v[i]));
     if (row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
-  } else {                                                     // one integer add per wave; the order of the list is free
-    const unsigned long long mask = __ballot(1);
-    const int lane = threadIdx.x & (HFL_WAVE - 1);
-    const int leader = __ffsll((long long)mask) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(counter, __popcll(mask));
-    base = __shfl(base, leader, HFL_WAVE);
-    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-    if (slot >= 0 && slot < n) pending[slot] = (int32_t)j;
+  } else {
+    knn_append_pending(pending, counter, j, n);
   }
 }
 
-// a wave per pending point, the waves striding over the list; every loop bound is the same in all lanes of a wave
 template <int K>
 __global__ void __launch_bounds__(kOutThreads)
 knn_fallback_kernel(float* __restrict__ avg, const int32_t* __restrict__ pending, const int32_t* __restrict__ counter,
                     const float* __restrict__ spts, const int64_t* __restrict__ perm, const hfl_knn_grid* __restrict__ grids,
                     const int64_t* __restrict__ off, int batch, int64_t n) {
-  const int lane = threadIdx.x & (HFL_WAVE - 1);
-  const int64_t wave = (int64_t)blockIdx.x * kOutWaves + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * kOutWaves;
-  const int64_t count = min((int64_t)max(*counter, 0), n);
-  for (int64_t e = wave; e < count; e += waves) {
-    const int64_t j = pending[e];
-    if (j < 0 || j >= n) continue;
-    const int c = find_cloud(off, batch, j);
-    const int64_t first = off[c], last = min(off[c + 1], n);
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int c, int64_t first, int64_t last) {
     const int k = min(max(grids[c].k, 1), K);
     const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
     KnnList<K> list;
-    list.clear();
-    for (int64_t q = first + lane; q < last; q += HFL_WAVE) list.insert(knn_d2(px, py, pz, spts + q * 3));
+    knn_cloud_first(list, px, py, pz, spts, first, last);
     float sum = 0.f;
-    for (int r = 0; r < k; ++r) {                              // ascending: the smallest head of the 64 lists, k times
-      const float head = list.v[0];
-      float m = head;
-#pragma unroll
-      for (int s = HFL_WAVE / 2; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, HFL_WAVE));
-      const unsigned long long owners = __ballot(head == m);
-      if (lane == __ffsll((long long)owners) - 1) list.pop();  // one lane gives up one copy: equal values stay a multiset
-      sum = __fadd_rn(sum, knn_sqrt(m));
-    }
+    knn_wave_merge(list, k, [&](float m) { sum = __fadd_rn(sum, knn_sqrt(m)); });      // ascending
     const int64_t row = perm[j];
-    if (lane == 0 && row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
-  }
+    if (knn_lane() == 0 && row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
+  });
 }
 
 // the sums below are `block_sum` of ragged_common.h, the order of hfl_pair_stats: a thread's rows in ascending order, the
@@ -206,25 +157,6 @@ radius_mask_kernel(uint8_t* __restrict__ keep, const float* __restrict__ pts, in
 
 bool out_batch_ok(int batch, int64_t n_points) { return batch >= 1 && n_points >= batch; }
 
-template <int K>
-int knn_launch(float* avg, int32_t* pending, int32_t* counter, int32_t* starts, const float* spts, const int64_t* skeys,
-               const int64_t* perm, const hfl_knn_grid* grids, const int64_t* off, int batch, int64_t n, int64_t n_cells,
-               int phases, hipStream_t s) {
-  if (phases & HFL_KNN_PHASE_STARTS)
-    knn_cell_starts_kernel<<<(unsigned)hfl_cdiv(n_cells + 1, kOutThreads), kOutThreads, 0, s>>>(starts, skeys, n, n_cells);
-  if (phases & HFL_KNN_PHASE_QUERY) {
-    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return (int)e;
-    knn_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(avg, pending, counter, spts, skeys, perm,
-                                                                                  starts, grids, off, batch, n);
-  }
-  if (phases & HFL_KNN_PHASE_FALLBACK) {
-    const int64_t blocks = min(hfl_cdiv(n, kOutWaves), (int64_t)hfl_stream_cus(s) * 8);
-    knn_fallback_kernel<K><<<(unsigned)blocks, kOutThreads, 0, s>>>(avg, pending, counter, spts, perm, grids, off, batch, n);
-  }
-  HFL_RETURN_LAST_ERROR();
-}
-
 }  // namespace
 
 extern "C" int hfl_cloud_nonfinite(int32_t* flags, const float* points, const int64_t* cloud_offsets, int batch,
@@ -244,10 +176,8 @@ extern "C" int hfl_knn_cell_keys(int64_t* keys, const hfl_knn_grid* grids_host, 
                                  hfl_stream_t stream) {
   if (keys == nullptr || grids_host == nullptr || grids == nullptr || points == nullptr || cloud_offsets == nullptr)
     return HFL_EINVAL;
-  if (!out_batch_ok(batch, n_points) || n_cells < 1) return HFL_EINVAL;
-  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   knn_cell_keys_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(
       keys, grids, points, cloud_offsets, batch, n_points);
   HFL_RETURN_LAST_ERROR();
@@ -260,19 +190,22 @@ extern "C" int hfl_knn_mean_dist(float* avg, int32_t* pending, int32_t* counter,
   if (avg == nullptr || pending == nullptr || counter == nullptr || cell_starts == nullptr || sorted_points == nullptr ||
       sorted_keys == nullptr || perm == nullptr || grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
     return HFL_EINVAL;
-  if (!out_batch_ok(batch, n_points) || n_cells < 1 || phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
-  if (batch > HFL_VOXEL_MAX_CLOUDS || n_points > HFL_VOXEL_MAX_POINTS || n_cells > HFL_KNN_MAX_CELLS) return HFL_ECAPACITY;
+  if (phases < 1 || phases > HFL_KNN_PHASE_ALL) return HFL_EINVAL;
   int k_max = 0;
-  if (!knn_grids_ok(grids_host, batch, n_cells, &k_max)) return HFL_EINVAL;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (k_max <= 8)
-    return knn_launch<8>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
-                         n_points, n_cells, phases, s);
-  if (k_max <= 16)
-    return knn_launch<16>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
-                          n_points, n_cells, phases, s);
-  return knn_launch<32>(avg, pending, counter, cell_starts, sorted_points, sorted_keys, perm, grids, cloud_offsets, batch,
-                        n_points, n_cells, phases, s);
+  const int64_t n = n_points;
+  if (const int rc = knn_launch_starts(cell_starts, counter, sorted_keys, n, n_cells, phases, s)) return rc;
+  return knn_dispatch_k(k_max, [&](auto kc) -> int {
+    constexpr int K = decltype(kc)::value;
+    if (phases & HFL_KNN_PHASE_QUERY)
+      knn_query_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+          avg, pending, counter, sorted_points, sorted_keys, perm, cell_starts, grids, cloud_offsets, batch, n);
+    if (phases & HFL_KNN_PHASE_FALLBACK)
+      knn_fallback_kernel<K><<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(avg, pending, counter, sorted_points, perm,
+                                                                              grids, cloud_offsets, batch, n);
+    HFL_RETURN_LAST_ERROR();
+  });
 }
 
 extern "C" int hfl_outlier_threshold(double* stats, const float* avg, const int64_t* cloud_offsets, int batch,

@@ -2291,23 +2291,33 @@ class KnnWorkspace:
         self.counter = torch.zeros(1, dtype=torch.int32, device=device)
 
 
+def _knn_sorted_check(what: str, table: KnnGridTable, sorted_points: torch.Tensor, offsets: torch.Tensor,
+                      workspace: KnnWorkspace, label: str, *vectors):
+    """What every call on a sorted batch checks before it launches: `_knn_check`, the (P,) int64 `vectors` (`label` names
+    them in the message), and a workspace made for this batch (a fresh one for None).  -> (P, the workspace)"""
+    _knn_check(what, table, sorted_points, offsets)
+    _dev(*vectors)
+    n = int(sorted_points.shape[0])
+    for t in vectors:
+        _vector_check(what, t, torch.int64, n, label)
+    ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
+    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
+        raise ValueError('%s: the workspace was made for another batch' % what)
+    _dev(ws.starts, ws.pending, ws.counter)
+    return n, ws
+
+
 def knn_mean_dist(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
                   table: KnnGridTable, phases: int = KNN_PHASE_ALL, workspace: KnnWorkspace = None, out: torch.Tensor = None):
     """`hfl_knn_mean_dist`: the ascending keys of `knn_cell_keys`, the sort's permutation and `points[perm]` -> (avg (P,)
     fp32 in INPUT order: the mean distance to the k nearest points of the own cloud, pending (1,) int32 on the GPU: how many
     points the whole-cloud scan had to finish).  `phases` runs single launches on a `workspace` and an `out` kept from an
     earlier call.  Nothing is read back."""
-    _knn_check('knn_mean_dist', table, sorted_points, offsets)
-    _dev(sorted_keys, perm)
-    n = int(sorted_points.shape[0])
-    for t in (sorted_keys, perm):
-        _vector_check('knn_mean_dist', t, torch.int64, n, 'keys and permutation')
-    ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
-    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
-        raise ValueError('knn_mean_dist: the workspace was made for another batch')
+    n, ws = _knn_sorted_check('knn_mean_dist', table, sorted_points, offsets, workspace, 'keys and permutation', sorted_keys,
+                              perm)
     avg = out if out is not None else torch.empty(n, dtype=torch.float32, device=sorted_points.device)
     _vector_check('knn_mean_dist', avg, torch.float32, n, 'output')
-    _dev(ws.starts, ws.pending, ws.counter, avg)
+    _dev(avg)
     check(_native.load().hfl_knn_mean_dist(avg.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
                                            sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(),
                                            table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
@@ -2321,22 +2331,15 @@ def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: to
     """`hfl_knn_normals`: the arguments of `knn_mean_dist` -> (normals (P, 3) fp32, curvature (P,) fp32, counts (P,) int32,
     all in INPUT order, pending (1,) int32 on the GPU).  `viewpoints`: (B, 3) float64 on the GPU, one per cloud, or None for
     the upward rule.  Nothing is read back."""
-    _knn_check('knn_normals', table, sorted_points, offsets)
-    _dev(sorted_keys, perm)
-    n = int(sorted_points.shape[0])
-    for t in (sorted_keys, perm):
-        _vector_check('knn_normals', t, torch.int64, n, 'keys and permutation')
+    n, ws = _knn_sorted_check('knn_normals', table, sorted_points, offsets, workspace, 'keys and permutation', sorted_keys,
+                              perm)
     if viewpoints is not None:
         _dev(viewpoints)
         if viewpoints.dtype != torch.float64 or tuple(viewpoints.shape) != (table.batch, 3) or not viewpoints.is_contiguous():
             raise TypeError('knn_normals: contiguous (%d, 3) float64 viewpoints expected' % table.batch)
-    ws = workspace if workspace is not None else KnnWorkspace(n, table.cells, sorted_points.device)
-    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
-        raise ValueError('knn_normals: the workspace was made for another batch')
     normals = torch.empty((n, 3), dtype=torch.float32, device=sorted_points.device)
     curvature = torch.empty(n, dtype=torch.float32, device=sorted_points.device)
     counts = torch.empty(n, dtype=torch.int32, device=sorted_points.device)
-    _dev(ws.starts, ws.pending, ws.counter)
     check(_native.load().hfl_knn_normals(normals.data_ptr(), curvature.data_ptr(), counts.data_ptr(), ws.pending.data_ptr(),
                                          ws.counter.data_ptr(), ws.starts.data_ptr(), sorted_points.data_ptr(),
                                          sorted_keys.data_ptr(), perm.data_ptr(), table.host.ctypes.data,
@@ -2365,12 +2368,8 @@ class FpfhWorkspace(KnnWorkspace):
 
 def _fpfh_check(what: str, ws: FpfhWorkspace, table: KnnGridTable, sorted_points: torch.Tensor, offsets: torch.Tensor,
                 sorted_keys: torch.Tensor) -> int:
-    _knn_check(what, table, sorted_points, offsets)
-    n = int(sorted_points.shape[0])
-    _dev(sorted_keys, ws.starts, ws.pending, ws.counter, ws.r2, ws.proven, ws.hist, ws.pairs)
-    _vector_check(what, sorted_keys, torch.int64, n, 'keys')
-    if tuple(ws.starts.shape) != (table.cells + 1,) or tuple(ws.pending.shape) != (n,):
-        raise ValueError('%s: the workspace was made for another batch' % what)
+    n, _ = _knn_sorted_check(what, table, sorted_points, offsets, ws, 'keys', sorted_keys)
+    _dev(ws.r2, ws.proven, ws.hist, ws.pairs)
     return n
 
 
