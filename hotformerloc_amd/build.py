@@ -69,7 +69,7 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, 'hfl_common.h'), os.path.join(CSRC, 'x3_math.h'), os.path.join(CSRC, 'stage_stream.h'),
                os.path.join(CSRC, 'prep_common.h'), os.path.join(CSRC, 'ragged_common.h'), os.path.join(CSRC, 'ln_row.h'),
-               os.path.join(CSRC, 'knn_common.h'), os.path.join(CSRC, 'jacobi3.h'),
+               os.path.join(CSRC, 'knn_common.h'), os.path.join(CSRC, 'pair_scan.h'), os.path.join(CSRC, 'jacobi3.h'),
                os.path.join(HERE, '..', 'include', 'hotformerloc_hip.h')]
     jobs = []
     for src in SOURCES:

@@ -15,11 +15,12 @@
 //   hfl_fpfh_combine   the same scan once more: the neighbours' histograms weighted by 100 / pairs_j / d2 and added in
 //                      float64 (33 accumulators in registers, every index a constant), normalised per group, added to the
 //                      point's own SPFH, rounded to fp32 and stored at row perm[j].
-//   hfl_feature_nn     brute force over descriptor rows, modelled on hfl_nn_dist (csrc/overlap.hip): a workgroup of 256
-//                      threads owns 512 consecutive query rows of one pair, two rows per thread in registers; the pair's
-//                      target rows stream through a 24 KiB LDS tile, row after row, every lane reading the same row by
-//                      broadcast ds_read_b128.  d2 = d0 d0, then fmaf(dc, dc, d2) for c = 1 .. D - 1; a strict `<` over
-//                      ascending target rows keeps the lowest index of equal distances.
+//   hfl_feature_nn     brute force over descriptor rows on the pieces of pair_scan.h (the workgroup's tile, the rule that
+//                      keeps a candidate, the entry point's checks): a workgroup of 256 threads owns 512 consecutive query
+//                      rows of one pair, two rows per thread in registers; the pair's target rows stream through a 24 KiB
+//                      LDS tile, row after row, every lane reading the same row by broadcast ds_read_b128.  d2 = d0 d0, then
+//                      fmaf(dc, dc, d2) for c = 1 .. D - 1, over ascending target rows.  The distance over D columns and
+//                      the row-major tile are this file's own.
 //
 // Histograms and pair counts are integers and the neighbourhood is a pure function of the input, so they do not depend on
 // the grid or on any order.  The float64 sums of hfl_fpfh_combine run in an order fixed by the sort and the grid.  No
@@ -28,6 +29,7 @@
 #include <math.h>
 
 #include "knn_common.h"
+#include "pair_scan.h"
 
 namespace {
 
@@ -276,8 +278,8 @@ fpfh_combine_fallback_kernel(float* __restrict__ fpfh, const int32_t* __restrict
 // ------------------------------------------------------------------------------------------------------------ feature NN
 constexpr int FN_THREADS = 256;
 constexpr int FN_QPT = HFL_FEATURE_ROWS / FN_THREADS;            // query rows a thread keeps in registers
-constexpr int FN_TILE_FLOATS = 6144;                             // 24 KiB of static LDS, the tile of nn_dist_kernel
-static_assert(HFL_FEATURE_ROWS % FN_THREADS == 0 && FN_QPT >= 1, "whole query rows per thread");
+constexpr int FN_TILE_FLOATS = 6144;                             // 24 KiB of static LDS, as much as the planes of pair_scan3
+static_assert(HFL_FEATURE_ROWS % FN_THREADS == 0 && FN_QPT >= 1 && HFL_FEATURE_MAX_DIM <= 64, "whole rows per thread, a launch per D");
 
 // DP: the row length in registers and in LDS, D rounded up to one of a few multiples of four.  The columns past D hold 0 on
 // both sides, and fmaf(0, 0, acc) == acc: the padding changes no bit.
@@ -290,33 +292,30 @@ feature_nn_kernel(float* __restrict__ dist2, int32_t* __restrict__ idx, const fl
   static_assert(DP % 4 == 0 && DP >= 4 && DP <= HFL_FEATURE_MAX_DIM, "rows of whole float4");
   constexpr int TILE_ROWS = FN_TILE_FLOATS / DP;
   __shared__ __align__(16) float s_t[TILE_ROWS * DP];
-  const int64_t p = tiles[2 * (int64_t)blockIdx.x], row0 = tiles[2 * (int64_t)blockIdx.x + 1];
-  if (p < 0 || p >= n_pairs || row0 < 0) return;                 // uniform over the workgroup
-  // the offsets are clamped to the arrays, so a wrong table or offset cannot make the kernel read or write outside them
-  const int64_t q_end = min(q_off[p + 1], n_queries);
-  const int64_t t_begin = max(t_off[p], (int64_t)0), t_end = min(t_off[p + 1], n_targets);
-
+  PairTile w;
+  if (!pair_tile(w, tiles, n_pairs)) return;
+  pair_ranges(w, q_off, n_queries, t_off, n_targets);
   float q[FN_QPT][DP], best[FN_QPT];
   int32_t at[FN_QPT];
 #pragma unroll
   for (int r = 0; r < FN_QPT; ++r) {
-    const int64_t row = row0 + r * FN_THREADS + threadIdx.x;
-    const bool valid = row < q_end;
+    const int64_t row = w.row<FN_THREADS>(r);
+    const bool valid = row < w.q_end;
 #pragma unroll
     for (int c = 0; c < DP; ++c) q[r][c] = (valid && c < dim) ? queries[row * dim + c] : 0.f;
     best[r] = INFINITY;
     at[r] = -1;
   }
 
-  for (int64_t tile = t_begin; tile < t_end; tile += TILE_ROWS) {
-    const int len = (int)min((int64_t)TILE_ROWS, t_end - tile);
+  for (int64_t tile = w.t_begin; tile < w.t_end; tile += TILE_ROWS) {
+    const int len = (int)min((int64_t)TILE_ROWS, w.t_end - tile);
     __syncthreads();                                             // the previous tile has been read by every wave
     for (int e = threadIdx.x; e < len * DP; e += FN_THREADS) {
       const int r = e / DP, c = e - r * DP;
       s_t[e] = c < dim ? targets[(tile + r) * dim + c] : 0.f;
     }
     __syncthreads();
-    const int32_t base = (int32_t)(tile - t_begin);              // < 2^31: the entry point bounds n_targets
+    const int32_t base = (int32_t)(tile - w.t_begin);            // < 2^31: the entry point bounds n_targets
     for (int k = 0; k < len; ++k) {                              // ascending target row
       const float4* row = reinterpret_cast<const float4*>(&s_t[k * DP]);   // the same address in every lane: broadcast
       float acc[FN_QPT];
@@ -333,18 +332,14 @@ feature_nn_kernel(float* __restrict__ dist2, int32_t* __restrict__ idx, const fl
           }
       }
 #pragma unroll
-      for (int r = 0; r < FN_QPT; ++r) {
-        const bool closer = acc[r] < best[r];                    // strict: of equal distances the lowest index stays
-        best[r] = closer ? acc[r] : best[r];
-        at[r] = closer ? base + k : at[r];
-      }
+      for (int r = 0; r < FN_QPT; ++r) pair_keep_closer(acc[r], base + k, best[r], at[r]);
     }
   }
 
 #pragma unroll
   for (int r = 0; r < FN_QPT; ++r) {
-    const int64_t row = row0 + r * FN_THREADS + threadIdx.x;
-    if (row < q_end) {
+    const int64_t row = w.row<FN_THREADS>(r);
+    if (row < w.q_end) {
       dist2[row] = best[r];                                      // +inf and -1: an empty target
       idx[row] = at[r];
     }
@@ -433,27 +428,20 @@ extern "C" int hfl_fpfh_combine(float* fpfh, const int32_t* hist, const int32_t*
 extern "C" int hfl_feature_nn(float* dist2, int32_t* idx, const float* queries, const int64_t* q_offsets, int64_t n_queries,
                               const float* targets, const int64_t* t_offsets, int64_t n_targets, int dim,
                               const int64_t* tiles, int64_t n_tiles, int64_t n_pairs, hfl_stream_t stream) {
-  if (dist2 == nullptr || idx == nullptr || queries == nullptr || q_offsets == nullptr || targets == nullptr ||
-      t_offsets == nullptr || tiles == nullptr || n_queries < 0 || n_targets < 0 || n_tiles < 0 || n_pairs < 1 ||
-      dim < 1 || dim > HFL_FEATURE_MAX_DIM)
-    return HFL_EINVAL;
-  // a target index is an int32, the grid is one-dimensional
-  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  if (n_tiles == 0) return HFL_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  return pair_scan_call({dist2, idx, queries, q_offsets, targets, t_offsets, tiles}, dim >= 1 && dim <= HFL_FEATURE_MAX_DIM,
+                        n_queries, n_targets, n_tiles, n_pairs, [&] {
 #define HFL_FEATURE_NN_CASE(DP)                                                                                        \
-  if (dim <= DP) {                                                                                                     \
-    feature_nn_launch<DP>(dist2, idx, queries, q_offsets, n_queries, targets, t_offsets, n_targets, dim, tiles, n_tiles, \
-                          (int)n_pairs, s);                                                                            \
-    HFL_RETURN_LAST_ERROR();                                                                                           \
-  }
-  HFL_FEATURE_NN_CASE(4)
-  HFL_FEATURE_NN_CASE(8)
-  HFL_FEATURE_NN_CASE(16)
-  HFL_FEATURE_NN_CASE(24)
-  HFL_FEATURE_NN_CASE(36)
-  HFL_FEATURE_NN_CASE(48)
-  HFL_FEATURE_NN_CASE(64)
+  if (dim <= DP)                                                                                                       \
+    return feature_nn_launch<DP>(dist2, idx, queries, q_offsets, n_queries, targets, t_offsets, n_targets, dim, tiles, \
+                                 n_tiles, (int)n_pairs, s);
+    HFL_FEATURE_NN_CASE(4)
+    HFL_FEATURE_NN_CASE(8)
+    HFL_FEATURE_NN_CASE(16)
+    HFL_FEATURE_NN_CASE(24)
+    HFL_FEATURE_NN_CASE(36)
+    HFL_FEATURE_NN_CASE(48)
+    HFL_FEATURE_NN_CASE(64)                                      // dim <= HFL_FEATURE_MAX_DIM = 64: one of them launches
 #undef HFL_FEATURE_NN_CASE
-  return HFL_EINVAL;
+  });
 }

@@ -4,20 +4,13 @@
 // distance it never computed.  A batch of P pairs is ragged: the points of all clouds concatenated as (N_total, 3) fp32 with
 // (P + 1) int64 offsets, cloud p at rows [off[p], off[p + 1]).
 //
-// hfl_transform_points: one thread per point, the owning pair found by a binary search over the offsets.  Per coordinate c
-// with matrix row (r0 r1 r2 t) one fmaf chain in this order:
-//     acc = fmaf(r0, x, t);  acc = fmaf(r1, y, acc);  out_c = fmaf(r2, z, acc).
+// hfl_transform_points: one thread per point, the owning pair found by a binary search over the offsets; every coordinate
+// is `rigid_coord` of pair_scan.h.
 //
-// hfl_nn_dist: brute force, exact.  A workgroup of 256 threads owns OV_ROWS consecutive query rows of one pair (the host's
-// tile table says which), each thread keeping OV_QPT = OV_ROWS / 256 query points in registers; the pair's target cloud
-// streams through LDS in tiles of OV_TILE points stored as three coordinate planes, and every lane reads the same four
-// target points (three broadcast ds_read_b128, conflict-free) for its 4 x OV_QPT tests.  A last tile that is no multiple of
-// four is padded with points at +inf, whose d2 is +inf and never wins.  fp32 on the differences themselves,
-//     d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)),
-// the convention of pairwise.hip, one correctly rounded square root at the end.  Tie rule: the lowest target index wins.
-// A query is scanned by one thread over ascending indices with a strict `<`, so there are no partial results to combine:
-// if the scan of one query is ever split, the parts combine by (d2, index) lexicographically.  Inputs must be finite and
-// small enough that d2 does not overflow; this is not checked (a query whose every d2 is +inf or NaN reports index -1).
+// hfl_nn_dist: brute force, exact: the scan of pair_scan.h.  A workgroup of 256 threads owns OV_ROWS consecutive query rows
+// of one pair (the host's tile table says which), each thread keeping OV_QPT = OV_ROWS / 256 query points in registers; the
+// pair's target cloud streams through LDS in tiles of OV_TILE points.  d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in fp32, the
+// lowest target index of equal distances, one correctly rounded square root at the end.
 //
 // hfl_pair_stats: one workgroup per pair; a thread sums rows off[p] + tid, + 256, ... in float64 in that order, a wave
 // combines its lanes by the xor butterfly 32, 16, ... 1, and thread 0 adds the four wave results in wave order.
@@ -25,7 +18,7 @@
 // No atomics anywhere; every output element has one writer and a fixed evaluation order: two runs give the same bits.
 #include <math.h>
 
-#include "ragged_common.h"
+#include "pair_scan.h"
 
 namespace {
 
@@ -52,11 +45,7 @@ transform_points_kernel(float* __restrict__ out, const float* __restrict__ point
   const float* m = transforms + 12 * (int64_t)lo;
   const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float acc = fmaf(m[4 * c], x, m[4 * c + 3]);
-    acc = fmaf(m[4 * c + 1], y, acc);
-    out[3 * i + c] = fmaf(m[4 * c + 2], z, acc);
-  }
+  for (int c = 0; c < 3; ++c) out[3 * i + c] = rigid_coord(m + 4 * c, x, y, z);
 }
 
 __global__ void __launch_bounds__(OV_THREADS)
@@ -64,64 +53,25 @@ nn_dist_kernel(float* __restrict__ dist, int32_t* __restrict__ idx, const float*
                const int64_t* __restrict__ q_off, int64_t n_queries, const float* __restrict__ targets,
                const int64_t* __restrict__ t_off, int64_t n_targets, const int64_t* __restrict__ tiles, int n_pairs) {
   __shared__ __align__(16) float s_x[OV_TILE], s_y[OV_TILE], s_z[OV_TILE];
-  const int64_t p = tiles[2 * (int64_t)blockIdx.x], row0 = tiles[2 * (int64_t)blockIdx.x + 1];
-  if (p < 0 || p >= n_pairs || row0 < 0) return;                 // uniform over the workgroup
-  // the offsets are clamped to the arrays, so a wrong table or offset cannot make the kernel read or write outside them
-  const int64_t q_end = min(q_off[p + 1], n_queries);
-  const int64_t t_begin = max(t_off[p], (int64_t)0), t_end = min(t_off[p + 1], n_targets);
-
+  PairTile w;
+  if (!pair_tile(w, tiles, n_pairs)) return;
+  pair_ranges(w, q_off, n_queries, t_off, n_targets);
   float qx[OV_QPT], qy[OV_QPT], qz[OV_QPT], best[OV_QPT];
   int32_t at[OV_QPT];
 #pragma unroll
   for (int r = 0; r < OV_QPT; ++r) {
-    const int64_t row = row0 + r * OV_THREADS + threadIdx.x;
-    const bool valid = row < q_end;
+    const int64_t row = w.row<OV_THREADS>(r);
+    const bool valid = row < w.q_end;
     qx[r] = valid ? queries[3 * row] : 0.f;
     qy[r] = valid ? queries[3 * row + 1] : 0.f;
     qz[r] = valid ? queries[3 * row + 2] : 0.f;
-    best[r] = INFINITY;
-    at[r] = -1;
   }
-
-  for (int64_t tile = t_begin; tile < t_end; tile += OV_TILE) {
-    const int len = (int)min((int64_t)OV_TILE, t_end - tile);
-    const int len4 = (len + 3) & ~3;                             // the last tile is padded to whole groups of four
-    __syncthreads();                                             // the previous tile has been read by every wave
-    for (int k = threadIdx.x; k < len4; k += OV_THREADS) {
-      const int64_t j = tile + k;
-      const bool real = k < len;                                 // padding lies at +inf: its d2 is +inf, never `<` a best
-      s_x[k] = real ? targets[3 * j] : INFINITY;
-      s_y[k] = real ? targets[3 * j + 1] : INFINITY;
-      s_z[k] = real ? targets[3 * j + 2] : INFINITY;
-    }
-    __syncthreads();
-    const int32_t base = (int32_t)(tile - t_begin);              // < 2^31: the entry point bounds n_targets
-#pragma unroll 2
-    for (int k = 0; k < len4; k += 4) {
-      // the same address in every lane: three broadcast ds_read_b128 bring four target points
-      const float4 cx = *reinterpret_cast<const float4*>(&s_x[k]);
-      const float4 cy = *reinterpret_cast<const float4*>(&s_y[k]);
-      const float4 cz = *reinterpret_cast<const float4*>(&s_z[k]);
-      const float tx[4] = {cx.x, cx.y, cx.z, cx.w}, ty[4] = {cy.x, cy.y, cy.z, cy.w}, tz[4] = {cz.x, cz.y, cz.z, cz.w};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {                              // ascending target index
-#pragma unroll
-        for (int r = 0; r < OV_QPT; ++r) {
-          const float dx = qx[r] - tx[u], dy = qy[r] - ty[u], dz = qz[r] - tz[u];
-          const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-          const bool closer = d2 < best[r];                      // strict: of equal distances the lowest index stays
-          best[r] = closer ? d2 : best[r];
-          at[r] = closer ? base + k + u : at[r];
-        }
-      }
-    }
-  }
-
+  pair_scan3<OV_THREADS>(w, targets, s_x, s_y, s_z, qx, qy, qz, best, at);
 #pragma unroll
   for (int r = 0; r < OV_QPT; ++r) {
-    const int64_t row = row0 + r * OV_THREADS + threadIdx.x;
-    if (row < q_end) {
-      dist[row] = __fsqrt_rn(best[r]);                           // sqrt(+inf) = +inf: an empty target cloud
+    const int64_t row = w.row<OV_THREADS>(r);
+    if (row < w.q_end) {
+      dist[row] = pair_sqrt(best[r]);                            // +inf: an empty target cloud
       idx[row] = at[r];
     }
   }
@@ -198,15 +148,11 @@ extern "C" int hfl_transform_points(float* out, const float* points, const int64
 extern "C" int hfl_nn_dist(float* dist, int32_t* idx, const float* queries, const int64_t* q_offsets, int64_t n_queries,
                            const float* targets, const int64_t* t_offsets, int64_t n_targets, const int64_t* tiles,
                            int64_t n_tiles, int64_t n_pairs, hfl_stream_t stream) {
-  if (dist == nullptr || idx == nullptr || queries == nullptr || q_offsets == nullptr || targets == nullptr ||
-      t_offsets == nullptr || tiles == nullptr || n_queries < 0 || n_targets < 0 || n_tiles < 0 || n_pairs < 1)
-    return HFL_EINVAL;
-  // a target index is an int32, the grid is one-dimensional
-  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  if (n_tiles == 0) return HFL_OK;
-  nn_dist_kernel<<<(unsigned)n_tiles, OV_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      dist, idx, queries, q_offsets, n_queries, targets, t_offsets, n_targets, tiles, (int)n_pairs);
-  HFL_RETURN_LAST_ERROR();
+  return pair_scan_call({dist, idx, queries, q_offsets, targets, t_offsets, tiles}, true, n_queries, n_targets, n_tiles,
+                        n_pairs, [&] {
+    nn_dist_kernel<<<(unsigned)n_tiles, OV_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        dist, idx, queries, q_offsets, n_queries, targets, t_offsets, n_targets, tiles, (int)n_pairs);
+  });
 }
 
 extern "C" int hfl_pair_stats(double* sums, int64_t* counts, const float* dist, const int64_t* offsets, int64_t n_dist,

@@ -7,9 +7,9 @@
 //
 // hfl_icp_correspond: hfl_nn_dist with the transform in front of it and the reduction behind it.  A workgroup of 256 threads
 // owns RG_ROWS consecutive source rows of one pair (the tile table of hfl_nn_dist).  A pair that is no longer RUNNING makes
-// its workgroups return at once.  Otherwise the workgroup rounds the pair's float64 pose to fp32, moves its rows by the fmaf
-// chain of hfl_transform_points, scans the pair's target cloud through LDS exactly as nn_dist_kernel does (the same
-// expressions in the same order, so dist and idx have the bits of hfl_nn_dist on the transformed cloud), reads the winner's
+// its workgroups return at once.  Otherwise the workgroup rounds the pair's float64 pose to fp32, moves its rows by
+// `rigid_coord` and scans the pair's target cloud by `pair_scan3`, both of pair_scan.h and both what hfl_transform_points
+// and hfl_nn_dist run (so dist and idx have the bits of hfl_nn_dist on the transformed cloud), reads the winner's
 // coordinates from global memory once the scan is over, and sums over its inlier rows (d <= max_dist in fp32) the 17
 // float64 quantities
 //     n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2         p' the moved source point, q its target.
@@ -28,7 +28,7 @@
 // unconstrained optimum is a reflection, and a planar cloud needs no special case.
 //
 // hfl_icp_correspond_plane / hfl_icp_solve_plane: the point-to-plane estimator, the same two kernels
-// instantiated with PLANE.  The scan, dist, idx and the inlier rule are the same text; the winner's normal nq is read from
+// instantiated with PLANE.  The scan, dist, idx and the inlier rule are the same code; the winner's normal nq is read from
 // global memory beside its coordinates, and the sums are the 29 float64 quantities
 //     n, sum d^2, g = sum J r (6), the upper triangle of A = sum J J^T row-major (21),   r = (p' - q) . nq, J = (p' x nq, nq),
 // reduced in the same order.  The solve factorises A = L D L^T without pivoting in a fixed order, solves A x = -g for
@@ -38,7 +38,7 @@
 #include <math.h>
 
 #include "jacobi3.h"
-#include "ragged_common.h"
+#include "pair_scan.h"
 
 namespace {
 
@@ -53,7 +53,7 @@ constexpr int RG_SWEEPS = 12;                                    // a 3 x 3 conv
 constexpr double RG_RANK_TOL = 1e-12;                            // second singular value <= this x the largest: degenerate
 constexpr double RG_PIVOT_TOL = 1e-12;                           // a pivot of the LDL^T <= this x its diagonal entry: degenerate
 static_assert(RG_ROWS % RG_THREADS == 0 && RG_QPT >= 1, "whole source points per thread");
-// 3 x 2048 x 4 B = 24 KiB of static LDS as in nn_dist_kernel; the wave results of the reduction reuse the x plane
+// 3 x 2048 x 4 B = 24 KiB of static LDS, the planes of the scan; the wave results of the reduction reuse the x plane
 static_assert(RG_TILE % 4 == 0 && RG_TILE * 12 <= 32 * 1024, "static LDS stays at 32 KiB or less");
 static_assert(RG_WAVES * RG_SUMS * sizeof(double) <= RG_TILE * sizeof(float), "the wave results fit the x plane");
 static_assert(RG_WAVES * RG_PLANE_SUMS * sizeof(double) <= RG_TILE * sizeof(float), "the wave results fit the x plane");
@@ -73,81 +73,36 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
                       const double* __restrict__ state, const int32_t* __restrict__ istate, float max_dist, int n_pairs) {
   constexpr int NS = PLANE ? RG_PLANE_SUMS : RG_SUMS;
   __shared__ __align__(16) float s_x[RG_TILE], s_y[RG_TILE], s_z[RG_TILE];
-  const int64_t p = tiles[2 * (int64_t)blockIdx.x], row0 = tiles[2 * (int64_t)blockIdx.x + 1];
-  if (p < 0 || p >= n_pairs || row0 < 0) return;                 // uniform over the workgroup
-  if (istate[2 * p + 1] != HFL_ICP_RUNNING) return;              // the pair has stopped: its partials are not read again
-  // the offsets are clamped to the arrays, so a wrong table or offset cannot make the kernel read or write outside them
-  const int64_t q_end = min(s_off[p + 1], n_source);
-  const int64_t t_begin = max(t_off[p], (int64_t)0), t_end = min(t_off[p + 1], n_targets);
-
+  PairTile w;
+  if (!pair_tile(w, tiles, n_pairs)) return;
+  if (istate[2 * w.pair + 1] != HFL_ICP_RUNNING) return;         // the pair has stopped: its partials are not read again
+  pair_ranges(w, s_off, n_source, t_off, n_targets);
+  const int64_t t_begin = w.t_begin;
   float m[12];                                                   // the pose, rounded once to fp32
 #pragma unroll
-  for (int k = 0; k < 12; ++k) m[k] = (float)state[16 * p + k];
+  for (int k = 0; k < 12; ++k) m[k] = (float)state[16 * w.pair + k];
 
   float qx[RG_QPT], qy[RG_QPT], qz[RG_QPT], best[RG_QPT];
   int32_t at[RG_QPT];
 #pragma unroll
   for (int r = 0; r < RG_QPT; ++r) {
-    const int64_t row = row0 + r * RG_THREADS + threadIdx.x;
-    const bool valid = row < q_end;
+    const int64_t row = w.row<RG_THREADS>(r);
+    const bool valid = row < w.q_end;
     const float x = valid ? source[3 * row] : 0.f, y = valid ? source[3 * row + 1] : 0.f, z = valid ? source[3 * row + 2] : 0.f;
-    float c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {                                // the chain of transform_points_kernel
-      float acc = fmaf(m[4 * a], x, m[4 * a + 3]);
-      acc = fmaf(m[4 * a + 1], y, acc);
-      c[a] = fmaf(m[4 * a + 2], z, acc);
-    }
-    qx[r] = c[0];
-    qy[r] = c[1];
-    qz[r] = c[2];
-    best[r] = INFINITY;
-    at[r] = -1;
+    qx[r] = rigid_coord(m, x, y, z);
+    qy[r] = rigid_coord(m + 4, x, y, z);
+    qz[r] = rigid_coord(m + 8, x, y, z);
   }
-
-  // the scan of nn_dist_kernel (overlap.hip), expression for expression
-  for (int64_t tile = t_begin; tile < t_end; tile += RG_TILE) {
-    const int len = (int)min((int64_t)RG_TILE, t_end - tile);
-    const int len4 = (len + 3) & ~3;                             // the last tile is padded to whole groups of four
-    __syncthreads();                                             // the previous tile has been read by every wave
-    for (int k = threadIdx.x; k < len4; k += RG_THREADS) {
-      const int64_t j = tile + k;
-      const bool real = k < len;                                 // padding lies at +inf: its d2 is +inf, never `<` a best
-      s_x[k] = real ? targets[3 * j] : INFINITY;
-      s_y[k] = real ? targets[3 * j + 1] : INFINITY;
-      s_z[k] = real ? targets[3 * j + 2] : INFINITY;
-    }
-    __syncthreads();
-    const int32_t base = (int32_t)(tile - t_begin);              // < 2^31: the entry point bounds n_targets
-#pragma unroll 2
-    for (int k = 0; k < len4; k += 4) {
-      // the same address in every lane: three broadcast ds_read_b128 bring four target points
-      const float4 cx = *reinterpret_cast<const float4*>(&s_x[k]);
-      const float4 cy = *reinterpret_cast<const float4*>(&s_y[k]);
-      const float4 cz = *reinterpret_cast<const float4*>(&s_z[k]);
-      const float tx[4] = {cx.x, cx.y, cx.z, cx.w}, ty[4] = {cy.x, cy.y, cy.z, cy.w}, tz[4] = {cz.x, cz.y, cz.z, cz.w};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {                              // ascending target index
-#pragma unroll
-        for (int r = 0; r < RG_QPT; ++r) {
-          const float dx = qx[r] - tx[u], dy = qy[r] - ty[u], dz = qz[r] - tz[u];
-          const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-          const bool closer = d2 < best[r];                      // strict: of equal distances the lowest index stays
-          best[r] = closer ? d2 : best[r];
-          at[r] = closer ? base + k + u : at[r];
-        }
-      }
-    }
-  }
+  pair_scan3<RG_THREADS>(w, targets, s_x, s_y, s_z, qx, qy, qz, best, at);
 
   double acc[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) acc[k] = 0.0;
 #pragma unroll
   for (int r = 0; r < RG_QPT; ++r) {                             // a thread's rows in row order
-    const int64_t row = row0 + r * RG_THREADS + threadIdx.x;
-    if (row < q_end) {
-      const float d = __fsqrt_rn(best[r]);                       // sqrt(+inf) = +inf: an empty target cloud
+    const int64_t row = w.row<RG_THREADS>(r);
+    if (row < w.q_end) {
+      const float d = pair_sqrt(best[r]);                        // +inf: an empty target cloud
       if (dist != nullptr) dist[row] = d;
       if (idx != nullptr) idx[row] = at[r];
       if (at[r] >= 0 && d <= max_dist) {                         // 0 <= at < t_end - t_begin: the gather stays in the cloud
@@ -383,16 +338,12 @@ extern "C" int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, c
                                   int64_t n_source, const float* targets, const int64_t* t_offsets, int64_t n_targets,
                                   const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                   float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  if (partials == nullptr || source == nullptr || s_offsets == nullptr || targets == nullptr || t_offsets == nullptr ||
-      tiles == nullptr || state == nullptr || istate == nullptr || n_source < 0 || n_targets < 0 || n_tiles < 0 || n_pairs < 1)
-    return HFL_EINVAL;
-  // a target index is an int32, the grid is one-dimensional
-  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  if (n_tiles == 0) return HFL_OK;
-  icp_correspond_kernel<false><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets, tiles, state, istate, max_dist,
-      (int)n_pairs);
-  HFL_RETURN_LAST_ERROR();
+  return pair_scan_call({partials, source, s_offsets, targets, t_offsets, tiles, state, istate}, true, n_source, n_targets,
+                        n_tiles, n_pairs, [&] {
+    icp_correspond_kernel<false><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets, tiles, state, istate,
+        max_dist, (int)n_pairs);
+  });
 }
 
 extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const float* source,
@@ -400,16 +351,12 @@ extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* 
                                         const float* target_normals, const int64_t* t_offsets, int64_t n_targets,
                                         const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                         float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  if (partials == nullptr || source == nullptr || s_offsets == nullptr || targets == nullptr || target_normals == nullptr ||
-      t_offsets == nullptr || tiles == nullptr || state == nullptr || istate == nullptr || n_source < 0 || n_targets < 0 ||
-      n_tiles < 0 || n_pairs < 1)
-    return HFL_EINVAL;
-  if (n_targets > 0x7fffffffLL || n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  if (n_tiles == 0) return HFL_OK;
-  icp_correspond_kernel<true><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
-      max_dist, (int)n_pairs);
-  HFL_RETURN_LAST_ERROR();
+  return pair_scan_call({partials, source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate}, true,
+                        n_source, n_targets, n_tiles, n_pairs, [&] {
+    icp_correspond_kernel<true><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
+        max_dist, (int)n_pairs);
+  });
 }
 
 extern "C" int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials,

@@ -60,7 +60,7 @@ import torch
 
 from . import _native, ops, outliers, ragged
 from .normals import _check_neighbours
-from .registration import _fmaf
+from .overlap import _host_argmin32, _host_d2_32
 
 BINS, DIM = 11, ops.FPFH_DIM
 _EDGES = -np.pi + 2.0 * np.pi * np.arange(1, BINS, dtype=np.float64) / float(BINS)
@@ -299,28 +299,12 @@ def _split(x, off, was_list):
     return list(torch.split(x, sizes, 0)) if isinstance(x, torch.Tensor) else [x[s:e] for s, e in zip(off[:-1], off[1:])]
 
 
-def _host_feature_d2(q: np.ndarray, t: np.ndarray) -> np.ndarray:
-    """the (n, m) float32 squared distances between two sets of feature rows with the arithmetic of `hfl_feature_nn`"""
-    with np.errstate(over='ignore', invalid='ignore'):
-        d = q[:, None, 0] - t[None, :, 0]                        # float32 throughout
-        acc = d * d
-        for col in range(1, q.shape[1]):
-            d = q[:, None, col] - t[None, :, col]
-            acc = _fmaf(d, d, acc)
-    return acc
+_host_feature_d2 = _host_d2_32           # the arithmetic of `hfl_feature_nn` is that of the pair scan at any D
 
 
 def _host_feature_nn(q: np.ndarray, t: np.ndarray):
     """(idx (n,) int32, dist2 (n,) float32) of one pair, brute force, chunked over the rows"""
-    idx, dist2 = np.full(q.shape[0], -1, np.int32), np.full(q.shape[0], np.inf, np.float32)
-    if q.shape[0] == 0 or t.shape[0] == 0:
-        return idx, dist2
-    rows = max(1, _HOST_CHUNK // t.shape[0])
-    for r0 in range(0, q.shape[0], rows):
-        acc = _host_feature_d2(q[r0:r0 + rows], t)
-        best = np.argmin(acc, axis=1)                            # the first of equal minima: the lowest index
-        idx[r0:r0 + rows] = best
-        dist2[r0:r0 + rows] = acc[np.arange(acc.shape[0]), best]
+    dist2, idx = _host_argmin32(q, t, _HOST_CHUNK)
     return idx, dist2
 
 

@@ -1844,13 +1844,35 @@ def _some(t: torch.Tensor):
 def overlap_tiles(lengths):
     """The tile table of `hfl_nn_dist` from the query clouds' lengths on the host: (n_tiles, 2) int64 numpy rows of (pair,
     first query row), OVERLAP_ROWS rows of one pair per workgroup, pairs in order; an empty cloud has no tile."""
+    return pair_tiles(lengths)[0]
+
+
+def pair_tiles(lengths):
+    """`overlap_tiles` and, beside it, the (P + 1,) int64 offsets of every pair's rows in that table."""
     lengths = np.asarray(lengths, dtype=np.int64)
-    per = -(-lengths // OVERLAP_ROWS)
-    pair = np.repeat(np.arange(lengths.shape[0], dtype=np.int64), per)
-    first = np.cumsum(per) - per                                   # the first tile of every pair
+    tile_off = np.zeros(lengths.shape[0] + 1, np.int64)
+    np.cumsum(-(-lengths // OVERLAP_ROWS), out=tile_off[1:])
+    pair = np.repeat(np.arange(lengths.shape[0], dtype=np.int64), np.diff(tile_off))
     start = np.cumsum(lengths) - lengths
-    row = start[pair] + (np.arange(pair.shape[0], dtype=np.int64) - first[pair]) * OVERLAP_ROWS
-    return np.stack([pair, row], 1)
+    row = start[pair] + (np.arange(pair.shape[0], dtype=np.int64) - tile_off[pair]) * OVERLAP_ROWS
+    return np.stack([pair, row], 1), tile_off
+
+
+def _pair_batch_check(what: str, queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
+                      tiles: torch.Tensor, sides=('query', 'target'), rows_check=_points_check) -> int:
+    """What every launch of the pair scan takes: two ragged batches of the same P pairs and the (n_tiles, 2) int64 tile
+    table, on the current device -> P.  The order of the checks: the device of all five, the query side's rows and
+    offsets, the target side's, the number of pairs, the tile table; what a caller checks besides comes after."""
+    _dev(queries, q_offsets, targets, t_offsets, tiles)
+    for rows, offsets in ((queries, q_offsets), (targets, t_offsets)):
+        rows_check(what, rows)
+        _offsets_check(what, offsets)
+    pairs = int(q_offsets.shape[0]) - 1
+    if int(t_offsets.shape[0]) - 1 != pairs:
+        raise ValueError('%s: the %s batch and the %s batch differ in their number of pairs' % ((what,) + tuple(sides)))
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('%s: contiguous (n_tiles, 2) int64 tile table expected' % what)
+    return pairs
 
 
 def transform_points(points: torch.Tensor, offsets: torch.Tensor, transforms: torch.Tensor):
@@ -1872,12 +1894,7 @@ def nn_dist(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tenso
     """`hfl_nn_dist`: two ragged batches of the same P pairs and the (n_tiles, 2) int64 device copy of `overlap_tiles` ->
     (dist (Nq,) fp32, idx (Nq,) int32): every query's distance to the nearest point of its pair's target cloud and that
     point's index within the cloud, +inf and -1 where the cloud is empty.  Rows the table does not cover stay unwritten."""
-    pairs = _ragged_check('nn_dist', queries, q_offsets)
-    if _ragged_check('nn_dist', targets, t_offsets) != pairs:
-        raise ValueError('nn_dist: the query batch and the target batch differ in their number of pairs')
-    _dev(tiles)
-    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
-        raise TypeError('nn_dist: contiguous (n_tiles, 2) int64 tile table expected')
+    pairs = _pair_batch_check('nn_dist', queries, q_offsets, targets, t_offsets, tiles)
     n_q = int(queries.shape[0])
     dist = torch.empty(n_q, dtype=torch.float32, device=queries.device)
     idx = torch.empty(n_q, dtype=torch.int32, device=queries.device)
@@ -1928,62 +1945,33 @@ def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch
     given (the iteration loop allocates once), dist (Ns,) fp32 and idx (Ns,) int32 are None unless `want_rows`.  Rows of
     pairs that are not RUNNING stay unwritten.  With `target_normals` ((Nt, 3) fp32, the rows of `targets`) it is
     `hfl_icp_correspond_plane` and the partials have ICP_PLANE_SUMS columns."""
-    if target_normals is not None:
-        return _icp_correspond_plane(source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate, max_dist,
-                                     partials, want_rows)
-    pairs = _ragged_check('icp_correspond', source, s_offsets)
-    if _ragged_check('icp_correspond', targets, t_offsets) != pairs:
-        raise ValueError('icp_correspond: the source batch and the target batch differ in their number of pairs')
-    _icp_state_check('icp_correspond', state, istate, pairs)
-    _dev(tiles)
-    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
-        raise TypeError('icp_correspond: contiguous (n_tiles, 2) int64 tile table expected')
-    n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
-    if partials is None:
-        partials = torch.empty((max(n_tiles, 1), ICP_SUMS), dtype=torch.float64, device=source.device)
-    _dev(partials)
-    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
-            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
-        raise TypeError('icp_correspond: contiguous (>= %d, %d) float64 partials expected' % (n_tiles, ICP_SUMS))
-    dist = torch.empty(n_s, dtype=torch.float32, device=source.device) if want_rows else None
-    idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
-    if n_tiles:
-        check(_native.load().hfl_icp_correspond(partials.data_ptr(), dist.data_ptr() if want_rows else None,
-                                                idx.data_ptr() if want_rows else None, source.data_ptr(),
-                                                s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), t_offsets.data_ptr(),
-                                                int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(),
-                                                istate.data_ptr(), float(max_dist), pairs, _stream()), 'hfl_icp_correspond')
-    return partials, dist, idx
-
-
-def _icp_correspond_plane(source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate, max_dist, partials,
-                          want_rows):
-    what = 'icp_correspond_plane'
-    pairs = _ragged_check(what, source, s_offsets)
-    if _ragged_check(what, targets, t_offsets) != pairs:
-        raise ValueError('%s: the source batch and the target batch differ in their number of pairs' % what)
-    _ragged_check(what, target_normals, t_offsets)
-    if target_normals.shape[0] != targets.shape[0]:
-        raise ValueError('%s: %d target normals for %d target points' % (what, target_normals.shape[0], targets.shape[0]))
+    plane = target_normals is not None
+    n_sums = ICP_PLANE_SUMS if plane else ICP_SUMS
+    what = 'icp_correspond_plane' if plane else 'icp_correspond'
+    name = 'hfl_' + what
+    pairs = _pair_batch_check(what, source, s_offsets, targets, t_offsets, tiles, ('source', 'target'))
+    if plane:
+        _dev(target_normals)
+        _points_check(what, target_normals)
+        if target_normals.shape[0] != targets.shape[0]:
+            raise ValueError('%s: %d target normals for %d target points' % (what, target_normals.shape[0], targets.shape[0]))
     _icp_state_check(what, state, istate, pairs)
-    _dev(tiles)
-    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
-        raise TypeError('%s: contiguous (n_tiles, 2) int64 tile table expected' % what)
     n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
     if partials is None:
-        partials = torch.empty((max(n_tiles, 1), ICP_PLANE_SUMS), dtype=torch.float64, device=source.device)
+        partials = torch.empty((max(n_tiles, 1), n_sums), dtype=torch.float64, device=source.device)
     _dev(partials)
     if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
-            partials.shape[1] != ICP_PLANE_SUMS or not partials.is_contiguous():
-        raise TypeError('%s: contiguous (>= %d, %d) float64 partials expected' % (what, n_tiles, ICP_PLANE_SUMS))
+            partials.shape[1] != n_sums or not partials.is_contiguous():
+        raise TypeError('%s: contiguous (>= %d, %d) float64 partials expected' % (what, n_tiles, n_sums))
     dist = torch.empty(n_s, dtype=torch.float32, device=source.device) if want_rows else None
     idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
     if n_tiles:
-        check(_native.load().hfl_icp_correspond_plane(
+        normals = (_some(target_normals).data_ptr(),) if plane else ()          # the one argument the plane entry point adds
+        check(getattr(_native.load(), name)(
             partials.data_ptr(), dist.data_ptr() if want_rows else None, idx.data_ptr() if want_rows else None,
-            source.data_ptr(), s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), _some(target_normals).data_ptr(),
-            t_offsets.data_ptr(), int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(),
-            float(max_dist), pairs, _stream()), 'hfl_icp_correspond_plane')
+            source.data_ptr(), s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), *normals, t_offsets.data_ptr(),
+            int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(), float(max_dist), pairs,
+            _stream()), name)
     return partials, dist, idx
 
 
@@ -2350,7 +2338,7 @@ def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: to
 
 
 FPFH_DIM = 33                          # three groups of 11 bins
-FEATURE_ROWS = 512                     # HFL_FEATURE_ROWS: query rows of a workgroup of hfl_feature_nn (two per thread)
+FEATURE_ROWS = OVERLAP_ROWS            # HFL_FEATURE_ROWS: query rows of a workgroup of hfl_feature_nn, as `feature_tiles` needs
 FEATURE_MAX_DIM = 64                   # HFL_FEATURE_MAX_DIM
 
 
@@ -2423,10 +2411,14 @@ def fpfh_combine(ws: FpfhWorkspace, sorted_points: torch.Tensor, sorted_keys: to
     return fpfh
 
 
-def feature_tiles(lengths):
-    """The tile table of `hfl_feature_nn` from the query lengths of the pairs on the host: `overlap_tiles`, whose
-    OVERLAP_ROWS rows per workgroup are the FEATURE_ROWS of this kernel."""
-    return overlap_tiles(lengths)
+# the tile table of `hfl_feature_nn` from the query lengths of the pairs on the host; right while FEATURE_ROWS is OVERLAP_ROWS,
+# which csrc/pair_scan.h asserts of the header's two defines
+feature_tiles = overlap_tiles
+
+
+def _feature_rows_check(what: str, rows: torch.Tensor):
+    if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous():
+        raise TypeError('%s: contiguous (N, D) float32 rows expected' % what)
 
 
 def feature_nn(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
@@ -2435,21 +2427,11 @@ def feature_nn(queries: torch.Tensor, q_offsets: torch.Tensor, targets: torch.Te
     the (n_tiles, 2) int64 device copy of `feature_tiles` -> (dist2 (Nq,) fp32, idx (Nq,) int32): every query row's smallest
     squared distance to a target row of its pair and that row's index within the pair, +inf and -1 where the pair has no
     target.  Rows the table does not cover stay unwritten."""
-    _dev(queries, q_offsets, targets, t_offsets, tiles)
-    for t in (queries, targets):
-        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
-            raise TypeError('feature_nn: contiguous (N, D) float32 rows expected')
+    pairs = _pair_batch_check('feature_nn', queries, q_offsets, targets, t_offsets, tiles, rows_check=_feature_rows_check)
     dim = int(queries.shape[1])
     if int(targets.shape[1]) != dim or not 1 <= dim <= FEATURE_MAX_DIM:
         raise ValueError('feature_nn: both sides need the same D in 1..%d, got %d and %d'
                          % (FEATURE_MAX_DIM, dim, int(targets.shape[1])))
-    _offsets_check('feature_nn', q_offsets)
-    _offsets_check('feature_nn', t_offsets)
-    pairs = int(q_offsets.shape[0]) - 1
-    if int(t_offsets.shape[0]) - 1 != pairs:
-        raise ValueError('feature_nn: the query batch and the target batch differ in their number of pairs')
-    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
-        raise TypeError('feature_nn: contiguous (n_tiles, 2) int64 tile table expected')
     n_q = int(queries.shape[0])
     dist2 = torch.empty(n_q, dtype=torch.float32, device=queries.device)
     idx = torch.empty(n_q, dtype=torch.int32, device=queries.device)

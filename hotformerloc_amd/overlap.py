@@ -335,6 +335,39 @@ def _host_nn_one(q, t, chunk_pairs):
     return dist, idx
 
 
+def _fmaf(a, b, c):
+    """fmaf on float32 arrays: the product is exact in float64, the sum is rounded there and then to float32"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _host_d2_32(q, t):
+    """the (n, m) float32 squared distances between two sets of (., D) float32 rows with the arithmetic of the device's pair
+    scan: d0 d0, then fmaf(dc, dc, acc) for c = 1 .. D - 1 (for D = 3 that is fmaf(dz, dz, fmaf(dy, dy, dx dx)))"""
+    with np.errstate(over='ignore', invalid='ignore'):
+        d = q[:, None, 0] - t[None, :, 0]                              # float32 throughout
+        acc = d * d
+        for col in range(1, q.shape[1]):
+            d = q[:, None, col] - t[None, :, col]
+            acc = _fmaf(d, d, acc)
+    return acc
+
+
+def _host_argmin32(q, t, chunk_pairs=_HOST_CHUNK_PAIRS // 2):
+    """(dist2 (n,) float32, idx (n,) int32) of one pair by `_host_d2_32`, brute force, chunked over query rows: the twin of
+    `hfl_nn_dist` before its square root (D = 3) and of `hfl_feature_nn`.  +inf and -1 without targets."""
+    dist2 = np.full(q.shape[0], np.inf, np.float32)
+    idx = np.full(q.shape[0], -1, np.int32)
+    if q.shape[0] == 0 or t.shape[0] == 0:
+        return dist2, idx
+    rows = max(1, int(chunk_pairs) // t.shape[0])
+    for r0 in range(0, q.shape[0], rows):
+        d2 = _host_d2_32(q[r0:r0 + rows], t)
+        k = d2.argmin(1)                                               # the first of equal minima: the lowest index
+        dist2[r0:r0 + rows] = d2[np.arange(k.shape[0]), k]
+        idx[r0:r0 + rows] = k
+    return dist2, idx
+
+
 def nn_distances_host(src, dst, chunk_pairs=_HOST_CHUNK_PAIRS):
     """`nn_distances` on the CPU, brute force in float64 between the float32 points: `(dist float64, idx int32, offsets
     int64)` as numpy arrays.  `chunk_pairs` bounds the point pairs of one temporary; the result does not depend on it."""

@@ -74,7 +74,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .overlap import _HOST_CHUNK_PAIRS, _host_ragged, _matrices, _ragged, _same_pairs
+from .overlap import _fmaf, _host_argmin32, _host_ragged, _matrices, _ragged, _same_pairs
 
 RUNNING, CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE = range(5)     # HFL_ICP_*: a pair's status
 N_SUMS = 17                            # n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2
@@ -154,10 +154,7 @@ class _Batch:
             if self.plane else None
         self.pairs = self.s_off.shape[0] - 1
         dev = self.s.device
-        lengths = np.diff(self.s_off)
-        tiles = ops.overlap_tiles(lengths)
-        tile_off = np.zeros(self.pairs + 1, np.int64)
-        np.cumsum(-(-lengths // ops.OVERLAP_ROWS), out=tile_off[1:])
+        tiles, tile_off = ops.pair_tiles(np.diff(self.s_off))
         self.n_tiles = int(tiles.shape[0])
         with torch.cuda.device(dev):
             self.s_dev, self.t_dev = torch.from_numpy(self.s_off).to(dev), torch.from_numpy(self.t_off).to(dev)
@@ -269,11 +266,6 @@ def plane_update(sums, min_correspondences=6):
 
 
 # ---------------------------------------------------------------------------------------------------------------- host route
-def _fmaf(a, b, c):
-    """fmaf on float32 arrays: the product is exact in float64, the sum is rounded there and then to float32"""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-
-
 def _host_move(points, m34):
     """the fmaf chain of `hfl_transform_points` with the float32 rounding of one (3, 4) float64 pose"""
     m = m34.astype(np.float32)
@@ -284,23 +276,10 @@ def _host_move(points, m34):
     return out
 
 
-def _host_nn32(q, t, chunk_pairs=_HOST_CHUNK_PAIRS // 2):
-    """(dist (n,) float32, idx (n,) int32) of one pair with the arithmetic of `hfl_nn_dist`, brute force, chunked over rows"""
-    dist = np.full(q.shape[0], np.inf, np.float32)
-    idx = np.full(q.shape[0], -1, np.int32)
-    if q.shape[0] == 0 or t.shape[0] == 0:
-        return dist, idx
-    rows = max(1, int(chunk_pairs) // t.shape[0])
-    for r0 in range(0, q.shape[0], rows):
-        c = q[r0:r0 + rows]
-        dx = c[:, None, 0] - t[None, :, 0]                              # float32 throughout
-        dy = c[:, None, 1] - t[None, :, 1]
-        dz = c[:, None, 2] - t[None, :, 2]
-        d2 = _fmaf(dz, dz, _fmaf(dy, dy, dx * dx))
-        k = d2.argmin(1)                                               # the first of equal minima: the lowest index
-        dist[r0:r0 + rows] = np.sqrt(d2[np.arange(k.shape[0]), k])     # float32 sqrt, correctly rounded
-        idx[r0:r0 + rows] = k
-    return dist, idx
+def _host_nn32(q, t):
+    """(dist (n,) float32, idx (n,) int32) of one pair with the arithmetic of `hfl_nn_dist`, brute force"""
+    dist2, idx = _host_argmin32(q, t)
+    return np.sqrt(dist2), idx                                         # float32 sqrt, correctly rounded; sqrt(+inf) = +inf
 
 
 def _host_plane_sums(p, q, n, d):

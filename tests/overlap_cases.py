@@ -70,6 +70,29 @@ def ragged_pairs(seed, sizes_a=(700, 0, 1300, 40, 515), sizes_b=(900, 300, 0, 21
     return a, b
 
 
+def pair_scan_batches(rows, tile):
+    """What the consumers of the pair scan are compared on (tests/test_gpu_pair_scan.py and its host twin): the ragged
+    batch with a pair without source and a pair without target, and one pair of rows + 1 queries against 2 tile + 1 targets
+    with exact duplicates, query 0 a copy of a target whose lowest copy lies before the first tile edge and itself after it.
+    -> [(sources, targets), ...] and that query's expected index"""
+    dst, lowest = with_duplicates(forest(2 * tile + 1, 7), 8)
+    late = np.flatnonzero((lowest < tile) & (np.arange(dst.shape[0]) >= tile))
+    assert late.size
+    src = forest(rows + 1, 9)
+    src[0] = dst[late[-1]]
+    return [ragged_pairs(31), ([src], [dst])], int(lowest[late[-1]])
+
+
+def mutual_from_indices(idx, back, q_off, t_off):
+    """the mutual mask from both directions' nearest-neighbour indices (numpy, concatenated, local to the pair)"""
+    mask = np.zeros(idx.shape[0], bool)
+    for p in range(q_off.shape[0] - 1):
+        k = idx[q_off[p]:q_off[p + 1]]
+        if k.size and t_off[p + 1] > t_off[p]:
+            mask[q_off[p]:q_off[p + 1]] = back[t_off[p] + k] == np.arange(k.shape[0])
+    return mask
+
+
 def max_abs_after(clouds, transforms):
     """L: the largest coordinate magnitude of the float64 transformed clouds"""
     big = 0.0

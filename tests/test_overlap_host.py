@@ -10,9 +10,10 @@ import pytest
 import torch
 
 import overlap_cases as oc
-from hotformerloc_amd import (_native, chamfer_distance, chamfer_distance_host, match_nearest_pose, nn_distances,
-                              nn_distances_host, ops, overlap_ratio, overlap_ratio_host, pose_matrix, relative_pose,
-                              submap_overlap, submap_overlap_host, transform_points, transform_points_host)
+from hotformerloc_amd import (_native, chamfer_distance, chamfer_distance_host, feature_correspondences_host,
+                              icp_correspondences_host, match_nearest_pose, nn_distances, nn_distances_host, ops, overlap_ratio,
+                              overlap_ratio_host, pose_matrix, relative_pose, submap_overlap, submap_overlap_host,
+                              transform_points, transform_points_host)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UTM = np.array([5.0e5, 6.9e6])
@@ -178,6 +179,33 @@ def test_tile_table():
     for name in ('ROWS', 'TILE', 'MAX_TAUS'):                               # the constants ops exports are the header's
         assert int(re.search(r'#define HFL_OVERLAP_%s (\d+)' % name, header).group(1)) == getattr(ops, 'OVERLAP_' + name)
     assert ops.OVERLAP_ROWS % 256 == 0 and ops.OVERLAP_TILE * 12 <= 32 * 1024
+    # `feature_tiles` is this table: the workgroups of hfl_feature_nn own the rows of those of hfl_nn_dist
+    assert ops.FEATURE_ROWS == ops.OVERLAP_ROWS
+    assert ops.feature_tiles([3, 0, q + 1]).tolist() == ops.overlap_tiles([3, 0, q + 1]).tolist()
+    assert int(re.search(r'#define HFL_FEATURE_ROWS (\d+)', header).group(1)) == ops.OVERLAP_ROWS
+    both, tile_off = ops.pair_tiles([0, 1, q, q + 1, 0, 2 * q + 1])        # the table and every pair's rows in it
+    assert np.array_equal(both, tiles) and tile_off.tolist() == [0, 0, 1, 2, 4, 4, 7]
+
+
+def test_host_twins_of_the_pair_scan_agree_bit_for_bit():
+    """The host side of tests/test_gpu_pair_scan.py: the fp32 twin of `hfl_nn_dist` (through `icp_correspondences_host` at
+    the identity pose) and the twin of `hfl_feature_nn` at D = 3 pick the same rows at the same distances, and so give the
+    same mutual mask."""
+    bits = lambda x: np.ascontiguousarray(x, np.float32).view(np.uint32)      # noqa: E731
+    offsets = lambda clouds: np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)      # noqa: E731
+    batches, lowest = oc.pair_scan_batches(ops.OVERLAP_ROWS, ops.OVERLAP_TILE)
+    for src, dst in batches:
+        eye = np.tile(np.eye(4), (len(src), 1, 1))
+        dist, idx, _, _ = icp_correspondences_host(src, dst, eye, 1.0)
+        back = icp_correspondences_host(dst, src, eye, 1.0)[1]
+        f_idx, f_d2, f_mask = (np.concatenate(x) for x in feature_correspondences_host(src, dst, mutual=True))
+        assert dist.dtype == np.float32 and f_d2.dtype == np.float32 and np.array_equal(f_idx, idx)
+        assert np.array_equal(bits(np.sqrt(f_d2)), bits(dist))
+        want = oc.mutual_from_indices(idx, back, offsets(src), offsets(dst))
+        assert np.array_equal(f_mask, want) and want.any() and not want.all()
+        empty = np.repeat([len(c) == 0 for c in dst], [len(c) for c in src])
+        assert np.array_equal(idx == -1, empty) and np.array_equal(np.isinf(dist), empty)
+    assert idx[0] == lowest and dist[0] == 0.0                              # the tie across a tile edge: the lowest copy
 
 
 def test_device_functions_refuse_cpu_tensors_and_float64_points():
