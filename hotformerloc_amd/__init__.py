@@ -11,7 +11,10 @@ every step has a numpy `*_host` twin that states its definition.
 
 Towards a pose for a retrieved candidate: `estimate_normals`, then `compute_fpfh` (33-bin FPFH descriptors per point on the
 same search) and `feature_correspondences` (nearest rows in descriptor space, optionally mutual) give the point pairs a
-robust estimator needs before `icp_refine`; `compute_fpfh_host` / `feature_correspondences_host` define them.
+robust estimator needs; `ransac_registration` is that estimator (a deterministic RANSAC over `correspondence_pairs`:
+`ransac_hypotheses`, `score_hypotheses`, select, a short polish) and hands `icp_refine(init=...)` its starting pose;
+`global_registration` chains all of it from two raw clouds to a refined 6-DoF pose in one call.  The `*_host` twins define
+every step.
 """
 
 import os as _os
@@ -47,5 +50,8 @@ from .registration import (icp_refine, icp_refine_host, icp_correspondences, icp
 from .normals import estimate_normals, estimate_normals_host                                            # noqa: F401,E402
 from .fpfh import (compute_fpfh, compute_fpfh_host, feature_correspondences,                            # noqa: F401,E402
                    feature_correspondences_host)
+from .global_registration import (correspondence_pairs, correspondence_pairs_host, ransac_hypotheses,   # noqa: F401,E402
+                                  ransac_hypotheses_host, score_hypotheses, score_hypotheses_host, ransac_registration,
+                                  ransac_registration_host, global_registration, global_registration_host, RansacResult)
 
 __version__ = '0.1.0'

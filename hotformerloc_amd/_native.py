@@ -271,6 +271,13 @@ SIGNATURES = {
                                          c_void_p]),
     'hfl_icp_solve_plane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                     c_double, c_double, c_int, c_void_p]),
+    'hfl_ransac_hypotheses': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_uint64,
+                                      c_double, c_void_p]),
+    'hfl_ransac_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                 c_int64, c_float, c_void_p]),
+    'hfl_ransac_select': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    'hfl_ransac_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                c_float, c_void_p]),
     'hfl_ema_update': (c_int, [c_void_p, c_int, c_float, c_void_p]),
     'hfl_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     'hfl_kd_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBNAME = 'libhotformerloc_hip.so'
 ARCH = 'gfx950'
-SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'normals.hip', 'fpfh.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'mixer_chain.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'registration.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
+SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'normals.hip', 'fpfh.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'mixer_chain.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'registration.hip', 'global_registration.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc',
          '-Wall', '-Wno-unused-function']
 # hipBLASLt for hfl_gemm_bf16 (the ROCm copy that matches the headers; rpath so the loader finds it)
@@ -45,7 +45,11 @@ EXTRA_FLAGS = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                # normals.hip: the same search, and float64 sums and a Jacobi that follow the numpy route operation for operation
                'normals.hip': ['-ffp-contract=off'],
                # fpfh.hip: the same search, and float64 pair features whose bins must equal the numpy route's bit for bit
-               'fpfh.hip': ['-ffp-contract=off']}
+               'fpfh.hip': ['-ffp-contract=off'],
+               # global_registration.hip: the float64 edge check and Kabsch solve of a drawn triple follow the numpy route
+               # operation for operation; the score kernel's two hypotheses per thread, packed into v_pk_fma_f32 pairs by SLP
+               # vectorisation, need 146 VGPRs (three waves per SIMD) where the plain form needs 74 (six)
+               'global_registration.hip': ['-ffp-contract=off', '-fno-slp-vectorize']}
 
 
 def _hipcc() -> str:
@@ -70,6 +74,7 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     headers = [os.path.join(CSRC, 'hfl_common.h'), os.path.join(CSRC, 'x3_math.h'), os.path.join(CSRC, 'stage_stream.h'),
                os.path.join(CSRC, 'prep_common.h'), os.path.join(CSRC, 'ragged_common.h'), os.path.join(CSRC, 'ln_row.h'),
                os.path.join(CSRC, 'knn_common.h'), os.path.join(CSRC, 'pair_scan.h'), os.path.join(CSRC, 'jacobi3.h'),
+               os.path.join(CSRC, 'kabsch.h'), os.path.join(CSRC, 'philox.h'),
                os.path.join(HERE, '..', 'include', 'hotformerloc_hip.h')]
     jobs = []
     for src in SOURCES:

@@ -22,28 +22,10 @@
 // Normalize, the block rectangle and the masks are IEEE add / mul / div / sqrt with every rounding of the reference's mix
 // of float32 tensors and Python doubles kept (_rn intrinsics, no FMA contraction).  logf / cosf / sinf of the jitter are the
 // device library's; a last-bit difference there is 1e-10 in a coordinate.
+#include "philox.h"
 #include "prep_common.h"
 
 namespace {
-
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
 
 __device__ __forceinline__ float unit_open(uint32_t w) {                 // (u32 + 0.5) * 2^-32, in (0, 1]
   return __fmul_rn(__fadd_rn(__uint2float_rn(w), 0.5f), 2.3283064365386963e-10f);

@@ -1,0 +1,615 @@
+"""Global registration of a ragged batch of submap pairs: RANSAC over point correspondences, feeding ICP, on the GPU.
+
+`icp_refine` needs a starting pose.  A pair that came with surveyed poses has one (`SubmapOverlap.transforms`); a candidate
+that `FlatL2Index.search` merely retrieved has none, and the identity fails once the revisit is turned or a few metres off.
+`feature_correspondences` on `compute_fpfh` descriptors gives point pairs of which most are wrong; this module finds the
+rigid pose most of the rest agree on.  open3d is not a dependency and parity with its `registration_ransac_based_on_
+correspondence` is not claimed (it stops early on a confidence estimate and draws from a thread-dependent generator): what
+is computed is stated here, and the `*_host` functions are this text in numpy.
+
+    correspondence_pairs   the (C_i, 2) [source row, target row] pairs of a `feature_correspondences` result
+    ransac_hypotheses      H candidate poses per pair from drawn triples of correspondences
+    score_hypotheses       the inlier count of every candidate
+    ransac_registration    draw (or take the caller's candidates), score, select, polish -> `RansacResult`
+    global_registration    two raw clouds -> normals -> FPFH -> correspondences -> RANSAC -> ICP, in one call
+
+The package exports the function `global_registration` under the name of this module; the module itself (`inlier_d2`,
+`NO_HYPOTHESIS`) is `importlib.import_module('hotformerloc_amd.global_registration')`.
+
+Definition (DESIGN.md section 7n has the reasons).  `source` and `target` come in the layouts of `overlap.py`;
+`correspondences` is a list of (C_i, 2) integer arrays [source row, target row] local to the pair, or `((C, 2) rows,
+(P + 1,) offsets)`.  The rows are gathered once into fp32 point pairs (p_c, q_c), c = 0 .. C - 1.  A row out of range is a
+`ValueError`.
+
+  Hypotheses, h = 0 .. H - 1 of pair number `pair`.  (x0, x1, x2, _) = philox4x32_10(counter = (h, pair, 0, 0), key = seed)
+  (`augment.philox4x32_10`; the key is the seed's low and high 32 bits); the sample rows are i_k = (uint64(x_k) . C) >> 32,
+  reported as `draws` in any case.  A hypothesis is INVALID when C < 3; or two of the three rows are equal; or the edge-length
+  check fails: for the index pairs (0,1), (0,2), (1,2), in float64 with one rounding per operation, ls = (dx dx + dy dy) +
+  dz dz between the source points and lt likewise between the target points, and both ls >= rho2 lt and lt >= rho2 ls are
+  required, rho2 = float64(edge_length_ratio)^2 (a ratio of 0 disables the check); or the Kabsch solve reports rank < 2.  That
+  solve is `kabsch_solve` of csrc/kabsch.h, the one of the ICP (`registration._host_kabsch_one`), on the 17 float64 sums of
+  the three pairs added in the order 0, 1, 2 (n = 3, sum d^2 = 0).  The pose is rounded to fp32: twelve values, the row-major
+  (R | t) `hfl_transform_points` takes.  An invalid hypothesis has a pose of twelve NaNs.
+
+  Score.  For every correspondence p' = the fmaf chain of `hfl_transform_points` on p (acc = fmaf(r0, x, t); acc = fmaf(r1,
+  y, acc); fmaf(r2, z, acc)) and d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) on p' - q, in fp32.  It is an inlier iff d2 <= D2,
+  D2 the largest finite fp32 with sqrtf(D2) <= fp32(max_correspondence_distance) (`inlier_d2` finds it by stepping
+  `nextafter` around the square).  The correctly rounded root is monotone, so this is the predicate of the ICP, sqrt(d2) <=
+  fp32(tau), without a root per test.  count_h is the number of inliers, -1 for an invalid hypothesis.  Counts are integers:
+  their value does not depend on the order of summation.  Where the caller gives poses and no flags, a hypothesis is valid
+  iff its twelve values are finite.
+
+  Select.  The largest count, the lowest h on a tie.  If every count is -1 the pair ends NO_HYPOTHESIS (status 5, beside the
+  codes of `registration.py`) with the identity, fitness 0 and rmse NaN.
+
+  Polish.  The evaluate / update loop of `icp_refine` with the correspondences fixed and no convergence rule.  T_0 =
+  float64(the selected fp32 pose).  For k = 0 .. refine_iterations: the inliers of fp32(T_k) by the predicate above; the 17
+  float64 sums n, Sp, Sq, Spq, sum d^2 over them (d = sqrtf(d2), as in the ICP); fitness = n / C and rmse = sqrt(sum d^2 /
+  n).  n < min_correspondences: TOO_FEW, rmse NaN.  k == refine_iterations: MAX_ITERATIONS, the normal end.  A degenerate
+  update (rank < 2): DEGENERATE.  Otherwise T_{k+1} = [R | t] . T_k in float64.  The returned figures always belong to the
+  returned pose.
+
+Deliberately absent: an early stop on confidence, a host read inside the loop, float atomics.  Two runs give the same
+bits, and so do two values of any tiling constant.
+
+The device functions raise `NativeLibraryError` on CPU clouds and launch on the current stream (csrc/global_registration.hip):
+`hfl_ransac_hypotheses` (one thread per hypothesis), `hfl_ransac_score` (the hot path: 512 hypotheses in the registers of a
+workgroup against 1024 correspondences in LDS, integer atomic adds between the tiles of a pair), `hfl_ransac_select`, and
+per polish iteration `hfl_ransac_sums` and the `hfl_icp_solve` of the ICP itself, with relative thresholds 0 and the
+correspondence offsets as its denominators.  The results are read once at the end.
+
+The host twins emulate the fp32 steps as `registration.py` does (an fmaf through one float64 operation) and sum in numpy's
+order: the two routes agree in draws, flags and counts wherever no d2 lies within rounding of D2 and no edge or rank ratio
+within rounding of its threshold, and in poses to rounding.
+"""
+
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import augment
+from . import registration as reg
+from .overlap import _fmaf, _host_ragged, _ragged, _same_pairs
+from .registration import DEGENERATE, MAX_ITERATIONS, RANK_TOL, RUNNING, TOO_FEW, JACOBI_SWEEPS, N_SUMS
+
+NO_HYPOTHESIS = 5                      # HFL_RANSAC_NO_HYPOTHESIS: every hypothesis of the pair was invalid
+_HOST_CHUNK = 1 << 21                  # (hypothesis, correspondence) tests of one temporary of the numpy route
+
+RansacResult = namedtuple('RansacResult', ['transforms', 'fitness', 'inlier_rmse', 'inliers', 'hypothesis',
+                                           'hypothesis_inliers', 'valid_hypotheses', 'status'])
+RansacResult.__doc__ = """What `ransac_registration` returns, numpy arrays on the host.  transforms: (P, 4, 4) float64, source
+frame -> target frame; fitness: (P,) float64, the share of the pair's correspondences that are inliers of that pose;
+inlier_rmse: (P,) float64 over them, NaN where the pair is TOO_FEW or NO_HYPOTHESIS; inliers: (P,) int64, their number;
+hypothesis: (P,) int64, the selected h, -1 for NO_HYPOTHESIS; hypothesis_inliers: (P,) int64, its count before the polish (-1
+likewise); valid_hypotheses: (P,) int64; status: (P,) int64, one of MAX_ITERATIONS (the normal end), TOO_FEW, DEGENERATE,
+NO_HYPOTHESIS."""
+
+
+# ----------------------------------------------------------------------------------------------------------------- arguments
+def _options(hypotheses, seed, edge_length_ratio, what):
+    if int(hypotheses) != hypotheses or hypotheses < 1:
+        raise ValueError('%s: hypotheses must be an integer >= 1' % what)
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError('%s: seed must be an integer of 64 bits, >= 0' % what)
+    rho = float(edge_length_ratio)
+    if not 0.0 <= rho <= 1.0:
+        raise ValueError('%s: edge_length_ratio must be a number in [0, 1]' % what)
+    return int(hypotheses), int(seed), float(np.float64(rho) * np.float64(rho))
+
+
+def _polish_options(max_correspondence_distance, refine_iterations, min_correspondences, what):
+    d = float(max_correspondence_distance)
+    if not d >= 0.0:
+        raise ValueError('%s: max_correspondence_distance must be a number >= 0' % what)
+    if int(refine_iterations) != refine_iterations or refine_iterations < 0:
+        raise ValueError('%s: refine_iterations must be an integer >= 0' % what)
+    if int(min_correspondences) != min_correspondences or min_correspondences < 0:
+        raise ValueError('%s: min_correspondences must be an integer >= 0' % what)
+    return d, int(refine_iterations), int(min_correspondences)
+
+
+def inlier_d2(max_correspondence_distance):
+    """D2 of the module docstring: the largest finite float32 whose correctly rounded float32 root is <= float32(tau)."""
+    tau = np.float32(max_correspondence_distance)
+    if not tau >= 0.0:
+        raise ValueError('max_correspondence_distance must be a number >= 0')
+    top = np.finfo(np.float32).max
+    with np.errstate(over='ignore'):
+        x = np.float32(min(tau * tau, top))
+    while np.sqrt(x) > tau:
+        x = np.nextafter(x, np.float32(-np.inf))
+    while x < top and np.sqrt(np.nextafter(x, np.float32(np.inf))) <= tau:
+        x = np.nextafter(x, np.float32(np.inf))
+    return np.float32(x)
+
+
+def _key(seed):
+    return seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+
+
+def _corr_rows(correspondences, pairs, what, to_rows):
+    """(rows (C, 2) int64 as `to_rows` makes them, offsets (P + 1,) int64 numpy) of a list of (C_i, 2) integer arrays or a
+    `(rows, offsets)` tuple"""
+    as_list = isinstance(correspondences, list)
+    if not as_list and not (isinstance(correspondences, tuple) and len(correspondences) == 2):
+        raise ValueError('%s: correspondences: a list of (C_i, 2) integer arrays or a (rows, offsets) tuple expected' % what)
+    parts = [to_rows(c) for c in (correspondences if as_list else [correspondences[0]])]
+    for c in parts:
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError('%s: (C, 2) correspondence rows expected, got shape %s' % (what, tuple(c.shape)))
+        if c.dtype not in (torch.int32, torch.int64, np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError('%s: int32 or int64 correspondence rows expected, got %s' % (what, c.dtype))
+    if as_list:
+        if len(parts) != pairs:
+            raise ValueError('%s: %d sets of correspondences for %d pairs: they must pair up' % (what, len(parts), pairs))
+        off = np.zeros(pairs + 1, np.int64)
+        np.cumsum([c.shape[0] for c in parts], out=off[1:])
+        return parts, off
+    offsets = correspondences[1]
+    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    if off.ndim != 1 or off.shape[0] != pairs + 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError('%s: (%d,) integer correspondence offsets expected: they must pair up with the clouds'
+                         % (what, pairs + 1))
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != parts[0].shape[0] or (np.diff(off) < 0).any():
+        raise ValueError('%s: correspondence offsets must start at 0, not decrease, and end at the number of rows (%d)'
+                         % (what, parts[0].shape[0]))
+    return parts, off
+
+
+def _poses_of(poses, pairs, what):
+    """(P, H, 12) float32 as given (numpy or tensor) from (P, H, 3, 4)"""
+    shape = tuple(poses.shape)
+    if len(shape) != 4 or shape[0] != pairs or shape[1] < 1 or shape[2:] != (3, 4):
+        raise ValueError('%s: (%d, H >= 1, 3, 4) poses expected, got shape %s' % (what, pairs, shape))
+    if poses.dtype not in (torch.float32, np.dtype(np.float32)):
+        raise TypeError('%s: float32 poses expected, got %s' % (what, poses.dtype))
+    return poses.reshape(pairs, shape[1], 12)
+
+
+def _valid_of(valid, pairs, n_hyp, what):
+    shape = tuple(valid.shape)
+    if shape != (pairs, n_hyp):
+        raise ValueError('%s: (%d, %d) flags expected, got shape %s' % (what, pairs, n_hyp, shape))
+    if valid.dtype not in (torch.bool, np.dtype(bool)):
+        raise TypeError('%s: bool flags expected, got %s' % (what, valid.dtype))
+    return valid
+
+
+# -------------------------------------------------------------------------------------------------------------- device route
+class _Batch:
+    """The correspondences of a batch of pairs on the device, gathered once: (C, 6) fp32 point pairs, their offsets, the
+    tile table and its per-pair offsets."""
+
+    def __init__(self, source, target, correspondences, what):
+        from . import ops
+        s, s_off, _ = _ragged(source, what, True)
+        t, t_off, _ = _ragged(target, what, True)
+        _same_pairs(s_off, t_off, what)
+        self.pairs = s_off.shape[0] - 1
+        self.device = dev = s.device
+        if t.device != dev:
+            raise ValueError('%s: source and target lie on different devices' % what)
+        parts, self.c_off = _corr_rows(correspondences, self.pairs, what, lambda c: torch.as_tensor(c))
+        with torch.cuda.device(dev):
+            rows = torch.cat([c.to(dev).to(torch.int64) for c in parts], 0)
+            lengths = torch.from_numpy(np.diff(self.c_off)).to(dev)
+            pair = torch.repeat_interleave(torch.arange(self.pairs, device=dev), lengths)
+            n_s, n_t = torch.from_numpy(np.diff(s_off)).to(dev)[pair], torch.from_numpy(np.diff(t_off)).to(dev)[pair]
+            # the one compare, before anything launches
+            if bool(((rows < 0) | (rows >= torch.stack([n_s, n_t], 1))).any()):
+                raise ValueError('%s: a correspondence names a row outside its cloud' % what)
+            at_s = torch.from_numpy(s_off).to(dev)[pair] + rows[:, 0]
+            at_t = torch.from_numpy(t_off).to(dev)[pair] + rows[:, 1]
+            self.corr = torch.cat([s[at_s], t[at_t]], 1).contiguous()
+            self.c_dev = torch.from_numpy(self.c_off).to(dev)
+            tiles, tile_off = ops.ransac_tiles(np.diff(self.c_off))
+            self.n_tiles = int(tiles.shape[0])
+            self.tiles, self.tile_off = torch.from_numpy(tiles).to(dev), torch.from_numpy(tile_off).to(dev)
+
+    def device_poses(self, poses, valid, what):
+        """the caller's candidates as ((P, H, 12) fp32, (P, H) uint8) on the device"""
+        poses = _poses_of(torch.as_tensor(poses), self.pairs, what).to(self.device).contiguous()
+        if valid is None:
+            valid = torch.isfinite(poses).all(2)
+        else:
+            valid = _valid_of(torch.as_tensor(valid), self.pairs, int(poses.shape[1]), what).to(self.device)
+        return poses, valid.to(torch.uint8).contiguous()
+
+
+def ransac_hypotheses(source, target, correspondences, *, hypotheses=4096, seed=0, edge_length_ratio=0.9):
+    """H candidate poses for each of P pairs, as the module's docstring defines them, on the device -> `(poses (P, H, 3, 4)
+    float32, valid (P, H) bool, draws (P, H, 3) int32)`, device tensors.  An invalid hypothesis has a pose of NaNs."""
+    from . import ops
+    what = 'ransac_hypotheses'
+    n_hyp, seed, rho2 = _options(hypotheses, seed, edge_length_ratio, what)
+    b = _Batch(source, target, correspondences, what)
+    with torch.cuda.device(b.device):
+        poses, valid, draws = ops.ransac_hypotheses(b.corr, b.c_dev, n_hyp, seed, rho2)
+    return poses.view(b.pairs, n_hyp, 3, 4), valid.to(torch.bool), draws
+
+
+def score_hypotheses(source, target, correspondences, poses, max_correspondence_distance, valid=None):
+    """The inlier counts of given candidates on the device -> (P, H) int32 device tensor, -1 where `valid` ((P, H) bool) is
+    False; without `valid` a candidate counts as valid iff its twelve values are finite.  `poses`: (P, H, 3, 4) float32."""
+    from . import ops
+    what = 'score_hypotheses'
+    dist, _, _ = _polish_options(max_correspondence_distance, 0, 0, what)
+    b = _Batch(source, target, correspondences, what)
+    with torch.cuda.device(b.device):
+        poses, valid = b.device_poses(poses, valid, what)
+        return ops.ransac_score(b.corr, b.c_dev, b.tiles, poses, valid, float(inlier_d2(dist)))
+
+
+def ransac_registration(source, target, correspondences, *, max_correspondence_distance=0.8, hypotheses=4096, seed=0,
+                        edge_length_ratio=0.9, refine_iterations=3, min_correspondences=3, poses=None):
+    """RANSAC on the correspondences of P pairs, as the module's docstring defines it -> `RansacResult`.  `poses`: (P, H, 3,
+    4) float32 candidates of the caller's own in place of the drawn ones (a yaw sweep round a surveyed pose, say); one
+    with a value that is not finite counts as invalid.  Everything is enqueued on the current stream without a host read;
+    the results are read once at the end."""
+    from . import ops
+    what = 'ransac_registration'
+    n_hyp, seed, rho2 = _options(hypotheses, seed, edge_length_ratio, what)
+    dist, iters, min_corr = _polish_options(max_correspondence_distance, refine_iterations, min_correspondences, what)
+    d2_max = float(inlier_d2(dist))
+    b = _Batch(source, target, correspondences, what)
+    with torch.cuda.device(b.device):
+        if poses is None:
+            poses, valid, _ = ops.ransac_hypotheses(b.corr, b.c_dev, n_hyp, seed, rho2)
+        else:
+            poses, valid = b.device_poses(poses, None, what)
+        counts = ops.ransac_score(b.corr, b.c_dev, b.tiles, poses, valid, d2_max)
+        state, istate, chosen = ops.ransac_select(counts, poses)
+        partials = torch.zeros((max(b.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=b.device)
+        inliers = torch.zeros(b.pairs, dtype=torch.float64, device=b.device)
+        for k in range(iters + 1):
+            running = istate[:, 1] == RUNNING
+            ops.ransac_sums(b.corr, b.c_dev, b.tiles, state, istate, d2_max, partials=partials)
+            sums = ops.icp_solve(state, istate, partials, b.tile_off, b.n_tiles, b.c_dev, min_corr, 0.0, 0.0, k == iters,
+                                 want_sums=True)
+            inliers = torch.where(running, sums[:, 0], inliers)        # the n of the evaluation a pair stopped at
+        state, istate = state.cpu().numpy(), istate.cpu().numpy().astype(np.int64)
+        chosen, inliers = chosen.cpu().numpy().astype(np.int64), inliers.cpu().numpy().astype(np.int64)
+    return RansacResult(reg._full(state[:, :12].reshape(-1, 3, 4)), state[:, 12].copy(), state[:, 13].copy(), inliers,
+                        chosen[:, 0].copy(), chosen[:, 1].copy(), chosen[:, 2].copy(), istate[:, 1].copy())
+
+
+def _pairs_of(idx, mask, xp):
+    """the kept (C, 2) int64 rows of one pair, in ascending source row"""
+    keep = idx >= 0 if mask is None else (idx >= 0) & mask
+    if xp is np:
+        rows = np.nonzero(keep)[0].astype(np.int64)
+        return np.stack([rows, idx[rows].astype(np.int64)], 1)
+    rows = torch.nonzero(keep)[:, 0]
+    return torch.stack([rows, idx[rows].to(torch.int64)], 1)
+
+
+def _correspondence_pairs(idx, mask, as_array, xp, what):
+    as_list = isinstance(idx, list)
+    if not as_list and not (isinstance(idx, tuple) and len(idx) == 2):
+        raise ValueError('%s: a list of (N_i,) index arrays or an (idx, offsets) tuple expected' % what)
+    if mask is not None and isinstance(mask, list) != as_list:
+        raise ValueError('%s: mask must come in the layout of idx' % what)
+    parts = [as_array(i) for i in (idx if as_list else [idx[0]])]
+    masks = None if mask is None else [as_array(m) for m in (mask if as_list else [mask])]
+    if masks is not None and (len(masks) != len(parts) or any(tuple(m.shape) != tuple(i.shape) for m, i in zip(masks, parts))):
+        raise ValueError('%s: mask must hold one flag per row of idx' % what)
+    for i, part in enumerate(parts):
+        if part.ndim != 1 or part.dtype not in (torch.int32, torch.int64, np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError('%s: (N,) int32 or int64 target rows expected' % what)
+        if masks is not None and masks[i].dtype not in (torch.bool, np.dtype(bool)):
+            raise TypeError('%s: bool mask expected' % what)
+    if as_list:
+        return [_pairs_of(part, None if masks is None else masks[i], xp) for i, part in enumerate(parts)]
+    offsets = idx[1]
+    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    off = off.astype(np.int64)
+    if off.ndim != 1 or off.shape[0] < 2 or off[0] != 0 or off[-1] != parts[0].shape[0] or (np.diff(off) < 0).any():
+        raise ValueError('%s: offsets must start at 0, not decrease, and end at the number of rows (%d)'
+                         % (what, parts[0].shape[0]))
+    per_pair = [_pairs_of(parts[0][s:e], None if masks is None else masks[0][s:e], xp) for s, e in zip(off[:-1], off[1:])]
+    c_off = np.zeros(off.shape[0], np.int64)
+    np.cumsum([p.shape[0] for p in per_pair], out=c_off[1:])
+    return (xp.concatenate(per_pair, 0) if xp is np else torch.cat(per_pair, 0)), c_off
+
+
+def correspondence_pairs(idx, mask=None):
+    """The point pairs of a `feature_correspondences` result: a list of per-pair (N_i,) `idx` (and `mask`) -> a list of
+    (C_i, 2) int64 rows [source row, target row] with idx >= 0 (and mask), in ascending source row; an `(idx (N,), offsets
+    (P + 1,))` tuple (and the concatenated mask) -> `((C, 2) rows, (P + 1,) int64 numpy offsets)`.  Tensors stay on their
+    device; `correspondence_pairs_host` is the numpy route."""
+    return _correspondence_pairs(idx, mask, torch.as_tensor, torch, 'correspondence_pairs')
+
+
+def correspondence_pairs_host(idx, mask=None):
+    """`correspondence_pairs` in numpy."""
+    def as_array(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return _correspondence_pairs(idx, mask, as_array, np, 'correspondence_pairs')
+
+
+def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
+                        estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
+                        min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """From two lists of raw (N_i, 3) float32 GPU clouds to refined 6-DoF poses, source frame -> target frame, in one call:
+    `estimate_normals` -> `compute_fpfh` -> `feature_correspondences` (`mutual`) -> `correspondence_pairs` ->
+    `ransac_registration` (`ransac_distance` and its options) -> `icp_refine(init=...)` (`icp_distance`, `estimation`, its
+    options; point-to-plane uses the target normals already estimated).  -> `(RansacResult, RegistrationResult)`.  A pair
+    that ends NO_HYPOTHESIS enters the ICP at the identity."""
+    from .fpfh import compute_fpfh, feature_correspondences
+    from .normals import estimate_normals
+    return _global(source, target, estimate_normals, compute_fpfh, feature_correspondences, correspondence_pairs,
+                   ransac_registration, reg.icp_refine, True, nb_neighbors, mutual, ransac_distance, icp_distance, estimation,
+                   hypotheses, seed, edge_length_ratio, refine_iterations, min_correspondences, max_iterations,
+                   relative_fitness, relative_rmse)
+
+
+def _global(source, target, normals_of, fpfh_of, match, pairs_of, ransac, icp, device_route, nb, mutual, ransac_distance,
+            icp_distance, estimation, hypotheses, seed, ratio, refine_iterations, min_corr, max_iterations, rel_f, rel_r):
+    what = 'global_registration'
+    if not isinstance(source, list) or not isinstance(target, list) or not source or len(source) != len(target):
+        raise ValueError('%s: two lists of (N_i, 3) clouds that pair up expected' % what)
+    if estimation not in reg.ESTIMATIONS:
+        raise ValueError('%s: estimation must be one of %s, got %r' % (what, ', '.join(reg.ESTIMATIONS), estimation))
+    _ragged(source, what, device_route), _ragged(target, what, device_route)   # the refusals, before anything is computed
+    pairs = len(source)
+    normals = normals_of(source + target, nb)
+    features = fpfh_of(source + target, normals, nb)
+    matched = match(features[:pairs], features[pairs:], mutual=mutual)
+    corr = pairs_of(matched[0], matched[2] if mutual else None)
+    coarse = ransac(source, target, corr, max_correspondence_distance=ransac_distance, hypotheses=hypotheses, seed=seed,
+                    edge_length_ratio=ratio, refine_iterations=refine_iterations, min_correspondences=min_corr)
+    plane = estimation == 'point_to_plane'
+    fine = icp(source, target, init=coarse.transforms, max_correspondence_distance=icp_distance,
+               max_iterations=max_iterations, relative_fitness=rel_f, relative_rmse=rel_r, min_correspondences=min_corr,
+               estimation=estimation, target_normals=normals[pairs:] if plane else None)
+    return coarse, fine
+
+
+# ---------------------------------------------------------------------------------------------------------------- host route
+class _HostBatch:
+    """the (p, q) float32 point pairs of every pair, gathered once"""
+
+    def __init__(self, source, target, correspondences, what):
+        s, s_off, _ = _host_ragged(source, what)
+        t, t_off, _ = _host_ragged(target, what)
+        _same_pairs(s_off, t_off, what)
+        self.pairs = s_off.shape[0] - 1
+
+        def to_rows(c):
+            return c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+        parts, self.c_off = _corr_rows(correspondences, self.pairs, what, to_rows)
+        rows = np.concatenate(parts, 0).astype(np.int64)
+        self.p, self.q = [], []
+        for i in range(self.pairs):
+            r = rows[self.c_off[i]:self.c_off[i + 1]]
+            src, dst = s[s_off[i]:s_off[i + 1]], t[t_off[i]:t_off[i + 1]]
+            if (r < 0).any() or (r[:, 0] >= src.shape[0]).any() or (r[:, 1] >= dst.shape[0]).any():
+                raise ValueError('%s: a correspondence names a row outside its cloud' % what)
+            self.p.append(np.ascontiguousarray(src[r[:, 0]]))
+            self.q.append(np.ascontiguousarray(dst[r[:, 1]]))
+
+    def host_poses(self, poses, valid, what):
+        as_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)      # noqa: E731
+        poses = _poses_of(as_np(poses), self.pairs, what)
+        if valid is None:
+            return poses, np.isfinite(poses).all(2)
+        return poses, _valid_of(as_np(valid), self.pairs, poses.shape[1], what)
+
+
+def _rotate_many(g, v, p, q):
+    """`registration._jacobi_rotate` on arrays: one rotation of every hypothesis at once, the same operations element by
+    element"""
+    alpha = g[0][p] * g[0][p] + g[1][p] * g[1][p] + g[2][p] * g[2][p]
+    beta = g[0][q] * g[0][q] + g[1][q] * g[1][q] + g[2][q] * g[2][q]
+    gamma = g[0][p] * g[0][q] + g[1][p] * g[1][q] + g[2][p] * g[2][q]
+    skip = gamma == 0.0
+    zeta = (beta - alpha) / (2.0 * gamma)
+    t = np.where(zeta >= 0.0, 1.0, -1.0) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+    c = 1.0 / np.sqrt(1.0 + t * t)
+    s = c * t
+    for i in range(3):
+        gp, gq, vp, vq = g[i][p], g[i][q], v[i][p], v[i][q]
+        g[i][p], g[i][q] = np.where(skip, gp, c * gp - s * gq), np.where(skip, gq, s * gp + c * gq)
+        v[i][p], v[i][q] = np.where(skip, vp, c * vp - s * vq), np.where(skip, vq, s * vp + c * vq)
+
+
+def _pick(cols, j):
+    """cols[j[n]][n]: the run-time pick of a column"""
+    return np.where(j == 0, cols[0], np.where(j == 1, cols[1], cols[2]))
+
+
+def _host_kabsch_many(sums):
+    """`registration._host_kabsch_one` on (n, 17) sums at once: (R (n, 3, 3), t (n, 3), solved (n,) bool), the same float64
+    operations in the same order for every row (tests/test_global_registration_host.py compares the bits)"""
+    n_rows = sums.shape[0]
+    with np.errstate(all='ignore'):
+        s = [sums[:, k].astype(np.float64) for k in range(N_SUMS)]
+        n = s[0]
+        g = [[s[7 + 3 * a + b] - s[1 + a] * s[4 + b] / n for b in range(3)] for a in range(3)]
+        v = [[np.full(n_rows, np.float64(a == b)) for b in range(3)] for a in range(3)]
+        for _ in range(JACOBI_SWEEPS):
+            _rotate_many(g, v, 0, 1)
+            _rotate_many(g, v, 0, 2)
+            _rotate_many(g, v, 1, 2)
+        w = [np.sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]) for j in range(3)]
+        i1 = np.where((w[0] >= w[1]) & (w[0] >= w[2]), 0, np.where(w[1] >= w[2], 1, 2))
+        ja, jb = np.where(i1 == 0, 1, 0), np.where(i1 == 2, 1, 2)
+        i2 = np.where(_pick(w, ja) >= _pick(w, jb), ja, jb)
+        w1, w2 = _pick(w, i1), _pick(w, i2)
+        solved = w2 > RANK_TOL * w1
+        u1, u2 = [_pick(g[i], i1) / w1 for i in range(3)], [_pick(g[i], i2) / w2 for i in range(3)]
+        v1, v2 = [_pick(v[i], i1) for i in range(3)], [_pick(v[i], i2) for i in range(3)]
+        u3, v3 = reg._cross(u1, u2), reg._cross(v1, v2)
+        mp, mq = [s[1 + a] / n for a in range(3)], [s[4 + a] / n for a in range(3)]
+        r = [[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)]
+        t = [mq[a] - (r[a][0] * mp[0] + r[a][1] * mp[1] + r[a][2] * mp[2]) for a in range(3)]
+    return (np.stack([np.stack(row, 1) for row in r], 1).reshape(n_rows, 3, 3), np.stack(t, 1).reshape(n_rows, 3), solved)
+
+
+def _host_draws(pair, n_hyp, n_corr, seed):
+    """(H, 3) int32 sample rows of one pair"""
+    ctr = np.zeros((n_hyp, 4), np.uint32)
+    ctr[:, 0] = np.arange(n_hyp, dtype=np.uint32)
+    ctr[:, 1] = np.uint32(pair)
+    x = augment.philox4x32_10(ctr, _key(seed))[:, :3].astype(np.uint64)
+    return ((x * np.uint64(n_corr)) >> np.uint64(32)).astype(np.int32)
+
+
+def _edge2(a, b):
+    d = a - b
+    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def _host_triple_checks(p, q, draws, rho2):
+    """(ok (H,) bool: C >= 3, distinct rows and the edge check; the float64 points (a, b, d) of source and target at those
+    hypotheses)"""
+    i0, i1, i2 = draws[:, 0], draws[:, 1], draws[:, 2]
+    ok = np.full(draws.shape[0], p.shape[0] >= 3) & (i0 != i1) & (i0 != i2) & (i1 != i2)
+    at = np.nonzero(ok)[0]
+    ps = [p[draws[at, k]].astype(np.float64) for k in range(3)]
+    qs = [q[draws[at, k]].astype(np.float64) for k in range(3)]
+    if rho2 > 0.0:
+        edges = np.ones(at.shape[0], bool)
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            ls, lt = _edge2(ps[a], ps[b]), _edge2(qs[a], qs[b])
+            edges &= (ls >= rho2 * lt) & (lt >= rho2 * ls)
+        ok[at[~edges]] = False
+        ps, qs = [x[edges] for x in ps], [x[edges] for x in qs]
+    return ok, ps, qs
+
+
+def _host_triple_sums(ps, qs):
+    """the (n, 17) sums of the three pairs, added in the order 0, 1, 2"""
+    sums = np.zeros((ps[0].shape[0], N_SUMS), np.float64)
+    sums[:, 0] = 3.0
+    for u in range(3):
+        sums[:, 1 + u] = (ps[0][:, u] + ps[1][:, u]) + ps[2][:, u]
+        sums[:, 4 + u] = (qs[0][:, u] + qs[1][:, u]) + qs[2][:, u]
+        for v in range(3):
+            sums[:, 7 + 3 * u + v] = (ps[0][:, u] * qs[0][:, v] + ps[1][:, u] * qs[1][:, v]) + ps[2][:, u] * qs[2][:, v]
+    return sums
+
+
+def _host_hypotheses_one(p, q, pair, n_hyp, seed, rho2):
+    draws = _host_draws(pair, n_hyp, p.shape[0], seed)
+    poses = np.full((n_hyp, 12), np.nan, np.float32)
+    ok, ps, qs = _host_triple_checks(p, q, draws, rho2)
+    at = np.nonzero(ok)[0]
+    r, t, solved = _host_kabsch_many(_host_triple_sums(ps, qs))
+    ok[at[~solved]] = False
+    poses[at[solved]] = np.concatenate([r[solved], t[solved][:, :, None]], 2).reshape(-1, 12).astype(np.float32)
+    return poses, ok, draws
+
+
+def ransac_hypotheses_host(source, target, correspondences, *, hypotheses=4096, seed=0, edge_length_ratio=0.9):
+    """`ransac_hypotheses` on the CPU: `(poses (P, H, 3, 4) float32, valid (P, H) bool, draws (P, H, 3) int32)` numpy."""
+    what = 'ransac_hypotheses'
+    n_hyp, seed, rho2 = _options(hypotheses, seed, edge_length_ratio, what)
+    b = _HostBatch(source, target, correspondences, what)
+    parts = [_host_hypotheses_one(b.p[i], b.q[i], i, n_hyp, seed, rho2) for i in range(b.pairs)]
+    return (np.stack([x[0] for x in parts]).reshape(b.pairs, n_hyp, 3, 4), np.stack([x[1] for x in parts]),
+            np.stack([x[2] for x in parts]))
+
+
+def _host_d2(p, q, m):
+    """(H, C) float32 d2 of the correspondences (p, q) under the (H, 12) float32 poses m"""
+    with np.errstate(all='ignore'):
+        x, y, z = p[None, :, 0], p[None, :, 1], p[None, :, 2]
+        d = [_fmaf(m[:, 4 * c + 2, None], z, _fmaf(m[:, 4 * c + 1, None], y, _fmaf(m[:, 4 * c, None], x, m[:, 4 * c + 3, None])))
+             - q[None, :, c] for c in range(3)]
+        return _fmaf(d[2], d[2], _fmaf(d[1], d[1], d[0] * d[0]))
+
+
+def _host_counts_one(p, q, poses, valid, d2_max):
+    counts = np.where(valid, 0, -1).astype(np.int32)
+    rows = max(1, _HOST_CHUNK // max(p.shape[0], 1))
+    for h0 in range(0, poses.shape[0], rows):
+        sl = slice(h0, h0 + rows)
+        n = (_host_d2(p, q, poses[sl]) <= d2_max).sum(1).astype(np.int32)
+        counts[sl] = np.where(valid[sl], n, -1)
+    return counts
+
+
+def score_hypotheses_host(source, target, correspondences, poses, max_correspondence_distance, valid=None):
+    """`score_hypotheses` on the CPU: (P, H) int32 numpy counts."""
+    what = 'score_hypotheses'
+    dist, _, _ = _polish_options(max_correspondence_distance, 0, 0, what)
+    b = _HostBatch(source, target, correspondences, what)
+    poses, valid = b.host_poses(poses, valid, what)
+    d2_max = inlier_d2(dist)
+    return np.stack([_host_counts_one(b.p[i], b.q[i], poses[i], valid[i], d2_max) for i in range(b.pairs)])
+
+
+def _host_polish_sums(p, q, pose, d2_max):
+    """the 17 sums of the inliers of fp32(pose) among the fixed correspondences"""
+    moved = reg._host_move(p, pose)
+    d = moved - q                                                      # float32 throughout
+    d2 = _fmaf(d[:, 2], d[:, 2], _fmaf(d[:, 1], d[:, 1], d[:, 0] * d[:, 0]))
+    inl = d2 <= d2_max
+    sums = np.zeros(N_SUMS, np.float64)
+    if inl.any():
+        a, b, d = moved[inl].astype(np.float64), q[inl].astype(np.float64), np.sqrt(d2[inl]).astype(np.float64)
+        sums[0] = a.shape[0]
+        sums[1:4], sums[4:7] = a.sum(0), b.sum(0)
+        sums[7:16] = (a[:, :, None] * b[:, None, :]).sum(0).reshape(9)
+        sums[16] = (d * d).sum()
+    return sums
+
+
+def ransac_registration_host(source, target, correspondences, *, max_correspondence_distance=0.8, hypotheses=4096, seed=0,
+                             edge_length_ratio=0.9, refine_iterations=3, min_correspondences=3, poses=None):
+    """`ransac_registration` on the CPU: the module's definition in numpy, pair by pair -> `RansacResult`."""
+    what = 'ransac_registration'
+    n_hyp, seed, rho2 = _options(hypotheses, seed, edge_length_ratio, what)
+    dist, iters, min_corr = _polish_options(max_correspondence_distance, refine_iterations, min_correspondences, what)
+    d2_max = inlier_d2(dist)
+    b = _HostBatch(source, target, correspondences, what)
+    given = None if poses is None else b.host_poses(poses, None, what)
+    pose = np.tile(np.eye(4)[:3], (b.pairs, 1, 1))
+    fitness, rmse = np.zeros(b.pairs, np.float64), np.full(b.pairs, np.nan, np.float64)
+    inliers, status = np.zeros(b.pairs, np.int64), np.zeros(b.pairs, np.int64)
+    chosen, chosen_count, n_valid = (np.full(b.pairs, -1, np.int64), np.full(b.pairs, -1, np.int64),
+                                     np.zeros(b.pairs, np.int64))
+    for i in range(b.pairs):
+        p, q = b.p[i], b.q[i]
+        cand, valid = _host_hypotheses_one(p, q, i, n_hyp, seed, rho2)[:2] if given is None else (given[0][i], given[1][i])
+        counts = _host_counts_one(p, q, cand, valid, d2_max)
+        n_valid[i] = int((counts >= 0).sum())
+        best = int(counts.argmax())                                    # the first of equal maxima: the lowest h
+        if counts[best] < 0:
+            status[i] = NO_HYPOTHESIS
+            continue
+        chosen[i], chosen_count[i] = best, counts[best]
+        pose[i] = cand[best].astype(np.float64).reshape(3, 4)
+        for k in range(iters + 1):
+            sums = _host_polish_sums(p, q, pose[i], d2_max)
+            fitness[i], rmse[i], few = reg._host_figures(sums, p.shape[0], min_corr)
+            inliers[i] = int(sums[0])
+            if few:
+                status[i] = TOO_FEW
+                break
+            if k == iters:
+                status[i] = MAX_ITERATIONS
+                break
+            solved = reg._host_kabsch_one(sums)
+            if solved is None:
+                status[i] = DEGENERATE
+                break
+            r, t = solved
+            pose[i] = np.concatenate([r @ pose[i][:, :3], (r @ pose[i][:, 3] + t)[:, None]], 1)
+    return RansacResult(reg._full(pose), fitness, rmse, inliers, chosen, chosen_count, n_valid, status)
+
+
+def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
+                             estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9,
+                             refine_iterations=3, min_correspondences=3, max_iterations=30, relative_fitness=1e-6,
+                             relative_rmse=1e-6):
+    """`global_registration` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
+    from .fpfh import compute_fpfh_host, feature_correspondences_host
+    from .normals import estimate_normals_host
+    return _global(source, target, estimate_normals_host, compute_fpfh_host, feature_correspondences_host,
+                   correspondence_pairs_host, ransac_registration_host, reg.icp_refine_host, False, nb_neighbors, mutual,
+                   ransac_distance, icp_distance, estimation, hypotheses, seed, edge_length_ratio, refine_iterations,
+                   min_correspondences, max_iterations, relative_fitness, relative_rmse)

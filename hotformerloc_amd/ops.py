@@ -1847,14 +1847,15 @@ def overlap_tiles(lengths):
     return pair_tiles(lengths)[0]
 
 
-def pair_tiles(lengths):
-    """`overlap_tiles` and, beside it, the (P + 1,) int64 offsets of every pair's rows in that table."""
+def pair_tiles(lengths, rows=OVERLAP_ROWS):
+    """`overlap_tiles` and, beside it, the (P + 1,) int64 offsets of every pair's rows in that table; `rows` rows of one pair
+    per workgroup."""
     lengths = np.asarray(lengths, dtype=np.int64)
     tile_off = np.zeros(lengths.shape[0] + 1, np.int64)
-    np.cumsum(-(-lengths // OVERLAP_ROWS), out=tile_off[1:])
+    np.cumsum(-(-lengths // rows), out=tile_off[1:])
     pair = np.repeat(np.arange(lengths.shape[0], dtype=np.int64), np.diff(tile_off))
     start = np.cumsum(lengths) - lengths
-    row = start[pair] + (np.arange(pair.shape[0], dtype=np.int64) - tile_off[pair]) * OVERLAP_ROWS
+    row = start[pair] + (np.arange(pair.shape[0], dtype=np.int64) - tile_off[pair]) * rows
     return np.stack([pair, row], 1), tile_off
 
 
@@ -2002,7 +2003,119 @@ def icp_solve(state: torch.Tensor, istate: torch.Tensor, partials: torch.Tensor,
     return sums
 
 
-VOXEL_MAX_CLOUDS = 32767             # HFL_VOXEL_MAX_CLOUDS
+RANSAC_ROWS = 512                      # HFL_RANSAC_ROWS: hypotheses of a workgroup of hfl_ransac_score (two per thread)
+RANSAC_TILE = 1024                     # HFL_RANSAC_TILE: correspondences of a workgroup of hfl_ransac_score / hfl_ransac_sums
+RANSAC_NO_HYPOTHESIS = 5               # HFL_RANSAC_NO_HYPOTHESIS: a pair's status beside those of the ICP
+
+
+def ransac_tiles(lengths):
+    """The tile table of `hfl_ransac_score` and `hfl_ransac_sums` from the pairs' numbers of correspondences on the host:
+    `pair_tiles` with RANSAC_TILE correspondences of one pair per workgroup -- ((n_tiles, 2) int64 numpy rows of (pair, first
+    correspondence), pairs in order, none for a pair without correspondences; the (P + 1,) int64 offsets of every pair's
+    rows in it)."""
+    return pair_tiles(lengths, RANSAC_TILE)
+
+
+def _ransac_corr_check(what: str, corr: torch.Tensor, c_offsets: torch.Tensor) -> int:
+    """the gathered correspondences of P pairs on the current device -> P"""
+    _dev(corr, c_offsets)
+    if corr.dtype != torch.float32 or corr.dim() != 2 or corr.shape[1] != 6 or not corr.is_contiguous():
+        raise TypeError('%s: contiguous (C, 6) float32 point pairs expected' % what)
+    _offsets_check(what, c_offsets)
+    return int(c_offsets.shape[0]) - 1
+
+
+def _ransac_poses_check(what: str, poses: torch.Tensor, pairs: int) -> int:
+    _dev(poses)
+    if poses.dtype != torch.float32 or poses.dim() != 3 or poses.shape[0] != pairs or poses.shape[1] < 1 or \
+            poses.shape[2] != 12 or not poses.is_contiguous() or poses.data_ptr() % 16:
+        raise TypeError('%s: contiguous, 16-byte aligned (%d, H >= 1, 12) float32 poses expected' % (what, pairs))
+    return int(poses.shape[1])
+
+
+def _ransac_tiles_check(what: str, tiles: torch.Tensor):
+    _dev(tiles)
+    if tiles.dtype != torch.int64 or tiles.dim() != 2 or tiles.shape[1] != 2 or not tiles.is_contiguous():
+        raise TypeError('%s: contiguous (n_tiles, 2) int64 tile table expected' % what)
+
+
+def ransac_hypotheses(corr: torch.Tensor, c_offsets: torch.Tensor, hypotheses: int, seed: int, rho2: float):
+    """`hfl_ransac_hypotheses`: corr (C, 6) fp32 rows (source point, target point) of P pairs under c_offsets (P + 1,) int64,
+    all on the GPU -> (poses (P, H, 12) fp32, valid (P, H) uint8, draws (P, H, 3) int32); an invalid hypothesis has a pose of
+    NaNs.  `rho2`: the squared edge-length ratio as a float64, 0 for no check."""
+    pairs = _ransac_corr_check('ransac_hypotheses', corr, c_offsets)
+    n_hyp = int(hypotheses)
+    if n_hyp < 1 or not float(rho2) >= 0.0 or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError('ransac_hypotheses: hypotheses >= 1, rho2 >= 0 and a seed of 64 bits expected')
+    poses = torch.empty((pairs, n_hyp, 12), dtype=torch.float32, device=corr.device)
+    valid = torch.empty((pairs, n_hyp), dtype=torch.uint8, device=corr.device)
+    draws = torch.empty((pairs, n_hyp, 3), dtype=torch.int32, device=corr.device)
+    check(_native.load().hfl_ransac_hypotheses(poses.data_ptr(), valid.data_ptr(), draws.data_ptr(), _some(corr).data_ptr(),
+                                               c_offsets.data_ptr(), int(corr.shape[0]), pairs, n_hyp, int(seed), float(rho2),
+                                               _stream()), 'hfl_ransac_hypotheses')
+    return poses, valid, draws
+
+
+def ransac_score(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor, poses: torch.Tensor, valid: torch.Tensor,
+                 d2_max: float):
+    """`hfl_ransac_score`: the correspondences as above, the device copy of `ransac_tiles`, poses (P, H, 12) fp32 and valid
+    (P, H) uint8 -> counts (P, H) int32: the correspondences with d2 <= d2_max (fp32) under each pose, -1 where valid is 0."""
+    pairs = _ransac_corr_check('ransac_score', corr, c_offsets)
+    _ransac_tiles_check('ransac_score', tiles)
+    n_hyp = _ransac_poses_check('ransac_score', poses, pairs)
+    _dev(valid)
+    if valid.dtype != torch.uint8 or tuple(valid.shape) != (pairs, n_hyp) or not valid.is_contiguous():
+        raise TypeError('ransac_score: contiguous (%d, %d) uint8 flags expected' % (pairs, n_hyp))
+    counts = torch.empty((pairs, n_hyp), dtype=torch.int32, device=corr.device)
+    check(_native.load().hfl_ransac_score(counts.data_ptr(), valid.data_ptr(), poses.data_ptr(), _some(corr).data_ptr(),
+                                          c_offsets.data_ptr(), int(corr.shape[0]), _some(tiles).data_ptr(),
+                                          int(tiles.shape[0]), pairs, n_hyp, float(d2_max), _stream()), 'hfl_ransac_score')
+    return counts
+
+
+def ransac_select(counts: torch.Tensor, poses: torch.Tensor):
+    """`hfl_ransac_select`: counts (P, H) int32 and poses (P, H, 12) fp32 -> (state (P, 16) float64, istate (P, 2) int32,
+    chosen (P, 3) int32): the pose of the largest count (the lowest h of equal ones) as the state `icp_solve` takes, RUNNING
+    at iteration 0, and (h, its count, the number of counts >= 0); a pair whose counts are all -1 gets the identity,
+    RANSAC_NO_HYPOTHESIS and (-1, -1, 0)."""
+    _dev(counts)
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] < 1 or not counts.is_contiguous():
+        raise TypeError('ransac_select: contiguous (P >= 1, H) int32 counts expected')
+    pairs = int(counts.shape[0])
+    n_hyp = _ransac_poses_check('ransac_select', poses, pairs)
+    if int(counts.shape[1]) != n_hyp:
+        raise TypeError('ransac_select: %d counts for %d poses per pair' % (int(counts.shape[1]), n_hyp))
+    state = torch.empty((pairs, 16), dtype=torch.float64, device=counts.device)
+    istate = torch.empty((pairs, 2), dtype=torch.int32, device=counts.device)
+    chosen = torch.empty((pairs, 3), dtype=torch.int32, device=counts.device)
+    check(_native.load().hfl_ransac_select(state.data_ptr(), istate.data_ptr(), chosen.data_ptr(), counts.data_ptr(),
+                                           poses.data_ptr(), pairs, n_hyp, _stream()), 'hfl_ransac_select')
+    return state, istate, chosen
+
+
+def ransac_sums(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor, state: torch.Tensor, istate: torch.Tensor,
+                d2_max: float, partials=None):
+    """`hfl_ransac_sums`: one evaluation of every RUNNING pair on its fixed correspondences -> partials (n_tiles, ICP_SUMS)
+    float64, written in place where one is given: what `icp_solve` takes with the tile offsets of `ransac_tiles` and
+    `c_offsets` as the source offsets."""
+    pairs = _ransac_corr_check('ransac_sums', corr, c_offsets)
+    _ransac_tiles_check('ransac_sums', tiles)
+    _icp_state_check('ransac_sums', state, istate, pairs)
+    n_tiles = int(tiles.shape[0])
+    if partials is None:
+        partials = torch.empty((max(n_tiles, 1), ICP_SUMS), dtype=torch.float64, device=corr.device)
+    _dev(partials)
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
+            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
+        raise TypeError('ransac_sums: contiguous (>= %d, %d) float64 partials expected' % (n_tiles, ICP_SUMS))
+    if n_tiles:
+        check(_native.load().hfl_ransac_sums(partials.data_ptr(), corr.data_ptr(), c_offsets.data_ptr(), int(corr.shape[0]),
+                                             tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(), pairs,
+                                             float(d2_max), _stream()), 'hfl_ransac_sums')
+    return partials
+
+
+VOXEL_MAX_CLOUDS = 32767            # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
 

@@ -79,7 +79,7 @@ from .overlap import _fmaf, _host_argmin32, _host_ragged, _matrices, _ragged, _s
 RUNNING, CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE = range(5)     # HFL_ICP_*: a pair's status
 N_SUMS = 17                            # n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2
 N_SUMS_PLANE = 29                      # n, sum d^2, g (6), the upper triangle of A row-major (21)
-JACOBI_SWEEPS = 12                     # RG_SWEEPS of csrc/registration.hip
+JACOBI_SWEEPS = 12                     # KABSCH_SWEEPS of csrc/kabsch.h
 RANK_TOL = 1e-12                       # second singular value <= RANK_TOL x the largest: DEGENERATE
 PIVOT_TOL = 1e-12                      # a pivot of the LDL^T <= PIVOT_TOL x its diagonal entry of A: DEGENERATE
 ESTIMATIONS = ('point_to_point', 'point_to_plane')
@@ -340,7 +340,7 @@ def _cross(a, b):
 
 
 def _host_kabsch_one(s):
-    """(R (3, 3), t (3,)) of one pair's sums, or None where H has rank < 2: `kabsch_solve` of csrc/registration.hip, line by
+    """(R (3, 3), t (3,)) of one pair's sums, or None where H has rank < 2: `kabsch_solve` of csrc/kabsch.h, line by
     line, on numpy float64 scalars"""
     with np.errstate(all='ignore'):
         s = [np.float64(x) for x in s]

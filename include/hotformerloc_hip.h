@@ -1270,6 +1270,51 @@ int hfl_icp_solve_plane(double* state, int32_t* istate, double* sums, const doub
                         double relative_fitness, double relative_rmse, int is_last, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11g. Global registration from point correspondences: a deterministic RANSAC that gives hfl_icp_correspond its starting
+ *      pose (csrc/global_registration.hip; no counterpart in the reference).  Definition:
+ *      hotformerloc_amd/global_registration.py, DESIGN.md section 7n.
+ * ---------------------------------------------------------------------- */
+#define HFL_RANSAC_ROWS 512               /* hypotheses of a 256-thread workgroup of hfl_ransac_score (two per thread) */
+#define HFL_RANSAC_TILE 1024              /* correspondences of a workgroup of hfl_ransac_score and hfl_ransac_sums */
+#define HFL_RANSAC_NO_HYPOTHESIS 5        /* a pair's status beside HFL_ICP_*: no valid hypothesis, the pose is the identity */
+/* All four take the correspondences of P pairs as one ragged batch: corr (n_corr, 6) fp32 rows (px, py, pz, qx, qy, qz),
+ * source point and target point, with (P + 1) int64 DEVICE offsets, clamped to the array.  A hypothesis is twelve fp32
+ * values, the row-major (R | t) of hfl_transform_points; poses is (P, H, 12), valid (P, H) uint8, counts (P, H) int32.
+ * tiles (n_tiles, 2) int64 DEVICE rows of (pair, first correspondence), HFL_RANSAC_TILE correspondences of one pair per
+ * workgroup.  Launches on `stream`, no synchronisation, no host read, no float atomics: two runs give the same bits.  A NULL
+ * pointer, a negative count, P < 1 or H < 1: HFL_EINVAL; n_corr, P, H, P x H or the tiles at 2^31 or more, or more than
+ * 65535 x HFL_RANSAC_ROWS hypotheses: HFL_ECAPACITY. */
+/* Hypothesis h of pair p: (x0, x1, x2, _) = Philox4x32-10(counter (h, p, 0, 0), key = seed), rows i_k = (x_k * C) >> 32 of
+ * the pair's C correspondences (written to draws (P, H, 3) int32 in any case).  Invalid (valid = 0, the pose twelve NaNs)
+ * where C < 3, two rows are equal, an edge of the triple fails ls >= rho2 lt and lt >= rho2 ls (squared lengths in float64
+ * between the source points and between the target points; rho2 = 0 disables it) or the solve of hfl_icp_solve on the 17
+ * sums of the three pairs reports rank < 2; otherwise its (R | t) rounded to fp32. */
+int hfl_ransac_hypotheses(float* poses, uint8_t* valid, int32_t* draws, const float* corr, const int64_t* c_offsets,
+                          int64_t n_corr, int64_t n_pairs, int64_t n_hypotheses, uint64_t seed, double rho2,
+                          hfl_stream_t stream);
+/* counts[p, h] = -1 where valid[p, h] = 0, else the number of the pair's correspondences with d2 <= d2_max in fp32, d2 the
+ * squared distance of hfl_nn_dist between the moved source point (the fmaf chain of hfl_transform_points) and the target
+ * point.  Two launches: the first writes 0 or -1, the second adds every (correspondence tile, hypothesis tile)'s counts by
+ * integer atomic adds. */
+int hfl_ransac_score(int32_t* counts, const uint8_t* valid, const float* poses, const float* corr, const int64_t* c_offsets,
+                     int64_t n_corr, const int64_t* tiles, int64_t n_tiles, int64_t n_pairs, int64_t n_hypotheses,
+                     float d2_max, hfl_stream_t stream);
+/* One workgroup per pair: the largest count, of equal counts the lowest h.  chosen (P, 3) int32 = that h, its count, the
+ * number of counts >= 0; state (P, 16) float64 and istate (P, 2) int32 of section 11f receive the chosen pose, fitness 0,
+ * rmse NaN, iteration 0 and HFL_ICP_RUNNING -- or, where every count is -1, the identity, HFL_RANSAC_NO_HYPOTHESIS and
+ * chosen = (-1, -1, 0). */
+int hfl_ransac_select(double* state, int32_t* istate, int32_t* chosen, const int32_t* counts, const float* poses,
+                      int64_t n_pairs, int64_t n_hypotheses, hfl_stream_t stream);
+/* hfl_icp_correspond with the correspondences fixed: for every RUNNING pair the inliers (d2 <= d2_max as above) of the fp32
+ * rounding of the pose in `state` are reduced to partials (n_tiles, HFL_ICP_SUMS) float64 in the order of
+ * hfl_icp_correspond (d = the correctly rounded fp32 root of d2), row i for tile i; hfl_icp_solve with tile offsets over
+ * this table and c_offsets as its denominators then decides and updates.  Rows of pairs that are not RUNNING are not
+ * written. */
+int hfl_ransac_sums(double* partials, const float* corr, const int64_t* c_offsets, int64_t n_corr, const int64_t* tiles,
+                    int64_t n_tiles, const double* state, const int32_t* istate, int64_t n_pairs, float d2_max,
+                    hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
