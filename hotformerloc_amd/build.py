@@ -71,11 +71,9 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(LIBDIR, 'obj')
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'hfl_common.h'), os.path.join(CSRC, 'x3_math.h'), os.path.join(CSRC, 'stage_stream.h'),
-               os.path.join(CSRC, 'prep_common.h'), os.path.join(CSRC, 'ragged_common.h'), os.path.join(CSRC, 'ln_row.h'),
-               os.path.join(CSRC, 'knn_common.h'), os.path.join(CSRC, 'pair_scan.h'), os.path.join(CSRC, 'jacobi3.h'),
-               os.path.join(CSRC, 'kabsch.h'), os.path.join(CSRC, 'philox.h'),
-               os.path.join(HERE, '..', 'include', 'hotformerloc_hip.h')]
+    # every header: one that is left out leaves stale objects behind when objects are reused
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + \
+        [os.path.join(HERE, '..', 'include', 'hotformerloc_hip.h')]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

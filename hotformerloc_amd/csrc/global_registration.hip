@@ -21,12 +21,13 @@
 // identity, fitness 0 and rmse NaN where every count is -1.
 //
 // hfl_ransac_sums: hfl_icp_correspond without the search.  A workgroup owns the RS_TILE correspondences of one row of the
-// tile table, moves p by the fp32 rounding of the pair's pose, and reduces the 17 float64 sums of its inliers in the order of
-// icp_correspond_kernel (a thread its rows in row order, the xor butterfly, the four waves in wave order) into row
-// blockIdx.x of the partials, which hfl_icp_solve reads as it reads those of hfl_icp_correspond.  A pair that is not RUNNING
-// makes its workgroups return at once.
+// tile table, moves p by the fp32 rounding of the pair's pose, and adds and reduces the 17 float64 sums of its inliers by the
+// row step and the reduction of icp_sums.h, the code icp_correspond_kernel runs (a thread its rows in row order, the xor
+// butterfly, the four waves in wave order), into row blockIdx.x of the partials, which hfl_icp_solve reads as it reads those
+// of hfl_icp_correspond.  A pair that is not RUNNING makes its workgroups return at once.
 #include <math.h>
 
+#include "icp_sums.h"
 #include "kabsch.h"
 #include "pair_scan.h"
 #include "philox.h"
@@ -57,12 +58,17 @@ __device__ __forceinline__ bool corr_tile(CorrTile& w, const int64_t* __restrict
   return true;
 }
 
-// d2 of the pair scan on p' - q
+// p' = the row-major (R | t) m on p, and the d2 of the pair scan on p' - q
+__device__ __forceinline__ float corr_move_d2(const float* __restrict__ m, float px, float py, float pz, float qx, float qy,
+                                              float qz, float (&moved)[3]) {
+  moved[0] = rigid_coord(m, px, py, pz), moved[1] = rigid_coord(m + 4, px, py, pz), moved[2] = rigid_coord(m + 8, px, py, pz);
+  const float dx = moved[0] - qx, dy = moved[1] - qy, dz = moved[2] - qz;
+  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
 __device__ __forceinline__ float corr_d2(const float* __restrict__ m, float px, float py, float pz, float qx, float qy,
                                          float qz) {
-  const float dx = rigid_coord(m, px, py, pz) - qx, dy = rigid_coord(m + 4, px, py, pz) - qy,
-              dz = rigid_coord(m + 8, px, py, pz) - qz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+  float moved[3];
+  return corr_move_d2(m, px, py, pz, qx, qy, qz, moved);
 }
 
 __device__ __forceinline__ double edge2(const float* __restrict__ a, const float* __restrict__ b) {
@@ -250,39 +256,17 @@ ransac_sums_kernel(double* __restrict__ partials, const float* __restrict__ corr
     const int64_t row = w.row0 + r * RS_THREADS + threadIdx.x;
     if (row < w.c_end) {
       const float* c = corr + 6 * row;
-      const float px = rigid_coord(m, c[0], c[1], c[2]), py = rigid_coord(m + 4, c[0], c[1], c[2]),
-                  pz = rigid_coord(m + 8, c[0], c[1], c[2]);
-      const float dx = px - c[3], dy = py - c[4], dz = pz - c[5];
-      const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+      float p[3];
+      const float d2 = corr_move_d2(m, c[0], c[1], c[2], c[3], c[4], c[5], p);
       if (d2 <= d2_max) {
-        const double pc[3] = {(double)px, (double)py, (double)pz};
+        const double pc[3] = {(double)p[0], (double)p[1], (double)p[2]};
         const double qc[3] = {(double)c[3], (double)c[4], (double)c[5]};
         const double dd = (double)pair_sqrt(d2);
-        acc[0] += 1.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          acc[1 + a] += pc[a];
-          acc[4 + a] += qc[a];
-#pragma unroll
-          for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += pc[a] * qc[b];     // exact products
-        }
-        acc[16] += dd * dd;
+        icp_point_row(acc, pc, qc, dd);
       }
     }
   }
-  const int lane = threadIdx.x & (HFL_WAVE - 1), wave = threadIdx.x / HFL_WAVE;
-#pragma unroll
-  for (int k = 0; k < RS_SUMS; ++k) acc[k] = wave_sum(acc[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < RS_SUMS; ++k) red[wave * RS_SUMS + k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < RS_SUMS) {
-    double v = red[threadIdx.x];
-    for (int u = 1; u < RS_WAVES; ++u) v += red[u * RS_SUMS + threadIdx.x];
-    partials[(int64_t)blockIdx.x * RS_SUMS + threadIdx.x] = v;
-  }
+  icp_reduce_partials<RS_SUMS, RS_THREADS>(acc, red, partials);
 }
 
 }  // namespace

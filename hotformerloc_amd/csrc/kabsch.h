@@ -1,8 +1,8 @@
 // The rigid update (R | t) of the 17 float64 sums n, Sp (3), Sq (3), Spq (9, row-major: p down, q across), sum d^2 of a set
 // of point pairs p -> q, once, for everything that solves it: hfl_icp_solve (csrc/registration.hip) on the inliers of an ICP
 // iteration and of the RANSAC polish, hfl_ransac_hypotheses (csrc/global_registration.hip) on a drawn triple.  A one-sided
-// cyclic Jacobi on H = Spq - Sp Sq^T / n with a fixed number of sweeps; `_host_kabsch_one` of hotformerloc_amd/registration.py
-// transcribes it line by line.  No array is indexed by a run-time value.
+// cyclic Jacobi on H = Spq - Sp Sq^T / n with a fixed number of sweeps; `_host_kabsch_many` of hotformerloc_amd/registration.py
+// is its one numpy transcription, line by line on arrays of rows.  No array is indexed by a run-time value.
 #pragma once
 #include <math.h>
 

@@ -13,10 +13,8 @@
 // coordinates from global memory once the scan is over, and sums over its inlier rows (d <= max_dist in fp32) the 17
 // float64 quantities
 //     n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2         p' the moved source point, q its target.
-// Every product of two fp32 values is exact in float64, so contracting a product into its sum changes no bit.  Order: a
-// thread adds its rows in row order, a wave combines its lanes by the xor butterfly 32 .. 1, and the four wave results are
-// added in wave order (threads 0 .. 16, one quantity each): the order of pair_stats_kernel.  The result is row blockIdx.x of
-// the (n_tiles, 17) partials.
+// The row step and the reduction, and with them the order of every addition, are those of icp_sums.h, which hfl_ransac_sums
+// (csrc/global_registration.hip) runs as well.  The result is row blockIdx.x of the (n_tiles, 17) partials.
 //
 // hfl_icp_solve: one wave per pair.  Lanes 0 .. 16 add the pair's tile partials in ascending tile order, one quantity each;
 // lane 0 then applies the stop rules, solves for the rigid update and composes the pose, all in float64.  The solve is a
@@ -37,6 +35,7 @@
 // No atomics; every output element has one writer and a fixed evaluation order: two runs give the same bits.
 #include <math.h>
 
+#include "icp_sums.h"
 #include "kabsch.h"
 #include "pair_scan.h"
 
@@ -108,7 +107,6 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
         const double pc[3] = {(double)qx[r], (double)qy[r], (double)qz[r]};
         const double qc[3] = {(double)w[0], (double)w[1], (double)w[2]};
         const double dd = (double)d;
-        acc[0] += 1.0;
         if constexpr (PLANE) {
           // the normal at the winner, read once per source row; r, a = p' x n and J = (a, n) with every operation rounded
           // once, so the rows are the host route's to the bit and only the order of the sums differs
@@ -120,6 +118,7 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
           const double jac[6] = {__dsub_rn(__dmul_rn(pc[1], nc[2]), __dmul_rn(pc[2], nc[1])),
                                  __dsub_rn(__dmul_rn(pc[2], nc[0]), __dmul_rn(pc[0], nc[2])),
                                  __dsub_rn(__dmul_rn(pc[0], nc[1]), __dmul_rn(pc[1], nc[0])), nc[0], nc[1], nc[2]};
+          acc[0] += 1.0;
           acc[1] += dd * dd;
           int slot = 8;
 #pragma unroll
@@ -129,34 +128,14 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
             for (int b = a; b < 6; ++b) acc[slot++] += jac[a] * jac[b];     // a zero normal adds zeros
           }
         } else {
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            acc[1 + a] += pc[a];
-            acc[4 + a] += qc[a];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) acc[7 + 3 * a + b] += pc[a] * qc[b];
-          }
-          acc[16] += dd * dd;
+          icp_point_row(acc, pc, qc, dd);
         }
       }
     }
   }
 
-  double* red = reinterpret_cast<double*>(s_x);                  // (RG_WAVES, NS)
-  const int lane = threadIdx.x & (HFL_WAVE - 1), wave = threadIdx.x / HFL_WAVE;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc[k] = wave_sum(acc[k]);
   __syncthreads();                                               // the last tile has been read by every wave
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) red[wave * NS + k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = red[threadIdx.x];
-    for (int w = 1; w < RG_WAVES; ++w) v += red[w * NS + threadIdx.x];
-    partials[(int64_t)blockIdx.x * NS + threadIdx.x] = v;
-  }
+  icp_reduce_partials<NS, RG_THREADS>(acc, reinterpret_cast<double*>(s_x), partials);          // (RG_WAVES, NS) in the x plane
 }
 
 // the point-to-plane update (R | t) of the 29 sums: A x = -g by an LDL^T factorisation without pivoting in a fixed operation
@@ -287,16 +266,44 @@ icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, doubl
 
 }  // namespace
 
+namespace {
+
+// `target_normals` is required with PLANE and not looked at without
+template <bool PLANE>
+int icp_correspond_call(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
+                        int64_t n_source, const float* targets, const float* target_normals, const int64_t* t_offsets,
+                        int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
+                        float max_dist, int64_t n_pairs, hfl_stream_t stream) {
+  return pair_scan_call({partials, source, s_offsets, targets, t_offsets, tiles, state, istate},
+                        !PLANE || target_normals != nullptr, n_source, n_targets, n_tiles, n_pairs, [&] {
+    icp_correspond_kernel<PLANE><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+        partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
+        max_dist, (int)n_pairs);
+  });
+}
+
+template <bool PLANE>
+int icp_solve_call(double* state, int32_t* istate, double* sums, const double* partials, const int64_t* tile_offsets,
+                   int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs, int min_correspondences,
+                   double relative_fitness, double relative_rmse, int is_last, hfl_stream_t stream) {
+  if (state == nullptr || istate == nullptr || partials == nullptr || tile_offsets == nullptr || s_offsets == nullptr ||
+      n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
+    return HFL_EINVAL;
+  if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
+  icp_solve_kernel<PLANE><<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
+      state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
+      is_last);
+  HFL_RETURN_LAST_ERROR();
+}
+
+}  // namespace
+
 extern "C" int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
                                   int64_t n_source, const float* targets, const int64_t* t_offsets, int64_t n_targets,
                                   const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                   float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  return pair_scan_call({partials, source, s_offsets, targets, t_offsets, tiles, state, istate}, true, n_source, n_targets,
-                        n_tiles, n_pairs, [&] {
-    icp_correspond_kernel<false><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-        partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets, tiles, state, istate,
-        max_dist, (int)n_pairs);
-  });
+  return icp_correspond_call<false>(partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets,
+                                    tiles, n_tiles, state, istate, max_dist, n_pairs, stream);
 }
 
 extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const float* source,
@@ -304,38 +311,22 @@ extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* 
                                         const float* target_normals, const int64_t* t_offsets, int64_t n_targets,
                                         const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                         float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  return pair_scan_call({partials, source, s_offsets, targets, target_normals, t_offsets, tiles, state, istate}, true,
-                        n_source, n_targets, n_tiles, n_pairs, [&] {
-    icp_correspond_kernel<true><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-        partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
-        max_dist, (int)n_pairs);
-  });
+  return icp_correspond_call<true>(partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets,
+                                   n_targets, tiles, n_tiles, state, istate, max_dist, n_pairs, stream);
 }
 
 extern "C" int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials,
                              const int64_t* tile_offsets, int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs,
                              int min_correspondences, double relative_fitness, double relative_rmse, int is_last,
                              hfl_stream_t stream) {
-  if (state == nullptr || istate == nullptr || partials == nullptr || tile_offsets == nullptr || s_offsets == nullptr ||
-      n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
-    return HFL_EINVAL;
-  if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  icp_solve_kernel<false><<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
-      state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
-      is_last);
-  HFL_RETURN_LAST_ERROR();
+  return icp_solve_call<false>(state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, n_pairs, min_correspondences,
+                               relative_fitness, relative_rmse, is_last, stream);
 }
 
 extern "C" int hfl_icp_solve_plane(double* state, int32_t* istate, double* sums, const double* partials,
                                    const int64_t* tile_offsets, int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs,
                                    int min_correspondences, double relative_fitness, double relative_rmse, int is_last,
                                    hfl_stream_t stream) {
-  if (state == nullptr || istate == nullptr || partials == nullptr || tile_offsets == nullptr || s_offsets == nullptr ||
-      n_tiles < 0 || n_pairs < 1 || min_correspondences < 0)
-    return HFL_EINVAL;
-  if (n_tiles > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return HFL_ECAPACITY;
-  icp_solve_kernel<true><<<(unsigned)n_pairs, HFL_WAVE, 0, static_cast<hipStream_t>(stream)>>>(
-      state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, min_correspondences, relative_fitness, relative_rmse,
-      is_last);
-  HFL_RETURN_LAST_ERROR();
+  return icp_solve_call<true>(state, istate, sums, partials, tile_offsets, n_tiles, s_offsets, n_pairs, min_correspondences,
+                              relative_fitness, relative_rmse, is_last, stream);
 }

@@ -60,7 +60,7 @@ import torch
 
 from . import _native, ops, outliers, ragged
 from .normals import _check_neighbours
-from .overlap import _host_argmin32, _host_d2_32
+from .overlap import _as_numpy, _host_argmin32, _host_d2_32
 
 BINS, DIM = 11, ops.FPFH_DIM
 _EDGES = -np.pi + 2.0 * np.pi * np.arange(1, BINS, dtype=np.float64) / float(BINS)
@@ -269,7 +269,7 @@ def _feature_rows(batch, what: str):
         np.cumsum([c.shape[0] for c in parts], out=off[1:])
         return torch.cat(parts, 0).contiguous(), off, True
     offsets = batch[1]
-    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    off = _as_numpy(offsets)
     if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
         raise ValueError('%s: (P + 1,) integer offsets with P >= 1 expected' % what)
     off = off.astype(np.int64)

@@ -70,8 +70,10 @@ import torch
 
 from . import augment
 from . import registration as reg
-from .overlap import _fmaf, _host_ragged, _ragged, _same_pairs
-from .registration import DEGENERATE, MAX_ITERATIONS, RANK_TOL, RUNNING, TOO_FEW, JACOBI_SWEEPS, N_SUMS
+from .overlap import _as_numpy, _fmaf, _host_ragged, _ragged, _same_pairs
+# the statuses of a `RansacResult` and the solver's constants are names of this module too
+from .registration import DEGENERATE, MAX_ITERATIONS, RANK_TOL, RUNNING, TOO_FEW, JACOBI_SWEEPS, N_SUMS      # noqa: F401
+from .registration import _host_kabsch_many
 
 NO_HYPOTHESIS = 5                      # HFL_RANSAC_NO_HYPOTHESIS: every hypothesis of the pair was invalid
 _HOST_CHUNK = 1 << 21                  # (hypothesis, correspondence) tests of one temporary of the numpy route
@@ -99,14 +101,9 @@ def _options(hypotheses, seed, edge_length_ratio, what):
 
 
 def _polish_options(max_correspondence_distance, refine_iterations, min_correspondences, what):
-    d = float(max_correspondence_distance)
-    if not d >= 0.0:
-        raise ValueError('%s: max_correspondence_distance must be a number >= 0' % what)
-    if int(refine_iterations) != refine_iterations or refine_iterations < 0:
-        raise ValueError('%s: refine_iterations must be an integer >= 0' % what)
-    if int(min_correspondences) != min_correspondences or min_correspondences < 0:
-        raise ValueError('%s: min_correspondences must be an integer >= 0' % what)
-    return d, int(refine_iterations), int(min_correspondences)
+    d, iters, _, _, min_corr = reg._options(max_correspondence_distance, refine_iterations, 0.0, 0.0, min_correspondences, what,
+                                            'refine_iterations')
+    return d, iters, min_corr
 
 
 def inlier_d2(max_correspondence_distance):
@@ -147,7 +144,7 @@ def _corr_rows(correspondences, pairs, what, to_rows):
         np.cumsum([c.shape[0] for c in parts], out=off[1:])
         return parts, off
     offsets = correspondences[1]
-    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    off = _as_numpy(offsets)
     if off.ndim != 1 or off.shape[0] != pairs + 1 or not np.issubdtype(off.dtype, np.integer):
         raise ValueError('%s: (%d,) integer correspondence offsets expected: they must pair up with the clouds'
                          % (what, pairs + 1))
@@ -262,17 +259,14 @@ def ransac_registration(source, target, correspondences, *, max_correspondence_d
         counts = ops.ransac_score(b.corr, b.c_dev, b.tiles, poses, valid, d2_max)
         state, istate, chosen = ops.ransac_select(counts, poses)
         partials = torch.zeros((max(b.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=b.device)
-        inliers = torch.zeros(b.pairs, dtype=torch.float64, device=b.device)
-        for k in range(iters + 1):
-            running = istate[:, 1] == RUNNING
-            ops.ransac_sums(b.corr, b.c_dev, b.tiles, state, istate, d2_max, partials=partials)
-            sums = ops.icp_solve(state, istate, partials, b.tile_off, b.n_tiles, b.c_dev, min_corr, 0.0, 0.0, k == iters,
-                                 want_sums=True)
-            inliers = torch.where(running, sums[:, 0], inliers)        # the n of the evaluation a pair stopped at
-        state, istate = state.cpu().numpy(), istate.cpu().numpy().astype(np.int64)
+        _, _, inliers = reg._iterate_on_device(
+            state, istate, iters, lambda st, ist: ops.ransac_sums(b.corr, b.c_dev, b.tiles, st, ist, d2_max, partials=partials),
+            lambda st, ist, is_last: ops.icp_solve(st, ist, partials, b.tile_off, b.n_tiles, b.c_dev, min_corr, 0.0, 0.0,
+                                                   is_last, want_sums=True), count=True)
+        transforms, fitness, rmse, _, status = reg._read_state(state, istate)
         chosen, inliers = chosen.cpu().numpy().astype(np.int64), inliers.cpu().numpy().astype(np.int64)
-    return RansacResult(reg._full(state[:, :12].reshape(-1, 3, 4)), state[:, 12].copy(), state[:, 13].copy(), inliers,
-                        chosen[:, 0].copy(), chosen[:, 1].copy(), chosen[:, 2].copy(), istate[:, 1].copy())
+    return RansacResult(transforms, fitness, rmse, inliers, chosen[:, 0].copy(), chosen[:, 1].copy(), chosen[:, 2].copy(),
+                        status)
 
 
 def _pairs_of(idx, mask, xp):
@@ -303,7 +297,7 @@ def _correspondence_pairs(idx, mask, as_array, xp, what):
     if as_list:
         return [_pairs_of(part, None if masks is None else masks[i], xp) for i, part in enumerate(parts)]
     offsets = idx[1]
-    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    off = _as_numpy(offsets)
     off = off.astype(np.int64)
     if off.ndim != 1 or off.shape[0] < 2 or off[0] != 0 or off[-1] != parts[0].shape[0] or (np.diff(off) < 0).any():
         raise ValueError('%s: offsets must start at 0, not decrease, and end at the number of rows (%d)'
@@ -324,9 +318,7 @@ def correspondence_pairs(idx, mask=None):
 
 def correspondence_pairs_host(idx, mask=None):
     """`correspondence_pairs` in numpy."""
-    def as_array(x):
-        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return _correspondence_pairs(idx, mask, as_array, np, 'correspondence_pairs')
+    return _correspondence_pairs(idx, mask, _as_numpy, np, 'correspondence_pairs')
 
 
 def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
@@ -376,10 +368,7 @@ class _HostBatch:
         t, t_off, _ = _host_ragged(target, what)
         _same_pairs(s_off, t_off, what)
         self.pairs = s_off.shape[0] - 1
-
-        def to_rows(c):
-            return c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
-        parts, self.c_off = _corr_rows(correspondences, self.pairs, what, to_rows)
+        parts, self.c_off = _corr_rows(correspondences, self.pairs, what, _as_numpy)
         rows = np.concatenate(parts, 0).astype(np.int64)
         self.p, self.q = [], []
         for i in range(self.pairs):
@@ -391,61 +380,10 @@ class _HostBatch:
             self.q.append(np.ascontiguousarray(dst[r[:, 1]]))
 
     def host_poses(self, poses, valid, what):
-        as_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)      # noqa: E731
-        poses = _poses_of(as_np(poses), self.pairs, what)
+        poses = _poses_of(_as_numpy(poses), self.pairs, what)
         if valid is None:
             return poses, np.isfinite(poses).all(2)
-        return poses, _valid_of(as_np(valid), self.pairs, poses.shape[1], what)
-
-
-def _rotate_many(g, v, p, q):
-    """`registration._jacobi_rotate` on arrays: one rotation of every hypothesis at once, the same operations element by
-    element"""
-    alpha = g[0][p] * g[0][p] + g[1][p] * g[1][p] + g[2][p] * g[2][p]
-    beta = g[0][q] * g[0][q] + g[1][q] * g[1][q] + g[2][q] * g[2][q]
-    gamma = g[0][p] * g[0][q] + g[1][p] * g[1][q] + g[2][p] * g[2][q]
-    skip = gamma == 0.0
-    zeta = (beta - alpha) / (2.0 * gamma)
-    t = np.where(zeta >= 0.0, 1.0, -1.0) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
-    c = 1.0 / np.sqrt(1.0 + t * t)
-    s = c * t
-    for i in range(3):
-        gp, gq, vp, vq = g[i][p], g[i][q], v[i][p], v[i][q]
-        g[i][p], g[i][q] = np.where(skip, gp, c * gp - s * gq), np.where(skip, gq, s * gp + c * gq)
-        v[i][p], v[i][q] = np.where(skip, vp, c * vp - s * vq), np.where(skip, vq, s * vp + c * vq)
-
-
-def _pick(cols, j):
-    """cols[j[n]][n]: the run-time pick of a column"""
-    return np.where(j == 0, cols[0], np.where(j == 1, cols[1], cols[2]))
-
-
-def _host_kabsch_many(sums):
-    """`registration._host_kabsch_one` on (n, 17) sums at once: (R (n, 3, 3), t (n, 3), solved (n,) bool), the same float64
-    operations in the same order for every row (tests/test_global_registration_host.py compares the bits)"""
-    n_rows = sums.shape[0]
-    with np.errstate(all='ignore'):
-        s = [sums[:, k].astype(np.float64) for k in range(N_SUMS)]
-        n = s[0]
-        g = [[s[7 + 3 * a + b] - s[1 + a] * s[4 + b] / n for b in range(3)] for a in range(3)]
-        v = [[np.full(n_rows, np.float64(a == b)) for b in range(3)] for a in range(3)]
-        for _ in range(JACOBI_SWEEPS):
-            _rotate_many(g, v, 0, 1)
-            _rotate_many(g, v, 0, 2)
-            _rotate_many(g, v, 1, 2)
-        w = [np.sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]) for j in range(3)]
-        i1 = np.where((w[0] >= w[1]) & (w[0] >= w[2]), 0, np.where(w[1] >= w[2], 1, 2))
-        ja, jb = np.where(i1 == 0, 1, 0), np.where(i1 == 2, 1, 2)
-        i2 = np.where(_pick(w, ja) >= _pick(w, jb), ja, jb)
-        w1, w2 = _pick(w, i1), _pick(w, i2)
-        solved = w2 > RANK_TOL * w1
-        u1, u2 = [_pick(g[i], i1) / w1 for i in range(3)], [_pick(g[i], i2) / w2 for i in range(3)]
-        v1, v2 = [_pick(v[i], i1) for i in range(3)], [_pick(v[i], i2) for i in range(3)]
-        u3, v3 = reg._cross(u1, u2), reg._cross(v1, v2)
-        mp, mq = [s[1 + a] / n for a in range(3)], [s[4 + a] / n for a in range(3)]
-        r = [[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)]
-        t = [mq[a] - (r[a][0] * mp[0] + r[a][1] * mp[1] + r[a][2] * mp[2]) for a in range(3)]
-    return (np.stack([np.stack(row, 1) for row in r], 1).reshape(n_rows, 3, 3), np.stack(t, 1).reshape(n_rows, 3), solved)
+        return poses, _valid_of(_as_numpy(valid), self.pairs, poses.shape[1], what)
 
 
 def _host_draws(pair, n_hyp, n_corr, seed):
@@ -548,14 +486,7 @@ def _host_polish_sums(p, q, pose, d2_max):
     d = moved - q                                                      # float32 throughout
     d2 = _fmaf(d[:, 2], d[:, 2], _fmaf(d[:, 1], d[:, 1], d[:, 0] * d[:, 0]))
     inl = d2 <= d2_max
-    sums = np.zeros(N_SUMS, np.float64)
-    if inl.any():
-        a, b, d = moved[inl].astype(np.float64), q[inl].astype(np.float64), np.sqrt(d2[inl]).astype(np.float64)
-        sums[0] = a.shape[0]
-        sums[1:4], sums[4:7] = a.sum(0), b.sum(0)
-        sums[7:16] = (a[:, :, None] * b[:, None, :]).sum(0).reshape(9)
-        sums[16] = (d * d).sum()
-    return sums
+    return reg._host_point_sums(moved[inl].astype(np.float64), q[inl].astype(np.float64), np.sqrt(d2[inl]).astype(np.float64))
 
 
 def ransac_registration_host(source, target, correspondences, *, max_correspondence_distance=0.8, hypotheses=4096, seed=0,
@@ -582,23 +513,9 @@ def ransac_registration_host(source, target, correspondences, *, max_corresponde
             status[i] = NO_HYPOTHESIS
             continue
         chosen[i], chosen_count[i] = best, counts[best]
-        pose[i] = cand[best].astype(np.float64).reshape(3, 4)
-        for k in range(iters + 1):
-            sums = _host_polish_sums(p, q, pose[i], d2_max)
-            fitness[i], rmse[i], few = reg._host_figures(sums, p.shape[0], min_corr)
-            inliers[i] = int(sums[0])
-            if few:
-                status[i] = TOO_FEW
-                break
-            if k == iters:
-                status[i] = MAX_ITERATIONS
-                break
-            solved = reg._host_kabsch_one(sums)
-            if solved is None:
-                status[i] = DEGENERATE
-                break
-            r, t = solved
-            pose[i] = np.concatenate([r @ pose[i][:, :3], (r @ pose[i][:, 3] + t)[:, None]], 1)
+        pose[i], fitness[i], rmse[i], inliers[i], _, status[i] = reg._host_iterate(
+            lambda m34: _host_polish_sums(p, q, m34, d2_max), p.shape[0], cand[best].astype(np.float64).reshape(3, 4), iters,
+            min_corr, 0.0, 0.0, reg._host_kabsch_one)
     return RansacResult(reg._full(pose), fitness, rmse, inliers, chosen, chosen_count, n_valid, status)
 
 

@@ -78,7 +78,7 @@ def _check_viewpoint(viewpoint, batch: int):
 
 # ------------------------------------------------------------------------------------------------ host route (numpy)
 def _rotate(g, v, p, q):
-    """`_jacobi_rotate` of registration.py on (n, 3, 3) stacks: where gamma == 0 a matrix is left alone"""
+    """`jacobi_rotate` of csrc/jacobi3.h on (n, 3, 3) stacks: where gamma == 0 a matrix is left alone"""
     alpha = g[:, 0, p] * g[:, 0, p] + g[:, 1, p] * g[:, 1, p] + g[:, 2, p] * g[:, 2, p]
     beta = g[:, 0, q] * g[:, 0, q] + g[:, 1, q] * g[:, 1, q] + g[:, 2, q] * g[:, 2, q]
     gamma = g[:, 0, p] * g[:, 0, q] + g[:, 1, p] * g[:, 1, q] + g[:, 2, p] * g[:, 2, q]

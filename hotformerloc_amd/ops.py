@@ -1937,6 +1937,14 @@ def _icp_state_check(what: str, state: torch.Tensor, istate: torch.Tensor, pairs
         raise TypeError('%s: contiguous (%d, 2) int32 iterations / status expected' % (what, pairs))
 
 
+def _partials_check(what: str, partials: torch.Tensor, rows: int, n_sums: int):
+    """the per-workgroup sums an evaluation writes and `icp_solve` reads: at least `rows` rows of `n_sums`"""
+    _dev(partials)
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < rows or \
+            partials.shape[1] != n_sums or not partials.is_contiguous():
+        raise TypeError('%s: contiguous (>= %d, %d) float64 partials expected' % (what, rows, n_sums))
+
+
 def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
                    tiles: torch.Tensor, state: torch.Tensor, istate: torch.Tensor, max_dist: float, partials=None,
                    want_rows: bool = False, target_normals: torch.Tensor = None):
@@ -1960,10 +1968,7 @@ def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch
     n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
     if partials is None:
         partials = torch.empty((max(n_tiles, 1), n_sums), dtype=torch.float64, device=source.device)
-    _dev(partials)
-    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
-            partials.shape[1] != n_sums or not partials.is_contiguous():
-        raise TypeError('%s: contiguous (>= %d, %d) float64 partials expected' % (what, n_tiles, n_sums))
+    _partials_check(what, partials, n_tiles, n_sums)
     dist = torch.empty(n_s, dtype=torch.float32, device=source.device) if want_rows else None
     idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
     if n_tiles:
@@ -1992,9 +1997,7 @@ def icp_solve(state: torch.Tensor, istate: torch.Tensor, partials: torch.Tensor,
     _dev(partials, tile_offsets, s_offsets)
     if tile_offsets.shape[0] != pairs + 1:
         raise TypeError('icp_solve: (%d,) tile offsets expected' % (pairs + 1))
-    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < max(int(n_tiles), 1) or \
-            partials.shape[1] != n_sums or not partials.is_contiguous():
-        raise TypeError('icp_solve: contiguous (>= %d, %d) float64 partials expected' % (max(int(n_tiles), 1), n_sums))
+    _partials_check('icp_solve', partials, max(int(n_tiles), 1), n_sums)
     sums = torch.zeros((pairs, n_sums), dtype=torch.float64, device=state.device) if want_sums else None
     check(getattr(_native.load(), name)(state.data_ptr(), istate.data_ptr(), sums.data_ptr() if want_sums else None,
                                         partials.data_ptr(), tile_offsets.data_ptr(), int(n_tiles), s_offsets.data_ptr(), pairs,
@@ -2104,10 +2107,7 @@ def ransac_sums(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor
     n_tiles = int(tiles.shape[0])
     if partials is None:
         partials = torch.empty((max(n_tiles, 1), ICP_SUMS), dtype=torch.float64, device=corr.device)
-    _dev(partials)
-    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[0] < n_tiles or \
-            partials.shape[1] != ICP_SUMS or not partials.is_contiguous():
-        raise TypeError('ransac_sums: contiguous (>= %d, %d) float64 partials expected' % (n_tiles, ICP_SUMS))
+    _partials_check('ransac_sums', partials, n_tiles, ICP_SUMS)
     if n_tiles:
         check(_native.load().hfl_ransac_sums(partials.data_ptr(), corr.data_ptr(), c_offsets.data_ptr(), int(corr.shape[0]),
                                              tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(), pairs,

@@ -135,7 +135,7 @@ def _ragged(batch, what, device_route):
     points = _float32_points(torch.as_tensor(points), what)
     if device_route and not points.is_cuda:
         raise _native.NativeLibraryError('%s runs on the GPU and takes GPU tensors (%s_host is the CPU route)' % (what, what))
-    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    off = _as_numpy(offsets)
     if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
         raise ValueError('%s: (P + 1,) integer offsets with P >= 1 expected' % what)
     off = off.astype(np.int64)
@@ -153,7 +153,7 @@ def _unragged(points, off, was_list):
 
 def _matrices(transforms, pairs, what):
     """(P, 3, 4) float64 numpy from (P, 4, 4) or (P, 3, 4) (a single matrix serves a single pair)"""
-    m = transforms.detach().cpu().numpy() if isinstance(transforms, torch.Tensor) else np.asarray(transforms)
+    m = _as_numpy(transforms)
     m = np.asarray(m, dtype=np.float64)
     if m.ndim == 2:
         m = m[None]
@@ -264,7 +264,7 @@ def overlap_ratio(a, b, transforms=None, tau=DEFAULT_TAU):
 
 
 def _poses(poses, pairs, what):
-    p = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
+    p = _as_numpy(poses)
     p = np.asarray(p, dtype=np.float64)
     if p.shape == (pairs, 7):
         return pose_matrix(p)
@@ -296,6 +296,11 @@ def submap_overlap(ground, aerial, ground_poses, aerial_poses, tau=DEFAULT_TAU):
 
 
 # -------------------------------------------------------------------------------------------------------------- host route
+def _as_numpy(x):
+    """a tensor (wherever it lies) or anything array-like as a numpy array"""
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
 def _host_ragged(batch, what):
     if isinstance(batch, list):
         batch = [torch.as_tensor(c).cpu() for c in batch]

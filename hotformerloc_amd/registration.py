@@ -74,7 +74,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .overlap import _fmaf, _host_argmin32, _host_ragged, _matrices, _ragged, _same_pairs
+from .overlap import _as_numpy, _fmaf, _host_argmin32, _host_ragged, _matrices, _ragged, _same_pairs
 
 RUNNING, CONVERGED, MAX_ITERATIONS, TOO_FEW, DEGENERATE = range(5)     # HFL_ICP_*: a pair's status
 N_SUMS = 17                            # n, Sp (3), Sq (3), Spq (9, row-major: p' down, q across), sum d^2
@@ -98,12 +98,14 @@ def _init_matrices(init, pairs, what):
     return _matrices(init, pairs, what)
 
 
-def _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse, min_correspondences, what):
+def _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse, min_correspondences, what,
+             iterations_name='max_iterations'):
+    """the options of the ICP, and of the RANSAC polish, which calls its iteration count `refine_iterations`"""
     d = float(max_correspondence_distance)
     if not d >= 0.0:
         raise ValueError('%s: max_correspondence_distance must be a number >= 0' % what)
     if int(max_iterations) != max_iterations or max_iterations < 0:
-        raise ValueError('%s: max_iterations must be an integer >= 0' % what)
+        raise ValueError('%s: %s must be an integer >= 0' % (what, iterations_name))
     if int(min_correspondences) != min_correspondences or min_correspondences < 0:
         raise ValueError('%s: min_correspondences must be an integer >= 0' % what)
     return d, int(max_iterations), float(relative_fitness), float(relative_rmse), int(min_correspondences)
@@ -140,6 +142,37 @@ def _full(m34):
 
 
 # -------------------------------------------------------------------------------------------------------------- device route
+def _device_state(m34, device):
+    """(state (P, 16) float64, istate (P, 2) int32) on the device: the (P, 3, 4) poses, every pair RUNNING at iteration 0"""
+    pairs = m34.shape[0]
+    st = np.zeros((pairs, 16), np.float64)
+    st[:, :12] = m34.reshape(pairs, 12)
+    return torch.from_numpy(st).to(device), torch.zeros((pairs, 2), dtype=torch.int32, device=device)
+
+
+def _iterate_on_device(state, istate, iters, evaluate, solve, count=False):
+    """The loop of the estimator, enqueued without a host read: for k = 0 .. iters, `evaluate(state, istate)` reduces the
+    correspondences of every RUNNING pair to partials and `solve(state, istate, is_last)` decides and updates -> what the
+    last `evaluate` and the last `solve` returned and, with `count` (`solve` must then return the pairs' sums), the (P,)
+    float64 n of the evaluation each pair stopped at, else None.  ICP and the RANSAC polish differ in the two callables."""
+    n = torch.zeros(state.shape[0], dtype=torch.float64, device=state.device) if count else None
+    found = sums = None
+    for k in range(iters + 1):
+        running = istate[:, 1] == RUNNING if count else None
+        found = evaluate(state, istate)
+        sums = solve(state, istate, k == iters)
+        if count:
+            n = torch.where(running, sums[:, 0], n)
+    return found, sums, n
+
+
+def _read_state(state, istate):
+    """the one read at the end: `(transforms (P, 4, 4), fitness, rmse, iterations, status)`, numpy"""
+    state, istate = state.cpu().numpy(), istate.cpu().numpy().astype(np.int64)
+    return (_full(state[:, :12].reshape(-1, 3, 4)), state[:, 12].copy(), state[:, 13].copy(), istate[:, 0].copy(),
+            istate[:, 1].copy())
+
+
 class _Batch:
     """A batch of pairs on the device with everything an iteration needs: both clouds, their offsets, the tile table of the
     source clouds and its per-pair offsets, the partials."""
@@ -163,10 +196,7 @@ class _Batch:
                                         dtype=torch.float64, device=dev)
 
     def state(self, m34):
-        """(state, istate) on the device: the given poses, every pair RUNNING at iteration 0"""
-        st = np.zeros((self.pairs, 16), np.float64)
-        st[:, :12] = m34.reshape(self.pairs, 12)
-        return torch.from_numpy(st).to(self.s.device), torch.zeros((self.pairs, 2), dtype=torch.int32, device=self.s.device)
+        return _device_state(m34, self.s.device)
 
     def correspond(self, state, istate, max_dist, want_rows=False):
         from . import ops
@@ -193,12 +223,9 @@ def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_i
     b = _Batch(source, target, what, target_normals)
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_init_matrices(init, b.pairs, what))
-        for k in range(iters + 1):
-            b.correspond(state, istate, dist)
-            b.solve(state, istate, min_corr, rel_f, rel_r, k == iters)
-        state, istate = state.cpu().numpy(), istate.cpu().numpy().astype(np.int64)
-    return RegistrationResult(_full(state[:, :12].reshape(-1, 3, 4)), state[:, 12].copy(), state[:, 13].copy(),
-                              istate[:, 0].copy(), istate[:, 1].copy())
+        _iterate_on_device(state, istate, iters, lambda st, ist: b.correspond(st, ist, dist),
+                           lambda st, ist, is_last: b.solve(st, ist, min_corr, rel_f, rel_r, is_last))
+        return RegistrationResult(*_read_state(state, istate))
 
 
 def _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences, what, want_rows,
@@ -207,8 +234,9 @@ def _evaluate(source, target, transforms, max_correspondence_distance, min_corre
     b = _Batch(source, target, what, target_normals)
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_matrices(transforms, b.pairs, what))
-        _, d, j = b.correspond(state, istate, dist, want_rows=want_rows)
-        sums = b.solve(state, istate, min_corr, 0.0, 0.0, True, want_sums=True)
+        (_, d, j), sums, _ = _iterate_on_device(
+            state, istate, 0, lambda st, ist: b.correspond(st, ist, dist, want_rows=want_rows),
+            lambda st, ist, is_last: b.solve(st, ist, min_corr, 0.0, 0.0, is_last, want_sums=True))
     return d, j, sums, state, dist
 
 
@@ -247,10 +275,7 @@ def _update_on_device(sums, min_correspondences, n_sums, what, plane):
         raise TypeError('%s: (P >= 1, %d) float64 sums expected, got %s %s' % (what, n_sums, sums.dtype, tuple(sums.shape)))
     pairs = int(sums.shape[0])
     with torch.cuda.device(sums.device):
-        st = np.zeros((pairs, 16), np.float64)
-        st[:, :12] = np.eye(4)[:3].reshape(12)                         # (R | t) . identity = (R | t), exactly
-        state = torch.from_numpy(st).to(sums.device)
-        istate = torch.zeros((pairs, 2), dtype=torch.int32, device=sums.device)
+        state, istate = _device_state(_init_matrices(None, pairs, what), sums.device)   # (R | t) . I = (R | t), exactly
         one_each = torch.arange(pairs + 1, dtype=torch.int64, device=sums.device)       # one tile, one source point per pair
         ops.icp_solve(state, istate, sums.contiguous(), one_each, pairs, one_each, int(min_correspondences), 0.0, 0.0, False,
                       plane=plane)
@@ -300,70 +325,86 @@ def _host_plane_sums(p, q, n, d):
     return sums
 
 
+def _host_point_sums(p, q, d):
+    """the 17 sums of given inlier rows, float64 (n, 3) each and the distances (n,); zeros where there is no row"""
+    sums = np.zeros(N_SUMS, np.float64)
+    sums[0] = p.shape[0]
+    sums[1:4], sums[4:7] = p.sum(0), q.sum(0)
+    sums[7:16] = (p[:, :, None] * q[:, None, :]).sum(0).reshape(9)
+    sums[16] = (d * d).sum()
+    return sums
+
+
 def _host_evaluate_one(src, dst, m34, max_dist32, normals=None):
     """one pair, one evaluation: (dist float32, idx int32, inlier bool, sums (17,) float64, or (29,) with the target's
     normals)"""
     moved = _host_move(src, m34)
     dist, idx = _host_nn32(moved, dst)
     inl = (idx >= 0) & (dist <= max_dist32)
+    p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
     if normals is not None:
-        p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
         return dist, idx, inl, _host_plane_sums(p, q, normals[idx[inl]].astype(np.float64).reshape(-1, 3), d)
-    sums = np.zeros(N_SUMS, np.float64)
-    if inl.any():
-        p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
-        sums[0] = p.shape[0]
-        sums[1:4], sums[4:7] = p.sum(0), q.sum(0)
-        sums[7:16] = (p[:, :, None] * q[:, None, :]).sum(0).reshape(9)
-        sums[16] = (d * d).sum()
-    return dist, idx, inl, sums
+    return dist, idx, inl, _host_point_sums(p, q, d)
 
 
-def _jacobi_rotate(g, v, p, q):
+def _rotate_many(g, v, p, q):
+    """`jacobi_rotate<p, q>` of csrc/jacobi3.h on every row at once; a row whose columns are orthogonal already is left"""
     alpha = g[0][p] * g[0][p] + g[1][p] * g[1][p] + g[2][p] * g[2][p]
     beta = g[0][q] * g[0][q] + g[1][q] * g[1][q] + g[2][q] * g[2][q]
     gamma = g[0][p] * g[0][q] + g[1][p] * g[1][q] + g[2][p] * g[2][q]
-    if gamma == 0.0:
-        return
+    skip = gamma == 0.0
     zeta = (beta - alpha) / (2.0 * gamma)
-    t = (1.0 if zeta >= 0.0 else -1.0) / (abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+    t = np.where(zeta >= 0.0, 1.0, -1.0) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
     c = 1.0 / np.sqrt(1.0 + t * t)
     s = c * t
     for i in range(3):
         gp, gq, vp, vq = g[i][p], g[i][q], v[i][p], v[i][q]
-        g[i][p], g[i][q] = c * gp - s * gq, s * gp + c * gq
-        v[i][p], v[i][q] = c * vp - s * vq, s * vp + c * vq
+        g[i][p], g[i][q] = np.where(skip, gp, c * gp - s * gq), np.where(skip, gq, s * gp + c * gq)
+        v[i][p], v[i][q] = np.where(skip, vp, c * vp - s * vq), np.where(skip, vq, s * vp + c * vq)
+
+
+def _pick(cols, j):
+    """cols[j[n]][n]: the run-time pick of a column"""
+    return np.where(j == 0, cols[0], np.where(j == 1, cols[1], cols[2]))
 
 
 def _cross(a, b):
     return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
 
 
-def _host_kabsch_one(s):
-    """(R (3, 3), t (3,)) of one pair's sums, or None where H has rank < 2: `kabsch_solve` of csrc/kabsch.h, line by
-    line, on numpy float64 scalars"""
+def _host_kabsch_many(sums):
+    """(R (n, 3, 3), t (n, 3), solved (n,) bool) of (n, 17) sums; solved is False where H has rank < 2, and R and t mean
+    nothing there.  `kabsch_solve` of csrc/kabsch.h, line by line, every float64 operation on all rows at once: the one
+    transcription, for the ICP, the RANSAC polish and the hypotheses alike"""
+    n_rows = sums.shape[0]
     with np.errstate(all='ignore'):
-        s = [np.float64(x) for x in s]
+        s = [sums[:, k].astype(np.float64) for k in range(N_SUMS)]
         n = s[0]
         g = [[s[7 + 3 * a + b] - s[1 + a] * s[4 + b] / n for b in range(3)] for a in range(3)]
-        v = [[np.float64(a == b) for b in range(3)] for a in range(3)]
+        v = [[np.full(n_rows, np.float64(a == b)) for b in range(3)] for a in range(3)]
         for _ in range(JACOBI_SWEEPS):
-            _jacobi_rotate(g, v, 0, 1)
-            _jacobi_rotate(g, v, 0, 2)
-            _jacobi_rotate(g, v, 1, 2)
+            _rotate_many(g, v, 0, 1)
+            _rotate_many(g, v, 0, 2)
+            _rotate_many(g, v, 1, 2)
         w = [np.sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]) for j in range(3)]
-        i1 = 0 if (w[0] >= w[1] and w[0] >= w[2]) else (1 if w[1] >= w[2] else 2)
-        ja, jb = (1 if i1 == 0 else 0), (1 if i1 == 2 else 2)
-        i2 = ja if w[ja] >= w[jb] else jb
-        if not w[i2] > RANK_TOL * w[i1]:
-            return None
-        u1, u2 = [g[i][i1] / w[i1] for i in range(3)], [g[i][i2] / w[i2] for i in range(3)]
-        v1, v2 = [v[i][i1] for i in range(3)], [v[i][i2] for i in range(3)]
+        i1 = np.where((w[0] >= w[1]) & (w[0] >= w[2]), 0, np.where(w[1] >= w[2], 1, 2))
+        ja, jb = np.where(i1 == 0, 1, 0), np.where(i1 == 2, 1, 2)
+        i2 = np.where(_pick(w, ja) >= _pick(w, jb), ja, jb)
+        w1, w2 = _pick(w, i1), _pick(w, i2)
+        solved = w2 > RANK_TOL * w1
+        u1, u2 = [_pick(g[i], i1) / w1 for i in range(3)], [_pick(g[i], i2) / w2 for i in range(3)]
+        v1, v2 = [_pick(v[i], i1) for i in range(3)], [_pick(v[i], i2) for i in range(3)]
         u3, v3 = _cross(u1, u2), _cross(v1, v2)
         mp, mq = [s[1 + a] / n for a in range(3)], [s[4 + a] / n for a in range(3)]
-        r = np.array([[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)], np.float64)
-        t = np.array([mq[a] - (r[a, 0] * mp[0] + r[a, 1] * mp[1] + r[a, 2] * mp[2]) for a in range(3)], np.float64)
-    return r, t
+        r = [[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)]
+        t = [mq[a] - (r[a][0] * mp[0] + r[a][1] * mp[1] + r[a][2] * mp[2]) for a in range(3)]
+    return (np.stack([np.stack(row, 1) for row in r], 1).reshape(n_rows, 3, 3), np.stack(t, 1).reshape(n_rows, 3), solved)
+
+
+def _host_kabsch_one(s):
+    """(R (3, 3), t (3,)) of one pair's sums, or None where H has rank < 2: `_host_kabsch_many` on one row"""
+    r, t, solved = _host_kabsch_many(np.asarray(s, np.float64).reshape(1, N_SUMS))
+    return (r[0], t[0]) if solved[0] else None
 
 
 def kabsch_update_host(sums, min_correspondences=3):
@@ -372,7 +413,7 @@ def kabsch_update_host(sums, min_correspondences=3):
 
 
 def _update_on_host(sums, min_correspondences, n_sums, what, solve_one):
-    sums = np.asarray(sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
+    sums = np.asarray(_as_numpy(sums), dtype=np.float64)
     if sums.ndim != 2 or sums.shape[1] != n_sums or sums.shape[0] < 1:
         raise TypeError('%s: (P >= 1, %d) float64 sums expected, got shape %s' % (what, n_sums, sums.shape))
     pairs = sums.shape[0]
@@ -459,6 +500,31 @@ def _host_figures(sums, n_source, min_corr):
     return float(fitness), float(rmse), bool(few)
 
 
+def _host_iterate(evaluate, n_rows, pose0, iters, min_corr, rel_f, rel_r, solve_one):
+    """Evaluate, decide, update on one pair, as the module's docstring defines them -> `(pose (3, 4), fitness, rmse, n, k,
+    status)`, the figures and the inlier count n of the evaluation the pair stopped at.  `evaluate(pose)` gives the sums of
+    the inliers under a (3, 4) float64 pose, `n_rows` is the denominator of the fitness, `solve_one(sums)` the update or
+    None.  The RANSAC polish runs it with both relative thresholds 0: abs(x) < 0 never holds, so it cannot end CONVERGED."""
+    pose, prev = pose0, None
+    for k in range(iters + 1):
+        sums = evaluate(pose)
+        fitness, rmse, few = _host_figures(sums, n_rows, min_corr)
+        if few:
+            status = TOO_FEW
+        elif k >= 1 and abs(fitness - prev[0]) < rel_f and abs(rmse - prev[1]) < rel_r:
+            status = CONVERGED
+        elif k == iters:
+            status = MAX_ITERATIONS
+        else:
+            solved = solve_one(sums)
+            status = DEGENERATE if solved is None else RUNNING
+        if status != RUNNING:
+            return pose, fitness, rmse, int(sums[0]), k, status
+        r, t = solved
+        pose = np.concatenate([r @ pose[:, :3], (r @ pose[:, 3] + t)[:, None]], 1)    # (R | t) . T_k, the row 0 0 0 1 implied
+        prev = (fitness, rmse)
+
+
 def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
                     relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None):
     """`icp_refine` on the CPU: the module's definition in numpy, pair by pair -> `RegistrationResult`."""
@@ -471,28 +537,9 @@ def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, 
     fitness, rmse = np.zeros(len(batch), np.float64), np.zeros(len(batch), np.float64)
     iterations, status = np.zeros(len(batch), np.int64), np.zeros(len(batch), np.int64)
     for p, (src, dst, *nrm) in enumerate(batch):
-        prev = None
-        for k in range(iters + 1):
-            sums = _host_evaluate_one(src, dst, pose[p], np.float32(dist), *nrm)[3]
-            fitness[p], rmse[p], few = _host_figures(sums, src.shape[0], min_corr)
-            iterations[p] = k
-            if few:
-                status[p] = TOO_FEW
-                break
-            if k >= 1 and abs(fitness[p] - prev[0]) < rel_f and abs(rmse[p] - prev[1]) < rel_r:
-                status[p] = CONVERGED
-                break
-            if k == iters:
-                status[p] = MAX_ITERATIONS
-                break
-            solved = solve_one(sums)
-            if solved is None:
-                status[p] = DEGENERATE
-                break
-            r, t = solved
-            step = np.concatenate([r, t[:, None]], 1)                  # (R | t) . T_k, the bottom row 0 0 0 1 implied
-            pose[p] = np.concatenate([step[:, :3] @ pose[p][:, :3], (step[:, :3] @ pose[p][:, 3] + step[:, 3])[:, None]], 1)
-            prev = (fitness[p], rmse[p])
+        pose[p], fitness[p], rmse[p], _, iterations[p], status[p] = _host_iterate(
+            lambda m34: _host_evaluate_one(src, dst, m34, np.float32(dist), *nrm)[3], src.shape[0], pose[p], iters, min_corr,
+            rel_f, rel_r, solve_one)
     return RegistrationResult(_full(pose), fitness, rmse, iterations, status)
 
 

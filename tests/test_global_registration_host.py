@@ -49,6 +49,11 @@ def test_shared_headers_hold_the_one_copy():
     text = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith(('.hip', '.h'))}
     assert [f for f, t in text.items() if re.search(r'\bU4 philox4x32_10\(', t)] == ['philox.h']
     assert [f for f, t in text.items() if re.search(r'\bbool kabsch_solve\(', t)] == ['kabsch.h']
+    assert [f for f, t in text.items() if re.search(r'\bvoid icp_point_row\(', t)] == ['icp_sums.h']
+    assert [f for f, t in text.items() if re.search(r'\bvoid icp_reduce_partials\(', t)] == ['icp_sums.h']
+    # and nobody writes the row step or the reduction out beside them
+    assert [f for f, t in text.items() if re.search(r'acc\[7 \+ 3 \* a \+ b\] \+=', t)] == ['icp_sums.h']
+    assert [f for f, t in text.items() if re.search(r'red\[\w+ \* \w+ \+ threadIdx\.x\]', t)] == ['icp_sums.h']
 
 
 def test_ransac_tiles():
@@ -140,6 +145,12 @@ def test_d2_threshold_against_a_sweep_of_neighbouring_floats():
 
 
 def test_kabsch_of_many_has_the_bits_of_kabsch_of_one():
+    """The array solver, and `_host_kabsch_one` row by row, against the scalar transcription of csrc/kabsch.h that stood in
+    `registration.py` until the array form became the only one.  `tests/golden/kabsch_scalar.npz` holds what that scalar
+    `_host_kabsch_one` (numpy float64 scalars, one Python statement per line of `kabsch_solve`) returned on the 60 rows
+    built below, recorded on the last commit that had it: `solved` (60,) bool, `r` (60, 3, 3) and `t` (60, 3) float64,
+    zeros where a row is not solved."""
+    golden = np.load(os.path.join(ROOT, 'tests', 'golden', 'kabsch_scalar.npz'))
     rng = np.random.default_rng(5)
     sums = []
     for kind in range(60):
@@ -153,13 +164,15 @@ def test_kabsch_of_many_has_the_bits_of_kabsch_of_one():
             p[:, 2] = q[:, 2] = 0.0                                    # exact zeros: rotations that are skipped
         sums.append(GR._host_triple_sums([p[k:k + 1] for k in range(3)], [q[k:k + 1] for k in range(3)])[0])
     sums = np.stack(sums)
-    r, t, solved = GR._host_kabsch_many(sums)
+    r, t, solved = reg._host_kabsch_many(sums)
     assert solved.any() and not solved.all()
+    assert golden['solved'].shape == (60,) and np.array_equal(solved, golden['solved'])
     for i in range(sums.shape[0]):
         one = reg._host_kabsch_one(sums[i])
-        assert (one is not None) == bool(solved[i])
+        assert (one is not None) == bool(golden['solved'][i])
         if one is not None:
-            assert np.array_equal(one[0], r[i]) and np.array_equal(one[1], t[i])
+            assert np.array_equal(golden['r'][i], r[i]) and np.array_equal(golden['t'][i], t[i])
+            assert np.array_equal(golden['r'][i], one[0]) and np.array_equal(golden['t'][i], one[1])
 
 
 def test_fewer_than_three_correspondences():

@@ -117,6 +117,17 @@ def test_score_exact_case_matches_hand_counts():
         assert np.array_equal(got.cpu().numpy()[0], counts[name]), name
 
 
+def assert_result_of_the_host(res, host):
+    """the rule of the module docstring for a whole call"""
+    for name in ('hypothesis', 'hypothesis_inliers', 'inliers', 'status', 'valid_hypotheses'):
+        assert getattr(res, name).dtype == np.int64
+        assert np.array_equal(getattr(res, name), getattr(host, name)), name
+    assert np.abs(res.transforms - host.transforms).max() <= 1e-9
+    assert np.array_equal(res.fitness, host.fitness, equal_nan=True)
+    assert np.array_equal(np.isnan(res.inlier_rmse), np.isnan(host.inlier_rmse))
+    assert np.nanmax(np.abs(res.inlier_rmse - host.inlier_rmse), initial=0.0) <= 1e-6
+
+
 def compare_whole_call(batch, n_hyp, **kw):
     on = on_device(batch)
     poses, valid, _ = hfl.ransac_hypotheses(*on, hypotheses=n_hyp)
@@ -126,13 +137,7 @@ def compare_whole_call(batch, n_hyp, **kw):
         assert np.array_equal(a, b, equal_nan=True)                    # drawn or handed in: the same candidates, the same bits
     guarded_counts(batch, poses.cpu().numpy(), valid.cpu().numpy(), gc.TAU)
     host = hfl.ransac_registration_host(*batch, poses=poses.cpu().numpy(), max_correspondence_distance=gc.TAU, **kw)
-    for name in ('hypothesis', 'hypothesis_inliers', 'inliers', 'status', 'valid_hypotheses'):
-        assert getattr(res, name).dtype == np.int64
-        assert np.array_equal(getattr(res, name), getattr(host, name)), name
-    assert np.abs(res.transforms - host.transforms).max() <= 1e-9
-    assert np.array_equal(res.fitness, host.fitness, equal_nan=True)
-    assert np.array_equal(np.isnan(res.inlier_rmse), np.isnan(host.inlier_rmse))
-    assert np.nanmax(np.abs(res.inlier_rmse - host.inlier_rmse), initial=0.0) <= 1e-6
+    assert_result_of_the_host(res, host)
     counts = hfl.score_hypotheses(*on, poses, gc.TAU, valid).cpu().numpy()
     best = counts.argmax(1)                                            # the first of equal maxima: the lowest h
     assert np.array_equal(res.hypothesis, np.where(counts.max(1) >= 0, best, -1))
@@ -152,6 +157,33 @@ def test_whole_call_too_few_and_no_refinement():
     batch = batch_of((3, 40), frac=0.0)
     res = compare_whole_call(batch, 64, min_correspondences=4, refine_iterations=0)
     assert res.status.tolist() == [reg.TOO_FEW, reg.MAX_ITERATIONS]
+
+
+def polish_case(n_corr):
+    """(batch, poses (1, 2, 3, 4), options, the host's result): one pair of `n_corr` correspondences, 30 % of them wrong,
+    polished once from the truth rounded to fp32; the second candidate is a pose of NaNs.  min_correspondences = 0, so that
+    the sums are taken and solved at any size.  The d2 guard is asserted on the handed-in pose."""
+    batch = batch_of((n_corr,), frac=0.3)
+    poses = np.full((1, 2, 3, 4), np.nan, np.float32)
+    poses[0, 0] = gc.truth().astype(np.float32)
+    kw = dict(max_correspondence_distance=gc.TAU, refine_iterations=1, min_correspondences=0)
+    gc.guard_d2(*gc.gathered(batch[0][0], batch[1][0], batch[2][0]), poses[0].reshape(-1, 12), gc.TAU)
+    return batch, poses, kw, hfl.ransac_registration_host(*batch, poses=poses, **kw)
+
+
+@pytest.mark.parametrize('n_corr', C_SIZES)
+def test_polish_correspondence_sizes(n_corr):
+    """`hfl_ransac_sums` round its tile: one correspondence, a partial last tile, a whole one, one row more, three
+    workgroups.  A single correspondence has H = 0: the host ends DEGENERATE after one evaluation with one inlier, and
+    the device must end as the host does."""
+    batch, poses, kw, host = polish_case(n_corr)
+    on = on_device(batch)
+    res = hfl.ransac_registration(*on, poses=dev(poses), **kw)
+    again = hfl.ransac_registration(*on, poses=dev(poses), **kw)
+    for a, b in zip(res, again):
+        assert np.array_equal(a, b, equal_nan=True)                    # two runs, the same bits
+    assert res.hypothesis.tolist() == [0] and res.valid_hypotheses.tolist() == [1]
+    assert_result_of_the_host(res, host)
 
 
 def test_purpose_sixty_percent_wrong_correspondences():
