@@ -15,6 +15,10 @@ robust estimator needs; `ransac_registration` is that estimator (a deterministic
 `ransac_hypotheses`, `score_hypotheses`, select, a short polish) and hands `icp_refine(init=...)` its starting pose;
 `global_registration` chains all of it from two raw clouds to a refined 6-DoF pose in one call.  The `*_host` twins define
 every step.
+
+Back to the ranking: `spectral_consistency` scores how many of a pair's correspondences agree with one rigid motion (the
+leading eigenvalue of their length-consistency matrix, no pose estimated), `prune_correspondences` keeps the ones its
+eigenvector trusts, and `rerank_candidates` re-orders the (Q, k) result of `FlatL2Index.search` by that score.
 """
 
 import os as _os
@@ -53,5 +57,7 @@ from .fpfh import (compute_fpfh, compute_fpfh_host, feature_correspondences,    
 from .global_registration import (correspondence_pairs, correspondence_pairs_host, ransac_hypotheses,   # noqa: F401,E402
                                   ransac_hypotheses_host, score_hypotheses, score_hypotheses_host, ransac_registration,
                                   ransac_registration_host, global_registration, global_registration_host, RansacResult)
+from .spectral import (spectral_consistency, spectral_consistency_host, prune_correspondences,          # noqa: F401,E402
+                       prune_correspondences_host, rerank_candidates, rerank_candidates_host, SpectralResult, RerankResult)
 
 __version__ = '0.1.0'

@@ -177,7 +177,7 @@ def _valid_of(valid, pairs, n_hyp, what):
 # -------------------------------------------------------------------------------------------------------------- device route
 class _Batch:
     """The correspondences of a batch of pairs on the device, gathered once: (C, 6) fp32 point pairs, their offsets, the
-    tile table and its per-pair offsets."""
+    tile table and its per-pair offsets; `n_source`: every pair's number of source points (numpy), for `spectral.py`."""
 
     def __init__(self, source, target, correspondences, what):
         from . import ops
@@ -185,6 +185,7 @@ class _Batch:
         t, t_off, _ = _ragged(target, what, True)
         _same_pairs(s_off, t_off, what)
         self.pairs = s_off.shape[0] - 1
+        self.n_source = np.diff(s_off)
         self.device = dev = s.device
         if t.device != dev:
             raise ValueError('%s: source and target lie on different devices' % what)
@@ -361,13 +362,14 @@ def _global(source, target, normals_of, fpfh_of, match, pairs_of, ransac, icp, d
 
 # ---------------------------------------------------------------------------------------------------------------- host route
 class _HostBatch:
-    """the (p, q) float32 point pairs of every pair, gathered once"""
+    """the (p, q) float32 point pairs of every pair, gathered once, and every pair's number of source points"""
 
     def __init__(self, source, target, correspondences, what):
         s, s_off, _ = _host_ragged(source, what)
         t, t_off, _ = _host_ragged(target, what)
         _same_pairs(s_off, t_off, what)
         self.pairs = s_off.shape[0] - 1
+        self.n_source = np.diff(s_off)
         parts, self.c_off = _corr_rows(correspondences, self.pairs, what, _as_numpy)
         rows = np.concatenate(parts, 0).astype(np.int64)
         self.p, self.q = [], []

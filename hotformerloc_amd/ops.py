@@ -2115,7 +2115,82 @@ def ransac_sums(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor
     return partials
 
 
-VOXEL_MAX_CLOUDS = 32767            # HFL_VOXEL_MAX_CLOUDS
+SPECTRAL_ROWS = 512                    # HFL_SPECTRAL_ROWS: rows (correspondences) of a workgroup of hfl_spectral_matvec (two per thread)
+SPECTRAL_TILE = 1024                   # HFL_SPECTRAL_TILE: columns of the LDS tile those rows share
+SPECTRAL_SUMS = 3                      # HFL_SPECTRAL_SUMS: sum v w, sum v^2, sum w^2
+
+
+def spectral_tiles(lengths):
+    """The tile table of `hfl_spectral_matvec` from the pairs' numbers of correspondences on the host: `pair_tiles` with
+    SPECTRAL_ROWS rows of one pair per workgroup -- ((n_tiles, 2) int64 numpy rows of (pair, first row), the (P + 1,) int64
+    offsets of every pair's rows in it)."""
+    return pair_tiles(lengths, SPECTRAL_ROWS)
+
+
+def _spectral_check(what: str, corr: torch.Tensor, c_offsets: torch.Tensor, tile_offsets: torch.Tensor, w, partials,
+                    n_tiles: int) -> int:
+    pairs = _ransac_corr_check(what, corr, c_offsets)
+    _dev(tile_offsets)
+    _offsets_check(what, tile_offsets)
+    if int(tile_offsets.shape[0]) != pairs + 1:
+        raise TypeError('%s: (%d,) tile offsets expected' % (what, pairs + 1))
+    if w is not None:
+        _dev(w)
+        _vector_check(what, w, torch.float32, int(corr.shape[0]), 'products')
+        _partials_check(what, partials, n_tiles, SPECTRAL_SUMS)
+    return pairs
+
+
+def spectral_matvec(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor, tile_offsets: torch.Tensor,
+                    inv_sigma2: float, w_in=None, partials_in=None, w_out=None, partials_out=None):
+    """`hfl_spectral_matvec`: one step of the power iteration on the length-consistency matrix of every pair's
+    correspondences (corr (C, 6) fp32 under c_offsets, as `ransac_score` takes them; tiles and tile_offsets: the device
+    copies of `spectral_tiles`).  `w_in` (C,) fp32 and `partials_in` (n_tiles, SPECTRAL_SUMS) float64 are the previous step's
+    results, which this step normalises as it loads them; without them it is the first step, v = 1.  -> (w (C,) fp32,
+    partials (n_tiles, SPECTRAL_SUMS) float64), written in place where `w_out` / `partials_out` are given (not the inputs)."""
+    what = 'spectral_matvec'
+    _ransac_tiles_check(what, tiles)
+    n_tiles, n_corr = int(tiles.shape[0]), int(corr.shape[0]) if corr.dim() else 0
+    if (w_in is None) != (partials_in is None):
+        raise TypeError('%s: w_in and partials_in come together' % what)
+    pairs = _spectral_check(what, corr, c_offsets, tile_offsets, w_in, partials_in, n_tiles)
+    if not (float(inv_sigma2) > 0.0 and np.isfinite(np.float32(inv_sigma2))):
+        raise ValueError('%s: a finite inv_sigma2 > 0 expected' % what)
+    if w_out is None:
+        w_out = torch.zeros(n_corr, dtype=torch.float32, device=corr.device)
+    if partials_out is None:
+        partials_out = torch.zeros((max(n_tiles, 1), SPECTRAL_SUMS), dtype=torch.float64, device=corr.device)
+    _spectral_check(what, corr, c_offsets, tile_offsets, w_out, partials_out, n_tiles)
+    if w_in is not None and n_tiles and (w_in.data_ptr() == w_out.data_ptr() or partials_in.data_ptr() == partials_out.data_ptr()):
+        raise ValueError('%s: a step cannot write where it reads' % what)
+    if n_tiles:
+        check(_native.load().hfl_spectral_matvec(
+            w_out.data_ptr(), partials_out.data_ptr(), corr.data_ptr(), c_offsets.data_ptr(), n_corr, tiles.data_ptr(), n_tiles,
+            tile_offsets.data_ptr(), None if w_in is None else w_in.data_ptr(),
+            None if partials_in is None else partials_in.data_ptr(), pairs, float(inv_sigma2), _stream()), 'hfl_spectral_matvec')
+    return w_out, partials_out
+
+
+def spectral_finish(w: torch.Tensor, partials: torch.Tensor, n_tiles: int, tile_offsets: torch.Tensor, corr: torch.Tensor,
+                    c_offsets: torch.Tensor, n_source: torch.Tensor):
+    """`hfl_spectral_finish` on the last step's (w, partials): -> (eigenvalue (P,) float64, score (P,) float64 = eigenvalue /
+    max(n_source, 1), weights (C,) fp32 = w / fp32(sqrt(sum w^2)) per pair); eigenvalue 0 and weights 0 where sum w^2 is 0.
+    n_source: (P,) int64, every pair's number of source points."""
+    what = 'spectral_finish'
+    pairs = _spectral_check(what, corr, c_offsets, tile_offsets, w, partials, int(n_tiles))
+    _dev(n_source)
+    _vector_check(what, n_source, torch.int64, pairs, 'source sizes')
+    eigenvalue = torch.empty(pairs, dtype=torch.float64, device=corr.device)
+    score = torch.empty(pairs, dtype=torch.float64, device=corr.device)
+    weights = torch.empty(int(corr.shape[0]), dtype=torch.float32, device=corr.device)
+    check(_native.load().hfl_spectral_finish(eigenvalue.data_ptr(), score.data_ptr(), _some(weights).data_ptr(),
+                                             _some(w).data_ptr(), partials.data_ptr(), int(n_tiles), tile_offsets.data_ptr(),
+                                             c_offsets.data_ptr(), int(corr.shape[0]), n_source.data_ptr(), pairs, _stream()),
+          'hfl_spectral_finish')
+    return eigenvalue, score, weights
+
+
+VOXEL_MAX_CLOUDS = 32767           # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS
 

@@ -1315,6 +1315,35 @@ int hfl_ransac_sums(double* partials, const float* corr, const int64_t* c_offset
                     hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11h. Spectral geometric verification: the leading eigenpair of the length-consistency matrix of a pair's point
+ *      correspondences by power iteration, for re-ranking retrieved candidates (csrc/spectral.hip; no counterpart in
+ *      the reference).  Definition: hotformerloc_amd/spectral.py, DESIGN.md section 7p.
+ * ---------------------------------------------------------------------- */
+#define HFL_SPECTRAL_ROWS 512             /* rows (correspondences) of a 256-thread workgroup of hfl_spectral_matvec (two per thread) */
+#define HFL_SPECTRAL_TILE 1024            /* columns of the LDS tile those rows share: seven fp32 planes */
+#define HFL_SPECTRAL_SUMS 3               /* float64 sums of a workgroup: r = sum v w, n = sum v^2, s2 = sum w^2 */
+/* Both take the correspondences as section 11g does: corr (n_corr, 6) fp32 rows with (P + 1) int64 DEVICE offsets, clamped
+ * to the array.  tiles (n_tiles, 2) int64 DEVICE rows of (pair, first row), HFL_SPECTRAL_ROWS rows of one pair per workgroup,
+ * pairs in order; tile_offsets (P + 1) int64 DEVICE: the rows of every pair in that table.  Launches on `stream`, no
+ * synchronisation, no host read, no atomics: two runs give the same bits.  A NULL pointer (but for the first step's two),
+ * a negative count or P < 1: HFL_EINVAL; n_corr, n_tiles or P at 2^31 or more: HFL_ECAPACITY. */
+/* One step of the power iteration.  m_ij = max(0, fmaf(-(e e), inv_sigma2, 1)), e = |p_i - p_j| - |q_i - q_j| with the
+ * lengths of hfl_nn_dist (the fmaf chain of d2, the correctly rounded fp32 root), m_ii = 0.  v_j = w_in[j] / fp32(sqrt(s2))
+ * with s2 the sum of the pair's rows of partials_in in tile order (v_j = 0 where s2 == 0); w_in == partials_in == NULL is the
+ * first step, v = 1.  w_out[i] = the fp32 chain acc = fmaf(m_ij, v_j, acc) from 0 over the pair's j ascending; row t of
+ * partials_out (n_tiles, HFL_SPECTRAL_SUMS) float64 = (sum v_i w_i, sum v_i^2, sum w_i^2) over the rows of tile t, reduced in
+ * the order of hfl_icp_correspond.  The outputs must not be the inputs.  inv_sigma2 finite and > 0, else HFL_EINVAL. */
+int hfl_spectral_matvec(float* w_out, double* partials_out, const float* corr, const int64_t* c_offsets, int64_t n_corr,
+                        const int64_t* tiles, int64_t n_tiles, const int64_t* tile_offsets, const float* w_in,
+                        const double* partials_in, int64_t n_pairs, float inv_sigma2, hfl_stream_t stream);
+/* One wave per pair, after the last step: (r, n, s2) = the pair's rows of `partials` in tile order; eigenvalue[p] = r / n,
+ * score[p] = eigenvalue[p] / max(n_source[p], 1), weights[i] = w[i] / fp32(sqrt(s2)) -- or, where s2 == 0 (fewer than two
+ * correspondences, or no two of them consistent), eigenvalue 0 and weights 0.  n_source (P) int64 DEVICE. */
+int hfl_spectral_finish(double* eigenvalue, double* score, float* weights, const float* w, const double* partials,
+                        int64_t n_tiles, const int64_t* tile_offsets, const int64_t* c_offsets, int64_t n_corr,
+                        const int64_t* n_source, int64_t n_pairs, hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
