@@ -19,6 +19,12 @@ every step.
 Back to the ranking: `spectral_consistency` scores how many of a pair's correspondences agree with one rigid motion (the
 leading eigenvalue of their length-consistency matrix, no pose estimated), `prune_correspondences` keeps the ones its
 eigenvector trusts, and `rerank_candidates` re-orders the (Q, k) result of `FlatL2Index.search` by that score.
+
+Where nearly every correspondence is wrong (95 % and more) drawn triples stop finding a pose: `consensus_registration`
+makes its candidates from the correspondences' second-order compatibility instead (`consensus_hypotheses`: a bit-matrix
+graph, one consensus set and one Kabsch solve per seed, nothing random) and scores, selects and polishes them as
+`ransac_registration` does; `global_registration(estimator='consensus')` and `rerank_candidates(..., estimator='consensus')`
+use it for the coarse pose.
 """
 
 import os as _os
@@ -59,5 +65,7 @@ from .global_registration import (correspondence_pairs, correspondence_pairs_hos
                                   ransac_registration_host, global_registration, global_registration_host, RansacResult)
 from .spectral import (spectral_consistency, spectral_consistency_host, prune_correspondences,          # noqa: F401,E402
                        prune_correspondences_host, rerank_candidates, rerank_candidates_host, SpectralResult, RerankResult)
+from .consensus import (consensus_hypotheses, consensus_hypotheses_host, consensus_registration,        # noqa: F401,E402
+                        consensus_registration_host)
 
 __version__ = '0.1.0'

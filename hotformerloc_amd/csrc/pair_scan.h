@@ -58,6 +58,11 @@ __device__ __forceinline__ void pair_keep_closer(float d2, int32_t j, float& bes
 // correctly rounded under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt, as numpy's float32 sqrt is.
 __device__ __forceinline__ float pair_sqrt(float d2) { return __builtin_sqrtf(d2); }
 
+// The length of a difference: the d2 chain of the scan and the correctly rounded root (csrc/spectral.hip, csrc/consensus.hip)
+__device__ __forceinline__ float pair_len(float dx, float dy, float dz) {
+  return pair_sqrt(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+}
+
 // The scan of (N, 3) points: best[r] and at[r] become the smallest fp32 squared distance from (qx[r], qy[r], qz[r]) to a
 // point of the tile's target cloud and that point's index within the cloud, +inf and -1 for an empty cloud.  The cloud
 // streams through the three LDS planes in tiles of TILE points; every lane reads the same four target points (three

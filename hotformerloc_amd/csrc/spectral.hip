@@ -37,16 +37,11 @@ static_assert(SP_ROWS % SP_THREADS == 0 && SP_RPT >= 1, "whole rows per thread")
 static_assert(SP_TILE % 4 == 0 && SP_ROWS % 4 == 0, "whole groups of four columns");
 static_assert(SP_TILE * SP_PLANES * 4 + SP_WAVES * SP_SUMS * 8 <= 32 * 1024, "static LDS stays at 32 KiB or less");
 
-// the length of a difference: the d2 chain of the pair scan and the correctly rounded root
-__device__ __forceinline__ float spectral_len(float dx, float dy, float dz) {
-  return pair_sqrt(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
-}
-
 // m_ij for i != j: max(0, 1 - (|p_i - p_j| - |q_i - q_j|)^2 / sigma^2), symmetric to the bit
 __device__ __forceinline__ float spectral_entry(const float (&p)[3], const float (&q)[3], float pjx, float pjy, float pjz,
                                                 float qjx, float qjy, float qjz, float inv_s2) {
-  const float a = spectral_len(p[0] - pjx, p[1] - pjy, p[2] - pjz);
-  const float b = spectral_len(q[0] - qjx, q[1] - qjy, q[2] - qjz);
+  const float a = pair_len(p[0] - pjx, p[1] - pjy, p[2] - pjz);
+  const float b = pair_len(q[0] - qjx, q[1] - qjy, q[2] - qjz);
   const float e = a - b;
   return fmaxf(0.f, fmaf(-(e * e), inv_s2, 1.f));
 }

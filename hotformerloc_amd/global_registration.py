@@ -11,7 +11,9 @@ is computed is stated here, and the `*_host` functions are this text in numpy.
     ransac_hypotheses      H candidate poses per pair from drawn triples of correspondences
     score_hypotheses       the inlier count of every candidate
     ransac_registration    draw (or take the caller's candidates), score, select, polish -> `RansacResult`
-    global_registration    two raw clouds -> normals -> FPFH -> correspondences -> RANSAC -> ICP, in one call
+    global_registration    two raw clouds -> normals -> FPFH -> correspondences -> RANSAC -> ICP, in one call; with
+                           `estimator='consensus'` the coarse pose comes from `consensus_registration` (`consensus.py`), which
+                           shares the score -> select -> polish below (`_select_and_polish`)
 
 The package exports the function `global_registration` under the name of this module; the module itself (`inlier_d2`,
 `NO_HYPOTHESIS`) is `importlib.import_module('hotformerloc_amd.global_registration')`.
@@ -76,6 +78,7 @@ from .registration import DEGENERATE, MAX_ITERATIONS, RANK_TOL, RUNNING, TOO_FEW
 from .registration import _host_kabsch_many
 
 NO_HYPOTHESIS = 5                      # HFL_RANSAC_NO_HYPOTHESIS: every hypothesis of the pair was invalid
+ESTIMATORS = ('ransac', 'consensus')   # who makes the candidates of the coarse pose: drawn triples, or `consensus.py`
 _HOST_CHUNK = 1 << 21                  # (hypothesis, correspondence) tests of one temporary of the numpy route
 
 RansacResult = namedtuple('RansacResult', ['transforms', 'fitness', 'inlier_rmse', 'inliers', 'hypothesis',
@@ -257,15 +260,23 @@ def ransac_registration(source, target, correspondences, *, max_correspondence_d
             poses, valid, _ = ops.ransac_hypotheses(b.corr, b.c_dev, n_hyp, seed, rho2)
         else:
             poses, valid = b.device_poses(poses, None, what)
-        counts = ops.ransac_score(b.corr, b.c_dev, b.tiles, poses, valid, d2_max)
-        state, istate, chosen = ops.ransac_select(counts, poses)
-        partials = torch.zeros((max(b.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=b.device)
-        _, _, inliers = reg._iterate_on_device(
-            state, istate, iters, lambda st, ist: ops.ransac_sums(b.corr, b.c_dev, b.tiles, st, ist, d2_max, partials=partials),
-            lambda st, ist, is_last: ops.icp_solve(st, ist, partials, b.tile_off, b.n_tiles, b.c_dev, min_corr, 0.0, 0.0,
-                                                   is_last, want_sums=True), count=True)
-        transforms, fitness, rmse, _, status = reg._read_state(state, istate)
-        chosen, inliers = chosen.cpu().numpy().astype(np.int64), inliers.cpu().numpy().astype(np.int64)
+        return _select_and_polish(b, poses, valid, d2_max, iters, min_corr)
+
+
+def _select_and_polish(b, poses, valid, d2_max, iters, min_corr):
+    """Score, select and polish of the module docstring on the candidates (poses (P, H, 12) fp32, valid (P, H) uint8) of a
+    `_Batch`, whoever made them (`ransac_registration`, `consensus_registration`) -> `RansacResult`.  Enqueued on the current
+    stream of the batch's device, which the caller has made current; the one read comes at the end."""
+    from . import ops
+    counts = ops.ransac_score(b.corr, b.c_dev, b.tiles, poses, valid, d2_max)
+    state, istate, chosen = ops.ransac_select(counts, poses)
+    partials = torch.zeros((max(b.n_tiles, 1), ops.ICP_SUMS), dtype=torch.float64, device=b.device)
+    _, _, inliers = reg._iterate_on_device(
+        state, istate, iters, lambda st, ist: ops.ransac_sums(b.corr, b.c_dev, b.tiles, st, ist, d2_max, partials=partials),
+        lambda st, ist, is_last: ops.icp_solve(st, ist, partials, b.tile_off, b.n_tiles, b.c_dev, min_corr, 0.0, 0.0,
+                                               is_last, want_sums=True), count=True)
+    transforms, fitness, rmse, _, status = reg._read_state(state, istate)
+    chosen, inliers = chosen.cpu().numpy().astype(np.int64), inliers.cpu().numpy().astype(np.int64)
     return RansacResult(transforms, fitness, rmse, inliers, chosen[:, 0].copy(), chosen[:, 1].copy(), chosen[:, 2].copy(),
                         status)
 
@@ -322,24 +333,48 @@ def correspondence_pairs_host(idx, mask=None):
     return _correspondence_pairs(idx, mask, _as_numpy, np, 'correspondence_pairs')
 
 
+def _coarse_estimator(estimator, device_route, what, ransac_distance, refine_iterations, min_correspondences, hypotheses,
+                      seed, edge_length_ratio, consensus_distance, seeds, consensus_size):
+    """The coarse step of `global_registration` and `rerank_candidates(register=True)` as one callable (source, target,
+    correspondences) -> `RansacResult`: 'ransac' is `ransac_registration` with `hypotheses`, `seed` and `edge_length_ratio`,
+    'consensus' is `consensus_registration` with `consensus_distance`, `seeds` and `consensus_size`; both score and polish
+    with `ransac_distance`, `refine_iterations` and `min_correspondences`."""
+    if estimator not in ESTIMATORS:
+        raise ValueError('%s: estimator must be one of %s, got %r' % (what, ', '.join(ESTIMATORS), estimator))
+    kw = dict(max_correspondence_distance=ransac_distance, refine_iterations=refine_iterations,
+              min_correspondences=min_correspondences)
+    if estimator == 'ransac':
+        run = ransac_registration if device_route else ransac_registration_host
+        kw.update(hypotheses=hypotheses, seed=seed, edge_length_ratio=edge_length_ratio)
+    else:
+        from .consensus import consensus_registration, consensus_registration_host
+        run = consensus_registration if device_route else consensus_registration_host
+        kw.update(distance_threshold=consensus_distance, seeds=seeds, consensus_size=consensus_size)
+    return lambda source, target, correspondences: run(source, target, correspondences, **kw)
+
+
 def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                         estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
-                        min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6):
+                        min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                        estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
     """From two lists of raw (N_i, 3) float32 GPU clouds to refined 6-DoF poses, source frame -> target frame, in one call:
     `estimate_normals` -> `compute_fpfh` -> `feature_correspondences` (`mutual`) -> `correspondence_pairs` ->
     `ransac_registration` (`ransac_distance` and its options) -> `icp_refine(init=...)` (`icp_distance`, `estimation`, its
     options; point-to-plane uses the target normals already estimated).  -> `(RansacResult, RegistrationResult)`.  A pair
-    that ends NO_HYPOTHESIS enters the ICP at the identity."""
+    that ends NO_HYPOTHESIS enters the ICP at the identity.  `estimator='consensus'` takes the coarse pose from
+    `consensus_registration` (`consensus_distance`, `seeds`, `consensus_size`; `ransac_distance`, `refine_iterations` and
+    `min_correspondences` as before) instead; `hypotheses`, `seed` and `edge_length_ratio` are then unused."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
-    return _global(source, target, estimate_normals, compute_fpfh, feature_correspondences, correspondence_pairs,
-                   ransac_registration, reg.icp_refine, True, nb_neighbors, mutual, ransac_distance, icp_distance, estimation,
-                   hypotheses, seed, edge_length_ratio, refine_iterations, min_correspondences, max_iterations,
+    coarse = _coarse_estimator(estimator, True, 'global_registration', ransac_distance, refine_iterations, min_correspondences,
+                               hypotheses, seed, edge_length_ratio, consensus_distance, seeds, consensus_size)
+    return _global(source, target, estimate_normals, compute_fpfh, feature_correspondences, correspondence_pairs, coarse,
+                   reg.icp_refine, True, nb_neighbors, mutual, icp_distance, estimation, min_correspondences, max_iterations,
                    relative_fitness, relative_rmse)
 
 
-def _global(source, target, normals_of, fpfh_of, match, pairs_of, ransac, icp, device_route, nb, mutual, ransac_distance,
-            icp_distance, estimation, hypotheses, seed, ratio, refine_iterations, min_corr, max_iterations, rel_f, rel_r):
+def _global(source, target, normals_of, fpfh_of, match, pairs_of, coarse_of, icp, device_route, nb, mutual, icp_distance,
+            estimation, min_corr, max_iterations, rel_f, rel_r):
     what = 'global_registration'
     if not isinstance(source, list) or not isinstance(target, list) or not source or len(source) != len(target):
         raise ValueError('%s: two lists of (N_i, 3) clouds that pair up expected' % what)
@@ -351,8 +386,7 @@ def _global(source, target, normals_of, fpfh_of, match, pairs_of, ransac, icp, d
     features = fpfh_of(source + target, normals, nb)
     matched = match(features[:pairs], features[pairs:], mutual=mutual)
     corr = pairs_of(matched[0], matched[2] if mutual else None)
-    coarse = ransac(source, target, corr, max_correspondence_distance=ransac_distance, hypotheses=hypotheses, seed=seed,
-                    edge_length_ratio=ratio, refine_iterations=refine_iterations, min_correspondences=min_corr)
+    coarse = coarse_of(source, target, corr)
     plane = estimation == 'point_to_plane'
     fine = icp(source, target, init=coarse.transforms, max_correspondence_distance=icp_distance,
                max_iterations=max_iterations, relative_fitness=rel_f, relative_rmse=rel_r, min_correspondences=min_corr,
@@ -500,6 +534,13 @@ def ransac_registration_host(source, target, correspondences, *, max_corresponde
     d2_max = inlier_d2(dist)
     b = _HostBatch(source, target, correspondences, what)
     given = None if poses is None else b.host_poses(poses, None, what)
+    return _host_select_and_polish(
+        b, lambda i: _host_hypotheses_one(b.p[i], b.q[i], i, n_hyp, seed, rho2)[:2] if given is None else (given[0][i], given[1][i]),
+        d2_max, iters, min_corr)
+
+
+def _host_select_and_polish(b, candidates, d2_max, iters, min_corr):
+    """`_select_and_polish` in numpy on a `_HostBatch`; `candidates(i)` -> (poses (H, 12) float32, valid (H,) bool) of pair i"""
     pose = np.tile(np.eye(4)[:3], (b.pairs, 1, 1))
     fitness, rmse = np.zeros(b.pairs, np.float64), np.full(b.pairs, np.nan, np.float64)
     inliers, status = np.zeros(b.pairs, np.int64), np.zeros(b.pairs, np.int64)
@@ -507,7 +548,7 @@ def ransac_registration_host(source, target, correspondences, *, max_corresponde
                                      np.zeros(b.pairs, np.int64))
     for i in range(b.pairs):
         p, q = b.p[i], b.q[i]
-        cand, valid = _host_hypotheses_one(p, q, i, n_hyp, seed, rho2)[:2] if given is None else (given[0][i], given[1][i])
+        cand, valid = candidates(i)
         counts = _host_counts_one(p, q, cand, valid, d2_max)
         n_valid[i] = int((counts >= 0).sum())
         best = int(counts.argmax())                                    # the first of equal maxima: the lowest h
@@ -524,11 +565,13 @@ def ransac_registration_host(source, target, correspondences, *, max_corresponde
 def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                              estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9,
                              refine_iterations=3, min_correspondences=3, max_iterations=30, relative_fitness=1e-6,
-                             relative_rmse=1e-6):
+                             relative_rmse=1e-6, estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
     """`global_registration` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
+    coarse = _coarse_estimator(estimator, False, 'global_registration', ransac_distance, refine_iterations,
+                               min_correspondences, hypotheses, seed, edge_length_ratio, consensus_distance, seeds,
+                               consensus_size)
     return _global(source, target, estimate_normals_host, compute_fpfh_host, feature_correspondences_host,
-                   correspondence_pairs_host, ransac_registration_host, reg.icp_refine_host, False, nb_neighbors, mutual,
-                   ransac_distance, icp_distance, estimation, hypotheses, seed, edge_length_ratio, refine_iterations,
-                   min_correspondences, max_iterations, relative_fitness, relative_rmse)
+                   correspondence_pairs_host, coarse, reg.icp_refine_host, False, nb_neighbors, mutual, icp_distance,
+                   estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse)

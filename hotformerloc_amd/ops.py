@@ -2190,6 +2190,86 @@ def spectral_finish(w: torch.Tensor, partials: torch.Tensor, n_tiles: int, tile_
     return eigenvalue, score, weights
 
 
+CONSENSUS_ROWS = 512                   # HFL_CONSENSUS_ROWS: rows (correspondences) of a workgroup of hfl_consensus_graph (two per thread)
+CONSENSUS_TILE = 1024                  # HFL_CONSENSUS_TILE: columns of the LDS tile those rows share
+CONSENSUS_MAX_CORRESPONDENCES = 16384  # HFL_CONSENSUS_MAX_CORRESPONDENCES: of one pair
+CONSENSUS_MAX_SIZE = 64                # HFL_CONSENSUS_MAX_SIZE: the largest consensus set, the seed included
+
+
+def consensus_tiles(lengths):
+    """The tile table of `hfl_consensus_graph` from the pairs' numbers of correspondences on the host: `pair_tiles` with
+    CONSENSUS_ROWS rows of one pair per workgroup."""
+    return pair_tiles(lengths, CONSENSUS_ROWS)
+
+
+def consensus_words(lengths):
+    """Where every pair's bit matrix lies, from the pairs' numbers of correspondences on the host: ((P + 1,) int64 numpy word
+    offsets, the last one the total; (P,) int64 words of a row, 4 ceil(C / 128))."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    row_words = 4 * (-(-lengths // 128))
+    word_off = np.zeros(lengths.shape[0] + 1, np.int64)
+    np.cumsum(lengths * row_words, out=word_off[1:])
+    return word_off, row_words
+
+
+def _consensus_graph_check(what: str, bits: torch.Tensor, word_offsets: torch.Tensor, pairs: int):
+    _dev(bits, word_offsets)
+    _vector_check(what, bits, torch.int32, None, 'bit matrices')
+    _vector_check(what, word_offsets, torch.int64, pairs + 1, 'word offsets')
+    if bits.data_ptr() % 16:
+        raise TypeError('%s: 16-byte aligned bit matrices expected' % what)
+
+
+def consensus_graph(corr: torch.Tensor, c_offsets: torch.Tensor, tiles: torch.Tensor, word_offsets: torch.Tensor, n_words: int,
+                    distance: float):
+    """`hfl_consensus_graph`: the compatibility graph of every pair's correspondences (corr (C, 6) fp32 under c_offsets, as
+    `ransac_score` takes them; tiles: the device copy of `consensus_tiles`; word_offsets (P + 1,) int64: the device copy of
+    `consensus_words`, n_words its last entry) -> (bits (n_words,) int32: every pair's row-major bit matrix, degree (C,)
+    int32)."""
+    what = 'consensus_graph'
+    pairs = _ransac_corr_check(what, corr, c_offsets)
+    _ransac_tiles_check(what, tiles)
+    if not (float(distance) > 0.0 and np.isfinite(np.float32(distance)) and np.float32(distance) > 0.0):
+        raise ValueError('%s: a distance that is a finite float32 > 0 expected' % what)
+    bits = torch.empty(max(int(n_words), 4), dtype=torch.int32, device=corr.device)
+    _consensus_graph_check(what, bits, word_offsets, pairs)
+    degree = torch.zeros(int(corr.shape[0]), dtype=torch.int32, device=corr.device)
+    if int(tiles.shape[0]):
+        check(_native.load().hfl_consensus_graph(bits.data_ptr(), degree.data_ptr(), corr.data_ptr(), c_offsets.data_ptr(),
+                                                 int(corr.shape[0]), tiles.data_ptr(), int(tiles.shape[0]),
+                                                 word_offsets.data_ptr(), int(n_words), pairs, float(distance), _stream()),
+              'hfl_consensus_graph')
+    return bits, degree
+
+
+def consensus_poses(corr: torch.Tensor, c_offsets: torch.Tensor, bits: torch.Tensor, word_offsets: torch.Tensor, n_words: int,
+                    seeds: torch.Tensor, consensus_size: int):
+    """`hfl_consensus_poses`: seeds (P, S) int32, a row of the pair or -1, against the graph `consensus_graph` wrote -> (poses
+    (P, S, 12) fp32, valid (P, S) uint8, members (P, S, consensus_size) int32 padded with -1, support (P, S) int32); an
+    unused slot or an invalid set has a pose of NaNs, no members and support 0."""
+    what = 'consensus_poses'
+    pairs = _ransac_corr_check(what, corr, c_offsets)
+    _consensus_graph_check(what, bits, word_offsets, pairs)
+    _dev(seeds)
+    k1 = int(consensus_size)
+    if seeds.dtype != torch.int32 or seeds.dim() != 2 or seeds.shape[0] != pairs or seeds.shape[1] < 1 or \
+            not seeds.is_contiguous():
+        raise TypeError('%s: contiguous (%d, S >= 1) int32 seeds expected' % (what, pairs))
+    if not 3 <= k1 <= CONSENSUS_MAX_SIZE or not 0 <= int(n_words) <= int(bits.shape[0]):
+        raise ValueError('%s: consensus_size in 3 .. %d and n_words within the bit matrices expected'
+                         % (what, CONSENSUS_MAX_SIZE))
+    n_seeds = int(seeds.shape[1])
+    poses = torch.empty((pairs, n_seeds, 12), dtype=torch.float32, device=corr.device)
+    valid = torch.empty((pairs, n_seeds), dtype=torch.uint8, device=corr.device)
+    members = torch.empty((pairs, n_seeds, k1), dtype=torch.int32, device=corr.device)
+    support = torch.empty((pairs, n_seeds), dtype=torch.int32, device=corr.device)
+    check(_native.load().hfl_consensus_poses(poses.data_ptr(), valid.data_ptr(), members.data_ptr(), support.data_ptr(),
+                                             seeds.data_ptr(), bits.data_ptr(), word_offsets.data_ptr(), int(n_words),
+                                             _some(corr).data_ptr(), c_offsets.data_ptr(), int(corr.shape[0]), pairs, n_seeds,
+                                             k1, _stream()), 'hfl_consensus_poses')
+    return poses, valid, members, support
+
+
 VOXEL_MAX_CLOUDS = 32767           # HFL_VOXEL_MAX_CLOUDS
 VOXEL_MAX_CELLS = 65535                # HFL_VOXEL_MAX_CELLS: a cloud may span this many cells along an axis
 VOXEL_MAX_POINTS = 2147483646          # HFL_VOXEL_MAX_POINTS

@@ -372,10 +372,11 @@ def _cross(a, b):
     return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
 
 
-def _host_kabsch_many(sums):
+def _host_kabsch_many(sums, want_ratio=False):
     """(R (n, 3, 3), t (n, 3), solved (n,) bool) of (n, 17) sums; solved is False where H has rank < 2, and R and t mean
     nothing there.  `kabsch_solve` of csrc/kabsch.h, line by line, every float64 operation on all rows at once: the one
-    transcription, for the ICP, the RANSAC polish and the hypotheses alike"""
+    transcription, for the ICP, the RANSAC polish and the hypotheses alike.  With `want_ratio` also the (n,) rank ratios the
+    decision was taken on, second over largest singular value (NaN where H is 0 or not finite)"""
     n_rows = sums.shape[0]
     with np.errstate(all='ignore'):
         s = [sums[:, k].astype(np.float64) for k in range(N_SUMS)]
@@ -398,7 +399,9 @@ def _host_kabsch_many(sums):
         mp, mq = [s[1 + a] / n for a in range(3)], [s[4 + a] / n for a in range(3)]
         r = [[v1[a] * u1[b] + v2[a] * u2[b] + v3[a] * u3[b] for b in range(3)] for a in range(3)]
         t = [mq[a] - (r[a][0] * mp[0] + r[a][1] * mp[1] + r[a][2] * mp[2]) for a in range(3)]
-    return (np.stack([np.stack(row, 1) for row in r], 1).reshape(n_rows, 3, 3), np.stack(t, 1).reshape(n_rows, 3), solved)
+        ratio = w2 / w1
+    out = (np.stack([np.stack(row, 1) for row in r], 1).reshape(n_rows, 3, 3), np.stack(t, 1).reshape(n_rows, 3), solved)
+    return out + (ratio,) if want_ratio else out
 
 
 def _host_kabsch_one(s):

@@ -172,7 +172,8 @@ def prune_correspondences_host(correspondences, weights, keep):
 def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors=30, mutual=False, distance_threshold=0.4,
                       iterations=10, register=False, keep=None, ransac_distance=0.8, icp_distance=0.8,
                       estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
-                      min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6):
+                      min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                      estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
     """Re-rank the candidates of a search by spectral consistency.  `query_clouds`: a list of Q raw (N_i, 3) float32 GPU
     clouds; `database_clouds`: the list of the database's clouds, of which only the named ones are touched; `candidates`:
     the (Q, k) index tensor of `FlatL2Index.search`, -1 for an unused slot.  Normals and FPFH are computed once per
@@ -180,23 +181,24 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
     `spectral_consistency` call (`distance_threshold`, `iterations`) cover all Q k pairs, the query as the source.  ->
     `RerankResult`.  With `register`, every query's new top-1 pair also goes through `prune_correspondences` (where `keep`
     is given) -> `ransac_registration` -> `icp_refine` on the features already computed, with the options of
-    `global_registration`: -> `(RerankResult, RansacResult, RegistrationResult)`, query frame -> candidate frame, one row per
-    query; a query without a candidate is then a `ValueError`."""
+    `global_registration` (`estimator='consensus'` and its three options included): -> `(RerankResult, RansacResult,
+    RegistrationResult)`, query frame -> candidate frame, one row per query; a query without a candidate is then a
+    `ValueError`."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
     return _rerank(query_clouds, database_clouds, candidates, estimate_normals, compute_fpfh, feature_correspondences,
-                   GR.correspondence_pairs, spectral_consistency, prune_correspondences, GR.ransac_registration,
+                   GR.correspondence_pairs, spectral_consistency, prune_correspondences,
+                   GR._coarse_estimator(estimator, True, 'rerank_candidates', ransac_distance, refine_iterations,
+                                        min_correspondences, hypotheses, seed, edge_length_ratio, consensus_distance, seeds,
+                                        consensus_size),
                    reg.icp_refine, True, nb_neighbors, mutual, distance_threshold, iterations, register, keep,
-                   dict(max_correspondence_distance=ransac_distance, hypotheses=hypotheses, seed=seed,
-                        edge_length_ratio=edge_length_ratio, refine_iterations=refine_iterations,
-                        min_correspondences=min_correspondences),
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
                         min_correspondences=min_correspondences, estimation=estimation))
 
 
-def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of, spectral, prune, ransac, icp, device_route,
-            nb, mutual, sigma, iterations, register, keep, ransac_kw, icp_kw):
+def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of, spectral, prune, coarse_of, icp,
+            device_route, nb, mutual, sigma, iterations, register, keep, icp_kw):
     what = 'rerank_candidates'
     if not isinstance(queries, list) or not isinstance(database, list) or not queries or not database:
         raise ValueError('%s: two lists of (N_i, 3) clouds expected' % what)
@@ -249,7 +251,7 @@ def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of,
     if keep is not None:
         top_corr = prune(top_corr, [weights[i] for i in top], keep)
     src, dst = [clouds[q] for q in range(n_q)], [clouds[place[i]] for i in indices[:, 0]]
-    coarse = ransac(src, dst, top_corr, **ransac_kw)
+    coarse = coarse_of(src, dst, top_corr)
     plane = icp_kw['estimation'] == 'point_to_plane'
     fine = icp(src, dst, init=coarse.transforms, target_normals=[normals[place[i]] for i in indices[:, 0]] if plane else None,
                **icp_kw)
@@ -305,17 +307,18 @@ def spectral_consistency_host(source, target, correspondences, *, distance_thres
 def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neighbors=30, mutual=False, distance_threshold=0.4,
                            iterations=10, register=False, keep=None, ransac_distance=0.8, icp_distance=0.8,
                            estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
-                           min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6):
+                           min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                           estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
     """`rerank_candidates` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
     return _rerank(query_clouds, database_clouds, candidates, estimate_normals_host, compute_fpfh_host,
                    feature_correspondences_host, GR.correspondence_pairs_host, spectral_consistency_host,
-                   prune_correspondences_host, GR.ransac_registration_host, reg.icp_refine_host, False, nb_neighbors, mutual,
-                   distance_threshold, iterations, register, keep,
-                   dict(max_correspondence_distance=ransac_distance, hypotheses=hypotheses, seed=seed,
-                        edge_length_ratio=edge_length_ratio, refine_iterations=refine_iterations,
-                        min_correspondences=min_correspondences),
+                   prune_correspondences_host,
+                   GR._coarse_estimator(estimator, False, 'rerank_candidates', ransac_distance, refine_iterations,
+                                        min_correspondences, hypotheses, seed, edge_length_ratio, consensus_distance, seeds,
+                                        consensus_size),
+                   reg.icp_refine_host, False, nb_neighbors, mutual, distance_threshold, iterations, register, keep,
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
                         min_correspondences=min_correspondences, estimation=estimation))

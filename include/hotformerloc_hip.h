@@ -1344,6 +1344,40 @@ int hfl_spectral_finish(double* eigenvalue, double* score, float* weights, const
                         const int64_t* n_source, int64_t n_pairs, hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11i. Consensus registration: pose hypotheses from the second-order compatibility of a pair's point correspondences
+ *      (csrc/consensus.hip; no counterpart in the reference).  Definition: hotformerloc_amd/consensus.py, DESIGN.md
+ *      section 7q.
+ * ---------------------------------------------------------------------- */
+#define HFL_CONSENSUS_ROWS 512            /* rows (correspondences) of a 256-thread workgroup of hfl_consensus_graph (two per thread) */
+#define HFL_CONSENSUS_TILE 1024           /* columns of the LDS tile those rows share: six fp32 planes */
+#define HFL_CONSENSUS_MAX_CORRESPONDENCES 16384   /* of one pair: a row of second-order counts fits LDS as 16-bit values */
+#define HFL_CONSENSUS_MAX_SIZE 64         /* the largest consensus set, the seed included */
+/* Both take the correspondences as section 11g does: corr (n_corr, 6) fp32 rows with (P + 1) int64 DEVICE offsets, clamped
+ * to the array.  The compatibility graph of pair p with C correspondences is a bit matrix at bits + word_offsets[p]: C rows
+ * of W = 4 ceil(C / 128) 32-bit words, row-major; bit (j & 31) of word (j >> 5) of row i is B_ij = | |p_i - p_j| - |q_i -
+ * q_j| | <= distance in fp32 (the d2 fmaf chain, the correctly rounded root), B_ii = 0, the bits from column C on 0.
+ * word_offsets (P) int64 DEVICE, multiples of 4; n_words: the length of `bits`, which is 16-byte aligned.  A pair whose
+ * matrix does not lie inside [0, n_words), or with more than HFL_CONSENSUS_MAX_CORRESPONDENCES correspondences, is skipped
+ * (hfl_consensus_poses: its slots are invalid).  Launches on `stream`, no synchronisation, no host read, no atomics: two
+ * runs give the same bits.  A NULL pointer, a negative count, P < 1: HFL_EINVAL; n_corr, P, the tiles or P x S at 2^31 or
+ * more: HFL_ECAPACITY. */
+/* tiles (n_tiles, 2) int64 DEVICE rows of (pair, first row), HFL_CONSENSUS_ROWS rows of one pair per workgroup.  Writes
+ * every word of every pair's matrix and degree[i] = sum_j B_ij (n_corr) int32.  distance finite and > 0, else HFL_EINVAL. */
+int hfl_consensus_graph(uint32_t* bits, int32_t* degree, const float* corr, const int64_t* c_offsets, int64_t n_corr,
+                        const int64_t* tiles, int64_t n_tiles, const int64_t* word_offsets, int64_t n_words, int64_t n_pairs,
+                        float distance, hfl_stream_t stream);
+/* One workgroup per (pair, slot): seeds (P, S) int32, a row of the pair or -1 for an unused slot.  n_sj = B_sj sum_k B_sk
+ * B_jk; the consensus set is s and the consensus_size - 1 columns of largest n_sj >= 1, the lower j of equal ones; its
+ * members in ascending order give the 17 float64 sums (one accumulator each) kabsch_solve takes.  poses (P, S, 12) fp32,
+ * valid (P, S) uint8, members (P, S, consensus_size) int32 padded with -1, support (P, S) int32 = the n_sj of the weakest
+ * member.  An unused slot, a set of fewer than three members or of rank < 2: twelve NaNs, 0, -1 throughout, 0.
+ * consensus_size outside 3 .. HFL_CONSENSUS_MAX_SIZE or S < 1: HFL_EINVAL. */
+int hfl_consensus_poses(float* poses, uint8_t* valid, int32_t* members, int32_t* support, const int32_t* seeds,
+                        const uint32_t* bits, const int64_t* word_offsets, int64_t n_words, const float* corr,
+                        const int64_t* c_offsets, int64_t n_corr, int64_t n_pairs, int64_t n_seeds, int64_t consensus_size,
+                        hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 12. MESA self-distillation (training/trainer.py:161-163, 305-338, 360-361; models/losses/loss.py:138-147)
  * ---------------------------------------------------------------------- */
 /* One chunk of one (ema, src) tensor pair: `count` (1..HFL_EMA_CHUNK) fp32 elements at both pointers.  The host cuts each
