@@ -269,6 +269,9 @@ SIGNATURES = {
     'hfl_icp_correspond_plane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_int64,
                                          c_void_p]),
+    'hfl_icp_correspond_generalized': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float,
+                                               c_double, c_int64, c_void_p]),
     'hfl_icp_solve_plane': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                     c_double, c_double, c_int, c_void_p]),
     'hfl_ransac_hypotheses': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_uint64,

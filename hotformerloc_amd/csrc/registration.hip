@@ -1,7 +1,7 @@
-// Rigid ICP, point-to-point and point-to-plane, for a ragged batch of P (source, target) pairs: the definition is in
-// hotformerloc_amd/registration.py and DESIGN.md section 7i.  The layout is that of overlap.hip: the points of all clouds
-// concatenated as (N, 3) fp32 with (P + 1) int64 offsets.  One iteration is two launches, and a whole batch runs to
-// convergence without a host read: the state of a pair lives in two plain device arrays,
+// Rigid ICP, point-to-point, point-to-plane and generalized, for a ragged batch of P (source, target) pairs: the definition is
+// in hotformerloc_amd/registration.py and DESIGN.md sections 7i, 7j and 7r.  The layout is that of overlap.hip: the points of
+// all clouds concatenated as (N, 3) fp32 with (P + 1) int64 offsets.  One iteration is two launches, and a whole batch runs
+// to convergence without a host read: the state of a pair lives in two plain device arrays,
 //     state  (P, 16) float64: the pose as a row-major 3 x 4 (R | t), fitness, rmse, previous fitness, previous rmse
 //     istate (P, 2)  int32:   iterations, status (HFL_ICP_RUNNING .. HFL_ICP_DEGENERATE).
 //
@@ -32,6 +32,14 @@
 // reduced in the same order.  The solve factorises A = L D L^T without pivoting in a fixed order, solves A x = -g for
 // x = (alpha, beta, gamma, tx, ty, tz) and builds R = Rz(gamma) Ry(beta) Rx(alpha): det R = +1 by construction.
 //
+// hfl_icp_correspond_generalized: the generalized (plane-to-plane) estimator, the third instantiation
+// of the correspondence kernel.  The row's source normal is loaded beside the point and turned by the fp32 rotation already
+// in registers (no translation, no renormalisation); the winner's normal is gathered as PLANE gathers it.  Per inlier row, in
+// float64 with every operation rounded once (`icp_generalized_row`): C = 2 I - (1 - eps)(a a^T + b b^T), M = C^-1 by the
+// adjugate over the determinant, r = p' - q, J = (-[p']x | I), and the same 29 sums in the same layout,
+//     n, sum d^2, g = sum J^T M r (6), the upper triangle of A = sum J^T M J row-major (21),
+// which hfl_icp_solve_plane solves as it stands: with M = nq nq^T they are the point-to-plane sums.
+//
 // No atomics; every output element has one writer and a fixed evaluation order: two runs give the same bits.
 #include <math.h>
 
@@ -57,18 +65,79 @@ static_assert(RG_WAVES * RG_PLANE_SUMS * sizeof(double) <= RG_TILE * sizeof(floa
 static_assert(RG_SUMS == 17, "n, Sp, Sq, Spq, sum d^2");
 static_assert(RG_PLANE_SUMS == 29, "n, sum d^2, g, the upper triangle of A");
 
+enum { RG_POINT = 0, RG_PLANE = 1, RG_GENERALIZED = 2 };          // the estimator a correspondence kernel sums for
+
+// One inlier row of the generalized sums, in this statement order with every operation rounded once (no contraction: the
+// products of M are not exact, and the host route rounds each).  p, q: the moved source point and its target; a: the moved
+// source normal; b: the target's normal; all fp32 values widened, a zero normal leaves its cloud's covariance the identity.
+// keep = 1 - epsilon.  C = 2 I - keep (a a^T + b b^T) has its eigenvalues in [2 epsilon, 2] for unit or zero normals, so the
+// determinant is positive and the reciprocal finite.
+__device__ __forceinline__ void icp_generalized_row(double (&acc)[HFL_ICP_PLANE_SUMS], const double (&p)[3],
+                                                    const double (&q)[3], const double (&a)[3], const double (&b)[3], double dd,
+                                                    double keep) {
+#pragma clang fp contract(off)
+  const double c00 = 2.0 - keep * (a[0] * a[0] + b[0] * b[0]), c11 = 2.0 - keep * (a[1] * a[1] + b[1] * b[1]),
+               c22 = 2.0 - keep * (a[2] * a[2] + b[2] * b[2]);
+  const double c01 = -(keep * (a[0] * a[1] + b[0] * b[1])), c02 = -(keep * (a[0] * a[2] + b[0] * b[2])),
+               c12 = -(keep * (a[1] * a[2] + b[1] * b[2]));
+  // the adjugate (cofactors of a symmetric matrix), the determinant along the first row, one reciprocal
+  const double k00 = c11 * c22 - c12 * c12, k01 = c02 * c12 - c01 * c22, k02 = c01 * c12 - c02 * c11;
+  const double k11 = c00 * c22 - c02 * c02, k12 = c01 * c02 - c00 * c12, k22 = c00 * c11 - c01 * c01;
+  const double rcp = 1.0 / ((c00 * k00 + c01 * k01) + c02 * k02);
+  double m[3][3];
+  m[0][0] = k00 * rcp, m[1][1] = k11 * rcp, m[2][2] = k22 * rcp;
+  m[0][1] = m[1][0] = k01 * rcp, m[0][2] = m[2][0] = k02 * rcp, m[1][2] = m[2][1] = k12 * rcp;
+  const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  double w[3];                                                   // M r
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = (m[i][0] * r[0] + m[i][1] * r[1]) + m[i][2] * r[2];
+  acc[0] = acc[0] + 1.0;
+  acc[1] = acc[1] + dd * dd;
+  int slot = 8;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                                  // rows 0 .. 2 of J^T: row i of [p]x
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+    acc[2 + i] = acc[2 + i] + (p[i1] * w[i2] - p[i2] * w[i1]);   // (p x M r)_i
+    acc[5 + i] = acc[5 + i] + w[i];
+    double t[3];                                                 // row i of [p]x M: (p x column j of M)_i
+#pragma unroll
+    for (int j = 0; j < 3; ++j) t[j] = p[i1] * m[i2][j] - p[i2] * m[i1][j];
+#pragma unroll
+    for (int j = i; j < 3; ++j) {                                // row i of [p]x M [p]x^T from the diagonal on
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      acc[slot] = acc[slot] + (p[j1] * t[j2] - p[j2] * t[j1]);
+      ++slot;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      acc[slot] = acc[slot] + t[j];
+      ++slot;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j) {
+      acc[slot] = acc[slot] + m[i][j];
+      ++slot;
+    }
+}
+
 // six waves per SIMD, the residency of nn_dist_kernel (six workgroups of 24 KiB per CU): 80 VGPRs, which the reduction's 17
 // float64 sums beside the gathered coordinates would otherwise exceed by two.  PLANE is the point-to-plane estimator: the
 // same scan, the winner's normal gathered beside its coordinates, 29 sums; those do not fit 80 VGPRs, so that instantiation
-// asks for four waves per SIMD.
-template <bool PLANE>
-__global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(PLANE ? 4 : 6)))
+// asks for four waves per SIMD.  RG_GENERALIZED keeps the same scan, the row's moved source normal beside its point, both
+// normals and `icp_generalized_row` behind the scan, and the 29 sums; it asks for four waves per SIMD as well.
+template <int EST>
+__global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(EST != RG_POINT ? 4 : 6)))
 icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, int32_t* __restrict__ idx,
                       const float* __restrict__ source, const int64_t* __restrict__ s_off, int64_t n_source,
                       const float* __restrict__ targets, const float* __restrict__ t_normals,
                       const int64_t* __restrict__ t_off, int64_t n_targets, const int64_t* __restrict__ tiles,
-                      const double* __restrict__ state, const int32_t* __restrict__ istate, float max_dist, int n_pairs) {
-  constexpr int NS = PLANE ? RG_PLANE_SUMS : RG_SUMS;
+                      const double* __restrict__ state, const int32_t* __restrict__ istate, float max_dist, int n_pairs,
+                      const float* __restrict__ s_normals, double epsilon) {   // the last two: RG_GENERALIZED alone
+  constexpr bool PLANE = EST == RG_PLANE, GENERALIZED = EST == RG_GENERALIZED;
+  constexpr int NS = EST != RG_POINT ? RG_PLANE_SUMS : RG_SUMS;
   __shared__ __align__(16) float s_x[RG_TILE], s_y[RG_TILE], s_z[RG_TILE];
   PairTile w;
   if (!pair_tile(w, tiles, n_pairs)) return;
@@ -80,6 +149,8 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
   for (int k = 0; k < 12; ++k) m[k] = (float)state[16 * w.pair + k];
 
   float qx[RG_QPT], qy[RG_QPT], qz[RG_QPT], best[RG_QPT];
+  constexpr int NQ = GENERALIZED ? RG_QPT : 1;
+  float ax[NQ], ay[NQ], az[NQ];                                  // the moved source normals (RG_GENERALIZED alone)
   int32_t at[RG_QPT];
 #pragma unroll
   for (int r = 0; r < RG_QPT; ++r) {
@@ -89,7 +160,15 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
     qx[r] = rigid_coord(m, x, y, z);
     qy[r] = rigid_coord(m + 4, x, y, z);
     qz[r] = rigid_coord(m + 8, x, y, z);
+    if constexpr (GENERALIZED) {                                 // R n: rigid_coord without the translation
+      const float u = valid ? s_normals[3 * row] : 0.f, v = valid ? s_normals[3 * row + 1] : 0.f,
+                  t = valid ? s_normals[3 * row + 2] : 0.f;
+      ax[r] = fmaf(m[2], t, fmaf(m[1], v, m[0] * u));
+      ay[r] = fmaf(m[6], t, fmaf(m[5], v, m[4] * u));
+      az[r] = fmaf(m[10], t, fmaf(m[9], v, m[8] * u));
+    }
   }
+  const double keep = 1.0 - epsilon;
   pair_scan3<RG_THREADS>(w, targets, s_x, s_y, s_z, qx, qy, qz, best, at);
 
   double acc[NS];
@@ -127,6 +206,11 @@ icp_correspond_kernel(double* __restrict__ partials, float* __restrict__ dist, i
 #pragma unroll
             for (int b = a; b < 6; ++b) acc[slot++] += jac[a] * jac[b];     // a zero normal adds zeros
           }
+        } else if constexpr (GENERALIZED) {
+          const float* v = t_normals + 3 * (t_begin + at[r]);     // the winner's normal, once per source row
+          const double sa[3] = {(double)ax[r], (double)ay[r], (double)az[r]};
+          const double nc[3] = {(double)v[0], (double)v[1], (double)v[2]};
+          icp_generalized_row(acc, pc, qc, sa, nc, dd, keep);
         } else {
           icp_point_row(acc, pc, qc, dd);
         }
@@ -268,17 +352,20 @@ icp_solve_kernel(double* __restrict__ state, int32_t* __restrict__ istate, doubl
 
 namespace {
 
-// `target_normals` is required with PLANE and not looked at without
-template <bool PLANE>
-int icp_correspond_call(double* partials, float* dist, int32_t* idx, const float* source, const int64_t* s_offsets,
-                        int64_t n_source, const float* targets, const float* target_normals, const int64_t* t_offsets,
-                        int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
-                        float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  return pair_scan_call({partials, source, s_offsets, targets, t_offsets, tiles, state, istate},
-                        !PLANE || target_normals != nullptr, n_source, n_targets, n_tiles, n_pairs, [&] {
-    icp_correspond_kernel<PLANE><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+// `target_normals` is required with RG_PLANE and RG_GENERALIZED and not looked at without; `source_normals` and `epsilon`
+// (in (0, 1]; a NaN fails the test) go with RG_GENERALIZED alone
+template <int EST>
+int icp_correspond_call(double* partials, float* dist, int32_t* idx, const float* source, const float* source_normals,
+                        const int64_t* s_offsets, int64_t n_source, const float* targets, const float* target_normals,
+                        const int64_t* t_offsets, int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state,
+                        const int32_t* istate, float max_dist, double epsilon, int64_t n_pairs, hfl_stream_t stream) {
+  const bool ok = (EST == RG_POINT || target_normals != nullptr) &&
+                  (EST != RG_GENERALIZED || (source_normals != nullptr && epsilon > 0.0 && epsilon <= 1.0));
+  return pair_scan_call({partials, source, s_offsets, targets, t_offsets, tiles, state, istate}, ok, n_source, n_targets,
+                        n_tiles, n_pairs, [&] {
+    icp_correspond_kernel<EST><<<(unsigned)n_tiles, RG_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
         partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets, n_targets, tiles, state, istate,
-        max_dist, (int)n_pairs);
+        max_dist, (int)n_pairs, source_normals, epsilon);
   });
 }
 
@@ -302,8 +389,8 @@ extern "C" int hfl_icp_correspond(double* partials, float* dist, int32_t* idx, c
                                   int64_t n_source, const float* targets, const int64_t* t_offsets, int64_t n_targets,
                                   const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                   float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  return icp_correspond_call<false>(partials, dist, idx, source, s_offsets, n_source, targets, nullptr, t_offsets, n_targets,
-                                    tiles, n_tiles, state, istate, max_dist, n_pairs, stream);
+  return icp_correspond_call<RG_POINT>(partials, dist, idx, source, nullptr, s_offsets, n_source, targets, nullptr, t_offsets,
+                                       n_targets, tiles, n_tiles, state, istate, max_dist, 1.0, n_pairs, stream);
 }
 
 extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const float* source,
@@ -311,8 +398,19 @@ extern "C" int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* 
                                         const float* target_normals, const int64_t* t_offsets, int64_t n_targets,
                                         const int64_t* tiles, int64_t n_tiles, const double* state, const int32_t* istate,
                                         float max_dist, int64_t n_pairs, hfl_stream_t stream) {
-  return icp_correspond_call<true>(partials, dist, idx, source, s_offsets, n_source, targets, target_normals, t_offsets,
-                                   n_targets, tiles, n_tiles, state, istate, max_dist, n_pairs, stream);
+  return icp_correspond_call<RG_PLANE>(partials, dist, idx, source, nullptr, s_offsets, n_source, targets, target_normals,
+                                       t_offsets, n_targets, tiles, n_tiles, state, istate, max_dist, 1.0, n_pairs, stream);
+}
+
+extern "C" int hfl_icp_correspond_generalized(double* partials, float* dist, int32_t* idx, const float* source,
+                                              const float* source_normals, const int64_t* s_offsets, int64_t n_source,
+                                              const float* targets, const float* target_normals, const int64_t* t_offsets,
+                                              int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state,
+                                              const int32_t* istate, float max_dist, double epsilon, int64_t n_pairs,
+                                              hfl_stream_t stream) {
+  return icp_correspond_call<RG_GENERALIZED>(partials, dist, idx, source, source_normals, s_offsets, n_source, targets,
+                                             target_normals, t_offsets, n_targets, tiles, n_tiles, state, istate, max_dist,
+                                             epsilon, n_pairs, stream);
 }
 
 extern "C" int hfl_icp_solve(double* state, int32_t* istate, double* sums, const double* partials,

@@ -356,11 +356,12 @@ def _coarse_estimator(estimator, device_route, what, ransac_distance, refine_ite
 def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                         estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                         min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                        estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
+                        estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10, covariance_epsilon=1e-3):
     """From two lists of raw (N_i, 3) float32 GPU clouds to refined 6-DoF poses, source frame -> target frame, in one call:
     `estimate_normals` -> `compute_fpfh` -> `feature_correspondences` (`mutual`) -> `correspondence_pairs` ->
     `ransac_registration` (`ransac_distance` and its options) -> `icp_refine(init=...)` (`icp_distance`, `estimation`, its
-    options; point-to-plane uses the target normals already estimated).  -> `(RansacResult, RegistrationResult)`.  A pair
+    options; point-to-plane uses the target normals already estimated, 'generalized' those and the source normals, with
+    `covariance_epsilon`).  -> `(RansacResult, RegistrationResult)`.  A pair
     that ends NO_HYPOTHESIS enters the ICP at the identity.  `estimator='consensus'` takes the coarse pose from
     `consensus_registration` (`consensus_distance`, `seeds`, `consensus_size`; `ransac_distance`, `refine_iterations` and
     `min_correspondences` as before) instead; `hypotheses`, `seed` and `edge_length_ratio` are then unused."""
@@ -370,16 +371,17 @@ def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_
                                hypotheses, seed, edge_length_ratio, consensus_distance, seeds, consensus_size)
     return _global(source, target, estimate_normals, compute_fpfh, feature_correspondences, correspondence_pairs, coarse,
                    reg.icp_refine, True, nb_neighbors, mutual, icp_distance, estimation, min_correspondences, max_iterations,
-                   relative_fitness, relative_rmse)
+                   relative_fitness, relative_rmse, covariance_epsilon)
 
 
 def _global(source, target, normals_of, fpfh_of, match, pairs_of, coarse_of, icp, device_route, nb, mutual, icp_distance,
-            estimation, min_corr, max_iterations, rel_f, rel_r):
+            estimation, min_corr, max_iterations, rel_f, rel_r, epsilon=1e-3):
     what = 'global_registration'
     if not isinstance(source, list) or not isinstance(target, list) or not source or len(source) != len(target):
         raise ValueError('%s: two lists of (N_i, 3) clouds that pair up expected' % what)
     if estimation not in reg.ESTIMATIONS:
         raise ValueError('%s: estimation must be one of %s, got %r' % (what, ', '.join(reg.ESTIMATIONS), estimation))
+    reg._epsilon(epsilon, what)
     _ragged(source, what, device_route), _ragged(target, what, device_route)   # the refusals, before anything is computed
     pairs = len(source)
     normals = normals_of(source + target, nb)
@@ -387,10 +389,11 @@ def _global(source, target, normals_of, fpfh_of, match, pairs_of, coarse_of, icp
     matched = match(features[:pairs], features[pairs:], mutual=mutual)
     corr = pairs_of(matched[0], matched[2] if mutual else None)
     coarse = coarse_of(source, target, corr)
-    plane = estimation == 'point_to_plane'
+    plane, generalized = estimation != 'point_to_point', estimation == 'generalized'
     fine = icp(source, target, init=coarse.transforms, max_correspondence_distance=icp_distance,
                max_iterations=max_iterations, relative_fitness=rel_f, relative_rmse=rel_r, min_correspondences=min_corr,
-               estimation=estimation, target_normals=normals[pairs:] if plane else None)
+               estimation=estimation, target_normals=normals[pairs:] if plane else None,
+               source_normals=normals[:pairs] if generalized else None, covariance_epsilon=epsilon)
     return coarse, fine
 
 
@@ -565,7 +568,8 @@ def _host_select_and_polish(b, candidates, d2_max, iters, min_corr):
 def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                              estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9,
                              refine_iterations=3, min_correspondences=3, max_iterations=30, relative_fitness=1e-6,
-                             relative_rmse=1e-6, estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
+                             relative_rmse=1e-6, estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
+                             covariance_epsilon=1e-3):
     """`global_registration` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
@@ -574,4 +578,4 @@ def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ra
                                consensus_size)
     return _global(source, target, estimate_normals_host, compute_fpfh_host, feature_correspondences_host,
                    correspondence_pairs_host, coarse, reg.icp_refine_host, False, nb_neighbors, mutual, icp_distance,
-                   estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse)
+                   estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse, covariance_epsilon)

@@ -1947,16 +1947,21 @@ def _partials_check(what: str, partials: torch.Tensor, rows: int, n_sums: int):
 
 def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch.Tensor, t_offsets: torch.Tensor,
                    tiles: torch.Tensor, state: torch.Tensor, istate: torch.Tensor, max_dist: float, partials=None,
-                   want_rows: bool = False, target_normals: torch.Tensor = None):
+                   want_rows: bool = False, target_normals: torch.Tensor = None, source_normals: torch.Tensor = None,
+                   epsilon: float = 1e-3):
     """`hfl_icp_correspond`: one evaluation of every RUNNING pair.  source / targets: two ragged batches of the same P pairs;
     tiles: the device copy of `overlap_tiles` of the source lengths; state (P, 16) float64 and istate (P, 2) int32 as the
     header lays them out.  -> (partials (n_tiles, ICP_SUMS) float64, dist, idx): `partials` is written in place where one is
     given (the iteration loop allocates once), dist (Ns,) fp32 and idx (Ns,) int32 are None unless `want_rows`.  Rows of
     pairs that are not RUNNING stay unwritten.  With `target_normals` ((Nt, 3) fp32, the rows of `targets`) it is
-    `hfl_icp_correspond_plane` and the partials have ICP_PLANE_SUMS columns."""
+    `hfl_icp_correspond_plane` and the partials have ICP_PLANE_SUMS columns; with `source_normals` ((Ns, 3) fp32, the rows
+    of `source`) as well it is `hfl_icp_correspond_generalized` with the covariance `epsilon` in (0, 1]."""
     plane = target_normals is not None
+    generalized = source_normals is not None
+    if generalized and not plane:
+        raise ValueError('icp_correspond: source_normals go with target_normals')
     n_sums = ICP_PLANE_SUMS if plane else ICP_SUMS
-    what = 'icp_correspond_plane' if plane else 'icp_correspond'
+    what = 'icp_correspond_generalized' if generalized else 'icp_correspond_plane' if plane else 'icp_correspond'
     name = 'hfl_' + what
     pairs = _pair_batch_check(what, source, s_offsets, targets, t_offsets, tiles, ('source', 'target'))
     if plane:
@@ -1964,6 +1969,13 @@ def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch
         _points_check(what, target_normals)
         if target_normals.shape[0] != targets.shape[0]:
             raise ValueError('%s: %d target normals for %d target points' % (what, target_normals.shape[0], targets.shape[0]))
+    if generalized:
+        _dev(source_normals)
+        _points_check(what, source_normals)
+        if source_normals.shape[0] != source.shape[0]:
+            raise ValueError('%s: %d source normals for %d source points' % (what, source_normals.shape[0], source.shape[0]))
+        if not 0.0 < float(epsilon) <= 1.0:
+            raise ValueError('%s: epsilon must lie in (0, 1], got %r' % (what, epsilon))
     _icp_state_check(what, state, istate, pairs)
     n_s, n_tiles = int(source.shape[0]), int(tiles.shape[0])
     if partials is None:
@@ -1973,10 +1985,12 @@ def icp_correspond(source: torch.Tensor, s_offsets: torch.Tensor, targets: torch
     idx = torch.empty(n_s, dtype=torch.int32, device=source.device) if want_rows else None
     if n_tiles:
         normals = (_some(target_normals).data_ptr(),) if plane else ()          # the one argument the plane entry point adds
+        s_normals = (source_normals.data_ptr(),) if generalized else ()         # and the two of the generalized one
+        eps = (float(epsilon),) if generalized else ()
         check(getattr(_native.load(), name)(
             partials.data_ptr(), dist.data_ptr() if want_rows else None, idx.data_ptr() if want_rows else None,
-            source.data_ptr(), s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), *normals, t_offsets.data_ptr(),
-            int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(), float(max_dist), pairs,
+            source.data_ptr(), *s_normals, s_offsets.data_ptr(), n_s, _some(targets).data_ptr(), *normals, t_offsets.data_ptr(),
+            int(targets.shape[0]), tiles.data_ptr(), n_tiles, state.data_ptr(), istate.data_ptr(), float(max_dist), *eps, pairs,
             _stream()), name)
     return partials, dist, idx
 

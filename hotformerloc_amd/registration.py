@@ -1,4 +1,4 @@
-"""Rigid ICP registration, point-to-point or point-to-plane, of a ragged batch of submap pairs, on the GPU.
+"""Rigid ICP registration, point-to-point, point-to-plane or generalized, of a ragged batch of submap pairs, on the GPU.
 
 Retrieval names a place; the query scan is useful once it is registered against it.  `submap_overlap` aligns a ground submap
 to an aerial one by the surveyed poses alone, so its Chamfer distance mixes pose error with real disagreement between the
@@ -10,7 +10,7 @@ points themselves.  The reference has no such step and open3d is not a dependenc
     icp_correspondences    one evaluation: every source point's distance, target, inlier flag, and the 17 sums of a pair
     evaluate_registration  fitness and inlier rmse of a given alignment (the k = 0 evaluation alone)
     kabsch_update          the rigid update (R, t) of given sums
-    plane_update           the point-to-plane update (R, t) of given sums
+    plane_update           the point-to-plane update (R, t) of given sums, and the generalized one: the same 29 sums
 
 Definition (DESIGN.md section 7i has the reasons).  Per pair, T_0 = init (float64 4 x 4, the identity by default;
 `SubmapOverlap.transforms` feeds in directly).  For k = 0 .. max_iterations: evaluate, decide, update.
@@ -52,6 +52,33 @@ modes.  Only the update differs:
   R = Rz(gamma) Ry(beta) Rx(alpha) (open3d's `TransformVector6dToMatrix4d`), t = (tx, ty, tz), T_{k+1} = [R | t] . T_k in
   float64; R is a product of three rotations, so det R = +1 by construction.
 
+Generalized, or plane-to-plane (`estimation='generalized'`, after Segal, Haehnel and Thrun 2009; `source_normals` in the
+layout of `source` and `target_normals` in the layout of `target`, both unit to fp32 rounding or zero for "no normal", which
+is what `estimate_normals` returns and is not checked; `covariance_epsilon`, 1e-3 by default, 0 < epsilon <= 1).
+Point-to-plane trusts the target's normal alone; here both clouds carry a local surface, a disc of covariance R diag(eps, 1,
+1) R^T = I - (1 - eps) n n^T round its normal, and every residual is weighted by the inverse of the two covariances added up
+(DESIGN.md section 7r has the reasons).  Parity with open3d's `registration_generalized_icp` is not claimed.  Evaluate,
+fitness, `inlier_rmse` (the point-to-point distance rmse still), the stop rules, `iterations` and the status codes are
+exactly as above; dist, idx and the inlier flags keep the bits of the call without normals.  Only the update differs:
+
+  Moved source normal.  a = fp32(R_k) . n_s, the chain of the evaluation without the translation (acc = r0 * x; acc =
+  fmaf(r1, y, acc); fmaf(r2, z, acc)), not renormalised.  b = target_normals[j(p')].
+
+  Row.  In float64 from the fp32 values p', q, a, b, every operation rounded once, keep = 1 - eps:
+    C_ii = 2 - keep (a_i a_i + b_i b_i),  C_ij = -(keep (a_i a_j + b_i b_j)) for i < j         (a zero normal: its term is I)
+    K00 = C11 C22 - C12 C12, K01 = C02 C12 - C01 C22, K02 = C01 C12 - C02 C11, K11 = C00 C22 - C02 C02,
+    K12 = C01 C02 - C00 C12, K22 = C00 C11 - C01 C01;  rcp = 1 / ((C00 K00 + C01 K01) + C02 K02);  M_ij = K_ij rcp, symmetric
+    r = p' - q;  w_i = (M_i0 r_0 + M_i1 r_1) + M_i2 r_2;  with i1 = i + 1 mod 3, i2 = i + 2 mod 3:
+    g_i = p'_i1 w_i2 - p'_i2 w_i1 (i < 3),  g_{3+i} = w_i;  T_ij = p'_i1 M_i2,j - p'_i2 M_i1,j (row i of [p']x M);
+    A_ij = p'_j1 T_i,j2 - p'_j2 T_i,j1 (i <= j < 3),  A_i,3+j = T_ij,  A_3+i,3+j = M_ij (i <= j).
+  The eigenvalues of C lie in [2 eps, 2] for unit or zero normals, so C is positive definite and cond(C) <= 1 / eps.  These
+  are g = J^T M r and A = J^T M J for J = (-[p']x | I) (3 x 6); with M = n n^T they are the point-to-plane row.
+
+  Sums and solve.  The `N_SUMS_PLANE` = 29 sums in the layout of point-to-plane -- n, sum d^2, g (6), the upper triangle of A
+  row-major (21) -- and its solve as it stands (LDL^T, R = Rz Ry Rx, `PIVOT_TOL`): `plane_update` solves either.  M is
+  positive definite in every row, so three non-collinear inliers determine the pose, and a flat target under vertical normals,
+  DEGENERATE for point-to-plane, is not degenerate here.
+
 `iterations` is the k at which the pair stopped: the number of updates its pose received.  An empty source cloud is TOO_FEW
 with fitness NaN (0 / 0), an empty target cloud TOO_FEW with fitness 0.
 
@@ -82,7 +109,7 @@ N_SUMS_PLANE = 29                      # n, sum d^2, g (6), the upper triangle o
 JACOBI_SWEEPS = 12                     # KABSCH_SWEEPS of csrc/kabsch.h
 RANK_TOL = 1e-12                       # second singular value <= RANK_TOL x the largest: DEGENERATE
 PIVOT_TOL = 1e-12                      # a pivot of the LDL^T <= PIVOT_TOL x its diagonal entry of A: DEGENERATE
-ESTIMATIONS = ('point_to_point', 'point_to_plane')
+ESTIMATIONS = ('point_to_point', 'point_to_plane', 'generalized')
 
 RegistrationResult = namedtuple('RegistrationResult', ['transforms', 'fitness', 'inlier_rmse', 'iterations', 'status'])
 RegistrationResult.__doc__ = """What `icp_refine` returns, numpy arrays on the host.  transforms: (P, 4, 4) float64, source
@@ -111,25 +138,39 @@ def _options(max_correspondence_distance, max_iterations, relative_fitness, rela
     return d, int(max_iterations), float(relative_fitness), float(relative_rmse), int(min_correspondences)
 
 
-def _estimation(estimation, target_normals, what):
-    """True for point-to-plane; the normals go with that estimator and with no other"""
+def _epsilon(covariance_epsilon, what):
+    eps = float(covariance_epsilon)
+    if not 0.0 < eps <= 1.0:
+        raise ValueError('%s: covariance_epsilon must lie in (0, 1], got %r' % (what, covariance_epsilon))
+    return eps
+
+
+def _estimation(estimation, target_normals, what, source_normals=None, covariance_epsilon=1e-3):
+    """True where the sums are the 29 of point-to-plane (that estimator and the generalized one); the target's normals go
+    with those two and with no other, the source's with the generalized one alone"""
     if estimation not in ESTIMATIONS:
         raise ValueError('%s: estimation must be one of %s, got %r' % (what, ', '.join(ESTIMATIONS), estimation))
-    plane = estimation == 'point_to_plane'
+    _epsilon(covariance_epsilon, what)
+    plane, generalized = estimation != 'point_to_point', estimation == 'generalized'
     if plane and target_normals is None:
-        raise ValueError("%s: estimation='point_to_plane' needs target_normals" % what)
+        raise ValueError('%s: estimation=%r needs target_normals' % (what, estimation))
     if not plane and target_normals is not None:
-        raise ValueError("%s: target_normals go with estimation='point_to_plane'" % what)
+        raise ValueError("%s: target_normals go with estimation='point_to_plane' or 'generalized'" % what)
+    if generalized and source_normals is None:
+        raise ValueError("%s: estimation='generalized' needs source_normals" % what)
+    if not generalized and source_normals is not None:
+        raise ValueError("%s: source_normals go with estimation='generalized'" % what)
     return plane
 
 
-def _normals_of(target, target_normals, t_off, what, ragged):
-    """the (M, 3) float32 normals of the target batch: a list like `target`, or the packed array under the target's offsets"""
+def _normals_of(target, target_normals, t_off, what, ragged, side='target'):
+    """the (M, 3) float32 normals of the target batch: a list like `target`, or the packed array under the target's offsets;
+    with `side='source'` the same of the source batch"""
     if isinstance(target, list) != isinstance(target_normals, list):
-        raise ValueError('%s: target_normals must come in the layout of target' % what)
+        raise ValueError('%s: %s_normals must come in the layout of %s' % (what, side, side))
     nrm, n_off, _ = ragged(target_normals if isinstance(target_normals, list) else (target_normals, t_off), what)
     if not np.array_equal(n_off, t_off):
-        raise ValueError('%s: target_normals must hold one normal per target point, cloud by cloud' % what)
+        raise ValueError('%s: %s_normals must hold one normal per %s point, cloud by cloud' % (what, side, side))
     return nrm
 
 
@@ -177,14 +218,17 @@ class _Batch:
     """A batch of pairs on the device with everything an iteration needs: both clouds, their offsets, the tile table of the
     source clouds and its per-pair offsets, the partials."""
 
-    def __init__(self, source, target, what, target_normals=None):
+    def __init__(self, source, target, what, target_normals=None, source_normals=None, epsilon=1e-3):
         from . import ops
         self.s, self.s_off, _ = _ragged(source, what, True)
         self.t, self.t_off, _ = _ragged(target, what, True)
         _same_pairs(self.s_off, self.t_off, what)
-        self.plane = target_normals is not None
-        self.normals = _normals_of(target, target_normals, self.t_off, what, lambda b, w: _ragged(b, w, True)) \
-            if self.plane else None
+        self.plane = target_normals is not None                    # the 29 sums and their solve: point-to-plane, generalized
+        on_device = lambda b, w: _ragged(b, w, True)               # noqa: E731
+        self.normals = _normals_of(target, target_normals, self.t_off, what, on_device) if self.plane else None
+        self.s_normals = None if source_normals is None else \
+            _normals_of(source, source_normals, self.s_off, what, on_device, 'source')
+        self.epsilon = epsilon
         self.pairs = self.s_off.shape[0] - 1
         dev = self.s.device
         tiles, tile_off = ops.pair_tiles(np.diff(self.s_off))
@@ -201,7 +245,8 @@ class _Batch:
     def correspond(self, state, istate, max_dist, want_rows=False):
         from . import ops
         return ops.icp_correspond(self.s, self.s_dev, self.t, self.t_dev, self.tiles, state, istate, max_dist,
-                                  partials=self.partials, want_rows=want_rows, target_normals=self.normals)
+                                  partials=self.partials, want_rows=want_rows, target_normals=self.normals,
+                                  source_normals=self.s_normals, epsilon=self.epsilon)
 
     def solve(self, state, istate, min_corr, rel_fitness, rel_rmse, is_last, want_sums=False):
         from . import ops
@@ -210,17 +255,19 @@ class _Batch:
 
 
 def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
-               relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None):
+               relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None,
+               source_normals=None, covariance_epsilon=1e-3):
     """ICP of P (source, target) pairs, as the module's docstring defines it -> `RegistrationResult`.  `init`: (P, 4, 4) or
     (P, 3, 4) float64, numpy or tensor, source frame -> target frame; None is the identity.  `estimation`:
     'point_to_point', or 'point_to_plane' with `target_normals` in the layout of `target` (a list of (M_i, 3) float32, or the
-    packed (M, 3) tensor under the target's offsets).  The whole loop is enqueued on the current stream without a host read;
-    the results are read once at the end."""
+    packed (M, 3) tensor under the target's offsets), or 'generalized' with those and `source_normals` in the layout of
+    `source`, and `covariance_epsilon` in (0, 1].  The whole loop is enqueued on the current stream without a host read; the
+    results are read once at the end."""
     what = 'icp_refine'
     dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
                                                    min_correspondences, what)
-    _estimation(estimation, target_normals, what)
-    b = _Batch(source, target, what, target_normals)
+    _estimation(estimation, target_normals, what, source_normals, covariance_epsilon)
+    b = _Batch(source, target, what, target_normals, source_normals, float(covariance_epsilon))
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_init_matrices(init, b.pairs, what))
         _iterate_on_device(state, istate, iters, lambda st, ist: b.correspond(st, ist, dist),
@@ -228,10 +275,18 @@ def icp_refine(source, target, init=None, max_correspondence_distance=0.8, max_i
         return RegistrationResult(*_read_state(state, istate))
 
 
+def _sums_of_normals(target_normals, source_normals, covariance_epsilon, what):
+    """which sums `icp_correspondences` is asked for, by the normals it is given -> epsilon"""
+    if source_normals is not None and target_normals is None:
+        raise ValueError('%s: source_normals go with target_normals (the generalized sums)' % what)
+    return _epsilon(covariance_epsilon, what)
+
+
 def _evaluate(source, target, transforms, max_correspondence_distance, min_correspondences, what, want_rows,
-              target_normals=None):
+              target_normals=None, source_normals=None, covariance_epsilon=1e-3):
     dist, _, _, _, min_corr = _options(max_correspondence_distance, 0, 0.0, 0.0, min_correspondences, what)
-    b = _Batch(source, target, what, target_normals)
+    eps = _sums_of_normals(target_normals, source_normals, covariance_epsilon, what)
+    b = _Batch(source, target, what, target_normals, source_normals, eps)
     with torch.cuda.device(b.s.device):
         state, istate = b.state(_matrices(transforms, b.pairs, what))
         (_, d, j), sums, _ = _iterate_on_device(
@@ -240,14 +295,16 @@ def _evaluate(source, target, transforms, max_correspondence_distance, min_corre
     return d, j, sums, state, dist
 
 
-def icp_correspondences(source, target, transforms, max_correspondence_distance, target_normals=None):
+def icp_correspondences(source, target, transforms, max_correspondence_distance, target_normals=None, source_normals=None,
+                        covariance_epsilon=1e-3):
     """One evaluation at the given poses, on the device: `(dist (Ns,) float32, idx (Ns,) int32, inlier (Ns,) bool, sums
     (P, 17) float64)`.  dist and idx have the bits of `nn_distances(transform_points(source, transforms), target)`; inlier is
     `dist <= fp32(max_correspondence_distance)` where there is a target; sums are n, Sp, Sq, Spq (row-major) and sum d^2
     over a pair's inliers, in the device's fixed order.  With `target_normals` (the layout of `target`) the sums are the
-    (P, 29) of the point-to-plane update -- n, sum d^2, g, the upper triangle of A -- and the rest keeps its bits."""
+    (P, 29) of the point-to-plane update -- n, sum d^2, g, the upper triangle of A -- and the rest keeps its bits; with
+    `source_normals` (the layout of `source`) as well they are the (P, 29) of the generalized update at `covariance_epsilon`."""
     d, j, sums, _, dist = _evaluate(source, target, transforms, max_correspondence_distance, 0, 'icp_correspondences', True,
-                                    target_normals)
+                                    target_normals, source_normals, covariance_epsilon)
     return d, j, (j >= 0) & (d <= float(np.float32(dist))), sums
 
 
@@ -286,7 +343,8 @@ def _update_on_device(sums, min_correspondences, n_sums, what, plane):
 def plane_update(sums, min_correspondences=6):
     """The update step of `hfl_icp_solve_plane` on given sums (P, 29) float64 on the device -> `(R (P, 3, 3), t (P, 3),
     status (P,) int32)` on the device: the twin of `kabsch_update`.  status is RUNNING where (R, t) is the update, TOO_FEW
-    where n < min_correspondences and DEGENERATE where a pivot of the LDL^T fails; there R = I and t = 0."""
+    where n < min_correspondences and DEGENERATE where a pivot of the LDL^T fails; there R = I and t = 0.  The sums of the
+    generalized estimator have the same layout and are solved by the same call."""
     return _update_on_device(sums, min_correspondences, N_SUMS_PLANE, 'plane_update', True)
 
 
@@ -325,6 +383,60 @@ def _host_plane_sums(p, q, n, d):
     return sums
 
 
+def _host_turn(normals, m34):
+    """the moved source normals: `_host_move` without the translation, acc = r0 * x first"""
+    m = m34.astype(np.float32)
+    x, y, z = normals[:, 0], normals[:, 1], normals[:, 2]
+    out = np.empty_like(normals)
+    for c in range(3):
+        out[:, c] = _fmaf(m[c, 2], z, _fmaf(m[c, 1], y, m[c, 0] * x))
+    return out
+
+
+def _host_generalized_rows(p, q, a, b, d, epsilon):
+    """The (n, 29) terms of given inlier rows under the generalized estimator, the row of the module's docstring operation for
+    operation (`icp_generalized_row` of csrc/registration.hip): float64 (n, 3) moved source points p, targets q, moved source
+    normals a and target normals b, the distances d (n,); their sum over the rows is the pair's 29 sums."""
+    p, q, a, b = ([np.asarray(x, np.float64)[:, i] for i in range(3)] for x in (p, q, a, b))
+    d = np.asarray(d, np.float64)
+    keep = np.float64(1.0) - np.float64(epsilon)
+    c = [[None] * 3 for _ in range(3)]
+    for i in range(3):
+        c[i][i] = 2.0 - keep * (a[i] * a[i] + b[i] * b[i])
+        for j in range(i + 1, 3):
+            c[i][j] = c[j][i] = -(keep * (a[i] * a[j] + b[i] * b[j]))
+    k00, k01, k02 = c[1][1] * c[2][2] - c[1][2] * c[1][2], c[0][2] * c[1][2] - c[0][1] * c[2][2], \
+        c[0][1] * c[1][2] - c[0][2] * c[1][1]
+    k11, k12, k22 = c[0][0] * c[2][2] - c[0][2] * c[0][2], c[0][1] * c[0][2] - c[0][0] * c[1][2], \
+        c[0][0] * c[1][1] - c[0][1] * c[0][1]
+    rcp = 1.0 / ((c[0][0] * k00 + c[0][1] * k01) + c[0][2] * k02)
+    m = [[k00 * rcp, k01 * rcp, k02 * rcp], [None, k11 * rcp, k12 * rcp], [None, None, k22 * rcp]]
+    m[1][0], m[2][0], m[2][1] = m[0][1], m[0][2], m[1][2]
+    r = [p[i] - q[i] for i in range(3)]
+    w = [(m[i][0] * r[0] + m[i][1] * r[1]) + m[i][2] * r[2] for i in range(3)]
+    rows = np.zeros((d.shape[0], N_SUMS_PLANE), np.float64)
+    rows[:, 0] = 1.0
+    rows[:, 1] = d * d
+    slot = 8
+    for i in range(3):
+        i1, i2 = (i + 1) % 3, (i + 2) % 3
+        rows[:, 2 + i] = p[i1] * w[i2] - p[i2] * w[i1]
+        rows[:, 5 + i] = w[i]
+        t = [p[i1] * m[i2][j] - p[i2] * m[i1][j] for j in range(3)]
+        for j in range(i, 3):
+            j1, j2 = (j + 1) % 3, (j + 2) % 3
+            rows[:, slot] = p[j1] * t[j2] - p[j2] * t[j1]
+            slot += 1
+        for j in range(3):
+            rows[:, slot] = t[j]
+            slot += 1
+    for i in range(3):
+        for j in range(i, 3):
+            rows[:, slot] = m[i][j]
+            slot += 1
+    return rows
+
+
 def _host_point_sums(p, q, d):
     """the 17 sums of given inlier rows, float64 (n, 3) each and the distances (n,); zeros where there is no row"""
     sums = np.zeros(N_SUMS, np.float64)
@@ -335,13 +447,19 @@ def _host_point_sums(p, q, d):
     return sums
 
 
-def _host_evaluate_one(src, dst, m34, max_dist32, normals=None):
+def _host_evaluate_one(src, dst, m34, max_dist32, normals=None, s_normals=None, epsilon=1e-3):
     """one pair, one evaluation: (dist float32, idx int32, inlier bool, sums (17,) float64, or (29,) with the target's
-    normals)"""
+    normals: those of point-to-plane, or with the source's normals too those of the generalized estimator)"""
     moved = _host_move(src, m34)
     dist, idx = _host_nn32(moved, dst)
     inl = (idx >= 0) & (dist <= max_dist32)
     p, q, d = moved[inl].astype(np.float64), dst[idx[inl]].astype(np.float64), dist[inl].astype(np.float64)
+    if s_normals is not None:
+        a = _host_turn(s_normals, m34)[inl].astype(np.float64).reshape(-1, 3)
+        b = normals[idx[inl]].astype(np.float64).reshape(-1, 3)
+        sums = _host_generalized_rows(p.reshape(-1, 3), q.reshape(-1, 3), a, b, d, epsilon).sum(0)
+        sums[1] = (d * d).sum()                                        # in the order of the other two modes: the same rmse bits
+        return dist, idx, inl, sums
     if normals is not None:
         return dist, idx, inl, _host_plane_sums(p, q, normals[idx[inl]].astype(np.float64).reshape(-1, 3), d)
     return dist, idx, inl, _host_point_sums(p, q, d)
@@ -478,11 +596,13 @@ def _host_plane_one(s):
 
 
 def plane_update_host(sums, min_correspondences=6):
-    """`plane_update` on the CPU: `(R (P, 3, 3) float64, t (P, 3) float64, status (P,) int32)` numpy arrays."""
+    """`plane_update` on the CPU: `(R (P, 3, 3) float64, t (P, 3) float64, status (P,) int32)` numpy arrays; the sums of the
+    generalized estimator as well."""
     return _update_on_host(sums, min_correspondences, N_SUMS_PLANE, 'plane_update', _host_plane_one)
 
 
-def _host_batch(source, target, what, target_normals=None):
+def _host_batch(source, target, what, target_normals=None, source_normals=None):
+    """per pair (source, target), then the target's normals where given, then the source's"""
     s, s_off, _ = _host_ragged(source, what)
     t, t_off, _ = _host_ragged(target, what)
     _same_pairs(s_off, t_off, what)
@@ -490,7 +610,11 @@ def _host_batch(source, target, what, target_normals=None):
     if target_normals is None:
         return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
     n = _normals_of(target, target_normals, t_off, what, _host_ragged)
-    return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]], n[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
+    if source_normals is None:
+        return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]], n[t_off[p]:t_off[p + 1]]) for p in range(pairs)], s_off
+    a = _normals_of(source, source_normals, s_off, what, _host_ragged, 'source')
+    return [(s[s_off[p]:s_off[p + 1]], t[t_off[p]:t_off[p + 1]], n[t_off[p]:t_off[p + 1]], a[s_off[p]:s_off[p + 1]])
+            for p in range(pairs)], s_off
 
 
 def _host_figures(sums, n_source, min_corr):
@@ -529,31 +653,37 @@ def _host_iterate(evaluate, n_rows, pose0, iters, min_corr, rel_f, rel_r, solve_
 
 
 def icp_refine_host(source, target, init=None, max_correspondence_distance=0.8, max_iterations=30, relative_fitness=1e-6,
-                    relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None):
+                    relative_rmse=1e-6, min_correspondences=3, estimation='point_to_point', target_normals=None,
+                    source_normals=None, covariance_epsilon=1e-3):
     """`icp_refine` on the CPU: the module's definition in numpy, pair by pair -> `RegistrationResult`."""
     what = 'icp_refine'
     dist, iters, rel_f, rel_r, min_corr = _options(max_correspondence_distance, max_iterations, relative_fitness, relative_rmse,
                                                    min_correspondences, what)
-    solve_one = _host_plane_one if _estimation(estimation, target_normals, what) else _host_kabsch_one
-    batch, _ = _host_batch(source, target, what, target_normals)
+    plane = _estimation(estimation, target_normals, what, source_normals, covariance_epsilon)
+    solve_one = _host_plane_one if plane else _host_kabsch_one
+    batch, _ = _host_batch(source, target, what, target_normals, source_normals)
+    eps = float(covariance_epsilon)
     pose = _init_matrices(init, len(batch), what).copy()
     fitness, rmse = np.zeros(len(batch), np.float64), np.zeros(len(batch), np.float64)
     iterations, status = np.zeros(len(batch), np.int64), np.zeros(len(batch), np.int64)
     for p, (src, dst, *nrm) in enumerate(batch):
         pose[p], fitness[p], rmse[p], _, iterations[p], status[p] = _host_iterate(
-            lambda m34: _host_evaluate_one(src, dst, m34, np.float32(dist), *nrm)[3], src.shape[0], pose[p], iters, min_corr,
-            rel_f, rel_r, solve_one)
+            lambda m34: _host_evaluate_one(src, dst, m34, np.float32(dist), *nrm, epsilon=eps)[3], src.shape[0], pose[p], iters,
+            min_corr, rel_f, rel_r, solve_one)
     return RegistrationResult(_full(pose), fitness, rmse, iterations, status)
 
 
-def icp_correspondences_host(source, target, transforms, max_correspondence_distance, target_normals=None):
+def icp_correspondences_host(source, target, transforms, max_correspondence_distance, target_normals=None,
+                             source_normals=None, covariance_epsilon=1e-3):
     """`icp_correspondences` on the CPU: `(dist float32, idx int32, inlier bool, sums (P, 17) float64)` numpy arrays; with
-    `target_normals` the sums are (P, 29)."""
+    `target_normals` the sums are (P, 29), those of the generalized estimator where `source_normals` are given too."""
     what = 'icp_correspondences'
     dist = _options(max_correspondence_distance, 0, 0.0, 0.0, 0, what)[0]
-    batch, _ = _host_batch(source, target, what, target_normals)
+    eps = _sums_of_normals(target_normals, source_normals, covariance_epsilon, what)
+    batch, _ = _host_batch(source, target, what, target_normals, source_normals)
     m = _matrices(transforms, len(batch), what)
-    parts = [_host_evaluate_one(pair[0], pair[1], m[p], np.float32(dist), *pair[2:]) for p, pair in enumerate(batch)]
+    parts = [_host_evaluate_one(pair[0], pair[1], m[p], np.float32(dist), *pair[2:], epsilon=eps)
+             for p, pair in enumerate(batch)]
     return (np.concatenate([x[0] for x in parts]), np.concatenate([x[1] for x in parts]), np.concatenate([x[2] for x in parts]),
             np.stack([x[3] for x in parts]))
 

@@ -173,7 +173,8 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
                       iterations=10, register=False, keep=None, ransac_distance=0.8, icp_distance=0.8,
                       estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                       min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                      estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
+                      estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
+                      covariance_epsilon=1e-3):
     """Re-rank the candidates of a search by spectral consistency.  `query_clouds`: a list of Q raw (N_i, 3) float32 GPU
     clouds; `database_clouds`: the list of the database's clouds, of which only the named ones are touched; `candidates`:
     the (Q, k) index tensor of `FlatL2Index.search`, -1 for an unused slot.  Normals and FPFH are computed once per
@@ -181,7 +182,8 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
     `spectral_consistency` call (`distance_threshold`, `iterations`) cover all Q k pairs, the query as the source.  ->
     `RerankResult`.  With `register`, every query's new top-1 pair also goes through `prune_correspondences` (where `keep`
     is given) -> `ransac_registration` -> `icp_refine` on the features already computed, with the options of
-    `global_registration` (`estimator='consensus'` and its three options included): -> `(RerankResult, RansacResult,
+    `global_registration` (`estimator='consensus'` and its three options included; `estimation='generalized'` takes the
+    query's normals as the source's, with `covariance_epsilon`): -> `(RerankResult, RansacResult,
     RegistrationResult)`, query frame -> candidate frame, one row per query; a query without a candidate is then a
     `ValueError`."""
     from .fpfh import compute_fpfh, feature_correspondences
@@ -194,7 +196,8 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
                    reg.icp_refine, True, nb_neighbors, mutual, distance_threshold, iterations, register, keep,
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
-                        min_correspondences=min_correspondences, estimation=estimation))
+                        min_correspondences=min_correspondences, estimation=estimation,
+                        covariance_epsilon=covariance_epsilon))
 
 
 def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of, spectral, prune, coarse_of, icp,
@@ -204,6 +207,7 @@ def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of,
         raise ValueError('%s: two lists of (N_i, 3) clouds expected' % what)
     if icp_kw['estimation'] not in reg.ESTIMATIONS:
         raise ValueError('%s: estimation must be one of %s, got %r' % (what, ', '.join(reg.ESTIMATIONS), icp_kw['estimation']))
+    reg._epsilon(icp_kw['covariance_epsilon'], what)
     _options(sigma, iterations, what)
     if keep is not None and (int(keep) != keep or keep < 0):
         raise ValueError('%s: keep must be None or an integer >= 0' % what)
@@ -252,9 +256,9 @@ def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of,
         top_corr = prune(top_corr, [weights[i] for i in top], keep)
     src, dst = [clouds[q] for q in range(n_q)], [clouds[place[i]] for i in indices[:, 0]]
     coarse = coarse_of(src, dst, top_corr)
-    plane = icp_kw['estimation'] == 'point_to_plane'
+    plane, generalized = icp_kw['estimation'] != 'point_to_point', icp_kw['estimation'] == 'generalized'
     fine = icp(src, dst, init=coarse.transforms, target_normals=[normals[place[i]] for i in indices[:, 0]] if plane else None,
-               **icp_kw)
+               source_normals=[normals[q] for q in range(n_q)] if generalized else None, **icp_kw)
     return ranked, coarse, fine
 
 
@@ -308,7 +312,8 @@ def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neig
                            iterations=10, register=False, keep=None, ransac_distance=0.8, icp_distance=0.8,
                            estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                            min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                           estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10):
+                           estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
+                           covariance_epsilon=1e-3):
     """`rerank_candidates` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
@@ -321,4 +326,5 @@ def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neig
                    reg.icp_refine_host, False, nb_neighbors, mutual, distance_threshold, iterations, register, keep,
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
-                        min_correspondences=min_correspondences, estimation=estimation))
+                        min_correspondences=min_correspondences, estimation=estimation,
+                        covariance_epsilon=covariance_epsilon))

@@ -1268,6 +1268,21 @@ int hfl_icp_correspond_plane(double* partials, float* dist, int32_t* idx, const 
 int hfl_icp_solve_plane(double* state, int32_t* istate, double* sums, const double* partials, const int64_t* tile_offsets,
                         int64_t n_tiles, const int64_t* s_offsets, int64_t n_pairs, int min_correspondences,
                         double relative_fitness, double relative_rmse, int is_last, hfl_stream_t stream);
+/* The generalized (plane-to-plane) estimator, DESIGN.md section 7r: hfl_icp_correspond_plane with a normal on both sides.
+ * source_normals (DEVICE, (n_source, 3) fp32, the rows of `source`) are turned by the fp32 rotation of the pair's pose, the
+ * fmaf chain of hfl_transform_points without the translation and without renormalising: a.  b = target_normals[idx].  Both
+ * are unit to fp32 rounding, or zero for "no normal" (not checked).  Per inlier row, in float64 from those fp32 values with
+ * every operation rounded once: C = 2 I - (1 - epsilon)(a a^T + b b^T), M = C^-1 (adjugate times the reciprocal of the
+ * determinant), r = p' - q, J = (-[p']x | I); the HFL_ICP_PLANE_SUMS sums are n, sum d^2, g = sum J^T M r (6), the upper
+ * triangle of A = sum J^T M J row-major (21), which hfl_icp_solve_plane takes as they are.  dist, idx, the inlier rule and
+ * the order of the reduction are those of hfl_icp_correspond.  A NULL source_normals or target_normals, or an epsilon
+ * outside (0, 1]: HFL_EINVAL. */
+int hfl_icp_correspond_generalized(double* partials, float* dist, int32_t* idx, const float* source,
+                                   const float* source_normals, const int64_t* s_offsets, int64_t n_source,
+                                   const float* targets, const float* target_normals, const int64_t* t_offsets,
+                                   int64_t n_targets, const int64_t* tiles, int64_t n_tiles, const double* state,
+                                   const int32_t* istate, float max_dist, double epsilon, int64_t n_pairs,
+                                   hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 11g. Global registration from point correspondences: a deterministic RANSAC that gives hfl_icp_correspond its starting

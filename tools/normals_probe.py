@@ -9,7 +9,10 @@
   plane     one point-to-plane iteration (`hfl_icp_correspond_plane` + `hfl_icp_solve_plane`) against one point-to-point
             iteration (`hfl_icp_correspond` + `hfl_icp_solve`) on 64 pairs of 30 000 x 30 000 points, the scenes of
             tools/registration_probe.py, every pair RUNNING, `--launches` iterations back to back between two HIP events.
-            The target normals are `estimate_normals` of the targets.
+            The target normals are `estimate_normals` of the targets.  A third leg times the generalized iteration
+            (`hfl_icp_correspond_generalized` + `hfl_icp_solve_plane`) on the same pairs with `estimate_normals` of the
+            sources as well, and a whole `icp_refine` call of each mode with the updates it needed.  `--only-plane` leaves
+            the normals part out.
 
 No throughput target is set: the figures to report are the two ratios, each measured in one run.  Median / min / max of
 `--repeats` measurements after `--warmup`.  One JSON line.  Run it under `timeout`."""
@@ -97,9 +100,11 @@ def probe_plane(args):
     d_normals = estimate_normals(d_target, NB)
     torch.cuda.synchronize()
     res['estimate_normals_of_the_targets_ms'] = round((time.perf_counter() - t0) * 1e3, 3)
+    s_normals = estimate_normals(d_source, NB)
     identity = np.tile(np.eye(4)[:3], (pairs, 1, 1))
-    for name, normals in (('point_to_point_iteration', None), ('point_to_plane_iteration', d_normals)):
-        batch = reg._Batch(d_source, d_target, 'normals_probe', normals)
+    for name, normals, more in (('point_to_point_iteration', None, None), ('point_to_plane_iteration', d_normals, None),
+                                ('generalized_iteration', d_normals, s_normals)):
+        batch = reg._Batch(d_source, d_target, 'normals_probe', normals, more)
         state, istate = batch.state(identity)
 
         def iteration():
@@ -109,13 +114,18 @@ def probe_plane(args):
 
         res[name] = events(iteration, args.repeats, args.warmup, args.launches)
     res['plane_over_point'] = round(res['point_to_plane_iteration']['median_ms'] / res['point_to_point_iteration']['median_ms'], 3)
+    res['generalized_over_plane'] = round(res['generalized_iteration']['median_ms'] /
+                                          res['point_to_plane_iteration']['median_ms'], 3)
     for name, kw in (('icp_refine_point_to_point', {}),
-                     ('icp_refine_point_to_plane', dict(estimation='point_to_plane', target_normals=d_normals))):
+                     ('icp_refine_point_to_plane', dict(estimation='point_to_plane', target_normals=d_normals)),
+                     ('icp_refine_generalized', dict(estimation='generalized', target_normals=d_normals,
+                                                     source_normals=s_normals))):
         got = {}
         res[name] = wall(lambda: got.update(r=reg.icp_refine(d_source, d_target, max_correspondence_distance=MAX_DIST, **kw)),
                          max(args.repeats // 2, 1), 1)
         r = got['r']
         res[name].update({'iterations_min': int(r.iterations.min()), 'iterations_max': int(r.iterations.max()),
+                          'iterations_mean': round(float(r.iterations.mean()), 3),
                           'status_counts': np.bincount(r.status, minlength=5).tolist(),
                           'mean_fitness': round(float(r.fitness.mean()), 4),
                           'mean_inlier_rmse': round(float(np.nanmean(r.inlier_rmse)), 4)})
@@ -132,10 +142,12 @@ def main():
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--launches', type=int, default=3)
+    ap.add_argument('--only-plane', action='store_true', help='the ICP iterations alone, without the normals part')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('normals_probe needs a GPU: nothing is timed without one')
-    res = {'normals': [probe_normals(args, points) for points in args.points], 'plane': probe_plane(args)}
+    res = {'normals': [] if args.only_plane else [probe_normals(args, points) for points in args.points],
+           'plane': probe_plane(args)}
     print(json.dumps(res), flush=True)
 
 
