@@ -4,7 +4,9 @@ Public surface (mirrors the reference's): `model_factory`, `ModelParams`, `Octre
 `merge_octrees`, and the `dwconv` op module.  See DESIGN.md / INTEGRATION.md.
 
 Raw-submap post-processing on the device (the reference's open3d / CSF toolkit): `trim_radius`, `remove_outliers` (and
-`knn_mean_distance`, the exact k-nearest-neighbour mean distance behind it; `estimate_normals` on the same search),
+`knn_mean_distance`, the exact k-nearest-neighbour mean distance behind it; `estimate_normals` on the same search;
+`remove_radius_outliers` / `radius_neighbour_counts` on its radius form, which `estimate_normals(radius=)` and
+`compute_fpfh(radius=)` take as hybrid or radius-only neighbourhoods),
 `remove_ground`, `voxel_downsample` /
 `pnvlad_downsample` / `random_downsample`, `normalise_submaps`, chained by `prepare_submaps` / `prepare_submaps_fixed`;
 every step has a numpy `*_host` twin that states its definition.
@@ -48,7 +50,8 @@ from .voxel import (voxel_downsample, normalise_submaps, prepare_submaps, voxel_
                     normalise_submaps_padded_host, prepare_submaps_fixed)
 from .ground import remove_ground, remove_ground_host                                              # noqa: F401,E402
 from .outliers import (remove_outliers, remove_outliers_host, knn_mean_distance, knn_mean_distance_host,   # noqa: F401,E402
-                       trim_radius, trim_radius_host)
+                       trim_radius, trim_radius_host, radius_neighbour_counts, radius_neighbour_counts_host,
+                       remove_radius_outliers, remove_radius_outliers_host)
 from .tuples import (radius_lists, radius_counts, radius_lists_host, radius_counts_host,          # noqa: F401,E402
                      tuple_index_from_poses, truth_from_poses)
 from .overlap import (pose_matrix, relative_pose, match_nearest_pose, transform_points, nn_distances,   # noqa: F401,E402

@@ -152,7 +152,12 @@ SIGNATURES = {
     'hfl_knn_cell_keys': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     'hfl_knn_mean_dist': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     'hfl_knn_normals': (c_int, [c_void_p] * 11 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    'hfl_knn_normals_radius': (c_int, [c_void_p] * 11 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_float, c_int, c_int,
+                                                        c_void_p]),
+    'hfl_knn_radius_count': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_float, c_int, c_void_p]),
+    'hfl_count_mask': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'hfl_fpfh_radius': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    'hfl_fpfh_radius_capped': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_float, c_int, c_void_p]),
     'hfl_fpfh_spfh': (c_int, [c_void_p] * 12 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'hfl_fpfh_combine': (c_int, [c_void_p] * 13 + [c_int, c_int64, c_void_p, c_int64, c_void_p]),
     'hfl_feature_nn': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p,

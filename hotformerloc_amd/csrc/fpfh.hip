@@ -8,6 +8,10 @@
 //                      the k-th smallest fp32 squared distance (the sorted register list), and notes whether the
 //                      completeness bound proves that every point with d2 <= r2 lies in the block; the others are appended
 //                      to a list, and a wave per listed point finds r2 in the point's whole cloud.
+//   hfl_fpfh_radius_capped  the same with r2 = min(k-th smallest, R2) (hybrid), or, radius-only, r2 = R2 for every point
+//                      with no scan at all: one thread per point asks the completeness bound whether its block holds every
+//                      point within R2 and lists the point if not.  The two calls below read r2 and the proof and never k,
+//                      so they serve all three kinds of neighbourhood unchanged.
 //   hfl_fpfh_spfh      one thread per proven point re-scans its block, a wave per listed point its whole cloud: every
 //                      neighbour with d2 <= r2 that forms a pair is binned, in float64, into the thread's 33 counters.  The
 //                      counters live in LDS, one column per thread (33 x 256 x 4 B = 33 KiB a workgroup, four workgroups a
@@ -101,13 +105,27 @@ __global__ void __launch_bounds__(kOutThreads)
 fpfh_radius_kernel(float* __restrict__ r2s, uint8_t* __restrict__ proven, int32_t* __restrict__ pending,
                    int32_t* __restrict__ counter, const float* __restrict__ spts, const int64_t* __restrict__ skeys,
                    const int32_t* __restrict__ starts, const hfl_knn_grid* __restrict__ grids,
-                   const int64_t* __restrict__ off, int batch, int64_t n) {
+                   const int64_t* __restrict__ off, int batch, int64_t n, float cap) {
   const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
   if (j >= n) return;
   const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
   KnnList<K> list;
-  const KnnFirst f = knn_first_scan(list, p, spts, starts);
+  const KnnFirst f = knn_first_scan(list, p, spts, starts, cap);
   r2s[j] = f.r2;
+  proven[j] = f.resolved ? 1 : 0;
+  if (!f.resolved) knn_append_pending(pending, counter, j, n);
+}
+
+// r2 = cap for every point, the pending ones too: nothing is scanned and no fallback follows
+__global__ void __launch_bounds__(kOutThreads)
+fpfh_radius_only_kernel(float* __restrict__ r2s, uint8_t* __restrict__ proven, int32_t* __restrict__ pending,
+                        int32_t* __restrict__ counter, const float* __restrict__ spts, const int64_t* __restrict__ skeys,
+                        const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, int batch, int64_t n,
+                        float cap) {
+  const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (j >= n) return;
+  const KnnFirst f = knn_radius_first(knn_point(spts, skeys, grids, off, batch, n, j), cap);
+  r2s[j] = cap;
   proven[j] = f.resolved ? 1 : 0;
   if (!f.resolved) knn_append_pending(pending, counter, j, n);
 }
@@ -116,12 +134,13 @@ template <int K>
 __global__ void __launch_bounds__(kOutThreads)
 fpfh_radius_fallback_kernel(float* __restrict__ r2s, const int32_t* __restrict__ pending,
                             const int32_t* __restrict__ counter, const float* __restrict__ spts,
-                            const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, int batch, int64_t n) {
+                            const hfl_knn_grid* __restrict__ grids, const int64_t* __restrict__ off, int batch, int64_t n,
+                            float cap) {
   knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int c, int64_t first, int64_t last) {
     const int k = min(max(grids[c].k, 1), K);
     KnnList<K> list;
     knn_cloud_first(list, spts[j * 3 + 0], spts[j * 3 + 1], spts[j * 3 + 2], spts, first, last);
-    const float r2 = knn_wave_kth(list, k);
+    const float r2 = knn_wave_kth(list, k, cap);
     if (knn_lane() == 0) r2s[j] = r2;
   });
 }
@@ -356,27 +375,41 @@ void feature_nn_launch(float* dist2, int32_t* idx, const float* queries, const i
 
 }  // namespace
 
-extern "C" int hfl_fpfh_radius(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* cell_starts,
-                               const float* sorted_points, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
-                               const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets,
-                               int64_t n_points, hfl_stream_t stream) {
+extern "C" int hfl_fpfh_radius_capped(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                                      const float* sorted_points, const int64_t* sorted_keys,
+                                      const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                                      const int64_t* cloud_offsets, int64_t n_points, float radius2, int radius_only,
+                                      hfl_stream_t stream) {
   if (r2 == nullptr || proven == nullptr || pending == nullptr || counter == nullptr || cell_starts == nullptr ||
       sorted_points == nullptr || sorted_keys == nullptr || grids_host == nullptr || grids == nullptr ||
-      cloud_offsets == nullptr)
+      cloud_offsets == nullptr || !knn_cap_ok(radius2))
     return HFL_EINVAL;
   int k_max = 0;
   if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n = n_points;
   if (const int rc = knn_launch_starts(cell_starts, counter, sorted_keys, n, n_cells, HFL_KNN_PHASE_ALL, s)) return rc;
+  if (radius_only) {
+    fpfh_radius_only_kernel<<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+        r2, proven, pending, counter, sorted_points, sorted_keys, grids, cloud_offsets, batch, n, radius2);
+    HFL_RETURN_LAST_ERROR();
+  }
   return knn_dispatch_k(k_max, [&](auto kc) -> int {
     constexpr int K = decltype(kc)::value;
     fpfh_radius_kernel<K><<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
-        r2, proven, pending, counter, sorted_points, sorted_keys, cell_starts, grids, cloud_offsets, batch, n);
-    fpfh_radius_fallback_kernel<K><<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(r2, pending, counter, sorted_points,
-                                                                                     grids, cloud_offsets, batch, n);
+        r2, proven, pending, counter, sorted_points, sorted_keys, cell_starts, grids, cloud_offsets, batch, n, radius2);
+    fpfh_radius_fallback_kernel<K><<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(
+        r2, pending, counter, sorted_points, grids, cloud_offsets, batch, n, radius2);
     HFL_RETURN_LAST_ERROR();
   });
+}
+
+extern "C" int hfl_fpfh_radius(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                               const float* sorted_points, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
+                               const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets,
+                               int64_t n_points, hfl_stream_t stream) {
+  return hfl_fpfh_radius_capped(r2, proven, pending, counter, cell_starts, sorted_points, sorted_keys, grids_host, grids,
+                                batch, n_cells, cloud_offsets, n_points, INFINITY, 0, stream);
 }
 
 extern "C" int hfl_fpfh_spfh(int32_t* hist, int32_t* pairs, const float* r2, const uint8_t* proven, const int32_t* pending,

@@ -6,6 +6,12 @@
 // (`knn_append_pending`) and the wave-per-point walk over it (`knn_for_pending`, `knn_cloud_scan`, `knn_wave_merge`).  The
 // kernels of the three files keep only what they do with a neighbour.  hotformerloc_amd/outliers.py and DESIGN.md section
 // 7g define the search; every file that includes this is built with -ffp-contract=off.
+//
+// Radius and hybrid neighbourhoods.  `cap` is R2, the largest fp32 d2 that counts as "within the
+// radius", a launch argument, the same for every cloud of a call; +inf is no cap and changes no bit.  Hybrid: the first scan
+// and the fallback take r2 = min(k-th smallest, cap).  Radius-only: r2 = cap for every point, so there is no list and no
+// first scan -- `knn_radius_first` only asks the bound whether the block holds every point within cap, and the consumer
+// does its work in one pass over the block (or over the cloud, for a pending point).
 #pragma once
 #include <math.h>
 
@@ -126,9 +132,10 @@ struct KnnPoint {
   int32_t first, last;
   int64_t local;
   float px, py, pz;
+  __device__ __forceinline__ bool in_cells() const { return local >= 0 && local < (int64_t)g.nx * g.ny * g.nz; }
   template <int K>
   __device__ __forceinline__ bool on_grid() const {            // a key off its own grid goes to the whole-cloud scan
-    return local >= 0 && local < (int64_t)g.nx * g.ny * g.nz && g.k >= 1 && g.k <= K;
+    return in_cells() && g.k >= 1 && g.k <= K;
   }
 };
 
@@ -144,8 +151,10 @@ __device__ __forceinline__ KnnPoint knn_point(const float* __restrict__ spts, co
   return p;
 }
 
-// The first scan of a point: the K smallest squared distances of its block in `list`, r2 the k-th smallest of them, and
-// whether the bound proves that every point with d2 <= r2 lies in the block.  Off the grid: +inf, not resolved, no block.
+// The first scan of a point: the K smallest squared distances of its block in `list`, r2 the smaller of the k-th smallest
+// of them and `cap`, and whether the bound proves that every point with d2 <= r2 lies in the block.  A block with fewer
+// than k points has a k-th of +inf and is resolved through the cap alone: every point within the cap lies in the block.
+// Off the grid: +inf, not resolved, no block.
 struct KnnFirst {
   KnnBlock blk = {};
   float r2 = INFINITY;
@@ -154,15 +163,27 @@ struct KnnFirst {
 
 template <int K>
 __device__ __forceinline__ KnnFirst knn_first_scan(KnnList<K>& list, const KnnPoint& p, const float* __restrict__ spts,
-                                                   const int32_t* __restrict__ starts) {
+                                                   const int32_t* __restrict__ starts, float cap = INFINITY) {
   KnnFirst f;
   list.clear();
   if (p.on_grid<K>()) {
     f.blk = knn_block(p.g, p.local);
     knn_block_scan(p.g, f.blk, starts, p.first, p.last,
                    [&](int32_t q) { list.insert(knn_d2(p.px, p.py, p.pz, spts + (int64_t)q * 3)); });
-    f.r2 = list.kth(p.g.k);
+    f.r2 = fminf(list.kth(p.g.k), cap);
     f.resolved = f.r2 < knn_block_bound(p.px, p.py, p.pz, p.g, f.blk);
+  }
+  return f;
+}
+
+// what takes the first scan's place when r2 is the cap for every point: the block, and whether the bound proves that every
+// point with d2 <= cap lies in it.  The grid's k is not read.  Off the grid: not resolved, no block.
+__device__ __forceinline__ KnnFirst knn_radius_first(const KnnPoint& p, float cap) {
+  KnnFirst f;
+  f.r2 = cap;
+  if (p.in_cells()) {
+    f.blk = knn_block(p.g, p.local);
+    f.resolved = cap < knn_block_bound(p.px, p.py, p.pz, p.g, f.blk);
   }
   return f;
 }
@@ -185,13 +206,16 @@ __device__ __forceinline__ void knn_wave_merge(KnnList<K>& list, int k, F&& f) {
   }
 }
 
-// the k-th smallest value of the 64 lists: the last of the k rounds
+// the smaller of `cap` and the k-th smallest value of the 64 lists: the last of the k rounds
 template <int K>
-__device__ __forceinline__ float knn_wave_kth(KnnList<K>& list, int k) {
+__device__ __forceinline__ float knn_wave_kth(KnnList<K>& list, int k, float cap = INFINITY) {
   float r2 = INFINITY;
   knn_wave_merge(list, k, [&](float m) { r2 = m; });
-  return r2;
+  return fminf(r2, cap);
 }
+
+// a cap is a squared distance or +inf: not negative, not a NaN
+inline bool knn_cap_ok(float cap) { return cap >= 0.f; }
 
 // appends sorted position j to the list of points the block could not resolve: one integer add per wave, the order of the
 // list is free.  Every lane that calls it must be active together (call it under one condition).

@@ -14,6 +14,11 @@
 //                          is strictly below the square of a conservative distance to the nearest face of the block that has
 //                          cells behind it, else it is appended to a list; (3) a wave per listed point scans the point's
 //                          whole cloud, a list per lane, and merges the 64 lists by k rounds of a wave minimum
+//   hfl_knn_radius_count   counts = the number of points of the own cloud with d2 <= R2, the point itself included (open3d's
+//                          remove_radius_outlier counts the same set): no list and no first scan -- one thread per point
+//                          counts over its 3 x 3 x 3 block where the bound proves that the block holds every point within
+//                          R2, a wave per other point over its whole cloud.  An integer: the same for any grid.
+//   hfl_count_mask         keep = counts > nb_points
 //   hfl_outlier_threshold  per cloud, in float64 in the order of hfl_pair_stats: mean, std, mean + ratio std, n_valid
 //   hfl_outlier_mask       keep = avg > 0 and double(avg) < threshold
 //   hfl_radius_mask        keep = sqrt(x x + y y) <= radius_max in float64
@@ -101,6 +106,47 @@ knn_fallback_kernel(float* __restrict__ avg, const int32_t* __restrict__ pending
     const int64_t row = perm[j];
     if (knn_lane() == 0 && row >= 0 && row < n) avg[row] = __fdiv_rn(sum, (float)k);
   });
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+radius_count_kernel(int32_t* __restrict__ counts, int32_t* __restrict__ pending, int32_t* __restrict__ counter,
+                    const float* __restrict__ spts, const int64_t* __restrict__ skeys, const int64_t* __restrict__ perm,
+                    const int32_t* __restrict__ starts, const hfl_knn_grid* __restrict__ grids,
+                    const int64_t* __restrict__ off, int batch, int64_t n, float cap) {
+  const int64_t j = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (j >= n) return;
+  const KnnPoint p = knn_point(spts, skeys, grids, off, batch, n, j);
+  const KnnFirst f = knn_radius_first(p, cap);
+  if (f.resolved) {
+    int m = 0;
+    knn_block_scan(p.g, f.blk, starts, p.first, p.last,
+                   [&](int32_t q) { m += knn_d2(p.px, p.py, p.pz, spts + (int64_t)q * 3) <= cap ? 1 : 0; });
+    const int64_t row = perm[j];
+    if (row >= 0 && row < n) counts[row] = m;
+  } else {
+    knn_append_pending(pending, counter, j, n);
+  }
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+radius_count_fallback_kernel(int32_t* __restrict__ counts, const int32_t* __restrict__ pending,
+                             const int32_t* __restrict__ counter, const float* __restrict__ spts,
+                             const int64_t* __restrict__ perm, const int64_t* __restrict__ off, int batch, int64_t n,
+                             float cap) {
+  knn_for_pending(pending, counter, off, batch, n, [&](int64_t j, int, int64_t first, int64_t last) {
+    const float px = spts[j * 3 + 0], py = spts[j * 3 + 1], pz = spts[j * 3 + 2];
+    int m = 0;
+    knn_cloud_scan(first, last, [&](int64_t q) { m += knn_d2(px, py, pz, spts + q * 3) <= cap ? 1 : 0; });
+    m = wave_sum(m);                                           // integers: any order gives the same sum
+    const int64_t row = perm[j];
+    if (knn_lane() == 0 && row >= 0 && row < n) counts[row] = m;
+  });
+}
+
+__global__ void __launch_bounds__(kOutThreads)
+count_mask_kernel(uint8_t* __restrict__ keep, const int32_t* __restrict__ counts, int64_t n, int32_t nb_points) {
+  const int64_t i = (int64_t)blockIdx.x * kOutThreads + threadIdx.x;
+  if (i < n) keep[i] = counts[i] > nb_points ? 1 : 0;
 }
 
 // the sums below are `block_sum` of ragged_common.h, the order of hfl_pair_stats: a thread's rows in ascending order, the
@@ -206,6 +252,38 @@ extern "C" int hfl_knn_mean_dist(float* avg, int32_t* pending, int32_t* counter,
                                                                               grids, cloud_offsets, batch, n);
     HFL_RETURN_LAST_ERROR();
   });
+}
+
+extern "C" int hfl_knn_radius_count(int32_t* counts, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                                    const float* sorted_points, const int64_t* sorted_keys, const int64_t* perm,
+                                    const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                                    const int64_t* cloud_offsets, int64_t n_points, float radius2, int phases,
+                                    hfl_stream_t stream) {
+  if (counts == nullptr || pending == nullptr || counter == nullptr || cell_starts == nullptr || sorted_points == nullptr ||
+      sorted_keys == nullptr || perm == nullptr || grids_host == nullptr || grids == nullptr || cloud_offsets == nullptr)
+    return HFL_EINVAL;
+  if (phases < 1 || phases > HFL_KNN_PHASE_ALL || !knn_cap_ok(radius2)) return HFL_EINVAL;
+  int k_max = 0;
+  if (const int rc = knn_call_check(batch, n_points, n_cells, grids_host, &k_max)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t n = n_points;
+  if (const int rc = knn_launch_starts(cell_starts, counter, sorted_keys, n, n_cells, phases, s)) return rc;
+  if (phases & HFL_KNN_PHASE_QUERY)
+    radius_count_kernel<<<(unsigned)hfl_cdiv(n, kOutThreads), kOutThreads, 0, s>>>(
+        counts, pending, counter, sorted_points, sorted_keys, perm, cell_starts, grids, cloud_offsets, batch, n, radius2);
+  if (phases & HFL_KNN_PHASE_FALLBACK)
+    radius_count_fallback_kernel<<<knn_fallback_blocks(n, s), kOutThreads, 0, s>>>(counts, pending, counter, sorted_points,
+                                                                                   perm, cloud_offsets, batch, n, radius2);
+  HFL_RETURN_LAST_ERROR();
+}
+
+extern "C" int hfl_count_mask(uint8_t* keep, const int32_t* counts, int64_t n_points, int32_t nb_points,
+                              hfl_stream_t stream) {
+  if (keep == nullptr || counts == nullptr || n_points < 1 || nb_points < 0) return HFL_EINVAL;
+  if (n_points > HFL_VOXEL_MAX_POINTS) return HFL_ECAPACITY;
+  count_mask_kernel<<<(unsigned)hfl_cdiv(n_points, kOutThreads), kOutThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      keep, counts, n_points, nb_points);
+  HFL_RETURN_LAST_ERROR();
 }
 
 extern "C" int hfl_outlier_threshold(double* stats, const float* avg, const int64_t* cloud_offsets, int batch,

@@ -37,6 +37,16 @@ k = min(`nb_neighbors`, n):
     value by about 1e-14 of itself and the fp32 result by at most one ulp.  A group with pairs sums to 100 before the
     weighted term and to 200 with it.
 
+Radius and hybrid neighbourhoods (`radius=`): step 1 takes the neighbourhood of `normals.py` with
+the same keyword -- hybrid (`nb_neighbors` in 3..32 and a radius) r2_i = min(k-th smallest d2(i, .), R2) with R2 =
+`global_registration.inlier_d2(radius)`, radius-only (`nb_neighbors=None` and a radius) r2_i = R2 -- and steps 2 to 5 are
+unchanged.  A histogram over a ball of fixed size describes the same patch of a surface in two clouds of different
+density, which one over the k nearest points does not.  In hybrid mode `nb_neighbors` stays in 3..32 (open3d's usual
+`max_nn=100` is not reachable; radius-only is the route to larger neighbourhoods), and a very large radius-only search
+on a large cloud is quadratic work per thread.  `radius=None` is the k-nearest definition with the bits it always had.
+On the device `hfl_fpfh_radius_capped` fills r2 and the proof (radius-only: no scan at all, and no point pending at the
+default cell); `hfl_fpfh_spfh` and `hfl_fpfh_combine` read only those and run unchanged.
+
 Device route (`csrc/fpfh.hip`): `outliers.sorted_batch` unchanged, the normals gathered by its
 permutation, then `hfl_fpfh_radius` (r2 and whether the 3 x 3 x 3 completeness bound proves it; the others from a whole-cloud
 scan, a wave per point), `hfl_fpfh_spfh` (one thread per point re-scans its cells, a wave per unproven point its cloud; 33
@@ -125,11 +135,11 @@ def _d2_rows(a: np.ndarray, s: int, e: int) -> np.ndarray:
     return (dx * dx + dy * dy) + dz * dz                         # fp32 arrays: every operation rounded once
 
 
-def _fpfh_host(a: np.ndarray, nrm: np.ndarray, nb: int):
+def _fpfh_host(a: np.ndarray, nrm: np.ndarray, nb, cap=None):
     """the definition for one (n, 3) fp32 cloud by brute force in row chunks -> (fpfh (n, 33) float32, hist (n, 33) int32,
-    pairs (n,) int32)"""
+    pairs (n,) int32).  `cap`: None or R2 (fp32); `nb` None: radius-only"""
     n = a.shape[0]
-    k = min(nb, n)
+    k = n if nb is None else min(nb, n)
     a64, n64, has = a.astype(np.float64), nrm.astype(np.float64), _has_normal(nrm)
     hist, pairs = np.zeros((n, DIM), np.int32), np.zeros(n, np.int32)
     r2 = np.empty(n, np.float32)
@@ -138,7 +148,12 @@ def _fpfh_host(a: np.ndarray, nrm: np.ndarray, nb: int):
         for s in range(0, n, chunk):
             e = min(n, s + chunk)
             d2 = _d2_rows(a, s, e)
-            r2[s:e] = np.partition(d2, k - 1, axis=1)[:, k - 1]
+            if nb is None:
+                r2[s:e] = cap
+            else:
+                r2[s:e] = np.partition(d2, k - 1, axis=1)[:, k - 1]
+                if cap is not None:
+                    r2[s:e] = np.minimum(r2[s:e], cap)
             near = (d2 <= r2[s:e, None]) & has[s:e, None] & has[None, :]
             near[np.arange(e - s), np.arange(s, e)] = False
             i, j = np.nonzero(near)
@@ -183,14 +198,17 @@ def _checked_normals(normals, sizes):
     return arrays
 
 
-def compute_fpfh_host(clouds: Sequence, normals: Sequence, nb_neighbors: int = 30, *, return_histograms: bool = False):
+def compute_fpfh_host(clouds: Sequence, normals: Sequence, nb_neighbors=30, *, radius=None,
+                      return_histograms: bool = False):
     """The definition of the module docstring in numpy: the route without a GPU and the yardstick of the tests.  Brute
     force, O(n^2): meant for tests and small clouds.  Lists of (n_i, 3) clouds and normals -> list of (n_i, 33) float32
-    arrays; with `return_histograms` also the lists of (n_i, 33) int32 SPFH histograms and (n_i,) int32 pair counts."""
-    nb = _check_neighbours(nb_neighbors)
+    arrays; with `return_histograms` also the lists of (n_i, 33) int32 SPFH histograms and (n_i,) int32 pair counts.
+    `radius`: the hybrid neighbourhood, or, with `nb_neighbors=None`, the radius-only one."""
+    nb, r = outliers.check_neighbourhood(nb_neighbors, radius, _check_neighbours)
+    cap = None if r is None else outliers.radius2(r)
     arrays = outliers._checked_arrays(clouds)
     nrms = _checked_normals(normals, [a.shape[0] for a in arrays])
-    parts = [_fpfh_host(a, nr, nb) for a, nr in zip(arrays, nrms)]
+    parts = [_fpfh_host(a, nr, nb, cap) for a, nr in zip(arrays, nrms)]
     return ragged.results([p[0] for p in parts], [p[1] for p in parts] if return_histograms else None,
                           [p[2] for p in parts] if return_histograms else None)
 
@@ -207,13 +225,15 @@ def _normal_tensors(normals, sizes):
     return ts
 
 
-def compute_fpfh_packed(packed, normals: torch.Tensor, nb: int, cell=None):
+def compute_fpfh_packed(packed, normals: torch.Tensor, nb, cell=None, radius=None):
     """the descriptors of a packed batch and its (P, 3) fp32 device normals -> (fpfh (P, 33) fp32, hist (P, 33) int32, pairs
-    (P,) int32, all in INPUT order, pending (1,) int32), everything on the device"""
-    table, sorted_pts, sorted_keys, perm = outliers.sorted_batch(packed, nb, cell)
+    (P,) int32, all in INPUT order, pending (1,) int32), everything on the device; `nb` and `radius` as
+    `outliers.check_neighbourhood` returns them"""
+    table, sorted_pts, sorted_keys, perm = outliers.sorted_batch(packed, nb, cell, radius)
     sorted_nrm = ops.voxel_gather_rows(normals, perm)
     ws = ops.FpfhWorkspace(int(sorted_pts.shape[0]), table.cells, sorted_pts.device)
-    pending = ops.fpfh_radius(ws, sorted_pts, sorted_keys, packed.off, table)
+    pending = ops.fpfh_radius(ws, sorted_pts, sorted_keys, packed.off, table,
+                              radius2=None if radius is None else outliers.radius2(radius), radius_only=nb is None)
     ops.fpfh_spfh(ws, sorted_pts, sorted_nrm, sorted_keys, packed.off, table, THETA_TABLE)
     fpfh = ops.fpfh_combine(ws, sorted_pts, sorted_keys, perm, packed.off, table)
     hist, pairs = torch.empty_like(ws.hist), torch.empty_like(ws.pairs)
@@ -222,16 +242,18 @@ def compute_fpfh_packed(packed, normals: torch.Tensor, nb: int, cell=None):
     return fpfh, hist, pairs, pending
 
 
-def compute_fpfh(clouds: Sequence, normals: Sequence, nb_neighbors: int = 30, *, device='cuda', cell_size=None,
+def compute_fpfh(clouds: Sequence, normals: Sequence, nb_neighbors=30, *, radius=None, device='cuda', cell_size=None,
                  return_histograms: bool = False, return_pending: bool = False):
     """`compute_fpfh_host` on the device: lists of raw (n_i, 3) clouds and their normals (numpy / torch, host or device; for
     instance what `estimate_normals` returned, which never leaves the device) -> list of (n_i, 33) float32 device tensors,
     the descriptors of the module docstring.  `return_histograms`: also the lists of (n_i, 33) int32 SPFH histograms and
     (n_i,) int32 pair counts, equal to the numpy route's; `return_pending`: the number of points of the batch that the
     whole-cloud scan finished (a debug counter).  `cell_size` sets the edge of the search grid's cells: it changes no
-    histogram, and a descriptor by at most an fp32 ulp.  `ValueError` for a bad parameter, an empty cloud or normals of the
-    wrong shape (before the device is touched) and, naming the cloud, for a coordinate that is not finite."""
-    nb = _check_neighbours(nb_neighbors)
+    histogram, and a descriptor by at most an fp32 ulp.  `radius`: the hybrid neighbourhood of the module docstring, or,
+    with `nb_neighbors=None`, the radius-only one (no point pending at the default cell).  `ValueError` for a bad
+    parameter, an empty cloud or normals of the wrong shape (before the device is touched) and, naming the cloud, for a
+    coordinate that is not finite."""
+    nb, r = outliers.check_neighbourhood(nb_neighbors, radius, _check_neighbours)
     cell = None if cell_size is None else ragged.check_positive('cell_size', cell_size)
     nrm_ts = _normal_tensors(normals, [int(t.shape[0]) for t in ragged.as_tensors(clouds)])
     with ragged.intake(clouds, device) as packed:
@@ -239,7 +261,7 @@ def compute_fpfh(clouds: Sequence, normals: Sequence, nb_neighbors: int = 30, *,
             return ragged.results([], [] if return_histograms else None, [] if return_histograms else None,
                                   0 if return_pending else None)
         nrm = ragged.upload(nrm_ts, packed.pts.device).pts
-        fpfh, hist, pairs, pending = compute_fpfh_packed(packed, nrm, nb, cell)
+        fpfh, hist, pairs, pending = compute_fpfh_packed(packed, nrm, nb, cell, r)
         return ragged.results(packed.split(fpfh), packed.split(hist) if return_histograms else None,
                               packed.split(pairs) if return_histograms else None,
                               int(pending.item()) if return_pending else None)

@@ -353,10 +353,21 @@ def _coarse_estimator(estimator, device_route, what, ransac_distance, refine_ite
     return lambda source, target, correspondences: run(source, target, correspondences, **kw)
 
 
+def _with_radii(normals_of, fpfh_of, nb, normal_radius, feature_radius, what):
+    """`normals_of(clouds, nb)` and `fpfh_of(clouds, normals, nb)` with the radii of `global_registration` and
+    `rerank_candidates` bound: None leaves a step at its k nearest points; `nb` None is radius-only and needs both"""
+    if nb is None and (normal_radius is None or feature_radius is None):
+        raise ValueError('%s: nb_neighbors=None is the radius-only neighbourhood and needs normal_radius and feature_radius'
+                         % what)
+    return (normals_of if normal_radius is None else lambda clouds, k: normals_of(clouds, k, radius=normal_radius),
+            fpfh_of if feature_radius is None else lambda clouds, normals, k: fpfh_of(clouds, normals, k, radius=feature_radius))
+
+
 def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                         estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                         min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                        estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10, covariance_epsilon=1e-3):
+                        estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10, covariance_epsilon=1e-3,
+                        normal_radius=None, feature_radius=None):
     """From two lists of raw (N_i, 3) float32 GPU clouds to refined 6-DoF poses, source frame -> target frame, in one call:
     `estimate_normals` -> `compute_fpfh` -> `feature_correspondences` (`mutual`) -> `correspondence_pairs` ->
     `ransac_registration` (`ransac_distance` and its options) -> `icp_refine(init=...)` (`icp_distance`, `estimation`, its
@@ -364,12 +375,16 @@ def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_
     `covariance_epsilon`).  -> `(RansacResult, RegistrationResult)`.  A pair
     that ends NO_HYPOTHESIS enters the ICP at the identity.  `estimator='consensus'` takes the coarse pose from
     `consensus_registration` (`consensus_distance`, `seeds`, `consensus_size`; `ransac_distance`, `refine_iterations` and
-    `min_correspondences` as before) instead; `hypotheses`, `seed` and `edge_length_ratio` are then unused."""
+    `min_correspondences` as before) instead; `hypotheses`, `seed` and `edge_length_ratio` are then unused.
+    `normal_radius` and `feature_radius` are the `radius` of `estimate_normals` and of `compute_fpfh` (hybrid
+    neighbourhoods); `nb_neighbors=None` is radius-only and needs both."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
     coarse = _coarse_estimator(estimator, True, 'global_registration', ransac_distance, refine_iterations, min_correspondences,
                                hypotheses, seed, edge_length_ratio, consensus_distance, seeds, consensus_size)
-    return _global(source, target, estimate_normals, compute_fpfh, feature_correspondences, correspondence_pairs, coarse,
+    normals_of, fpfh_of = _with_radii(estimate_normals, compute_fpfh, nb_neighbors, normal_radius, feature_radius,
+                                      'global_registration')
+    return _global(source, target, normals_of, fpfh_of, feature_correspondences, correspondence_pairs, coarse,
                    reg.icp_refine, True, nb_neighbors, mutual, icp_distance, estimation, min_correspondences, max_iterations,
                    relative_fitness, relative_rmse, covariance_epsilon)
 
@@ -569,13 +584,15 @@ def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ra
                              estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9,
                              refine_iterations=3, min_correspondences=3, max_iterations=30, relative_fitness=1e-6,
                              relative_rmse=1e-6, estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                             covariance_epsilon=1e-3):
+                             covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
     """`global_registration` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
     coarse = _coarse_estimator(estimator, False, 'global_registration', ransac_distance, refine_iterations,
                                min_correspondences, hypotheses, seed, edge_length_ratio, consensus_distance, seeds,
                                consensus_size)
-    return _global(source, target, estimate_normals_host, compute_fpfh_host, feature_correspondences_host,
+    normals_of, fpfh_of = _with_radii(estimate_normals_host, compute_fpfh_host, nb_neighbors, normal_radius, feature_radius,
+                                      'global_registration')
+    return _global(source, target, normals_of, fpfh_of, feature_correspondences_host,
                    correspondence_pairs_host, coarse, reg.icp_refine_host, False, nb_neighbors, mutual, icp_distance,
                    estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse, covariance_epsilon)

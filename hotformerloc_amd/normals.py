@@ -29,6 +29,25 @@ Definition, for one cloud of n finite fp32 points, `nb_neighbors` an integer in 
     n_z == 0, n_y > 0, or, if that is 0 too, n_x > 0.
  7. Outputs, rounded once to fp32: normals (n, 3), curvature (n,); counts (n,) int32.
 
+Radius and hybrid neighbourhoods (`radius=`; after open3d's `KDTreeSearchParamHybrid(radius,
+max_nn)` and `KDTreeSearchParamRadius`, parity again not claimed).  A k-nearest neighbourhood has no physical size: it
+shrinks where a cloud is dense and grows where it is sparse, so two clouds of different density describe different patches
+of one surface.  `radius` is a float, positive and finite in fp32, and R2 = `global_registration.inlier_d2(radius)`, the
+largest fp32 d2 with sqrtf(d2) <= float32(radius): "within the radius" means exactly what "within
+`max_correspondence_distance`" means to ICP and RANSAC.  Only step 2 changes:
+
+ * **Hybrid** (`nb_neighbors` in 3..32 and a radius): r2_i = min(k-th smallest d2(i, .), R2), N(i) = { j : d2(i, j) <=
+   r2_i }, ties included as before.  |N(i)| may now lie below k, down to 1 (the point itself, which then has no normal by
+   step 5).  `nb_neighbors` stays in 3..32 -- the sorted register list of the search is 32 floats at the most -- so open3d's
+   usual `max_nn=100` is not reachable; radius-only is the route to larger neighbourhoods.
+ * **Radius-only** (`nb_neighbors=None` and a radius): r2_i = R2, that is hybrid with k = n.  |N(i)| has no cap; counts
+   stay int32.  Every point of 27 grid cells of edge >= radius is visited per query: a very large radius on a large cloud
+   is quadratic work per thread.
+ * `radius=None` is the k-nearest definition above with the bits it always had.
+
+Steps 3 to 7 are unchanged.  On the device the grid takes the radius into account (`outliers.grid_layout`): at the default
+cell of a radius-only call no point is left to the whole-cloud scan, and there is no list and no first scan.
+
 Device route (`csrc/normals.hip`): `outliers.sorted_batch` unchanged (bounds, the finite check with
 its one host read, grid layout, keys, sort, gather), then `hfl_knn_normals`: the cell-start table; one thread per point
 scanning the 3 x 3 x 3 cells round its own twice -- first for r2 with the sorted register list and the completeness bound
@@ -137,11 +156,11 @@ def _signed(normal, pts, view):
     return np.where(flip[:, None], -normal, normal)
 
 
-def _normals_host(a: np.ndarray, nb: int, view):
+def _normals_host(a: np.ndarray, nb, view, cap=None):
     """steps 1 to 6 for one (n, 3) fp32 cloud by brute force in row chunks -> (normals, curvature, both float64: step 7
-    rounds them; counts int32; eigenvalues (n, 3) float64)"""
+    rounds them; counts int32; eigenvalues (n, 3) float64).  `cap`: None or R2 (fp32); `nb` None: radius-only"""
     n = a.shape[0]
-    k = min(nb, n)
+    k = n if nb is None else min(nb, n)
     x, y, z = a[:, 0], a[:, 1], a[:, 2]
     a64 = a.astype(np.float64)
     s1, s2, counts = np.empty((n, 3), np.float64), np.empty((n, 6), np.float64), np.empty(n, np.int32)
@@ -151,7 +170,12 @@ def _normals_host(a: np.ndarray, nb: int, view):
             e = min(n, s + chunk)
             dx, dy, dz = x[s:e, None] - x[None, :], y[s:e, None] - y[None, :], z[s:e, None] - z[None, :]
             d2 = (dx * dx + dy * dy) + dz * dz                   # fp32 arrays: every operation rounded once
-            r2 = np.partition(d2, k - 1, axis=1)[:, k - 1]
+            if nb is None:
+                r2 = np.full(e - s, cap, np.float32)
+            else:
+                r2 = np.partition(d2, k - 1, axis=1)[:, k - 1]
+                if cap is not None:
+                    r2 = np.minimum(r2, cap)
             near = d2 <= r2[:, None]
             counts[s:e] = near.sum(1)
             diff = np.where(near[:, :, None], a64[None, :, :] - a64[s:e, None, :], 0.0)
@@ -162,18 +186,19 @@ def _normals_host(a: np.ndarray, nb: int, view):
     return _signed(normal, a, view), curvature, counts, lam
 
 
-def estimate_normals_host(clouds: Sequence, nb_neighbors: int = 30, *, viewpoint=None, return_curvature: bool = False,
+def estimate_normals_host(clouds: Sequence, nb_neighbors=30, *, radius=None, viewpoint=None, return_curvature: bool = False,
                           return_counts: bool = False, return_eigenvalues: bool = False):
     """The definition of the module docstring in numpy, fp32 for the distances and float64 for the rest: the route without
     a GPU and the yardstick of the tests.  Brute force, O(n^2): meant for tests and small clouds.  List of (n_i, 3) clouds
     -> list of (n_i, 3) float32 unit normals, zero where a point has none; with `return_curvature` also the (n_i,) float32
     surface variation, with `return_counts` the (n_i,) int32 neighbourhood sizes, with `return_eigenvalues` the (n_i, 3)
     float64 eigenvalues in ascending order (NaN where fewer than three neighbours), by which a caller judges how well a
-    normal is determined."""
-    nb = _check_neighbours(nb_neighbors)
+    normal is determined.  `radius`: the hybrid neighbourhood, or, with `nb_neighbors=None`, the radius-only one."""
+    nb, r = outliers.check_neighbourhood(nb_neighbors, radius, _check_neighbours)
+    cap = None if r is None else outliers.radius2(r)
     arrays = outliers._checked_arrays(clouds)
     views = _check_viewpoint(viewpoint, len(arrays))
-    parts = [_normals_host(a, nb, None if views is None else views[i]) for i, a in enumerate(arrays)]
+    parts = [_normals_host(a, nb, None if views is None else views[i], cap) for i, a in enumerate(arrays)]
     return ragged.results([p[0].astype(np.float32) for p in parts],
                           [p[1].astype(np.float32) for p in parts] if return_curvature else None,
                           [p[2] for p in parts] if return_counts else None,
@@ -181,15 +206,17 @@ def estimate_normals_host(clouds: Sequence, nb_neighbors: int = 30, *, viewpoint
 
 
 # ------------------------------------------------------------------------------------------------ device route
-def estimate_normals_packed(packed, nb: int, views=None, cell=None):
+def estimate_normals_packed(packed, nb, views=None, cell=None, radius=None):
     """the estimate on a packed batch -> (normals (P, 3) fp32, curvature (P,) fp32, counts (P,) int32, pending (1,) int32),
-    everything on the device; `views` None or (B, 3) float64 numpy"""
-    table, sorted_pts, sorted_keys, perm = outliers.sorted_batch(packed, nb, cell)
+    everything on the device; `views` None or (B, 3) float64 numpy; `nb` and `radius` as `outliers.check_neighbourhood`
+    returns them"""
+    table, sorted_pts, sorted_keys, perm = outliers.sorted_batch(packed, nb, cell, radius)
     dev_views = None if views is None else torch.from_numpy(views).to(packed.pts.device)
-    return ops.knn_normals(sorted_pts, sorted_keys, perm, packed.off, table, dev_views)
+    return ops.knn_normals(sorted_pts, sorted_keys, perm, packed.off, table, dev_views,
+                           radius2=None if radius is None else outliers.radius2(radius), radius_only=nb is None)
 
 
-def estimate_normals(clouds: Sequence, nb_neighbors: int = 30, *, viewpoint=None, device='cuda', cell_size=None,
+def estimate_normals(clouds: Sequence, nb_neighbors=30, *, radius=None, viewpoint=None, device='cuda', cell_size=None,
                      return_curvature: bool = False, return_counts: bool = False, return_pending: bool = False):
     """`estimate_normals_host` on the device: list of raw (n_i, 3) clouds (numpy / torch, host or device) -> list of
     (n_i, 3) float32 device tensors, the unit normals of the module docstring, zero where a point has none.
@@ -197,16 +224,18 @@ def estimate_normals(clouds: Sequence, nb_neighbors: int = 30, *, viewpoint=None
     upward.  `return_curvature`: also the (n_i,) float32 surface variation; `return_counts`: the (n_i,) int32 neighbourhood
     sizes, equal to the numpy route's; `return_pending`: the number of points of the batch that the whole-cloud scan
     finished (a debug counter).  `cell_size` sets the edge of the search grid's cells: it changes no count and no zero
-    normal, and the rest only to rounding.  `ValueError` for a bad parameter or an empty cloud (before the device is
-    touched) and, naming the cloud, for a coordinate that is not finite (before any kernel of the estimate runs)."""
-    nb = _check_neighbours(nb_neighbors)
+    normal, and the rest only to rounding.  `radius`: the hybrid neighbourhood of the module docstring, or, with
+    `nb_neighbors=None`, the radius-only one (no point pending at the default cell).  `ValueError` for a bad parameter or
+    an empty cloud (before the device is touched) and, naming the cloud, for a coordinate that is not finite (before any
+    kernel of the estimate runs)."""
+    nb, r = outliers.check_neighbourhood(nb_neighbors, radius, _check_neighbours)
     cell = None if cell_size is None else ragged.check_positive('cell_size', cell_size)
     views = _check_viewpoint(viewpoint, len(clouds))
     with ragged.intake(clouds, device) as packed:
         if packed is None:
             return ragged.results([], [] if return_curvature else None, [] if return_counts else None,
                                   0 if return_pending else None)
-        normals, curvature, counts, pending = estimate_normals_packed(packed, nb, views, cell)
+        normals, curvature, counts, pending = estimate_normals_packed(packed, nb, views, cell, r)
         return ragged.results(packed.split(normals), packed.split(curvature) if return_curvature else None,
                               packed.split(counts) if return_counts else None,
                               int(pending.item()) if return_pending else None)

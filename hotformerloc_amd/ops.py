@@ -2595,12 +2595,23 @@ def knn_mean_dist(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: 
     return avg, ws.counter
 
 
+def _radius2(what: str, radius2) -> float:
+    """R2 of a radius or hybrid search as the float the C-ABI takes: a squared distance or +inf, as fp32 holds it"""
+    r2 = float(np.float32(radius2))
+    if not r2 >= 0.0:
+        raise ValueError('%s: radius2 must be a squared distance >= 0 (+inf allowed), got %r' % (what, radius2))
+    return r2
+
+
 def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
                 table: KnnGridTable, viewpoints: torch.Tensor = None, phases: int = KNN_PHASE_ALL,
-                workspace: KnnWorkspace = None):
+                workspace: KnnWorkspace = None, radius2=None, radius_only: bool = False):
     """`hfl_knn_normals`: the arguments of `knn_mean_dist` -> (normals (P, 3) fp32, curvature (P,) fp32, counts (P,) int32,
     all in INPUT order, pending (1,) int32 on the GPU).  `viewpoints`: (B, 3) float64 on the GPU, one per cloud, or None for
-    the upward rule.  Nothing is read back."""
+    the upward rule.  With `radius2` (R2 as fp32 holds it) `hfl_knn_normals_radius`: r2 = min(k-th smallest, R2), or, with
+    `radius_only`, r2 = R2 and the table's k unread.  Nothing is read back."""
+    if radius_only and radius2 is None:
+        raise ValueError('knn_normals: radius_only needs radius2')
     n, ws = _knn_sorted_check('knn_normals', table, sorted_points, offsets, workspace, 'keys and permutation', sorted_keys,
                               perm)
     if viewpoints is not None:
@@ -2610,13 +2621,41 @@ def knn_normals(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: to
     normals = torch.empty((n, 3), dtype=torch.float32, device=sorted_points.device)
     curvature = torch.empty(n, dtype=torch.float32, device=sorted_points.device)
     counts = torch.empty(n, dtype=torch.int32, device=sorted_points.device)
-    check(_native.load().hfl_knn_normals(normals.data_ptr(), curvature.data_ptr(), counts.data_ptr(), ws.pending.data_ptr(),
-                                         ws.counter.data_ptr(), ws.starts.data_ptr(), sorted_points.data_ptr(),
-                                         sorted_keys.data_ptr(), perm.data_ptr(), table.host.ctypes.data,
-                                         table.device.data_ptr(), table.batch, table.cells, offsets.data_ptr(), n,
-                                         viewpoints.data_ptr() if viewpoints is not None else None, int(phases), _stream()),
-          'hfl_knn_normals')
+    args = (normals.data_ptr(), curvature.data_ptr(), counts.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(),
+            ws.starts.data_ptr(), sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(), table.host.ctypes.data,
+            table.device.data_ptr(), table.batch, table.cells, offsets.data_ptr(), n,
+            viewpoints.data_ptr() if viewpoints is not None else None)
+    if radius2 is None:
+        check(_native.load().hfl_knn_normals(*args, int(phases), _stream()), 'hfl_knn_normals')
+    else:
+        check(_native.load().hfl_knn_normals_radius(*args, _radius2('knn_normals', radius2), int(bool(radius_only)),
+                                                    int(phases), _stream()), 'hfl_knn_normals_radius')
     return normals, curvature, counts, ws.counter
+
+
+def knn_radius_count(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
+                     table: KnnGridTable, radius2, phases: int = KNN_PHASE_ALL, workspace: KnnWorkspace = None):
+    """`hfl_knn_radius_count`: the arguments of `knn_mean_dist` and R2 -> (counts (P,) int32 in INPUT order: the points of
+    the own cloud with d2 <= R2, the point itself included; pending (1,) int32 on the GPU).  Nothing is read back."""
+    n, ws = _knn_sorted_check('knn_radius_count', table, sorted_points, offsets, workspace, 'keys and permutation',
+                              sorted_keys, perm)
+    counts = torch.empty(n, dtype=torch.int32, device=sorted_points.device)
+    check(_native.load().hfl_knn_radius_count(counts.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(),
+                                              ws.starts.data_ptr(), sorted_points.data_ptr(), sorted_keys.data_ptr(),
+                                              perm.data_ptr(), table.host.ctypes.data, table.device.data_ptr(), table.batch,
+                                              table.cells, offsets.data_ptr(), n, _radius2('knn_radius_count', radius2),
+                                              int(phases), _stream()), 'hfl_knn_radius_count')
+    return counts, ws.counter
+
+
+def count_mask(counts: torch.Tensor, nb_points: int):
+    """`hfl_count_mask`: counts (P,) int32 on the GPU -> keep (P,) uint8, 1 where counts > nb_points."""
+    _dev(counts)
+    n = int(counts.shape[0])
+    _vector_check('count_mask', counts, torch.int32, n, 'counts')
+    keep = torch.empty(n, dtype=torch.uint8, device=counts.device)
+    check(_native.load().hfl_count_mask(keep.data_ptr(), counts.data_ptr(), n, int(nb_points), _stream()), 'hfl_count_mask')
+    return keep
 
 
 FPFH_DIM = 33                          # three groups of 11 bins
@@ -2644,14 +2683,22 @@ def _fpfh_check(what: str, ws: FpfhWorkspace, table: KnnGridTable, sorted_points
 
 
 def fpfh_radius(ws: FpfhWorkspace, sorted_points: torch.Tensor, sorted_keys: torch.Tensor, offsets: torch.Tensor,
-                table: KnnGridTable):
+                table: KnnGridTable, radius2=None, radius_only: bool = False):
     """`hfl_fpfh_radius`: the sorted batch of `knn_mean_dist` -> ws.r2, ws.proven and the pending list filled; returns the
-    (1,) int32 counter of points the whole-cloud scan finished.  Nothing is read back."""
+    (1,) int32 counter of points the whole-cloud scan finished.  With `radius2` (R2 as fp32 holds it)
+    `hfl_fpfh_radius_capped`: r2 = min(k-th smallest, R2), or, with `radius_only`, r2 = R2 and no scan.  Nothing is read
+    back."""
+    if radius_only and radius2 is None:
+        raise ValueError('fpfh_radius: radius_only needs radius2')
     n = _fpfh_check('fpfh_radius', ws, table, sorted_points, offsets, sorted_keys)
-    check(_native.load().hfl_fpfh_radius(ws.r2.data_ptr(), ws.proven.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(),
-                                         ws.starts.data_ptr(), sorted_points.data_ptr(), sorted_keys.data_ptr(),
-                                         table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
-                                         offsets.data_ptr(), n, _stream()), 'hfl_fpfh_radius')
+    args = (ws.r2.data_ptr(), ws.proven.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
+            sorted_points.data_ptr(), sorted_keys.data_ptr(), table.host.ctypes.data, table.device.data_ptr(), table.batch,
+            table.cells, offsets.data_ptr(), n)
+    if radius2 is None:
+        check(_native.load().hfl_fpfh_radius(*args, _stream()), 'hfl_fpfh_radius')
+    else:
+        check(_native.load().hfl_fpfh_radius_capped(*args, _radius2('fpfh_radius', radius2), int(bool(radius_only)),
+                                                    _stream()), 'hfl_fpfh_radius_capped')
     return ws.counter
 
 

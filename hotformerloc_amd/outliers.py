@@ -48,6 +48,26 @@ filter exists to find, among others -- are finished by a whole-cloud scan, a wav
 cloud is one cell the first scan is the brute force.  Then `hfl_outlier_threshold`, `hfl_outlier_mask`, and the compaction
 of `ragged.compact`: `torch.nonzero`, `hfl_voxel_gather_rows`, one `searchsorted` on the host offsets.
 
+Radius outlier removal, after open3d's `remove_radius_outlier`.  `radius` is a float, positive and
+finite in fp32; R2 = `global_registration.inlier_d2(radius)` is the largest fp32 d2 whose correctly rounded fp32 root is <=
+float32(radius), so "within the radius" means what "within `max_correspondence_distance`" means to ICP and RANSAC.
+counts[i] = |{ j : d2(i, j) <= R2 }| with the d2 of step 1, the point itself included (int32, so always >= 1);
+`remove_radius_outliers` keeps row i when counts[i] > `nb_points` (an integer >= 0), rows in input order.  Only integers
+are written, so the device and the numpy route agree to the bit.  Device route: `sorted_batch` with the radius,
+`hfl_knn_radius_count` (one pass over the 3 x 3 x 3 block, no list; the whole-cloud scan for a point whose block is not
+proven to hold the ball), `hfl_count_mask`, `ragged.compact`.  A radius-only search visits every point of 27 cells of
+edge >= radius per query: **a very large radius on a large cloud is quadratic work per thread**.
+
+The search grid with a radius (`grid_layout(radius=...)`).  `knn_block_bound` proves a point resolved when r2 lies below
+((gap - margin) (1 - 2^-20))^2, gap the fp32 distance to the nearest face of the block with cells behind it.  A point of
+cell ix has a >= ix cell (1 - 2^-24) along an axis (the rounded division that assigned it) and the face lies at
+fl((ix - 1) cell), so gap >= cell (1 - nx 2^-23); the margin is 2^-20 nx cell; three roundings and the shrink take less
+than 2^-19 more.  With nmax the largest of nx, ny, nz the root of the bound is therefore above cell (1 - `RADIUS_LOSS`),
+`RADIUS_LOSS` = 2^-20 (1.25 nmax + 4), and R2 <= radius^2 (1 + 2^-23): the **radius cell** radius / (1 - RADIUS_LOSS)
+(doubled first while the loss is not below 1 / 2) leaves NO point pending, and a larger cell (the budget doubling) keeps
+that, because nmax only falls.  Radius-only calls take the radius cell by default, hybrid calls the smaller of it and the
+density cell; `cell_size=` still overrides, and still changes no count.
+
 Batch limits as in `ragged.py`."""
 
 import math
@@ -70,6 +90,27 @@ def _check_neighbours(nb_neighbors) -> int:
             not 1 <= int(nb_neighbors) <= MAX_NEIGHBOURS:
         raise ValueError('nb_neighbors must be an integer in 1..%d, got %r' % (MAX_NEIGHBOURS, nb_neighbors))
     return int(nb_neighbors)
+
+
+def check_radius(radius, name: str = 'radius') -> float:
+    """float(radius), positive and finite, also once rounded to float32"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError('%s must be a positive, finite number, got %r' % (name, radius))
+    return ragged.check_positive(name, radius, fp32=True)
+
+
+def radius2(radius: float) -> np.float32:
+    """R2 of the module docstring for a checked radius"""
+    from .global_registration import inlier_d2       # that module imports nothing of this one
+    return inlier_d2(radius)
+
+
+def check_neighbourhood(nb_neighbors, radius, check_nb):
+    """The (nb_neighbors, radius) pair of `estimate_normals` and `compute_fpfh` -> (nb or None, radius or None): k nearest
+    (nb, None), hybrid (nb, radius), radius-only (None, radius); `check_nb` checks an integer nb_neighbors."""
+    if nb_neighbors is None and radius is None:
+        raise ValueError('nb_neighbors=None is the radius-only neighbourhood and needs a radius')
+    return (None if nb_neighbors is None else check_nb(nb_neighbors)), (None if radius is None else check_radius(radius))
 
 
 def _nonfinite_error(i: int):
@@ -144,6 +185,43 @@ def remove_outliers_host(clouds: Sequence, nb_neighbors: int = 20, std_ratio: fl
                           [dict(mean=s[0], std=s[1], threshold=s[2], n_valid=s[3]) for s in stats] if return_stats else None)
 
 
+def _radius_counts_host(a: np.ndarray, r2) -> np.ndarray:
+    """counts of the module docstring for one (n, 3) fp32 cloud by brute force in row chunks -> (n,) int32"""
+    n = a.shape[0]
+    x, y, z = a[:, 0], a[:, 1], a[:, 2]
+    out = np.empty(n, dtype=np.int32)
+    chunk = max(1, (1 << 23) // n)
+    with np.errstate(over='ignore', invalid='ignore'):
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
+            dx, dy, dz = x[s:e, None] - x[None, :], y[s:e, None] - y[None, :], z[s:e, None] - z[None, :]
+            out[s:e] = (((dx * dx + dy * dy) + dz * dz) <= r2).sum(1)
+    return out
+
+
+def _check_nb_points(nb_points) -> int:
+    if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or not 0 <= int(nb_points) < 2 ** 31:
+        raise ValueError('nb_points must be an integer >= 0, got %r' % (nb_points,))
+    return int(nb_points)
+
+
+def radius_neighbour_counts_host(clouds: Sequence, radius: float) -> List[np.ndarray]:
+    """The radius counts of the module docstring in numpy fp32: per cloud the (n_i,) int32 number of points of the cloud
+    within `radius` of each point, the point itself included.  Brute force, O(n^2): meant for tests and small clouds."""
+    r2 = radius2(check_radius(radius))
+    return [_radius_counts_host(a, r2) for a in _checked_arrays(clouds)]
+
+
+def remove_radius_outliers_host(clouds: Sequence, nb_points: int, radius: float, *, return_mask: bool = False):
+    """Radius outlier removal in numpy: list of (n_i, 3) clouds -> list of (k_i, 3) float32 arrays, the rows with more than
+    `nb_points` points of the cloud within `radius` (themselves included) in input order (k_i may be 0); with `return_mask`
+    also the (n_i,) bool masks."""
+    nb, r2 = _check_nb_points(nb_points), radius2(check_radius(radius))
+    arrays = _checked_arrays(clouds)
+    masks = [_radius_counts_host(a, r2) > nb for a in arrays]
+    return ragged.results([a[m] for a, m in zip(arrays, masks)], masks if return_mask else None)
+
+
 def trim_radius_host(clouds: Sequence, radius_max: float = 30.0, *, return_mask: bool = False):
     """The radius trim in numpy float64 -> list of (k_i, 3) float32 arrays, the rows with sqrt(x x + y y) <= radius_max in
     input order (k_i may be 0); with `return_mask` also the (n_i,) bool masks."""
@@ -159,10 +237,30 @@ def _grid_dims(extent: np.ndarray, cell: float):
     return np.floor(extent / cell).astype(np.int64) + 1
 
 
-def grid_layout(lo_hi: np.ndarray, sizes, nb: int, cell_size=None, budget_bytes: int = CELL_BUDGET_BYTES) -> np.ndarray:
+def radius_loss(extent: np.ndarray, cell: float) -> float:
+    """`RADIUS_LOSS` of the module docstring: the share of `cell` by which the root of `knn_block_bound` may lie below it"""
+    return 2.0 ** -20 * (1.25 * float(_grid_dims(extent, cell).max()) + 4.0)
+
+
+def radius_cell(extent: np.ndarray, radius: float) -> float:
+    """the radius cell of the module docstring, as a float that fp32 holds: no point of a grid of this cell, or of a larger
+    one, is pending in a search within `radius`"""
+    cell = float(radius)
+    while not radius_loss(extent, cell) < 0.5:
+        cell *= 2.0
+    cell = max(cell, float(radius) / (1.0 - radius_loss(extent, cell)))
+    as32 = _F(min(cell, 1e30))
+    return float(as32 if float(as32) >= cell else np.nextafter(as32, _F(np.inf)))
+
+
+def grid_layout(lo_hi: np.ndarray, sizes, nb, cell_size=None, budget_bytes: int = CELL_BUDGET_BYTES, radius=None) -> np.ndarray:
     """The search grids of a batch from the fp32 bounds (B, 6) and the cloud sizes -> `ops.KNN_GRID_DTYPE` rows.  The
-    default cell is the smallest at which a cloud has at most n / `POINTS_PER_CELL` cells; any cell, the caller's included,
-    is doubled until the cloud's cells fit its share of `budget_bytes`.  The grid only decides the speed."""
+    default cell is the smallest at which a cloud has at most n / `POINTS_PER_CELL` cells; with a `radius`, the smaller of
+    that and `radius_cell`, and for a radius-only search (`nb` None, the rows' k then unread) the radius cell.  Any cell,
+    the caller's included, is doubled until the cloud's cells fit its share of `budget_bytes`.  The grid only decides the
+    speed."""
+    if nb is None and radius is None:
+        raise ValueError('grid_layout: a number of neighbours, a radius, or both')
     batch = len(sizes)
     share = max(int(budget_bytes) // 4 // batch - 1, 1)
     grids = np.zeros(batch, dtype=np.dtype(ops.KNN_GRID_DTYPE))
@@ -175,6 +273,8 @@ def grid_layout(lo_hi: np.ndarray, sizes, nb: int, cell_size=None, budget_bytes:
             cell = float(cell_size)
         elif not widest > 0.0:
             cell = 1.0
+        elif nb is None:
+            cell = radius_cell(extent, radius)
         else:
             want = max(min(n / POINTS_PER_CELL, share), 1.0)
             small, large = widest * 2.0 ** -24, widest * 2.0             # bisect the monotone cell count in log space
@@ -184,14 +284,14 @@ def grid_layout(lo_hi: np.ndarray, sizes, nb: int, cell_size=None, budget_bytes:
                     large = mid
                 else:
                     small = mid
-            cell = large
+            cell = large if radius is None else min(large, radius_cell(extent, radius))
         cell = float(_F(min(max(cell, 1e-30), 1e30)))
         while float(np.prod(_grid_dims(extent, cell).astype(np.float64))) > share:
             cell = float(_F(cell * 2.0))
         nx, ny, nz = (int(d) for d in _grid_dims(extent, cell))
         margin = [float(_F(FACE_MARGIN * d * cell)) for d in (nx, ny, nz)]
-        grids[b] = (lo_hi[b, 0], lo_hi[b, 1], lo_hi[b, 2], cell, margin[0], margin[1], margin[2], min(nb, n), nx, ny, nz, 0,
-                    base)
+        grids[b] = (lo_hi[b, 0], lo_hi[b, 1], lo_hi[b, 2], cell, margin[0], margin[1], margin[2],
+                    min(MAX_NEIGHBOURS if nb is None else nb, n), nx, ny, nz, 0, base)
         base += nx * ny * nz
     return grids
 
@@ -202,9 +302,9 @@ def check_params(nb_neighbors: int = 20, std_ratio: float = 3.0, cell_size=None)
             None if cell_size is None else ragged.check_positive('cell_size', cell_size))
 
 
-def sorted_batch(packed, nb: int, cell_size=None):
-    """bounds and the finite check (the one host read before the search), the grids, keys, sort, gather -> (table, the points
-    cell by cell, their ascending keys, the sort's permutation)"""
+def sorted_batch(packed, nb, cell_size=None, radius=None):
+    """bounds and the finite check (the one host read before the search), the grids (`grid_layout` with `nb`, `cell_size`
+    and `radius`), keys, sort, gather -> (table, the points cell by cell, their ascending keys, the sort's permutation)"""
     pts, off, batch = packed.pts, packed.off, packed.batch
     bounds, flags = ops.voxel_bounds(pts, off), ops.cloud_nonfinite(pts, off)
     host = torch.cat([bounds.reshape(-1), flags]).cpu().numpy()
@@ -212,7 +312,7 @@ def sorted_batch(packed, nb: int, cell_size=None):
     for i in range(batch):
         if host[6 * batch + i] or not np.isfinite(lo_hi[i]).all():
             raise _nonfinite_error(i)
-    table = ops.KnnGridTable(grid_layout(lo_hi, packed.sizes(), nb, cell_size), pts.device)
+    table = ops.KnnGridTable(grid_layout(lo_hi, packed.sizes(), nb, cell_size, radius=radius), pts.device)
     keys = ops.knn_cell_keys(pts, off, table)
     sorted_keys, perm = torch.sort(keys)
     return table, ops.voxel_gather_rows(pts, perm), sorted_keys, perm
@@ -264,6 +364,41 @@ def remove_outliers(clouds: Sequence, nb_neighbors: int = 20, std_ratio: float =
                               packed.split(avg) if return_distances else None,
                               [dict(mean=m, std=s, threshold=t, n_valid=int(v)) for m, s, t, v in stats.cpu().tolist()]
                               if return_stats else None)
+
+
+def radius_counts_packed(packed, radius: float, cell=None):
+    """the radius counts of a packed batch, `radius` checked -> (counts (P,) int32, pending (1,) int32), on the device"""
+    table, sorted_pts, sorted_keys, perm = sorted_batch(packed, None, cell, radius)
+    return ops.knn_radius_count(sorted_pts, sorted_keys, perm, packed.off, table, radius2(radius))
+
+
+def radius_neighbour_counts(clouds: Sequence, radius: float, *, device='cuda', cell_size=None, return_pending: bool = False):
+    """`radius_neighbour_counts_host` on the device: list of (n_i,) int32 device tensors, equal to the numpy route's for any
+    `cell_size`.  With `return_pending` also the number of points of the batch that the whole-cloud scan finished: 0 at the
+    default cell (a debug counter)."""
+    r = check_radius(radius)
+    cell = None if cell_size is None else ragged.check_positive('cell_size', cell_size)
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ([], 0) if return_pending else []
+        counts, pending = radius_counts_packed(packed, r, cell)
+        return (packed.split(counts), int(pending.item())) if return_pending else packed.split(counts)
+
+
+def remove_radius_outliers(clouds: Sequence, nb_points: int, radius: float, *, device='cuda', return_mask: bool = False,
+                           cell_size=None):
+    """`remove_radius_outliers_host` on the device: list of raw (n_i, 3) clouds -> list of (k_i, 3) float32 device tensors,
+    the rows with more than `nb_points` points of their cloud within `radius` (themselves included), in input order, bit
+    for bit the rows the numpy route returns (k_i may be 0); with `return_mask` also the (n_i,) bool masks.  `cell_size`
+    changes no output."""
+    nb, r = _check_nb_points(nb_points), check_radius(radius)
+    cell = None if cell_size is None else ragged.check_positive('cell_size', cell_size)
+    with ragged.intake(clouds, device) as packed:
+        if packed is None:
+            return ragged.empty_results(return_mask)
+        counts, _ = radius_counts_packed(packed, r, cell)
+        keep = ops.count_mask(counts, nb)
+        return ragged.results(ragged.compact(packed, keep).split(), packed.split(keep.bool()) if return_mask else None)
 
 
 def trim_radius_packed(packed, radius_max: float):

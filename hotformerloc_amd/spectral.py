@@ -174,7 +174,7 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
                       estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                       min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
                       estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                      covariance_epsilon=1e-3):
+                      covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
     """Re-rank the candidates of a search by spectral consistency.  `query_clouds`: a list of Q raw (N_i, 3) float32 GPU
     clouds; `database_clouds`: the list of the database's clouds, of which only the named ones are touched; `candidates`:
     the (Q, k) index tensor of `FlatL2Index.search`, -1 for an unused slot.  Normals and FPFH are computed once per
@@ -185,10 +185,12 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
     `global_registration` (`estimator='consensus'` and its three options included; `estimation='generalized'` takes the
     query's normals as the source's, with `covariance_epsilon`): -> `(RerankResult, RansacResult,
     RegistrationResult)`, query frame -> candidate frame, one row per query; a query without a candidate is then a
-    `ValueError`."""
+    `ValueError`.  `normal_radius` and `feature_radius` as in `global_registration`."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
-    return _rerank(query_clouds, database_clouds, candidates, estimate_normals, compute_fpfh, feature_correspondences,
+    normals_of, fpfh_of = GR._with_radii(estimate_normals, compute_fpfh, nb_neighbors, normal_radius, feature_radius,
+                                         'rerank_candidates')
+    return _rerank(query_clouds, database_clouds, candidates, normals_of, fpfh_of, feature_correspondences,
                    GR.correspondence_pairs, spectral_consistency, prune_correspondences,
                    GR._coarse_estimator(estimator, True, 'rerank_candidates', ransac_distance, refine_iterations,
                                         min_correspondences, hypotheses, seed, edge_length_ratio, consensus_distance, seeds,
@@ -313,11 +315,13 @@ def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neig
                            estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                            min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
                            estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                           covariance_epsilon=1e-3):
+                           covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
     """`rerank_candidates` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
-    return _rerank(query_clouds, database_clouds, candidates, estimate_normals_host, compute_fpfh_host,
+    normals_of, fpfh_of = GR._with_radii(estimate_normals_host, compute_fpfh_host, nb_neighbors, normal_radius,
+                                         feature_radius, 'rerank_candidates')
+    return _rerank(query_clouds, database_clouds, candidates, normals_of, fpfh_of,
                    feature_correspondences_host, GR.correspondence_pairs_host, spectral_consistency_host,
                    prune_correspondences_host,
                    GR._coarse_estimator(estimator, False, 'rerank_candidates', ransac_distance, refine_iterations,

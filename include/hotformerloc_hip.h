@@ -415,6 +415,28 @@ int hfl_knn_normals(float* normals, float* curvature, int32_t* counts, int32_t* 
                     const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
                     const int64_t* cloud_offsets, int64_t n_points, const double* viewpoints, int phases,
                     hfl_stream_t stream);
+/* Radius and hybrid neighbourhoods on the same search.  radius2 is R2, the largest fp32 squared
+ * distance that counts as "within the radius" (what sqrtf(d2) <= radius admits), one value for every cloud of the call;
+ * >= 0, +inf allowed, a NaN or a negative value: HFL_EINVAL.  radius_only == 0 (hybrid): r2 = min(k-th smallest, R2), so
+ * |N(p)| may lie below k, down to 1; with R2 = +inf this is hfl_knn_normals bit for bit, which calls it so.
+ * radius_only != 0: r2 = R2 for every point, |N(p)| has no cap, the grids' k is checked (1 .. HFL_KNN_MAX_NEIGHBOURS) but
+ * not read; no register list and no first scan -- one pass over the 3 x 3 x 3 block where the completeness bound proves
+ * that it holds every point within R2 (always, when cell >= about the radius), one pass of a wave over the cloud for the
+ * others.  Everything else as hfl_knn_normals. */
+int hfl_knn_normals_radius(float* normals, float* curvature, int32_t* counts, int32_t* pending, int32_t* counter,
+                           int32_t* cell_starts, const float* sorted_points, const int64_t* sorted_keys,
+                           const int64_t* perm, const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch,
+                           int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points, const double* viewpoints,
+                           float radius2, int radius_only, int phases, hfl_stream_t stream);
+/* counts[p] (INPUT order) = the number of points of p's own cloud with d2 <= radius2, p itself included: the radius-only
+ * search of hfl_knn_normals_radius with a count for its work (csrc/outliers.hip; open3d's remove_radius_outlier counts this
+ * set).  An integer and a pure function of the input: the same for any grid.  Workspace and `phases` as hfl_knn_mean_dist. */
+int hfl_knn_radius_count(int32_t* counts, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                         const float* sorted_points, const int64_t* sorted_keys, const int64_t* perm,
+                         const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                         const int64_t* cloud_offsets, int64_t n_points, float radius2, int phases, hfl_stream_t stream);
+/* keep[p] = counts[p] > nb_points (nb_points >= 0).  One launch on `stream`. */
+int hfl_count_mask(uint8_t* keep, const int32_t* counts, int64_t n_points, int32_t nb_points, hfl_stream_t stream);
 /* FPFH descriptors by the same search (csrc/fpfh.hip; defined in hotformerloc_amd/fpfh.py and DESIGN.md section 7k), in
  * three calls that share the workspace of hfl_knn_mean_dist.  Everything but the last output is indexed by SORTED position.
  *
@@ -425,6 +447,13 @@ int hfl_fpfh_radius(float* r2, uint8_t* proven, int32_t* pending, int32_t* count
                     const float* sorted_points, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
                     const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets, int64_t n_points,
                     hfl_stream_t stream);
+/* hfl_fpfh_radius with radius2 and radius_only as hfl_knn_normals_radius takes them.  Hybrid: r2[j] = min(k-th smallest,
+ * R2).  Radius-only: r2[j] = R2 for every point, proven[j] from the completeness bound alone, one launch and no scan.
+ * hfl_fpfh_spfh and hfl_fpfh_combine read r2 and proven and never k, so they follow either unchanged. */
+int hfl_fpfh_radius_capped(float* r2, uint8_t* proven, int32_t* pending, int32_t* counter, int32_t* cell_starts,
+                           const float* sorted_points, const int64_t* sorted_keys, const hfl_knn_grid* grids_host,
+                           const hfl_knn_grid* grids, int batch, int64_t n_cells, const int64_t* cloud_offsets,
+                           int64_t n_points, float radius2, int radius_only, hfl_stream_t stream);
 /* hist (P, 33) int32 and pairs (P) int32: the SPFH histogram of every point over N(j) = { q : d2 <= r2[j] } and the number
  * of pairs binned; three groups of 11 bins (theta, f2, f3 of the Darboux frame).  sorted_normals (P, 3) = normals[perm]; a
  * zero row, or one with a component that is not finite, is "no normal".  theta_table_host: HOST memory, 10 rows of

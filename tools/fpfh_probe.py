@@ -11,6 +11,10 @@
             `hfl_nn_dist` on 64 pairs of 30 000 x 30 000 points measured the same way; pairs per second for both, and the
             whole `feature_correspondences(mutual=True)` call.
 
+  radius    with `--radius R` (0: the radius at which a ball holds about nb_neighbors points): `compute_fpfh` with the k
+            nearest, the hybrid and the radius-only neighbourhood on the same batches and the same normals, the three whole
+            calls ALTERNATING in every round; mean pairs and pending points of each.  `--only-radius` runs this leg alone.
+
 No time is fixed in advance: the yardsticks are `estimate_normals` and `hfl_nn_dist` in the same run.  Median / min / max of
 `--repeats` measurements after `--warmup`.  One JSON line.  Run it under `timeout`."""
 import argparse
@@ -25,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hotformerloc_amd import compute_fpfh, estimate_normals, feature_correspondences, fpfh, ops, outliers, ragged  # noqa: E402
 from hotformerloc_amd import synthetic as syn                                                                     # noqa: E402
+import radius_legs                                                                                                # noqa: E402
 from normals_probe import NB, events, wall                                                                        # noqa: E402
 
 DIM = 33
@@ -61,6 +66,25 @@ def probe_fpfh(args, points):
                                                             ops.KNN_PHASE_ALL, knn_ws), args.repeats, args.warmup)
     three = sum(res[k]['median_ms'] for k in ('hfl_fpfh_radius', 'hfl_fpfh_spfh', 'hfl_fpfh_combine'))
     res['kernel_ratio'] = round(three / res['hfl_knn_normals']['median_ms'], 3)
+    return res
+
+
+def probe_radius(args, points):
+    device = torch.device('cuda', torch.cuda.current_device())
+    resident = [torch.from_numpy(syn.raw_submap(700 + i, points, extent=args.extent)).to(device) for i in range(args.clouds)]
+    total = points * args.clouds
+    radius, how = radius_legs.radius_of(args, resident, NB)
+    res = {'points_per_cloud': points, 'clouds': args.clouds, 'nb_neighbors': NB, 'radius_m': round(radius, 4), 'radius': how}
+    normals = estimate_normals(resident, NB)
+    for name, nb, r in (('k_nearest', NB, None), ('hybrid', NB, radius), ('radius_only', None, radius)):
+        _, _, pairs, pending = compute_fpfh(resident, normals, nb, radius=r, return_histograms=True, return_pending=True)
+        res[name] = {'mean_pairs': round(float(sum(int(p.sum()) for p in pairs)) / total, 4), 'pending': pending}
+    timed = radius_legs.alternate({'k_nearest': lambda: compute_fpfh(resident, normals, NB),
+                                   'hybrid': lambda: compute_fpfh(resident, normals, NB, radius=radius),
+                                   'radius_only': lambda: compute_fpfh(resident, normals, None, radius=radius)},
+                                  args.repeats, args.warmup)
+    for name, t in timed.items():
+        res[name]['compute_fpfh_call'] = t
     return res
 
 
@@ -102,10 +126,17 @@ def main():
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--launches', type=int, default=3)
+    radius_legs.add_arguments(ap)
     args = ap.parse_args()
+    if args.only_radius and args.radius is None:
+        ap.error('--only-radius needs --radius')
     if not torch.cuda.is_available():
         raise SystemExit('fpfh_probe needs a GPU: nothing is timed without one')
-    res = {'fpfh': [probe_fpfh(args, points) for points in args.points], 'matcher': probe_matcher(args)}
+    res = {}
+    if not args.only_radius:
+        res = {'fpfh': [probe_fpfh(args, points) for points in args.points], 'matcher': probe_matcher(args)}
+    if args.radius is not None:
+        res['radius'] = [probe_radius(args, points) for points in args.points]
     print(json.dumps(res), flush=True)
 
 

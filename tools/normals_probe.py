@@ -14,6 +14,11 @@
             sources as well, and a whole `icp_refine` call of each mode with the updates it needed.  `--only-plane` leaves
             the normals part out.
 
+  radius    with `--radius R` (0: the radius at which a ball holds about nb_neighbors points, found by bisection on
+            `radius_neighbour_counts`): `estimate_normals` with the k nearest, with the hybrid and with the radius-only
+            neighbourhood on the same batches, the three whole calls ALTERNATING in every round; the mean |N(i)| and the
+            number of points the whole-cloud scan finished for each.  `--only-radius` runs this leg alone.
+
 No throughput target is set: the figures to report are the two ratios, each measured in one run.  Median / min / max of
 `--repeats` measurements after `--warmup`.  One JSON line.  Run it under `timeout`."""
 import argparse
@@ -30,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hotformerloc_amd import estimate_normals, knn_mean_distance, ops, outliers, ragged, transform_points_host   # noqa: E402
 from hotformerloc_amd import registration as reg                                                                # noqa: E402
 from hotformerloc_amd import synthetic as syn                                                                   # noqa: E402
+import radius_legs                                                                                              # noqa: E402
 from registration_probe import MAX_DIST, small_motion                                                           # noqa: E402
 from submap_overlap_probe import scene, spread                                                                  # noqa: E402
 
@@ -84,6 +90,25 @@ def probe_normals(args, points):
     res['hfl_knn_mean_dist'] = events(lambda: ops.knn_mean_dist(sorted_pts, sorted_keys, perm, packed.off, table,
                                                                 ops.KNN_PHASE_ALL, ws, out), args.repeats, args.warmup)
     res['kernel_ratio'] = round(res['hfl_knn_normals']['median_ms'] / res['hfl_knn_mean_dist']['median_ms'], 3)
+    return res
+
+
+def probe_radius(args, points):
+    device = torch.device('cuda', torch.cuda.current_device())
+    resident = [torch.from_numpy(syn.raw_submap(700 + i, points, extent=args.extent)).to(device) for i in range(args.clouds)]
+    total = points * args.clouds
+    radius, how = radius_legs.radius_of(args, resident, NB)
+    res = {'points_per_cloud': points, 'clouds': args.clouds, 'nb_neighbors': NB, 'radius_m': round(radius, 4), 'radius': how}
+    for name, nb, r in (('k_nearest', NB, None), ('hybrid', NB, radius), ('radius_only', None, radius)):
+        normals, counts, pending = estimate_normals(resident, nb, radius=r, return_counts=True, return_pending=True)
+        res[name] = {'mean_neighbourhood': round(float(sum(int(c.sum()) for c in counts)) / total, 4), 'pending': pending,
+                     'zero_normals': int(sum(int((~n.any(1)).sum()) for n in normals))}
+    timed = radius_legs.alternate({'k_nearest': lambda: estimate_normals(resident, NB),
+                                   'hybrid': lambda: estimate_normals(resident, NB, radius=radius),
+                                   'radius_only': lambda: estimate_normals(resident, None, radius=radius)},
+                                  args.repeats, args.warmup)
+    for name, t in timed.items():
+        res[name]['estimate_normals_call'] = t
     return res
 
 
@@ -143,11 +168,18 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--launches', type=int, default=3)
     ap.add_argument('--only-plane', action='store_true', help='the ICP iterations alone, without the normals part')
+    radius_legs.add_arguments(ap)
     args = ap.parse_args()
+    if args.only_radius and args.radius is None:
+        ap.error('--only-radius needs --radius')
     if not torch.cuda.is_available():
         raise SystemExit('normals_probe needs a GPU: nothing is timed without one')
-    res = {'normals': [] if args.only_plane else [probe_normals(args, points) for points in args.points],
-           'plane': probe_plane(args)}
+    res = {}
+    if not args.only_radius:
+        res = {'normals': [] if args.only_plane else [probe_normals(args, points) for points in args.points],
+               'plane': probe_plane(args)}
+    if args.radius is not None:
+        res['radius'] = [probe_radius(args, points) for points in args.points]
     print(json.dumps(res), flush=True)
 
 

@@ -12,6 +12,11 @@ returns 15 to 40 m above each.
   host         `scipy.spatial.cKDTree(p).query(p, k=20, workers=16)` in float64 per cloud, where scipy imports: the
                neighbour search alone, the yardstick for steps 1-2.
 
+  radius       with `--radius R` (0: the radius at which a ball holds about 20 points): `radius_neighbour_counts` and
+               `remove_radius_outliers(nb_points=2)` against `knn_mean_distance` and `remove_outliers` on the same resident
+               clouds, the whole calls ALTERNATING in every round; the mean count and the pending points.  `--only-radius`
+               runs this leg alone.
+
 Wall clock with a device synchronisation on both sides, median / min / max of `--repeats` calls after `--warmup`; the
 device avg is compared with the KD-tree's (1e-5 relative) before anything is timed.  One JSON line.  Run it under
 `timeout`."""
@@ -25,9 +30,11 @@ import time
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hotformerloc_amd import ops, outliers, ragged                              # noqa: E402
 from hotformerloc_amd import synthetic as syn                                   # noqa: E402
+import radius_legs                                                              # noqa: E402
 
 
 def submap(seed, points, extent, strays):
@@ -143,6 +150,22 @@ def probe(args, points):
     return res
 
 
+def probe_radius(args, points):
+    device = torch.device('cuda', torch.cuda.current_device())
+    resident = [torch.from_numpy(submap(700 + i, points, args.extent, args.strays)).to(device) for i in range(args.clouds)]
+    radius, how = radius_legs.radius_of(args, resident, 20)
+    mean, pending = radius_legs.mean_count(resident, radius, with_pending=True)
+    res = {'points_per_cloud': points, 'nb_neighbors': 20, 'radius_m': round(radius, 4), 'radius': how,
+           'mean_count': round(mean, 4), 'pending': pending,
+           'kept_points': [int(k.shape[0]) for k in outliers.remove_radius_outliers(resident, 2, radius)]}
+    res.update(radius_legs.alternate({'knn_mean_distance_call': lambda: outliers.knn_mean_distance(resident),
+                                      'radius_neighbour_counts_call': lambda: outliers.radius_neighbour_counts(resident, radius),
+                                      'remove_outliers_call': lambda: outliers.remove_outliers(resident),
+                                      'remove_radius_outliers_call': lambda: outliers.remove_radius_outliers(resident, 2, radius)},
+                                     args.repeats, args.warmup))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--clouds', type=int, default=8)
@@ -153,11 +176,18 @@ def main():
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--host-repeats', type=int, default=1)
     ap.add_argument('--warmup', type=int, default=2)
+    radius_legs.add_arguments(ap)
     args = ap.parse_args()
+    if args.only_radius and args.radius is None:
+        ap.error('--only-radius needs --radius')
     if not torch.cuda.is_available():
         raise SystemExit('outlier_probe needs a GPU: nothing is timed without one')
-    print(json.dumps({'clouds': args.clouds, 'extent_m': args.extent, 'strays': args.strays,
-                      'runs': [probe(args, n) for n in args.points]}))
+    res = {'clouds': args.clouds, 'extent_m': args.extent, 'strays': args.strays}
+    if not args.only_radius:
+        res['runs'] = [probe(args, n) for n in args.points]
+    if args.radius is not None:
+        res['radius'] = [probe_radius(args, n) for n in args.points]
+    print(json.dumps(res))
 
 
 if __name__ == '__main__':
