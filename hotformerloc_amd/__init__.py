@@ -27,6 +27,11 @@ makes its candidates from the correspondences' second-order compatibility instea
 graph, one consensus set and one Kabsch solve per seed, nothing random) and scores, selects and polishes them as
 `ransac_registration` does; `global_registration(estimator='consensus')` and `rerank_candidates(..., estimator='consensus')`
 use it for the coarse pose.
+
+Matching on fewer than all points: `iss_keypoints` (Intrinsic Shape Signatures: `iss_saliency`, then the non-maximum
+suppression `iss_select`) keeps the few per cent of a cloud's points where the surface bends in all three directions;
+`global_registration` and `rerank_candidates` take `salient_radius=` and `non_max_radius=` and then match, verify and
+estimate the coarse pose on those rows only, while the ICP still refines on the full clouds.
 """
 
 import os as _os
@@ -61,6 +66,8 @@ from .registration import (icp_refine, icp_refine_host, icp_correspondences, icp
                            evaluate_registration, evaluate_registration_host, kabsch_update, kabsch_update_host,
                            plane_update, plane_update_host, RegistrationResult)
 from .normals import estimate_normals, estimate_normals_host                                            # noqa: F401,E402
+from .keypoints import (iss_saliency, iss_saliency_host, iss_select, iss_select_host, iss_keypoints,    # noqa: F401,E402
+                        iss_keypoints_host)
 from .fpfh import (compute_fpfh, compute_fpfh_host, feature_correspondences,                            # noqa: F401,E402
                    feature_correspondences_host)
 from .global_registration import (correspondence_pairs, correspondence_pairs_host, ransac_hypotheses,   # noqa: F401,E402

@@ -156,6 +156,9 @@ SIGNATURES = {
                                                         c_void_p]),
     'hfl_knn_radius_count': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_float, c_int, c_void_p]),
     'hfl_count_mask': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    'hfl_iss_saliency': (c_int, [c_void_p] * 11 + [c_int, c_int64, c_void_p, c_int64, c_float, c_double, c_double, c_int, c_int,
+                                                  c_void_p]),
+    'hfl_iss_select': (c_int, [c_void_p] * 10 + [c_int, c_int64, c_void_p, c_int64, c_float, c_int, c_int, c_void_p]),
     'hfl_fpfh_radius': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_void_p]),
     'hfl_fpfh_radius_capped': (c_int, [c_void_p] * 9 + [c_int, c_int64, c_void_p, c_int64, c_float, c_int, c_void_p]),
     'hfl_fpfh_spfh': (c_int, [c_void_p] * 12 + [c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

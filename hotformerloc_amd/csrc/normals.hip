@@ -25,84 +25,38 @@
 // floating-point atomics (one integer add per wave appends to the list); no workgroup waits for another.
 #include <math.h>
 
-#include "jacobi3.h"
+#include "cov_eigen.h"
 #include "knn_common.h"
 
 namespace {
 
-constexpr int NR_SWEEPS = 12;                                    // RG_SWEEPS of registration.hip
 constexpr double NR_RANK_TOL = 1e-12;                            // middle eigenvalue <= this x the largest: no normal
-constexpr int NR_SUMS = 9;                                       // S1 (3), S2 (xx, xy, xz, yy, yz, zz)
 
-// one neighbour's contribution, e = p_j - p_i in float64
-__device__ __forceinline__ void normal_add(double (&s)[NR_SUMS], float px, float py, float pz, const float* __restrict__ q) {
-  const double ex = (double)q[0] - (double)px, ey = (double)q[1] - (double)py, ez = (double)q[2] - (double)pz;
-  s[0] += ex;
-  s[1] += ey;
-  s[2] += ez;
-  s[3] += ex * ex;
-  s[4] += ex * ey;
-  s[5] += ex * ez;
-  s[6] += ey * ey;
-  s[7] += ey * ez;
-  s[8] += ez * ez;
-}
-
-// steps 3 to 7 of the definition for one point: from the sums over its m neighbours to the stores at `row`
+// steps 3 to 7 of the definition for one point: from the sums over its m neighbours (`normal_add` and the eigenvalues are
+// cov_eigen.h's) to the stores at `row`
 __device__ void normal_finish(float* __restrict__ normals, float* __restrict__ curvature, int32_t* __restrict__ counts,
                               int64_t row, int64_t n, const double (&s)[NR_SUMS], int m, float px, float py, float pz,
                               const double* __restrict__ view) {
   if (row < 0 || row >= n) return;
   double nx = 0.0, ny = 0.0, nz = 0.0, curv = 0.0;
   if (m >= 3) {
-    const double dm = (double)m;
-    const double mu[3] = {s[0] / dm, s[1] / dm, s[2] / dm};
-    double g[3][3], v[3][3];
-    g[0][0] = s[3] / dm - mu[0] * mu[0];
-    g[0][1] = s[4] / dm - mu[0] * mu[1];
-    g[0][2] = s[5] / dm - mu[0] * mu[2];
-    g[1][1] = s[6] / dm - mu[1] * mu[1];
-    g[1][2] = s[7] / dm - mu[1] * mu[2];
-    g[2][2] = s[8] / dm - mu[2] * mu[2];
-    g[1][0] = g[0][1];
-    g[2][0] = g[0][2];
-    g[2][1] = g[1][2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) v[a][b] = a == b ? 1.0 : 0.0;
-    // G = C V with orthogonal columns: their norms are the eigenvalues of the positive semi-definite C, V's columns the
-    // eigenvectors
-    for (int sweep = 0; sweep < NR_SWEEPS; ++sweep) {
-      jacobi_rotate<0, 1>(g, v);
-      jacobi_rotate<0, 2>(g, v);
-      jacobi_rotate<1, 2>(g, v);
-    }
-    double w[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) w[j] = sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j]);
-    // the largest, then the larger of the other two, the lowest column on a tie
-    const int i2 = (w[0] >= w[1] && w[0] >= w[2]) ? 0 : (w[1] >= w[2] ? 1 : 2);
-    const int ja = i2 == 0 ? 1 : 0, jb = i2 == 2 ? 1 : 2;
-    const int i1 = w[ja] >= w[jb] ? ja : jb, i0 = w[ja] >= w[jb] ? jb : ja;
-    const double l0 = i0 == 0 ? w[0] : (i0 == 1 ? w[1] : w[2]);
-    const double l1 = i1 == 0 ? w[0] : (i1 == 1 ? w[1] : w[2]);
-    const double l2 = i2 == 0 ? w[0] : (i2 == 1 ? w[1] : w[2]);
-    if (l1 > NR_RANK_TOL * l2) {                                 // false for a NaN and for C = 0 as well
-      nx = pick(v, 0, i0);
-      ny = pick(v, 1, i0);
-      nz = pick(v, 2, i0);
-      const double sum = (l0 + l1) + l2;
-      curv = sum > 0.0 ? l0 / sum : 0.0;
-      // one number decides the sign in either mode: n . (viewpoint - p), or the first of n_z, n_y, n_x that is not zero
-      double facing = nz != 0.0 ? nz : (ny != 0.0 ? ny : nx);
-      if (view != nullptr)
-        facing = (nx * (view[0] - (double)px) + ny * (view[1] - (double)py)) + nz * (view[2] - (double)pz);
-      const double turn = facing < 0.0 ? -1.0 : 1.0;             // a product by +-1 is exact
-      nx *= turn;
-      ny *= turn;
-      nz *= turn;
-    }
+    cov_eigen(s, m, [&](double l0, double l1, double l2, const double (&v)[3][3], int i0) {
+      if (l1 > NR_RANK_TOL * l2) {                               // false for a NaN and for C = 0 as well
+        nx = pick(v, 0, i0);
+        ny = pick(v, 1, i0);
+        nz = pick(v, 2, i0);
+        const double sum = (l0 + l1) + l2;
+        curv = sum > 0.0 ? l0 / sum : 0.0;
+        // one number decides the sign in either mode: n . (viewpoint - p), or the first of n_z, n_y, n_x that is not zero
+        double facing = nz != 0.0 ? nz : (ny != 0.0 ? ny : nx);
+        if (view != nullptr)
+          facing = (nx * (view[0] - (double)px) + ny * (view[1] - (double)py)) + nz * (view[2] - (double)pz);
+        const double turn = facing < 0.0 ? -1.0 : 1.0;           // a product by +-1 is exact
+        nx *= turn;
+        ny *= turn;
+        nz *= turn;
+      }
+    });
   }
   normals[row * 3 + 0] = (float)nx;
   normals[row * 3 + 1] = (float)ny;

@@ -363,11 +363,32 @@ def _with_radii(normals_of, fpfh_of, nb, normal_radius, feature_radius, what):
             fpfh_of if feature_radius is None else lambda clouds, normals, k: fpfh_of(clouds, normals, k, radius=feature_radius))
 
 
+def _keypoints_of(salient_radius, non_max_radius, device_route, what):
+    """None when both radii are None, else `iss_keypoints` (or its numpy twin) with the two radii bound and the gammas and
+    `min_neighbors` at their defaults: clouds -> the per-cloud keypoint rows.  Only one radius: `ValueError`."""
+    from . import keypoints
+    radii = keypoints.check_radii(salient_radius, non_max_radius, what)
+    if radii is None:
+        return None
+    run = keypoints.iss_keypoints if device_route else keypoints.iss_keypoints_host
+    return lambda clouds: run(clouds, *radii)
+
+
+def _at_keypoints(clouds, features, keypoints_of, device_route):
+    """(clouds, features) as they are when `keypoints_of` is None, else their rows at the keypoints of every cloud, which
+    may be none: what the matcher, the verification and the coarse estimator then work on"""
+    if keypoints_of is None:
+        return clouds, features
+    rows = keypoints_of(clouds)
+    as_rows = torch.as_tensor if device_route else _as_numpy
+    return [as_rows(c)[k] for c, k in zip(clouds, rows)], [f[k] for f, k in zip(features, rows)]
+
+
 def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_distance=0.8, icp_distance=0.8,
                         estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                         min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
                         estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10, covariance_epsilon=1e-3,
-                        normal_radius=None, feature_radius=None):
+                        normal_radius=None, feature_radius=None, salient_radius=None, non_max_radius=None):
     """From two lists of raw (N_i, 3) float32 GPU clouds to refined 6-DoF poses, source frame -> target frame, in one call:
     `estimate_normals` -> `compute_fpfh` -> `feature_correspondences` (`mutual`) -> `correspondence_pairs` ->
     `ransac_registration` (`ransac_distance` and its options) -> `icp_refine(init=...)` (`icp_distance`, `estimation`, its
@@ -377,7 +398,13 @@ def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_
     `consensus_registration` (`consensus_distance`, `seeds`, `consensus_size`; `ransac_distance`, `refine_iterations` and
     `min_correspondences` as before) instead; `hypotheses`, `seed` and `edge_length_ratio` are then unused.
     `normal_radius` and `feature_radius` are the `radius` of `estimate_normals` and of `compute_fpfh` (hybrid
-    neighbourhoods); `nb_neighbors=None` is radius-only and needs both."""
+    neighbourhoods); `nb_neighbors=None` is radius-only and needs both.
+    `salient_radius` and `non_max_radius` (both, or neither) put `iss_keypoints` in front of the matcher, with its other
+    parameters at their defaults: `feature_correspondences` then sees the descriptor rows at the keypoints only, and the
+    coarse estimator their points, so both work on a few per cent of the rows.  Normals and FPFH are still computed on
+    all points -- an FPFH row needs the SPFH of all its neighbours, so nothing is saved there -- and `icp_refine` still
+    gets the full clouds and normals.  A cloud without a keypoint gives its pair no correspondence: NO_HYPOTHESIS, and
+    the ICP from the identity.  With both None every result keeps its bits."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
     coarse = _coarse_estimator(estimator, True, 'global_registration', ransac_distance, refine_iterations, min_correspondences,
@@ -386,11 +413,12 @@ def global_registration(source, target, *, nb_neighbors=30, mutual=True, ransac_
                                       'global_registration')
     return _global(source, target, normals_of, fpfh_of, feature_correspondences, correspondence_pairs, coarse,
                    reg.icp_refine, True, nb_neighbors, mutual, icp_distance, estimation, min_correspondences, max_iterations,
-                   relative_fitness, relative_rmse, covariance_epsilon)
+                   relative_fitness, relative_rmse, covariance_epsilon,
+                   _keypoints_of(salient_radius, non_max_radius, True, 'global_registration'))
 
 
 def _global(source, target, normals_of, fpfh_of, match, pairs_of, coarse_of, icp, device_route, nb, mutual, icp_distance,
-            estimation, min_corr, max_iterations, rel_f, rel_r, epsilon=1e-3):
+            estimation, min_corr, max_iterations, rel_f, rel_r, epsilon=1e-3, keypoints_of=None):
     what = 'global_registration'
     if not isinstance(source, list) or not isinstance(target, list) or not source or len(source) != len(target):
         raise ValueError('%s: two lists of (N_i, 3) clouds that pair up expected' % what)
@@ -401,9 +429,10 @@ def _global(source, target, normals_of, fpfh_of, match, pairs_of, coarse_of, icp
     pairs = len(source)
     normals = normals_of(source + target, nb)
     features = fpfh_of(source + target, normals, nb)
-    matched = match(features[:pairs], features[pairs:], mutual=mutual)
+    points, rows = _at_keypoints(source + target, features, keypoints_of, device_route)
+    matched = match(rows[:pairs], rows[pairs:], mutual=mutual)
     corr = pairs_of(matched[0], matched[2] if mutual else None)
-    coarse = coarse_of(source, target, corr)
+    coarse = coarse_of(points[:pairs], points[pairs:], corr)
     plane, generalized = estimation != 'point_to_point', estimation == 'generalized'
     fine = icp(source, target, init=coarse.transforms, max_correspondence_distance=icp_distance,
                max_iterations=max_iterations, relative_fitness=rel_f, relative_rmse=rel_r, min_correspondences=min_corr,
@@ -584,7 +613,8 @@ def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ra
                              estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9,
                              refine_iterations=3, min_correspondences=3, max_iterations=30, relative_fitness=1e-6,
                              relative_rmse=1e-6, estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                             covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
+                             covariance_epsilon=1e-3, normal_radius=None, feature_radius=None, salient_radius=None,
+                             non_max_radius=None):
     """`global_registration` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
@@ -595,4 +625,5 @@ def global_registration_host(source, target, *, nb_neighbors=30, mutual=True, ra
                                       'global_registration')
     return _global(source, target, normals_of, fpfh_of, feature_correspondences_host,
                    correspondence_pairs_host, coarse, reg.icp_refine_host, False, nb_neighbors, mutual, icp_distance,
-                   estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse, covariance_epsilon)
+                   estimation, min_correspondences, max_iterations, relative_fitness, relative_rmse, covariance_epsilon,
+                   _keypoints_of(salient_radius, non_max_radius, False, 'global_registration'))

@@ -2648,6 +2648,44 @@ def knn_radius_count(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, per
     return counts, ws.counter
 
 
+def iss_saliency(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor,
+                 table: KnnGridTable, radius2, gamma_21: float, gamma_32: float, min_neighbors: int,
+                 phases: int = KNN_PHASE_ALL, workspace: KnnWorkspace = None):
+    """`hfl_iss_saliency`: the arguments of `knn_mean_dist`, R2 of the salient radius and the three thresholds -> (saliency
+    (P,) fp32 and counts (P,) int32 in INPUT order, the same saliency by SORTED position for `iss_select`, pending (1,)
+    int32 on the GPU).  Nothing is read back."""
+    n, ws = _knn_sorted_check('iss_saliency', table, sorted_points, offsets, workspace, 'keys and permutation', sorted_keys,
+                              perm)
+    saliency, sorted_saliency = (torch.empty(n, dtype=torch.float32, device=sorted_points.device) for _ in range(2))
+    counts = torch.empty(n, dtype=torch.int32, device=sorted_points.device)
+    check(_native.load().hfl_iss_saliency(saliency.data_ptr(), sorted_saliency.data_ptr(), counts.data_ptr(),
+                                          ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
+                                          sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(),
+                                          table.host.ctypes.data, table.device.data_ptr(), table.batch, table.cells,
+                                          offsets.data_ptr(), n, _radius2('iss_saliency', radius2), float(gamma_21),
+                                          float(gamma_32), int(min_neighbors), int(phases), _stream()), 'hfl_iss_saliency')
+    return saliency, counts, sorted_saliency, ws.counter
+
+
+def iss_select(sorted_points: torch.Tensor, sorted_keys: torch.Tensor, perm: torch.Tensor, sorted_saliency: torch.Tensor,
+               offsets: torch.Tensor, table: KnnGridTable, radius2, min_neighbors: int, phases: int = KNN_PHASE_ALL,
+               workspace: KnnWorkspace = None):
+    """`hfl_iss_select`: the arguments of `knn_mean_dist`, the (P,) fp32 saliency by SORTED position (`saliency[perm]`), R2
+    of the non-maximum radius -> (mask (P,) uint8 in INPUT order, pending (1,) int32 on the GPU).  A `workspace` that an
+    earlier call on this batch filled spares the cell-start table (`phases` without `KNN_PHASE_STARTS`).  Nothing is read
+    back."""
+    n, ws = _knn_sorted_check('iss_select', table, sorted_points, offsets, workspace, 'keys and permutation', sorted_keys, perm)
+    _dev(sorted_saliency)
+    _vector_check('iss_select', sorted_saliency, torch.float32, n, 'saliency')
+    mask = torch.empty(n, dtype=torch.uint8, device=sorted_points.device)
+    check(_native.load().hfl_iss_select(mask.data_ptr(), ws.pending.data_ptr(), ws.counter.data_ptr(), ws.starts.data_ptr(),
+                                        sorted_points.data_ptr(), sorted_keys.data_ptr(), perm.data_ptr(),
+                                        sorted_saliency.data_ptr(), table.host.ctypes.data, table.device.data_ptr(),
+                                        table.batch, table.cells, offsets.data_ptr(), n, _radius2('iss_select', radius2),
+                                        int(min_neighbors), int(phases), _stream()), 'hfl_iss_select')
+    return mask, ws.counter
+
+
 def count_mask(counts: torch.Tensor, nb_points: int):
     """`hfl_count_mask`: counts (P,) int32 on the GPU -> keep (P,) uint8, 1 where counts > nb_points."""
     _dev(counts)

@@ -174,7 +174,8 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
                       estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                       min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
                       estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                      covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
+                      covariance_epsilon=1e-3, normal_radius=None, feature_radius=None, salient_radius=None,
+                      non_max_radius=None):
     """Re-rank the candidates of a search by spectral consistency.  `query_clouds`: a list of Q raw (N_i, 3) float32 GPU
     clouds; `database_clouds`: the list of the database's clouds, of which only the named ones are touched; `candidates`:
     the (Q, k) index tensor of `FlatL2Index.search`, -1 for an unused slot.  Normals and FPFH are computed once per
@@ -185,7 +186,10 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
     `global_registration` (`estimator='consensus'` and its three options included; `estimation='generalized'` takes the
     query's normals as the source's, with `covariance_epsilon`): -> `(RerankResult, RansacResult,
     RegistrationResult)`, query frame -> candidate frame, one row per query; a query without a candidate is then a
-    `ValueError`.  `normal_radius` and `feature_radius` as in `global_registration`."""
+    `ValueError`.  `normal_radius` and `feature_radius` as in `global_registration`, and so are `salient_radius` and
+    `non_max_radius`: `iss_keypoints` once per distinct cloud; the matcher, the score, the pruning and the coarse
+    estimator on the keypoints' rows (the query's number of keypoints takes the place of its size in the score); the ICP
+    on the full clouds."""
     from .fpfh import compute_fpfh, feature_correspondences
     from .normals import estimate_normals
     normals_of, fpfh_of = GR._with_radii(estimate_normals, compute_fpfh, nb_neighbors, normal_radius, feature_radius,
@@ -199,11 +203,12 @@ def rerank_candidates(query_clouds, database_clouds, candidates, *, nb_neighbors
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
                         min_correspondences=min_correspondences, estimation=estimation,
-                        covariance_epsilon=covariance_epsilon))
+                        covariance_epsilon=covariance_epsilon),
+                   GR._keypoints_of(salient_radius, non_max_radius, True, 'rerank_candidates'))
 
 
 def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of, spectral, prune, coarse_of, icp,
-            device_route, nb, mutual, sigma, iterations, register, keep, icp_kw):
+            device_route, nb, mutual, sigma, iterations, register, keep, icp_kw, keypoints_of=None):
     what = 'rerank_candidates'
     if not isinstance(queries, list) or not isinstance(database, list) or not queries or not database:
         raise ValueError('%s: two lists of (N_i, 3) clouds expected' % what)
@@ -226,17 +231,18 @@ def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of,
     n_q, k = cand.shape
     slot_q, slot_j = np.nonzero(cand >= 0)                             # the pairs, query by query in retrieval order
     scores = np.full((n_q, k), -1.0, np.float64)
-    corr = weights = normals = None
+    corr = weights = normals = points = None
     place = np.full(len(database), -1, np.int64)
     place[named] = n_q + np.arange(named.shape[0])
     if slot_q.shape[0]:
         clouds = list(queries) + [database[i] for i in named]
         normals = normals_of(clouds, nb)
         features = fpfh_of(clouds, normals, nb)
+        points, rows = GR._at_keypoints(clouds, features, keypoints_of, device_route)
         at_t = place[cand[slot_q, slot_j]]
-        matched = match([features[q] for q in slot_q], [features[t] for t in at_t], mutual=mutual)
+        matched = match([rows[q] for q in slot_q], [rows[t] for t in at_t], mutual=mutual)
         corr = pairs_of(matched[0], matched[2] if mutual else None)
-        res = spectral([clouds[q] for q in slot_q], [clouds[t] for t in at_t], corr, distance_threshold=sigma,
+        res = spectral([points[q] for q in slot_q], [points[t] for t in at_t], corr, distance_threshold=sigma,
                        iterations=iterations)
         scores[slot_q, slot_j], weights = res.score, res.weights
     order = np.argsort(-scores, axis=1, kind='stable')                 # the earlier rank of equal scores; -1 slots last
@@ -257,7 +263,7 @@ def _rerank(queries, database, candidates, normals_of, fpfh_of, match, pairs_of,
     if keep is not None:
         top_corr = prune(top_corr, [weights[i] for i in top], keep)
     src, dst = [clouds[q] for q in range(n_q)], [clouds[place[i]] for i in indices[:, 0]]
-    coarse = coarse_of(src, dst, top_corr)
+    coarse = coarse_of([points[q] for q in range(n_q)], [points[place[i]] for i in indices[:, 0]], top_corr)
     plane, generalized = icp_kw['estimation'] != 'point_to_point', icp_kw['estimation'] == 'generalized'
     fine = icp(src, dst, init=coarse.transforms, target_normals=[normals[place[i]] for i in indices[:, 0]] if plane else None,
                source_normals=[normals[q] for q in range(n_q)] if generalized else None, **icp_kw)
@@ -315,7 +321,8 @@ def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neig
                            estimation='point_to_plane', hypotheses=4096, seed=0, edge_length_ratio=0.9, refine_iterations=3,
                            min_correspondences=3, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6,
                            estimator='ransac', consensus_distance=0.4, seeds=64, consensus_size=10,
-                           covariance_epsilon=1e-3, normal_radius=None, feature_radius=None):
+                           covariance_epsilon=1e-3, normal_radius=None, feature_radius=None, salient_radius=None,
+                           non_max_radius=None):
     """`rerank_candidates` on the CPU, from the numpy twins of every step (brute force: for tests and small clouds)."""
     from .fpfh import compute_fpfh_host, feature_correspondences_host
     from .normals import estimate_normals_host
@@ -331,4 +338,5 @@ def rerank_candidates_host(query_clouds, database_clouds, candidates, *, nb_neig
                    dict(max_correspondence_distance=icp_distance, max_iterations=max_iterations,
                         relative_fitness=relative_fitness, relative_rmse=relative_rmse,
                         min_correspondences=min_correspondences, estimation=estimation,
-                        covariance_epsilon=covariance_epsilon))
+                        covariance_epsilon=covariance_epsilon),
+                   GR._keypoints_of(salient_radius, non_max_radius, False, 'rerank_candidates'))

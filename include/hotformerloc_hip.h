@@ -437,6 +437,29 @@ int hfl_knn_radius_count(int32_t* counts, int32_t* pending, int32_t* counter, in
                          const int64_t* cloud_offsets, int64_t n_points, float radius2, int phases, hfl_stream_t stream);
 /* keep[p] = counts[p] > nb_points (nb_points >= 0).  One launch on `stream`. */
 int hfl_count_mask(uint8_t* keep, const int32_t* counts, int64_t n_points, int32_t nb_points, hfl_stream_t stream);
+/* ISS keypoints (csrc/keypoints.hip; defined in hotformerloc_amd/keypoints.py and DESIGN.md section 7t): two radius-only
+ * searches on ONE sorted batch laid out for the larger of the two radii.  Workspace and `phases` as hfl_knn_mean_dist.
+ *
+ * hfl_iss_saliency: over N(p) = { q : d2 <= radius2 } (p itself included, m = |N(p)|) the float64 sums and the ordered
+ * eigenvalues l0 <= l1 <= l2 of hfl_knn_normals; the saliency is float(l0) where m >= max(min_neighbors, 3), l1 < gamma_21 l2
+ * and l0 < gamma_32 l1 (float64 products, a NaN fails), else 0.  It is written twice: sorted_saliency (P) by SORTED position,
+ * for hfl_iss_select, and saliency (P) in INPUT order; counts (P) int32 = m in INPUT order.  gamma_21, gamma_32 in (0, 1],
+ * min_neighbors >= 1, radius2 >= 0 (+inf allowed), else HFL_EINVAL.  counts and the set of zeros do not depend on the grid,
+ * the values do to rounding; two runs give the same bits. */
+int hfl_iss_saliency(float* saliency, float* sorted_saliency, int32_t* counts, int32_t* pending, int32_t* counter,
+                     int32_t* cell_starts, const float* sorted_points, const int64_t* sorted_keys, const int64_t* perm,
+                     const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                     const int64_t* cloud_offsets, int64_t n_points, float radius2, double gamma_21, double gamma_32,
+                     int min_neighbors, int phases, hfl_stream_t stream);
+/* hfl_iss_select: mask (P) uint8 in INPUT order, 1 where the point's saliency s is > 0, at least min_neighbors points of its
+ * cloud lie within radius2 (itself included), and none of them has a saliency > s, or == s at a lower input row.
+ * sorted_saliency (P) is indexed by SORTED position (saliency[perm]); any fp32 values, a NaN is no candidate and beats
+ * nobody.  Integers and comparisons only: a pure function of the points and the saliency, the same for any grid. */
+int hfl_iss_select(uint8_t* mask, int32_t* pending, int32_t* counter, int32_t* cell_starts, const float* sorted_points,
+                   const int64_t* sorted_keys, const int64_t* perm, const float* sorted_saliency,
+                   const hfl_knn_grid* grids_host, const hfl_knn_grid* grids, int batch, int64_t n_cells,
+                   const int64_t* cloud_offsets, int64_t n_points, float radius2, int min_neighbors, int phases,
+                   hfl_stream_t stream);
 /* FPFH descriptors by the same search (csrc/fpfh.hip; defined in hotformerloc_amd/fpfh.py and DESIGN.md section 7k), in
  * three calls that share the workspace of hfl_knn_mean_dist.  Everything but the last output is indexed by SORTED position.
  *
