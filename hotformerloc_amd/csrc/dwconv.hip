@@ -517,10 +517,12 @@ __global__ void __launch_bounds__(256) cpe_fwd_kernel(float* __restrict__ out, f
       const float inv_c = 1.0f / (float)C;
       const float mean = hfl_group_sum<TPR>((acc.x + acc.y) + (acc.z + acc.w)) * inv_c;
       const float4 d = make_float4(acc.x - mean, acc.y - mean, acc.z - mean, acc.w - mean);
+      const float dm = hfl_group_sum<TPR>((d.x + d.y) + (d.z + d.w)) * inv_c;     // the corrected mean of csrc/ln_row.h
       const float var = hfl_group_sum<TPR>((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * inv_c;
-      const float rstd = 1.0f / sqrtf(var + eps);
-      y = make_float4(fmaf(d.x * rstd, gm.x, bt.x), fmaf(d.y * rstd, gm.y, bt.y),
-                      fmaf(d.z * rstd, gm.z, bt.z), fmaf(d.w * rstd, gm.w, bt.w));
+      const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, var), 0.f) + eps);
+      const float dr = dm * rstd;
+      y = make_float4(fmaf(fmaf(d.x, rstd, -dr), gm.x, bt.x), fmaf(fmaf(d.y, rstd, -dr), gm.y, bt.y),
+                      fmaf(fmaf(d.z, rstd, -dr), gm.z, bt.z), fmaf(fmaf(d.w, rstd, -dr), gm.w, bt.w));
     }
     if (live) {
       // (training: the convolution's output is the LayerNorm backward's input)

@@ -182,7 +182,8 @@ __device__ __forceinline__ void x3_epilogue(const X3Params& p, f32x4 (&acc)[4][M
 // EPI 3: EPI 1 + the pre-activation acc + bias also written as f32 to aux (training forward of fc1: GELU's backward needs it)
 // EPI 4: out split2 = split((acc + bias) * gelu'(aux)) (training backward: dx of fc2 straight into the operand of fc1's gradients)
 // EPI 2: out = the window-attention operand layout of acc + bias (qkv projection): per row [Q | K | V] regions of C
-//        features, per head 16 dims as [16 x hi | 16 x lo] fp16 (hi = RTZ(v), lo = RTZ(v - hi): 22 significant bits), the
+//        features, per head 16 dims as [16 x hi | 16 x lo] fp16 (hi = RTZ(v), lo = RTZ(v - hi): 2^-20 relative, never
+//        better than the fp16 quantum 2^-24, |v| < 65504: DESIGN.md "numeric range contract"), the
 //        queries pre-multiplied by q_scale -- csrc/attention.hip, window_attn_kernel_v5 loads these as MFMA fragments
 // MT = 16-row tiles of x per wave: 4 -> 128-row workgroup tile (3 workgroups / CU), 8 -> 256-row tile (2 / CU): the
 // weight tile is then shared by twice the rows, 25 % less L2 -> LDS operand traffic per MAC -- the k-loop runs at the

@@ -39,7 +39,8 @@ __device__ __forceinline__ void hfl_store_split2(uint16_t* row, int c4, const fl
 }
 
 // LayerNorm (+ ReLU) of row r, held as VPL float4 per lane by the TPR lanes that own it (C = 4 * TPR * VPL; a[] of a row that
-// is not `live` is zero), and its store.  Two-pass statistics by butterfly over the TPR lanes: EVERY lane of the wave calls this.
+// is not `live` is zero), and its store.  Two-pass statistics with a corrected mean, by butterfly over the TPR lanes: EVERY lane
+// of the wave calls this.
 // SPLIT: 0 = fp32 output, 1 = bf16 [hi|hi|lo] (K-concatenated, hipBLASLt route), 2 = bf16 split2 (gemm_x3 route)
 template <int TPR, int VPL, int SPLIT>
 __device__ __forceinline__ void hfl_ln_row(float* __restrict__ h_out, float4 (&a)[VPL], const float4 (&gm)[VPL],
@@ -50,21 +51,27 @@ __device__ __forceinline__ void hfl_ln_row(float* __restrict__ h_out, float4 (&a
 #pragma unroll
   for (int v = 0; v < VPL; ++v) sum += (a[v].x + a[v].y) + (a[v].z + a[v].w);
   const float mean = hfl_group_sum<TPR>(sum) * inv_c;
-  float sq = 0.f;
+  // `mean` carries the rounding of a sum of C values of the row's magnitude (2^-9 for a row around 2^14); the residuals do
+  // not (x - mean is exact for x near mean), so their own mean `dm` is what the first pass missed: it is taken off the
+  // variance and, folded into one fma, off every element.  A constant row comes out as beta whatever its sum rounded to.
+  float sq = 0.f, rs = 0.f;
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
     a[v].x -= mean; a[v].y -= mean; a[v].z -= mean; a[v].w -= mean;
+    rs += (a[v].x + a[v].y) + (a[v].z + a[v].w);
     sq += (a[v].x * a[v].x + a[v].y * a[v].y) + (a[v].z * a[v].z + a[v].w * a[v].w);
   }
-  const float rstd = 1.0f / sqrtf(hfl_group_sum<TPR>(sq) * inv_c + eps);
+  const float dm = hfl_group_sum<TPR>(rs) * inv_c;
+  const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, hfl_group_sum<TPR>(sq) * inv_c), 0.f) + eps);
+  const float dr = dm * rstd;
   if (live) {
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
       float4 o;
-      o.x = fmaf(a[v].x * rstd, gm[v].x, bt[v].x);
-      o.y = fmaf(a[v].y * rstd, gm[v].y, bt[v].y);
-      o.z = fmaf(a[v].z * rstd, gm[v].z, bt[v].z);
-      o.w = fmaf(a[v].w * rstd, gm[v].w, bt[v].w);
+      o.x = fmaf(fmaf(a[v].x, rstd, -dr), gm[v].x, bt[v].x);
+      o.y = fmaf(fmaf(a[v].y, rstd, -dr), gm[v].y, bt[v].y);
+      o.z = fmaf(fmaf(a[v].z, rstd, -dr), gm[v].z, bt[v].z);
+      o.w = fmaf(fmaf(a[v].w, rstd, -dr), gm[v].w, bt[v].w);
       if (relu) {                              // conv -> norm -> ReLU of the stem (octformer_layers.py:80-98) in one pass
         o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
       }

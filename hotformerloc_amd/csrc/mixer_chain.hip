@@ -160,15 +160,18 @@ mixer_chain_kernel(const MixerChainParams p) {
         sum += ((a[j][0].x + a[j][0].y) + (a[j][0].z + a[j][0].w)) + ((a[j][1].x + a[j][1].y) + (a[j][1].z + a[j][1].w));
       }
       const float mean = hfl_group_sum<LPR>(sum) * (1.0f / (float)MC);
-      float sq = 0.f;
+      float sq = 0.f, rs = 0.f;                 // rs: what the rounding of `sum` left in the residuals (csrc/ln_row.h)
 #pragma unroll
       for (int j = 0; j < NCH; ++j)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           a[j][h].x -= mean; a[j][h].y -= mean; a[j][h].z -= mean; a[j][h].w -= mean;
+          rs += (a[j][h].x + a[j][h].y) + (a[j][h].z + a[j][h].w);
           sq += (a[j][h].x * a[j][h].x + a[j][h].y * a[j][h].y) + (a[j][h].z * a[j][h].z + a[j][h].w * a[j][h].w);
         }
-      const float rstd = 1.0f / sqrtf(hfl_group_sum<LPR>(sq) * (1.0f / (float)MC) + p.eps);
+      const float dm = hfl_group_sum<LPR>(rs) * (1.0f / (float)MC);
+      const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, hfl_group_sum<LPR>(sq) * (1.0f / (float)MC)), 0.f) + p.eps);
+      const float dr = dm * rstd;
 #pragma unroll
       for (int j = 0; j < NCH; ++j) {
         const int ch = j * LPR + nl;
@@ -177,8 +180,8 @@ mixer_chain_kernel(const MixerChainParams p) {
         for (int h = 0; h < 2; ++h) {
           const float4 g = *reinterpret_cast<const float4*>(lp + ch * 8 + h * 4);
           const float4 b = *reinterpret_cast<const float4*>(lp + MC + ch * 8 + h * 4);
-          const f32x2 v01 = {fmaf(a[j][h].x * rstd, g.x, b.x), fmaf(a[j][h].y * rstd, g.y, b.y)};
-          const f32x2 v23 = {fmaf(a[j][h].z * rstd, g.z, b.z), fmaf(a[j][h].w * rstd, g.w, b.w)};
+          const f32x2 v01 = {fmaf(fmaf(a[j][h].x, rstd, -dr), g.x, b.x), fmaf(fmaf(a[j][h].y, rstd, -dr), g.y, b.y)};
+          const f32x2 v23 = {fmaf(fmaf(a[j][h].z, rstd, -dr), g.z, b.z), fmaf(fmaf(a[j][h].w, rstd, -dr), g.w, b.w)};
           x3_split_pair(v01, hi[2 * h], lo[2 * h]);
           x3_split_pair(v23, hi[2 * h + 1], lo[2 * h + 1]);
         }

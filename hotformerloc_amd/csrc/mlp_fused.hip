@@ -230,17 +230,22 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
       sum += __shfl_xor(sum, 16, 64);
       sum += __shfl_xor(sum, 32, 64);
       const float mean = sum * (1.0f / (float)C);
-      float sq = 0.f;
+      float sq = 0.f, rs = 0.f;                 // rs: what the rounding of `sum` left in the residuals (csrc/ln_row.h)
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           a[ks][h].x -= mean; a[ks][h].y -= mean; a[ks][h].z -= mean; a[ks][h].w -= mean;
+          rs += (a[ks][h].x + a[ks][h].y) + (a[ks][h].z + a[ks][h].w);
           sq += (a[ks][h].x * a[ks][h].x + a[ks][h].y * a[ks][h].y) + (a[ks][h].z * a[ks][h].z + a[ks][h].w * a[ks][h].w);
         }
+      rs += __shfl_xor(rs, 16, 64);
+      rs += __shfl_xor(rs, 32, 64);
       sq += __shfl_xor(sq, 16, 64);
       sq += __shfl_xor(sq, 32, 64);
-      const float rstd = 1.0f / sqrtf(sq * (1.0f / (float)C) + p.eps);
+      const float dm = rs * (1.0f / (float)C);
+      const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, sq * (1.0f / (float)C)), 0.f) + p.eps);
+      const float dr = dm * rstd;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         uint32_t hi[4], lo[4];
@@ -248,8 +253,8 @@ ln_mlp_fused_kernel(const MlpFusedParams p) {
         for (int h = 0; h < 2; ++h) {
           const float4 gm = *reinterpret_cast<const float4*>(gms + ks * 32 + fq * 8 + h * 4);
           const float4 bt = *reinterpret_cast<const float4*>(bts + ks * 32 + fq * 8 + h * 4);
-          const f32x2 v01 = {fmaf(a[ks][h].x * rstd, gm.x, bt.x), fmaf(a[ks][h].y * rstd, gm.y, bt.y)};
-          const f32x2 v23 = {fmaf(a[ks][h].z * rstd, gm.z, bt.z), fmaf(a[ks][h].w * rstd, gm.w, bt.w)};
+          const f32x2 v01 = {fmaf(fmaf(a[ks][h].x, rstd, -dr), gm.x, bt.x), fmaf(fmaf(a[ks][h].y, rstd, -dr), gm.y, bt.y)};
+          const f32x2 v23 = {fmaf(fmaf(a[ks][h].z, rstd, -dr), gm.z, bt.z), fmaf(fmaf(a[ks][h].w, rstd, -dr), gm.w, bt.w)};
           x3_split_pair(v01, hi[2 * h], lo[2 * h]);
           x3_split_pair(v23, hi[2 * h + 1], lo[2 * h + 1]);
         }

@@ -88,17 +88,22 @@ __device__ __forceinline__ void relay_ln_split(const float* xr, const float* gm,
   sum += __shfl_xor(sum, 16, 64);
   sum += __shfl_xor(sum, 32, 64);
   const float mean = sum * (1.0f / (float)RC);
-  float sq = 0.f;
+  float sq = 0.f, rs = 0.f;                 // rs: what the rounding of `sum` left in the residuals (csrc/ln_row.h)
 #pragma unroll
   for (int ks = 0; ks < RKS; ++ks)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       a[ks][h].x -= mean; a[ks][h].y -= mean; a[ks][h].z -= mean; a[ks][h].w -= mean;
+      rs += (a[ks][h].x + a[ks][h].y) + (a[ks][h].z + a[ks][h].w);
       sq += (a[ks][h].x * a[ks][h].x + a[ks][h].y * a[ks][h].y) + (a[ks][h].z * a[ks][h].z + a[ks][h].w * a[ks][h].w);
     }
+  rs += __shfl_xor(rs, 16, 64);
+  rs += __shfl_xor(rs, 32, 64);
   sq += __shfl_xor(sq, 16, 64);
   sq += __shfl_xor(sq, 32, 64);
-  const float rstd = 1.0f / sqrtf(sq * (1.0f / (float)RC) + eps);
+  const float dm = rs * (1.0f / (float)RC);
+  const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, sq * (1.0f / (float)RC)), 0.f) + eps);
+  const float dr = dm * rstd;
 #pragma unroll
   for (int ks = 0; ks < RKS; ++ks) {
     uint32_t hi[4], lo[4];
@@ -106,8 +111,8 @@ __device__ __forceinline__ void relay_ln_split(const float* xr, const float* gm,
     for (int h = 0; h < 2; ++h) {
       const float4 g = *reinterpret_cast<const float4*>(gm + ks * 32 + fq * 8 + h * 4);
       const float4 b = *reinterpret_cast<const float4*>(bt + ks * 32 + fq * 8 + h * 4);
-      const f32x2 v01 = {fmaf(a[ks][h].x * rstd, g.x, b.x), fmaf(a[ks][h].y * rstd, g.y, b.y)};
-      const f32x2 v23 = {fmaf(a[ks][h].z * rstd, g.z, b.z), fmaf(a[ks][h].w * rstd, g.w, b.w)};
+      const f32x2 v01 = {fmaf(fmaf(a[ks][h].x, rstd, -dr), g.x, b.x), fmaf(fmaf(a[ks][h].y, rstd, -dr), g.y, b.y)};
+      const f32x2 v23 = {fmaf(fmaf(a[ks][h].z, rstd, -dr), g.z, b.z), fmaf(fmaf(a[ks][h].w, rstd, -dr), g.w, b.w)};
       x3_split_pair(v01, hi[2 * h], lo[2 * h]);
       x3_split_pair(v23, hi[2 * h + 1], lo[2 * h + 1]);
     }

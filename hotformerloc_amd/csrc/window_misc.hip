@@ -363,17 +363,21 @@ layer_norm_bwd_kernel(float* __restrict__ dx, float* __restrict__ dg_part, float
       sum += (a[v].x + a[v].y) + (a[v].z + a[v].w);
     }
     const float mean = hfl_group_sum<TPR>(sum) * inv_c;
-    float sq = 0.f;
+    float sq = 0.f, rsum = 0.f;               // the statistics of the forward, corrected mean included (csrc/ln_row.h)
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
       a[v].x -= mean; a[v].y -= mean; a[v].z -= mean; a[v].w -= mean;
+      rsum += (a[v].x + a[v].y) + (a[v].z + a[v].w);
       sq += (a[v].x * a[v].x + a[v].y * a[v].y) + (a[v].z * a[v].z + a[v].w * a[v].w);
     }
-    const float rstd = 1.0f / sqrtf(hfl_group_sum<TPR>(sq) * inv_c + eps);
+    const float dm = hfl_group_sum<TPR>(rsum) * inv_c;
+    const float rstd = 1.0f / sqrtf(fmaxf(fmaf(-dm, dm, hfl_group_sum<TPR>(sq) * inv_c), 0.f) + eps);
+    const float dr = dm * rstd;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
-      a[v].x *= rstd; a[v].y *= rstd; a[v].z *= rstd; a[v].w *= rstd;             // xhat
+      a[v].x = fmaf(a[v].x, rstd, -dr); a[v].y = fmaf(a[v].y, rstd, -dr);         // xhat
+      a[v].z = fmaf(a[v].z, rstd, -dr); a[v].w = fmaf(a[v].w, rstd, -dr);
       ab[v].x += d[v].x; ab[v].y += d[v].y; ab[v].z += d[v].z; ab[v].w += d[v].w;
       ag[v].x = fmaf(d[v].x, a[v].x, ag[v].x); ag[v].y = fmaf(d[v].y, a[v].y, ag[v].y);
       ag[v].z = fmaf(d[v].z, a[v].z, ag[v].z); ag[v].w = fmaf(d[v].w, a[v].w, ag[v].w);

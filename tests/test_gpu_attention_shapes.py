@@ -27,48 +27,12 @@ from hotformerloc_amd.params import CONFIG_DIR, ModelParams
 from oracle import hotformer_ref
 from oracle.testing import oracle_octree, synthetic_state_dict
 
-from attention_cases import DEV, octrees, pack_qkv_f16, window_plans
+from attention_cases import (DEV, ODEPTH, SIZES, octrees, pack_qkv_f16, window_plans, clouds as _clouds,
+                             mask_pos as _mask_pos, oracle_plan as _oracle_plan, plan_args as _plan_args, plans as _plans,
+                             relay_ref as _relay_ref, sequence_table as _sequence_table, windows_ref as _windows_ref)
 
 HFL_EINVAL, HFL_ECAPACITY = -1, -2
 LOG2E = 1.4426950408889634
-ODEPTH = 7                                 # octree depth: attention at depths 5..2
-SIZES = (900, 25, 600)                     # the 25-point cloud lies inside one window, with both its boundaries, at every K
-_CACHE = {}
-
-
-def _clouds():
-    return [syn.unit_ball_cloud(2100, SIZES[0]), syn.unit_ball_cloud(2101, SIZES[1]), syn.forest_cloud(2102, SIZES[2])]
-
-
-def _oracle_plan(K, D):
-    """The oracle's plan alone (no GPU): every depth 5..2 is a relay-token depth, so that `hat_mask` exists at depth 5 too."""
-    key = ('oplan', K, D)
-    if key not in _CACHE:
-        if 'ref' not in _CACHE:
-            _CACHE['ref'] = oracle_octree(_clouds(), ODEPTH)
-        _CACHE[key] = hotformer_ref.WindowPlan(_CACHE['ref'], **_plan_args(K, D))
-    return _CACHE[key]
-
-
-def _plan_args(K, D):
-    return dict(patch_size=K, dilation=D, max_depth=ODEPTH - 2, start_depth=ODEPTH - 5, num_pyramid_levels=4,
-                num_octf_levels=0, adape_mode=None)
-
-
-def _plans(K, D):
-    key = ('plans', K, D)
-    if key not in _CACHE:
-        if 'dev' not in _CACHE:
-            _CACHE['ref'], _CACHE['dev'] = octrees(_clouds(), ODEPTH)
-        from hotformerloc_amd.plan import WindowPlan
-        _CACHE[key] = (_oracle_plan(K, D), WindowPlan(_CACHE['dev'], **_plan_args(K, D)))
-    return _CACHE[key]
-
-
-def _mask_pos(oplan, depth, G, dil):
-    if dil > 1:
-        return oplan.dilate_mask[depth], oplan.dilate_pos[depth]
-    return (oplan.hat_mask[depth] if G else oplan.patch_mask[depth]), oplan.rel_pos[depth]
 
 
 def _clamp_is_live(oplan, depth, G, dil, K):
@@ -76,25 +40,6 @@ def _clamp_is_live(oplan, depth, G, dil, K):
     bnd = int(0.8 * K * dil ** 0.5)
     mask, pos = _mask_pos(oplan, depth, 0, dil)          # (relay tokens carry no position)
     return bool(((pos.abs().amax(-1) > bnd) & (mask == 0)).any())
-
-
-def _windows_ref(oplan, qkv_tok, qkv_rt, table, depth, K, G, dil, H):
-    """The reference's materialised window attention in the dtype of its arguments (float64 here): (windows (W, K + G, C),
-    token rows (nt, C))."""
-    C = H * 16
-    xw = oplan.to_windows(qkv_tok, depth, dil > 1)
-    if G:
-        xw = torch.cat([qkv_rt.unsqueeze(1), xw], 1)
-    q, k, v = xw.reshape(-1, K + G, 3, H, 16).permute(2, 0, 3, 1, 4)
-    mask, pos = _mask_pos(oplan, depth, G, dil)
-    bias = mask.to(qkv_tok.dtype).unsqueeze(1)
-    if table is not None:
-        rpe = hotformer_ref.rpe_bias(table, pos, K, dil)
-        if G:
-            rpe = torch.nn.functional.pad(rpe, (G, 0, G, 0))
-        bias = bias + rpe
-    o = hotformer_ref._sdpa(q, k, v, bias, 0.25).transpose(1, 2).reshape(-1, K + G, C)
-    return o, oplan.from_windows(o[:, G:], depth, dil > 1)
 
 
 def _heads_per_wg(H):
@@ -406,34 +351,6 @@ def test_window_attention_rejects_what_it_has_no_kernel_for(what, over, fwd):
 
 # ------------------------------------------------------------------------------------------------------------ relay attention
 RELAY_LENGTHS = [1, 15, 16, 17, 63, 64, 65, 0, 250]           # the <= 64 fast path, the 16-row tile edges, an empty cloud
-
-
-def _sequence_table(lengths, n_rows, seed):
-    """Sequences over a seeded permutation of [0, n_rows): the rows that no sequence lists are orphans."""
-    perm = np.random.RandomState(seed).permutation(n_rows).astype(np.int32)
-    n = int(sum(lengths))
-    assert n < n_rows
-    seq_rows = perm[:n]
-    seq_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
-    orphans = np.sort(perm[n:]).astype(np.int32)
-    return seq_rows, seq_off, orphans
-
-
-def _relay_ref(qkv, seq_rows, seq_off, H):
-    """Per-cloud dense softmax attention in the dtype of qkv; rows of no sequence stay 0."""
-    C = H * 16
-    out = qkv.new_zeros((qkv.shape[0], C))
-    parts = []
-    for b in range(len(seq_off) - 1):
-        rows = torch.from_numpy(seq_rows[seq_off[b]:seq_off[b + 1]].astype(np.int64))
-        if rows.numel() == 0:
-            continue
-        q, k, v = qkv[rows].view(-1, 3, H, 16).permute(1, 2, 0, 3)
-        p = torch.softmax(torch.matmul(q, k.transpose(-2, -1)) * 0.25, dim=-1)
-        parts.append((rows, torch.matmul(p, v).transpose(0, 1).reshape(-1, C)))
-    for rows, o in parts:
-        out = out.index_put((rows,), o)
-    return out
 
 
 @pytest.mark.parametrize('lengths,n_rows', [(RELAY_LENGTHS, 600), ([611], 640)], ids=['ragged', 'one-of-611'])
