@@ -41,16 +41,18 @@ smoothap_rows_kernel(float* __restrict__ ap, float* __restrict__ dap_ds, const f
     s_m[z] = (uint8_t)((pos[(int64_t)q * B + z] ? 1 : 0) | (neg[(int64_t)q * B + z] ? 2 : 0));
   }
   __syncthreads();
+  // a slot counts iff its index lies in [0, B) and points at a positive; compared as int64, so that 2^32 + z is not z
+  auto slot = [&](int j) -> int {
+    const int64_t p = idx[(int64_t)q * P + j];
+    return (p >= 0 && p < (int64_t)B && (s_m[p] & 1)) ? (int)p : -1;
+  };
   int n_valid = 0;
-  for (int j = 0; j < P; ++j) {
-    const int pj = (int)idx[(int64_t)q * P + j];
-    if (pj >= 0 && pj < B && (s_m[pj] & 1)) ++n_valid;
-  }
+  for (int j = 0; j < P; ++j) n_valid += slot(j) >= 0;
   float ap_q = 0.f;
   const float inv_tau = 1.0f / tau;
   for (int j = 0; j < P; ++j) {
-    const int pj = (int)idx[(int64_t)q * P + j];
-    if (!(pj >= 0 && pj < B && (s_m[pj] & 1))) continue;      // fewer than P true positives: slot unused
+    const int pj = slot(j);
+    if (pj < 0) continue;                                      // fewer than P true positives: slot unused
     const float sp = s_row[pj];
     float sum_p = 0.f, sum_n = 0.f;
     for (int z = threadIdx.x; z < B; z += blockDim.x) {
@@ -64,16 +66,19 @@ smoothap_rows_kernel(float* __restrict__ ap, float* __restrict__ dap_ds, const f
     const float nn = block_sum(sum_n, s_red);
     const float rw = rp + nn;
     ap_q += rp / rw;
-    const float c_p = nn / (rw * rw) / (float)n_valid;       // d(r_j / n_valid) / d r_p
-    const float c_n = -rp / (rw * rw) / (float)n_valid;      // d(r_j / n_valid) / d N
+    // the two coefficients multiply every term of this slot: formed in double and rounded once, 1 / tau included
+    const double den = (double)rw * (double)rw * (double)n_valid * (double)tau;
+    const float c_p = (float)((double)nn / den);             // d(r_j / n_valid) / d r_p / tau
+    const float c_n = (float)(-(double)rp / den);            // d(r_j / n_valid) / d N / tau
     float to_pj = 0.f;
     for (int z = threadIdx.x; z < B; z += blockDim.x) {
       const float x = -(s_row[z] - sp) * inv_tau;
       if (x < -50.f || x > 50.f) continue;                    // clamped exponent: zero gradient
-      const float a = 1.0f / (1.0f + expf(x));
+      const float ex = expf(x);
+      const float a = 1.0f / (1.0f + ex);
       const uint8_t m = s_m[z];
       const float coef = (((m & 1) && z != pj) ? c_p : 0.f) + ((m & 2) ? c_n : 0.f);
-      const float gz = coef * a * (1.0f - a) * inv_tau;
+      const float gz = coef * (a * (a * ex));                  // 1 - a = a e^x: 1.0f - a is 0 from x = -17 down, e^x is not
       s_g[z] += gz;                                            // thread-private z: no race
       to_pj -= gz;
     }
@@ -95,7 +100,8 @@ smoothap_rows_kernel(float* __restrict__ ap, float* __restrict__ dap_ds, const f
 //     kl = sum_j q_j delta_j + c,   c = log(Zp / Zq) = log1p(sum_j (exp(a_j) - exp(b_j)) / Zq),
 //     p_j - q_j = q_j expm1(-(delta_j + c)),
 // and not from two log-sum-exps of about log D each.  Where the rows differ grossly (|delta| >= 1) the plain differences are
-// exact enough and cannot overflow.
+// exact enough and cannot overflow; where Zp is less than half of Zq the sum of the differences cancels, and Zp is the direct
+// sum of the exp(a_j).
 template <int K>
 __global__ void __launch_bounds__(256)
 kd_rows_kernel(float* __restrict__ kl, float* __restrict__ dkl, const float* __restrict__ Y, const float* __restrict__ Tt,
@@ -116,26 +122,31 @@ kd_rows_kernel(float* __restrict__ kl, float* __restrict__ dkl, const float* __r
   my = hfl_group_max<64>(my);
   mt = hfl_group_max<64>(mt);
   const float dm = mt - my;
-  float zq = 0.f, s_diff = 0.f, s_qd = 0.f;
+  float zq = 0.f, zp = 0.f, s_diff = 0.f, s_qd = 0.f;
   float eq[K], dl[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     const float a = (y[i] - my) * inv_t, b = (t[i] - mt) * inv_t;
     const float d = ((t[i] - y[i]) - dm) * inv_t;           // b - a, from the two small differences
-    const float e = expf(b);
+    const float e = expf(b), ea = expf(a);
     eq[i] = e;
     dl[i] = d;
     zq += e;
-    s_diff += fabsf(d) < 1.f ? e * expm1f(-d) : expf(a) - e;
+    zp += ea;
+    s_diff += fabsf(d) < 1.f ? e * expm1f(-d) : ea - e;
     s_qd += e * d;                                           // e == 0 (underflow) times a finite d: 0
   }
   zq = hfl_group_sum<64>(zq);
+  zp = hfl_group_sum<64>(zp);
   s_diff = hfl_group_sum<64>(s_diff);
   s_qd = hfl_group_sum<64>(s_qd);
   const float x = s_diff / zq;                               // Zp / Zq - 1  (> -1)
-  const float c = x > -0.5f ? log1pf(x) : logf(1.f + x);
+  // Zp < Zq / 2 (a peaked student against a flat teacher): Zq + s_diff is then what is left of a cancellation, with the
+  // rounding of sums of Zq's size in it (relative error about D 2^-24); the direct sum of the exp(a_j) has none
+  const bool direct = !(x > -0.5f);
+  const float c = direct ? logf(zp / zq) : log1pf(x);
   if (lane == 0) kl[row] = s_qd / zq + c;
-  const float inv_zq = 1.f / zq, inv_zp = 1.f / (zq + s_diff);
+  const float inv_zq = 1.f / zq, inv_zp = 1.f / (direct ? zp : zq + s_diff);
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     const float q = eq[i] * inv_zq;

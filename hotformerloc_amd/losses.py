@@ -17,19 +17,13 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import check
 from . import ops
 
 
 class _SmoothAPRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sim, pos_u8, neg_u8, idx, tau):
-        b = sim.shape[0]
-        ap = torch.empty(b, dtype=torch.float32, device=sim.device)
-        dap = torch.empty((b, b), dtype=torch.float32, device=sim.device)
-        check(_native.load().hfl_smoothap_rows(ap.data_ptr(), dap.data_ptr(), sim.data_ptr(), pos_u8.data_ptr(),
-                                               neg_u8.data_ptr(), idx.data_ptr(), b, idx.shape[1], float(tau),
-                                               ops._stream()), 'hfl_smoothap_rows')
+        ap, dap = ops.smoothap_rows(sim, pos_u8, neg_u8, idx, tau)
         ctx.save_for_backward(dap)
         return ap
 

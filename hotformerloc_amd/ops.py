@@ -1694,6 +1694,51 @@ def kd_rows(y: torch.Tensor, t: torch.Tensor, temperature: float):
     return kl, dkl
 
 
+def smoothap_rows(sim: torch.Tensor, pos_u8: torch.Tensor, neg_u8: torch.Tensor, idx: torch.Tensor, tau: float, out=None):
+    """Per query row q of the (B, B) similarity matrix: the smoothed AP over the selected positives idx[q, :] and its
+    derivative with respect to the row (`hfl_smoothap_rows`).  sim: (B, B) fp32, contiguous; pos_u8, neg_u8: (B, B) uint8
+    masks (non-zero = set), contiguous; idx: (B, P >= 1) int64, contiguous; a slot counts iff 0 <= idx < B and it points at a
+    positive, a row without such a slot gets AP 0 and a zero gradient row.  B <= 17066 (the row, its gradient and the masks sit
+    in LDS).  Nothing is converted or copied: an operand of another dtype, shape or layout is an error.  `out`: an
+    (ap (B,), dap_ds (B, B)) pair of contiguous fp32 tensors to write into.  Returns (ap (B,), dap_ds (B, B))."""
+    operands = (('sim', sim), ('pos_u8', pos_u8), ('neg_u8', neg_u8), ('idx', idx))
+    for name, t in operands[1:]:
+        if t.device != sim.device:
+            raise ValueError('smoothap_rows: %s on %s, sim on %s' % (name, t.device, sim.device))
+    _dev(sim, pos_u8, neg_u8, idx)
+    if sim.dtype != torch.float32:
+        raise TypeError('smoothap_rows: float32 sim expected, got %s' % sim.dtype)
+    if sim.dim() != 2 or sim.shape[0] != sim.shape[1] or sim.shape[0] < 1:
+        raise ValueError('smoothap_rows: a (B, B) similarity matrix with B >= 1 expected, got %s' % (tuple(sim.shape),))
+    b = sim.shape[0]
+    for name, t in operands[1:3]:
+        if t.dtype != torch.uint8:
+            raise TypeError('smoothap_rows: uint8 %s expected, got %s' % (name, t.dtype))
+        if tuple(t.shape) != (b, b):
+            raise ValueError('smoothap_rows: (%d, %d) %s expected, got %s' % (b, b, name, tuple(t.shape)))
+    if idx.dtype != torch.int64:
+        raise TypeError('smoothap_rows: int64 idx expected, got %s' % idx.dtype)
+    if idx.dim() != 2 or idx.shape[0] != b or idx.shape[1] < 1:
+        raise ValueError('smoothap_rows: (%d, P >= 1) idx expected, got %s' % (b, tuple(idx.shape)))
+    for name, t in operands:
+        if not t.is_contiguous():
+            raise ValueError('smoothap_rows: %s must be contiguous (strides %s)' % (name, tuple(t.stride())))
+    tau = float(tau)
+    if not tau > 0.0:
+        raise ValueError('smoothap_rows: tau > 0 expected, got %r' % (tau,))
+    if out is None:
+        ap = torch.empty(b, dtype=torch.float32, device=sim.device)
+        dap = torch.empty((b, b), dtype=torch.float32, device=sim.device)
+    else:
+        ap, dap = out
+        for name, t, shape in (('out[0]', ap, (b,)), ('out[1]', dap, (b, b))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != sim.device:
+                raise ValueError('smoothap_rows: %s must be a contiguous float32 %s tensor on %s' % (name, shape, sim.device))
+    check(_native.load().hfl_smoothap_rows(ap.data_ptr(), dap.data_ptr(), sim.data_ptr(), pos_u8.data_ptr(), neg_u8.data_ptr(),
+                                           idx.data_ptr(), b, idx.shape[1], tau, _stream()), 'hfl_smoothap_rows')
+    return ap, dap
+
+
 def pairwise_dist(emb: torch.Tensor):
     """dist[i, j] = ||emb[i] - emb[j]||, summed over the differences themselves (`hfl_pairwise_dist`).  emb: (B, D) fp32,
     any B >= 1 and D >= 1.  Returns (B, B) fp32: bitwise symmetric, exactly 0 on the diagonal and between equal rows."""
