@@ -207,13 +207,29 @@ __global__ void dwconv_fwd_scalar(float* __restrict__ out, const float* __restri
   }
 }
 
+// More than 64 KiB of dynamic LDS has to be granted to the kernel before the occupancy query and the launch may ask for it
+// (K = 27 passes 64 KiB from C = 608 on; the largest case this path takes, K = 27, C = 1024, int64, is 110 808 bytes of the
+// CU's 160 KiB).  Asked for on every such call, not behind the LDS-keyed occupancy cache below: the grant is per kernel and
+// device, the cache is neither.
+template <typename IdxT, int KFIX>
+static bool fwd_lds_granted(size_t lds) {
+  if (lds <= 64 * 1024) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_fwd_vec4<IdxT, KFIX>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) == hipSuccess)
+    return true;
+  (void)hipGetLastError();                          // refused: the caller takes the scalar kernel, the call does not fail
+  return false;
+}
+
 template <typename IdxT>
 static int launch_fwd(float* out, const float* data, const float* weight, const IdxT* neigh,
                       int64_t n_out, int64_t C, int K, hipStream_t s) {
   if (n_out == 0) return HFL_OK;
-  if (C % 4 == 0 && C <= 1024 && K <= kMaxTaps) {
-    RowGeom g = row_geom(C);
-    const size_t lds = (size_t)K * C * sizeof(float) + (size_t)g.rpb * K * sizeof(IdxT);
+  bool vec4 = C % 4 == 0 && C <= 1024 && K <= kMaxTaps;
+  RowGeom g = row_geom(vec4 ? C : 4);
+  const size_t lds = (size_t)K * C * sizeof(float) + (size_t)g.rpb * K * sizeof(IdxT);
+  if (vec4) vec4 = K == 27 ? fwd_lds_granted<IdxT, 27>(lds) : fwd_lds_granted<IdxT, 0>(lds);
+  if (vec4) {
     const int64_t need = hfl_cdiv(n_out, g.rpb);
     static int nb27 = 0, nb0 = 0;
     static size_t l27 = 0, l0 = 0;
@@ -389,8 +405,9 @@ static int launch_wgrad(float* out, const float* grad, const float* data, const 
   if (C % 4 == 0 && C <= 1024 && K <= kMaxTaps) {
     RowGeom g = row_geom(C);
     const int blocks = wgrad_blocks(n_rows, g.rpb);
+    // row tables | the row reduction's nine-tap block: (rpb - 1) * 9 * C * 4 <= 36 KiB for every C, below the 64 KiB that need a grant
     const size_t lds = (((size_t)g.rpb * K * sizeof(IdxT) + 15) & ~(size_t)15) +
-                       (size_t)(g.rpb - 1) * 9 * C * sizeof(float);          // row tables | the row reduction's nine-tap block
+                       (size_t)(g.rpb - 1) * 9 * C * sizeof(float);
     float* partial = static_cast<float*>(workspace);
     // nine gathers in flight per lane (six and three were measured and lost)
     dwconv_wgrad_partial<IdxT, 9><<<blocks, g.tpr * g.rpb, lds, s>>>(partial, grad, data, neigh, n_rows, (int)C, K, g.tpr, g.rpb);
@@ -481,15 +498,19 @@ __global__ void __launch_bounds__(256) cpe_fwd_kernel(float* __restrict__ out, f
         float4 v[B];
         int e[B];
 #pragma unroll
-        for (int j = 0; j < B; ++j) {                 // past the end: repeat the last live tap (same line, weight 0)
+        for (int j = 0; j < B; ++j) {                 // past the end: repeat the last live tap (same line, product dropped)
           e[j] = ty * K + min(k0 + j, n_live - 1);
           v[j] = reinterpret_cast<const float4*>(x + (int64_t)s_idx[e[j]] * C)[tx];
         }
 #pragma unroll
         for (int j = 0; j < B; ++j) {
-          float4 w = s_w[(int)s_tap[e[j]] * TPR + tx];
-          if (k0 + j >= n_live) w = make_float4(0.f, 0.f, 0.f, 0.f);
-          acc = hfl_fma4(w, v[j], acc);
+          // dropped by a select, not by a zero weight: 0 * inf of the repeated row would turn the row's own inf into a NaN
+          const float4 a = hfl_fma4(s_w[(int)s_tap[e[j]] * TPR + tx], v[j], acc);
+          const bool on = k0 + j < n_live;
+          acc.x = on ? a.x : acc.x;
+          acc.y = on ? a.y : acc.y;
+          acc.z = on ? a.z : acc.z;
+          acc.w = on ? a.w : acc.w;
         }
       }
     } else {
@@ -560,7 +581,7 @@ template <int TPR, int NORM>
 static int launch_slot_sum(float* out, const float* part, const int32_t* slot, const float* bias, const float* gamma,
                            const float* beta, int64_t n_out, int64_t channels, int K, float eps, int relu, hipStream_t s) {
   const RowGeom g = row_geom(channels);
-  const size_t lds = (size_t)g.rpb * K * sizeof(int32_t);
+  const size_t lds = (size_t)g.rpb * K * sizeof(int32_t);      // at most 16 x 32 x 4 B: no grant needed
   static int nb = 0;
   static size_t nb_lds = 0;
   const int per_cu = persistent_per_cu(reinterpret_cast<const void*>(slot_sum_kernel<TPR, NORM, 8>), g.tpr * g.rpb, lds, 8, &nb,

@@ -80,7 +80,10 @@ tap_wgrad_kernel(float* __restrict__ ws, const float* __restrict__ g, const floa
       for (int s = 0; s < 4; ++s) {
         const bool ok = p0 + 4 * s + q < end;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[s][i] = ok ? a[s][i] : 0.f;
+        for (int i = 0; i < 4; ++i) {                 // both operands: 0 * inf of a clamped pair is a NaN in the tile
+          a[s][i] = ok ? a[s][i] : 0.f;
+          b[s][i] = ok ? b[s][i] : 0.f;
+        }
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s)

@@ -46,7 +46,9 @@ const char* hfl_arch(void);
  *   replaces  Tensor dwconv_forward_backward(Tensor data, Tensor weight, Tensor neigh)
  *             libs/dwconv/csrc/dwconv.h:13, dwconv.cu:24-42,99-113, pybind.cpp:11
  *   data (n_in,C) ; weight (K,1,C) ; neigh (n_out,K) ; out (n_out,C).  Also used for
- *   the input gradient with the inverse table (libs/dwconv/dwconv/nn.py:36-38). */
+ *   the input gradient with the inverse table (libs/dwconv/dwconv/nn.py:36-38).
+ *   Unchecked precondition: with n_out > 0, `data` holds at least one row (n_in >= 1, not NULL).  The kernel reads row 0
+ *   for every dead tap and drops the value; the API has no n_in to check this against. */
 int hfl_dwconv_forward_backward(float* out, const float* data, const float* weight,
                                 const void* neigh, int idx64, int64_t n_out,
                                 int64_t channels, int kngh, hfl_stream_t stream);
@@ -72,7 +74,9 @@ int hfl_slot_sum_norm(float* out_f32, uint16_t* out_split2, const float* part, c
 /* gW[k,c] = sum_h [neigh[h,k] >= 0] data[neigh[h,k], c] * grad[h,c]
  *   replaces  Tensor dwconv_weight_backward(Tensor grad, Tensor data, Tensor neigh)
  *             libs/dwconv/csrc/dwconv.h:14, dwconv.cu:44-72,115-131, pybind.cpp:12
- *   out (K,1,C).  `workspace` must hold hfl_dwconv_weight_backward_workspace() bytes. */
+ *   out (K,1,C).  `workspace` must hold hfl_dwconv_weight_backward_workspace() bytes.
+ *   Unchecked precondition: with n_rows > 0, `data` holds at least one row (not NULL): row 0 is read for every dead tap
+ *   and dropped by a select; the API has no source row count to check this against. */
 int64_t hfl_dwconv_weight_backward_workspace(int64_t n_rows, int64_t channels, int kngh);
 int hfl_dwconv_weight_backward(float* out, const float* grad, const float* data,
                                const void* neigh, int idx64, int64_t n_rows,
