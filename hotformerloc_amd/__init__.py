@@ -32,6 +32,11 @@ Matching on fewer than all points: `iss_keypoints` (Intrinsic Shape Signatures: 
 suppression `iss_select`) keeps the few per cent of a cloud's points where the surface bends in all three directions;
 `global_registration` and `rerank_candidates` take `salient_radius=` and `non_max_radius=` and then match, verify and
 estimate the coarse pose on those rows only, while the ICP still refines on the full clouds.
+
+Training losses: `make_loss_fn(params)` builds what a training config's `loss =` names, `TruncatedSmoothAP` or the two
+batch-hard losses `BatchHardTripletLossWithMasks` / `BatchHardContrastiveLossWithMasks` (`batch_hard_mine` is their miner;
+`batch_hard_*_host` are the numpy twins); `should_expand_batch` and `expand_batch_size` turn their statistics into the
+reference's dynamic batch sizing.
 """
 
 import os as _os
@@ -77,5 +82,8 @@ from .spectral import (spectral_consistency, spectral_consistency_host, prune_co
                        prune_correspondences_host, rerank_candidates, rerank_candidates_host, SpectralResult, RerankResult)
 from .consensus import (consensus_hypotheses, consensus_hypotheses_host, consensus_registration,        # noqa: F401,E402
                         consensus_registration_host)
+from .losses import (BatchHardTripletLossWithMasks, BatchHardContrastiveLossWithMasks, batch_hard_mine,  # noqa: F401,E402
+                     batch_hard_mine_host, batch_hard_triplet_host, batch_hard_contrastive_host, make_loss_fn)
+from .training import expand_batch_size, should_expand_batch                                            # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -261,6 +261,14 @@ SIGNATURES = {
                                   c_float, c_void_p]),
     'hfl_pairwise_dist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'hfl_pairwise_dist_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'hfl_batch_hard_mine_workspace': (c_int64, [c_int]),
+    'hfl_batch_hard_mine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_void_p]),
+    'hfl_batch_hard_terms_workspace': (c_int64, [c_int]),
+    'hfl_batch_hard_terms': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p]),
+    'hfl_batch_hard_grad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_int, c_int, c_void_p]),
     'hfl_batch_masks': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p]),
     'hfl_radius_lists': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_double,

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBNAME = 'libhotformerloc_hip.so'
 ARCH = 'gfx950'
-SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'normals.hip', 'keypoints.hip', 'fpfh.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'mixer_chain.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'registration.hip', 'global_registration.hip', 'spectral.hip', 'consensus.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
+SOURCES = ['capi.hip', 'dwconv.hip', 'octree.hip', 'preprocess.hip', 'augment.hip', 'voxel.hip', 'ground.hip', 'outliers.hip', 'normals.hip', 'keypoints.hip', 'fpfh.hip', 'window_misc.hip', 'attention.hip', 'gemm_x3.hip', 'gemm_x6.hip', 'mlp_fused.hip', 'qkv_fused.hip', 'attn_fused.hip', 'attn_ws.hip', 'relay_block.hip', 'mixer_chain.hip', 'attn_pool.hip', 'wgrad_x3.hip', 'wgrad_f32.hip', 'tapconv.hip', 'gemm_lt.hip', 'loss.hip', 'pairwise.hip', 'batch_hard.hip', 'batch_masks.hip', 'radius.hip', 'overlap.hip', 'registration.hip', 'global_registration.hip', 'spectral.hip', 'consensus.hip', 'ema.hip', 'optim.hip', 'retrieval.hip']
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc',
          '-Wall', '-Wno-unused-function']
 # hipBLASLt for hfl_gemm_bf16 (the ROCm copy that matches the headers; rpath so the loader finds it)
@@ -57,7 +57,10 @@ EXTRA_FLAGS = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                'spectral.hip': ['-ffp-contract=off'],
                # consensus.hip: the same matrix entry, and float64 sums and a Kabsch solve that follow the numpy route
                # operation for operation
-               'consensus.hip': ['-ffp-contract=off']}
+               'consensus.hip': ['-ffp-contract=off'],
+               # batch_hard.hip: the distances carry the bits of hfl_pairwise_dist, and the terms and the gradient follow the
+               # numpy twins operation for operation
+               'batch_hard.hip': ['-ffp-contract=off']}
 
 
 def _hipcc() -> str:

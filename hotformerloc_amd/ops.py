@@ -1770,7 +1770,99 @@ def pairwise_dist_bwd(grad_dist: torch.Tensor, dist: torch.Tensor, emb: torch.Te
     return d_emb
 
 
-BATCH_MASKS_LDS_ENTRIES = 4096         # HFL_BATCH_MASKS_LDS_ENTRIES: entries of each list a workgroup stages in LDS
+BATCH_HARD_TRIPLET, BATCH_HARD_CONTRASTIVE = 0, 1          # the mode argument of hfl_batch_hard_terms / hfl_batch_hard_grad
+
+
+def _batch_hard_rows(who, emb):
+    _dev(emb)
+    if emb.dim() != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
+        raise ValueError('%s: a (B, D) matrix with B >= 1 and D >= 1 expected, got %s' % (who, tuple(emb.shape)))
+    return _f32c(emb)
+
+
+def _batch_hard_vectors(who, emb, vectors):
+    """(B,) contiguous vectors of the given dtypes on emb's device; nothing is converted."""
+    b = emb.shape[0]
+    for name, t, dtype in vectors:
+        if t.device != emb.device:
+            raise ValueError('%s: %s on %s, emb on %s' % (who, name, t.device, emb.device))
+        if t.dtype != dtype:
+            raise TypeError('%s: %s %s expected, got %s' % (who, dtype, name, t.dtype))
+        if tuple(t.shape) != (b,) or not t.is_contiguous():
+            raise ValueError('%s: a contiguous (%d,) %s expected, got %s' % (who, b, name, tuple(t.shape)))
+
+
+def batch_hard_mine(emb: torch.Tensor, pos_u8: torch.Tensor, neg_u8: torch.Tensor):
+    """Hardest positive and hardest negative of every row (`hfl_batch_hard_mine`): p[a] = the first arg-max of
+    `pairwise_dist(emb)[a]` over the columns with pos_u8[a] != 0, n[a] = the first arg-min over those with neg_u8[a] != 0, and
+    the two distances, bit for bit the entries of that matrix, which is never formed.  emb: (B, D) fp32, any B >= 1 and
+    D >= 1; pos_u8, neg_u8: (B, B) uint8, contiguous (an operand of another dtype, shape or layout is an error).
+    Returns (p (B,) int32, d_ap (B,) fp32, n (B,) int32, d_an (B,) fp32); index -1 and distance 0 where a row has none."""
+    emb = _batch_hard_rows('batch_hard_mine', emb)
+    b, d = emb.shape
+    for name, t in (('pos_u8', pos_u8), ('neg_u8', neg_u8)):
+        if t.device != emb.device:
+            raise ValueError('batch_hard_mine: %s on %s, emb on %s' % (name, t.device, emb.device))
+        if t.dtype != torch.uint8:
+            raise TypeError('batch_hard_mine: uint8 %s expected, got %s' % (name, t.dtype))
+        if tuple(t.shape) != (b, b):
+            raise ValueError('batch_hard_mine: (%d, %d) %s expected, got %s' % (b, b, name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('batch_hard_mine: %s must be contiguous (strides %s)' % (name, tuple(t.stride())))
+    lib = _native.load()
+    work = torch.empty(int(lib.hfl_batch_hard_mine_workspace(b)), dtype=torch.uint8, device=emb.device)
+    idx = torch.empty((2, b), dtype=torch.int32, device=emb.device)
+    dist = torch.empty((2, b), dtype=torch.float32, device=emb.device)
+    check(lib.hfl_batch_hard_mine(idx[0].data_ptr(), dist[0].data_ptr(), idx[1].data_ptr(), dist[1].data_ptr(), work.data_ptr(),
+                                  emb.data_ptr(), pos_u8.data_ptr(), neg_u8.data_ptr(), b, d, _stream()), 'hfl_batch_hard_mine')
+    return idx[0], dist[0], idx[1], dist[1]
+
+
+def batch_hard_terms(emb: torch.Tensor, p: torch.Tensor, d_ap: torch.Tensor, n: torch.Tensor, d_an: torch.Tensor, mode: int,
+                     margin0: float, margin1: float = 0.0):
+    """Loss terms of mined triples, one entry point for both losses (`hfl_batch_hard_terms`).  emb: (B, D) fp32; p, n: (B,) int32 and d_ap, d_an:
+    (B,) fp32 as `batch_hard_mine` returns them.  mode BATCH_HARD_TRIPLET: margin0 is the margin; BATCH_HARD_CONTRASTIVE:
+    margin0, margin1 are pos_margin, neg_margin.  Returns (stats (16,) float64, scale (4,) fp32, d_pn (B,) fp32,
+    flags (B,) int32) on the device, laid out as include/hotformerloc_hip.h says; scale[2] is the loss."""
+    emb = _batch_hard_rows('batch_hard_terms', emb)
+    _batch_hard_vectors('batch_hard_terms', emb, (('p', p, torch.int32), ('d_ap', d_ap, torch.float32),
+                                                  ('n', n, torch.int32), ('d_an', d_an, torch.float32)))
+    if mode not in (BATCH_HARD_TRIPLET, BATCH_HARD_CONTRASTIVE):
+        raise ValueError('batch_hard_terms: mode 0 (triplet) or 1 (contrastive) expected, got %r' % (mode,))
+    b, d = emb.shape
+    stats = torch.empty(16, dtype=torch.float64, device=emb.device)
+    scale = torch.empty(4, dtype=torch.float32, device=emb.device)
+    d_pn = torch.empty(b, dtype=torch.float32, device=emb.device)
+    flags = torch.empty(b, dtype=torch.int32, device=emb.device)
+    lib = _native.load()
+    work = torch.empty(int(lib.hfl_batch_hard_terms_workspace(b)) // 8, dtype=torch.float64, device=emb.device)
+    check(lib.hfl_batch_hard_terms(stats.data_ptr(), scale.data_ptr(), d_pn.data_ptr(), flags.data_ptr(), work.data_ptr(),
+                                   emb.data_ptr(), p.data_ptr(), d_ap.data_ptr(), n.data_ptr(), d_an.data_ptr(), b, d,
+                                   int(mode), float(margin0), float(margin1), _stream()), 'hfl_batch_hard_terms')
+    return stats, scale, d_pn, flags
+
+
+def batch_hard_grad(emb: torch.Tensor, p: torch.Tensor, n: torch.Tensor, d_ap: torch.Tensor, d_an: torch.Tensor,
+                    d_pn: torch.Tensor, flags: torch.Tensor, scale: torch.Tensor, mode: int):
+    """Gradient of the loss of `batch_hard_terms` (same mode) with respect to emb for unit upstream gradient
+    (`hfl_batch_hard_grad`), from what `batch_hard_mine` and `batch_hard_terms` returned.  Returns (B, D) fp32."""
+    emb = _batch_hard_rows('batch_hard_grad', emb)
+    _batch_hard_vectors('batch_hard_grad', emb, (('p', p, torch.int32), ('n', n, torch.int32), ('d_ap', d_ap, torch.float32),
+                                                 ('d_an', d_an, torch.float32), ('d_pn', d_pn, torch.float32),
+                                                 ('flags', flags, torch.int32)))
+    if scale.device != emb.device or scale.dtype != torch.float32 or tuple(scale.shape) != (4,) or not scale.is_contiguous():
+        raise ValueError('batch_hard_grad: scale must be the contiguous (4,) float32 vector of batch_hard_terms')
+    if mode not in (BATCH_HARD_TRIPLET, BATCH_HARD_CONTRASTIVE):
+        raise ValueError('batch_hard_grad: mode 0 (triplet) or 1 (contrastive) expected, got %r' % (mode,))
+    b, d = emb.shape
+    d_emb = torch.empty((b, d), dtype=torch.float32, device=emb.device)
+    check(_native.load().hfl_batch_hard_grad(d_emb.data_ptr(), emb.data_ptr(), p.data_ptr(), n.data_ptr(), d_ap.data_ptr(),
+                                             d_an.data_ptr(), d_pn.data_ptr(), flags.data_ptr(), scale.data_ptr(), b, d, int(mode),
+                                             _stream()), 'hfl_batch_hard_grad')
+    return d_emb
+
+
+BATCH_MASKS_LDS_ENTRIES = 4096        # HFL_BATCH_MASKS_LDS_ENTRIES: entries of each list a workgroup stages in LDS
 
 
 def batch_masks(labels: torch.Tensor, pos_off: torch.Tensor, pos_idx: torch.Tensor, nn_off: torch.Tensor, nn_idx: torch.Tensor,

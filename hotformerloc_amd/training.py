@@ -22,6 +22,30 @@ import torch.distributed as dist
 from .distributed import all_gather_descriptors
 
 
+def expand_batch_size(batch_size: int, rate: float, limit: int) -> int:
+    """The arithmetic of the reference's `BatchSampler.expand_batch` (`datasets/samplers.py:79-90`): the next batch size,
+    `min(int(batch_size * rate), limit)`, or `batch_size` itself once it has reached `limit`."""
+    if not rate > 1.0:
+        raise ValueError('batch_expansion_rate must be greater than 1, got %r' % (rate,))
+    if batch_size >= limit:
+        return batch_size
+    return min(int(batch_size * rate), limit)
+
+
+def should_expand_batch(stats: dict, threshold: Optional[float]) -> bool:
+    """The rule of the reference's dynamic batch sizing (`training/trainer.py:506-512`): expand when the share of non-zero
+    triplets, `stats['num_non_zero_triplets'] / stats['num_triplets']` of the last epoch's training statistics, falls below
+    `batch_expansion_th`.  Only the batch-hard triplet loss reports the two counts; other statistics are a KeyError, as in
+    the reference.  `threshold=None` (dynamic sizing off) and an epoch without a triplet never expand."""
+    if threshold is None:
+        return False
+    if not 0.0 < threshold < 1.0:
+        raise ValueError('batch_expansion_th must be between 0 and 1, got %r' % (threshold,))
+    if stats['num_triplets'] == 0:
+        return False
+    return stats['num_non_zero_triplets'] / stats['num_triplets'] < threshold
+
+
 def _stage1_numerics(model, phase):
     """Stage 1 must reproduce what stage 3 recomputes (see hotformerloc_amd.model.training_numerics); models
     that are not this package's encoder (tests) need nothing."""

@@ -1193,6 +1193,46 @@ int hfl_pairwise_dist_bwd(float* d_emb, const float* grad_dist, const float* dis
                           hfl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * 11b'. Batch-hard triplet and contrastive losses (models/losses/loss.py:27-135 with pytorch-metric-learning's
+ *       LpDistance(p = 2, power = 1), TripletMarginLoss(swap = True), ContrastiveLoss and AvgNonZeroReducer).  Every distance
+ *       below carries the bits hfl_pairwise_dist writes for that entry.  Any B >= 1 and D >= 1, else HFL_EINVAL.  No float
+ *       atomics; every output element has one writer and a fixed summation order (two launches agree bitwise).
+ * ---------------------------------------------------------------------- */
+/* Bytes of workspace hfl_batch_hard_mine needs for a batch (the partial results of its column splits). */
+int64_t hfl_batch_hard_mine_workspace(int batch);
+
+/* Per row a: p[a] the column with the largest dist[a, j] among pos_mask[a, j] != 0 and d_ap[a] that distance, n[a] the column
+ * with the smallest dist[a, j] among neg_mask[a, j] != 0 and d_an[a]; the lowest column wins a tie; index -1 and distance 0
+ * where the row has none.  The (B, B) matrix is never written: two launches, the second combines the column splits in
+ * ascending order.  emb (B,D) f32, masks (B,B) u8 row-major, p and n (B,) i32, d_ap and d_an (B,) f32. */
+int hfl_batch_hard_mine(int* p, float* d_ap, int* n, float* d_an, void* workspace, const float* emb, const uint8_t* pos_mask,
+                        const uint8_t* neg_mask, int batch, int dim, hfl_stream_t stream);
+
+/* Bytes of workspace hfl_batch_hard_terms needs for a batch (one set of partial sums per 64 rows; 8-byte aligned). */
+int64_t hfl_batch_hard_terms_workspace(int batch);
+
+/* Loss terms of the mined triples; one entry point for both losses, selected by `mode`.  Two launches: a workgroup per 64
+ * rows, then one wave that adds the workgroups' partial sums in a fixed order.  A row is kept iff 0 <= p[a] < B and
+ * 0 <= n[a] < B; the terms are float64 expressions of the f32 distances.
+ *   mode 0 (triplet): d_pn[a] = dist[p[a], n[a]]; v = d_ap - min(d_an, d_pn) + margin0 (d_pn is taken iff d_pn < d_an);
+ *     flags[a] = 1 kept | 2 v > 0 | 4 v > 0 and d_pn taken; loss = mean of the v > 0.
+ *   mode 1 (contrastive): flags[a] = 1 kept | 2 d_ap - margin0 > 0 | 4 margin1 - d_an > 0; d_pn = 0;
+ *     loss = mean of the positive d_ap - margin0 + mean of the positive margin1 - d_an.
+ * stats (16,) f64: 0 kept rows, 1 and 2 the counts of flag 2 and flag 4, 3 and 4 the sums of the two term sets, 5-7 mean, max,
+ * min of the kept d_ap, 8-10 of the kept d_an (NaN without a kept row), 11 the mean row norm, 12 loss, 13 and 14 the two
+ * means of mode 1, 15 zero.  scale (4,) f32: 1 / count of each term set (0 for an empty set), the loss, zero. */
+int hfl_batch_hard_terms(double* stats, float* scale, float* d_pn, int* flags, void* workspace, const float* emb, const int* p,
+                         const float* d_ap, const int* n, const float* d_an, int batch, int dim, int mode, double margin0,
+                         double margin1, hfl_stream_t stream);
+
+/* d_emb (B,D) f32: the gradient of the loss of hfl_batch_hard_terms (same mode) for unit upstream gradient, from what mine and
+ * terms wrote.  A pair at distance 0 contributes nothing.  Row i sums, anchors ascending, w (emb[i] - emb[other]) with
+ * w = +-scale / distance by fmaf. */
+int hfl_batch_hard_grad(float* d_emb, const float* emb, const int* p, const int* n, const float* d_ap, const float* d_an,
+                        const float* d_pn, const int* flags, const float* scale, int batch, int dim, int mode,
+                        hfl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * 11c. The batch's positives / negatives masks (datasets/dataset_utils.py:118-123, the collate function's two nested list
  *      comprehensions over in_sorted_array, :201-206; the lists are TrainingTuple.positives / .non_negatives,
  *      datasets/base_datasets.py:11-28)
